@@ -10,7 +10,15 @@ graph; every frame carries its own can_bus AND its own calibration matrices (fre
 local cameras; ONE RCCL all-reduce of the masked camera sums per encoder layer, captured into the graph;
 `--exchange gather`: BASELINE config 4's per-camera all-gathers, eager) -- strong scaling: the job is still one frame.
 
-Sub-records of the same JSON line (N = 1):
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: it builds the model, warms up, times
+the K frames and prints the line (`value`, `ms_per_step`, `dtype`, ...); the sub-records below are null there.
+`--full` measures them too, in the same line (each is still dropped by its --no-* option).  `--dump-outputs DIR` writes
+what the timed path handed its caller in the last timed step as DIR/<name>.npy in float32 (end to end: the class
+scores and box coordinates of all six decoder layers; --no-end-to-end: the last output of each sampling operator,
+as a fixed seeded sample where an output is larger than its share of 60 MB); the inputs are seeded, so the same
+arguments give the same inputs on every run and every build.
+
+Sub-records of the same JSON line (N = 1, --full):
   protocol_sync : the reference's own FPS protocol for the same frames (one frame between two stream syncs, first and
                  last dropped, 1000 / mean ms; det2trt/utils/tensorrt.py:72-76) -- also inside every other
                  end-to-end record below;
@@ -67,6 +75,28 @@ BASE = dict(
 )
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 MFMA_F16_PEAK_TFLOPS = 2500.0  # dense fp16 / bf16 MFMA peak (the task statement's figure; no sparsity)
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # --dump-outputs: values of all files together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor, None skipped) as directory/<name>.npy in float32.  A
+    tensor with more elements than its equal share of `budget` is written as a fixed sample of that many elements:
+    flat indices drawn by a generator seeded with 0, in ascending order -- the same elements on every run and every
+    build for the same shape.  Returns {name: (shape written, elements of the full tensor)}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = budget // 4 // max(1, len(arrays))
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > share:
+            idx = torch.randint(0, t.numel(), (share,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written[name] = (list(a.shape), int(arrays[name].numel()))
+    return written
 
 
 def msda_inputs(cfg, dtype, device, gen, cams=None):
@@ -227,7 +257,8 @@ def build_workload(bev, kind, dev, my_cams):
 
 def run_hot_path(wl, steps, warmup, dev, dist, exchange, world):
     """W untimed + K timed frames of the hot path, barrier + synchronize on both sides, MAX over
-    ranks.  Returns (elapsed seconds, [HIP-event pairs around every base SCA call])."""
+    ranks.  Returns (elapsed seconds, [HIP-event pairs around every base SCA call], {name: the last output of each
+    operator in the last timed frame})."""
     op_msda, op_dcn, op_rot = wl["ops"]
     nq, embed = BASE["sca"]["nq"], BASE["embed"]
     sca, tsa, dec, rot, dcn, sca_bs = wl["sca"], wl["tsa"], wl["dec"], wl["rot"], wl["dcn"], wl["sca_bs"]
@@ -243,13 +274,17 @@ def run_hot_path(wl, steps, warmup, dev, dist, exchange, world):
         a = sca if i is None else tuple(t[i:i + 1] if k in (0, 2, 3, 4) else t for k, t in enumerate(sca))
         return op_msda(*a)
 
-    def step(record):
-        for count, a in dcn:
+    def step(record, keep=None):
+        def kept(name, t):    # (the last timed frame only: every other frame drops its outputs as they come)
+            if keep is not None:
+                keep[name] = t
+
+        for (count, a), stage in zip(dcn, ("dcn_stage3", "dcn_stage4")):
             for _ in range(count):
-                op_dcn(*a)
-        op_rot(*rot)
+                kept(stage, op_dcn(*a))
+        kept("rotate", op_rot(*rot))
         for _ in range(BASE["enc_layers"]):
-            op_msda(*tsa)
+            kept("tsa_msda", op_msda(*tsa))
             if record and sca_bs:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -258,6 +293,7 @@ def run_hot_path(wl, steps, warmup, dev, dist, exchange, world):
                 ex.gather(lambda i: sca_call(i).view(1, nq, embed), (nq, embed), out_dtype, dev)
             else:
                 out = sca_call() if sca_bs else empty
+                kept("sca_msda", out)
                 if ex is not None:   # (int8: partial sums in int32 on every rank, whatever its camera count)
                     acc_dt = torch.int32 if wl["int8"] else out.dtype
                     part = out.view(out.shape[0], nq, embed).sum(0, keepdim=True, dtype=acc_dt) if out.shape[0] else \
@@ -267,7 +303,7 @@ def run_hot_path(wl, steps, warmup, dev, dist, exchange, world):
                 e1.record()
                 sca_events.append((e0, e1))
         for _ in range(BASE["dec_layers"]):
-            op_msda(*dec)
+            kept("dec_msda", op_msda(*dec))
 
     def fence():
         torch.cuda.synchronize()
@@ -279,15 +315,16 @@ def run_hot_path(wl, steps, warmup, dev, dist, exchange, world):
         step(False)
     fence()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        step(True)
+    last = {}
+    for i in range(steps):
+        step(True, last if i == steps - 1 else None)
     fence()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    return elapsed, sca_events
+    return elapsed, sca_events, last
 
 
 def pmc_traffic(int8):
@@ -607,7 +644,8 @@ class ModelFrames:
 
 
 def run_frames(frames, steps, warmup, dev, dist):
-    """W untimed + K timed model frames, barrier + synchronize on both sides, MAX over ranks."""
+    """W untimed + K timed model frames, barrier + synchronize on both sides, MAX over ranks.  Returns (elapsed
+    seconds, what the last timed frame's `step` returned)."""
     def fence():
         torch.cuda.synchronize()
         if dist is not None:
@@ -618,15 +656,16 @@ def run_frames(frames, steps, warmup, dev, dist):
         frames.step()
     fence()
     t0 = time.perf_counter()
+    out = None
     for _ in range(steps):
-        frames.step()
+        out = frames.step()
     fence()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    return elapsed
+    return elapsed, out
 
 
 def run_frames_protocol(frames, steps):
@@ -668,7 +707,7 @@ def bevdet_frames(dev, steps, warmup, int8=True):
         class _F:
             step = staticmethod(graph.replay)
 
-        el = run_frames(_F, steps, warmup, dev, None)
+        el, _ = run_frames(_F, steps, warmup, dev, None)
         return {"value": round(steps / el, 3), "unit": "frames/s", "ms_per_step": round(el / steps * 1e3, 4),
                 "hip_graph": True, "protocol_sync": run_frames_protocol(_F, steps)}
 
@@ -743,6 +782,12 @@ def main():
     ap.add_argument("--sharded-path", action="store_true",
                     help="run the N > 1 code path (process group, camera / query sharding, collectives inside the frame's "
                          "HIP graph) even with ONE rank: what the GPU test of this file's multi-GPU path uses on a 1-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the sub-records (INT8 engine, tiny / small / BEVDet, hot path, rooflines, "
+                         "reference FPS protocol, CPU baselines); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32, 64 MB at most)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true",
                     help="profiling runs: time the sampling hot path only (the line's value is then the hot-path rate)")
@@ -781,20 +826,27 @@ def main():
     headline = None
     if not args.no_end_to_end:
         frames = ModelFrames(dev, args.dtype, world, rank, dist, args.exchange)
-        elapsed = run_frames(frames, args.steps, args.warmup, dev, dist)
+        elapsed, (cls, crd) = run_frames(frames, args.steps, args.warmup, dev, dist)
+        if args.dump_outputs and rank == 0:   # (before anything else replays the frame's graph into these buffers)
+            dump_outputs(args.dump_outputs, {"cls_scores": cls, "bbox_preds": crd})
+        del cls, crd
         headline = {"elapsed": elapsed, "hip_graph": frames.graph, "note": frames.note, "protocol_sync": None}
-        if not sharded:
+        if args.full and not sharded:
             headline["protocol_sync"] = run_frames_protocol(frames, args.steps)
         del frames
         torch.cuda.empty_cache()
 
-    # ---- sub-records (N = 1 and the hot-path step; at N > 1 the hot path is measured when asked to stand alone)
+    # ---- sub-records (--full: N = 1 and the hot-path step; at N > 1 the hot path is measured when asked to stand
+    # alone) -- with --no-end-to-end the hot path is the headline and runs in a plain run too
     my_cams = camera_shards(BASE["sca"]["bs"], world)[rank]
     hot = roofline = None
-    if not args.no_hot_path and (not sharded or args.no_end_to_end):
+    if not args.no_hot_path and (not sharded or args.no_end_to_end) and (args.full or headline is None):
         kind = "int8" if args.dtype == "int8" else "fp16"
         wl = build_workload(bev, kind, dev, my_cams)
-        el, sca_events = run_hot_path(wl, args.steps, args.warmup, dev, dist, args.exchange, world)
+        el, sca_events, last = run_hot_path(wl, args.steps, args.warmup, dev, dist, args.exchange, world)
+        if args.dump_outputs and rank == 0 and headline is None:
+            dump_outputs(args.dump_outputs, last)
+        del last
         roofline = sca_roofline(wl, sca_events)
         hot = {"what": "one frame's pass over the sampling operators only: 26x DCNv2 + rotate + 6x(TSA + SCA) MSDA "
                        "+ 6x decoder MSDA, op-test inputs (uniform-random reference points)",
@@ -803,7 +855,7 @@ def main():
         if roofline is not None and sharded:
             roofline["note"] = ("N>1: rank 0's cameras only (bytes_per_launch counts them); the bracket spans the "
                                 "per-camera sampler calls of one encoder layer and the wait for its exchange")
-        if roofline is not None and not sharded and kind == "fp16" and not args.no_geometry_extra:
+        if roofline is not None and not sharded and kind == "fp16" and not args.no_geometry_extra and args.full:
             try:
                 roofline.update(geometry_rooflines(bev, wl, dev))
             except Exception as exc:  # the contract line must still be printed
@@ -812,12 +864,12 @@ def main():
 
     # the other precision, measured in the SAME default run (the metric is "fp16/INT8")
     other = None
-    if not sharded and not args.no_int8 and args.dtype == "fp16":
+    if args.full and not sharded and not args.no_int8 and args.dtype == "fp16":
         other = {"dtype": "i8"}
         if not args.no_hot_path:
             try:
                 wl8 = build_workload(bev, "int8", dev, my_cams)
-                el8, ev8 = run_hot_path(wl8, args.steps, args.warmup, dev, None, args.exchange, 1)
+                el8, ev8, _ = run_hot_path(wl8, args.steps, args.warmup, dev, None, args.exchange, 1)
                 other["hot_path"] = {"value": round(args.steps / el8, 3), "unit": "frames/s",
                                      "ms_per_step": round(el8 / args.steps * 1e3, 4),
                                      "scales": "entropy (KL) calibrator per plugin-boundary tensor; fp16 reference points "
@@ -829,7 +881,7 @@ def main():
         if not args.no_end_to_end:
             try:
                 f8 = ModelFrames(dev, "int8", 1, 0, None, args.exchange)
-                e8 = run_frames(f8, args.steps, args.warmup, dev, None)
+                e8, _ = run_frames(f8, args.steps, args.warmup, dev, None)
                 other["end_to_end"] = {"value": round(args.steps / e8, 3), "unit": "frames/s",
                                        "ms_per_step": round(e8 / args.steps * 1e3, 4), "hip_graph": f8.graph,
                                        "build": f8.note, "protocol_sync": run_frames_protocol(f8, args.steps)}
@@ -843,7 +895,7 @@ def main():
                 if not args.int8_sca_plugin:
                     raise StopIteration
                 f8 = ModelFrames(dev, "int8", 1, 0, None, args.exchange, sca_int8=True)
-                e8 = run_frames(f8, args.steps, args.warmup, dev, None)
+                e8, _ = run_frames(f8, args.steps, args.warmup, dev, None)
                 other["end_to_end_sca_on_int8_plugin"] = {"value": round(args.steps / e8, 3), "unit": "frames/s",
                                                           "ms_per_step": round(e8 / args.steps * 1e3, 4),
                                                           "hip_graph": f8.graph, "build": f8.note}
@@ -856,7 +908,7 @@ def main():
 
     # BASELINE config 3: BEVFormer-small fp16 / INT8 end to end (same protocol pair)
     small = tiny = None
-    if not sharded and not args.no_end_to_end and not args.no_small:
+    if args.full and not sharded and not args.no_end_to_end and not args.no_small:
         small = {"config": "BEVFormer-small: 6x(3x736x1280) -> ResNet-101-DCN (C5) + FPN level -> 3 encoder layers "
                            "(150x150 BEV queries) -> 6 decoder layers -> heads"}
         tiny = {"config": "BEVFormer-tiny (BASELINE config 2): 6x(3x480x800) -> ResNet-50 (C5) + FPN level -> 3 encoder "
@@ -865,7 +917,7 @@ def main():
             for kind in ("fp16",) + (() if args.no_int8 else ("int8",)):
                 try:
                     fs = ModelFrames(dev, kind, 1, 0, None, args.exchange, name=name)
-                    es = run_frames(fs, args.steps, args.warmup, dev, None)
+                    es, _ = run_frames(fs, args.steps, args.warmup, dev, None)
                     rec[kind] = {"value": round(args.steps / es, 3), "unit": "frames/s",
                                  "ms_per_step": round(es / args.steps * 1e3, 4), "hip_graph": fs.graph, "build": fs.note,
                                  "protocol_sync": run_frames_protocol(fs, args.steps)}
@@ -875,12 +927,12 @@ def main():
                     rec[kind] = {"error": repr(exc)[:300]}
 
     frame_roof = {}
-    if not sharded and not args.no_hot_path:
+    if args.full and not sharded and not args.no_hot_path:
         frame_roof = frame_rooflines(bev, dev)
         torch.cuda.empty_cache()
 
     bevdet = None
-    if not sharded and not args.no_end_to_end and not args.no_small:
+    if args.full and not sharded and not args.no_end_to_end and not args.no_small:
         try:
             bevdet = bevdet_frames(dev, args.steps, args.warmup, not args.no_int8)
         except Exception as exc:
@@ -888,7 +940,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if not sharded and not args.no_cpu_baseline:
+        if args.full and not sharded and not args.no_cpu_baseline:
             v, sample = cpu_baseline()
             cpu = {"value": round(v, 5), "unit": "frames/s", "cores": torch.get_num_threads(),
                    "kind": "port",

@@ -18,10 +18,14 @@ reference's own torch statement of it (make_golden.load_reference_msda).  Dense 
 torch.nn.Linear with seeded weights, which travel in the fixture.
 Also written here: the base-size (200x200 BEV, 928x1600 images) geometry golden as SHA-256 digests
 of the arrays' bytes plus a strided sample (the arrays themselves are 11 MB).
+decoder_loop.npz (the decoder loop's keys) and bevdet_geometry.npz are checked bit for bit, so they are
+recorded in a child interpreter under tests/conftest.py's PINNED_CPU_ENV, the CPU kernel choice their
+tests run with (`... make_wrapper_golden.py bevdet` re-records just these two).
 """
 import ast
 import hashlib
 import os
+import subprocess
 import sys
 import textwrap
 
@@ -90,7 +94,8 @@ def params(prefix, **mods):
     return out
 
 
-def make_wrappers():
+def make_wrappers(pinned=False):
+    """wrappers.npz; `pinned` (the child run under conftest.PINNED_CPU_ENV): decoder_loop.npz, the loop's keys only."""
     msda_fn = MG.load_reference_msda()._MultiScaleDeformableAttnFunction.apply
     g = torch.Generator().manual_seed(0)
     res = {}
@@ -202,6 +207,9 @@ def make_wrappers():
                     "loop.inter": inter.numpy(), "loop.inter_ref": inter_ref.numpy(),
                     "loop.layer_ref_in": torch.stack([l.seen[0] for l in layers]).numpy()})
         print("decoder loop", tuple(inter_ref.shape))
+    if pinned:
+        np.savez_compressed(os.path.join(HERE, "decoder_loop.npz"), **{k: v for k, v in res.items() if k.startswith("loop.")})
+        return
     np.savez_compressed(os.path.join(HERE, "wrappers.npz"), **res)
 
 
@@ -292,11 +300,23 @@ def make_bevdet_geometry():
     print("bevdet geometry: points", int(res["ranks_bev_len"]), "intervals", int(res["interval_starts_len"]), "D", me.D)
 
 
+def make_pinned():
+    """The fixtures of the bit-exact CPU tests that run under conftest.PINNED_CPU_ENV, recorded in a child interpreter
+    under the same settings (they must be in place before torch and MKL load)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from conftest import PINNED_CPU_ENV
+    subprocess.check_call([sys.executable, os.path.abspath(__file__), "pinned"], env=dict(os.environ, **PINNED_CPU_ENV))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "pinned":
+        make_wrappers(pinned=True)
+        make_bevdet_geometry()
+        raise SystemExit(0)
     torch.set_num_threads(4)
     if len(sys.argv) > 1 and sys.argv[1] == "bevdet":
-        make_bevdet_geometry()
+        make_pinned()
         raise SystemExit(0)
     make_wrappers()
     make_geometry_base()
-    make_bevdet_geometry()
+    make_pinned()

@@ -42,3 +42,35 @@ def test_camera_partition_for_every_gpu_count():
         sh = camera_shards(6, world)
         assert sorted(c for r in sh for c in r) == list(range(6))
         assert max(len(r) for r in sh) == -(-6 // world)
+
+
+def test_dump_outputs_whole_small_sampled_large(tmp_path):
+    """--dump-outputs: float32 .npy per output; a small output whole with its shape, a large one as the same seeded
+    sample on every call, and all files together within the 64 MB the option promises."""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(1)
+    small = torch.randn(6, 1, 900, 10, generator=g).half()
+    big = torch.randint(-127, 128, (3, 1000, 1000), generator=g, dtype=torch.int8)
+    budget = 4 * 1_000_000                                  # 1 M values: a share of 500 000 each
+    w1 = b.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big, "none": None}, budget=budget)
+    w2 = b.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big.clone()}, budget=budget)
+    assert w1 == w2 and sorted(w1) == ["big", "small"]
+    s, bg = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and s.shape == (6, 1, 900, 10) and np.array_equal(s, small.float().numpy())
+    assert bg.dtype == np.float32 and bg.shape == (500_000,) and w1["big"] == ([500_000], 3_000_000)
+    assert np.array_equal(bg, np.load(tmp_path / "b" / "big.npy"))
+    assert set(np.unique(bg)) <= set(range(-127, 128)) and len(np.unique(bg)) > 200   # values of the tensor, spread
+    assert not (tmp_path / "a" / "none.npy").exists()
+    assert b.DUMP_BUDGET_BYTES + 16 * 4096 <= 64 * 10 ** 6
+
+
+def test_cli_has_full_and_dump_outputs():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=120, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    for opt in ("--full", "--dump-outputs", "--steps", "--warmup", "--gpus"):
+        assert opt in r.stdout

@@ -35,3 +35,29 @@ def test_sharded_bench_line_on_one_rank(extra, port):
     assert d["config"]["parallelism"] == f"cameras/1+{want}"
     assert d["dtype"] == ("i8" if "int8" in extra else "f16")
     assert d["scaling"] == "strong" and d["unit"] == "frames/s"
+
+
+def test_plain_run_is_lean_and_dumps_the_last_frame(tmp_path):
+    """A plain run (no --full) times the fp16 base frames only: the headline fields are there, the sub-records are
+    null; --dump-outputs writes the last timed frame's class scores and box coordinates (all six decoder layers)."""
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1000:]
+    d = json.loads(lines[0])
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f16"
+    assert "end-to-end" in d["metric"] and d["config"]["hip_graph"] is True
+    for key in ("protocol_sync", "hot_path", "roofline", "roofline_frame", "int8", "small", "tiny", "bevdet_r50",
+                "cpu_baseline"):
+        assert d[key] is None, key
+    import numpy as np
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["bbox_preds.npy", "cls_scores.npy"]
+    for name in files:
+        a = np.load(out / name)
+        assert a.dtype == np.float32 and a.shape[:3] == (6, 1, 900) and np.isfinite(a).all()
+    assert sum((out / n).stat().st_size for n in files) <= 64 * 10 ** 6

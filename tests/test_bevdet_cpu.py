@@ -8,7 +8,7 @@ import hashlib
 import numpy as np
 import torch
 
-from conftest import golden
+from conftest import golden, run_pinned
 from bevformer_tensorrt_amd.bevdet import BEVDET_R50, LSSViewTransformer
 
 
@@ -16,7 +16,7 @@ def _digest(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
-def test_ranks_and_intervals_bit_exact():
+def ranks_and_intervals():
     g = golden("bevdet_geometry")
     vt = LSSViewTransformer(**BEVDET_R50, ops=object())
     assert vt.D == int(g["D"]) == 59
@@ -35,3 +35,9 @@ def test_ranks_and_intervals_bit_exact():
     rb, st, ln = ranks[0].numpy(), ranks[3].numpy(), ranks[4].numpy()
     assert (np.diff(rb) >= 0).all() and st[0] == 0 and (st[1:] == np.cumsum(ln)[:-1]).all() and ln.sum() == rb.size
     assert rb.max() < 128 * 128
+
+
+def test_ranks_and_intervals_bit_exact():
+    """frustum, lidar coordinates and the five index arrays against the reference's own methods, bit for bit; run
+    with the CPU kernel choice pinned (conftest.run_pinned), the setting the golden was recorded in."""
+    run_pinned("test_bevdet_cpu", "ranks_and_intervals")

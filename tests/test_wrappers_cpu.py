@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import golden
+from conftest import golden, run_pinned
 from util_refops import RefOps
 
 
@@ -65,11 +65,9 @@ def test_rehosted_wrapper_equals_reference_forward_trt(run):
     assert np.abs(got - want).max() <= 1e-5, np.abs(got - want).max()
 
 
-def test_decoder_reference_point_loop_bit_exact():
-    """decoder.py:52-112: what each layer receives as reference_points and the refined points
-    after each reg branch -- same torch ops in the same order => identical bits on the CPU."""
+def decoder_reference_point_loop():
     from bevformer_tensorrt_amd import geometry as G
-    g = golden("wrappers")
+    g = golden("decoder_loop")
     ref = t(g, "loop.ref0")
     out = t(g, "loop.query")
     for i in range(3):
@@ -80,6 +78,13 @@ def test_decoder_reference_point_loop_bit_exact():
         tmp = torch.nn.functional.linear(out, t(g, f"loop.reg{i}.weight"), t(g, f"loop.reg{i}.bias")).view(1, -1, 10)
         ref = G.refine_reference_points(tmp, ref)
         assert np.array_equal(ref.numpy(), g["loop.inter_ref"][i]), i
+
+
+def test_decoder_reference_point_loop_bit_exact():
+    """decoder.py:52-112: what each layer receives as reference_points and the refined points
+    after each reg branch -- same torch ops in the same order => identical bits on the CPU
+    (tests/golden/decoder_loop.npz; run with the CPU kernel choice pinned, conftest.run_pinned)."""
+    run_pinned("test_wrappers_cpu", "decoder_reference_point_loop")
 
 
 def test_decoder_and_head_inverse_sigmoid_differ_only_below_eps():

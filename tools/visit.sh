@@ -5,7 +5,7 @@
 #   tests[:EXPR]   GPU suite (pytest -m gpu [-k EXPR]) -> pytest_gpu_tail.log
 #   testsv:EXPR    the same with -s (the tests' printed error figures) -> pytest_gpu_verbose.log
 #   smoke          __graft_entry__.smoke()              -> smoke.log
-#   bench[:ARGS]   python bench.py ARGS (default --steps 20 --warmup 5) -> bench_n1.json (+ bench.err)
+#   bench[:ARGS]   python bench.py --full ARGS (default --steps 20 --warmup 5) -> bench_n1.json (+ bench.err)
 #   trace[:int8]   kernel trace of one base frame (tools/model_profile.sh) -> model_frame[_int8]_kernel_trace.txt
 #   prof           rocprofv3 --kernel-trace --stats of the hot-path bench command -> prof/
 #   pmc            FETCH_SIZE / WRITE_SIZE passes of the same command (separate runs) -> pmc_fetch/, pmc_write/
@@ -17,7 +17,9 @@
 TAG=${1:?tag}; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 rocminfo | grep -E "Marketing|gfx|Compute Unit" | head -6 > $OUT/rocminfo.txt 2>&1; nproc >> $OUT/rocminfo.txt
-HOT="python $GRAFT_REPO_ROOT/bench.py --warmup 1 --no-cpu-baseline --no-end-to-end --no-geometry-extra"
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+# (--full: the profiled command runs the INT8 hot path and the frame rooflines too, as the PMC files bench.py reads expect)
+HOT="python $ROOT/bench.py --full --warmup 1 --no-cpu-baseline --no-end-to-end --no-geometry-extra"
 for step in "$@"; do
   name=${step%%:*}; arg=""; [ "$name" != "$step" ] && arg=${step#*:}
   cd $GRAFT_REPO_ROOT
@@ -25,7 +27,7 @@ for step in "$@"; do
     tests) ( timeout 1700 python -m pytest tests -m gpu -q -p no:cacheprovider ${arg:+-k "$arg"} 2>&1 | tail -40 ) > $OUT/pytest_gpu_tail.log; tail -8 $OUT/pytest_gpu_tail.log ;;
     testsv) ( timeout 1700 python -m pytest tests -m gpu -q -s -p no:cacheprovider -k "$arg" 2>&1 | grep -vE "^\s*$" | tail -200 ) > $OUT/pytest_gpu_verbose.log; grep -E "passed|failed|err|agreement|max " $OUT/pytest_gpu_verbose.log | tail -30 ;;
     smoke) ( timeout 200 python __graft_entry__.py smoke 2>&1 | tail -4 ) > $OUT/smoke.log; tail -2 $OUT/smoke.log ;;
-    bench) ( timeout 1500 python bench.py ${arg:---steps 20 --warmup 5} 2>$OUT/bench.err | tail -1 ) > $OUT/bench_n1.json; cut -c1-700 $OUT/bench_n1.json; tail -3 $OUT/bench.err ;;
+    bench) ( timeout 1500 python bench.py --full ${arg:---steps 20 --warmup 5} 2>$OUT/bench.err | tail -1 ) > $OUT/bench_n1.json; cut -c1-700 $OUT/bench_n1.json; tail -3 $OUT/bench.err ;;
     trace) if [ "$arg" = int8 ]; then bash tools/model_profile.sh $TAG/model_int8 base --int8 > $OUT/model_frame_int8_kernel_trace.txt 2>&1; rm -rf $OUT/model_int8
            else bash tools/model_profile.sh $TAG/model base > $OUT/model_frame_kernel_trace.txt 2>&1; rm -rf $OUT/model; head -16 $OUT/model_frame_kernel_trace.txt | cut -c1-130; fi ;;
     prof) cd /tmp; ( timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- $HOT --steps 5 2>&1 | tail -3 ) > $OUT/rocprof.log ;;
