@@ -47,6 +47,12 @@ const Entry kTable[] = {
     {"bevops_mdconv_forward_int8_packed", (void *)&bevops_mdconv_forward_int8_packed},
     {"ModulatedDeformableConv2dTRT", (void *)&bevops_mdconv_forward},
     {"ModulatedDeformableConv2dTRT2", (void *)&bevops_mdconv_forward},
+    {"bevops_qkv_forward", (void *)&bevops_qkv_forward},
+    {"bevops_qkv_workspace_size", (void *)&bevops_qkv_workspace_size},
+    {"QKVTRT", (void *)&bevops_qkv_forward},
+    {"QKVTRT2", (void *)&bevops_qkv_forward},
+    {"bevops_inverse_forward", (void *)&bevops_inverse_forward},
+    {"InverseTRT", (void *)&bevops_inverse_forward},
     // entries that are not reference plugins: workspace-lending / channels-last / fused forms
     {"bevops_grid_sampler_2d_forward_ws", (void *)&bevops_grid_sampler_2d_forward_ws},
     {"bevops_grid_sampler_2d_workspace_size", (void *)&bevops_grid_sampler_2d_workspace_size},

@@ -129,6 +129,10 @@ SIGNATURES = {
     "bevops_mdconv_pack_weight": (c_int, [c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "bevops_grid_sampler_3d_forward": (c_int, [c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 11 +
                                        [c_void_p]),
+    "bevops_qkv_workspace_size": (c_size_t, [c_int] * 5),
+    "bevops_qkv_forward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_float] * 4 +
+                           [c_void_p, c_size_t, c_void_p]),
+    "bevops_inverse_forward": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
 }
 
 F32, F16, I8, U8 = 0, 1, 2, 3

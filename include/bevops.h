@@ -64,7 +64,10 @@ const char *bevops_status_string(int status);
 /* Address of an entry point by plugin/op name, or NULL.  Accepts the ABI symbol
  * ("bevops_msda_forward") and the reference's plugin type names
  * ("MultiScaleDeformableAttnTRT", "MultiScaleDeformableAttnTRT2", "RotateTRT",
- * ...; multiScaleDeformableAttnPlugin.cpp:17-18 etc.), standing in for
+ * "RotateTRT2", "GridSampler2DTRT", "GridSampler2DTRT2", "GridSampler3DTRT",
+ * "GridSampler3DTRT2", "BEVPoolV2TRT", "BEVPoolV2TRT2", "ModulatedDeformableConv2dTRT",
+ * "ModulatedDeformableConv2dTRT2", "QKVTRT", "QKVTRT2", "InverseTRT";
+ * multiScaleDeformableAttnPlugin.cpp:17-18 etc.), standing in for
  * TensorRT's plugin-creator registry (REGISTER_TENSORRT_PLUGIN,
  * multiScaleDeformableAttnPlugin.cpp:345-346). */
 void *bevops_query(const char *name);
@@ -672,6 +675,35 @@ int bevops_mdconv_forward_packed(int dtype, const void *input, const void *offse
                                  int Cin, int H, int W, int Cout, int Kh, int Kw, int stride_h,
                                  int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
                                  int groups, int deform_groups, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Scaled dot-product attention, QKVTRT / QKVTRT2 (csrc/qkv.hip).
+ * Replaces QKVPlugin::enqueue (TensorRT/plugin/multi_head_attn/multiHeadAttnPlugin.cpp:89-150)
+ * and what it computes, det2trt/models/functions/multi_head_attn.py:12-16:
+ *   output[b, i, :] = sum_j softmax_j(<query[b, i, :], key[b, j, :]> / sqrt(embed_dim)) value[b, j, :]
+ *   query [batch, q_len, embed_dim], key / value [batch, kv_len, embed_dim], output [batch, q_len, embed_dim]
+ * F32 (f32 operands throughout) and F16 (fp32 scores, statistics and sums; probabilities rounded to binary16 for
+ * the second product); any lengths >= 1; embed_dim % 16 == 0 and 16 <= embed_dim <= 128, else
+ * BEVOPS_NOT_SUPPORTED.  scale_*: the INT8 per-tensor scales the plugin reads (multiHeadAttnPlugin.cpp:97-100),
+ * ignored for F32 / F16; I8 is BEVOPS_NOT_SUPPORTED.  workspace: bevops_qkv_workspace_size bytes (0 = none
+ * needed; more than 0 when few query tiles meet many keys and the keys are split across blocks), 16-byte aligned;
+ * a NULL or short one is BEVOPS_BAD_PARAM.  No atomics: results are bit-reproducible.
+ * ------------------------------------------------------------------------ */
+size_t bevops_qkv_workspace_size(int dtype, int batch, int q_len, int kv_len, int embed_dim);
+int bevops_qkv_forward(int dtype, const void *query, const void *key, const void *value, void *output, int batch,
+                       int q_len, int kv_len, int embed_dim, float scale_q, float scale_k, float scale_v,
+                       float scale_o, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Batched matrix inverse, InverseTRT (csrc/inverse.hip).
+ * Replaces InversePlugin::enqueue (TensorRT/plugin/inverse/inversePlugin.cpp:58-75, inverseKernel.cu:9-41:
+ * cublasSgetrfBatched + cublasSgetriBatched) and torch.linalg.inv (functions/inverse.py:11-13):
+ *   output[b] = input[b]^-1, input / output [batch, n, n] F32, 1 <= n <= 32 (else, and for F16 / I8,
+ *   BEVOPS_NOT_SUPPORTED).  Partial pivoting.  A matrix with an exactly zero pivot comes back all NaN and the
+ *   status stays BEVOPS_SUCCESS (the plugin cannot report a failure per matrix either); the other matrices of the
+ *   batch are unaffected.
+ * ------------------------------------------------------------------------ */
+int bevops_inverse_forward(int dtype, const void *input, void *output, int batch, int n, void *stream);
 
 #ifdef __cplusplus
 }
