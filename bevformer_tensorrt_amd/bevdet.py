@@ -132,6 +132,9 @@ from . import bevformer as _B   # noqa: E402  (ResNet and the channels-last conv
 import torch.nn.functional as F   # noqa: E402
 
 HEADS_R50 = (("reg", 2), ("height", 1), ("dim", 3), ("rot", 2), ("vel", 2), ("heatmap", 10))
+# bbox_coder of configs/bevdet/bevdet-r50-cbgs.py:138-147 (= test_cfg :167-178); norm_bbox=True (:152)
+CENTERPOINT_CODER_R50 = dict(pc_range=[-51.2, -51.2], post_center_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0], max_num=500,
+                             score_threshold=0.1, out_size_factor=8, voxel_size=[0.1, 0.1], code_size=9)
 
 
 def _conv(ops, x, conv, relu=False, residual=None):
@@ -257,6 +260,28 @@ class BEVDet(nn.Module):
         ops = self.ops
         s = _conv(ops, feat, self.shared_conv, True)
         return tuple(_conv(ops, _conv(ops, s, h[0], True), h[1]) for h in (self.heads[k] for k, _ in HEADS_R50))
+
+
+    # ---- CenterHead.get_bboxes up to the NMS (centerpoint_head.py:716-746), configs/bevdet/bevdet-r50-cbgs.py:138-147
+    @property
+    def bbox_coder(self):
+        from .postprocess import CenterPointBBoxCoder
+        if getattr(self, "_bbox_coder", None) is None:
+            self._bbox_coder = CenterPointBBoxCoder(**CENTERPOINT_CODER_R50)
+        return self._bbox_coder
+
+    def get_candidates(self, outputs, padded=False):
+        """outputs = `forward`'s (reg, height, dim, rot, vel, heatmap): the top 500 heat-map cells decoded to boxes
+        (x, y, z, w, l, h, yaw, vx, vy), those with score > 0.1 inside post_center_range kept -- the input of
+        the rotated scale-NMS of CenterHead.get_task_detections, which is left to the caller.  padded=True: (boxes
+        [B, 500, 9], scores [B, 500], labels [B, 500] int32, count [B] int32) without a host synchronisation; else one
+        {"bboxes", "scores", "labels"} per batch item, trimmed (labels float32, as the reference's)."""
+        reg, height, dim, rot, vel, heatmap = outputs
+        out = self.bbox_coder.decode_heads(reg, height, dim, rot, vel, heatmap, norm_bbox=True)
+        if padded:
+            return out
+        from .postprocess import _dicts
+        return _dicts(out, 9, torch.float32, heatmap.device)
 
 
 def synthetic_rig(view, n_cams=6, seed=0):

@@ -53,6 +53,8 @@ CONFIGS = {
                  levels=4, image=(928, 1600), bev=(200, 200), enc_layers=6, style="caffe"),
 }
 PC_RANGE = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
+POST_CENTER_RANGE = [-61.2, -61.2, -10.0, 61.2, 61.2, 10.0]   # bbox_coder, configs/bevformer/bevformer_base.py:166-173
+MAX_DETECTIONS = 300
 EMBED, HEADS, NUM_QUERY, NUM_CAMS = 256, 8, 900, 6
 
 
@@ -1061,6 +1063,27 @@ class BEVFormer(nn.Module):
         crd[..., 4:5] = crd[..., 4:5] * (PC_RANGE[5] - PC_RANGE[2]) + PC_RANGE[2]
         return bev_embed, self._cls_batched(hs).view(6, 1, NUM_QUERY, -1), crd
 
+    # ---- bevformer_head.py:538-566 (get_bboxes) with the coder of configs/bevformer/bevformer_base.py:166-173
+    @property
+    def bbox_coder(self):
+        from .postprocess import NMSFreeCoder
+        if getattr(self, "_bbox_coder", None) is None:
+            self._bbox_coder = NMSFreeCoder(PC_RANGE, voxel_size=[0.512, 0.512, 8], post_center_range=POST_CENTER_RANGE,
+                                            max_num=MAX_DETECTIONS, num_classes=10)
+        return self._bbox_coder
+
+    def get_bboxes(self, classes, coords, padded=False):
+        """Detections of the LAST decoder level of `forward`'s classes / coords [6, B, 900, 10]: the top 300 of the
+        9 000 (query, class) scores inside post_center_range, boxes on their bottom centre (z -= h / 2).
+        padded=True: (boxes [B, 300, 9], scores [B, 300], labels [B, 300] int32, count [B] int32), no host
+        synchronisation (this is what FrameRunner(decode=True) captures); else one {"bboxes", "scores", "labels"}
+        per batch item, trimmed to its count (labels int64, as the reference's)."""
+        padded_out = self.bbox_coder.decode_padded(classes[-1], coords[-1], bottom_center=True)
+        if padded:
+            return padded_out
+        from .postprocess import _dicts
+        return _dicts(padded_out, 9, torch.int64, classes.device)
+
     def _cls_batched(self, hs):
         """cls_branches[l](hs[l]) for the six decoder levels as batched GEMMs: Linear -> LayerNorm -> ReLU ->
         Linear -> LayerNorm -> ReLU -> Linear with the per-level parameters stacked along the batch."""
@@ -1110,11 +1133,14 @@ class FrameRunner:
     first frame of a scene replays the "no history" graph, every other frame the "history" graph, and
     neither carries the per-layer select between prev_bev and the repeated query."""
 
-    def __init__(self, model, device, dtype, graph=False, cams=None, gather=None, clone_outputs=True):
-        """clone_outputs=False: under graph replay `step` hands out the graph's own output buffers (valid until the
+    def __init__(self, model, device, dtype, graph=False, cams=None, gather=None, clone_outputs=True, decode=False):
+        """decode=True: the frame also decodes its detections (BEVFormer.get_bboxes, padded form) -- inside the captured
+        graph under graph=True, with no host synchronisation -- and `step` returns (classes, coords, boxes [1, 300, 9],
+        scores [1, 300], labels [1, 300] int32, count [1] int32) instead of (classes, coords).
+        clone_outputs=False: under graph replay `step` hands out the graph's own output buffers (valid until the
         next `step`, like the output bindings of a TensorRT execution context) instead of copies."""
         self.model, self.device, self.dtype, self.clone_outputs = model, device, dtype, clone_outputs
-        self.cams, self.gather = cams, gather
+        self.cams, self.gather, self.decode = cams, gather, decode
         self.tuned_gemms = use_tuned_gemms() if device.type == "cuda" else False
         nq = model.bev_h * model.bev_w
         self.prev_bev = torch.zeros(nq, 1, EMBED, device=device, dtype=dtype)
@@ -1172,7 +1198,9 @@ class FrameRunner:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):       # warm-up on the capture stream (allocations, MIOpen find)
             for _ in range(2):
-                self._forward()
+                out = self._forward()
+                if self.decode:
+                    self.model.get_bboxes(out[1], out[2], padded=True)
         torch.cuda.current_stream().wait_stream(s)
         graph = torch.cuda.CUDAGraph()
         # camera-sharded frames capture their RCCL collectives too (the process group's stream joins the capture
@@ -1189,7 +1217,8 @@ class FrameRunner:
         with torch.cuda.graph(graph, **kw):
             bev, cls, crd = self._forward()
             self.prev_bev.copy_(bev)     # state update is part of the graph
-        self._graphs[self._use] = (graph, (cls, crd))
+            det = self.model.get_bboxes(cls, crd, padded=True) if self.decode else ()
+        self._graphs[self._use] = (graph, (cls, crd) + tuple(det))
 
     def step_raw(self, raw_images, can_bus, lidar2img, scene_token):
         """Frame from RAW camera images [6, H0, W0, 3] (uint8 or fp32, BGR, on the device): the
@@ -1248,4 +1277,6 @@ class FrameRunner:
             return tuple(t.clone() for t in outs) if self.clone_outputs else outs
         bev_embed, cls, crd = self._forward()
         self.prev_bev = bev_embed                                               # stays on device (:144)
+        if self.decode:
+            return (cls, crd) + tuple(self.model.get_bboxes(cls, crd, padded=True))
         return cls, crd

@@ -53,6 +53,9 @@ const Entry kTable[] = {
     {"QKVTRT2", (void *)&bevops_qkv_forward},
     {"bevops_inverse_forward", (void *)&bevops_inverse_forward},
     {"InverseTRT", (void *)&bevops_inverse_forward},
+    {"bevops_nms_free_decode", (void *)&bevops_nms_free_decode},
+    {"bevops_centerpoint_decode", (void *)&bevops_centerpoint_decode},
+    {"bevops_centerpoint_decode_workspace_size", (void *)&bevops_centerpoint_decode_workspace_size},
     // entries that are not reference plugins: workspace-lending / channels-last / fused forms
     {"bevops_grid_sampler_2d_forward_ws", (void *)&bevops_grid_sampler_2d_forward_ws},
     {"bevops_grid_sampler_2d_workspace_size", (void *)&bevops_grid_sampler_2d_workspace_size},

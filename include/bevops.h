@@ -705,6 +705,66 @@ int bevops_qkv_forward(int dtype, const void *query, const void *key, const void
  * ------------------------------------------------------------------------ */
 int bevops_inverse_forward(int dtype, const void *input, void *output, int batch, int n, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Detection decode (csrc/decode.hip): raw head outputs -> boxes, scores, labels.  Not reference plugins: the
+ * reference runs these steps as ~30 framework launches with data-dependent shapes in `post_process`
+ * (det2trt/models/detector/bevformer.py:46-49, bevdet.py:84-89).  Not to be confused with bevops_decode_boxes,
+ * which is the head's sigmoid + de-normalisation of the regression output.
+ *
+ * Both entries write FIXED-CAPACITY outputs, so they need no host round trip and can be captured:
+ *   boxes [batch, max_num, 9] F32, scores [batch, max_num] F32, labels [batch, max_num] int32, count [batch] int32.
+ * The kept detections of item b are rows 0 .. count[b]-1, in rank order (what boolean-mask indexing of the
+ * reference's descending top-k list gives); rows at and behind count[b] are zero.  Inputs are F32 or F16 (an F16
+ * input means its values widened); all arithmetic and all outputs are F32; I8 is BEVOPS_NOT_SUPPORTED.  Inputs need
+ * no particular alignment.  No atomic whose order can show in a result: outputs are bit-reproducible.
+ * NULL pointers (where not stated optional), max_num < 1 and max_num above the number of candidates are
+ * BEVOPS_BAD_PARAM, returned before any device call.  `*_host` arrays are read during the call only.
+ *
+ * RANKING RULE.  Selection ranks the candidates by their fp32 LOGIT, larger first (sigmoid is monotone, so this is
+ * a top-k of the scores); equal logits (-0 equals +0) rank by LOWER FLAT INDEX first -- NMS-free:
+ * query * num_classes + class; CenterPoint: class * H * W + row * W + col.  torch.topk leaves the order among
+ * equals unspecified, so this is one valid reading of the reference, fixed so that results are reproducible.
+ *
+ * bevops_nms_free_decode: NMSFreeCoder.decode_single (third_party/bev_mmdet3d/core/bbox/coders/nms_free_coder.py:42-98,
+ * denormalize_bbox core/bbox/util.py:26-53) per batch item, optionally with the z shift of BEVFormerHead.get_bboxes
+ * (models/dense_heads/bevformer_head.py:556).
+ *   cls_logits [batch, num_query, num_classes], bbox_preds [batch, num_query, 10] =
+ *   (cx, cy, log w, log l, cz, log h, sin, cos, vx, vy); score = sigmoid(logit), label = flat index % num_classes,
+ *   box = (cx, cy, cz, e^w, e^l, e^h, atan2(sin, cos), vx, vy).  Kept: centre inside post_center_range_host[6]
+ *   (x, y, z lower bounds, then upper bounds, both inclusive) and the score test: score_threshold < 0 = none;
+ *   otherwise score > threshold, and when no candidate of the item passes, the reference's relaxation
+ *   (threshold *= 0.9 in double, test score >= threshold, until something passes; keep all once it falls below
+ *   0.01), evaluated on the device.  NaN / infinite thresholds are BEVOPS_BAD_PARAM.  bottom_center = 1 applies
+ *   z -= e^h / 2 AFTER the range test (the coder's output when 0).  num_query * num_classes <= 16 384, else
+ *   BEVOPS_NOT_SUPPORTED.  One launch, one workgroup per batch item.
+ *
+ * bevops_centerpoint_decode: CenterHead.get_bboxes up to the NMS (models/dense_heads/centerpoint_head.py:716-746)
+ * with CenterPointBBoxCoder.decode (core/bbox/coders/centerpoint_bbox_coders.py:138-230): the global top max_num of
+ * the num_classes x H x W heat map (what the coder's two-stage top-k selects), gather of the heads at the winning
+ * cells, x = (col + reg[0]) * out_size_factor * voxel_x + pc_x (y likewise with row, reg[1]; each step rounded to
+ * F32 like the reference's tensor ops), box = (x, y, height, dim[0..2] (exp'd when norm_bbox), atan2(rot[0], rot[1]),
+ * vel[0], vel[1]), label = class.  heatmap_is_score = 1: the map already holds scores (the coder's own `decode`
+ * receives the sigmoid's output); they are ranked and reported as they are, no sigmoid is applied.  Kept: score > score_threshold (< 0 = none) and (x, y, height) inside
+ * post_center_range_host.  Maps: reg [batch, 2, H, W], height [.,1,.,.], dim [.,3,.,.], rot [.,2,.,.],
+ * vel [.,2,.,.], heatmap [., num_classes, ., .], each dense per batch item (item stride = channels * H * W) and read
+ * in place through strides_host[12] = (channel stride, pixel stride) in elements for reg, height, dim, rot, vel,
+ * heatmap: (H * W, 1) for contiguous NCHW, (1, channels) for channels-last.  vel may be NULL (box columns 7, 8
+ * zero), reg may be NULL (+ 0.5).  max_num <= 4 096, else BEVOPS_NOT_SUPPORTED.  workspace:
+ * bevops_centerpoint_decode_workspace_size bytes, 8-byte aligned (0 = none needed: the heat map fits one
+ * workgroup's selection, one launch; otherwise two launches); a NULL or short one is BEVOPS_BAD_PARAM.
+ * ------------------------------------------------------------------------ */
+int bevops_nms_free_decode(int dtype, const void *cls_logits, const void *bbox_preds, float *boxes, float *scores,
+                           int32_t *labels, int32_t *count, int batch, int num_query, int num_classes, int max_num,
+                           const float *post_center_range_host, float score_threshold, int bottom_center,
+                           void *stream);
+size_t bevops_centerpoint_decode_workspace_size(int batch, int num_classes, int height, int width, int max_num);
+int bevops_centerpoint_decode(int dtype, const void *reg, const void *height, const void *dim, const void *rot,
+                              const void *vel, const void *heatmap, const int32_t *strides_host, float *boxes,
+                              float *scores, int32_t *labels, int32_t *count, int batch, int num_classes, int map_h,
+                              int map_w, int max_num, float out_size_factor, float voxel_x, float voxel_y, float pc_x,
+                              float pc_y, const float *post_center_range_host, float score_threshold, int norm_bbox,
+                              int heatmap_is_score, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bevformer_tensorrt_amd import bevformer as B, geometry as G  # noqa: E402
 
 
-def run(name, frames, dtype, graph=False, int8=False, clone=True, static_image=False):
+def run(name, frames, dtype, graph=False, int8=False, clone=True, static_image=False, decode=False):
     dev = torch.device("cuda")
     if int8:    # the PTQ build of bench.py (base only): int8 plugin sites + LinearQ / Conv2dQ dense layers
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,7 +24,7 @@ def run(name, frames, dtype, graph=False, int8=False, clone=True, static_image=F
         runner = bench.ModelFrames(dev, "int8", 1, 0, None, None, graph=graph).runner
     else:
         model = B.BEVFormer(name).to(dev, dtype)
-        runner = B.FrameRunner(model, dev, dtype, graph=graph, clone_outputs=clone)
+        runner = B.FrameRunner(model, dev, dtype, graph=graph, clone_outputs=clone, decode=decode)
     H, W = B.CONFIGS[name]["image"]
     l2i = G.synthetic_lidar2img((H, W)).to(dev)
     g = torch.Generator().manual_seed(0)
@@ -66,6 +66,7 @@ if __name__ == "__main__":
     ap.add_argument("--mdconv-variant", type=int, default=0, help="bevops_mdconv_set_variant (A/B)")
     ap.add_argument("--msda-variant", type=int, default=0, help="bevops_msda_set_variant before the frames are captured (A/B), e.g. 3015")
     ap.add_argument("--no-clone", action="store_true", help="hand out the graph's output buffers instead of copies")
+    ap.add_argument("--decode", action="store_true", help="FrameRunner(decode=True): the detections are decoded inside the frame")
     ap.add_argument("--static-image", action="store_true", help="images already in the frame's static input buffer")
     a = ap.parse_args()
     if a.conv_variant or a.mdconv_variant:
@@ -77,5 +78,5 @@ if __name__ == "__main__":
         load_library().bevops_msda_set_variant(a.msda_variant)
     dt = torch.float16 if a.dtype == "fp16" else torch.float32
     for m in a.models:
-        print(json.dumps(dict(run(m, a.frames, dt, a.graph, a.int8, not a.no_clone, a.static_image),
+        print(json.dumps(dict(run(m, a.frames, dt, a.graph, a.int8, not a.no_clone, a.static_image, a.decode),
                               mdconv_variant=a.mdconv_variant, msda_variant=a.msda_variant)), flush=True)
