@@ -135,6 +135,10 @@ HEADS_R50 = (("reg", 2), ("height", 1), ("dim", 3), ("rot", 2), ("vel", 2), ("he
 # bbox_coder of configs/bevdet/bevdet-r50-cbgs.py:138-147 (= test_cfg :167-178); norm_bbox=True (:152)
 CENTERPOINT_CODER_R50 = dict(pc_range=[-51.2, -51.2], post_center_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0], max_num=500,
                              score_threshold=0.1, out_size_factor=8, voxel_size=[0.1, 0.1], code_size=9)
+# test_cfg of configs/bevdet/bevdet-r50-cbgs.py:167-182 (the values the NMS reads; one task): rotated scale-NMS
+CENTERPOINT_TEST_CFG_R50 = dict(nms_type="rotate", nms_thr=0.2, pre_max_size=1000, post_max_size=500,
+                                nms_rescale_factor=[1.0, 0.7, 0.7, 0.4, 0.55, 1.1, 1.0, 1.0, 1.5, 3.5],
+                                min_radius=[4, 12, 10, 1, 0.85, 0.175])
 
 
 def _conv(ops, x, conv, relu=False, residual=None):
@@ -273,7 +277,7 @@ class BEVDet(nn.Module):
     def get_candidates(self, outputs, padded=False):
         """outputs = `forward`'s (reg, height, dim, rot, vel, heatmap): the top 500 heat-map cells decoded to boxes
         (x, y, z, w, l, h, yaw, vx, vy), those with score > 0.1 inside post_center_range kept -- the input of
-        the rotated scale-NMS of CenterHead.get_task_detections, which is left to the caller.  padded=True: (boxes
+        the rotated scale-NMS of CenterHead.get_task_detections (`get_bboxes`).  padded=True: (boxes
         [B, 500, 9], scores [B, 500], labels [B, 500] int32, count [B] int32) without a host synchronisation; else one
         {"bboxes", "scores", "labels"} per batch item, trimmed (labels float32, as the reference's)."""
         reg, height, dim, rot, vel, heatmap = outputs
@@ -282,6 +286,30 @@ class BEVDet(nn.Module):
             return out
         from .postprocess import _dicts
         return _dicts(out, 9, torch.float32, heatmap.device)
+
+    test_cfg = CENTERPOINT_TEST_CFG_R50
+
+    def get_bboxes(self, outputs, padded=False):
+        """CenterHead.get_bboxes (centerpoint_head.py:704-806) for the one task of the R50 configuration:
+        `get_candidates`, then the NMS of `test_cfg` (rotated scale-NMS: threshold 0.2, per-class rescale factors,
+        pre_max_size 1000, post_max_size 500; "circle" takes min_radius[0]), the size restore and z -= h / 2.
+        padded=True: (boxes [B, 500, 9], scores [B, 500], labels [B, 500] int32, count [B] int32, index [B, 500] int32 =
+        rows of `get_candidates(padded=True)`) without a host synchronisation, so the call can be captured; else one
+        [bboxes [n, 9], scores [n], labels [n] int32] per batch item, as the reference returns them -- the boxes as a
+        plain tensor: the `box_type_3d` wrapper class of the reference is not re-hosted.  A multi-task head would add
+        its class offset to the labels (centerpoint_head.py:800-804); that bookkeeping is the caller's."""
+        from .functions.nms import bev_nms
+        cfg = self.test_cfg
+        boxes, scores, labels, count = self.get_candidates(outputs, padded=True)
+        circle = cfg["nms_type"] == "circle"
+        out = bev_nms(boxes, scores, labels, count, nms_type=cfg["nms_type"],
+                      threshold=cfg["min_radius"][0] if circle else cfg["nms_thr"],
+                      pre_max_size=None if circle else cfg["pre_max_size"],
+                      post_max_size=min(cfg["post_max_size"], boxes.shape[1]),
+                      rescale_factor=None if circle else cfg.get("nms_rescale_factor"), bottom_center=True, padded=True)
+        if padded:
+            return out
+        return [[out[0][b, :n], out[1][b, :n], out[2][b, :n]] for b, n in enumerate(out[3].tolist())]
 
 
 def synthetic_rig(view, n_cams=6, seed=0):

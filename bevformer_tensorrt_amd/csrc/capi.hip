@@ -56,6 +56,9 @@ const Entry kTable[] = {
     {"bevops_nms_free_decode", (void *)&bevops_nms_free_decode},
     {"bevops_centerpoint_decode", (void *)&bevops_centerpoint_decode},
     {"bevops_centerpoint_decode_workspace_size", (void *)&bevops_centerpoint_decode_workspace_size},
+    {"bevops_bev_nms", (void *)&bevops_bev_nms},
+    {"bevops_bev_nms_workspace_size", (void *)&bevops_bev_nms_workspace_size},
+    {"bevops_bev_iou", (void *)&bevops_bev_iou},
     // entries that are not reference plugins: workspace-lending / channels-last / fused forms
     {"bevops_grid_sampler_2d_forward_ws", (void *)&bevops_grid_sampler_2d_forward_ws},
     {"bevops_grid_sampler_2d_workspace_size", (void *)&bevops_grid_sampler_2d_workspace_size},

@@ -13,9 +13,12 @@ stable descending sort.
 
 Both paths produce the padded form first -- boxes [B, max_num, 9] fp32, scores [B, max_num] fp32, labels
 [B, max_num] int32, count [B] int32, kept rows in rank order at the front, zero behind -- and the per-item dicts of the
-reference are cut from it.  Not here: BEVDet's rotated scale-NMS (CenterHead.get_task_detections); `decode` hands back
-what that NMS consumes.
+reference are cut from it.  BEVDet's rotated scale-NMS and the circle NMS (CenterHead.get_task_detections, get_bboxes)
+follow the CenterPoint coder: `bev_nms_torch` below is their CPU statement, with the pair test in fp64 -- the
+definition ("the exact overlapping area of the two boxes", box3d_nms.py:230-231) that the kernel's fp32 evaluation is
+measured against.
 """
+import numpy as np
 import torch
 
 from .functions.decode import nms_free_decode, centerpoint_decode
@@ -123,6 +126,142 @@ def centerpoint_decode_torch(reg, height, dim, rot, vel, heatmap, max_num, post_
         keep &= scores > score_threshold
     out = _pad(keep, boxes, scores, labels)
     return out + (index, keep) if return_index else out
+
+
+def _clip_half_plane(verts, n, axis, sign, bound):
+    """One Sutherland-Hodgman stage for P polygons at once: verts [P, 8, 2], n [P] vertex counts, kept part
+    sign * v[axis] <= bound [P].  Returns (verts, n) of the clipped polygons."""
+    P = verts.shape[0]
+    rows = torch.arange(P)
+    out = torch.zeros_like(verts)
+    m = torch.zeros(P, dtype=torch.long)
+    for k in range(8):
+        live = k < n
+        cur = verts[:, k]
+        nxt = verts[rows, torch.where(k + 1 < n, k + 1, 0)]
+        dc, dn = bound - sign * cur[:, axis], bound - sign * nxt[:, axis]
+        ic, inx = dc >= 0, dn >= 0
+        put = live & ic & (m < 8)
+        out[rows[put], m[put]] = cur[put]
+        m = m + put.long()
+        put = live & (ic != inx) & (m < 8)
+        t = torch.where(put, dc / torch.where(put, dc - dn, torch.ones_like(dc)), torch.zeros_like(dc))
+        p = cur + t[:, None] * (nxt - cur)
+        p[:, axis] = sign * bound
+        out[rows[put], m[put]] = p[put]
+        m = m + put.long()
+    return out, m
+
+
+def bev_iou_fp64(boxes_a, boxes_b):
+    """IoU [M, N] in fp64 of rotated rectangles (x, y, w, l, yaw), w along (cos yaw, sin yaw): rectangle b clipped
+    against the four edges of rectangle a in a's frame, area by the shoelace formula.  A pair whose union is not
+    positive has IoU 0; NaN inputs give NaN."""
+    a, b = boxes_a.detach().double().cpu(), boxes_b.detach().double().cpu()
+    M, N = a.shape[0], b.shape[0]
+    A, B = a[:, None, :].expand(M, N, 5).reshape(-1, 5), b[None, :, :].expand(M, N, 5).reshape(-1, 5)
+    iou = torch.zeros(M * N, dtype=torch.float64)
+    d = B[:, :2] - A[:, :2]
+    reach = 0.5 * (torch.hypot(A[:, 2], A[:, 3]) + torch.hypot(B[:, 2], B[:, 3]))
+    bad = torch.isnan(A).any(1) | torch.isnan(B).any(1)
+    near = (d.square().sum(1) <= reach.square() * (1 + 1e-9)) & ~bad
+    if near.any():
+        A, B, d = A[near], B[near], d[near]
+        ca, sa = torch.cos(A[:, 4]), torch.sin(A[:, 4])
+        rot = lambda v: torch.stack([v[:, 0] * ca + v[:, 1] * sa, v[:, 1] * ca - v[:, 0] * sa], 1)
+        cb, sb = torch.cos(B[:, 4]), torch.sin(B[:, 4])
+        e = rot(d)
+        u = rot(torch.stack([0.5 * B[:, 2] * cb, 0.5 * B[:, 2] * sb], 1))
+        v = rot(torch.stack([-0.5 * B[:, 3] * sb, 0.5 * B[:, 3] * cb], 1))
+        verts = torch.zeros(A.shape[0], 8, 2, dtype=torch.float64)
+        verts[:, 0], verts[:, 1], verts[:, 2], verts[:, 3] = e + u + v, e - u + v, e - u - v, e + u - v
+        n = torch.full((A.shape[0],), 4, dtype=torch.long)
+        hw, hl = 0.5 * A[:, 2], 0.5 * A[:, 3]
+        for axis, sign, bound in ((0, 1.0, hw), (0, -1.0, hw), (1, 1.0, hl), (1, -1.0, hl)):
+            verts, n = _clip_half_plane(verts, n, axis, sign, bound)
+        nxt = torch.roll(verts, -1, 1).clone()
+        rows = torch.arange(A.shape[0])
+        last = (n - 1).clamp(min=0)
+        nxt[rows, last] = verts[:, 0]
+        cross = verts[..., 0] * nxt[..., 1] - nxt[..., 0] * verts[..., 1]
+        cross = torch.where(torch.arange(8)[None, :] < n[:, None], cross, torch.zeros_like(cross))
+        inter = torch.where(n >= 3, 0.5 * cross.sum(1).abs(), torch.zeros_like(hw))
+        union = A[:, 2] * A[:, 3] + B[:, 2] * B[:, 3] - inter
+        iou[near] = torch.where(union > 0, inter / torch.where(union > 0, union, torch.ones_like(union)),
+                                torch.zeros_like(union))
+    iou[bad] = float("nan")
+    return iou.reshape(M, N)
+
+
+def _factor_list(rescale_factor):
+    from .functions.nms import _factors
+    return _factors(rescale_factor)
+
+
+def bev_nms_torch(boxes, scores, labels, count=None, *, nms_type="rotate", threshold, pre_max_size=None,
+                  post_max_size, rescale_factor=None, bottom_center=False):
+    """The padded result of `bev_nms` -- (boxes [B, post_max_size, 9], scores, labels int32, count, index int32) --
+    stated in torch ops on the CPU: stable descending sort (equal scores: lower row first), the sizes multiplied and
+    divided back in fp32 as the reference's tensor ops do (centerpoint_head.py:836-876), the pair test in fp64
+    (`bev_iou_fp64`; circle: the fp32 expression of box3d_nms.py:216), greedy scan, cut to post_max_size."""
+    boxes, scores = boxes.detach().float().cpu(), scores.detach().float().cpu()
+    labels = labels.detach().cpu()
+    if boxes.ndim == 2:
+        boxes, scores, labels = boxes[None], scores[None], labels[None]
+        count = None if count is None else count.reshape(1)
+    B, N = scores.shape
+    post = int(post_max_size)
+    if not 1 <= post <= N:
+        raise ValueError(f"post_max_size {post} outside 1 .. {N}")
+    if nms_type not in ("rotate", "circle"):
+        raise ValueError(f"nms_type must be 'rotate' or 'circle', got {nms_type!r}")
+    fac = _factor_list(rescale_factor)
+    counts = [N] * B if count is None else [min(max(int(c), 0), N) for c in count.tolist()]
+    pre = N if pre_max_size is None or int(pre_max_size) <= 0 else min(int(pre_max_size), N)
+    out_b, out_s = torch.zeros(B, post, 9), torch.zeros(B, post)
+    out_l, out_i = torch.zeros(B, post, dtype=torch.int32), torch.zeros(B, post, dtype=torch.int32)
+    out_c = torch.zeros(B, dtype=torch.int32)
+    thr32 = torch.tensor(float(threshold), dtype=torch.float32)
+    for b in range(B):
+        n = counts[b]
+        if n == 0:
+            continue
+        bx, sc, lb = boxes[b, :n].clone(), scores[b, :n], labels[b, :n].long()
+        f = torch.ones(n, dtype=torch.float32)
+        if len(fac) == 1:
+            f[:] = fac[0]
+        elif fac:
+            inside = (lb >= 0) & (lb < len(fac))
+            f[inside] = torch.tensor(fac, dtype=torch.float32)[lb[inside]]
+        scaled = bx[:, 3:6] * f[:, None]
+        order = torch.sort(sc + 0.0, descending=True, stable=True).indices[:pre]
+        if nms_type == "rotate":
+            q = torch.stack([bx[:, 0], bx[:, 1], scaled[:, 0], scaled[:, 1], bx[:, 6]], 1)[order]
+            sup = bev_iou_fp64(q, q) > float(thr32)          # (NaN compares false)
+        else:
+            x, y = bx[order, 0], bx[order, 1]
+            dx, dy = x[:, None] - x[None, :], y[:, None] - y[None, :]
+            sup = (dx * dx + dy * dy) <= thr32
+        sup = sup.numpy()
+        removed = np.zeros(order.numel(), dtype=bool)
+        keep = []
+        for i in range(order.numel()):
+            if removed[i]:
+                continue
+            keep.append(i)
+            if len(keep) == post:
+                break
+            removed[i + 1:] |= sup[i, i + 1:]
+        keep = order[torch.tensor(keep, dtype=torch.long)]
+        k = keep.numel()
+        if fac:
+            bx[:, 3:6] = scaled / f[:, None]
+        kept = bx[keep]
+        if bottom_center:
+            kept[:, 2] = kept[:, 2] - kept[:, 5] * 0.5
+        out_b[b, :k], out_s[b, :k], out_l[b, :k] = kept, sc[keep], lb[keep].to(torch.int32)
+        out_i[b, :k], out_c[b] = keep.to(torch.int32), k
+    return out_b, out_s, out_l, out_c, out_i
 
 
 def _dicts(padded, columns, label_dtype, device):

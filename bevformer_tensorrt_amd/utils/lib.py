@@ -137,6 +137,10 @@ SIGNATURES = {
     "bevops_centerpoint_decode_workspace_size": (c_size_t, [c_int] * 5),
     "bevops_centerpoint_decode": (c_int, [c_int] + [c_void_p] * 11 + [c_int] * 5 + [c_float] * 5 +
                                   [c_void_p, c_float, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "bevops_bev_nms_workspace_size": (c_size_t, [c_int, c_int]),
+    "bevops_bev_nms": (c_int, [c_int] + [c_void_p] * 9 + [c_int] * 4 + [c_float, c_void_p, c_int, c_int, c_void_p,
+                                                                        c_size_t, c_void_p]),
+    "bevops_bev_iou": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
 F32, F16, I8, U8 = 0, 1, 2, 3

@@ -765,6 +765,55 @@ int bevops_centerpoint_decode(int dtype, const void *reg, const void *height, co
                               float pc_y, const float *post_center_range_host, float score_threshold, int norm_bbox,
                               int heatmap_is_score, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------
+ * BEV non-maximum suppression (csrc/nms.hip): what CenterHead.get_bboxes does behind the coder
+ * (third_party/bev_mmdet3d/models/dense_heads/centerpoint_head.py:747-806) -- the rotated "scale-NMS" of
+ * get_task_detections (:808-905) through nms_bev (core/post_processing/box3d_nms.py:227-273), or circle_nms
+ * (box3d_nms.py:182-221), then the size restore (:870-876) and the z shift to the bottom centre (:793).
+ *
+ * bevops_bev_nms.  mode 0 = rotate (row j is suppressed by an earlier kept row i when IoU(i, j) > threshold,
+ * strictly), 1 = circle (when (x_i - x_j)^2 + (y_i - y_j)^2 <= threshold).
+ *   boxes_in [batch, num, 9] F32 = (x, y, z, w, l, h, yaw, vx, vy) as bevops_centerpoint_decode writes them, scores_in
+ *   [batch, num] F32, labels_in [batch, num] int32, count_in [batch] int32 = valid rows per item, read ON THE DEVICE
+ *   (NULL = num; above num is read as num, below 0 as 0).  Rows at and behind count_in[b] are never read as
+ *   candidates, whatever they hold.
+ *   Outputs, fixed capacity like the decoders': boxes [batch, post_max_size, 9], scores, labels [batch, post_max_size],
+ *   count [batch], index [batch, post_max_size] int32 = the kept rows as row numbers of the input (may be NULL); kept
+ *   rows first, in rank order, everything at and behind count[b] zero.  No host round trip: capturable.
+ * RANK (nms_bev :249-253, circle_nms :202): the valid rows in descending score order, cut to pre_max_size (<= 0 = no
+ *   cut).  Equal scores (-0 equals +0) rank by LOWER INPUT ROW first: the decoders' rule, the same 64-bit key.
+ * SCALE (centerpoint_head.py:836-844): w, l, h of a row with label c are multiplied by rescale_factor_host[c] in F32
+ *   (num_factors = 1: every row by rescale_factor_host[0]; 0: no scaling; labels outside [0, num_factors) are left
+ *   alone).  The pair test sees (x, y, w f, l f, yaw), the `.bev` columns 0, 1, 3, 4, 6 (lidar_box3d.py:94;
+ *   xyxyr2xywhr=False at centerpoint_head.py:865), w along (cos yaw, sin yaw).  At most 64 factors.
+ * PAIR TEST, rotate: intersection area of the two rotated rectangles over area_i + area_j - intersection -- nms_bev's
+ *   "exact overlapping area" -- evaluated in F32 in the frame of box i (rectangle j clipped against the four edges of
+ *   rectangle i, coordinates relative to i's centre); a pair whose union is not positive has IoU 0; a row with a
+ *   non-finite x, y, w, l or yaw suppresses nothing and is not suppressed.  bevops_bev_iou exposes this function;
+ *   its distance from the F64 value is bounded by a test at 5e-4 and measured near 1e-6 (design/postprocess.md).
+ * PAIR TEST, circle: the squared distance in F32, each operation rounded on its own, compared with `threshold` AS IT
+ *   IS: circle_nms compares min_radius with the SQUARED distance (:216-219), so min_radius is not squared here either.
+ * SCAN: in rank order, a row not yet suppressed is kept and suppresses; stops after post_max_size kept rows.
+ * WRITE: columns 0-2, 6-8, score and label are copied bits.  With factors, columns 3-5 are fl(fl(d f) / f), IEEE F32
+ *   division: the reference multiplies in place and divides back, which does not always return d.  bottom_center != 0:
+ *   then z = fl(z - fl(h 0.5)) with that h.
+ * LIMITS, checked before any device call: batch >= 1, 1 <= num <= 4 096 (above: BEVOPS_NOT_SUPPORTED, as are more
+ *   than 64 factors), 1 <= post_max_size <= num; NULL pointers (index and count_in excepted), a workspace shorter than
+ *   bevops_bev_nms_workspace_size(batch, num) or not 8-byte aligned, a non-finite threshold or factor, a factor <= 0:
+ *   BEVOPS_BAD_PARAM.  Three launches (rank + scale; suppression matrix as 64-bit words, one wave per word; scan +
+ *   gather), none sized by a device value.  Outputs are bit-reproducible.
+ *
+ * bevops_bev_iou: iou [num_a, num_b] F32 of boxes_a [num_a, 5] and boxes_b [num_b, 5], (x, y, w, l, yaw) each,
+ * evaluated in the frame of the a-box; NaN where a box has a non-finite entry.  num_a * num_b <= 2^30.
+ * ------------------------------------------------------------------------ */
+size_t bevops_bev_nms_workspace_size(int batch, int num);
+int bevops_bev_nms(int mode, const float *boxes_in, const float *scores_in, const int32_t *labels_in,
+                   const int32_t *count_in, float *boxes, float *scores, int32_t *labels, int32_t *count,
+                   int32_t *index, int batch, int num, int pre_max_size, int post_max_size, float threshold,
+                   const float *rescale_factor_host, int num_factors, int bottom_center, void *workspace,
+                   size_t workspace_bytes, void *stream);
+int bevops_bev_iou(const float *boxes_a, int num_a, const float *boxes_b, int num_b, float *iou, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

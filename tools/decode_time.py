@@ -14,9 +14,20 @@ The torch sequence is timed in two parts, because only the first can be captured
 Per case: median and max over >= 5 rounds of one replay of `iters` calls each.  One JSON line per case.
     python tools/decode_time.py [--rounds 7] [--once]
     python tools/decode_time.py --frame-ab tiny base [--pairs 3]
+    python tools/decode_time.py --nms [--rounds 7] [--once]
+    python tools/decode_time.py --bevdet-ab [--pairs 3]
 --once: every decode once, eagerly, no timing (for a `rocprofv3 --kernel-trace --stats` run: launches per call).
 --frame-ab: the whole frame with FrameRunner(decode=True) against decode=False as interleaved same-box pairs, each a
-fresh `tools/model_bench.py MODEL --graph --no-clone --static-image --frames 40 [--decode]` process."""
+fresh `tools/model_bench.py MODEL --graph --no-clone --static-image --frames 40 [--decode]` process.
+--nms: the BEV NMS (csrc/nms.hip) at BEVDet-R50's configuration (500 candidates, threshold 0.2, the per-class rescale
+factors, post_max_size 500; circle: min_radius 4, post_max_size 83) on a clustered scene (every object with ~8 near
+duplicates, as the top cells of a heat map) and on a sparse one (no overlaps), against the formulation a user without
+the kernel would write: the suppression matrix in vectorised torch device ops (rotate: both boxes' corners and edge
+intersections, sorted by angle, shoelace -- the usual differentiable rotated-IoU recipe; circle: one broadcast) plus the
+greedy loop as 500 row updates, captured and replayed the same way (`torch_graph_us`; the loop alone is
+`torch_scan_graph_us`).
+--bevdet-ab: the BEVDet-R50 frame (forward + post-processing in one captured graph) with get_bboxes against
+get_candidates as interleaved pairs of fresh processes (`--bevdet-frame MODE` is the child)."""
 import argparse
 import json
 import os
@@ -75,6 +86,184 @@ def torch_centerpoint(reg, hei, dim, rot, vel, heat, K, rng, thr, osf, voxel, pc
     mask &= (boxes[..., :3] <= rng[3:]).all(2)
     mask &= scores > thr
     return boxes, scores, labels.float(), mask
+
+
+R50_FACTORS = [1.0, 0.7, 0.7, 0.4, 0.55, 1.1, 1.0, 1.0, 1.5, 3.5]      # configs/bevdet/bevdet-r50-cbgs.py:182
+
+
+_SIGNS = {}
+
+
+def torch_rotated_iou(q):
+    """IoU [n, n] of boxes q [n, 5] (x, y, w, l, yaw) in torch device ops, fixed shapes (capturable): the 8 corners that
+    lie inside the other box and the 16 edge-edge intersections, sorted by angle about their mean, shoelace.  (Parallel
+    edges give no intersection, so a box against itself -- the diagonal, which the NMS never reads -- comes out 0.)"""
+    n = q.shape[0]
+    c, s = torch.cos(q[:, 4]), torch.sin(q[:, 4])
+    if q.device not in _SIGNS:       # (made by the warm-up call: a host-to-device copy cannot be captured)
+        _SIGNS[q.device] = (torch.tensor([0.5, -0.5, -0.5, 0.5], device=q.device),
+                            torch.tensor([0.5, 0.5, -0.5, -0.5], device=q.device))
+    sx, sy = _SIGNS[q.device]
+    lx, ly = q[:, 2:3] * sx, q[:, 3:4] * sy
+    corners = torch.stack([q[:, 0:1] + lx * c[:, None] - ly * s[:, None],
+                           q[:, 1:2] + lx * s[:, None] + ly * c[:, None]], -1)                # [n, 4, 2]
+    A = (corners[:, None] - q[:, None, None, :2]).expand(n, n, 4, 2)                            # relative to box i
+    Bc = corners[None] - q[:, None, None, :2]                                                   # box j, same origin
+
+    def inside(pts, ctr, cc, ss, w, l):            # pts [n, n, 4, 2] inside the box (ctr, w, l, yaw) broadcast [n, n]
+        d = pts - ctr[:, :, None, :]
+        u = d[..., 0] * cc[:, :, None] + d[..., 1] * ss[:, :, None]
+        v = d[..., 1] * cc[:, :, None] - d[..., 0] * ss[:, :, None]
+        return (u.abs() <= 0.5 * w[:, :, None] + 1e-6) & (v.abs() <= 0.5 * l[:, :, None] + 1e-6)
+    zero = torch.zeros(n, n, 2, device=q.device)
+    ci, si, wi, li = (t[:, None].expand(n, n) for t in (c, s, q[:, 2], q[:, 3]))
+    cj, sj, wj, lj = (t[None, :].expand(n, n) for t in (c, s, q[:, 2], q[:, 3]))
+    ctr_j = (q[None, :, :2] - q[:, None, :2])
+    a_in_b, b_in_a = inside(A, ctr_j, cj, sj, wj, lj), inside(Bc, zero, ci, si, wi, li)
+    a0, a1 = A[:, :, :, None, :], A.roll(-1, 2)[:, :, :, None, :]                               # edges of i x edges of j
+    b0, b1 = Bc[:, :, None, :, :], Bc.roll(-1, 2)[:, :, None, :, :]
+    da, db = a1 - a0, b1 - b0
+    den = da[..., 0] * db[..., 1] - da[..., 1] * db[..., 0]
+    w0 = b0 - a0
+    t = (w0[..., 0] * db[..., 1] - w0[..., 1] * db[..., 0]) / den
+    u = (w0[..., 0] * da[..., 1] - w0[..., 1] * da[..., 0]) / den
+    hit = (den.abs() > 1e-12) & (t >= 0) & (t <= 1) & (u >= 0) & (u <= 1)
+    cross = (a0 + t[..., None] * da).reshape(n, n, 16, 2)
+    pts = torch.cat([A, Bc, cross], 2)                                                          # [n, n, 24, 2]
+    ok = torch.cat([a_in_b, b_in_a, hit.reshape(n, n, 16)], 2)
+    cnt = ok.sum(2).clamp(min=1)
+    mean = (pts * ok[..., None]).sum(2) / cnt[..., None]
+    rel = pts - mean[:, :, None, :]
+    ang = torch.where(ok, torch.atan2(rel[..., 1], rel[..., 0]), torch.full_like(rel[..., 0], 10.0))
+    order = ang.argsort(2)
+    rel = rel.gather(2, order[..., None].expand(-1, -1, -1, 2))
+    ok = ok.gather(2, order)
+    first = rel[:, :, :1]
+    nxt = torch.where(ok.roll(-1, 2)[..., None], rel.roll(-1, 2), first.expand_as(rel))        # wrap to the first vertex
+    tw = (rel[..., 0] * nxt[..., 1] - nxt[..., 0] * rel[..., 1]) * ok
+    inter = 0.5 * tw.sum(2).abs()
+    area = q[:, 2] * q[:, 3]
+    union = area[:, None] + area[None, :] - inter
+    return torch.where(union > 0, inter / union, torch.zeros_like(union))
+
+
+def torch_nms(boxes, scores, labels, factors, thr, post, circle):
+    """What a user of the decoders alone would write on the device: sort, scale, suppression matrix, the greedy loop as
+    one row update per candidate (no host round trip, so it can be captured), gather, divide back, z shift.  Returns
+    the keep mask in rank order and the restored boxes (the compaction to the front is not even included)."""
+    order = scores.argsort(descending=True, stable=True)
+    b, l = boxes[order], labels[order].long()
+    if circle:
+        dx, dy = b[:, None, 0] - b[None, :, 0], b[:, None, 1] - b[None, :, 1]
+        sup = (dx * dx + dy * dy) <= thr
+        f = None
+    else:
+        f = factors[l][:, None]
+        sized = b[:, 3:6] * f
+        sup = torch_rotated_iou(torch.stack([b[:, 0], b[:, 1], sized[:, 0], sized[:, 1], b[:, 6]], 1)) > thr
+    sup = sup.triu(1)
+    keep = torch_scan(sup, post)
+    out = b.clone()
+    if f is not None:
+        out[:, 3:6] = sized / f
+    out[:, 2] = out[:, 2] - out[:, 5] * 0.5
+    return keep, out, scores[order], l
+
+
+def torch_scan(sup, post):
+    n = sup.shape[0]
+    removed = torch.zeros(n, dtype=torch.bool, device=sup.device)
+    for i in range(n):
+        removed |= sup[i] & ~removed[i]
+    keep = ~removed
+    return keep & (keep.cumsum(0) <= post)
+
+
+def nms_scenes():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
+    import util_nms as U
+    rng = np.random.default_rng(0)
+    return {"clustered": U.clustered_scene(rng, 500), "sparse": U.sparse_scene(rng, 500)}
+
+
+def nms_operators(args):
+    factors = torch.tensor(R50_FACTORS, device="cuda")
+    for scene, (bx, sc, lb) in nms_scenes().items():
+        boxes, scores, labels = (torch.from_numpy(a)[None].to("cuda") for a in (bx, sc, lb))
+        count = torch.tensor([500], dtype=torch.int32, device="cuda")
+        for kind in ("rotate", "circle"):
+            circle = kind == "circle"
+            kw = dict(nms_type=kind, threshold=4.0 if circle else 0.2, pre_max_size=None if circle else 1000,
+                      post_max_size=83 if circle else 500, rescale_factor=None if circle else R50_FACTORS,
+                      bottom_center=True, padded=True)
+            ours = lambda: bev.bev_nms(boxes, scores, labels, count, **kw)
+            if args.once:
+                ours()
+                torch.cuda.synchronize()
+                continue
+            theirs = lambda: torch_nms(boxes[0], scores[0], labels[0], factors, kw["threshold"], kw["post_max_size"], circle)
+            got = ours()
+            keep, out, _, _ = theirs()
+            kept = int(got[3][0])
+            same = kept == int(keep.sum()) and torch.equal(got[0][0, :kept], out[keep])
+            sup = torch.zeros(500, 500, dtype=torch.bool, device="cuda").triu(1)
+            o = stats(graph_times_us(ours, 50, args.rounds))
+            t = stats(graph_times_us(theirs, 4, args.rounds))
+            scan = stats(graph_times_us(lambda: torch_scan(sup, 500), 4, args.rounds))
+            print(json.dumps({"op": "bev_nms", "nms_type": kind, "scene": scene, "num": 500, "kept": kept,
+                              "torch_formulation_selects_the_same": bool(same), "us": o, "torch_graph_us": t,
+                              "torch_scan_graph_us": scan,
+                              "speedup_vs_torch_graph": round(t["median"] / o["median"], 1)}), flush=True)
+
+
+def bevdet_frame(mode, frames=40):
+    """Child of --bevdet-ab: BEVDet-R50 forward + get_candidates / get_bboxes (padded) in one captured graph."""
+    from bevformer_tensorrt_amd import bevdet as D
+    dev = torch.device("cuda")
+    model = D.BEVDet(seed=0).to(dev, torch.float16)
+    ranks = [r.to(dev) for r in model.view.get_bev_pool_input(*D.synthetic_rig(model.view))]
+    image = torch.randn(1, 6, 3, 256, 704, generator=torch.Generator().manual_seed(1)).to(dev, torch.float16)
+    post = model.get_bboxes if mode == "bboxes" else model.get_candidates
+    step = lambda: post(model(image, *ranks), padded=True)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            step()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = step()
+    for _ in range(5):
+        g.replay()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(frames):
+        g.replay()
+    b.record()
+    b.synchronize()
+    print(json.dumps({"model": "bevdet_r50", "postprocess": mode, "frames": frames,
+                      "ms_per_frame": round(a.elapsed_time(b) / frames, 4), "rows": int(out[3][0])}), flush=True)
+
+
+def bevdet_ab(pairs):
+    rows = {"candidates": [], "bboxes": []}
+    for _ in range(pairs):
+        for mode in rows:
+            cmd = [sys.executable, os.path.abspath(__file__), "--bevdet-frame", mode]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                sys.stderr.write(r.stderr[-2000:])
+                raise SystemExit(f"{' '.join(cmd)} failed with {r.returncode}")
+            rec = json.loads(r.stdout.strip().splitlines()[-1])
+            rows[mode].append(rec["ms_per_frame"])
+            print(json.dumps(rec), flush=True)
+    off, on = statistics.median(rows["candidates"]), statistics.median(rows["bboxes"])
+    print(json.dumps({"frame_ab": "bevdet_r50", "pairs": pairs, "ms_get_candidates": rows["candidates"],
+                      "ms_get_bboxes": rows["bboxes"], "median_candidates": off, "median_bboxes": on,
+                      "delta_us": round((on - off) * 1e3, 1), "delta_percent": round((on / off - 1) * 100, 2)}), flush=True)
 
 
 def eager_us(fn, rounds, iters=20):
@@ -166,10 +355,19 @@ def main():
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--frame-ab", nargs="+", metavar="MODEL")
     ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--nms", action="store_true")
+    ap.add_argument("--bevdet-ab", action="store_true")
+    ap.add_argument("--bevdet-frame", choices=["candidates", "bboxes"])
     args = ap.parse_args()
     if args.frame_ab:
         return frame_ab(args.frame_ab, args.pairs)
+    if args.bevdet_ab:
+        return bevdet_ab(args.pairs)
     assert torch.cuda.is_available(), "decode_time.py needs the GPU"
+    if args.bevdet_frame:
+        return bevdet_frame(args.bevdet_frame)
+    if args.nms:
+        return nms_operators(args)
     operators(args)
 
 
