@@ -8,8 +8,11 @@ the bev_pool_v2 plugin:
     239-312; det2trt/models/necks/view_transformer.py:8 `LSSViewTransformerTRT` adds nothing to
     them).  Index generation must be BIT-EXACT: same torch ops in the same order; the golden
     (tests/golden/bevdet_geometry.npz) is produced by executing the reference's own methods on the
-    calibration the reference's test hard-codes.  The ranks are computed once per rig on the HOST
-    (the reference feeds them to the engine as inputs, tools/bevdet/evaluate_trt.py:107-127);
+    calibration the reference's test hard-codes.  The reference computes the ranks on the host and
+    feeds them to the engine as inputs (tools/bevdet/evaluate_trt.py:107-127); `forward` takes them the
+    same way.  `forward_calibrated` / `BEVDetRunner` instead build them ON THE DEVICE from the frame's
+    calibration (csrc/lss_prepare.hip), inside the frame's HIP graph: only the twelve 3x3 matrices of
+    `calibration_matrices` are host work;
   * `view_transform` -- the slice of BEVDetTRT.forward_trt between the image neck and the BEV
     encoder (det2trt/models/detector/bevdet.py:50-76): depth_net (1x1 conv) -> softmax over the D
     depth bins -> bev_pool_v2 (HIP) -> [B, C, bev_h, bev_w].
@@ -101,6 +104,102 @@ class LSSViewTransformer(nn.Module):
         """BEVDetTRT.get_bev_pool_input (det2trt/models/detector/bevdet.py:14-27)."""
         coor = self.get_lidar_coor(sensor2keyegos, ego2globals, intrins, post_rots, post_trans, bda)
         return self.voxel_pooling_prepare_v2(coor)
+
+    # ---- the same geometry split for the device index build (functions/lss_prepare.py, csrc/lss_prepare.hip)
+    def calibration_matrices(self, sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda):
+        """The small matrices of get_lidar_coor, by the reference's own torch ops on the host, as ONE packed fp32
+        buffer [N * 24 + 9]: per camera [inverse(post_rots) 9 | post_trans 3 | combine 9 | trans 3] with
+        combine = sensor2ego[:3,:3] @ inverse(cam2imgs), trans = sensor2ego[:3,3]; then bda 9.  Batch 1.
+        `ego2global` is accepted and unused, as in the reference."""
+        B, N, _, _ = sensor2ego.shape
+        if B != 1:
+            raise ValueError("calibration_matrices: batch 1 only (the pooling plugin is batch-1)")
+        sensor2ego, cam2imgs, post_rots, post_trans, bda = (t.detach().to("cpu", torch.float32) for t in
+                                                            (sensor2ego, cam2imgs, post_rots, post_trans, bda))
+        inv_post = torch.inverse(post_rots)                                        # :143
+        combine = sensor2ego[:, :, :3, :3].matmul(torch.inverse(cam2imgs))         # :150
+        per_cam = torch.cat((inv_post.reshape(N, 9), post_trans.reshape(N, 3), combine.reshape(N, 9),
+                             sensor2ego[:, :, :3, 3].reshape(N, 3)), 1)
+        return torch.cat((per_cam.reshape(-1), bda.reshape(-1)[:9])).contiguous()
+
+    def lidar_coor_plain(self, calib):
+        """get_lidar_coor from the packed `calibration_matrices` buffer in plain order: fp32, every product and sum
+        rounded on its own, each 3x3 . 3x1 product summed in ascending k ((m0 p0 + m1 p1) + m2 p2).  This is the
+        arithmetic of the device kernel; on the CPU it equals get_lidar_coor bit for bit.  -> [1, N, D, H, W, 3]."""
+        calib = calib.detach().to("cpu", torch.float32).view(-1)
+        N = (calib.numel() - 9) // 24
+        cam = calib[:N * 24].view(N, 1, 1, 1, 24)
+
+        def mat3(m, p):
+            return torch.stack([(m[..., 3 * r] * p[..., 0] + m[..., 3 * r + 1] * p[..., 1]) + m[..., 3 * r + 2] * p[..., 2]
+                                for r in range(3)], -1)
+        p = self.frustum.to(torch.float32).unsqueeze(0) - cam[..., 9:12]
+        p = mat3(cam[..., 0:9], p)
+        p = torch.stack((p[..., 0] * p[..., 2], p[..., 1] * p[..., 2], p[..., 2]), -1)
+        p = mat3(cam[..., 12:21], p)
+        p = p + cam[..., 21:24]
+        p = mat3(calib[N * 24:].view(1, 1, 1, 1, 9), p)
+        return p.unsqueeze(0).contiguous()
+
+    def prepare_stable(self, coor):
+        """voxel_pooling_prepare_v2 with argsort(stable=True): the CPU / torch statement of what the device build
+        returns.  The reference's argsort leaves the order inside a cell unspecified; here it is ascending point index.
+        Same ranks_bev, interval_starts and interval_lengths; ranks_depth / ranks_feat permuted inside intervals."""
+        B, N, D, H, W, _ = coor.shape
+        num_points = B * N * D * H * W
+        ranks_depth = torch.arange(0, num_points, dtype=torch.int, device=coor.device)
+        ranks_feat = torch.arange(0, num_points // D, dtype=torch.int, device=coor.device)
+        ranks_feat = ranks_feat.reshape(B, N, 1, H, W).expand(B, N, D, H, W).flatten()
+        coor = (coor - self.grid_lower_bound.to(coor)) / self.grid_interval.to(coor)
+        coor = coor.long().view(num_points, 3)
+        batch_idx = torch.arange(0, B).reshape(B, 1).expand(B, num_points // B).reshape(num_points, 1).to(coor)
+        coor = torch.cat((coor, batch_idx), 1)
+        kept = ((coor[:, 0] >= 0) & (coor[:, 0] < self.grid_size[0]) & (coor[:, 1] >= 0)
+                & (coor[:, 1] < self.grid_size[1]) & (coor[:, 2] >= 0) & (coor[:, 2] < self.grid_size[2]))
+        if len(kept) == 0:
+            return None, None, None, None, None
+        coor, ranks_depth, ranks_feat = coor[kept], ranks_depth[kept], ranks_feat[kept]
+        ranks_bev = coor[:, 3] * (self.grid_size[2] * self.grid_size[1] * self.grid_size[0])
+        ranks_bev += coor[:, 2] * (self.grid_size[1] * self.grid_size[0])
+        ranks_bev += coor[:, 1] * self.grid_size[0] + coor[:, 0]
+        order = ranks_bev.argsort(stable=True)
+        ranks_bev, ranks_depth, ranks_feat = ranks_bev[order], ranks_depth[order], ranks_feat[order]
+        kept = torch.ones(ranks_bev.shape[0], device=ranks_bev.device, dtype=torch.bool)
+        kept[1:] = ranks_bev[1:] != ranks_bev[:-1]
+        interval_starts = torch.where(kept)[0].int()
+        if len(interval_starts) == 0:
+            return None, None, None, None, None
+        interval_lengths = torch.zeros_like(interval_starts)
+        interval_lengths[:-1] = interval_starts[1:] - interval_starts[:-1]
+        interval_lengths[-1] = ranks_bev.shape[0] - interval_starts[-1]
+        return (ranks_bev.int().contiguous(), ranks_depth.int().contiguous(), ranks_feat.int().contiguous(),
+                interval_starts.int().contiguous(), interval_lengths.int().contiguous())
+
+    def _frustum_on(self, device):
+        cache = self.__dict__.setdefault("_frustum_dev", {})
+        if device not in cache:
+            cache[device] = self.frustum.to(device, torch.float32).contiguous()
+        return cache[device]
+
+    def prepare_calibrated(self, calib, padded=True):
+        """The five index arrays (+ counts when padded) from the packed calibration buffer ON THE DEVICE `calib` lives
+        on: functions.lss_voxel_prepare with this transformer's frustum and grid."""
+        prepare = getattr(self.ops, "lss_voxel_prepare", _hip_ops.lss_voxel_prepare)   # (an INT8 operator set has none)
+        return prepare(self._frustum_on(calib.device), calib, self.grid_lower_bound, self.grid_interval, self.grid_size,
+                       padded=padded)
+
+    @torch.no_grad()
+    def view_transform_calibrated(self, x, calib):
+        """`view_transform` with the index build on the device: x as there, calib = the packed fp32 buffer of
+        `calibration_matrices` on x's device.  No host synchronisation: capturable with the frame."""
+        rb, rd, rf, ist, il, counts = self.prepare_calibrated(calib)
+        x = self.depth_net(x)
+        depth = x[:, : self.D].softmax(dim=1)
+        tran_feat = x[:, self.D: self.D + self.out_channels].permute(0, 2, 3, 1)
+        depth, tran_feat = depth.contiguous(), tran_feat.contiguous()
+        bev_h, bev_w = int(self.grid_size[1]), int(self.grid_size[0])
+        out = self.ops.bev_pool_v2_indirect(depth, tran_feat, rd, rf, rb, ist, il, counts, bev_h, bev_w)
+        return out.permute(0, 3, 1, 2).contiguous()
 
     @torch.no_grad()
     def view_transform(self, x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths):
@@ -265,6 +364,18 @@ class BEVDet(nn.Module):
         s = _conv(ops, feat, self.shared_conv, True)
         return tuple(_conv(ops, _conv(ops, s, h[0], True), h[1]) for h in (self.heads[k] for k, _ in HEADS_R50))
 
+    def _heads(self, bev):
+        feat = self.bev_encoder(bev)
+        ops = self.ops
+        s = _conv(ops, feat, self.shared_conv, True)
+        return tuple(_conv(ops, _conv(ops, s, h[0], True), h[1]) for h in (self.heads[k] for k, _ in HEADS_R50))
+
+    @torch.no_grad()
+    def forward_calibrated(self, image, calib):
+        """`forward` from the frame's calibration instead of ready-made ranks: calib = the packed fp32 buffer of
+        `view.calibration_matrices` on the image's device; the index build and the pooling run on the device."""
+        x = self.image_features(image.flatten(0, 1))
+        return self._heads(self.view.view_transform_calibrated(x, calib))
 
     # ---- CenterHead.get_bboxes up to the NMS (centerpoint_head.py:716-746), configs/bevdet/bevdet-r50-cbgs.py:138-147
     @property
@@ -312,6 +423,82 @@ class BEVDet(nn.Module):
         return [[out[0][b, :n], out[1][b, :n], out[2][b, :n]] for b, n in enumerate(out[3].tolist())]
 
 
+class BEVDetRunner:
+    """Frame loop of tools/bevdet/evaluate_trt.py:107-140 with the calibration as a per-FRAME input, the BEVDet
+    counterpart of bevformer.FrameRunner: `step` computes the small matrices of the frame's calibration on the host
+    (`calibration_matrices`), copies them into ONE static device buffer (N * 24 + 9 floats: 612 bytes for six cameras)
+    and, with graph=True, replays ONE captured HIP graph that holds the index build, the whole forward and -- post =
+    "candidates" / "bboxes" -- `get_candidates` / `get_bboxes` in their padded forms.  Inside `step` there is no host
+    synchronisation, and a changed calibration needs no new capture.  The upload goes through a small ring of pinned
+    host buffers (an asynchronous copy; a pageable source would make the copy wait for the previous frame): the host
+    only waits when it is a whole ring of frames ahead of the device."""
+    RING = 4
+
+    def __init__(self, model, device, graph=True, post=None, clone_outputs=True):
+        if post not in (None, "candidates", "bboxes"):
+            raise ValueError(f"post = {post!r}: None, 'candidates' or 'bboxes'")
+        self.model, self.device, self.use_graph, self.post, self.clone_outputs = model, device, graph, post, clone_outputs
+        dtype = next(model.parameters()).dtype
+        H, W = view_input_size(model.view)
+        self.n_cams = None
+        self._image_shape, self._dtype = (3, H, W), dtype
+        self._in, self._graph, self._outs = None, None, None
+        self._ring, self._frame = None, 0
+
+    @property
+    def image_buffer(self):
+        """The static [1, cams, 3, H, W] input buffer (after the first `step`): a caller that writes its images here
+        and passes this very tensor to `step` saves the per-frame copy."""
+        return None if self._in is None else self._in["image"]
+
+    def _forward(self):
+        out = self.model.forward_calibrated(self._in["image"], self._in["calib"])
+        if self.post == "candidates":
+            return out + tuple(self.model.get_candidates(out, padded=True))
+        if self.post == "bboxes":
+            return out + tuple(self.model.get_bboxes(out, padded=True))
+        return out
+
+    def _capture(self):
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):       # warm-up on the capture stream (allocations, library algorithm search)
+            for _ in range(2):
+                self._forward()
+        torch.cuda.current_stream().wait_stream(s)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self._outs = self._forward()
+
+    def step(self, image, sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda):
+        """-> (reg, height, dim, rot, vel, heatmap) of `BEVDet.forward`, followed by the padded outputs of
+        `get_candidates` (post="candidates") or `get_bboxes` (post="bboxes")."""
+        host = self.model.view.calibration_matrices(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
+        if self._in is None:
+            self.n_cams = sensor2ego.shape[1]
+            self._in = dict(image=torch.zeros((1, self.n_cams) + self._image_shape, device=self.device, dtype=self._dtype),
+                            calib=torch.zeros(host.numel(), device=self.device))
+            self._ring = [(torch.zeros(host.numel()).pin_memory(), torch.cuda.Event()) for _ in range(self.RING)]
+        i = self._in
+        if host.numel() != i["calib"].numel():
+            raise ValueError("the number of cameras is fixed by the first frame")
+        if image.data_ptr() != i["image"].data_ptr():      # (the caller may have filled the static buffer itself)
+            i["image"].copy_(image, non_blocking=True)
+        staged, done = self._ring[self._frame % self.RING]
+        self._frame += 1
+        done.synchronize()                                  # (returns at once unless the host is RING frames ahead)
+        staged.copy_(host)
+        with torch.cuda.device(self.device):
+            i["calib"].copy_(staged, non_blocking=True)     # one upload
+            done.record()
+        if self.use_graph:
+            if self._graph is None:
+                self._capture()
+            self._graph.replay()
+            return tuple(t.clone() for t in self._outs) if self.clone_outputs else self._outs
+        return self._forward()
+
+
 def synthetic_rig(view, n_cams=6, seed=0):
     """A plausible six-camera calibration for timing and tests (no nuScenes data here): cameras on a ring, 60 degrees
     apart, looking outwards, the resize / crop augmentation of the test pipeline as post_rots / post_trans.
@@ -336,6 +523,28 @@ def synthetic_rig(view, n_cams=6, seed=0):
     post_trans = torch.zeros(1, n_cams, 3)
     post_trans[..., 1] = -(900.0 * scale - H)
     bda = torch.eye(3).view(1, 3, 3)
+    return s2e, e2g, K, post_rots, post_trans, bda
+
+
+def jittered_rig(view, seed, n_cams=6):
+    """`synthetic_rig` perturbed the way real BEVDet input varies from sample to sample: camera translation and
+    focal length (another vehicle), a yawed, scaled and possibly flipped `bda` (the per-sample BEV augmentation), a
+    resize and crop offset in post_rots / post_trans (the per-image augmentation).  Deterministic in `seed`."""
+    import math
+    s2e, e2g, K, post_rots, post_trans, bda = synthetic_rig(view, n_cams)
+    g = torch.Generator().manual_seed(1000 + seed)
+    r = lambda *shape: torch.rand(*shape, generator=g) * 2 - 1
+    s2e[0, :, :3, 3] += 0.05 * r(n_cams, 3)
+    K[0, :, 0, 0] *= 1 + 0.02 * r(n_cams)
+    K[0, :, 1, 1] = K[0, :, 0, 0]
+    K[0, :, :2, 2] += 5.0 * r(n_cams, 2)
+    post_rots[0, :, :2, :2] *= (1 + 0.06 * r(n_cams)).view(n_cams, 1, 1)
+    post_trans[0, :, 0] -= 10.0 * (1 + r(n_cams))
+    post_trans[0, :, 1] += 4.0 * r(n_cams)
+    yaw, scale = math.radians(22.5) * float(r(1)), 1 + 0.05 * float(r(1))
+    rot = torch.tensor([[math.cos(yaw), -math.sin(yaw), 0.0], [math.sin(yaw), math.cos(yaw), 0.0], [0.0, 0.0, 1.0]])
+    flip = torch.diag(torch.tensor([-1.0 if seed % 2 else 1.0, -1.0 if seed % 3 == 0 else 1.0, 1.0]))
+    bda = (flip @ (rot * scale)).view(1, 3, 3)
     return s2e, e2g, K, post_rots, post_trans, bda
 
 

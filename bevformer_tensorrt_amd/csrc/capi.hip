@@ -59,6 +59,9 @@ const Entry kTable[] = {
     {"bevops_bev_nms", (void *)&bevops_bev_nms},
     {"bevops_bev_nms_workspace_size", (void *)&bevops_bev_nms_workspace_size},
     {"bevops_bev_iou", (void *)&bevops_bev_iou},
+    {"bevops_lss_voxel_prepare", (void *)&bevops_lss_voxel_prepare},
+    {"bevops_lss_voxel_prepare_workspace_size", (void *)&bevops_lss_voxel_prepare_workspace_size},
+    {"bevops_bev_pool_v2_forward_indirect", (void *)&bevops_bev_pool_v2_forward_indirect},
     // entries that are not reference plugins: workspace-lending / channels-last / fused forms
     {"bevops_grid_sampler_2d_forward_ws", (void *)&bevops_grid_sampler_2d_forward_ws},
     {"bevops_grid_sampler_2d_workspace_size", (void *)&bevops_grid_sampler_2d_workspace_size},

@@ -814,6 +814,59 @@ int bevops_bev_nms(int mode, const float *boxes_in, const float *scores_in, cons
                    size_t workspace_bytes, void *stream);
 int bevops_bev_iou(const float *boxes_a, int num_a, const float *boxes_b, int num_b, float *iou, void *stream);
 
+/* ------------------------------------------------------------------------
+ * BEVDet view-transformer index build (csrc/lss_prepare.hip): LSSViewTransformer.get_lidar_coor followed by
+ * voxel_pooling_prepare_v2 (third_party/bev_mmdet3d/models/necks/view_transformer.py:126-168, 239-312) on the device,
+ * with fixed-size outputs and no host round trip (capturable), so the five index arrays of bev_pool_v2 can follow the
+ * calibration of every frame.
+ *
+ * bevops_lss_voxel_prepare.
+ *   frustum [d, h, w, 3] F32 (device): the (u, v, depth) image-plane points of create_frustum.
+ *   calib (device, F32, n_cams * 24 + 9 values): per camera [inverse(post_rots) 9 | post_trans 3 | combine 9 | trans 3]
+ *   with combine = sensor2ego[:3,:3] @ inverse(cam2imgs) and trans = sensor2ego[:3,3], then bda 9; 3x3 row-major.
+ *   The small matrices are the caller's (host) work.
+ *   grid_host[9] (host, F32) = lower bound, interval, size of (x, y, z) as create_grid_infos holds them.
+ * ARITHMETIC, per frustum point of camera n, F32, every product and sum rounded on its own, each 3x3 . 3x1 product
+ *   summed in ascending k ((m0 p0 + m1 p1) + m2 p2), no contraction -- bit-equal to get_lidar_coor on the CPU:
+ *   p = frustum - post_trans; p = inverse(post_rots) . p; p = (p.x p.z, p.y p.z, p.z); p = combine . p; p += trans;
+ *   coor = bda . p.  coor (NULL or [n_cams, d, h, w, 3] F32) receives these coordinates.
+ * CELL: q = (coor - lower) / interval, IEEE division; t = trunc(q), toward zero as `.long()` does (a quotient in
+ *   (-1, 0) lands in cell 0); the point is kept when 0 <= t < size on all three axes, tested on the truncated FLOAT, so
+ *   a non-finite quotient or one beyond the int32 range drops the point and never becomes an address;
+ *   cell = z (ny nx) + y nx + x.
+ * ORDER: kept points ascending by cell; inside a cell ascending by point index (the stable sort: a valid reading of
+ *   the reference's argsort, whose order among equal keys is unspecified, and the rule that makes the arrays unique).
+ *   Intervals are the run-length encoding of the sorted cells.
+ * OUTPUTS, int32, fixed capacity: ranks_bev, ranks_depth (= point index ((n d + i) h + j) w + k), ranks_feat
+ *   (= (ranks_depth / (d h w)) (h w) + ranks_depth % (h w)): num_points = n_cams d h w entries each; interval_starts,
+ *   interval_lengths: min(num_points, cells) entries each; counts[2] = {n_points, n_intervals}.  Entries at and behind
+ *   the counts are zero.  No kept point: counts = {0, 0}, all arrays zero, BEVOPS_SUCCESS.
+ *   Bit-reproducible: atomics only produce digit counts, never an order.
+ * LIMITS, checked before any device call: NULL pointers (coor excepted), non-positive counts, a workspace shorter than
+ *   bevops_lss_voxel_prepare_workspace_size(n_cams, d, h, w) or not 16-byte aligned, a non-finite lower bound, a
+ *   non-finite or non-positive interval, a size that is non-finite or below 1: BEVOPS_BAD_PARAM.  batch != 1
+ *   (the pooling plugin is batch-1), num_points > 4 194 304 (2^22), a non-integral size, cells = nx ny nz >
+ *   16 777 216 (2^24): BEVOPS_NOT_SUPPORTED (the workspace size is 0 for such shapes).
+ *   Launches: 1 (cells + first digit counts) + 2 or 3 per 8-bit digit of `cells` (two digits up to 65 535 cells) + 4
+ *   (run starts, scan, emit, lengths); none sized by a device value.
+ *
+ * bevops_bev_pool_v2_forward_indirect: bevops_bev_pool_v2_forward with the interval count read on the device:
+ *   n_intervals_dev[0] (clamped to [0, max_intervals]); max_intervals, a host value, sizes the grid and is the
+ *   capacity of interval_starts / interval_lengths.  Same kernels and per-interval arithmetic: for equal index arrays
+ *   the output is bit-identical to bevops_bev_pool_v2_forward in F32, F16 and I8.
+ * ------------------------------------------------------------------------ */
+size_t bevops_lss_voxel_prepare_workspace_size(int n_cams, int d, int h, int w);
+int bevops_lss_voxel_prepare(const float *frustum, const float *calib, const float *grid_host, int32_t *ranks_bev,
+                             int32_t *ranks_depth, int32_t *ranks_feat, int32_t *interval_starts,
+                             int32_t *interval_lengths, int32_t *counts, float *coor, int batch, int n_cams, int d,
+                             int h, int w, void *workspace, size_t workspace_bytes, void *stream);
+int bevops_bev_pool_v2_forward_indirect(int dtype, const void *depth, const void *feat, const int32_t *ranks_depth,
+                                        const int32_t *ranks_feat, const int32_t *ranks_bev,
+                                        const int32_t *interval_starts, const int32_t *interval_lengths,
+                                        const int32_t *n_intervals_dev, void *output, int channels, int max_intervals,
+                                        int out_height, int out_width, float scale_depth, float scale_feat,
+                                        float scale_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
