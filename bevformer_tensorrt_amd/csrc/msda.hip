@@ -22,6 +22,8 @@
 //     (cameras that do not see a BEV pillar).
 //   * blockIdx is remapped so each XCD walks a contiguous item range (L2 locality
 //     for neighbouring BEV queries).
+#include <initializer_list>
+
 #include "msda_common.h"
 
 namespace bevops {
@@ -505,157 +507,226 @@ __global__ __launch_bounds__(kBlock) void msda_generic_int8_kernel(
   }
 }
 
-thread_local int g_variant = 0;
-
+// T: float / __half; value, ref, off, logit, out of the call are T tensors
 template <typename T, int PPL, int CH>
-int launch_quad(const T *value, const int32_t *shapes, const T *ref, const T *off, const T *logit,
-                T *out, const MsdaDims &d, hipStream_t st) {
-  const size_t n_item = (size_t)d.bs * d.nq * d.heads;
-  const size_t vbytes = (size_t)d.bs * d.nk * d.heads * d.C * sizeof(T);
+int launch_quad(const MsdaCall &c) {
+  const size_t n_item = c.d.n_item();
+  const size_t vbytes = c.d.value_elems() * sizeof(T);
   const unsigned grid = (unsigned)((n_item + kBlock / 4 - 1) / (kBlock / 4));
-  hipLaunchKernelGGL((msda_quad_kernel<T, PPL, CH>), dim3(grid), dim3(kBlock), 0, st, value,
-                     (unsigned)vbytes, shapes, ref, off, logit, out, d, (unsigned)n_item);
+  hipLaunchKernelGGL((msda_quad_kernel<T, PPL, CH>), dim3(grid), dim3(kBlock), 0, c.st, (const T *)c.value,
+                     (unsigned)vbytes, c.shapes, (const T *)c.ref, (const T *)c.off, (const T *)c.logit, (T *)c.out, c.d,
+                     (unsigned)n_item);
   return launch_status();
 }
 
+inline bool quad_aligned(const MsdaCall &c) {
+  return aligned16(c.value) && aligned16(c.off) && aligned16(c.logit) && aligned16(c.out) && aligned16(c.ref);
+}
+
 template <typename T>
-int msda_float(const T *value, const int32_t *shapes, const T *ref, const T *off, const T *logit,
-               T *out, const MsdaDims &d, hipStream_t st) {
-  const size_t n_item = (size_t)d.bs * d.nq * d.heads;
-  const size_t vbytes = (size_t)d.bs * d.nk * d.heads * d.C * sizeof(T);
+int msda_float(const MsdaCall &c, MsdaFamily family) {
+  const MsdaDims &d = c.d;
+  const size_t n_item = d.n_item();
+  const size_t vbytes = d.value_elems() * sizeof(T);
   const int LP = d.L * d.P;
   const bool quad_ok = d.C == 32 && LP % 4 == 0 && d.L <= kMaxLevels &&
                        vbytes < 0xFFFFFF00ull && n_item < 0x7FFFFFFFull &&
-                       n_item * 32 * sizeof(T) < 0xFFFFFFFFFFull && aligned16(value) &&
-                       aligned16(off) && aligned16(logit) && aligned16(out) && aligned16(ref) &&
-                       g_variant != 99;
+                       n_item * 32 * sizeof(T) < 0xFFFFFFFFFFull && quad_aligned(c) && family != kMsdaGeneric;
   if (quad_ok) {
-    const int v = g_variant;
+    const bool split2 = family == kMsdaQuad2, split8 = family == kMsdaQuad8;
     switch (LP / 4) {
-      case 1: return launch_quad<T, 1, 1>(value, shapes, ref, off, logit, out, d, st);
-      case 2: return launch_quad<T, 2, 2>(value, shapes, ref, off, logit, out, d, st);
+      case 1: return launch_quad<T, 1, 1>(c);
+      case 2: return launch_quad<T, 2, 2>(c);
       case 4:
-        if (v == 2) return launch_quad<T, 4, 2>(value, shapes, ref, off, logit, out, d, st);
-        return launch_quad<T, 4, 4>(value, shapes, ref, off, logit, out, d, st);
+        if (split2) return launch_quad<T, 4, 2>(c);
+        return launch_quad<T, 4, 4>(c);
       case 8:
-        if (v == 1) return launch_quad<T, 8, 8>(value, shapes, ref, off, logit, out, d, st);
-        if (v == 2) return launch_quad<T, 8, 2>(value, shapes, ref, off, logit, out, d, st);
-        return launch_quad<T, 8, 4>(value, shapes, ref, off, logit, out, d, st);
+        if (split8) return launch_quad<T, 8, 8>(c);
+        if (split2) return launch_quad<T, 8, 2>(c);
+        return launch_quad<T, 8, 4>(c);
       case 16:
-        if (v == 2) return launch_quad<T, 16, 2>(value, shapes, ref, off, logit, out, d, st);
-        return launch_quad<T, 16, 4>(value, shapes, ref, off, logit, out, d, st);
+        if (split2) return launch_quad<T, 16, 2>(c);
+        return launch_quad<T, 16, 4>(c);
       default: break;
     }
   }
   const size_t n_out = n_item * d.C;
   const size_t grid = (n_out + kBlock - 1) / kBlock;
   if (grid > 0x7FFFFFFFull) return BEVOPS_NOT_SUPPORTED;
-  hipLaunchKernelGGL((msda_generic_kernel<T>), dim3((unsigned)grid), dim3(kBlock), 0, st, value,
-                     shapes, ref, off, logit, out, d, n_out);
+  hipLaunchKernelGGL((msda_generic_kernel<T>), dim3((unsigned)grid), dim3(kBlock), 0, c.st, (const T *)c.value,
+                     c.shapes, (const T *)c.ref, (const T *)c.off, (const T *)c.logit, (T *)c.out, d, n_out);
   return launch_status();
 }
 
 template <typename RefT, bool U8W, int PPL, int CH>
-int launch_quad_i8(const int8_t *value, const int32_t *shapes, const RefT *ref, const int8_t *off,
-                   const int8_t *logit, int8_t *out, const MsdaDims &d, float s_v, float s_o,
-                   float s_w, float s_out, hipStream_t st) {
-  const size_t n_item = (size_t)d.bs * d.nq * d.heads;
-  const size_t vbytes = (size_t)d.bs * d.nk * d.heads * d.C;
+int launch_quad_i8(const MsdaCall &c) {
+  const size_t n_item = c.d.n_item();
   const unsigned grid = (unsigned)((n_item + kBlock / 4 - 1) / (kBlock / 4));
-  hipLaunchKernelGGL((msda_quad_int8_kernel<RefT, PPL, CH, U8W>), dim3(grid), dim3(kBlock), 0, st,
-                     value, (unsigned)vbytes, shapes, ref, off, logit, out, d, (unsigned)n_item, s_v,
-                     s_o, s_w, s_out);
+  hipLaunchKernelGGL((msda_quad_int8_kernel<RefT, PPL, CH, U8W>), dim3(grid), dim3(kBlock), 0, c.st,
+                     (const int8_t *)c.value, (unsigned)c.d.value_elems(), c.shapes, (const RefT *)c.ref,
+                     (const int8_t *)c.off, (const int8_t *)c.logit, (int8_t *)c.out, c.d, (unsigned)n_item, c.s_v,
+                     c.s_o, c.s_w, c.s_out);
   return launch_status();
 }
 
 template <typename RefT, bool U8W>
-int msda_int8(const int8_t *value, const int32_t *shapes, const RefT *ref, const int8_t *off,
-              const int8_t *logit, int8_t *out, const MsdaDims &d, float s_v, float s_o, float s_w,
-              float s_out, hipStream_t st) {
-  const size_t n_item = (size_t)d.bs * d.nq * d.heads;
-  const size_t vbytes = (size_t)d.bs * d.nk * d.heads * d.C;
+int msda_int8(const MsdaCall &c, MsdaFamily family) {
+  const MsdaDims &d = c.d;
+  const size_t n_item = d.n_item();
   const int LP = d.L * d.P;
-  const bool quad_ok = d.C == 32 && LP % 4 == 0 && d.L <= kMaxLevels && vbytes < 0xFFFFFF00ull &&
-                       n_item < 0x7FFFFFFFull && aligned16(value) && aligned16(off) &&
-                       aligned16(logit) && aligned16(out) && aligned16(ref) && g_variant != 99;
+  const bool quad_ok = d.C == 32 && LP % 4 == 0 && d.L <= kMaxLevels && d.value_elems() < 0xFFFFFF00ull &&
+                       n_item < 0x7FFFFFFFull && quad_aligned(c) && family != kMsdaGeneric;
   if (quad_ok) {
     switch (LP / 4) {
-      case 1: return launch_quad_i8<RefT, U8W, 1, 1>(value, shapes, ref, off, logit, out, d, s_v, s_o, s_w, s_out, st);
-      case 2: return launch_quad_i8<RefT, U8W, 2, 2>(value, shapes, ref, off, logit, out, d, s_v, s_o, s_w, s_out, st);
-      case 4: return launch_quad_i8<RefT, U8W, 4, 4>(value, shapes, ref, off, logit, out, d, s_v, s_o, s_w, s_out, st);
-      case 8: return launch_quad_i8<RefT, U8W, 8, 4>(value, shapes, ref, off, logit, out, d, s_v, s_o, s_w, s_out, st);
-      case 16: return launch_quad_i8<RefT, U8W, 16, 4>(value, shapes, ref, off, logit, out, d, s_v, s_o, s_w, s_out, st);
+      case 1: return launch_quad_i8<RefT, U8W, 1, 1>(c);
+      case 2: return launch_quad_i8<RefT, U8W, 2, 2>(c);
+      case 4: return launch_quad_i8<RefT, U8W, 4, 4>(c);
+      case 8: return launch_quad_i8<RefT, U8W, 8, 4>(c);
+      case 16: return launch_quad_i8<RefT, U8W, 16, 4>(c);
       default: break;
     }
   }
   const size_t n_out = n_item * d.C;
   const size_t grid = (n_out + kBlock - 1) / kBlock;
   if (grid > 0x7FFFFFFFull) return BEVOPS_NOT_SUPPORTED;
-  hipLaunchKernelGGL((msda_generic_int8_kernel<RefT, U8W>), dim3((unsigned)grid), dim3(kBlock), 0,
-                     st, value, shapes, ref, off, logit, out, d, n_out, s_v, s_o, s_w, s_out);
+  hipLaunchKernelGGL((msda_generic_int8_kernel<RefT, U8W>), dim3((unsigned)grid), dim3(kBlock), 0, c.st,
+                     (const int8_t *)c.value, c.shapes, (const RefT *)c.ref, (const int8_t *)c.off,
+                     (const int8_t *)c.logit, (int8_t *)c.out, d, n_out, c.s_v, c.s_o, c.s_w, c.s_out);
   return launch_status();
 }
 
 }  // namespace
+
+thread_local MsdaSelection g_msda_sel;
+
 }  // namespace bevops
 
 using namespace bevops;
 
-static thread_local bool g_sca_direct = true;   // bevops_sca_forward_planned: see set_variant 3012 / 3013
-static thread_local int g_variant_raw = 0;   // the value last REQUESTED (19 maps to 17 + a flag below)
+// The ONLY place that knows what a variant number means (the list: include/bevops.h).
 extern "C" int bevops_msda_set_variant(int variant) {
-  const int prev = g_variant_raw;   // handing this back to set_variant restores the flags too
+  MsdaSelection &s = g_msda_sel;
+  const int prev = s.raw;   // handing this back to set_variant restores the family and its flag
   // The 30xx values are independent knobs of the fused SCA op, NOT kernel-family selectors: they leave the family
-  // selection (g_variant / g_variant_raw) alone, so a save / restore pair around a family switch -- prev =
-  // set_variant(10); ...; set_variant(prev) -- still restores the family after any 30xx call in between.
+  // selection alone, so a save / restore pair around a family switch -- prev = set_variant(10); ...;
+  // set_variant(prev) -- still restores the family after any 30xx call in between.
   if (variant >= 3001 && variant <= 3008) {   // A/B: slices per CU of the planned fused SCA sampling (default 2)
-    msda_hm5_set_plan_blocks(variant - 3000);
+    s.sca_plan_blocks = variant - 3000;   // 1 .. 8: the range above is the clamp
     return prev;
   }
-  if (variant == 3010 || variant == 3011) {   // A/B: camera reduce of the fused SCA op unrolled (default) / rolled
-    msda_sca_set_reduce_rolled(variant == 3011);
-    return prev;
+  switch (variant) {
+    case 3010: case 3011:   // A/B: camera reduce of the fused SCA op unrolled (default) / rolled
+      s.sca_reduce_rolled = variant == 3011;
+      return prev;
+    case 3012: case 3013:   // A/B: planned SCA stores single-camera pairs into the output (default) / not
+      s.sca_direct = variant == 3012;
+      return prev;
+    case 3014: case 3015:   // A/B: planned SCA sampler with the record broadcasts folded into their consumers + fused
+      s.sca_fold = variant == 3014;   // LDS row taps (3014, default) / the round-5 build (3015)
+      return prev;
+    default: break;
   }
-  if (variant == 3012 || variant == 3013) {   // A/B: planned SCA stores single-camera pairs into the output (default) / not
-    g_sca_direct = variant == 3012;
-    return prev;
+  s.raw = variant;
+  s.h4_one_block = variant == 19;   // A/B: int8 hm4 on the one-block-per-CU plan (the partner of the default)
+  switch (variant) {
+    case 1: s.family = kMsdaQuad8; break;
+    case 2: s.family = kMsdaQuad2; break;
+    case 10: s.family = kMsdaNoHeadMajor; break;
+    case 11: s.family = kMsdaHm; break;
+    case 15: s.family = kMsdaHm2; break;
+    case 16: s.family = kMsdaHm3; break;
+    case 17: case 19: s.family = kMsdaHm4; break;   // hm4 wherever it is instantiated
+    case 99: s.family = kMsdaGeneric; break;
+    case 1000: s.family = kMsdaHm5; break;
+    case 1001: s.family = kMsdaHm5NoPrepass; break;
+    default: s.family = kMsdaAuto; break;   // 0 and every value the header does not list
   }
-  if (variant == 3014 || variant == 3015) {   // A/B: planned SCA sampler with the record broadcasts folded into their
-    msda_hm5_set_fold(variant == 3014);       // consumers + fused LDS row taps (3014, default) / the round-5 build (3015)
-    return prev;
-  }
-  g_variant_raw = variant;
-  // 19 (A/B): int8 hm4 on the one-block-per-CU plan (the partner of the default two-blocks plan); g_variant then
-  // reads 17 = "hm4 wherever it is instantiated"
-  msda_hm4_set_no_occ(variant == 19);
-  g_variant = variant == 19 ? 17 : variant;
   return prev;
 }
 
 // A head-major re-layout pays when a batch's maps overflow an XCD's 4 MiB L2 and there are enough
 // samples per pixel to amortise it (profiles/r01: base SCA 1.75x, base TSA 1.1x; small / tiny
 // maps are L2-resident already and stay on the layout-preserving kernels)
-static bool hm_pays(int esize, int bs, int nk, int heads, int channels, int num_levels, int num_query,
-                    int num_point) {
-  const double samples = (double)bs * num_query * heads * num_levels * num_point;
-  const double pixels = (double)bs * nk * heads;
-  const double plane_mb = (double)nk * heads * channels * esize / 1048576.0;
+static bool hm_pays(int esize, const MsdaDims &d) {
+  const double samples = (double)d.bs * d.nq * d.heads * d.L * d.P;
+  const double pixels = (double)d.bs * d.nk * d.heads;
+  const double plane_mb = (double)d.nk * d.heads * d.C * esize / 1048576.0;
   return (samples >= 16.0 * pixels && plane_mb >= 4.0) || (samples >= 4.0 * pixels && plane_mb >= 16.0);
+}
+
+// Which head-major families serve a call, in the order they are tried; behind them come the layout-preserving quad
+// and generic kernels (msda_float / msda_int8), which take every call.  A family returns BEVOPS_NOT_SUPPORTED for a
+// call outside its domain and the next candidate is tried -- unless the pick is `forced` (set_variant named that
+// family): then its status goes back to the caller.  `host_shapes`: the caller has (or, for a size query, will have)
+// the level shapes on the host; `shapes_host` itself may be null in a size query.
+struct MsdaOrder {
+  int n = 0;
+  struct { MsdaFamily family; bool forced; } pick[4];
+  void add(MsdaFamily family, bool forced) { pick[n].family = family; pick[n].forced = forced; ++n; }
+};
+static MsdaOrder msda_head_major_order(int dtype, const MsdaDims &d, const int32_t *shapes_host, bool host_shapes,
+                                       bool workspace, const MsdaSelection &sel) {
+  MsdaOrder o;
+  const MsdaFamily f = sel.family;
+  // a head-major path needs a workspace the caller lends
+  if (!workspace || f == kMsdaNoHeadMajor || f == kMsdaGeneric) return o;
+  if (dtype == BEVOPS_I8) {
+    // head-major int8 path (msda_hm4.hip); naming hm4 applies it wherever it is instantiated, but its NOT_SUPPORTED
+    // still falls back to the layout-preserving kernels
+    if (host_shapes && (f == kMsdaHm4 || hm_pays(1, d))) o.add(kMsdaHm4, false);
+    return o;
+  }
+  if (dtype != BEVOPS_F16 || f == kMsdaQuad8 || f == kMsdaQuad2) return o;
+  const bool automatic = f == kMsdaAuto;
+  const bool pays = hm_pays(2, d);
+  if (host_shapes) {
+    // hm4 (software-pipelined, msda_hm4.hip): fp16 default where every pyramid level is
+    // LDS-resident (tiny / small SCA: 106 vs 142 us at small SCA); for the base SCA call hm3 and
+    // hm4 are level (571 vs 579 us kernel, profiles/r02) and hm3 stays
+    if (f == kMsdaHm4 || (automatic && d.nq >= 8192 && msda_hm4_all_staged(d, shapes_host))) o.add(kMsdaHm4, !automatic);
+    // hm5 (msda_hm5.hip): hm3's planes, re-scheduled, plus the exact visibility pre-pass; default
+    // for the 4-level x 8-point SCA shape
+    if (f == kMsdaHm5 || f == kMsdaHm5NoPrepass || (automatic && pays)) o.add(automatic ? kMsdaHm5 : f, !automatic);
+    if (f == kMsdaHm3 || (automatic && pays && d.L * d.P >= 16)) o.add(kMsdaHm3, !automatic);
+  }
+  // msda_hm.hip (hm / hm2: it splits them by L*P unless one is named); also what a family that needs the host shapes
+  // falls back to when the call is big enough
+  if (f == kMsdaHm || f == kMsdaHm2 || pays) o.add(kMsdaHm, false);
+  return o;
+}
+
+// the two validation rules of the entries below (BEVOPS_BAD_PARAM): every required pointer non-null and every dim
+// positive; every level H, W > 0 and the levels cover exactly nk pixels
+static bool all_given(std::initializer_list<const void *> ptrs, std::initializer_list<int> dims) {
+  for (const void *p : ptrs)
+    if (!p) return false;
+  for (int v : dims)
+    if (v <= 0) return false;
+  return true;
+}
+static bool shapes_cover(const int32_t *shapes_host, int num_levels, int nk) {
+  long total = 0;
+  for (int l = 0; l < num_levels; ++l) {
+    const long H = shapes_host[2 * l], W = shapes_host[2 * l + 1];
+    if (H <= 0 || W <= 0) return false;
+    total += H * W;
+  }
+  return total == nk;
 }
 
 extern "C" size_t bevops_msda_workspace_size(int dtype, int bs, int nk, int heads, int channels,
                                              int num_levels, int num_query, int num_point) {
-  if (bs <= 0 || nk <= 0 || heads <= 0 || num_levels <= 0 || num_query <= 0 || num_point <= 0) return 0;
+  if (!all_given({}, {bs, nk, heads, num_levels, num_query, num_point})) return 0;
   if ((num_levels * num_point) % 4 != 0) return 0;
+  const MsdaDims d{bs, nk, heads, channels, num_levels, num_query, num_point, 0, 0};
   if (dtype == BEVOPS_I8) {
     // padded head-major int8 planes (msda_hm4.hip): 128-byte entries, at most (H + 2)(W + 1) <= 3 H W
     // + 2 of them per level -- an upper bound; bevops_msda_workspace_size_shapes gives the exact size
-    if (channels != 32 || g_variant == 10 || g_variant == 99) return 0;
-    if (g_variant != 17 && !hm_pays(1, bs, nk, heads, channels, num_levels, num_query, num_point)) return 0;
+    if (channels != 32 || msda_head_major_order(dtype, d, nullptr, true, true, g_msda_sel).n == 0) return 0;
     return (size_t)bs * heads * ((size_t)3 * nk + 2 * num_levels + 4) * 128 + 4096;
   }
   if (dtype != BEVOPS_F16) return 0;
-  return msda_hm_workspace_bytes(bs, nk, heads, channels, num_levels);
+  return msda_hm_workspace_bytes(d);
 }
 
 extern "C" size_t bevops_msda_workspace_size_shapes(int dtype, const int32_t *spatial_shapes_host,
@@ -664,14 +735,12 @@ extern "C" size_t bevops_msda_workspace_size_shapes(int dtype, const int32_t *sp
   const size_t a = bevops_msda_workspace_size(dtype, bs, nk, heads, channels, num_levels, num_query,
                                               num_point);
   if (a == 0 || !spatial_shapes_host) return a;
-  const size_t c = msda_hm4_workspace_bytes(spatial_shapes_host, bs, heads, channels, num_levels,
-                                            num_query, num_point, dtype == BEVOPS_I8);
+  const MsdaDims d{bs, nk, heads, channels, num_levels, num_query, num_point, 0, 0};
+  const size_t c = msda_hm4_workspace_bytes(d, spatial_shapes_host, dtype == BEVOPS_I8);
   if (dtype == BEVOPS_I8) return c;   // exact (0: shape outside the head-major domain)
   if (dtype != BEVOPS_F16) return a;
-  size_t b = msda_hm3_workspace_bytes(spatial_shapes_host, bs, heads, channels, num_levels,
-                                      num_query, num_point);
-  const size_t e = msda_hm5_workspace_bytes(spatial_shapes_host, bs, heads, channels, num_levels, num_query,
-                                            num_point);
+  size_t b = msda_hm3_workspace_bytes(d, spatial_shapes_host);
+  const size_t e = msda_hm5_workspace_bytes(d, spatial_shapes_host);
   if (e > b) b = e;
   return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
@@ -679,29 +748,24 @@ extern "C" size_t bevops_msda_workspace_size_shapes(int dtype, const int32_t *sp
 extern "C" size_t bevops_msda_packed_size(int dtype, const int32_t *spatial_shapes_host, int bs, int nk,
                                           int heads, int channels, int num_levels, int num_query,
                                           int num_point) {
-  if ((dtype != BEVOPS_F16 && dtype != BEVOPS_I8) || !spatial_shapes_host || bs <= 0 || nk <= 0 || heads <= 0 ||
-      num_levels <= 0 || num_query <= 0 || num_point <= 0)
+  if ((dtype != BEVOPS_F16 && dtype != BEVOPS_I8) ||
+      !all_given({spatial_shapes_host}, {bs, nk, heads, num_levels, num_query, num_point}))
     return 0;
-  return msda_hm4_workspace_bytes(spatial_shapes_host, bs, heads, channels, num_levels, num_query, num_point,
-                                  dtype == BEVOPS_I8);
+  return msda_hm4_workspace_bytes(MsdaDims{bs, nk, heads, channels, num_levels, num_query, num_point, 0, 0},
+                                  spatial_shapes_host, dtype == BEVOPS_I8);
 }
 
 extern "C" int bevops_msda_pack_value(int dtype, int ref_dtype, const void *value,
                                       const int32_t *spatial_shapes_host, void *packed, size_t packed_bytes,
                                       int bs, int nk, int heads, int channels, int num_levels, int num_query,
                                       int num_point, void *stream) {
-  if (!value || !spatial_shapes_host || !packed) return BEVOPS_BAD_PARAM;
-  if (bs <= 0 || nk <= 0 || heads <= 0 || channels <= 0 || num_levels <= 0 || num_query <= 0 || num_point <= 0)
+  if (!all_given({value, spatial_shapes_host, packed}, {bs, nk, heads, channels, num_levels, num_query, num_point}) ||
+      !shapes_cover(spatial_shapes_host, num_levels, nk))
     return BEVOPS_BAD_PARAM;
-  long total = 0;
-  for (int l = 0; l < num_levels; ++l) {
-    const long H = spatial_shapes_host[2 * l], W = spatial_shapes_host[2 * l + 1];
-    if (H <= 0 || W <= 0) return BEVOPS_BAD_PARAM;
-    total += H * W;
-  }
-  if (total != nk) return BEVOPS_BAD_PARAM;
-  return msda_hm4_pack(dtype, ref_dtype, value, spatial_shapes_host, bs, nk, heads, channels, num_levels,
-                       num_query, num_point, packed, packed_bytes, static_cast<hipStream_t>(stream));
+  const MsdaCall c{{bs, nk, heads, channels, num_levels, num_query, num_point, 0, 0},
+                   value, nullptr, nullptr, nullptr, nullptr, nullptr, dtype, ref_dtype, 1.f, 1.f, 1.f, 1.f,
+                   nullptr, spatial_shapes_host, packed, packed_bytes, static_cast<hipStream_t>(stream)};
+  return msda_hm4_pack(c);
 }
 
 extern "C" int bevops_msda_forward_prepacked(int dtype, const void *packed, size_t packed_bytes,
@@ -712,30 +776,37 @@ extern "C" int bevops_msda_forward_prepacked(int dtype, const void *packed, size
                                              int num_point, int points_per_group, float scale_value,
                                              float scale_offset, float scale_weight, float scale_out,
                                              int shared_offsets, void *stream) {
-  if (!packed || !spatial_shapes_host || !reference_points || !sampling_offsets || !attention_weights || !output)
-    return BEVOPS_BAD_PARAM;
-  if (bs <= 0 || nk <= 0 || heads <= 0 || channels <= 0 || num_levels <= 0 || num_query <= 0 ||
-      num_point <= 0 || points_per_group <= 0)
+  if (!all_given({packed, spatial_shapes_host, reference_points, sampling_offsets, attention_weights, output},
+                 {bs, nk, heads, channels, num_levels, num_query, num_point, points_per_group}))
     return BEVOPS_BAD_PARAM;
   if (dtype == BEVOPS_F16 && ref_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
   if (dtype == BEVOPS_I8 && (!(scale_value > 0.f) || !(scale_offset > 0.f) || !(scale_weight > 0.f) ||
                              !(scale_out > 0.f)))
     return BEVOPS_BAD_PARAM;
-  return msda_hm4_forward_prepacked(dtype, ref_dtype, packed, packed_bytes, spatial_shapes_host, reference_points,
-                                    sampling_offsets, attention_weights, output, bs, nk, heads, channels,
-                                    num_levels, num_query, num_point, points_per_group, shared_offsets ? 1 : 0,
-                                    scale_value, scale_offset, scale_weight, scale_out, 0, 0,
-                                    static_cast<hipStream_t>(stream));
+  const MsdaCall c{{bs, nk, heads, channels, num_levels, num_query, num_point, points_per_group, shared_offsets ? 1 : 0},
+                   nullptr, reference_points, sampling_offsets, attention_weights, nullptr, output, dtype, ref_dtype,
+                   scale_value, scale_offset, scale_weight, scale_out, nullptr, spatial_shapes_host,
+                   const_cast<void *>(packed), packed_bytes, static_cast<hipStream_t>(stream)};
+  return msda_hm4_forward_prepacked(c);
 }
 
 extern "C" size_t bevops_sca_workspace_size(int dtype, const int32_t *spatial_shapes_host, int num_cams,
                                             int nk, int heads, int channels, int num_levels,
                                             int num_query, int num_point) {
-  if (dtype != BEVOPS_F16 || !spatial_shapes_host || num_cams <= 0 || nk <= 0 || heads <= 0 ||
-      num_levels <= 0 || num_query <= 0 || num_point <= 0)
+  if (dtype != BEVOPS_F16 || !all_given({spatial_shapes_host}, {num_cams, nk, heads, num_levels, num_query, num_point}))
     return 0;
-  return msda_hm3_sca_workspace_bytes(spatial_shapes_host, num_cams, heads, channels, num_levels,
-                                      num_query, num_point);
+  return msda_hm3_sca_workspace_bytes(MsdaDims{num_cams, nk, heads, channels, num_levels, num_query, num_point, 0, 1},
+                                      spatial_shapes_host);
+}
+
+// The fused SCA op as an MsdaCall: fp16 throughout, offsets / logits shared by the cameras (`bs` = cameras)
+static MsdaCall sca_call(const void *value, const int32_t *shapes_host, const void *ref, const void *off,
+                         const void *logit, const void *mask, void *out, int num_cams, int nk, int heads, int channels,
+                         int num_levels, int num_query, int num_point, int points_per_group, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+  return MsdaCall{{num_cams, nk, heads, channels, num_levels, num_query, num_point, points_per_group, 1},
+                  value, ref, off, logit, mask, out, BEVOPS_F16, BEVOPS_F16, 1.f, 1.f, 1.f, 1.f, nullptr, shapes_host,
+                  workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
 }
 
 extern "C" int bevops_sca_forward(int dtype, const void *value, const int32_t *spatial_shapes_host,
@@ -744,31 +815,38 @@ extern "C" int bevops_sca_forward(int dtype, const void *value, const int32_t *s
                                   int num_cams, int nk, int heads, int channels, int num_levels,
                                   int num_query, int num_point, int points_per_group,
                                   void *workspace, size_t workspace_bytes, void *stream) {
-  if (!value || !spatial_shapes_host || !reference_points_cam || !sampling_offsets ||
-      !attention_weights || !bev_mask || !output)
+  if (!all_given({value, spatial_shapes_host, reference_points_cam, sampling_offsets, attention_weights, bev_mask, output},
+                 {num_cams, nk, heads, channels, num_levels, num_query, num_point, points_per_group}) ||
+      !shapes_cover(spatial_shapes_host, num_levels, nk))
     return BEVOPS_BAD_PARAM;
-  if (num_cams <= 0 || nk <= 0 || heads <= 0 || channels <= 0 || num_levels <= 0 || num_query <= 0 ||
-      num_point <= 0 || points_per_group <= 0)
-    return BEVOPS_BAD_PARAM;
-  long total = 0;
-  for (int l = 0; l < num_levels; ++l) {
-    const long H = spatial_shapes_host[2 * l], W = spatial_shapes_host[2 * l + 1];
-    if (H <= 0 || W <= 0) return BEVOPS_BAD_PARAM;
-    total += H * W;
-  }
-  if (total != nk) return BEVOPS_BAD_PARAM;
   if (dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-  return msda_hm3_sca_forward_f16((const __half *)value, spatial_shapes_host,
-                                  (const __half *)reference_points_cam, (const __half *)sampling_offsets,
-                                  (const __half *)attention_weights, (const __half *)bev_mask,
-                                  (__half *)output, num_cams, nk, heads, channels, num_levels, num_query,
-                                  num_point, points_per_group, workspace, workspace_bytes,
-                                  static_cast<hipStream_t>(stream));
+  return msda_hm3_sca_forward_f16(sca_call(value, spatial_shapes_host, reference_points_cam, sampling_offsets,
+                                           attention_weights, bev_mask, output, num_cams, nk, heads, channels,
+                                           num_levels, num_query, num_point, points_per_group, workspace,
+                                           workspace_bytes, stream));
 }
 
 extern "C" size_t bevops_sca_prepacked_workspace_size(int num_cams, int heads, int channels, int num_query) {
-  if (num_cams <= 0 || heads <= 0 || channels <= 0 || num_query <= 0) return 0;
+  if (!all_given({}, {num_cams, heads, channels, num_query})) return 0;
   return (size_t)num_cams * num_query * heads * channels * sizeof(__half);
+}
+
+// the checks the two entries on packed planes share, then the call: planes = `packed`, the per-camera rows go to
+// the `workspace`
+static int sca_packed_call(int dtype, const void *packed, size_t packed_bytes, const int32_t *shapes_host,
+                           const void *ref, const void *off, const void *logit, const void *mask, void *output, int num_cams, int nk, int heads, int channels, int num_levels, int num_query,
+                           int num_point, int points_per_group, void *workspace, size_t workspace_bytes, void *stream,
+                           MsdaCall &c) {
+  if (!all_given({packed, shapes_host, ref, off, logit, mask, output, workspace},
+                 {num_cams, nk, heads, channels, num_levels, num_query, num_point, points_per_group}))
+    return BEVOPS_BAD_PARAM;
+  if (dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  if (workspace_bytes < bevops_sca_prepacked_workspace_size(num_cams, heads, channels, num_query) ||
+      (reinterpret_cast<uintptr_t>(workspace) & 15u))
+    return BEVOPS_BAD_PARAM;
+  c = sca_call(nullptr, shapes_host, ref, off, logit, mask, workspace, num_cams, nk, heads, channels, num_levels,
+               num_query, num_point, points_per_group, const_cast<void *>(packed), packed_bytes, stream);
+  return BEVOPS_SUCCESS;
 }
 
 extern "C" int bevops_sca_forward_prepacked(int dtype, const void *packed, size_t packed_bytes,
@@ -778,24 +856,15 @@ extern "C" int bevops_sca_forward_prepacked(int dtype, const void *packed, size_
                                             int channels, int num_levels, int num_query, int num_point,
                                             int points_per_group, void *workspace, size_t workspace_bytes,
                                             void *stream) {
-  if (!packed || !spatial_shapes_host || !reference_points_cam || !sampling_offsets || !attention_weights || !bev_mask ||
-      !output || !workspace)
-    return BEVOPS_BAD_PARAM;
-  if (num_cams <= 0 || nk <= 0 || heads <= 0 || channels <= 0 || num_levels <= 0 || num_query <= 0 || num_point <= 0 ||
-      points_per_group <= 0)
-    return BEVOPS_BAD_PARAM;
-  if (dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-  if (workspace_bytes < bevops_sca_prepacked_workspace_size(num_cams, heads, channels, num_query) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 15u))
-    return BEVOPS_BAD_PARAM;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  __half *sampled = static_cast<__half *>(workspace);
-  const int rc = msda_hm5_sca_sample_f16(packed, packed_bytes, spatial_shapes_host, (const __half *)reference_points_cam,
-                                         (const __half *)sampling_offsets, (const __half *)attention_weights,
-                                         (const __half *)bev_mask, sampled, num_cams, nk, heads, channels, num_levels,
-                                         num_query, num_point, points_per_group, st);
+  MsdaCall c;
+  int rc = sca_packed_call(dtype, packed, packed_bytes, spatial_shapes_host, reference_points_cam, sampling_offsets,
+                           attention_weights, bev_mask, output, num_cams, nk, heads,
+                           channels, num_levels, num_query, num_point, points_per_group, workspace, workspace_bytes,
+                           stream, c);
+  if (rc == BEVOPS_SUCCESS) rc = msda_hm5_sca_sample_f16(c);
   if (rc != BEVOPS_SUCCESS) return rc;
-  msda_sca_reduce_launch(sampled, (const __half *)bev_mask, (__half *)output, num_cams, num_query, heads * channels, false, st);
+  msda_sca_reduce_launch((const __half *)c.out, (const __half *)bev_mask, (__half *)output, num_cams, num_query,
+                         heads * channels, false, c.st);
   return launch_status();
 }
 
@@ -803,7 +872,7 @@ extern "C" size_t bevops_sca_plan_size(int num_cams, int num_query) { return msd
 
 extern "C" int bevops_sca_plan_build(int dtype, const void *bev_mask, int num_cams, int num_query, void *plan,
                                      size_t plan_bytes, void *stream) {
-  if (!bev_mask || !plan || num_cams <= 0 || num_query <= 0) return BEVOPS_BAD_PARAM;
+  if (!all_given({bev_mask, plan}, {num_cams, num_query})) return BEVOPS_BAD_PARAM;
   if (dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
   return msda_hm5_plan_build((const __half *)bev_mask, num_cams, num_query, plan, plan_bytes,
                              static_cast<hipStream_t>(stream));
@@ -816,26 +885,17 @@ extern "C" int bevops_sca_forward_planned(int dtype, const void *packed, size_t 
                                           int num_cams, int nk, int heads, int channels, int num_levels, int num_query,
                                           int num_point, int points_per_group, void *workspace, size_t workspace_bytes,
                                           void *stream) {
-  if (!packed || !spatial_shapes_host || !reference_points_cam || !sampling_offsets || !attention_weights || !bev_mask ||
-      !plan || !output || !workspace)
-    return BEVOPS_BAD_PARAM;
-  if (num_cams <= 0 || nk <= 0 || heads <= 0 || channels <= 0 || num_levels <= 0 || num_query <= 0 || num_point <= 0 ||
-      points_per_group <= 0)
-    return BEVOPS_BAD_PARAM;
-  if (dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-  if (workspace_bytes < bevops_sca_prepacked_workspace_size(num_cams, heads, channels, num_query) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 15u))
-    return BEVOPS_BAD_PARAM;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  __half *sampled = static_cast<__half *>(workspace);
-  const int rc = msda_hm5_sca_sample_planned_f16(packed, packed_bytes, spatial_shapes_host,
-                                                 (const __half *)reference_points_cam, (const __half *)sampling_offsets,
-                                                 (const __half *)attention_weights, plan, plan_bytes, sampled,
-                                                 g_sca_direct ? (__half *)output : nullptr, num_cams, nk, heads, channels,
-                                                 num_levels, num_query, num_point, points_per_group, st);
+  if (!plan) return BEVOPS_BAD_PARAM;
+  MsdaCall c;
+  int rc = sca_packed_call(dtype, packed, packed_bytes, spatial_shapes_host, reference_points_cam, sampling_offsets,
+                           attention_weights, bev_mask, output, num_cams, nk, heads, channels, num_levels,
+                           num_query, num_point, points_per_group, workspace, workspace_bytes, stream, c);
+  const bool direct = g_msda_sel.sca_direct;   // see set_variant 3012 / 3013
+  if (rc == BEVOPS_SUCCESS)
+    rc = msda_hm5_sca_sample_planned_f16(c, plan, plan_bytes, direct ? (__half *)output : nullptr);
   if (rc != BEVOPS_SUCCESS) return rc;
-  msda_sca_reduce_launch(sampled, (const __half *)bev_mask, (__half *)output, num_cams, num_query, heads * channels,
-                         g_sca_direct, st);
+  msda_sca_reduce_launch((const __half *)c.out, (const __half *)bev_mask, (__half *)output, num_cams, num_query,
+                         heads * channels, direct, c.st);
   return launch_status();
 }
 
@@ -863,115 +923,41 @@ extern "C" int bevops_msda_forward_ws(int dtype, const void *value, const int32_
                                       int points_per_group, float scale_value, float scale_offset,
                                       float scale_weight, float scale_out, int shared_offsets,
                                       void *workspace, size_t workspace_bytes, void *stream) {
-  if (!value || !spatial_shapes || !reference_points || !sampling_offsets || !attention_weights ||
-      !output)
+  if (!all_given({value, spatial_shapes, reference_points, sampling_offsets, attention_weights, output},
+                 {bs, nk, heads, channels, num_levels, num_query, num_point, points_per_group}) ||
+      (spatial_shapes_host && !shapes_cover(spatial_shapes_host, num_levels, nk)))
     return BEVOPS_BAD_PARAM;
-  if (bs <= 0 || nk <= 0 || heads <= 0 || channels <= 0 || num_levels <= 0 || num_query <= 0 ||
-      num_point <= 0 || points_per_group <= 0)
-    return BEVOPS_BAD_PARAM;
-  if (spatial_shapes_host) {
-    long total = 0;
-    for (int l = 0; l < num_levels; ++l) {
-      const long H = spatial_shapes_host[2 * l], W = spatial_shapes_host[2 * l + 1];
-      if (H <= 0 || W <= 0) return BEVOPS_BAD_PARAM;
-      total += H * W;
+  const bool i8 = dtype == BEVOPS_I8;
+  if (dtype != BEVOPS_F32 && dtype != BEVOPS_F16 && !i8) return BEVOPS_NOT_SUPPORTED;
+  if (i8) {
+    // supportsFormatCombination (multiScaleDeformableAttnPlugin.cpp:151-156)
+    if (channels % 4 != 0 || num_point % 4 != 0) return BEVOPS_NOT_SUPPORTED;
+    if (!(scale_value > 0.f) || !(scale_offset > 0.f) || !(scale_weight > 0.f) || !(scale_out > 0.f))
+      return BEVOPS_BAD_PARAM;
+    if (ref_dtype != BEVOPS_F32 && ref_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  } else if (ref_dtype != dtype) {
+    return BEVOPS_NOT_SUPPORTED;
+  }
+  const MsdaCall c{{bs, nk, heads, channels, num_levels, num_query, num_point, points_per_group, shared_offsets ? 1 : 0},
+                   value, reference_points, sampling_offsets, attention_weights, nullptr, output, dtype, ref_dtype,
+                   i8 ? scale_value : 1.f, i8 ? scale_offset : 1.f, i8 ? scale_weight : 1.f, i8 ? scale_out : 1.f,
+                   spatial_shapes, spatial_shapes_host, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+  const MsdaSelection &sel = g_msda_sel;
+  const MsdaOrder order = msda_head_major_order(dtype, c.d, spatial_shapes_host, spatial_shapes_host != nullptr,
+                                                workspace != nullptr, sel);
+  for (int i = 0; i < order.n; ++i) {
+    int rc;
+    switch (order.pick[i].family) {
+      case kMsdaHm4: rc = msda_hm4_forward(c); break;
+      case kMsdaHm5: rc = msda_hm5_forward_f16(c, true); break;
+      case kMsdaHm5NoPrepass: rc = msda_hm5_forward_f16(c, false); break;
+      case kMsdaHm3: rc = msda_hm3_forward_f16(c); break;
+      default: rc = msda_hm_forward_f16(c, sel.family); break;   // kMsdaHm
     }
-    if (total != nk) return BEVOPS_BAD_PARAM;
+    if (rc != BEVOPS_NOT_SUPPORTED || order.pick[i].forced) return rc;
   }
-  const MsdaDims d{bs, nk, heads, channels, num_levels, num_query, num_point, points_per_group,
-                   shared_offsets ? 1 : 0};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case BEVOPS_F32:
-      if (ref_dtype != BEVOPS_F32) return BEVOPS_NOT_SUPPORTED;
-      return msda_float<float>((const float *)value, spatial_shapes, (const float *)reference_points,
-                               (const float *)sampling_offsets, (const float *)attention_weights,
-                               (float *)output, d, st);
-    case BEVOPS_F16:
-      if (ref_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-      // head-major path (msda_hm.hip) when the caller lends a workspace and the call is big
-      // enough to amortise the re-layout; variants 10 (never) / 11 (hm forced) / 15 (hm2 forced)
-      if (workspace && g_variant != 10 && g_variant != 99 && g_variant != 1 && g_variant != 2) {
-        const bool pays = hm_pays(2, bs, nk, heads, channels, num_levels, num_query, num_point);
-        const int LP = num_levels * num_point;
-        // hm4 (software-pipelined, msda_hm4.hip): fp16 default where every pyramid level is
-        // LDS-resident (tiny / small SCA: 106 vs 142 us at small SCA); for the base SCA call hm3 and
-        // hm4 are level (571 vs 579 us kernel, profiles/r02) and hm3 stays.  Variant 17 forces hm4 for
-        // every shape it supports, 16 hm3
-        const bool staged_all = spatial_shapes_host && g_variant == 0 && num_query >= 8192 &&
-                                msda_hm4_all_staged(spatial_shapes_host, bs, heads, channels, num_levels,
-                                                    num_query, num_point);
-        const bool h4 = g_variant == 17 || staged_all;
-        if (spatial_shapes_host && h4) {
-          const int rc = msda_hm4_forward(
-              BEVOPS_F16, BEVOPS_F16, value, spatial_shapes_host, reference_points, sampling_offsets,
-              attention_weights, output, bs, nk, heads, channels, num_levels, num_query, num_point,
-              points_per_group, shared_offsets ? 1 : 0, 1.f, 1.f, 1.f, 1.f, workspace, workspace_bytes, 0, 0, st);
-          if (rc != BEVOPS_NOT_SUPPORTED || g_variant != 0) return rc;
-        }
-        // hm5 (msda_hm5.hip): hm3's planes, re-scheduled, plus the exact visibility pre-pass; default
-        // for the 4-level x 8-point SCA shape.  Variants 1000 + flags select its A/B builds
-        if (spatial_shapes_host && (g_variant == 1000 || g_variant == 1001 || (g_variant == 0 && pays))) {
-          const int rc = msda_hm5_forward_f16(
-              (const __half *)value, spatial_shapes_host, (const __half *)reference_points,
-              (const __half *)sampling_offsets, (const __half *)attention_weights, (__half *)output,
-              bs, nk, heads, channels, num_levels, num_query, num_point, points_per_group,
-              shared_offsets ? 1 : 0, workspace, workspace_bytes, g_variant >= 1000 ? g_variant - 1000 : 0, false, st);
-          if (rc != BEVOPS_NOT_SUPPORTED || g_variant != 0) return rc;
-        }
-        if (spatial_shapes_host && (g_variant == 16 || (g_variant == 0 && pays && LP >= 16))) {
-          const int rc = msda_hm3_forward_f16(
-              (const __half *)value, spatial_shapes_host, (const __half *)reference_points,
-              (const __half *)sampling_offsets, (const __half *)attention_weights, (__half *)output,
-              bs, nk, heads, channels, num_levels, num_query, num_point, points_per_group,
-              shared_offsets ? 1 : 0, workspace, workspace_bytes, st);
-          if (rc != BEVOPS_NOT_SUPPORTED || g_variant == 16) return rc;
-        }
-        if (g_variant == 11 || g_variant == 15 || pays) {
-          const int rc = msda_hm_forward_f16(
-              (const __half *)value, spatial_shapes, spatial_shapes_host,
-              (const __half *)reference_points, (const __half *)sampling_offsets,
-              (const __half *)attention_weights, (__half *)output, bs, nk, heads, channels,
-              num_levels, num_query, num_point, points_per_group, shared_offsets ? 1 : 0, workspace,
-              workspace_bytes, g_variant, st);
-          if (rc != BEVOPS_NOT_SUPPORTED) return rc;
-        }
-      }
-      return msda_float<__half>((const __half *)value, spatial_shapes,
-                                (const __half *)reference_points, (const __half *)sampling_offsets,
-                                (const __half *)attention_weights, (__half *)output, d, st);
-    case BEVOPS_I8:
-      // supportsFormatCombination (multiScaleDeformableAttnPlugin.cpp:151-156)
-      if (channels % 4 != 0 || num_point % 4 != 0) return BEVOPS_NOT_SUPPORTED;
-      if (!(scale_value > 0.f) || !(scale_offset > 0.f) || !(scale_weight > 0.f) ||
-          !(scale_out > 0.f))
-        return BEVOPS_BAD_PARAM;
-      // head-major int8 path (msda_hm4.hip) when the caller lends a workspace and the call is big
-      // enough (variant 17 forces it, 10 / 99 keep the layout-preserving kernels)
-      if (workspace && spatial_shapes_host && g_variant != 10 && g_variant != 99 &&
-          (ref_dtype == BEVOPS_F32 || ref_dtype == BEVOPS_F16) &&
-          (g_variant == 17 || hm_pays(1, bs, nk, heads, channels, num_levels, num_query, num_point))) {
-        const int rc = msda_hm4_forward(BEVOPS_I8, ref_dtype, value, spatial_shapes_host, reference_points,
-                                        sampling_offsets, attention_weights, output, bs, nk, heads, channels,
-                                        num_levels, num_query, num_point, points_per_group,
-                                        shared_offsets ? 1 : 0, scale_value, scale_offset, scale_weight,
-                                        scale_out, workspace, workspace_bytes, 0, 0, st);
-        if (rc != BEVOPS_NOT_SUPPORTED) return rc;
-      }
-      if (ref_dtype == BEVOPS_F32)
-        return msda_int8<float, false>((const int8_t *)value, spatial_shapes,
-                                       (const float *)reference_points,
-                                       (const int8_t *)sampling_offsets,
-                                       (const int8_t *)attention_weights, (int8_t *)output, d,
-                                       scale_value, scale_offset, scale_weight, scale_out, st);
-      if (ref_dtype == BEVOPS_F16)
-        return msda_int8<__half, true>((const int8_t *)value, spatial_shapes,
-                                       (const __half *)reference_points,
-                                       (const int8_t *)sampling_offsets,
-                                       (const int8_t *)attention_weights, (int8_t *)output, d,
-                                       scale_value, scale_offset, scale_weight, scale_out, st);
-      return BEVOPS_NOT_SUPPORTED;
-    default:
-      return BEVOPS_NOT_SUPPORTED;
-  }
+  if (dtype == BEVOPS_F32) return msda_float<float>(c, sel.family);
+  if (dtype == BEVOPS_F16) return msda_float<__half>(c, sel.family);
+  if (ref_dtype == BEVOPS_F32) return msda_int8<float, false>(c, sel.family);
+  return msda_int8<__half, true>(c, sel.family);
 }

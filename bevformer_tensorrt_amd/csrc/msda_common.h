@@ -4,15 +4,51 @@
 #include "common.h"
 
 namespace bevops {
-namespace {
-
-constexpr int kMaxLevels = 16;
-constexpr int kBlock = 256;
 
 struct MsdaDims {
   int bs, nk, heads, C, L, nq, P, ppg;
   int shared;  // 1: sampling_offsets / attention_weights are [1, nq, heads, .] shared by all bs
+  size_t n_item() const { return (size_t)bs * nq * heads; }              // (batch, query, head) items
+  size_t value_elems() const { return (size_t)bs * nk * heads * C; }
 };
+
+// One MSDA / SCA call as the extern "C" entries hand it to the kernel families (built once per entry, after
+// validation).  `workspace` is where the head-major planes live: scratch the call re-lays `value` into, or the packed
+// planes of a *_prepacked / *_planned entry (`value` is then unused).  The SCA samplers write the per-camera rows to
+// `out`; `mask` is their bev_mask, null elsewhere.
+struct MsdaCall {
+  MsdaDims d;
+  const void *value, *ref, *off, *logit, *mask;
+  void *out;
+  int dtype, ref_dtype;
+  float s_v, s_o, s_w, s_out;            // int8 scales (value, offset, weight, output)
+  const int32_t *shapes, *shapes_host;   // [L][2] = (H, W) on the device / on the host (either may be null)
+  void *workspace;
+  size_t workspace_bytes;
+  hipStream_t st;
+};
+
+// What bevops_msda_set_variant asked for on this thread, decoded once (the numbers: include/bevops.h)
+enum MsdaFamily {
+  kMsdaAuto, kMsdaQuad8, kMsdaQuad2, kMsdaNoHeadMajor, kMsdaHm, kMsdaHm2, kMsdaHm3, kMsdaHm4, kMsdaHm5,
+  kMsdaHm5NoPrepass, kMsdaGeneric
+};
+struct MsdaSelection {
+  MsdaFamily family = kMsdaAuto;
+  bool h4_one_block = false;       // int8 hm4 on the one-block-per-CU plan (A/B partner of the two-blocks plan)
+  // knobs of the fused SCA op; sticky, independent of `family`
+  int sca_plan_blocks = 2;         // slices per CU of the planned sampling, 1 .. 8
+  bool sca_reduce_rolled = false;  // camera reduce with its camera loop rolled
+  bool sca_direct = true;          // planned sampling stores single-camera pairs straight into the output
+  bool sca_fold = true;            // the FOLD build of the planned kernel / the round-5 build
+  int raw = 0;                     // the family value last requested: what set_variant hands back
+};
+extern thread_local MsdaSelection g_msda_sel;   // msda.hip
+
+namespace {
+
+constexpr int kMaxLevels = 16;
+constexpr int kBlock = 256;
 
 // ---------------------------------------------------------------------------
 // element loaders: N consecutive T -> float
@@ -207,69 +243,35 @@ __device__ __forceinline__ float loc_im(float ref, float size, float off) {
 
 }  // namespace
 
-// msda_hm.hip -- fp16 head-major path.  Returns BEVOPS_NOT_SUPPORTED when the shape is
-// outside its domain (caller falls back to the quad kernel).
-size_t msda_hm_workspace_bytes(int bs, int nk, int heads, int C, int L);
-int msda_hm_forward_f16(const __half *value, const int32_t *shapes, const int32_t *shapes_host,
-                        const __half *ref, const __half *off, const __half *logit, __half *out,
-                        int bs, int nk, int heads, int C, int L, int nq, int P, int ppg, int shared,
-                        void *workspace, size_t workspace_bytes, int variant, hipStream_t st);
-// msda_hm3.hip -- padded head-major path with LDS-resident small levels; needs the shapes on
-// the host.  workspace_bytes == 0 / NOT_SUPPORTED when the shape is outside its domain.
-size_t msda_hm3_workspace_bytes(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq,
-                                int P);
-int msda_hm3_forward_f16(const __half *value, const int32_t *shapes_host, const __half *ref,
-                         const __half *off, const __half *logit, __half *out, int bs, int nk,
-                         int heads, int C, int L, int nq, int P, int ppg, int shared,
-                         void *workspace, size_t workspace_bytes, hipStream_t st);
+// The kernel families below return BEVOPS_NOT_SUPPORTED when the call is outside their domain (the caller then tries
+// its next candidate); their *_workspace_bytes partners return 0 there.
+// msda_hm.hip -- fp16 head-major path; `family` kMsdaHm / kMsdaHm2 forces that generation
+size_t msda_hm_workspace_bytes(const MsdaDims &d);
+int msda_hm_forward_f16(const MsdaCall &c, MsdaFamily family);
+// msda_hm3.hip -- padded head-major path with LDS-resident small levels; needs the shapes on the host
+size_t msda_hm3_workspace_bytes(const MsdaDims &d, const int32_t *shapes_host);
+int msda_hm3_forward_f16(const MsdaCall &c);
 // msda_hm4.hip -- software-pipelined successor of hm3 on the same padded layout idea; fp16 and
 // both int8 flavours (dtype BEVOPS_F16 / BEVOPS_I8, ref_dtype selects the int8 flavour).
-size_t msda_hm4_workspace_bytes(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq, int P, bool i8);
-int msda_hm4_forward(int dtype, int ref_dtype, const void *value, const int32_t *shapes_host, const void *ref,
-                     const void *off, const void *logit, void *out, int bs, int nk, int heads, int C, int L,
-                     int nq, int P, int ppg, int shared, float s_v, float s_o, float s_w, float s_out,
-                     void *workspace, size_t workspace_bytes, int chunk_override, int ablate, hipStream_t st);
-bool msda_hm4_all_staged(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq, int P);
-void msda_hm4_set_no_occ(bool v);
-int msda_hm4_pack(int dtype, int ref_dtype, const void *value, const int32_t *shapes_host, int bs, int nk,
-                  int heads, int C, int L, int nq, int P, void *packed, size_t packed_bytes, hipStream_t st);
-int msda_hm4_forward_prepacked(int dtype, int ref_dtype, const void *packed, size_t packed_bytes,
-                               const int32_t *shapes_host, const void *ref, const void *off, const void *logit,
-                               void *out, int bs, int nk, int heads, int C, int L, int nq, int P, int ppg,
-                               int shared, float s_v, float s_o, float s_w, float s_out, int chunk_override,
-                               int ablate, hipStream_t st);
+size_t msda_hm4_workspace_bytes(const MsdaDims &d, const int32_t *shapes_host, bool i8);
+int msda_hm4_forward(const MsdaCall &c);
+bool msda_hm4_all_staged(const MsdaDims &d, const int32_t *shapes_host);
+int msda_hm4_pack(const MsdaCall &c);
+int msda_hm4_forward_prepacked(const MsdaCall &c);
 // msda_hm5.hip -- re-scheduled successor of hm3 for the 4-level x 8-point SCA shape (same planes) with an
-// exact visibility pre-pass; `flags`: see msda_hm5_forward_f16
-size_t msda_hm5_workspace_bytes(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq, int P);
-int msda_hm5_forward_f16(const __half *value, const int32_t *shapes_host, const __half *ref, const __half *off,
-                         const __half *logit, __half *out, int bs, int nk, int heads, int C, int L, int nq, int P,
-                         int ppg, int shared, void *workspace, size_t workspace_bytes, int flags, bool prepacked,
-                         hipStream_t st);
-int msda_hm5_sca_sample_f16(const void *packed, size_t packed_bytes, const int32_t *shapes_host, const __half *ref,
-                            const __half *off, const __half *logit, const __half *qmask, __half *sampled, int bs,
-                            int nk, int heads, int C, int L, int nq, int P, int ppg, hipStream_t st);
-// visibility plan of the fused SCA op (per camera the ascending list of its visible queries) and the sampling on it
+// exact visibility pre-pass (`prepass` false: its A/B partner, every item sampled)
+size_t msda_hm5_workspace_bytes(const MsdaDims &d, const int32_t *shapes_host);
+int msda_hm5_forward_f16(const MsdaCall &c, bool prepass);
+int msda_hm5_sca_sample_f16(const MsdaCall &c);
+// visibility plan of the fused SCA op (per camera the ascending list of its visible queries) and the sampling on it;
+// `direct`: the output the single-camera pairs are stored into, or null
 size_t msda_hm5_plan_bytes(int bs, int nq);
 int msda_hm5_plan_build(const __half *qmask, int bs, int nq, void *plan, size_t plan_bytes, hipStream_t st);
-int msda_hm5_sca_sample_planned_f16(const void *packed, size_t packed_bytes, const int32_t *shapes_host,
-                                    const __half *ref, const __half *off, const __half *logit, const void *plan,
-                                    size_t plan_bytes, __half *sampled, __half *direct, int bs, int nk, int heads, int C,
-                                    int L, int nq, int P, int ppg, hipStream_t st);
-void msda_hm5_set_plan_blocks(int k);
-void msda_hm5_set_fold(bool on);
-void msda_sca_set_reduce_rolled(bool on);   // A/B partner of the unrolled camera reduce (set_variant 3010 / 3011)
+int msda_hm5_sca_sample_planned_f16(const MsdaCall &c, const void *plan, size_t plan_bytes, __half *direct);
 // skip_sole: rows of queries that exactly one camera sees with weight 1 are left alone (the planned sampler has
 // stored them already, msda_hm5.hip: kSoleBit)
 void msda_sca_reduce_launch(const __half *sampled, const __half *qmask, __half *out, int bs, int nq, int width,
                             bool skip_sole, hipStream_t st);
-bool msda_hm5_layout(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq, int P, void *tab,
-                     size_t *g_room, size_t *s_bytes);
-void msda_hm3_repack_launch(const void *value, char *gset, char *sset, const void *tab, int bs, int nk, int heads,
-                            hipStream_t st);
-size_t msda_hm3_sca_workspace_bytes(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq,
-                                    int P);
-int msda_hm3_sca_forward_f16(const __half *value, const int32_t *shapes_host, const __half *ref,
-                             const __half *off, const __half *logit, const __half *qmask,
-                             __half *out, int bs, int nk, int heads, int C, int L, int nq, int P,
-                             int ppg, void *workspace, size_t workspace_bytes, hipStream_t st);
+size_t msda_hm3_sca_workspace_bytes(const MsdaDims &d, const int32_t *shapes_host);
+int msda_hm3_sca_forward_f16(const MsdaCall &c);
 }  // namespace bevops

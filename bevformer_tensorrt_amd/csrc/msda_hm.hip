@@ -462,29 +462,34 @@ size_t hm_copy_bytes(int bs, int nk, int heads, int L) {
   return (((size_t)bs * heads * hm_nkp(nk, L) * kPixBytes) + 127) & ~size_t(127);
 }
 
-size_t msda_hm_workspace_bytes(int bs, int nk, int heads, int C, int L) {
-  if (C != 32 || L > kMaxLevels - 1) return 0;
-  const size_t one = hm_copy_bytes(bs, nk, heads, L);
-  const size_t v2 = hm2_bytes(bs, nk, heads, L);   // (hm2's two alignment copies: the larger of the two layouts)
+size_t msda_hm_workspace_bytes(const MsdaDims &d) {
+  if (d.C != 32 || d.L > kMaxLevels - 1) return 0;
+  const size_t one = hm_copy_bytes(d.bs, d.nk, d.heads, d.L);
+  const size_t v2 = hm2_bytes(d.bs, d.nk, d.heads, d.L);   // (hm2's two alignment copies: the larger of the two layouts)
   const size_t want = one > v2 ? one : v2;
   if (want < 0xFFFFFF00ull) return want;
   return one < 0xFFFFFF00ull ? one : 0;
 }
 
-int msda_hm_forward_f16(const __half *value, const int32_t *shapes, const int32_t *shapes_host,
-                        const __half *ref, const __half *off, const __half *logit, __half *out,
-                        int bs, int nk, int heads, int C, int L, int nq, int P, int ppg, int shared,
-                        void *workspace, size_t workspace_bytes, int variant, hipStream_t st) {
-  if (C != 32 || L > kMaxLevels - 1) return BEVOPS_NOT_SUPPORTED;
+int msda_hm_forward_f16(const MsdaCall &c, MsdaFamily family) {
+  const MsdaDims &d = c.d;
+  const int bs = d.bs, nk = d.nk, heads = d.heads, L = d.L;
+  if (d.C != 32 || L > kMaxLevels - 1) return BEVOPS_NOT_SUPPORTED;
+  const __half *value = (const __half *)c.value, *ref = (const __half *)c.ref, *off = (const __half *)c.off,
+               *logit = (const __half *)c.logit;
+  __half *out = (__half *)c.out;
+  const int32_t *shapes = c.shapes;
+  void *workspace = c.workspace;
+  hipStream_t st = c.st;
   const size_t one = hm_copy_bytes(bs, nk, heads, L);
-  const int LP = L * P;
+  const int LP = L * d.P;
   // default: hm2 for the many-point calls (SCA: L*P >= 16), hm for the few-point ones (TSA:
   // only half of an hm2 octet would own a point, and its two-copy re-layout costs more than
-  // it saves); variant 11 forces hm, 15 forces hm2
-  if ((variant == 15 || LP >= 16) && variant != 11) {
+  // it saves); kMsdaHm forces hm, kMsdaHm2 forces hm2
+  if ((family == kMsdaHm2 || LP >= 16) && family != kMsdaHm) {
     const size_t need2 = hm2_bytes(bs, nk, heads, L);
     const bool lp_ok = LP == 4 || LP == 8 || LP == 16 || LP == 32 || LP == 64;
-    if (workspace && workspace_bytes >= need2 && need2 < 0xFFFFFF00ull && lp_ok &&
+    if (workspace && c.workspace_bytes >= need2 && need2 < 0xFFFFFF00ull && lp_ok &&
         !(reinterpret_cast<uintptr_t>(workspace) & 127u)) {
       const int npairs = hm2_npairs(nk, L);
       char *vh2 = static_cast<char *>(workspace);
@@ -492,18 +497,17 @@ int msda_hm_forward_f16(const __half *value, const int32_t *shapes, const int32_
       const size_t threads = (size_t)bs * npairs * 2 * heads * 8;
       hipLaunchKernelGGL(msda_hm2_repack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
                          st, value, shapes, vh2, bs, nk, heads, L, npairs, copy_b);
-      const MsdaDims d2{bs, nk, heads, C, L, nq, P, ppg, shared};
       switch (LP) {
-        case 4: return launch_hm2<4>(vh2, need2, shapes, ref, off, logit, out, d2, npairs, copy_b, st);
-        case 8: return launch_hm2<8>(vh2, need2, shapes, ref, off, logit, out, d2, npairs, copy_b, st);
-        case 16: return launch_hm2<16>(vh2, need2, shapes, ref, off, logit, out, d2, npairs, copy_b, st);
-        case 32: return launch_hm2<32>(vh2, need2, shapes, ref, off, logit, out, d2, npairs, copy_b, st);
-        default: return launch_hm2<64>(vh2, need2, shapes, ref, off, logit, out, d2, npairs, copy_b, st);
+        case 4: return launch_hm2<4>(vh2, need2, shapes, ref, off, logit, out, d, npairs, copy_b, st);
+        case 8: return launch_hm2<8>(vh2, need2, shapes, ref, off, logit, out, d, npairs, copy_b, st);
+        case 16: return launch_hm2<16>(vh2, need2, shapes, ref, off, logit, out, d, npairs, copy_b, st);
+        case 32: return launch_hm2<32>(vh2, need2, shapes, ref, off, logit, out, d, npairs, copy_b, st);
+        default: return launch_hm2<64>(vh2, need2, shapes, ref, off, logit, out, d, npairs, copy_b, st);
       }
     }
-    if (variant == 15) return BEVOPS_NOT_SUPPORTED;
+    if (family == kMsdaHm2) return BEVOPS_NOT_SUPPORTED;
   }
-  if (!workspace || workspace_bytes < one || one >= 0xFFFFFF00ull || LP % 4 != 0 ||
+  if (!workspace || c.workspace_bytes < one || one >= 0xFFFFFF00ull || LP % 4 != 0 ||
       (reinterpret_cast<uintptr_t>(workspace) & 127u))
     return BEVOPS_NOT_SUPPORTED;
   const int nkp = hm_nkp(nk, L);
@@ -513,8 +517,6 @@ int msda_hm_forward_f16(const __half *value, const int32_t *shapes, const int32_
     hipLaunchKernelGGL(msda_hm_repack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st,
                        value, shapes, vh, bs, nk, heads, L, nkp);
   }
-  (void)shapes_host;
-  const MsdaDims d{bs, nk, heads, C, L, nq, P, ppg, shared};
   switch (LP / 4) {
     case 1: return launch_hm<1, 1>(vh, one, shapes, ref, off, logit, out, d, nkp, st);
     case 2: return launch_hm<2, 2>(vh, one, shapes, ref, off, logit, out, d, nkp, st);

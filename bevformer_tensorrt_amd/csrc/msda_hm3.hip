@@ -499,25 +499,20 @@ __global__ __launch_bounds__(256) void sca_camera_reduce_kernel(const __half *__
 
 }  // namespace
 
-// fp16 re-layout into the padded sets (shared with msda_hm4.hip, whose fp16 planes have the same
-// layout; `tab` points at an Hm3Tab -- passed untyped because the struct lives in each
-// translation unit's unnamed namespace)
-void msda_hm3_repack_launch(const void *value, char *gset, char *sset, const void *tab, int bs, int nk, int heads,
+// fp16 re-layout into the padded sets (shared with msda_hm4.hip and msda_hm5.hip, whose fp16 planes have the same
+// layout)
+void msda_hm3_repack_launch(const void *value, char *gset, char *sset, const Hm3Tab &t, int bs, int nk, int heads,
                             hipStream_t st) {
-  const Hm3Tab &t = *static_cast<const Hm3Tab *>(tab);
   const size_t threads = (size_t)bs * t.g_entries * heads * 8 + (size_t)bs * t.s_entries * heads * 4;
   hipLaunchKernelGGL(msda_hm3_repack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st,
                      static_cast<const __half *>(value), gset, sset, t, bs, nk, heads);
 }
 
-static thread_local bool g_reduce_rolled = false;
-void msda_sca_set_reduce_rolled(bool on) { g_reduce_rolled = on; }
-
 void msda_sca_reduce_launch(const __half *sampled, const __half *qmask, __half *out, int bs, int nq, int width,
                             bool skip_sole, hipStream_t st) {
   const size_t threads = (size_t)nq * (width / 8);
   const dim3 grid((unsigned)((threads + 255) / 256));
-  const int unrolled = (threads < (1ull << 31) && !g_reduce_rolled && (bs <= 3 || bs == 6)) ? bs : 0;
+  const int unrolled = (threads < (1ull << 31) && !g_msda_sel.sca_reduce_rolled && (bs <= 3 || bs == 6)) ? bs : 0;
 #define BEVOPS_REDUCE_GO(BS)                                                                                         \
   do {                                                                                                               \
     if (skip_sole)                                                                                                   \
@@ -537,86 +532,64 @@ void msda_sca_reduce_launch(const __half *sampled, const __half *qmask, __half *
 #undef BEVOPS_REDUCE_GO
 }
 
-size_t msda_hm3_workspace_bytes(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq,
-                                int P) {
+size_t msda_hm3_workspace_bytes(const MsdaDims &d, const int32_t *shapes_host) {
   Hm3Plan pl;
-  if (C != 32 || !hm3_plan(shapes_host, bs, heads, L, nq, hm3_box_bytes(L * P), pl)) return 0;
+  if (d.C != 32 || !hm3_plan(d, shapes_host, hm3_box_bytes(d.L * d.P), pl)) return 0;
   return pl.g_bytes + 128 + pl.s_bytes;
 }
 
-int msda_hm3_forward_f16(const __half *value, const int32_t *shapes_host, const __half *ref,
-                         const __half *off, const __half *logit, __half *out, int bs, int nk,
-                         int heads, int C, int L, int nq, int P, int ppg, int shared,
-                         void *workspace, size_t workspace_bytes, hipStream_t st) {
-  const int LP = L * P;
+// the domain both entries below share; fills the plan
+static bool hm3_domain(const MsdaCall &c, Hm3Plan &pl) {
+  const MsdaDims &d = c.d;
+  const int LP = d.L * d.P;
   const bool lp_ok = LP == 4 || LP == 8 || LP == 16 || LP == 32 || LP == 64;
+  if (d.C != 32 || !lp_ok || !c.workspace || (reinterpret_cast<uintptr_t>(c.workspace) & 127u) ||
+      !hm3_plan(d, c.shapes_host, hm3_box_bytes(LP), pl))
+    return false;
+  return (double)d.bs * d.nq * d.heads * LP * 4.0 < 4294967040.0;  // 32-bit offsets
+}
+
+// re-layout of c.value into the workspace, then the sampling into `out` (`qmask`: the SCA visibility mask or null)
+static int hm3_run(const MsdaCall &c, const Hm3Plan &pl, __half *out, const __half *qmask) {
+  const MsdaDims &d = c.d;
+  char *gset = static_cast<char *>(c.workspace);
+  char *sset = gset + ((pl.g_bytes + 127) & ~size_t(127));
+  const __half *ref = (const __half *)c.ref, *off = (const __half *)c.off, *logit = (const __half *)c.logit;
+  msda_hm3_repack_launch(c.value, gset, sset, pl.t, d.bs, d.nk, d.heads, c.st);
+  switch (d.L * d.P) {
+    case 4: return launch_hm3<4>(pl, gset, sset, ref, off, logit, out, d, qmask, c.st);
+    case 8: return launch_hm3<8>(pl, gset, sset, ref, off, logit, out, d, qmask, c.st);
+    case 16: return launch_hm3<16>(pl, gset, sset, ref, off, logit, out, d, qmask, c.st);
+    case 32: return launch_hm3<32>(pl, gset, sset, ref, off, logit, out, d, qmask, c.st);
+    default: return launch_hm3<64>(pl, gset, sset, ref, off, logit, out, d, qmask, c.st);
+  }
+}
+
+int msda_hm3_forward_f16(const MsdaCall &c) {
   Hm3Plan pl;
-  if (C != 32 || !lp_ok || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 127u) ||
-      !hm3_plan(shapes_host, bs, heads, L, nq, hm3_box_bytes(LP), pl))
-    return BEVOPS_NOT_SUPPORTED;
-  if ((double)bs * nq * heads * LP * 4.0 >= 4294967040.0) return BEVOPS_NOT_SUPPORTED;  // 32-bit offsets
-  const size_t g_room = (pl.g_bytes + 127) & ~size_t(127);
-  if (workspace_bytes < g_room + pl.s_bytes) return BEVOPS_NOT_SUPPORTED;
-  char *gset = static_cast<char *>(workspace);
-  char *sset = gset + g_room;
-  {
-    const size_t threads = (size_t)bs * pl.t.g_entries * heads * 8 + (size_t)bs * pl.t.s_entries * heads * 4;
-    hipLaunchKernelGGL(msda_hm3_repack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st,
-                       value, gset, sset, pl.t, bs, nk, heads);
-  }
-  const MsdaDims d{bs, nk, heads, C, L, nq, P, ppg, shared};
-  switch (LP) {
-    case 4: return launch_hm3<4>(pl, gset, sset, ref, off, logit, out, d, nullptr, st);
-    case 8: return launch_hm3<8>(pl, gset, sset, ref, off, logit, out, d, nullptr, st);
-    case 16: return launch_hm3<16>(pl, gset, sset, ref, off, logit, out, d, nullptr, st);
-    case 32: return launch_hm3<32>(pl, gset, sset, ref, off, logit, out, d, nullptr, st);
-    default: return launch_hm3<64>(pl, gset, sset, ref, off, logit, out, d, nullptr, st);
-  }
+  if (!hm3_domain(c, pl)) return BEVOPS_NOT_SUPPORTED;
+  if (c.workspace_bytes < ((pl.g_bytes + 127) & ~size_t(127)) + pl.s_bytes) return BEVOPS_NOT_SUPPORTED;
+  return hm3_run(c, pl, (__half *)c.out, nullptr);
 }
 
 // ---- fused SCA: camera-shared offsets / logits, visibility-masked sampling, masked
 // camera sum.  workspace = [big set][staged set][sampled: bs * nq * heads * 32 fp16]
-size_t msda_hm3_sca_workspace_bytes(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq,
-                                    int P) {
-  const size_t a = msda_hm3_workspace_bytes(shapes_host, bs, heads, C, L, nq, P);
+size_t msda_hm3_sca_workspace_bytes(const MsdaDims &d, const int32_t *shapes_host) {
+  const size_t a = msda_hm3_workspace_bytes(d, shapes_host);
   if (a == 0) return 0;
-  return ((a + 255) & ~size_t(255)) + (size_t)bs * nq * heads * C * sizeof(__half);
+  return ((a + 255) & ~size_t(255)) + d.n_item() * d.C * sizeof(__half);
 }
 
-int msda_hm3_sca_forward_f16(const __half *value, const int32_t *shapes_host, const __half *ref,
-                             const __half *off, const __half *logit, const __half *qmask,
-                             __half *out, int bs, int nk, int heads, int C, int L, int nq, int P,
-                             int ppg, void *workspace, size_t workspace_bytes, hipStream_t st) {
-  const int LP = L * P;
-  const bool lp_ok = LP == 4 || LP == 8 || LP == 16 || LP == 32 || LP == 64;
+int msda_hm3_sca_forward_f16(const MsdaCall &c) {
   Hm3Plan pl;
-  if (C != 32 || !lp_ok || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 127u) ||
-      !hm3_plan(shapes_host, bs, heads, L, nq, hm3_box_bytes(LP), pl))
-    return BEVOPS_NOT_SUPPORTED;
-  if ((double)bs * nq * heads * LP * 4.0 >= 4294967040.0) return BEVOPS_NOT_SUPPORTED;
-  const size_t need = msda_hm3_sca_workspace_bytes(shapes_host, bs, heads, C, L, nq, P);
-  if (workspace_bytes < need) return BEVOPS_BAD_PARAM;
-  const size_t g_room = (pl.g_bytes + 127) & ~size_t(127);
-  char *gset = static_cast<char *>(workspace);
-  char *sset = gset + g_room;
+  if (!hm3_domain(c, pl)) return BEVOPS_NOT_SUPPORTED;
+  if (c.workspace_bytes < msda_hm3_sca_workspace_bytes(c.d, c.shapes_host)) return BEVOPS_BAD_PARAM;
   __half *sampled = reinterpret_cast<__half *>(
-      gset + ((msda_hm3_workspace_bytes(shapes_host, bs, heads, C, L, nq, P) + 255) & ~size_t(255)));
-  {
-    const size_t threads = (size_t)bs * pl.t.g_entries * heads * 8 + (size_t)bs * pl.t.s_entries * heads * 4;
-    hipLaunchKernelGGL(msda_hm3_repack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st,
-                       value, gset, sset, pl.t, bs, nk, heads);
-  }
-  const MsdaDims d{bs, nk, heads, C, L, nq, P, ppg, 1};
-  int rc;
-  switch (LP) {
-    case 4: rc = launch_hm3<4>(pl, gset, sset, ref, off, logit, sampled, d, qmask, st); break;
-    case 8: rc = launch_hm3<8>(pl, gset, sset, ref, off, logit, sampled, d, qmask, st); break;
-    case 16: rc = launch_hm3<16>(pl, gset, sset, ref, off, logit, sampled, d, qmask, st); break;
-    case 32: rc = launch_hm3<32>(pl, gset, sset, ref, off, logit, sampled, d, qmask, st); break;
-    default: rc = launch_hm3<64>(pl, gset, sset, ref, off, logit, sampled, d, qmask, st); break;
-  }
+      static_cast<char *>(c.workspace) + ((msda_hm3_workspace_bytes(c.d, c.shapes_host) + 255) & ~size_t(255)));
+  const __half *qmask = (const __half *)c.mask;
+  const int rc = hm3_run(c, pl, sampled, qmask);
   if (rc != BEVOPS_SUCCESS) return rc;
-  msda_sca_reduce_launch(sampled, qmask, out, bs, nq, heads * C, false, st);
+  msda_sca_reduce_launch(sampled, qmask, (__half *)c.out, c.d.bs, c.d.nq, c.d.heads * c.d.C, false, c.st);
   return launch_status();
 }
 

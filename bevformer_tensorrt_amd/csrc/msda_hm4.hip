@@ -122,7 +122,10 @@ struct H4Args {
   MsdaDims d;
   Hm3Tab t;
   int chunk, nchunk, stage_bytes;
-  const __half *qmask;
+  // 8 unused bytes where the visibility-mask pointer of a removed build was: they keep the scales and the hidden
+  // kernel arguments at their offsets, so that every kernel's instruction stream (register allocation included)
+  // stays the one that was measured and verified
+  const void *reserved = nullptr;
   float s_v, s_o, s_w, s_out;
 };
 
@@ -174,20 +177,24 @@ __device__ __forceinline__ int gather_hi(int x0, int x1, int x2, int x3) {
 // <float> flavour with signed x127 weights); RefT: reference point type (fp16 path: __half).
 // NBIG: batches (of BT points) served by the L1/L2 path, the remaining ones come from LDS.
 // RR: the PP reference points of an owner lane are one contiguous run (BEVFormer SCA: 4 anchors).
-// SCHED: schedule bits of the production builds (results identical whatever they are): 32 operand request at the END
-// of the loop body (fp16), 64 one big batch in flight instead of two, 128 default cache policy for the streamed
-// operands / output (int8), 1024 compiled for 4 waves per SIMD (<= 128 VGPRs) so that TWO 512-thread blocks share a
-// CU when the staged planes are small (the int8 two-blocks plan).  The timing ablations, the "request behind the first
-// batches" schedule and the int8 pixel-pair entry format of rounds 2 / 4 are no longer in this file (history;
+// OCC2: the int8 two-blocks plan -- compiled for 4 waves per SIMD (<= 128 VGPRs) so that TWO 512-thread blocks share a
+// CU when the staged planes are small, with one big batch in flight instead of two.
+// The schedule of the production builds follows from I8 and OCC2 (results identical whatever it is;
+// profiles/r02/hm4_variants.jsonl): kRequestAtEnd -- fp16 requests the next operands at the END of the loop body, int8
+// at its start; kDefaultCachePolicy -- int8 streams its operands / output with the default cache policy, fp16 marks
+// the long read-once rows non-temporal; D -- big batches in flight.  The timing ablations, the "request behind the
+// first batches" schedule and the int8 pixel-pair entry format of rounds 2 / 4 are no longer in this file (history;
 // profiles/r02/hm4_ablation.jsonl, hm4_schedule_variants.jsonl, profiles/r04/msda_i8_pair_ab.jsonl).
-template <int LP, int NBIG, int THREADS, bool I8, bool U8W, typename RefT, bool MASKED, bool RR, int SCHED = 0>
-__global__ __launch_bounds__(THREADS, (SCHED & 1024) ? 4 : 1) void msda_hm4_kernel(const H4Args a) {
+template <int LP, int NBIG, int THREADS, bool I8, bool U8W, typename RefT, bool RR, bool OCC2 = false>
+__global__ __launch_bounds__(THREADS, OCC2 ? 4 : 1) void msda_hm4_kernel(const H4Args a) {
+  constexpr bool kRequestAtEnd = !I8;
+  constexpr bool kDefaultCachePolicy = I8;
   constexpr int NOWN = LP >= 8 ? 8 : LP;  // owner lanes per octet
   constexpr int PP = LP / NOWN;           // points per owner
   constexpr int BT = LP >= 4 ? 4 : LP;    // points per tap batch
   constexpr int NB = LP / BT;
   constexpr int NLDS = NB - NBIG;
-  constexpr int D = (NBIG >= 2 && !(SCHED & 64)) ? 2 : 1;    // big batches in flight
+  constexpr int D = (NBIG >= 2 && !OCC2) ? 2 : 1;    // big batches in flight
   constexpr int kBox = LP * 16 + 16;      // mailbox bytes per octet (+16: bank spread)
   constexpr int ESZ = I8 ? 1 : 2;         // bytes per logit / offset component
   constexpr unsigned kBigEnt = (unsigned)kEntBytes;
@@ -195,7 +202,7 @@ __global__ __launch_bounds__(THREADS, (SCHED & 1024) ? 4 : 1) void msda_hm4_kern
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const MsdaDims &d = a.d;
   const Hm3Tab &t = a.t;
-  // smem: [level table] [staged planes] [mailboxes] [compaction list]
+  // smem: [level table] [staged planes] [mailboxes]
   unsigned bh, ck;
   if (d.heads == 8) {  // XCD x keeps head x; all XCDs walk the same (batch, chunk) sequence
     const unsigned rest = blockIdx.x >> 3;
@@ -260,33 +267,8 @@ __global__ __launch_bounds__(THREADS, (SCHED & 1024) ? 4 : 1) void msda_hm4_kern
   }
   constexpr unsigned kStride = THREADS / 8;
   const unsigned q0 = ck * (unsigned)a.chunk;
-  unsigned n_items = q_end - q0;
-  const unsigned short *qlist = reinterpret_cast<const unsigned short *>(
-      smem + kTab + a.stage_bytes + (THREADS / 8) * kBox);
-  if constexpr (MASKED) {  // compact the chunk to the (camera, query) pairs with a non-zero weight
-    unsigned short *wl = const_cast<unsigned short *>(qlist);
-    unsigned *wtot = reinterpret_cast<unsigned *>(smem + kTab + a.stage_bytes + (THREADS / 8) * kBox + a.chunk * 2);
-    unsigned base_count = 0;
-    for (unsigned t0 = 0; t0 < n_items; t0 += THREADS) {
-      const unsigned i = t0 + threadIdx.x;
-      const bool vis = i < n_items && __half2float(a.qmask[(size_t)b * d.nq + q0 + i]) != 0.f;
-      const unsigned long long bal = __ballot(vis);
-      const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-      if (lane == 0) wtot[wv] = (unsigned)__popcll(bal);
-      __syncthreads();
-      unsigned before = base_count, all = 0;
-      for (unsigned w2 = 0; w2 < THREADS / 64; ++w2) {
-        const unsigned c = wtot[w2];
-        if (w2 < wv) before += c;
-        all += c;
-      }
-      if (vis) wl[before + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)i;
-      base_count += all;
-      __syncthreads();
-    }
-    n_items = base_count;
-  }
-  auto query_of = [&](unsigned i) { return MASKED ? q0 + (unsigned)qlist[i] : q0 + i; };
+  const unsigned n_items = q_end - q0;
+  auto query_of = [&](unsigned i) { return q0 + i; };
 
   // ---- streamed operands: byte offsets into the three descriptors
   constexpr int NLG = I8 ? 1 + (PP > 4) : (PP + 1) / 2;           // logits dwords per lane
@@ -299,7 +281,7 @@ __global__ __launch_bounds__(THREADS, (SCHED & 1024) ? 4 : 1) void msda_hm4_kern
   const unsigned rf_base = b * (unsigned)d.nq * (unsigned)d.ppg * 2u * (unsigned)sizeof(RefT);
   const unsigned rf_q = (unsigned)d.ppg * 2u * (unsigned)sizeof(RefT);
   static_assert(!RR || PP == 4, "RR");
-  constexpr int aux = (LP >= 32 && !(SCHED & 128)) ? 2 : 0;   // long read-once rows: non-temporal, the maps keep the L2
+  constexpr int aux = (LP >= 32 && !kDefaultCachePolicy) ? 2 : 0;   // long read-once rows: non-temporal, the maps keep the L2
   auto request = [&](Pre &r, unsigned q) {
     const unsigned o_lg = lg_base + q * lg_q, o_of = 2u * o_lg, o_rf = rf_base + q * rf_q;
 #pragma unroll
@@ -487,7 +469,7 @@ __global__ __launch_bounds__(THREADS, (SCHED & 1024) ? 4 : 1) void msda_hm4_kern
   for (; i < n_items; i += kStride) {
     const unsigned q = query_of(i);
     const unsigned q_pre = i + 2 * kStride < n_items ? query_of(i + 2 * kStride) : q0;
-    if constexpr (!(SCHED & 32)) request(pre2, q_pre);
+    if constexpr (!kRequestAtEnd) request(pre2, q_pre);
     float s_nxt;
     bool any_nxt;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -655,14 +637,14 @@ __global__ __launch_bounds__(THREADS, (SCHED & 1024) ? 4 : 1) void msda_hm4_kern
       uint2 v;
       v.x = pack_h2(acc[0] * inv, acc[1] * inv);
       v.y = pack_h2(acc[2] * inv, acc[3] * inv);
-      if constexpr (LP >= 32 && !(SCHED & 128)) {
+      if constexpr (LP >= 32 && !kDefaultCachePolicy) {
         __builtin_nontemporal_store(((unsigned long long)v.y << 32) | v.x,
                                     reinterpret_cast<unsigned long long *>(outp));
       } else {
         *reinterpret_cast<uint2 *>(outp) = v;
       }
     }
-    if constexpr (SCHED & 32) request(pre2, q_pre);
+    if constexpr (kRequestAtEnd) request(pre2, q_pre);
     post(pl);
     s_cur = s_nxt;
     any_cur = any_nxt;
@@ -683,182 +665,166 @@ inline int h4_box_bytes(int LP) { return (kH4Threads / 8) * (LP * 16 + 16); }
 // (profiles/r02/hm4_int8_occupancy_ab.jsonl).  The same plan in fp16 (two lines per big-level sample, spills
 // under the 128-register cap) takes 950 us instead of 565: fp16 keeps the one-block plan.
 constexpr int kOccStageCap = 40 * 1024;
-thread_local bool g_h4_no_occ = false;   // variant 19 / the ablation variants: the one-block plan for int8 too
 struct H4Plan {
   Hm3Plan p;
   int nbig;   // tap batches served by L1/L2
   bool occ2;  // the two-blocks-per-CU plan
 };
 
-bool h4_plan(const int32_t *shapes_host, int bs, int heads, int L, int P, int nq, H4Plan &pl, bool i8) {
-  const int LP = L * P;
+bool h4_plan(const MsdaDims &d, const int32_t *shapes_host, bool i8, H4Plan &pl) {
+  const int L = d.L, P = d.P, LP = L * P;
   const int bt = LP >= 4 ? 4 : LP;
   pl.occ2 = false;
-  if (i8 && !g_h4_no_occ && LP == 32) {
+  if (i8 && !g_msda_sel.h4_one_block && LP == 32) {
     // (hm3_plan budgets the staged planes as kLdsLimit - kTab - box bytes: a cap is a larger pretended box)
-    if (hm3_plan(shapes_host, bs, heads, L, nq, kLdsLimit - kTab - kOccStageCap, pl.p) && pl.p.t.ls < L &&
+    if (hm3_plan(d, shapes_host, kLdsLimit - kTab - kOccStageCap, pl.p) && pl.p.t.ls < L &&
         (pl.p.t.ls * P) % bt == 0 && pl.p.t.ls * P / bt == 6) {
       pl.nbig = 6;
       pl.occ2 = true;
       return true;
     }
   }
-  if (!hm3_plan(shapes_host, bs, heads, L, nq, h4_box_bytes(LP), pl.p)) return false;
+  if (!hm3_plan(d, shapes_host, h4_box_bytes(LP), pl.p)) return false;
   if ((pl.p.t.ls * P) % bt) return false;  // a batch never straddles the big / staged boundary
   pl.nbig = pl.p.t.ls * P / bt;
   return true;
 }
 
-template <int LP, int NBIG, bool I8, bool U8W, typename RefT, bool MASKED, bool RR, int SCHED = 0>
+template <int LP, int NBIG, bool I8, bool U8W, typename RefT, bool RR, bool OCC2 = false>
 int h4_go(const H4Args &a, hipStream_t st) {
-  const size_t lds = kTab + a.stage_bytes + (size_t)h4_box_bytes(LP) + (a.qmask ? a.chunk * 2 + 64 : 0);
+  const size_t lds = kTab + a.stage_bytes + (size_t)h4_box_bytes(LP);
   if (lds > (size_t)kLdsLimit) return BEVOPS_NOT_SUPPORTED;
-  if (!ensure_dynamic_lds<msda_hm4_kernel<LP, NBIG, kH4Threads, I8, U8W, RefT, MASKED, RR, SCHED>>(lds))
+  if (!ensure_dynamic_lds<msda_hm4_kernel<LP, NBIG, kH4Threads, I8, U8W, RefT, RR, OCC2>>(lds))
     return BEVOPS_FAILURE;
   const dim3 grid((unsigned)(a.d.bs * a.d.heads * a.nchunk));
-  hipLaunchKernelGGL((msda_hm4_kernel<LP, NBIG, kH4Threads, I8, U8W, RefT, MASKED, RR, SCHED>), grid,
+  hipLaunchKernelGGL((msda_hm4_kernel<LP, NBIG, kH4Threads, I8, U8W, RefT, RR, OCC2>), grid,
                      dim3(kH4Threads), lds, st, a);
   return launch_status();
 }
 
 // instantiated (L*P, big batches) combinations: the model's calls.  Anything else -> NOT_SUPPORTED
 // (the caller keeps its older kernels for those).
-template <bool I8, bool U8W, typename RefT, bool MASKED>
+#define BEVOPS_H4_CASES(X)                                                      \
+  X(32, 4) /* base SCA: 4 levels x 8 points, two levels staged */               \
+  X(32, 8) /*   ... nothing staged (few queries) */                             \
+  X(32, 6) /*   ... one level staged */                                         \
+  X(8, 0)  /* tiny / small SCA: 1 level x 8 points, staged */                   \
+  X(8, 2)  /*   ... not staged */                                               \
+  X(4, 1)  /* TSA / decoder: 1 level x 4 points */                              \
+  X(4, 0)
+
+template <bool I8, bool U8W, typename RefT>
 int h4_dispatch(int LP, int nbig, bool occ2, const H4Args &a, hipStream_t st) {
   // points of an owner lane (4 of them when L*P = 32) share ONE run of reference points
   const bool rr = LP == 32 && a.d.ppg == 4 && a.d.P % 4 == 0;
-  // production schedule (profiles/r02/hm4_variants.jsonl): fp16 requests the next operands at
-  // the END of the loop body (32); int8 streams them with the default cache policy (128)
-  constexpr int PROD = I8 ? 128 : 32;
-#define BEVOPS_H4_CASE(LP_, NBIG_)                                                        \
-  if (LP == LP_ && nbig == NBIG_) {                                                       \
-    if constexpr (LP_ == 32) {                                                            \
-      if (rr) return h4_go<LP_, NBIG_, I8, U8W, RefT, MASKED, true, PROD>(a, st);         \
-    }                                                                                     \
-    return h4_go<LP_, NBIG_, I8, U8W, RefT, MASKED, false, PROD>(a, st);                  \
-  }
-  if constexpr (I8 && !MASKED) {
+  if constexpr (I8) {
     // the two-blocks-per-CU plan (h4_plan): <= 128 VGPRs, one big batch in flight
     if (occ2) {
       if (LP != 32 || nbig != 6) return BEVOPS_NOT_SUPPORTED;
-      if (rr) return h4_go<32, 6, I8, U8W, RefT, MASKED, true, PROD | 1024 | 64>(a, st);
-      return h4_go<32, 6, I8, U8W, RefT, MASKED, false, PROD | 1024 | 64>(a, st);
+      if (rr) return h4_go<32, 6, I8, U8W, RefT, true, true>(a, st);
+      return h4_go<32, 6, I8, U8W, RefT, false, true>(a, st);
     }
   }
-  BEVOPS_H4_CASE(32, 4)   // base SCA: 4 levels x 8 points, two levels staged
-  BEVOPS_H4_CASE(32, 8)   //   ... nothing staged (few queries)
-  BEVOPS_H4_CASE(32, 6)   //   ... one level staged
-  BEVOPS_H4_CASE(8, 0)    // tiny / small SCA: 1 level x 8 points, staged
-  BEVOPS_H4_CASE(8, 2)    //   ... not staged
-  BEVOPS_H4_CASE(4, 1)    // TSA / decoder: 1 level x 4 points
-  BEVOPS_H4_CASE(4, 0)
+#define BEVOPS_H4_CASE(LP_, NBIG_)                                      \
+  if (LP == LP_ && nbig == NBIG_) {                                     \
+    if constexpr (LP_ == 32) {                                          \
+      if (rr) return h4_go<LP_, NBIG_, I8, U8W, RefT, true>(a, st);     \
+    }                                                                   \
+    return h4_go<LP_, NBIG_, I8, U8W, RefT, false>(a, st);              \
+  }
+  BEVOPS_H4_CASES(BEVOPS_H4_CASE)
 #undef BEVOPS_H4_CASE
   return BEVOPS_NOT_SUPPORTED;
 }
 
 bool h4_instantiated(int LP, int nbig) {
-  return (LP == 32 && (nbig == 4 || nbig == 8 || nbig == 6)) || (LP == 8 && (nbig == 0 || nbig == 2)) ||
-         (LP == 4 && (nbig == 1 || nbig == 0));
+#define BEVOPS_H4_CASE(LP_, NBIG_) if (LP == LP_ && nbig == NBIG_) return true;
+  BEVOPS_H4_CASES(BEVOPS_H4_CASE)
+#undef BEVOPS_H4_CASE
+  return false;
 }
 
-int h4_chunk(const Hm3Plan &p, int nq, int variant_chunk) {
-  if (variant_chunk > 0) return variant_chunk;
-  return p.stage_bytes ? 1280 : 512;
+int h4_chunk(const Hm3Plan &p) { return p.stage_bytes ? 1280 : 512; }
+
+// what pack, forward_prepacked and forward ask of a call before anything else; fills the plan
+bool h4_domain(const MsdaCall &c, H4Plan &pl) {
+  return c.d.C == 32 && c.workspace && !(reinterpret_cast<uintptr_t>(c.workspace) & 127u) && c.shapes_host &&
+         h4_plan(c.d, c.shapes_host, c.dtype == BEVOPS_I8, pl);
 }
 
 }  // namespace
 
-void msda_hm4_set_no_occ(bool v) { g_h4_no_occ = v; }
-
-size_t msda_hm4_workspace_bytes(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq, int P, bool i8) {
+size_t msda_hm4_workspace_bytes(const MsdaDims &d, const int32_t *shapes_host, bool i8) {
   H4Plan pl;
-  if (C != 32 || !shapes_host || !h4_plan(shapes_host, bs, heads, L, P, nq, pl, i8)) return 0;
+  if (d.C != 32 || !shapes_host || !h4_plan(d, shapes_host, i8, pl)) return 0;
   return ((pl.p.g_bytes + 127) & ~size_t(127)) + 128 + pl.p.s_bytes;
 }
 
 // every level LDS-resident and an instantiated kernel: the shapes where hm4 is the fp16 default
-bool msda_hm4_all_staged(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq, int P) {
+bool msda_hm4_all_staged(const MsdaDims &d, const int32_t *shapes_host) {
   H4Plan pl;
-  return C == 32 && shapes_host && h4_plan(shapes_host, bs, heads, L, P, nq, pl, false) && pl.nbig == 0 &&
-         h4_instantiated(L * P, 0);
+  return d.C == 32 && shapes_host && h4_plan(d, shapes_host, false, pl) && pl.nbig == 0 &&
+         h4_instantiated(d.L * d.P, 0);
 }
 
 // The call in two halves (bevops_msda_pack_value / bevops_msda_forward_prepacked): the re-layout
-// of `value` into the padded head-major sets, and the sampling kernel on those sets -- for callers
+// of `value` into the padded head-major sets in c.workspace, and the sampling kernel on those sets -- for callers
 // that sample one value tensor several times, or produce the packed form themselves.
 // dtype: BEVOPS_F16 (ref fp16) or BEVOPS_I8 (ref fp32 -> x127 flavour, ref fp16 -> x255 flavour:
 // its planes are biased, so the packed form is flavour-specific).
-int msda_hm4_pack(int dtype, int ref_dtype, const void *value, const int32_t *shapes_host, int bs, int nk,
-                  int heads, int C, int L, int nq, int P, void *packed, size_t packed_bytes, hipStream_t st) {
+int msda_hm4_pack(const MsdaCall &c) {
+  const MsdaDims &d = c.d;
   H4Plan pl;
-  if (C != 32 || !packed || (reinterpret_cast<uintptr_t>(packed) & 127u) || !shapes_host ||
-      !h4_plan(shapes_host, bs, heads, L, P, nq, pl, dtype == BEVOPS_I8))
-    return BEVOPS_NOT_SUPPORTED;
-  if (dtype != BEVOPS_F16 && dtype != BEVOPS_I8) return BEVOPS_NOT_SUPPORTED;
+  if (!h4_domain(c, pl)) return BEVOPS_NOT_SUPPORTED;
+  if (c.dtype != BEVOPS_F16 && c.dtype != BEVOPS_I8) return BEVOPS_NOT_SUPPORTED;
   const size_t g_room = (pl.p.g_bytes + 127) & ~size_t(127);
-  if (packed_bytes < g_room + pl.p.s_bytes) return BEVOPS_BAD_PARAM;
-  char *gset = static_cast<char *>(packed);
+  if (c.workspace_bytes < g_room + pl.p.s_bytes) return BEVOPS_BAD_PARAM;
+  char *gset = static_cast<char *>(c.workspace);
   char *sset = gset + g_room;
   const Hm3Tab &t = pl.p.t;
-  if (dtype == BEVOPS_I8) {
-    if (bs * heads > 65535) return BEVOPS_NOT_SUPPORTED;
-    const dim3 grid((unsigned)(((t.g_entries + 31) >> 5) + ((t.s_entries + 31) >> 5)), (unsigned)(bs * heads));
-    hipLaunchKernelGGL(msda_hm4_repack_i8_kernel, grid, dim3(256), 0, st, (const int8_t *)value, gset, sset, t, nk,
-                       heads, ref_dtype == BEVOPS_F16 ? 0x80808080u : 0u);
+  if (c.dtype == BEVOPS_I8) {
+    if (d.bs * d.heads > 65535) return BEVOPS_NOT_SUPPORTED;
+    const dim3 grid((unsigned)(((t.g_entries + 31) >> 5) + ((t.s_entries + 31) >> 5)), (unsigned)(d.bs * d.heads));
+    hipLaunchKernelGGL(msda_hm4_repack_i8_kernel, grid, dim3(256), 0, c.st, (const int8_t *)c.value, gset, sset, t,
+                       d.nk, d.heads, c.ref_dtype == BEVOPS_F16 ? 0x80808080u : 0u);
   } else {
-    msda_hm3_repack_launch(value, gset, sset, &t, bs, nk, heads, st);
+    msda_hm3_repack_launch(c.value, gset, sset, t, d.bs, d.nk, d.heads, c.st);
   }
   return launch_status();
 }
 
-int msda_hm4_forward_prepacked(int dtype, int ref_dtype, const void *packed, size_t packed_bytes,
-                               const int32_t *shapes_host, const void *ref, const void *off, const void *logit,
-                               void *out, int bs, int nk, int heads, int C, int L, int nq, int P, int ppg,
-                               int shared, float s_v, float s_o, float s_w, float s_out, int chunk_override,
-                               int ablate, hipStream_t st) {
-  const int LP = L * P;
+int msda_hm4_forward_prepacked(const MsdaCall &c) {
+  const MsdaDims &d = c.d;
+  const int LP = d.L * d.P;
+  const bool i8 = c.dtype == BEVOPS_I8;
   H4Plan pl;
-  if (C != 32 || !packed || (reinterpret_cast<uintptr_t>(packed) & 127u) || !shapes_host ||
-      !h4_plan(shapes_host, bs, heads, L, P, nq, pl, dtype == BEVOPS_I8))
-    return BEVOPS_NOT_SUPPORTED;
-  if ((double)bs * nq * heads * LP * 4.0 >= 4294967040.0) return BEVOPS_NOT_SUPPORTED;  // 32-bit offsets
+  if (!h4_domain(c, pl)) return BEVOPS_NOT_SUPPORTED;
+  if ((double)d.bs * d.nq * d.heads * LP * 4.0 >= 4294967040.0) return BEVOPS_NOT_SUPPORTED;  // 32-bit offsets
   const size_t g_room = (pl.p.g_bytes + 127) & ~size_t(127);
-  if (packed_bytes < g_room + pl.p.s_bytes) return BEVOPS_NOT_SUPPORTED;
-  const char *gset = static_cast<const char *>(packed);
+  if (c.workspace_bytes < g_room + pl.p.s_bytes) return BEVOPS_NOT_SUPPORTED;
+  const char *gset = static_cast<const char *>(c.workspace);
   H4Args a;
   a.gset = gset; a.g_bytes = (unsigned)pl.p.g_bytes; a.sset = gset + g_room;
-  a.ref = ref; a.off = off; a.logit = logit; a.out = out;
-  a.d = MsdaDims{bs, nk, heads, C, L, nq, P, ppg, shared};
+  a.ref = c.ref; a.off = c.off; a.logit = c.logit; a.out = c.out;
+  a.d = d;
   a.t = pl.p.t;
-  a.chunk = h4_chunk(pl.p, nq, chunk_override);
-  if (a.chunk > 0xffff) a.chunk = 0xff00;
-  a.nchunk = (nq + a.chunk - 1) / a.chunk;
+  a.chunk = h4_chunk(pl.p);
+  a.nchunk = (d.nq + a.chunk - 1) / a.chunk;
   a.stage_bytes = pl.p.stage_bytes;
-  a.qmask = nullptr;
-  a.s_v = s_v; a.s_o = s_o; a.s_w = s_w; a.s_out = s_out;
-  const bool i8 = dtype == BEVOPS_I8;
-  if (ablate) return BEVOPS_NOT_SUPPORTED;   // (the timing builds of round 2 are gone)
-  if (dtype == BEVOPS_F16) return h4_dispatch<false, false, __half, false>(LP, pl.nbig, pl.occ2, a, st);
-  if (i8 && ref_dtype == BEVOPS_F32) return h4_dispatch<true, false, float, false>(LP, pl.nbig, pl.occ2, a, st);
-  if (i8 && ref_dtype == BEVOPS_F16) return h4_dispatch<true, true, __half, false>(LP, pl.nbig, pl.occ2, a, st);
+  a.s_v = c.s_v; a.s_o = c.s_o; a.s_w = c.s_w; a.s_out = c.s_out;
+  if (c.dtype == BEVOPS_F16) return h4_dispatch<false, false, __half>(LP, pl.nbig, pl.occ2, a, c.st);
+  if (i8 && c.ref_dtype == BEVOPS_F32) return h4_dispatch<true, false, float>(LP, pl.nbig, pl.occ2, a, c.st);
+  if (i8 && c.ref_dtype == BEVOPS_F16) return h4_dispatch<true, true, __half>(LP, pl.nbig, pl.occ2, a, c.st);
   return BEVOPS_NOT_SUPPORTED;
 }
 
-int msda_hm4_forward(int dtype, int ref_dtype, const void *value, const int32_t *shapes_host, const void *ref,
-                     const void *off, const void *logit, void *out, int bs, int nk, int heads, int C, int L,
-                     int nq, int P, int ppg, int shared, float s_v, float s_o, float s_w, float s_out,
-                     void *workspace, size_t workspace_bytes, int chunk_override, int ablate, hipStream_t st) {
+int msda_hm4_forward(const MsdaCall &c) {
   H4Plan pl;   // (checked first so that an unsupported shape costs no launch)
-  if (C != 32 || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 127u) || !shapes_host ||
-      !h4_plan(shapes_host, bs, heads, L, P, nq, pl, dtype == BEVOPS_I8) || !h4_instantiated(L * P, pl.nbig))
-    return BEVOPS_NOT_SUPPORTED;
-  const int rc = msda_hm4_pack(dtype, ref_dtype, value, shapes_host, bs, nk, heads, C, L, nq, P, workspace,
-                               workspace_bytes, st);
+  if (!h4_domain(c, pl) || !h4_instantiated(c.d.L * c.d.P, pl.nbig)) return BEVOPS_NOT_SUPPORTED;
+  const int rc = msda_hm4_pack(c);
   if (rc == BEVOPS_BAD_PARAM) return BEVOPS_NOT_SUPPORTED;   // workspace too small: the caller's other kernels
   if (rc != BEVOPS_SUCCESS) return rc;
-  return msda_hm4_forward_prepacked(dtype, ref_dtype, workspace, workspace_bytes, shapes_host, ref, off, logit, out,
-                                    bs, nk, heads, C, L, nq, P, ppg, shared, s_v, s_o, s_w, s_out, chunk_override,
-                                    ablate, st);
+  return msda_hm4_forward_prepacked(c);
 }
 
 }  // namespace bevops

@@ -723,7 +723,7 @@ __global__ __launch_bounds__(kH5Threads, 1) void msda_hm5_kernel(
   }
 }
 
-inline int h5_lds_extra(int threads, int chunk) { (void)threads; return chunk * 2 + 128; }   // query list + wave totals
+inline int h5_lds_extra(int chunk) { return chunk * 2 + 128; }   // query list + wave totals
 inline int h5_plan_lds_extra(int chunk) { return chunk * 4; }                                  // the plan's 32-bit entries
 constexpr int kH5Chunk = 1280;
 
@@ -731,7 +731,7 @@ template <int LISTED>
 int h5_go(const Hm3Plan &pl, const char *gset, const char *sset, const __half *ref, const __half *off,
           const __half *logit, __half *out, const MsdaDims &d, const unsigned char *vis, int chunk, hipStream_t st) {
   const int nchunk = (d.nq + chunk - 1) / chunk;
-  const size_t lds = (size_t)pl.stage_bytes + h5_lds_extra(kH5Threads, chunk);
+  const size_t lds = (size_t)pl.stage_bytes + h5_lds_extra(chunk);
   if (lds > (size_t)kLdsLimit) return BEVOPS_NOT_SUPPORTED;
   if (!ensure_dynamic_lds<msda_hm5_kernel<LISTED>>(lds)) return (int)BEVOPS_FAILURE;
   const unsigned planes = (unsigned)(d.bs * d.heads);
@@ -743,59 +743,54 @@ int h5_go(const Hm3Plan &pl, const char *gset, const char *sset, const __half *r
 
 }  // namespace
 
-static bool h5_shape_ok(int C, int L, int P, int ppg) { return C == 32 && L == 4 && P == 8 && ppg == 4; }
+static bool h5_shape_ok(const MsdaDims &d, int ppg) { return d.C == 32 && d.L == 4 && d.P == 8 && ppg == 4; }
+static bool h5_plan(const MsdaDims &d, const int32_t *shapes_host, Hm3Plan &pl) {
+  return hm3_plan(d, shapes_host, h5_lds_extra(kH5Chunk), pl);
+}
 
-// The padded-plane layout hm5 reads, for producers that write it directly (tsgemm.hip: the value projection's
-// epilogue).  `tab` receives the Hm3Tab (untyped: the struct lives in each translation unit's unnamed
-// namespace), `g_room` the bytes reserved for the big set (the staged set follows).
-bool msda_hm5_layout(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq, int P, void *tab,
-                     size_t *g_room, size_t *s_bytes) {
+bool msda_hm5_layout(const MsdaDims &d, const int32_t *shapes_host, Hm3Tab *tab, size_t *g_room, size_t *s_bytes) {
   Hm3Plan pl;
-  if (!h5_shape_ok(C, L, P, 4) || !hm3_plan(shapes_host, bs, heads, L, nq, h5_lds_extra(1024, kH5Chunk), pl) ||
-      pl.t.ls != 2)
-    return false;
-  *static_cast<Hm3Tab *>(tab) = pl.t;
+  if (!h5_shape_ok(d, 4) || !h5_plan(d, shapes_host, pl) || pl.t.ls != 2) return false;
+  *tab = pl.t;
   *g_room = (pl.g_bytes + 127) & ~size_t(127);
   *s_bytes = pl.s_bytes;
   return true;
 }
 
-size_t msda_hm5_workspace_bytes(const int32_t *shapes_host, int bs, int heads, int C, int L, int nq, int P) {
+size_t msda_hm5_workspace_bytes(const MsdaDims &d, const int32_t *shapes_host) {
   Hm3Plan pl;
-  if (!h5_shape_ok(C, L, P, 4) || !hm3_plan(shapes_host, bs, heads, L, nq, h5_lds_extra(1024, kH5Chunk), pl)) return 0;
+  if (!h5_shape_ok(d, 4) || !h5_plan(d, shapes_host, pl)) return 0;
   const size_t planes = ((pl.g_bytes + 127) & ~size_t(127)) + pl.s_bytes;
-  return ((planes + 255) & ~size_t(255)) + (((size_t)bs * nq * heads + 255) & ~size_t(255));   // [planes][visibility bytes]
+  return ((planes + 255) & ~size_t(255)) + ((d.n_item() + 255) & ~size_t(255));   // [planes][visibility bytes]
 }
 
-// Fused SCA sampling on the planes `packed` already holds (written by the value projection's GEMM
+// the domain of the two fused-SCA samplers below (planes in c.workspace); fills the plan
+static bool h5_sca_domain(const MsdaCall &c, Hm3Plan &pl) {
+  const MsdaDims &d = c.d;
+  if (!h5_shape_ok(d, d.ppg) || !c.workspace || (reinterpret_cast<uintptr_t>(c.workspace) & 127u) ||
+      !h5_plan(d, c.shapes_host, pl) || pl.t.ls != 2)
+    return false;
+  return (double)d.nq * d.heads * 32 * 4.0 < 4294967040.0 && (double)d.bs * d.nq * d.heads * 64.0 < 4294967040.0;
+}
+
+// Fused SCA sampling on the planes c.workspace already holds (written by the value projection's GEMM
 // epilogue, bevops_value_proj_packed, or by msda_hm3_repack_launch): camera-shared offsets / logits, the
-// (camera, query) pairs with bev_mask weight 0 skipped, `sampled` [cams, nq, heads, 32] written for the others.
-int msda_hm5_sca_sample_f16(const void *packed, size_t packed_bytes, const int32_t *shapes_host, const __half *ref,
-                            const __half *off, const __half *logit, const __half *qmask, __half *sampled, int bs,
-                            int nk, int heads, int C, int L, int nq, int P, int ppg, hipStream_t st) {
+// (camera, query) pairs with bev_mask weight 0 skipped, c.out = `sampled` [cams, nq, heads, 32] written for the others.
+int msda_hm5_sca_sample_f16(const MsdaCall &c) {
   Hm3Plan pl;
-  if (!h5_shape_ok(C, L, P, ppg) || !packed || (reinterpret_cast<uintptr_t>(packed) & 127u) ||
-      !hm3_plan(shapes_host, bs, heads, L, nq, h5_lds_extra(1024, kH5Chunk), pl) || pl.t.ls != 2)
-    return BEVOPS_NOT_SUPPORTED;
-  if ((double)nq * heads * 32 * 4.0 >= 4294967040.0 || (double)bs * nq * heads * 64.0 >= 4294967040.0) return BEVOPS_NOT_SUPPORTED;
+  if (!h5_sca_domain(c, pl)) return BEVOPS_NOT_SUPPORTED;
   const size_t g_room = (pl.g_bytes + 127) & ~size_t(127);
-  if (packed_bytes < g_room + pl.s_bytes) return BEVOPS_BAD_PARAM;
-  const char *gset = static_cast<const char *>(packed);
-  const MsdaDims d{bs, nk, heads, C, L, nq, P, ppg, 1};
-  return h5_go<2>(pl, gset, gset + g_room, ref, off, logit, sampled, d, reinterpret_cast<const unsigned char *>(qmask),
-                  kH5Chunk, st);
+  if (c.workspace_bytes < g_room + pl.s_bytes) return BEVOPS_BAD_PARAM;
+  const char *gset = static_cast<const char *>(c.workspace);
+  return h5_go<2>(pl, gset, gset + g_room, (const __half *)c.ref, (const __half *)c.off, (const __half *)c.logit,
+                  (__half *)c.out, c.d, static_cast<const unsigned char *>(c.mask), kH5Chunk, c.st);
 }
 
 // ---- the same sampling on a visibility plan (msda_hm5_plan_kernel): balanced slices of the visible (camera, query)
-// pairs, `blocks_per_cu` blocks per CU's worth of slices (1: one slice per CU).
+// pairs, `sca_plan_blocks` blocks per CU's worth of slices (1: one slice per CU).
 // (two slices per CU measured best on the 6-camera rig: 108 us per call against 124 for one block per 1 280-query chunk,
 // 112 / 115 with three / four, profiles/r05/sca_plan_ab.jsonl; touching a slice's offset / logit rows ahead of the loop
 // so that the per-item requests hit the L2 was built and measured SLOWER, 117 us, and removed)
-static thread_local int g_h5_plan_k = 2;
-void msda_hm5_set_plan_blocks(int k) { g_h5_plan_k = k < 1 ? 1 : (k > 8 ? 8 : k); }
-static thread_local bool g_h5_fold = true;      // the FOLD build of the planned kernel (default) / the round-5 build
-void msda_hm5_set_fold(bool on) { g_h5_fold = on; }
-
 size_t msda_hm5_plan_bytes(int bs, int nq) {
   if (bs <= 0 || bs > kPlanCams || nq <= 0 || nq > 65535) return 0;
   return (size_t)kPlanCams * 4 + (size_t)bs * h5_plan_pad(nq) * 4 + (size_t)bs * kPlanBlocks * 4;   // counts, lists, scratch
@@ -816,69 +811,62 @@ int msda_hm5_plan_build(const __half *qmask, int bs, int nq, void *plan, size_t 
 }
 
 constexpr int kH5PlanChunk = 2048;   // list entries of a slice kept in LDS at a time
-int msda_hm5_sca_sample_planned_f16(const void *packed, size_t packed_bytes, const int32_t *shapes_host,
-                                    const __half *ref, const __half *off, const __half *logit, const void *plan,
-                                    size_t plan_bytes, __half *sampled, __half *direct, int bs, int nk, int heads, int C,
-                                    int L, int nq, int P, int ppg, hipStream_t st) {
+int msda_hm5_sca_sample_planned_f16(const MsdaCall &c, const void *plan, size_t plan_bytes, __half *direct) {
+  const MsdaDims &d = c.d;
   Hm3Plan pl;
-  if (!h5_shape_ok(C, L, P, ppg) || !packed || (reinterpret_cast<uintptr_t>(packed) & 127u) ||
-      !hm3_plan(shapes_host, bs, heads, L, nq, h5_lds_extra(1024, kH5Chunk), pl) || pl.t.ls != 2)
-    return BEVOPS_NOT_SUPPORTED;
-  if ((double)nq * heads * 32 * 4.0 >= 4294967040.0 || (double)bs * nq * heads * 64.0 >= 4294967040.0) return BEVOPS_NOT_SUPPORTED;
-  const size_t need = msda_hm5_plan_bytes(bs, nq);
+  if (!h5_sca_domain(c, pl)) return BEVOPS_NOT_SUPPORTED;
+  const size_t need = msda_hm5_plan_bytes(d.bs, d.nq);
   if (need == 0) return BEVOPS_NOT_SUPPORTED;
   // the plan of ANOTHER camera set or query count (a 6-camera plan handed to a camera-sharded rank's subset) has
   // another size: rejected here instead of sampling from the wrong lists
   if (!plan || plan_bytes != need || (reinterpret_cast<uintptr_t>(plan) & 15u)) return BEVOPS_BAD_PARAM;
   const size_t g_room = (pl.g_bytes + 127) & ~size_t(127);
-  if (packed_bytes < g_room + pl.s_bytes) return BEVOPS_BAD_PARAM;
-  const char *gset = static_cast<const char *>(packed);
-  const MsdaDims d{bs, nk, heads, C, L, nq, P, ppg, 1};
-  constexpr int THREADS = kH5Threads;
+  if (c.workspace_bytes < g_room + pl.s_bytes) return BEVOPS_BAD_PARAM;
+  const char *gset = static_cast<const char *>(c.workspace);
   const size_t lds = (size_t)pl.stage_bytes + h5_plan_lds_extra(kH5PlanChunk);
   if (lds > (size_t)kLdsLimit) return BEVOPS_NOT_SUPPORTED;
-  const bool fold = g_h5_fold;
+  const bool fold = g_msda_sel.sca_fold;
   auto kern = fold ? msda_hm5_kernel<3, true> : msda_hm5_kernel<3, false>;
   if (!(fold ? ensure_dynamic_lds<msda_hm5_kernel<3, true>>(lds) : ensure_dynamic_lds<msda_hm5_kernel<3, false>>(lds)))
     return (int)BEVOPS_FAILURE;
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   // slices per head: the CUs an XCD's share of the grid lands on (block i runs on XCD i % 8, head = i % heads)
-  const unsigned per_head = (unsigned)((cus > 0 ? cus : 256) * g_h5_plan_k + heads - 1) / (unsigned)heads;
-  hipLaunchKernelGGL(kern, dim3(per_head * (unsigned)heads), dim3(THREADS), lds, st, gset, (unsigned)pl.g_bytes,
-                     gset + g_room, ref, off, logit, sampled, d, pl.t, kH5PlanChunk, 1, pl.stage_bytes,
-                     static_cast<const unsigned char *>(plan), direct);
+  const unsigned per_head =
+      (unsigned)((cus > 0 ? cus : 256) * g_msda_sel.sca_plan_blocks + d.heads - 1) / (unsigned)d.heads;
+  hipLaunchKernelGGL(kern, dim3(per_head * (unsigned)d.heads), dim3(kH5Threads), lds, c.st, gset, (unsigned)pl.g_bytes,
+                     gset + g_room, (const __half *)c.ref, (const __half *)c.off, (const __half *)c.logit,
+                     (__half *)c.out, d, pl.t, kH5PlanChunk, 1, pl.stage_bytes, static_cast<const unsigned char *>(plan),
+                     direct);
   return launch_status();
 }
 
-// flags (A/B switch of the tests, bevops_msda_set_variant(1000 + flags)): 1 = no visibility pre-pass (every item is
-// sampled; the partner of the default).  The other builds of rounds 3 / 4 -- 768-thread blocks, 2 560-query chunks,
+// `prepass` false (A/B switch of the tests, kMsdaHm5NoPrepass): no visibility pre-pass, every item is
+// sampled; the partner of the default.  The other builds of rounds 3 / 4 -- 768-thread blocks, 2 560-query chunks,
 // records through an LDS mailbox, persistent blocks on strided sub-chunks, no raised priority, the level-class split
 // probe and the ablation (timing) builds -- were measured (design/msda.md, profiles/r03, profiles/r04) and removed from
 // the library in round 5, their template parameters with them.
-int msda_hm5_forward_f16(const __half *value, const int32_t *shapes_host, const __half *ref, const __half *off,
-                         const __half *logit, __half *out, int bs, int nk, int heads, int C, int L, int nq, int P,
-                         int ppg, int shared, void *workspace, size_t workspace_bytes, int flags, bool prepacked,
-                         hipStream_t st) {
+int msda_hm5_forward_f16(const MsdaCall &c, bool prepass) {
+  const MsdaDims &d = c.d;
   Hm3Plan pl;
-  if (!h5_shape_ok(C, L, P, ppg) || shared || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 127u) ||
-      !hm3_plan(shapes_host, bs, heads, L, nq, h5_lds_extra(1024, kH5Chunk), pl))
+  if (!h5_shape_ok(d, d.ppg) || d.shared || !c.workspace || (reinterpret_cast<uintptr_t>(c.workspace) & 127u) ||
+      !h5_plan(d, c.shapes_host, pl))
     return BEVOPS_NOT_SUPPORTED;
   if (pl.t.ls != 2) return BEVOPS_NOT_SUPPORTED;   // two big + two staged levels (the base SCA pyramid)
-  if ((double)bs * nq * heads * 32 * 4.0 >= 4294967040.0) return BEVOPS_NOT_SUPPORTED;  // 32-bit offsets
-  if (workspace_bytes < msda_hm5_workspace_bytes(shapes_host, bs, heads, C, L, nq, P)) return BEVOPS_NOT_SUPPORTED;
-  if (flags & ~1) return BEVOPS_NOT_SUPPORTED;
+  if ((double)d.bs * d.nq * d.heads * 32 * 4.0 >= 4294967040.0) return BEVOPS_NOT_SUPPORTED;  // 32-bit offsets
+  if (c.workspace_bytes < msda_hm5_workspace_bytes(d, c.shapes_host)) return BEVOPS_NOT_SUPPORTED;
   const size_t g_room = (pl.g_bytes + 127) & ~size_t(127);
-  char *gset = static_cast<char *>(workspace);
+  char *gset = static_cast<char *>(c.workspace);
   char *sset = gset + g_room;
   unsigned char *vis = reinterpret_cast<unsigned char *>(gset + ((g_room + pl.s_bytes + 255) & ~size_t(255)));
-  if (!prepacked) msda_hm3_repack_launch(value, gset, sset, &pl.t, bs, nk, heads, st);
-  const MsdaDims d{bs, nk, heads, C, L, nq, P, ppg, shared};
-  if (flags & 1) return h5_go<0>(pl, gset, sset, ref, off, logit, out, d, vis, kH5Chunk, st);
-  const unsigned n_pair = (unsigned)bs * (unsigned)nq;
+  const __half *ref = (const __half *)c.ref, *off = (const __half *)c.off, *logit = (const __half *)c.logit;
+  __half *out = (__half *)c.out;
+  msda_hm3_repack_launch(c.value, gset, sset, pl.t, d.bs, d.nk, d.heads, c.st);
+  if (!prepass) return h5_go<0>(pl, gset, sset, ref, off, logit, out, d, vis, kH5Chunk, c.st);
+  const unsigned n_pair = (unsigned)d.bs * (unsigned)d.nq;
   const unsigned waves = (n_pair + 63u) / 64u;
-  hipLaunchKernelGGL(msda_hm5_vis_kernel, dim3((waves + 3) / 4), dim3(256), 0, st, ref, off, out, vis, d, pl.t, n_pair);
-  return h5_go<1>(pl, gset, sset, ref, off, logit, out, d, vis, kH5Chunk, st);
+  hipLaunchKernelGGL(msda_hm5_vis_kernel, dim3((waves + 3) / 4), dim3(256), 0, c.st, ref, off, out, vis, d, pl.t, n_pair);
+  return h5_go<1>(pl, gset, sset, ref, off, logit, out, d, vis, kH5Chunk, c.st);
 }
 
 }  // namespace bevops

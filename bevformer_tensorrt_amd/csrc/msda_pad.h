@@ -9,7 +9,6 @@
 #include "msda_common.h"
 
 namespace bevops {
-namespace {
 
 constexpr int kHm3MaxLevels = 8;
 constexpr int kEntBytes = 128;   // big levels (fp16: pixel pair; int8: 2x2 footprint)
@@ -23,22 +22,6 @@ struct Hm3Tab {
   int src0[kHm3MaxLevels];      // first source pixel of the level
   int g_entries, s_entries;     // entries per (batch, head) plane of each set
 };
-
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-
-// padded-set entry -> source pixel of the level it falls in, or -1 for a pad
-__device__ __forceinline__ int hm3_source(const Hm3Tab &t, int l0, int l1, int f) {
-  int src = -1;
-  for (int l = l0; l < l1; ++l) {
-    const int Wp = t.W[l] + 1;
-    const int rel = f - t.ent0[l];
-    if (rel >= 0 && rel < (t.H[l] + 2) * Wp) {
-      const int yp = rel / Wp, x = rel - yp * Wp;
-      if (yp >= 1 && yp <= t.H[l] && x < t.W[l]) src = t.src0[l] + (yp - 1) * t.W[l] + x;
-    }
-  }
-  return src;
-}
 
 // level table in LDS, 32 B per level: {float W, float H, u32 byte offset of entry (row 0, col 0),
 // u32 row bytes} {i32 W + 1, u32 log2(bytes per entry), -, -}
@@ -58,7 +41,8 @@ struct Hm3Plan {
 inline int hm3_box_bytes(int LP) { return 128 * ((LP >= 8 ? 8 : LP) * 16 + 16); }
 
 // `box_bytes`: LDS the kernel needs next to the level table and the staged planes
-inline bool hm3_plan(const int32_t *shapes_host, int bs, int heads, int L, int nq, int box_bytes, Hm3Plan &pl) {
+inline bool hm3_plan(const MsdaDims &d, const int32_t *shapes_host, int box_bytes, Hm3Plan &pl) {
+  const int bs = d.bs, heads = d.heads, L = d.L, nq = d.nq;
   if (!shapes_host || L > kHm3MaxLevels) return false;
   Hm3Tab &t = pl.t;
   t.L = L;
@@ -95,6 +79,29 @@ inline bool hm3_plan(const int32_t *shapes_host, int bs, int heads, int L, int n
   pl.s_bytes = (((size_t)bs * heads * pl.stage_bytes) + 127) & ~size_t(127);
   pl.threads = ls < L ? 1024 : 256;
   return pl.g_bytes + 128 < 0xFFFFFF00ull;
+}
+
+// msda_hm3.hip: fp16 re-layout of `value` into the padded sets (hm4's and hm5's fp16 planes have the same layout)
+void msda_hm3_repack_launch(const void *value, char *gset, char *sset, const Hm3Tab &t, int bs, int nk, int heads,
+                            hipStream_t st);
+// msda_hm5.hip: the padded-plane layout hm5 reads, for producers that write it directly (tsgemm.hip: the value
+// projection's epilogue); `g_room`: the bytes reserved for the big set (the staged set follows)
+bool msda_hm5_layout(const MsdaDims &d, const int32_t *shapes_host, Hm3Tab *tab, size_t *g_room, size_t *s_bytes);
+
+namespace {
+
+// padded-set entry -> source pixel of the level it falls in, or -1 for a pad
+__device__ __forceinline__ int hm3_source(const Hm3Tab &t, int l0, int l1, int f) {
+  int src = -1;
+  for (int l = l0; l < l1; ++l) {
+    const int Wp = t.W[l] + 1;
+    const int rel = f - t.ent0[l];
+    if (rel >= 0 && rel < (t.H[l] + 2) * Wp) {
+      const int yp = rel / Wp, x = rel - yp * Wp;
+      if (yp >= 1 && yp <= t.H[l] && x < t.W[l]) src = t.src0[l] + (yp - 1) * t.W[l] + x;
+    }
+  }
+  return src;
 }
 
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));

@@ -703,7 +703,8 @@ extern "C" int bevops_tsgemm_s8(const void *a_q, float scale_a, const void *w_q,
 extern "C" size_t bevops_value_proj_packed_size(const int32_t *spatial_shapes_host, int num_cams, int nk, int heads,
                                                 int channels, int num_levels, int num_query, int num_point) {
   if (!spatial_shapes_host || num_cams <= 0 || nk <= 0) return 0;
-  return msda_hm5_workspace_bytes(spatial_shapes_host, num_cams, heads, channels, num_levels, num_query, num_point);
+  return msda_hm5_workspace_bytes(MsdaDims{num_cams, nk, heads, channels, num_levels, num_query, num_point, 4, 1},
+                                  spatial_shapes_host);
 }
 
 extern "C" int bevops_value_proj_packed(const void *x, const void *weight, const void *bias,
@@ -717,8 +718,8 @@ extern "C" int bevops_value_proj_packed(const void *x, const void *weight, const
   if (total != nk) return BEVOPS_BAD_PARAM;
   TsPacked pk{};
   size_t g_room = 0, s_bytes = 0;
-  if (!msda_hm5_layout(spatial_shapes_host, num_cams, heads, channels, num_levels, num_query, num_point, &pk.t, &g_room,
-                       &s_bytes))
+  const MsdaDims d{num_cams, nk, heads, channels, num_levels, num_query, num_point, 4, 1};
+  if (!msda_hm5_layout(d, spatial_shapes_host, &pk.t, &g_room, &s_bytes))
     return BEVOPS_NOT_SUPPORTED;
   if (packed_bytes < g_room + s_bytes || (reinterpret_cast<uintptr_t>(packed) & 127u)) return BEVOPS_BAD_PARAM;
   const int n = heads * channels, k = n;   // embed -> embed
@@ -748,11 +749,11 @@ extern "C" int bevops_value_pack_planes(const void *value, const int32_t *spatia
   if (!value || !spatial_shapes_host || !packed) return BEVOPS_BAD_PARAM;
   TsPacked pk{};
   size_t g_room = 0, s_bytes = 0;
-  if (!msda_hm5_layout(spatial_shapes_host, num_cams, heads, channels, num_levels, num_query, num_point, &pk.t, &g_room,
-                       &s_bytes))
+  const MsdaDims d{num_cams, nk, heads, channels, num_levels, num_query, num_point, 4, 1};
+  if (!msda_hm5_layout(d, spatial_shapes_host, &pk.t, &g_room, &s_bytes))
     return BEVOPS_NOT_SUPPORTED;
   if (packed_bytes < g_room + s_bytes || (reinterpret_cast<uintptr_t>(packed) & 127u)) return BEVOPS_BAD_PARAM;
-  msda_hm3_repack_launch(value, static_cast<char *>(packed), static_cast<char *>(packed) + g_room, &pk.t, num_cams, nk,
+  msda_hm3_repack_launch(value, static_cast<char *>(packed), static_cast<char *>(packed) + g_room, pk.t, num_cams, nk,
                          heads, static_cast<hipStream_t>(stream));
   return launch_status();
 }

@@ -135,7 +135,8 @@ int bevops_msda_forward_ws(int dtype, const void *value, const int32_t *spatial_
 /* Tuning hook: selects an internal MSDA kernel variant for subsequent calls from
  * this thread (0 = automatic).  Results are identical across variants; exists so
  * tests / tuning scripts can A/B a default against its partner in one process.  The complete list (decoded in
- * csrc/msda.hip: bevops_msda_set_variant, bevops_msda_forward_ws):
+ * csrc/msda.hip: bevops_msda_set_variant, the only place that knows the numbers).  A value that is not on the list
+ * selects the automatic choice, exactly as 0 does, and is handed back as it was given by the next call:
  *    1, 2     other point-splits of the layout-preserving quad kernel;   99  the one-thread-per-output generic kernel
  *    10       never a head-major kernel (what multi_scale_deformable_attn_local uses)
  *    11 / 15  head-major generations hm / hm2 forced;  16  hm3;  17  hm4 wherever it is instantiated
