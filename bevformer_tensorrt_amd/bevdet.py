@@ -25,6 +25,9 @@ import torch.nn as nn
 
 from . import functions as _hip_ops
 
+# data_config of configs/bevdet/bevdet-r50-cbgs.py:44-62, the entries the test pipeline reads
+DATA_CONFIG_R50 = dict(input_size=(256, 704), src_size=(900, 1600), crop_h=(0.0, 0.0), resize_test=0.0)
+
 BEVDET_R50 = dict(
     grid_config=dict(x=[-51.2, 51.2, 0.8], y=[-51.2, 51.2, 0.8], z=[-5, 3, 8], depth=[1.0, 60.0, 1.0]),
     input_size=(256, 704), downsample=16, in_channels=256, out_channels=64)
@@ -431,10 +434,18 @@ class BEVDetRunner:
     "candidates" / "bboxes" -- `get_candidates` / `get_bboxes` in their padded forms.  Inside `step` there is no host
     synchronisation, and a changed calibration needs no new capture.  The upload goes through a small ring of pinned
     host buffers (an asynchronous copy; a pageable source would make the copy wait for the previous frame): the host
-    only waits when it is a whole ring of frames ahead of the device."""
+    only waits when it is a whole ring of frames ahead of the device.
+
+    raw_size=(H0, W0) adds `step_raw`: the frame from the RAW camera images.  The test branch of PrepareImageInputs
+    (loading.py:747-792: PIL's resize, crop, flip; mmlabNormalize) then runs as the first launch of a second captured
+    graph (functions.image_resize_crop_normalize, bit-exact to PIL), reading the static uint8 `raw_buffer` and writing
+    `image_buffer`; flip / scale are sample_augmentation's arguments, data_config defaults to DATA_CONFIG_R50 with
+    the model's input size.  `step` is unchanged and keeps its own graph, so a runner on which both `step` and
+    `step_raw` are called holds two graphs and the frame's activations twice (see `step_raw`)."""
     RING = 4
 
-    def __init__(self, model, device, graph=True, post=None, clone_outputs=True):
+    def __init__(self, model, device, graph=True, post=None, clone_outputs=True, raw_size=None, flip=None, scale=None,
+                 data_config=None):
         if post not in (None, "candidates", "bboxes"):
             raise ValueError(f"post = {post!r}: None, 'candidates' or 'bboxes'")
         self.model, self.device, self.use_graph, self.post, self.clone_outputs = model, device, graph, post, clone_outputs
@@ -444,6 +455,19 @@ class BEVDetRunner:
         self._image_shape, self._dtype = (3, H, W), dtype
         self._in, self._graph, self._outs = None, None, None
         self._ring, self._frame = None, 0
+        self.raw_size, self._graph_raw, self._outs_raw = None, None, None
+        if raw_size is not None:
+            from .functions.image import bevdet_test_augmentation, bevdet_post_transform, image_resize_plan
+            self.raw_size = (int(raw_size[0]), int(raw_size[1]))
+            cfg = dict(DATA_CONFIG_R50 if data_config is None else data_config)
+            if data_config is None:
+                cfg["input_size"] = (H, W)
+            if tuple(cfg["input_size"]) != (H, W):
+                raise ValueError(f"data_config['input_size'] = {cfg['input_size']}, the model takes {(H, W)}")
+            self.resize, self.resize_dims, self.crop, self.flip, rotate = bevdet_test_augmentation(
+                *self.raw_size, cfg, flip=flip, scale=scale)
+            self._plan = image_resize_plan(*self.raw_size, self.resize_dims, self.crop, device)
+            self.post_rot, self.post_tran = bevdet_post_transform(self.resize, self.crop, self.flip)
 
     @property
     def image_buffer(self):
@@ -451,7 +475,16 @@ class BEVDetRunner:
         and passes this very tensor to `step` saves the per-frame copy."""
         return None if self._in is None else self._in["image"]
 
-    def _forward(self):
+    @property
+    def raw_buffer(self):
+        """The static [cams, H0, W0, 3] uint8 buffer `step_raw` reads (after its first call): a caller that decodes its
+        camera frames into it and passes this very tensor to `step_raw` saves the per-frame copy."""
+        return None if self._in is None else self._in.get("raw")
+
+    def _forward(self, raw=False):
+        if raw:
+            fn = getattr(self.model.ops, "image_resize_crop_normalize", _hip_ops.image_resize_crop_normalize)
+            fn(self._in["raw"], self._plan, flip=self.flip, out=self._in["image"][0])
         out = self.model.forward_calibrated(self._in["image"], self._in["calib"])
         if self.post == "candidates":
             return out + tuple(self.model.get_candidates(out, padded=True))
@@ -459,31 +492,60 @@ class BEVDetRunner:
             return out + tuple(self.model.get_bboxes(out, padded=True))
         return out
 
-    def _capture(self):
+    def _capture(self, raw=False):
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):       # warm-up on the capture stream (allocations, library algorithm search)
             for _ in range(2):
-                self._forward()
+                self._forward(raw)
         torch.cuda.current_stream().wait_stream(s)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self._outs = self._forward()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            outs = self._forward(raw)
+        if raw:
+            self._graph_raw, self._outs_raw = graph, outs
+        else:
+            self._graph, self._outs = graph, outs
+
+    def step_raw(self, raw, sensor2ego, ego2global, cam2imgs, bda):
+        """`step` from the RAW camera images [cams, H0, W0, 3] uint8 RGB on the device (raw_size=(H0, W0) at
+        construction): resize, crop, flip and normalisation run on the device as the first launch of the frame's graph,
+        post_rots / post_trans are the ones that augmentation implies (`bevdet_post_transform`).
+
+        `step_raw` replays a captured graph of its own, whose activation pool lies beside that of `step`'s graph: a
+        runner on which BOTH entry points are called holds the frame's activations twice.  A graph is captured at the
+        first call of its entry point, so a runner that only ever calls one of them pays for one."""
+        if self.raw_size is None:
+            raise RuntimeError("step_raw needs BEVDetRunner(..., raw_size=(H0, W0))")
+        n = sensor2ego.shape[1]
+        if raw.dtype != torch.uint8 or tuple(raw.shape) != (n,) + self.raw_size + (3,):
+            raise ValueError(f"raw must be uint8 [{n}, {self.raw_size[0]}, {self.raw_size[1]}, 3]")
+        post_rots = self.post_rot.view(1, 1, 3, 3).repeat(1, n, 1, 1)
+        post_trans = self.post_tran.view(1, 1, 3).repeat(1, n, 1)
+        host = self.model.view.calibration_matrices(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
+        return self._run_frame("raw", raw, host, n)
 
     def step(self, image, sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda):
         """-> (reg, height, dim, rot, vel, heatmap) of `BEVDet.forward`, followed by the padded outputs of
         `get_candidates` (post="candidates") or `get_bboxes` (post="bboxes")."""
         host = self.model.view.calibration_matrices(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
+        return self._run_frame("image", image, host, sensor2ego.shape[1])
+
+    def _run_frame(self, key, source, host, n_cams):
+        """The shared tail of `step` (key = "image") and `step_raw` (key = "raw"): `source` into its static buffer, the
+        calibration upload, the replay of that entry point's graph."""
         if self._in is None:
-            self.n_cams = sensor2ego.shape[1]
+            self.n_cams = n_cams
             self._in = dict(image=torch.zeros((1, self.n_cams) + self._image_shape, device=self.device, dtype=self._dtype),
                             calib=torch.zeros(host.numel(), device=self.device))
             self._ring = [(torch.zeros(host.numel()).pin_memory(), torch.cuda.Event()) for _ in range(self.RING)]
+            if self.raw_size is not None:
+                self._in["raw"] = torch.zeros((self.n_cams,) + self.raw_size + (3,), device=self.device, dtype=torch.uint8)
         i = self._in
         if host.numel() != i["calib"].numel():
             raise ValueError("the number of cameras is fixed by the first frame")
-        if image.data_ptr() != i["image"].data_ptr():      # (the caller may have filled the static buffer itself)
-            i["image"].copy_(image, non_blocking=True)
+        if source.data_ptr() != i[key].data_ptr():          # (the caller may have filled the static buffer itself)
+            i[key].copy_(source, non_blocking=True)
         staged, done = self._ring[self._frame % self.RING]
         self._frame += 1
         done.synchronize()                                  # (returns at once unless the host is RING frames ahead)
@@ -491,12 +553,14 @@ class BEVDetRunner:
         with torch.cuda.device(self.device):
             i["calib"].copy_(staged, non_blocking=True)     # one upload
             done.record()
-        if self.use_graph:
-            if self._graph is None:
-                self._capture()
-            self._graph.replay()
-            return tuple(t.clone() for t in self._outs) if self.clone_outputs else self._outs
-        return self._forward()
+        raw = key == "raw"
+        if not self.use_graph:
+            return self._forward(raw)
+        if (self._graph_raw if raw else self._graph) is None:
+            self._capture(raw)
+        graph, outs = (self._graph_raw, self._outs_raw) if raw else (self._graph, self._outs)
+        graph.replay()
+        return tuple(t.clone() for t in outs) if self.clone_outputs else outs
 
 
 def synthetic_rig(view, n_cams=6, seed=0):

@@ -43,3 +43,128 @@ def image_normalize_pad(images, mean=None, std=None, to_rgb=False, size_divisor=
             _lib.current_stream_ptr(images.device))
     _lib.check(st, "bevops_image_normalize_pad")
     return out
+
+
+# --------------------------------------------------------------------------- BEVDet: PIL-exact resize + crop + normalise
+# (csrc/image_prepare.hip, design/image_prepare.md): what the test branch of the reference's PrepareImageInputs
+# (third_party/bev_mmdet3d/datasets/pipelines/loading.py:691-792) computes, with the image work on the device.
+BEVDET_IMG_NORM = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)   # loading.py:694-696
+
+
+def bevdet_test_augmentation(H, W, data_config, flip=None, scale=None):
+    """The geometry BEVDet's test pipeline gives a raw H x W camera image (PrepareImageInputs.sample_augmentation with
+    is_train=False) -> (resize, resize_dims (W, H), crop (x0, y0, x1, y1), flip, rotate = 0).  All in float64, each
+    int() truncating: the resize ratio is the one that brings the width to the network's, plus `scale` (or the
+    config's resize_test); the crop window has the network's size, is centred horizontally, and its lower edge lies
+    where the mean of crop_h is cut off the bottom of the resized image."""
+    net_h, net_w = data_config["input_size"]
+    extra = data_config.get("resize_test", 0.0) if scale is None else scale
+    resize = float(net_w) / float(W) + extra
+    resized_w, resized_h = int(W * resize), int(H * resize)
+    cut = data_config["crop_h"]
+    lower_edge = int((1 - (cut[0] + cut[1]) / 2) * resized_h)
+    x0 = int(max(0, resized_w - net_w) / 2)
+    y0 = lower_edge - net_h
+    return resize, (resized_w, resized_h), (x0, y0, x0 + net_w, y0 + net_h), bool(flip), 0
+
+
+def bevdet_post_transform(resize, crop, flip):
+    """The map from raw-image pixels to prepared-image pixels that this geometry implies, as BEVDet's view transformer
+    takes it -> (post_rot [3, 3], post_tran [3]) float32: a scale by `resize`, a shift by the crop's corner and, when
+    flipped, the mirror x -> crop width - x.  The values are those of PrepareImageInputs.img_transform at rotate = 0
+    bit for bit (tests/golden/image_prepare.npz): float32(resize) on the diagonal, every zero a +0.0."""
+    x0, y0, x1, y1 = (float(v) for v in crop)
+    s = torch.tensor(float(resize), dtype=torch.float32)            # one rounding, to nearest
+    post_rot, post_tran = torch.zeros(3, 3), torch.zeros(3)
+    post_rot[0, 0], post_rot[1, 1], post_rot[2, 2] = s, s, 1.0
+    post_tran[0], post_tran[1] = 0.0 - x0, 0.0 - y0                 # (0 - x, not -x: a zero offset stays +0.0)
+    if flip:
+        post_rot[0, 0] = -s
+        post_tran[0] = (x1 - x0) - post_tran[0]
+    return post_rot, post_tran
+
+
+class ImageResizePlan:
+    """Pillow's coefficient and bounds tables of one (source size, resize_dims, crop), built on the host by
+    bevops_image_resize_plan_build (layout: include/bevops.h) and held on `device`."""
+    HEADER = 16
+
+    def __init__(self, H0, W0, resize_dims, crop, device):
+        handle = _lib.load_library()
+        self.H0, self.W0 = int(H0), int(W0)
+        self.resize_dims = tuple(int(v) for v in resize_dims)
+        self.crop = tuple(int(v) for v in crop)
+        self.geometry = (self.H0, self.W0) + self.resize_dims + self.crop
+        self.nbytes = handle.bevops_image_resize_plan_size(*self.geometry)
+        if self.nbytes == 0:
+            raise _lib.BevopsError(f"image_resize_plan: geometry {self.geometry} is outside the domain "
+                                   "(include/bevops.h: crop inside the resized image, one tile's window within 64 KiB)",
+                                   _lib.NOT_SUPPORTED)
+        self.host = torch.empty(self.nbytes // 4, dtype=torch.int32)
+        _lib.check(handle.bevops_image_resize_plan_build(*self.geometry, self.host.data_ptr(), self.nbytes),
+                   "bevops_image_resize_plan_build")
+        self.device = torch.device(device)
+        self.tensor = self.host.to(self.device)
+        self.out_size = (self.crop[3] - self.crop[1], self.crop[2] - self.crop[0])      # (fH, fW)
+
+    def tables(self):
+        """(bounds_x [fW, 2], coef_x [fW, ksize_x], bounds_y [fH, 2], coef_y [fH, ksize_y]) int32 host tensors."""
+        fH, fW = self.out_size
+        ksx, ksy = int(self.host[9]), int(self.host[10])
+        sizes = (2 * fW, fW * ksx, 2 * fH, fH * ksy)
+        bx, kx, by, ky = torch.split(self.host[self.HEADER:], sizes)
+        return bx.view(fW, 2), kx.view(fW, ksx), by.view(fH, 2), ky.view(fH, ksy)
+
+
+_PLANS = {}
+
+
+def image_resize_plan(H0, W0, resize_dims, crop, device):
+    """The cached device plan of one geometry: resize_dims = (W, H) and crop = (x0, y0, x1, y1) as
+    `bevdet_test_augmentation` (PIL's conventions) gives them."""
+    key = (int(H0), int(W0), tuple(int(v) for v in resize_dims), tuple(int(v) for v in crop), str(torch.device(device)))
+    if key not in _PLANS:
+        _PLANS[key] = ImageResizePlan(H0, W0, resize_dims, crop, device)
+    return _PLANS[key]
+
+
+def image_resize_crop_normalize(images, plan, flip=False, mean=None, std=None, to_rgb=True, dtype=torch.float16,
+                                channels_last=False, out=None, canvas=None):
+    """images [N, H0, W0, 3] uint8 RGB on the GPU -> [N, 3, fH, fW] `dtype`: img.resize(resize_dims).crop(crop), the
+    optional left-right flip and mmlabNormalize, bit-exact to PIL, one launch, no allocation when `out` (and `canvas`)
+    are given.  canvas: None -- not kept; True -- returned as a new [N, fH, fW, 3] uint8 tensor; a tensor -- filled.
+    Returns `out`, or (out, canvas) when a canvas was asked for."""
+    assert images.is_cuda and images.dim() == 4 and images.shape[-1] == 3
+    if images.dtype != torch.uint8:
+        raise TypeError("images must be uint8")
+    mean = BEVDET_IMG_NORM["mean"] if mean is None else mean
+    std = BEVDET_IMG_NORM["std"] if std is None else std
+    N, H0, W0, _ = images.shape
+    if (H0, W0) != (plan.H0, plan.W0) or plan.tensor.device != images.device:
+        raise ValueError(f"the plan is for {plan.H0} x {plan.W0} images on {plan.tensor.device}")
+    fH, fW = plan.out_size
+    images = images.contiguous()
+    if out is not None and (tuple(out.shape) != (N, 3, fH, fW) or out.device != images.device or not (
+            out.is_contiguous(memory_format=torch.channels_last) if channels_last else out.is_contiguous())):
+        raise ValueError(f"out must be a dense [N, 3, {fH}, {fW}] tensor on the GPU in the requested layout")
+    if out is None:
+        out = torch.empty((N, 3, fH, fW), dtype=dtype, device=images.device,
+                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    if canvas is True:
+        canvas = torch.empty((N, fH, fW, 3), dtype=torch.uint8, device=images.device)
+    elif canvas is not None and canvas is not False:
+        if tuple(canvas.shape) != (N, fH, fW, 3) or canvas.dtype != torch.uint8 or canvas.device != images.device \
+                or not canvas.is_contiguous():
+            raise ValueError(f"canvas must be a dense [N, {fH}, {fW}, 3] uint8 tensor on the GPU")
+    else:
+        canvas = None
+    m = (ctypes.c_double * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_double * 3)(*[float(v) for v in std])
+    handle = _lib.load_library()
+    with torch.cuda.device(images.device):
+        st = handle.bevops_image_resize_crop_normalize(
+            images.data_ptr(), plan.tensor.data_ptr(), plan.nbytes, _lib.torch_dtype_code(out), out.data_ptr(),
+            None if canvas is None else canvas.data_ptr(), N, *plan.geometry, 0, m, s, int(bool(to_rgb)), int(bool(flip)),
+            int(bool(channels_last)), _lib.current_stream_ptr(images.device))
+    _lib.check(st, "bevops_image_resize_crop_normalize")
+    return out if canvas is None else (out, canvas)

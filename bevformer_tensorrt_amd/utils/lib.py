@@ -94,6 +94,11 @@ SIGNATURES = {
                                                                   c_void_p, c_size_t, c_void_p]),
     "bevops_image_normalize_pad": (c_int, [c_int, c_void_p, c_int, c_void_p] + [c_int] * 5 +
                                    [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_int, c_int, c_void_p]),
+    "bevops_image_resize_plan_size": (c_size_t, [c_int] * 8),
+    "bevops_image_resize_plan_build": (c_int, [c_int] * 8 + [c_void_p, c_size_t]),
+    "bevops_image_resize_crop_normalize": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p] + [c_int] * 10 +
+                                           [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_int, c_int,
+                                            c_int, c_void_p]),
     "bevops_quantize_rows": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_float, c_void_p]),
     "bevops_dequantize_rows": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_float, c_void_p]),
     "bevops_linear_int8": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p,

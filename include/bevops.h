@@ -529,6 +529,41 @@ int bevops_mdconv_forward_int8_nhwc(const void *input_nhwc, float scale_in, cons
 int bevops_image_normalize_pad(int in_dtype, const void *images, int out_dtype, void *output, int N,
                                int H0, int W0, int Hp, int Wp, const double *mean_host,
                                const double *std_host, int to_rgb, int channels_last, void *stream);
+/* BEVDet's camera front end (design/image_prepare.md; not a plugin): the test branch of PrepareImageInputs
+ * (third_party/bev_mmdet3d/datasets/pipelines/loading.py:747-754, :691-699) in ONE launch, BIT-EXACT to PIL:
+ * `images` [N, H0, W0, 3] BEVOPS_U8 (RGB, as np.array(Image.open(f)) gives them) -> Image.resize((resize_w, resize_h))
+ * (Pillow's default antialiased bicubic, 8 bits per channel: 22-bit fixed-point coefficients, int32 sums, the
+ * horizontal pass first, clip to uint8 after each pass) -> crop (x0, y0, x1, y1) of the resized image -> left-right
+ * flip of the cropped columns if `flip` -> `canvas_or_null` [N, fH, fW, 3] uint8 (fH = y1 - y0, fW = x1 - x0) and
+ * `output` [N, 3, fH, fW] (channels_last: [N, fH, fW, 3]) BEVOPS_F16 / BEVOPS_F32 = mmcv.imnormalize of the canvas,
+ * as bevops_image_normalize_pad computes it (to_rgb swaps R and B: mmlabNormalize's order).
+ * The PLAN holds Pillow's precompute_coeffs for both axes, restricted to the cropped columns / rows, as int32 words:
+ *   [16 header: magic, H0, W0, resize_w, resize_h, x0, y0, x1, y1, ksize_x, ksize_y, window_w, window_h, 32, 16, 0]
+ *   [fW][2] (first source column, taps)  [fW][ksize_x] coefficients  [fH][2] (first source row, taps)  [fH][ksize_y]
+ * bevops_image_resize_plan_build is a PURE HOST function (doubles, no fused multiply-add, Pillow's operation order)
+ * that fills caller-owned host memory of bevops_image_resize_plan_size bytes; the caller uploads it once per
+ * geometry (4-byte aligned) and the per-frame call only launches: no allocation, no synchronisation, capturable.
+ * DOMAIN: N in 1 .. 65535; all sizes in 1 .. 2^20; the crop non-empty and inside the resized image (PIL would
+ * zero-fill outside: NOT_SUPPORTED); rotate == 0; and the LDS footprint of one 32 x 16 output tile -- its source
+ * window (+ 3 bytes a row), the uint8 intermediate of that window's rows and the tile's coefficients -- at most
+ * 64 KiB.  Every per-axis in / out ratio from 1/4 to 4 is inside (at 4: 80 window rows of 436 + 96 bytes and 3.3 KB
+ * of coefficients, 45 KB); larger ratios are inside when the images are small.  Every coefficient must also fit the
+ * kernel's 24-bit multiplier (|k| < 2^23, a normalised weight below 2: no bicubic geometry is known to miss it);
+ * plan_size and plan_build evaluate that same check BEFORE anything is written, so they agree.  plan_size returns 0
+ * outside the domain; the calls return NOT_SUPPORTED / BAD_PARAM before any device call, and BAD_PARAM unless
+ * plan_bytes == bevops_image_resize_plan_size(same geometry).  The 16 header words are INFORMATIONAL: they let a
+ * host program tell what a stored plan was built for; the device reads the tables only and checks neither the magic
+ * nor the geometry words, so the call trusts that plan_dev is the upload of a plan that plan_build returned
+ * BEVOPS_SUCCESS for with the SAME geometry arguments. */
+size_t bevops_image_resize_plan_size(int H0, int W0, int resize_w, int resize_h, int crop_x0, int crop_y0,
+                                     int crop_x1, int crop_y1);
+int bevops_image_resize_plan_build(int H0, int W0, int resize_w, int resize_h, int crop_x0, int crop_y0, int crop_x1,
+                                   int crop_y1, void *plan_host, size_t plan_bytes);
+int bevops_image_resize_crop_normalize(const void *images, const void *plan_dev, size_t plan_bytes, int out_dtype,
+                                       void *output, void *canvas_or_null, int N, int H0, int W0, int resize_w,
+                                       int resize_h, int crop_x0, int crop_y0, int crop_x1, int crop_y1, int rotate,
+                                       const double *mean_host, const double *std_host, int to_rgb, int flip,
+                                       int channels_last, void *stream);
 /* The MSDA call in two halves, for callers that sample ONE value tensor several times or want the
  * re-layout off their critical path (not a reference plugin: the plugin's enqueue is
  * bevops_msda_forward[_ws], which does both).  `packed` = the padded head-major form of `value`
