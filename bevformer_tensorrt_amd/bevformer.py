@@ -1133,8 +1133,14 @@ class FrameRunner:
     first frame of a scene replays the "no history" graph, every other frame the "history" graph, and
     neither carries the per-layer select between prev_bev and the repeated query."""
 
-    def __init__(self, model, device, dtype, graph=False, cams=None, gather=None, clone_outputs=True, decode=False):
-        """decode=True: the frame also decodes its detections (BEVFormer.get_bboxes, padded form) -- inside the captured
+    def __init__(self, model, device, dtype, graph=False, cams=None, gather=None, clone_outputs=True, decode=False,
+                 raw_size=None):
+        """raw_size=(H0, W0): `step_raw` takes the RAW uint8 camera frames of that size and the UNSCALED dataset
+        lidar2img, and runs the model's own test pipeline (functions.image.BEVFORMER_IMAGE_PIPELINES[model.name]:
+        normalise, rescale, pad; design/image_scale.md) as the first launch of the frame -- under graph=True as the first
+        node of graphs of its own, one per use_prev_bev value, captured at the first raw call.  ValueError when that
+        pipeline does not turn H0 x W0 into the model's input size.
+        decode=True: the frame also decodes its detections (BEVFormer.get_bboxes, padded form) -- inside the captured
         graph under graph=True, with no host synchronisation -- and `step` returns (classes, coords, boxes [1, 300, 9],
         scores [1, 300], labels [1, 300] int32, count [1] int32) instead of (classes, coords).
         clone_outputs=False: under graph replay `step` hands out the graph's own output buffers (valid until the
@@ -1145,8 +1151,17 @@ class FrameRunner:
         nq = model.bev_h * model.bev_w
         self.prev_bev = torch.zeros(nq, 1, EMBED, device=device, dtype=dtype)
         self.prev = {"scene": None, "pos": None, "angle": None}
-        self.use_graph, self._graphs, self._use = graph, {}, 0.0
+        self.use_graph, self._graphs, self._graphs_raw, self._use = graph, {}, {}, 0.0
         H, W = model.cfg["image"]
+        self.raw_size, self.pipeline = None, None
+        if raw_size is not None:
+            from .functions.image import BEVFORMER_IMAGE_PIPELINES, padded_size, scaled_size
+            self.raw_size = (int(raw_size[0]), int(raw_size[1]))
+            self.pipeline = BEVFORMER_IMAGE_PIPELINES[model.name]
+            net = padded_size(*scaled_size(*self.raw_size, self.pipeline["scale"]), self.pipeline["size_divisor"])
+            if tuple(net) != (H, W):
+                raise ValueError(f"raw_size {self.raw_size}: the {model.name} pipeline (scale {self.pipeline['scale']}, "
+                                 f"pad to {self.pipeline['size_divisor']}) gives {net}, the model takes {(H, W)}")
         # the frame's small host-side inputs travel as ONE upload: [can_bus (18) | bev shift (2) | lidar2img (6 x 4 x 4)].
         # The calibration matrices are per-FRAME inputs, as in the reference (an engine input next to can_bus,
         # tools/bevformer/evaluate_trt.py:99,131-132): the camera projection of the BEV pillars and the SCA visibility
@@ -1158,6 +1173,8 @@ class FrameRunner:
                         small=small, can_bus=small[:18], shift=small[18:20].view(1, 2),
                         lidar2img=small[20:].view(1, NUM_CAMS, 4, 4),
                         use=torch.zeros((), device=device, dtype=dtype))
+        if self.raw_size is not None:
+            self._in["raw"] = torch.zeros((NUM_CAMS,) + self.raw_size + (3,), device=device, dtype=torch.uint8)
 
     @property
     def image_buffer(self):
@@ -1166,10 +1183,27 @@ class FrameRunner:
         return self._in["image"]
 
     @property
+    def raw_buffer(self):
+        """The static [6, H0, W0, 3] uint8 buffer `step_raw` reads (None without raw_size): a caller that decodes its
+        camera frames into it and passes this very tensor to `step_raw` saves the per-frame copy."""
+        return self._in.get("raw")
+
+    @property
     def _graph(self):   # the graph of the current use_prev_bev value (None: not captured yet)
         return self._graphs.get(self._use, (None, None))[0]
 
-    def _forward(self):
+    def _prepare(self):
+        """The model's camera pipeline from the static raw buffer into the static image buffer: one launch."""
+        fn = getattr(self.model.ops, "image_normalize_resize_pad", None)
+        if fn is None:
+            raise RuntimeError("the operator set has no image_normalize_resize_pad")
+        p, buf = self.pipeline, self._in["image"][0]
+        fn(self._in["raw"], scale=p["scale"], mean=p["mean"], std=p["std"], to_rgb=p["to_rgb"],
+           size_divisor=p["size_divisor"], dtype=buf.dtype, out=buf)
+
+    def _forward(self, raw=False):
+        if raw:
+            self._prepare()
         if self.gather is not None and self.device.type == "cuda" and not _SHARDED_TABLE_BACKBONE["enabled"]:
             # camera-sharded: every rank must evaluate the REPLICATED layers (TSA, FFN, decoder, heads) with the same
             # kernels.  With _OWN_ENCODER those layers -- everything behind the backbone -- already run on the
@@ -1193,12 +1227,12 @@ class FrameRunner:
         return self.model(i["image"], self.prev_bev, self._use, i["can_bus"], i["lidar2img"], self.cams, self.gather,
                           shift=i["shift"])
 
-    def _capture(self):
+    def _capture(self, raw=False):
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):       # warm-up on the capture stream (allocations, MIOpen find)
             for _ in range(2):
-                out = self._forward()
+                out = self._forward(raw)
                 if self.decode:
                     self.model.get_bboxes(out[1], out[2], padded=True)
         torch.cuda.current_stream().wait_stream(s)
@@ -1215,16 +1249,30 @@ class FrameRunner:
             torch.cuda.synchronize()
             time.sleep(0.35)
         with torch.cuda.graph(graph, **kw):
-            bev, cls, crd = self._forward()
+            bev, cls, crd = self._forward(raw)
             self.prev_bev.copy_(bev)     # state update is part of the graph
             det = self.model.get_bboxes(cls, crd, padded=True) if self.decode else ()
-        self._graphs[self._use] = (graph, (cls, crd) + tuple(det))
+        (self._graphs_raw if raw else self._graphs)[self._use] = (graph, (cls, crd) + tuple(det))
 
     def step_raw(self, raw_images, can_bus, lidar2img, scene_token):
         """Frame from RAW camera images [6, H0, W0, 3] (uint8 or fp32, BGR, on the device): the
         reference's NormalizeMultiviewImage + PadMultiViewImage(32) + format bundle
         (configs/bevformer/bevformer_base.py:11,228-231) run as one HIP pass straight into the frame's
-        static input buffer, then `step`."""
+        static input buffer, then `step`.
+
+        With FrameRunner(..., raw_size=(H0, W0)): raw_images is uint8 [6, H0, W0, 3] and lidar2img the UNSCALED dataset
+        calibration; the model's own pipeline (normalise, rescale, pad) reads the static `raw_buffer` as the first launch
+        of the frame (of its captured graph under graph=True) and lidar2img is scaled by the pipeline's factor
+        (functions.image.scale_lidar2img) on its way into the frame's one small upload.  Passing `raw_buffer` itself
+        skips the copy."""
+        if self.raw_size is not None:
+            from .functions.image import scale_lidar2img
+            buf = self._in["raw"]
+            if raw_images.dtype != torch.uint8 or tuple(raw_images.shape) != tuple(buf.shape):
+                raise ValueError(f"raw_images must be uint8 {list(buf.shape)}")
+            if raw_images.data_ptr() != buf.data_ptr():
+                buf.copy_(raw_images, non_blocking=True)
+            return self._step(None, can_bus, scale_lidar2img(lidar2img, self.pipeline["scale"]), scene_token, raw=True)
         fn = getattr(self.model.ops, "image_normalize_pad", None)
         if fn is None:
             raise RuntimeError("the operator set has no image_normalize_pad")
@@ -1233,6 +1281,10 @@ class FrameRunner:
         return self.step(buf[None], can_bus, lidar2img, scene_token)
 
     def step(self, image, can_bus, lidar2img, scene_token):
+        return self._step(image, can_bus, lidar2img, scene_token)
+
+    def _step(self, image, can_bus, lidar2img, scene_token, raw=False):
+        """The frame from the static buffers; raw: the image buffer is written by the frame's own first launch."""
         can_bus = can_bus.clone().float()
         use_prev = 0.0 if scene_token != self.prev["scene"] else 1.0          # evaluate_trt.py:86-88
         pos, angle = can_bus[:3].clone(), can_bus[-1].clone()
@@ -1244,7 +1296,7 @@ class FrameRunner:
             can_bus[-1] = 0
         self.prev.update(scene=scene_token, pos=pos, angle=angle)
         i = self._in
-        if image.data_ptr() != i["image"].data_ptr():      # (the caller may have filled the static buffer itself)
+        if not raw and image.data_ptr() != i["image"].data_ptr():      # (the caller may have filled the static buffer itself)
             i["image"].copy_(image, non_blocking=True)
         m = self.model
         grid_length = ((PC_RANGE[4] - PC_RANGE[1]) / m.bev_h, (PC_RANGE[3] - PC_RANGE[0]) / m.bev_w)
@@ -1265,17 +1317,18 @@ class FrameRunner:
             i["use"].fill_(use_prev)
         self._use = use_prev
         if self.use_graph:
-            if self._graph is None:
+            graphs = self._graphs_raw if raw else self._graphs
+            if self._use not in graphs:
                 saved = self.prev_bev.clone()
-                self._capture()
+                self._capture(raw)
                 self.prev_bev.copy_(saved)   # capture/warm-up ran the model on scratch state
-            graph, outs = self._graphs[self._use]
+            graph, outs = graphs[self._use]
             graph.replay()
             # the capture's output buffers are overwritten by the next replay: hand out copies
             # (2 x 54 000 values), as the eager path hands out fresh tensors -- unless the caller asked for the
             # buffers themselves
             return tuple(t.clone() for t in outs) if self.clone_outputs else outs
-        bev_embed, cls, crd = self._forward()
+        bev_embed, cls, crd = self._forward(raw)
         self.prev_bev = bev_embed                                               # stays on device (:144)
         if self.decode:
             return (cls, crd) + tuple(self.model.get_bboxes(cls, crd, padded=True))

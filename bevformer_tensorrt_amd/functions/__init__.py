@@ -21,7 +21,8 @@ from .linear import (linear_bias_act, layer_norm, quantize_rows, dequantize_rows
                      dense_auto, tsa_split, queue_mean2)
 from .conv import conv_nhwc, conv3x3_nhwc, conv3x3_auto, conv3x3_c64, conv_int8_nhwc, stem_conv_pool
 from .image import (image_normalize_pad, padded_size, bevdet_test_augmentation, bevdet_post_transform, image_resize_plan,
-                    image_resize_crop_normalize)
+                    image_resize_crop_normalize, BEVFORMER_IMAGE_PIPELINES, scaled_size, scale_lidar2img,
+                    image_normalize_resize_pad)
 from .point_sampling import point_sampling
 from .attention import self_attention_qkv
 from .refine import refine_reference_points, decode_boxes
@@ -54,6 +55,7 @@ __all__ = [
     "bev_nms", "nms_bev", "circle_nms", "bev_iou",
     "lss_voxel_prepare", "lss_lidar_coor", "bev_pool_v2_indirect",
     "bevdet_test_augmentation", "bevdet_post_transform", "image_resize_plan", "image_resize_crop_normalize",
+    "BEVFORMER_IMAGE_PIPELINES", "scaled_size", "scale_lidar2img", "image_normalize_resize_pad",
     "spatial_cross_attention_sample", "spatial_cross_attention_projected", "spatial_cross_attention_plan", "modulated_deformable_conv2d_nhwc", "bias_act_nhwc_", "linear_bias_act", "layer_norm", "rotate_hwc", "conv_offset_nhwc", "upsample_add_nhwc_", "feat_embed_nhwc",
     "msda_pack_value", "multi_scale_deformable_attn_prepacked", "multi_scale_deformable_attn_local", "image_normalize_pad", "padded_size", "quantize_rows", "dequantize_rows", "linear_int8", "tsgemm", "tsgemm_ln", "tile_gemm", "small_gemm", "dense_auto", "tsa_split", "queue_mean2", "conv_nhwc", "conv3x3_nhwc", "conv3x3_auto", "conv3x3_c64", "conv_int8_nhwc", "bias_relu_maxpool_nhwc", "stem_conv_pool", "point_sampling", "self_attention_qkv", "refine_reference_points", "decode_boxes",
 ]

@@ -45,6 +45,74 @@ def image_normalize_pad(images, mean=None, std=None, to_rgb=False, size_divisor=
     return out
 
 
+# --------------------------------------------------------------------------- BEVFormer tiny / small: normalise + rescale + pad
+# (csrc/image_scale.hip, design/image_scale.md): NormalizeMultiviewImage -> RandomScaleImageMultiViewImage -> Pad of the
+# three shipped test pipelines (configs/bevformer/bevformer_tiny.py:19-20,229-231, bevformer_small.py:19,231-233,
+# bevformer_base.py:11,228-231); scale None = the pipeline has no rescale step.
+BEVFORMER_IMAGE_PIPELINES = {
+    "tiny": dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True, scale=0.5, size_divisor=32),
+    "small": dict(mean=[103.530, 116.280, 123.675], std=[1.0, 1.0, 1.0], to_rgb=False, scale=0.8, size_divisor=32),
+    "base": dict(mean=[103.530, 116.280, 123.675], std=[1.0, 1.0, 1.0], to_rgb=False, scale=None, size_divisor=32),
+}
+
+
+def scaled_size(H0, W0, scale):
+    """(height, width) RandomScaleImageMultiViewImage asks mmcv.imresize for (transform_3d.py:424-425): int(size * scale)
+    in Python floats; scale None (no rescale step) leaves the size."""
+    if scale is None:
+        return int(H0), int(W0)
+    return int(H0 * scale), int(W0 * scale)
+
+
+def scale_lidar2img(lidar2img, scale):
+    """diag(s, s, 1, 1) @ lidar2img in float64, then ONE rounding to float32 (transform_3d.py:426-433 followed by
+    tools/bevformer/evaluate_trt.py:99,131-132) for [..., 4, 4] host or device tensors: rows 0 and 1 times `scale`.
+    scale None returns the float32 cast alone."""
+    m = torch.as_tensor(lidar2img).detach().to(torch.float64)
+    if scale is not None:
+        m = m.clone()
+        m[..., :2, :] *= float(scale)
+    return m.to(torch.float32)
+
+
+def image_normalize_resize_pad(images, scale=None, size=None, mean=None, std=None, to_rgb=False, size_divisor=32,
+                               dtype=torch.float16, channels_last=False, out=None):
+    """images [N, H0, W0, 3] uint8 or float32 on the GPU (BGR, as cv2 loads them) -> normalised, resized to
+    `size` = (Hs, Ws) or `scaled_size(H0, W0, scale)` with float32 bilinear interpolation in cv::resize's operation
+    order (include/bevops.h), zero padded to multiples of `size_divisor`: [N, 3, Hp, Wp] `dtype` (memory format
+    channels_last if asked).  One launch, no allocation when `out` is given.  Neither scale nor size: no resize, the
+    result equals image_normalize_pad's bit for bit."""
+    assert images.is_cuda and images.dim() == 4 and images.shape[-1] == 3
+    if images.dtype not in (torch.uint8, torch.float32):
+        raise TypeError("images must be uint8 or float32")
+    if scale is not None and size is not None:
+        raise ValueError("give scale or size, not both")
+    mean = IMG_NORM_CFG["mean"] if mean is None else mean
+    std = IMG_NORM_CFG["std"] if std is None else std
+    N, H0, W0, _ = images.shape
+    Hs, Ws = (int(size[0]), int(size[1])) if size is not None else scaled_size(H0, W0, scale)
+    if Hs <= 0 or Ws <= 0:
+        raise ValueError(f"the resized image would be {Hs} x {Ws}")
+    Hp, Wp = padded_size(Hs, Ws, size_divisor)
+    images = images.contiguous()
+    if out is not None and (tuple(out.shape) != (N, 3, Hp, Wp) or not out.is_cuda or not (
+            out.is_contiguous(memory_format=torch.channels_last) if channels_last else out.is_contiguous())):
+        raise ValueError(f"out must be a dense [N, 3, {Hp}, {Wp}] tensor on the GPU in the requested layout")
+    if out is None:
+        out = torch.empty((N, 3, Hp, Wp), dtype=dtype, device=images.device,
+                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    m = (ctypes.c_double * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_double * 3)(*[float(v) for v in std])
+    handle = _lib.load_library()
+    with torch.cuda.device(images.device):
+        st = handle.bevops_image_normalize_resize_pad(
+            _lib.U8 if images.dtype == torch.uint8 else _lib.F32, images.data_ptr(), _lib.torch_dtype_code(out),
+            out.data_ptr(), N, H0, W0, Hs, Ws, Hp, Wp, m, s, int(bool(to_rgb)), int(bool(channels_last)),
+            _lib.current_stream_ptr(images.device))
+    _lib.check(st, "bevops_image_normalize_resize_pad")
+    return out
+
+
 # --------------------------------------------------------------------------- BEVDet: PIL-exact resize + crop + normalise
 # (csrc/image_prepare.hip, design/image_prepare.md): what the test branch of the reference's PrepareImageInputs
 # (third_party/bev_mmdet3d/datasets/pipelines/loading.py:691-792) computes, with the image work on the device.

@@ -564,6 +564,29 @@ int bevops_image_resize_crop_normalize(const void *images, const void *plan_dev,
                                        int resize_h, int crop_x0, int crop_y0, int crop_x1, int crop_y1, int rotate,
                                        const double *mean_host, const double *std_host, int to_rgb, int flip,
                                        int channels_last, void *stream);
+/* BEVFormer tiny / small camera front end (design/image_scale.md; not a plugin): NormalizeMultiviewImage ->
+ * RandomScaleImageMultiViewImage(scales=[s]) -> PadMultiViewImage (configs/bevformer/bevformer_tiny.py:19-20,229-231,
+ * bevformer_small.py:19,231-233; third_party/bev_mmdet3d/datasets/pipelines/transform_3d.py:404-438) in ONE launch.
+ * `images` [N, H0, W0, 3] BEVOPS_U8 or BEVOPS_F32 (BGR as loaded) -> every tap normalised as
+ * bevops_image_normalize_pad computes it -> float32 bilinear resize to [Hs, Ws] in the operation order of
+ * cv::resize(INTER_LINEAR): per axis scale = 1 / (double(out) / double(in)), position f = float32((d + 0.5) * scale -
+ * 0.5) (double arithmetic, one rounding), tap i = floor(f), f -= i; i < 0: i = 0, f = 0; i >= in - 1: i = in - 1,
+ * f = 0 (second tap clamped to in - 1); weights (1 - f, f); one pass = fl(fl(a * w0) + fl(b * w1)), never contracted;
+ * the HORIZONTAL pass first, the vertical pass on its float32 result; in == 2 * out in BOTH axes takes the area form
+ * fl(fl(fl(fl(a + b) + c) + d) * 0.25f) (a, b upper source row, c, d lower) -> zero padding bottom / right to
+ * [Hp, Wp] -> `output` [N, 3, Hp, Wp] (channels_last: [N, Hp, Wp, 3]) BEVOPS_F16 (its own rounding of the fp32 value)
+ * or BEVOPS_F32.  Parity against cv2 itself is UNPINNED; the contract is the numpy restatement of this order in
+ * tests/util_image_scale.py, bit for bit.  At Hs == H0, Ws == W0 the result equals bevops_image_normalize_pad's.
+ * One launch, no workspace, no allocation, no synchronisation, capturable; coefficients are evaluated on the device.
+ * DOMAIN: N in 1 .. 65535; sizes in 1 .. 2^20; the LDS footprint of one 64 x 8 output tile -- its uint8 source window
+ * (+ 6 bytes a row) and the float32 horizontal-pass result of that window's rows (768 bytes a row; none in the area
+ * form) -- at most 64 KiB: every per-axis ratio in / out from 1/2 to 4 is inside for both input types (at 4 in both
+ * axes: 34 window rows of 780 + 768 bytes = 52 KB); larger ratios are inside while the images are small.
+ * BAD_PARAM: null pointers, non-positive sizes, Hp < Hs, Wp < Ws, std <= 0, misaligned output;  NOT_SUPPORTED: other
+ * dtypes, geometry outside the domain; every status is returned before any device call. */
+int bevops_image_normalize_resize_pad(int in_dtype, const void *images, int out_dtype, void *output, int N,
+                                      int H0, int W0, int Hs, int Ws, int Hp, int Wp, const double *mean_host,
+                                      const double *std_host, int to_rgb, int channels_last, void *stream);
 /* The MSDA call in two halves, for callers that sample ONE value tensor several times or want the
  * re-layout off their critical path (not a reference plugin: the plugin's enqueue is
  * bevops_msda_forward[_ws], which does both).  `packed` = the padded head-major form of `value`
