@@ -367,6 +367,15 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(const float *__restric
 // full-Cout M tile.
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
+// A corner outside the image is SKIPPED, as the reference and im2col_nhwc_kernel skip it, not gathered from somewhere
+// and multiplied by a zero weight (0 * inf = NaN: one overflowed activation at pixel (0, 0) would reach every output
+// whose footprint leaves the image).  Its gather carries this per-lane byte offset: past the end of the image's
+// buffer descriptor (run() keeps the image below 0xFFFFFF00 bytes), so the descriptor's range check -- made on the
+// per-lane offset alone, the scalar offset of the k-step does not enter it -- returns zeros without a memory access,
+// exactly as the weight rows past Cout do (a_off = 0xFFFFFFF0).  0x20 below the top so that the second 16-byte vector
+// of the 256-thread register-staged kernel (offset + 16) neither wraps nor comes back into range.
+constexpr unsigned kDcnSkipOff = 0xFFFFFFE0u;
+
 __device__ __forceinline__ unsigned pk_fma(unsigned a, unsigned w, unsigned c) {
   const f16x2 r = __builtin_bit_cast(f16x2, a) * __builtin_bit_cast(f16x2, w) + __builtin_bit_cast(f16x2, c);
   return __builtin_bit_cast(unsigned, r);
@@ -496,7 +505,7 @@ __global__ __launch_bounds__(THREADS, 2) void dcn_fused_f16_kernel(
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const bool ok = in && hs[q] >= 0 && hs[q] <= d.H - 1 && ws[q] >= 0 && ws[q] <= d.W - 1;
-        fidx[q] = (int)(ximg_off + (unsigned)(ok ? hs[q] * d.W + ws[q] : 0) * (unsigned)(d.Cin * 2));
+        fidx[q] = ok ? (int)(ximg_off + (unsigned)(hs[q] * d.W + ws[q]) * (unsigned)(d.Cin * 2)) : (int)kDcnSkipOff;
         const float w = ok ? wq[q] * m : 0.f;
         fw[q] = pack_h2(w, w);
       }
@@ -504,7 +513,7 @@ __global__ __launch_bounds__(THREADS, 2) void dcn_fused_f16_kernel(
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-      for (int v = 0; v < NB; ++v)
+      for (int v = 0; v < NB; ++v)   // (NB <= 2: kDcnSkipOff + 16 * v stays past the descriptor's end, no wrap)
         rb[q][v] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, fidx[q] + 16 * v, c0 * 2, 0));
     const int a_s = (tap * cin_g + c0) * 2;
 #pragma unroll
@@ -747,7 +756,7 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const bool ok = in && hs[q] >= 0 && hs[q] <= d.H - 1 && ws[q] >= 0 && ws[q] <= d.W - 1;
-      fidx[q] = (int)(ximg_off + (unsigned)(ok ? hs[q] * d.W + ws[q] : 0) * (unsigned)(d.Cin * 2));
+      fidx[q] = ok ? (int)(ximg_off + (unsigned)(hs[q] * d.W + ws[q]) * (unsigned)(d.Cin * 2)) : (int)kDcnSkipOff;
       const float w = ok ? wq[q] * m : 0.f;
       fw[q] = pack_h2(w, w);
     }
@@ -1189,6 +1198,10 @@ static int mdconv_forward_impl(int dtype, const void *input, const void *offset,
                  groups, deform_groups))
     return BEVOPS_BAD_PARAM;
   if (dtype != BEVOPS_F32 && dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  // the raw offset-convolution output is read as [2 KK offsets | KK mask logits] of ONE deform group (a pack with
+  // several groups lays its channels out differently, and the 32-bit read of an (h, w) pair at half-word
+  // dg * 3 KK + 2 tap would be misaligned for odd dg * KK); bevops_mdconv_forward_int8_nhwc draws the same line
+  if (om_channels && deform_groups != 1) return BEVOPS_NOT_SUPPORTED;
   if (workspace_bytes < ws_layout(d, dtype == BEVOPS_F32 ? 4 : 2).total) return BEVOPS_BAD_PARAM;
   if (!aligned16(workspace) || (packed && !aligned16(weight))) return BEVOPS_BAD_PARAM;
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -308,9 +308,11 @@ int bevops_mdconv_pack_weight(int dtype, const void *weight, void *packed, int C
  * input and output NHWC, packed weights, optional fused ReLU; fp16 fused-kernel domain only
  * (NOT_SUPPORTED otherwise).  offset_mask_channels == 0: offset / mask keep the reference's
  * planar [B, ., Ho, Wo] layout.  offset_mask_channels == OC > 0: `offset` is the raw channels-last
- * output [B, Ho, Wo, OC] of the pack's offset convolution (cnn/dcn.py:62-70: 2*KK offset channels
- * then KK mask logits per deform group, OC >= deform_groups*3*KK, even), `mask` is ignored and
- * the sigmoid is applied in the kernel. */
+ * output [B, Ho, Wo, OC] of the pack's offset convolution (cnn/dcn.py:62-70) for ONE deform group:
+ * 2*KK offset channels (h, w per tap) then KK mask logits, OC >= 3*KK and even (BAD_PARAM otherwise),
+ * channels >= 3*KK ignored; `mask` is ignored and the sigmoid is applied in the kernel.
+ * deform_groups > 1 with offset_mask_channels > 0 is NOT_SUPPORTED (a pack with several deform groups
+ * orders its channels differently); planar offsets take any deform_groups of the fused domain. */
 int bevops_mdconv_forward_nhwc(int dtype, const void *input_nhwc, const void *offset,
                                const void *mask, const void *packed_weight, const void *bias,
                                void *output_nhwc, int relu, int offset_mask_channels,
