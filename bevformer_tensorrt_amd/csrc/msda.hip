@@ -721,9 +721,10 @@ extern "C" size_t bevops_msda_workspace_size(int dtype, int bs, int nk, int head
   const MsdaDims d{bs, nk, heads, channels, num_levels, num_query, num_point, 0, 0};
   if (dtype == BEVOPS_I8) {
     // padded head-major int8 planes (msda_hm4.hip): 128-byte entries, at most (H + 2)(W + 1) <= 3 H W
-    // + 2 of them per level -- an upper bound; bevops_msda_workspace_size_shapes gives the exact size
+    // + 3 of them per level (equality on a one-row level; + 2 holds only from two rows on), plus the lead and trail
+    // entries of the two sets -- an upper bound; bevops_msda_workspace_size_shapes gives the exact size
     if (channels != 32 || msda_head_major_order(dtype, d, nullptr, true, true, g_msda_sel).n == 0) return 0;
-    return (size_t)bs * heads * ((size_t)3 * nk + 2 * num_levels + 4) * 128 + 4096;
+    return (size_t)bs * heads * ((size_t)3 * nk + 3 * num_levels + 4) * 128 + 4096;
   }
   if (dtype != BEVOPS_F16) return 0;
   return msda_hm_workspace_bytes(d);
@@ -820,6 +821,8 @@ extern "C" int bevops_sca_forward(int dtype, const void *value, const int32_t *s
       !shapes_cover(spatial_shapes_host, num_levels, nk))
     return BEVOPS_BAD_PARAM;
   if (dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  // the sampler's planes need 128-byte alignment (include/bevops.h); this entry has no other kernel to fall back to
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 127u)) return BEVOPS_BAD_PARAM;
   return msda_hm3_sca_forward_f16(sca_call(value, spatial_shapes_host, reference_points_cam, sampling_offsets,
                                            attention_weights, bev_mask, output, num_cams, nk, heads, channels,
                                            num_levels, num_query, num_point, points_per_group, workspace,

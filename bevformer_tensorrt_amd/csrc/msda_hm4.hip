@@ -757,6 +757,8 @@ bool h4_domain(const MsdaCall &c, H4Plan &pl) {
 size_t msda_hm4_workspace_bytes(const MsdaDims &d, const int32_t *shapes_host, bool i8) {
   H4Plan pl;
   if (d.C != 32 || !shapes_host || !h4_plan(d, shapes_host, i8, pl)) return 0;
+  // 0 exactly where the sampler has no kernel: a size the caller could pack into and never sample from is no size
+  if (!h4_instantiated(d.L * d.P, pl.nbig)) return 0;
   return ((pl.p.g_bytes + 127) & ~size_t(127)) + 128 + pl.p.s_bytes;
 }
 
@@ -775,7 +777,7 @@ bool msda_hm4_all_staged(const MsdaDims &d, const int32_t *shapes_host) {
 int msda_hm4_pack(const MsdaCall &c) {
   const MsdaDims &d = c.d;
   H4Plan pl;
-  if (!h4_domain(c, pl)) return BEVOPS_NOT_SUPPORTED;
+  if (!h4_domain(c, pl) || !h4_instantiated(d.L * d.P, pl.nbig)) return BEVOPS_NOT_SUPPORTED;
   if (c.dtype != BEVOPS_F16 && c.dtype != BEVOPS_I8) return BEVOPS_NOT_SUPPORTED;
   const size_t g_room = (pl.p.g_bytes + 127) & ~size_t(127);
   if (c.workspace_bytes < g_room + pl.p.s_bytes) return BEVOPS_BAD_PARAM;

@@ -703,8 +703,14 @@ extern "C" int bevops_tsgemm_s8(const void *a_q, float scale_a, const void *w_q,
 extern "C" size_t bevops_value_proj_packed_size(const int32_t *spatial_shapes_host, int num_cams, int nk, int heads,
                                                 int channels, int num_levels, int num_query, int num_point) {
   if (!spatial_shapes_host || num_cams <= 0 || nk <= 0) return 0;
-  return msda_hm5_workspace_bytes(MsdaDims{num_cams, nk, heads, channels, num_levels, num_query, num_point, 4, 1},
-                                  spatial_shapes_host);
+  // 0 exactly where bevops_value_proj_packed answers NOT_SUPPORTED: whole 256-column tiles, the two-level staging
+  if (heads <= 0 || channels != 32 || (heads * channels) % kTsBN != 0) return 0;
+  const MsdaDims d{num_cams, nk, heads, channels, num_levels, num_query, num_point, 4, 1};
+  Hm3Tab tab;
+  size_t g_room = 0, s_bytes = 0;
+  if (!msda_hm5_layout(d, spatial_shapes_host, &tab, &g_room, &s_bytes)) return 0;
+  if ((double)num_cams * nk * heads * channels * 2 >= 4294967040.0) return 0;
+  return msda_hm5_workspace_bytes(d, spatial_shapes_host);
 }
 
 extern "C" int bevops_value_proj_packed(const void *x, const void *weight, const void *bias,

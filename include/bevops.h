@@ -108,8 +108,12 @@ int bevops_msda_forward(int dtype, const void *value, const int32_t *spatial_sha
  * lets the library re-lay `value` out head-major ([bs][heads][keys][32]) so that the two
  * x-corners of a sample share one cache line and each XCD's L2 holds the (camera, head)
  * plane it gathers from.  bevops_msda_workspace_size returns the bytes required (0 = the
- * path does not apply: non-fp16, channels != 32, ...); a NULL / too small workspace simply
- * selects the layout-preserving kernels, results are identical within fp32 rounding.
+ * path does not apply: channels != 32, ...); a NULL / too small workspace, or one that is not
+ * 128-BYTE ALIGNED, simply selects the layout-preserving kernels (a family forced with
+ * bevops_msda_set_variant returns BEVOPS_NOT_SUPPORTED instead), results are identical within
+ * fp32 rounding.  The library writes inside the first bevops_msda_workspace_size[_shapes] bytes only.
+ * For BEVOPS_I8 this query is an UPPER BOUND of the exact, shape-aware size: 3 nk + 3 num_levels + 4
+ * entries of 128 bytes per (batch, head) plane, plus 4096.
  * shared_offsets = 1: sampling_offsets / attention_weights are [1, num_query, heads, .] and
  * apply to every one of the bs value batches (BEVFormer's SCA repeats the same query for
  * all cameras, det2trt/models/modules/spatial_cross_attention.py:254) -- identical result
@@ -118,7 +122,9 @@ size_t bevops_msda_workspace_size(int dtype, int bs, int nk, int heads, int chan
                                   int num_levels, int num_query, int num_point);
 /* Same, for a caller that knows the level shapes on the host ([num_levels][2] = (H, W)):
  * also covers the zero-padded re-layout with LDS-resident small levels (msda_hm3.hip), whose
- * size depends on the level shapes.  >= bevops_msda_workspace_size. */
+ * size depends on the level shapes.  BEVOPS_F16: the largest need of every family that may serve
+ * the call, >= bevops_msda_workspace_size.  BEVOPS_I8: the exact size of the padded planes,
+ * <= bevops_msda_workspace_size (0: the shape is outside the head-major domain). */
 size_t bevops_msda_workspace_size_shapes(int dtype, const int32_t *spatial_shapes_host, int bs,
                                          int nk, int heads, int channels, int num_levels,
                                          int num_query, int num_point);
@@ -235,6 +241,8 @@ int bevops_bev_pool_v2_forward(int dtype, const void *depth, const void *feat,
  *   value [num_cams, nk, heads, C] fp16, reference_points_cam [num_cams, nq, 1, 2*ppg] fp16,
  *   bev_mask [num_cams, nq] fp16 (0 = not visible, else the weight), output [nq, heads, C] fp16.
  * F16, C == 32 only (NOT_SUPPORTED otherwise: compose the reference sequence instead).
+ * workspace: bevops_sca_workspace_size bytes (0 = unsupported arguments), 128-BYTE ALIGNED; a NULL, misaligned or
+ * short one is BEVOPS_BAD_PARAM (this entry has no other kernel to fall back to).
  * ------------------------------------------------------------------------ */
 size_t bevops_sca_workspace_size(int dtype, const int32_t *spatial_shapes_host, int num_cams, int nk,
                                  int heads, int channels, int num_levels, int num_query,
@@ -595,7 +603,9 @@ int bevops_image_normalize_resize_pad(int in_dtype, const void *images, int out_
  * (csrc/msda_pad.h, msda_hm4.hip), bevops_msda_packed_size() bytes, 128-byte aligned, caller-owned;
  * it depends on (dtype, shapes, bs, heads, num_query, num_point) and, for int8, on the flavour
  * (ref_dtype).  packed_size == 0 / NOT_SUPPORTED: shape outside the head-major domain (32 channels
- * per head, the instantiated (levels x points) combinations) -- use bevops_msda_forward. */
+ * per head, the instantiated (levels x points, staged levels) combinations) -- use bevops_msda_forward.
+ * bevops_msda_packed_size returns 0 exactly where bevops_msda_pack_value and
+ * bevops_msda_forward_prepacked return BEVOPS_NOT_SUPPORTED for the same arguments. */
 size_t bevops_msda_packed_size(int dtype, const int32_t *spatial_shapes_host, int bs, int nk, int heads,
                                int channels, int num_levels, int num_query, int num_point);
 int bevops_msda_pack_value(int dtype, int ref_dtype, const void *value, const int32_t *spatial_shapes_host,
