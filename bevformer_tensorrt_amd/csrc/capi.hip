@@ -128,6 +128,10 @@ const Entry kTable[] = {
     {"bevops_conv3x3_c32_pack_weight", (void *)&bevops_conv3x3_c32_pack_weight},
     {"bevops_conv3x3_c32_packed_weight_size", (void *)&bevops_conv3x3_c32_packed_weight_size},
     {"bevops_layer_norm", (void *)&bevops_layer_norm},
+    {"bevops_calib_state_size", (void *)&bevops_calib_state_size},
+    {"bevops_calib_collect", (void *)&bevops_calib_collect},
+    {"bevops_calib_threshold_workspace_size", (void *)&bevops_calib_threshold_workspace_size},
+    {"bevops_calib_threshold", (void *)&bevops_calib_threshold},
 };
 }  // namespace
 

@@ -31,6 +31,7 @@ from .inverse import inverse
 from .decode import nms_free_decode, centerpoint_decode
 from .nms import bev_nms, nms_bev, circle_nms, bev_iou
 from .lss_prepare import lss_voxel_prepare, lss_lidar_coor, bev_pool_v2_indirect
+from .calibrate import calib_state_size, calib_collect, calib_threshold
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -54,6 +55,7 @@ __all__ = [
     "nms_free_decode", "centerpoint_decode",
     "bev_nms", "nms_bev", "circle_nms", "bev_iou",
     "lss_voxel_prepare", "lss_lidar_coor", "bev_pool_v2_indirect",
+    "calib_state_size", "calib_collect", "calib_threshold",
     "bevdet_test_augmentation", "bevdet_post_transform", "image_resize_plan", "image_resize_crop_normalize",
     "BEVFORMER_IMAGE_PIPELINES", "scaled_size", "scale_lidar2img", "image_normalize_resize_pad",
     "spatial_cross_attention_sample", "spatial_cross_attention_projected", "spatial_cross_attention_plan", "modulated_deformable_conv2d_nhwc", "bias_act_nhwc_", "linear_bias_act", "layer_norm", "rotate_hwc", "conv_offset_nhwc", "upsample_add_nhwc_", "feat_embed_nhwc",

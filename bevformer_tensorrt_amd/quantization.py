@@ -7,7 +7,8 @@ wraps `trt.IInt8MinMaxCalibrator` / `IInt8EntropyCalibrator2` / `IInt8LegacyCali
 pytorch_quantization's max / 99.99-percentile histogram calibrators
 (det2trt/quantization/calibrator_qdq.py:29-80).  Neither library exists on ROCm, so the
 published algorithms are restated here as host logic (torch tensors, histograms on the
-device the data lives on):
+device the data lives on); the `*_device` calibrators further down keep the same statistics on the
+device (csrc/calibrate.hip) and add the calibration cache the reference's calibrator leaves empty:
 
   * MinMaxCalibrator      scale = max|x| / 127 over all calibration batches
   * PercentileCalibrator  scale = percentile(|x|, p) / 127 from a running histogram (p = 99.99)
@@ -111,6 +112,14 @@ class EntropyCalibrator(_Histogram):
 def entropy_threshold_bin(hist, num_levels=_NUM_LEVELS):
     """Clip bin minimising KL(P || Q) as described in the module docstring.  All candidate clip
     bins are evaluated at once (a [candidates, bins] batch) instead of one Python iteration each."""
+    kl = entropy_kl_curve(hist, num_levels)
+    best = int(torch.argmin(kl))                                 # first minimum, like the loop
+    return num_levels + best - 1 if math.isfinite(float(kl[best])) else hist.numel() - 1
+
+
+def entropy_kl_curve(hist, num_levels=_NUM_LEVELS):
+    """KL(P || Q) for every candidate i = num_levels .. bins kept bins (float64 [bins - num_levels + 1], +inf where
+    P or Q is empty): the curve entropy_threshold_bin takes the first minimum of."""
     hist = hist.double().cpu().clone()
     # the bin at zero takes the count of its neighbour (pytorch_quantization's histogram calibrator does the same,
     # `bins[0] = bins[1]` in _compute_amax_entropy): the exact zeros a ReLU emits -- half of the tensor or more --
@@ -140,12 +149,237 @@ def entropy_threshold_bin(hist, num_levels=_NUM_LEVELS):
     term = torch.where(pn > 0, pn * torch.log(pn.clamp(min=1e-300) / qn), torch.zeros_like(pn))
     kl = term.sum(1)
     kl[~ok[:, 0]] = math.inf
-    best = int(torch.argmin(kl))                                 # first minimum, like the loop
-    return int(cand[best]) - 1 if math.isfinite(float(kl[best])) else n - 1
+    return kl
+
+_CACHE_FORMAT = "bevops-calibration-1"
+_STATE_BYTES = 64 + 8 * _NUM_BINS          # bevops_calib_state_size(): tests hold the two equal
+_CACHE_KEYS = ("format", "names", "range", "amax", "count", "nonfinite", "batches", "hist", "extra")
+
+
+def unpack_calibration_states(raw):
+    """uint8 [S, 16448] state bytes (include/bevops.h, "PTQ calibration on the device") -> dict of numpy fields."""
+    import numpy as np
+    raw = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1, _STATE_BYTES)
+    head = raw[:, :64]
+    f32 = np.ascontiguousarray(head[:, :12]).view(np.float32)
+    return {"range": f32[:, 0].copy(), "amax": f32[:, 1].copy(),
+            "batches": np.ascontiguousarray(head[:, 12:16]).view(np.uint32)[:, 0].copy(),
+            "count": np.ascontiguousarray(head[:, 16:24]).view(np.uint64)[:, 0].copy(),
+            "nonfinite": np.ascontiguousarray(head[:, 24:32]).view(np.uint64)[:, 0].copy(),
+            "hist": np.ascontiguousarray(raw[:, 64:]).view(np.uint64).reshape(-1, _NUM_BINS).copy()}
+
+
+def pack_calibration_states(fields):
+    """The inverse of unpack_calibration_states: uint8 [S, 16448] (the scratch fields of the header are zero)."""
+    import numpy as np
+    n = len(fields["range"])
+    raw = np.zeros((n, _STATE_BYTES), dtype=np.uint8)
+    raw[:, 0:4] = np.asarray(fields["range"], dtype=np.float32).reshape(n, 1).view(np.uint8)
+    raw[:, 4:8] = np.asarray(fields["amax"], dtype=np.float32).reshape(n, 1).view(np.uint8)
+    raw[:, 12:16] = np.asarray(fields["batches"], dtype=np.uint32).reshape(n, 1).view(np.uint8)
+    raw[:, 16:24] = np.asarray(fields["count"], dtype=np.uint64).reshape(n, 1).view(np.uint8)
+    raw[:, 24:32] = np.asarray(fields["nonfinite"], dtype=np.uint64).reshape(n, 1).view(np.uint8)
+    raw[:, 64:] = np.ascontiguousarray(fields["hist"], dtype=np.uint64).reshape(n, _NUM_BINS).view(np.uint8)
+    return raw
+
+
+def write_calibration_cache(path, names, fields, extra=None):
+    """One .npz (no pickle): format, names, range, amax, count, nonfinite, batches, hist [S, 2048] uint64, and `extra`
+    as a JSON string.  What the reference's calibrator leaves as `pass`
+    (det2trt/quantization/calibrator_trt.py:86-90)."""
+    import json
+
+    import numpy as np
+    names = list(names)
+    assert len(names) == len(fields["range"]) and len(set(names)) == len(names)
+    with open(path, "wb") as f:
+        np.savez(f, format=np.array(_CACHE_FORMAT), names=np.array(names, dtype=np.str_),
+                 range=np.asarray(fields["range"], dtype=np.float32), amax=np.asarray(fields["amax"], dtype=np.float32),
+                 count=np.asarray(fields["count"], dtype=np.uint64),
+                 nonfinite=np.asarray(fields["nonfinite"], dtype=np.uint64),
+                 batches=np.asarray(fields["batches"], dtype=np.uint32),
+                 hist=np.asarray(fields["hist"], dtype=np.uint64).reshape(len(names), _NUM_BINS),
+                 extra=np.array(json.dumps(extra if extra is not None else {}, sort_keys=True)))
+
+
+def read_calibration_cache(path):
+    """-> (names, fields, extra) as write_calibration_cache took them."""
+    import json
+
+    import numpy as np
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in _CACHE_KEYS if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: not a calibration cache (missing {missing})")
+        if str(z["format"]) != _CACHE_FORMAT:
+            raise ValueError(f"{path}: calibration cache format {str(z['format'])!r}, expected {_CACHE_FORMAT!r}")
+        names = [str(n) for n in z["names"]]
+        fields = {k: z[k] for k in ("range", "amax", "count", "nonfinite", "batches", "hist")}
+        extra = json.loads(str(z["extra"]))
+    if fields["hist"].shape != (len(names), _NUM_BINS) or any(fields[k].shape != (len(names),) for k in
+                                                              ("range", "amax", "count", "nonfinite", "batches")):
+        raise ValueError(f"{path}: calibration cache arrays do not match its {len(names)} names")
+    return names, fields, extra
+
+
+class _DeviceCalibrator(_Base):
+    """Calibration state on the device (functions/calibrate.py, csrc/calibrate.hip): every site owns one 16 448-byte
+    slot of a zero-filled arena; `collect` is three launches and no host synchronisation, so it can sit inside a
+    captured frame; `scale` / `scales` run one threshold search over all sites and copy the headers and the bins to
+    the host once, cached until the next `collect`.  `_stats` maps a site to its slot index."""
+
+    CHUNK = 64            # slots per arena chunk; chunks are never moved (a captured graph may hold their addresses)
+    method = None         # calib_threshold's method; None: no search (min-max)
+    percentile = 99.99
+
+    def __init__(self):
+        super().__init__()
+        self._chunks = []
+        self._used = 0
+        self._device = None
+        self._cache = None
+
+    # ---- arena
+    @staticmethod
+    def _cuda_device(device):
+        device = torch.device("cuda" if device is None else device)
+        if device.type != "cuda":
+            raise TypeError(f"device calibrators keep their state on a CUDA device, not on {device}")
+        return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def reserve(self, n, device=None):
+        """Make room for `n` sites in all (one chunk holding the missing slots)."""
+        from .functions import calibrate as _c
+        if self._device is None:
+            self._device = self._cuda_device(device)
+        have = sum(c.shape[0] for c in self._chunks)
+        if n > have:
+            size = _c.calib_state_size()
+            assert size == _STATE_BYTES
+            self._chunks.append(torch.zeros(n - have, size, dtype=torch.uint8, device=self._device))
+        return self
+
+    def _slot(self, index):
+        for c in self._chunks:
+            if index < c.shape[0]:
+                return c[index]
+            index -= c.shape[0]
+        raise IndexError(index)
+
+    def _states(self):
+        """uint8 [sites, 16448]: the used slots in slot order (a device copy when they span chunks)."""
+        parts, left = [], self._used
+        for c in self._chunks:
+            if left <= 0:
+                break
+            parts.append(c[:min(left, c.shape[0])])
+            left -= c.shape[0]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    # ---- the calibrator interface
+    def collect(self, name, tensor):
+        from .functions import calibrate as _c
+        if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda:
+            raise TypeError(f"{type(self).__name__}.collect: expected a CUDA tensor")
+        if tensor.numel() == 0:
+            return
+        if self._device is not None and tensor.device != self._device:
+            raise ValueError(f"{type(self).__name__}: state lives on {self._device}, tensor on {tensor.device}")
+        index = self._stats.get(name)
+        if index is None:
+            have = sum(c.shape[0] for c in self._chunks)
+            if self._used >= have:
+                self.reserve(have + self.CHUNK, tensor.device)
+            index = self._stats[name] = self._used
+            self._used += 1
+        _c.calib_collect(tensor, self._slot(index))
+        self._cache = None
+
+    def _results(self):
+        """{name: (range, amax, count, bin)} as Python numbers: one search, one device-to-host copy."""
+        if self._cache is None:
+            import numpy as np
+            from .functions import calibrate as _c
+            names = list(self._stats)
+            out = {}
+            if names:
+                states = self._states()
+                n = states.shape[0]
+                packed = torch.zeros(n, 72, dtype=torch.uint8, device=states.device)
+                packed[:, :64] = states[:, :64]
+                if self.method is not None:
+                    bins, _ = _c.calib_threshold(states, self.method, self.percentile)
+                    packed[:, 64:68] = bins.view(torch.uint8).view(n, 4)
+                host = packed.cpu().numpy()
+                f32 = np.ascontiguousarray(host[:, :8]).view(np.float32)
+                count = np.ascontiguousarray(host[:, 16:24]).view(np.uint64)[:, 0]
+                bins = np.ascontiguousarray(host[:, 64:68]).view(np.int32)[:, 0]
+                for i, name in enumerate(names):
+                    out[name] = (float(f32[i, 0]), float(f32[i, 1]), int(count[i]), int(bins[i]))
+            self._cache = out
+        return self._cache
+
+    def _entry(self, name):
+        rng, amax, count, b = self._results()[name]
+        if count == 0:
+            raise ValueError(f"calibration site '{name}': every element it saw was NaN or infinite")
+        return rng, amax, b
+
+    def scales(self):
+        return {k: self.scale(k) for k in self._stats}
+
+    # ---- calibration cache
+    def save_calibration(self, path, extra=None):
+        """Write every site's state to `path` (write_calibration_cache); `extra`: a JSON-serialisable dict."""
+        raw = self._states().cpu().numpy() if self._stats else torch.zeros(0, _STATE_BYTES, dtype=torch.uint8).numpy()
+        write_calibration_cache(path, list(self._stats), unpack_calibration_states(raw), extra)
+
+    def load_calibration(self, path, device=None):
+        """Replace this calibrator's state with the cache at `path`; collection can go on afterwards.  Returns `extra`."""
+        names, fields, extra = read_calibration_cache(path)
+        self._stats, self._chunks, self._used, self._cache = {}, [], 0, None
+        if device is not None:
+            self._device = self._cuda_device(device)
+        if names:
+            self.reserve(len(names))
+            self._chunks[0].copy_(torch.from_numpy(pack_calibration_states(fields)))
+            self._stats = {n: i for i, n in enumerate(names)}
+            self._used = len(names)
+        return extra
+
+
+class DeviceMinMaxCalibrator(_DeviceCalibrator):
+    """MinMaxCalibrator on the device state: scale = running max|x| / 127, the host class's expression."""
+
+    def scale(self, name):
+        return max(self._entry(name)[1], 1e-12) / 127.0
+
+
+class DevicePercentileCalibrator(_DeviceCalibrator):
+    """PercentileCalibrator's rule on the device histogram."""
+    method = "percentile"
+
+    def __init__(self, percentile=99.99):
+        super().__init__()
+        self.percentile = percentile
+
+    def scale(self, name):
+        rng, _, b = self._entry(name)
+        return (b + 0.5) * rng / _NUM_BINS / 127.0
+
+
+class DeviceEntropyCalibrator(_DeviceCalibrator):
+    """EntropyCalibrator's search (entropy_threshold_bin) on the device histogram, all sites in one call."""
+    method = "entropy"
+
+    def scale(self, name):
+        rng, _, b = self._entry(name)
+        return (b + 0.5) * rng / _NUM_BINS / 127.0
 
 
 CALIBRATORS = {"minmax": MinMaxCalibrator, "entropy": EntropyCalibrator, "percentile": PercentileCalibrator,
-               "legacy": PercentileCalibrator}
+               "legacy": PercentileCalibrator, "minmax_device": DeviceMinMaxCalibrator,
+               "percentile_device": DevicePercentileCalibrator, "entropy_device": DeviceEntropyCalibrator}
 
 
 def get_calibrator(calibrator):
@@ -740,7 +974,7 @@ def engine_dense_select(name, mod):
 
 
 def build_int8_engine(B, name, dev, frames, calibrator="entropy", chain=True, dense_select=None, decoder_int8=False,
-                      sca_int8=False):
+                      sca_int8=False, calibration_cache=None):
     """The PTQ build of the re-hosted model that bench.py times (`B` = the bevformer module, `frames` = an iterable
     of (image, can_bus, lidar2img) calibration frames of one scene): int8 activation chain through the backbone
     (Int8ChainBackbone; chain=False: Conv2dQ layers with fp16 tensors between them, the round-3 build), encoder
@@ -749,8 +983,16 @@ def build_int8_engine(B, name, dev, frames, calibrator="entropy", chain=True, de
     int8, masked camera sum on the de-quantised result) as the reference's INT8 engines do
     (configs/bevformer/plugin/bevformer_base_trt_p2_q.py) -- instead of the fp16 projected sampler, which is faster
     than every int8 form of that site on MI355X; bench.py reports both builds.
+    calibration_cache (a path; `*_device` calibrators only): a file that does not exist is written after calibrating
+    from `frames`; one that exists is loaded INSTEAD of calibrating -- no frame is run, `frames` may be empty -- and
+    gives the same scales.  Besides the states it holds the MSDA sites' batch sizes, which `site_filter` reads.
     Returns (model, qops, note)."""
     dtype = torch.float16
+    if calibration_cache is not None:
+        cal_type = get_calibrator(calibrator) if isinstance(calibrator, str) else type(calibrator)
+        if not issubclass(cal_type, _DeviceCalibrator):
+            raise ValueError("calibration_cache needs a device calibrator (minmax_device, percentile_device, "
+                             "entropy_device)")
     qops = Int8PluginOps(calibrator, channels_last=True, fused_sca=not sca_int8, engine=True)
     if sca_int8:
         qops._pass = tuple(n for n in qops._pass if not n.startswith("spatial_cross_attention"))
@@ -774,11 +1016,18 @@ def build_int8_engine(B, name, dev, frames, calibrator="entropy", chain=True, de
         q += quantize_backbone_convs(model, qops.cal)
     for m in q:
         m.calibrate()
-    r = B.FrameRunner(model, dev, dtype)
     n = 0
-    for img, can, l2i in frames:
-        r.step(img, can, l2i, "calib")
-        n += 1
+    if calibration_cache is not None and os.path.exists(calibration_cache):
+        extra = qops.cal.load_calibration(calibration_cache, dev)
+        qops._site_bs = {k: int(v) for k, v in extra["site_bs"].items()}
+        n = int(extra["calibration_frames"])
+    else:
+        r = B.FrameRunner(model, dev, dtype)
+        for img, can, l2i in frames:
+            r.step(img, can, l2i, "calib")
+            n += 1
+        if calibration_cache is not None:
+            qops.cal.save_calibration(calibration_cache, {"site_bs": qops._site_bs, "calibration_frames": n})
     scales = qops.freeze()
     for m in q:
         m.freeze()

@@ -152,6 +152,11 @@ SIGNATURES = {
     "bevops_lss_voxel_prepare_workspace_size": (c_size_t, [c_int] * 4),
     "bevops_lss_voxel_prepare": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
     "bevops_bev_pool_v2_forward_indirect": (c_int, [c_int] + [c_void_p] * 9 + [c_int] * 4 + [c_float] * 3 + [c_void_p]),
+    "bevops_calib_state_size": (c_size_t, []),
+    "bevops_calib_collect": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "bevops_calib_threshold_workspace_size": (c_size_t, [c_int]),
+    "bevops_calib_threshold": (c_int, [c_int, ctypes.c_double, c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
 }
 
 F32, F16, I8, U8 = 0, 1, 2, 3

@@ -938,6 +938,52 @@ int bevops_bev_pool_v2_forward_indirect(int dtype, const void *depth, const void
                                         int out_height, int out_width, float scale_depth, float scale_feat,
                                         float scale_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * PTQ calibration on the device (csrc/calibrate.hip, design/calibration.md): a running 2048-bin histogram of |x| per
+ * calibration site and the threshold searches over it.  The reference hands calibration to TensorRT
+ * (det2trt/quantization/calibrator_trt.py:6-92); these entries are what quantization.py's *_device calibrators call.
+ *
+ * STATE: bevops_calib_state_size() = 16 448 bytes at a 64-byte aligned address; a zero-filled state is a valid empty
+ *   one.  Header (64 bytes): float range (0: no data yet; bin k covers [k, k + 1) range / 2048), float amax (running
+ *   maximum of |x|), float batch_amax, uint32 batches, uint64 count (finite elements binned), uint64 nonfinite, uint32
+ *   batch_finite, 28 bytes of zero; batch_amax and batch_finite are scratch of one collect call and zero between
+ *   calls.  Then uint64 hist[2048].
+ *
+ * bevops_calib_collect: one batch x[count] (F32 or F16, element-aligned; other dtypes: BEVOPS_NOT_SUPPORTED; count == 0:
+ *   BEVOPS_SUCCESS, nothing launched) into `state`.  Three launches, no host read, no allocation: capturable.
+ *   1. batch_amax = max |x| over the finite elements (integer atomic max on the bit pattern); NaN and +-inf are
+ *      skipped and counted into nonfinite.
+ *   2. One block.  A batch without a finite element changes nothing but batches.  Else: range == 0 becomes
+ *      max(batch_amax, 1e-12f); while batch_amax > range the range doubles, d times in all, and the bins merge:
+ *      new[j] = sum old[j 2^d .. (j + 1) 2^d - 1] for j < 2048 >> d, 0 above (d >= 11: everything in bin 0); amax =
+ *      max(amax, batch_amax).  Then batch_amax = 0, batches += 1.
+ *   3. bin = min((int)(fl(|x| fl(2048 / range))), 2047) for every finite x, F16 converted to F32 first (exact), both
+ *      operations IEEE F32; hist[bin] += 1, count += 1.
+ *   Only integer atomics: the state after a call does not depend on the order of arrival and repeats bit for bit.
+ *   NULL x / state, a misaligned x or state: BEVOPS_BAD_PARAM.  count > 2^40: BEVOPS_NOT_SUPPORTED.
+ *
+ * bevops_calib_threshold: bins[s] (int32[num_states]) = the clip bin of state s, the state at states + s state_stride
+ *   (state_stride >= the state size, a multiple of 64); -1 for a state with count == 0.  kl (optional,
+ *   double[num_states]) receives the minimum of the KL curve for method 0 (+inf where none is finite), 0 for method 1.
+ *   method 0, entropy (quantization.py: entropy_threshold_bin on the device): h = hist as double, h[0] = h[1]; for
+ *     every i in 128 .. 2048: P = h[:i] with the tail mass added to P[i - 1]; level of bin k =
+ *     ((2k + 1) 64 + i - 1) / i - 1 in integers; Q[k] = (sum of its level) / max(non-empty bins of its level, 1)
+ *     where h[k] > 0, else 0; KL = sum over pn > 0 of pn log(pn / max(Q / qsum, 1e-12)), pn = P / psum, +inf when
+ *     psum <= 0 or qsum <= 0.  bins[s] = (first minimising i) - 1; 2047 when every candidate is infinite.  Sums of
+ *     counts are exact; qsum and KL are summed in a fixed order, so results repeat bit for bit.
+ *   method 1, percentile: the first k with cdf[k] >= cdf[2047] * percentile / 100.0 (doubles, that operand order),
+ *     capped at 2047; no substitution in bin 0.
+ *   Other methods: BEVOPS_NOT_SUPPORTED.  NULL states / bins, num_states <= 0, a bad stride or alignment, a negative
+ *   or NaN percentile, a workspace that is NULL, not 8-byte aligned or shorter than
+ *   bevops_calib_threshold_workspace_size(num_states) (the [num_states, 1921] KL curves; both methods):
+ *   BEVOPS_BAD_PARAM.  num_states > 2^20: BEVOPS_NOT_SUPPORTED.  Two launches (method 0) or one (method 1).
+ * ------------------------------------------------------------------------ */
+size_t bevops_calib_state_size(void);
+int bevops_calib_collect(int dtype, const void *x, size_t count, void *state, void *stream);
+size_t bevops_calib_threshold_workspace_size(int num_states);
+int bevops_calib_threshold(int method, double percentile, const void *states, int num_states, size_t state_stride,
+                           int32_t *bins, double *kl, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
