@@ -21,7 +21,10 @@
 //     head-major planes the SCA sampler reads (msda_pad.h: pixel-pair entries of the big levels, row-major
 //     pixels of the staged ones), which removes the separate re-layout pass (70 us per SCA call).
 // N > 256: grid.y walks the 256-column chunks.  Domain: K % 64 == 0, N % 256 == 0 (other layers stay on
-// hipBLASLt).
+// hipBLASLt).  K <= 256 runs on the weight-stationary flavour further down (tsgemm_ws_kernel); this kernel stays
+// for K > 256 and as its A/B partner (bevops_tsgemm_set_variant).
+#include <stdlib.h>
+
 #include <type_traits>
 
 #include "common.h"
@@ -56,6 +59,144 @@ __device__ __forceinline__ float row16_sum(float v) {
 }
 
 typedef __attribute__((address_space(3))) void lds_void_t;
+
+// Staging accesses of the weight-stationary kernel, written as instructions: the compiler orders every LDS access it
+// emits itself behind ALL outstanding LDS-DMA (s_waitcnt vmcnt(0)), which would drain the row prefetch in front of each
+// epilogue.  The staging rows never overlap the DMA's row images; the kernel waits for its own writes (lgkmcnt) itself.
+__device__ __forceinline__ unsigned lds_addr(const void *p) {
+  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char *)p;
+}
+template <int OFF>
+__device__ __forceinline__ void lds_write16(unsigned addr, f32x4 v) {
+  asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
+}
+__device__ __forceinline__ void lds_read32(unsigned addr, float (&v)[8]) {   // 32 bytes, waited for
+  f32x4 a, b;
+  asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(a), "=&v"(b)
+               : "v"(addr)
+               : "memory");
+  v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+}
+
+// ---- per-thread epilogue arithmetic shared by the weight-stationary kernel below (a thread owns 8 consecutive columns
+// of one output row, fp32 values `v` read back from the staging rows)
+__device__ __forceinline__ void ts_add_res(float (&v)[8], const uint4 q) {
+  v[0] += h2f_lo(q.x); v[1] += h2f_hi(q.x); v[2] += h2f_lo(q.y); v[3] += h2f_hi(q.y);
+  v[4] += h2f_lo(q.z); v[5] += h2f_hi(q.z); v[6] += h2f_lo(q.w); v[7] += h2f_hi(q.w);
+}
+__device__ __forceinline__ uint4 ts_pack8(const float (&v)[8]) {
+  uint4 o;
+  o.x = pack_h2(v[0], v[1]); o.y = pack_h2(v[2], v[3]); o.z = pack_h2(v[4], v[5]); o.w = pack_h2(v[6], v[7]);
+  return o;
+}
+__device__ __forceinline__ float ts_sum8(const uint4 o) {
+  return (h2f_lo(o.x) + h2f_hi(o.x)) + (h2f_lo(o.y) + h2f_hi(o.y)) + (h2f_lo(o.z) + h2f_hi(o.z)) +
+         (h2f_lo(o.w) + h2f_hi(o.w));
+}
+
+// EPI 1: row m (tile row r of `rows`, columns col .. col + 7) into the padded planes.  `stage` is the fp32 staging image
+// of the tile's current 128-column half (rows of kTsEpiStride bytes): the right neighbour's values come from there.
+__device__ __forceinline__ void ts_store_planes(const float (&v)[8], const TsPacked &pk, size_t m, int col, int r, int rows,
+                                                int c8, const char *stage) {
+  // row m = pixel `s` of camera `cam`; column chunk -> (head, channels 8 q .. 8 q + 7)
+  const int cam = (int)(m / (size_t)pk.nk), s = (int)(m - (size_t)cam * pk.nk);
+  const int head = col >> 5, q8 = (col & 31) >> 3;
+  // the level's constants by compare-and-select over the (scalar) table: indexing the by-value table with a per-lane
+  // level would be vector loads from the argument segment, and waiting for those waits for the row prefetch as well
+  int l = 0, src0 = pk.t.src0[0], Wl = pk.t.W[0], ent0 = pk.t.ent0[0];
+#pragma unroll
+  for (int k = 1; k < kHm3MaxLevels; ++k)
+    if (k < pk.t.L && s >= pk.t.src0[k]) { l = k; src0 = pk.t.src0[k]; Wl = pk.t.W[k]; ent0 = pk.t.ent0[k]; }
+  const int rel = s - src0;
+  const int y = rel / Wl, xx = rel - y * Wl;
+  const int wp = Wl + 1;
+  const int f = ent0 + (y + 1) * wp + xx;        // padded entry of this pixel
+  const size_t plane = (size_t)cam * pk.heads + head;
+  const unsigned h0 = pack_h2(v[0], v[1]), h1 = pack_h2(v[2], v[3]), h2 = pack_h2(v[4], v[5]), h3 = pack_h2(v[6], v[7]);
+  if (l >= pk.t.ls) {   // staged level: row-major 64 B per pixel
+    *reinterpret_cast<uint4 *>(pk.sset + (plane * pk.t.s_entries + f) * kLdsPixBytes + q8 * 16) = make_uint4(h0, h1, h2, h3);
+    return;
+  }
+  // big level: entry f = (this pixel, right neighbour), entry f - 1 = (left neighbour, this pixel); this thread writes
+  // the halves that hold ITS pixel: the .lo lanes of entry f and the .hi lanes of entry f - 1
+  float nb[8];
+  const bool has_r = xx + 1 < Wl && r + 1 < rows;
+  const bool own_r = xx + 1 < Wl;
+  if (has_r) {
+    lds_read32(lds_addr(stage + (r + 1) * kTsEpiStride + c8 * 32), nb);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) nb[k] = 0.f;
+  }
+  char *e = pk.gset + (plane * pk.t.g_entries + f) * kEntBytes + q8 * 32;
+  if (has_r || !own_r) {   // the whole entry is known here: (mine, right) or (mine, pad)
+    uint4 o0, o1;
+    o0.x = pack_h2(v[0], nb[0]); o0.y = pack_h2(v[1], nb[1]); o0.z = pack_h2(v[2], nb[2]); o0.w = pack_h2(v[3], nb[3]);
+    o1.x = pack_h2(v[4], nb[4]); o1.y = pack_h2(v[5], nb[5]); o1.z = pack_h2(v[6], nb[6]); o1.w = pack_h2(v[7], nb[7]);
+    *reinterpret_cast<uint4 *>(e) = o0;
+    *reinterpret_cast<uint4 *>(e + 16) = o1;
+  } else {                 // right neighbour lives in the next tile: only my halves (2-byte stores)
+    unsigned short *e16 = reinterpret_cast<unsigned short *>(e);
+    const unsigned hv[4] = {h0, h1, h2, h3};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { e16[4 * k] = (unsigned short)(hv[k] & 0xffffu); e16[4 * k + 2] = (unsigned short)(hv[k] >> 16); }
+  }
+  if (xx == 0) {           // entry f - 1 is the pad before the row: (0, mine)
+    uint4 o0, o1;
+    o0.x = h0 << 16; o0.y = h0 & 0xffff0000u; o0.z = h1 << 16; o0.w = h1 & 0xffff0000u;
+    o1.x = h2 << 16; o1.y = h2 & 0xffff0000u; o1.z = h3 << 16; o1.w = h3 & 0xffff0000u;
+    *reinterpret_cast<uint4 *>(e - kEntBytes) = o0;
+    *reinterpret_cast<uint4 *>(e - kEntBytes + 16) = o1;
+  } else if (r == 0) {     // left neighbour lives in the previous tile: my halves of entry f - 1
+    unsigned short *e16 = reinterpret_cast<unsigned short *>(e - kEntBytes);
+    const unsigned hv[4] = {h0, h1, h2, h3};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { e16[4 * k + 1] = (unsigned short)(hv[k] & 0xffffu); e16[4 * k + 3] = (unsigned short)(hv[k] >> 16); }
+  }
+}
+
+// EPI 2: LayerNorm of one row of 256 from its rounded sums (`lo` / `hi8`: this thread's 8 columns of the two 128-column
+// halves, `rs`: their fp32 sum), the 16 threads of the row in one DPP row; two passes, one rounding.
+// `gb`: the norm's weight and bias for this thread's columns, {weight, bias} of half 0, then of half 1 (ts_ln_params).
+__device__ __forceinline__ void ts_ln_params(const TsPacked &pk, int c8, uint4 (&gb)[4]) {
+  const __half *gam = reinterpret_cast<const __half *>(pk.gset), *bet = reinterpret_cast<const __half *>(pk.sset);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    gb[2 * h] = *reinterpret_cast<const uint4 *>(gam + h * 128 + c8 * 8);
+    gb[2 * h + 1] = *reinterpret_cast<const uint4 *>(bet + h * 128 + c8 * 8);
+  }
+}
+__device__ __forceinline__ void ts_ln_row(const uint4 lo, const uint4 hi8, float rs, float eps, const uint4 (&gb)[4],
+                                          __half *out_row, int c8) {
+  const float mean = row16_sum(rs) * (1.f / 256.f);
+  float f[16];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint4 o = h ? hi8 : lo;
+    f[8 * h + 0] = h2f_lo(o.x) - mean; f[8 * h + 1] = h2f_hi(o.x) - mean;
+    f[8 * h + 2] = h2f_lo(o.y) - mean; f[8 * h + 3] = h2f_hi(o.y) - mean;
+    f[8 * h + 4] = h2f_lo(o.z) - mean; f[8 * h + 5] = h2f_hi(o.z) - mean;
+    f[8 * h + 6] = h2f_lo(o.w) - mean; f[8 * h + 7] = h2f_hi(o.w) - mean;
+  }
+  float sq = 0.f;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) sq = fmaf(f[k], f[k], sq);
+  const float rstd = rsqrtf(row16_sum(sq) * (1.f / 256.f) + eps);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int col = h * 128 + c8 * 8;
+    const uint4 g4 = gb[2 * h], b4 = gb[2 * h + 1];
+    const float gg[8] = {h2f_lo(g4.x), h2f_hi(g4.x), h2f_lo(g4.y), h2f_hi(g4.y),
+                         h2f_lo(g4.z), h2f_hi(g4.z), h2f_lo(g4.w), h2f_hi(g4.w)};
+    const float bb[8] = {h2f_lo(b4.x), h2f_hi(b4.x), h2f_lo(b4.y), h2f_hi(b4.y),
+                         h2f_lo(b4.z), h2f_hi(b4.z), h2f_lo(b4.w), h2f_hi(b4.w)};
+    float y[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) y[k] = fmaf(f[8 * h + k] * rstd, gg[k], bb[k]);
+    *reinterpret_cast<uint4 *>(out_row + col) = ts_pack8(y);
+  }
+}
 
 // EPI 0: out = act(acc + bias (+ residual)) -> [M, N] fp16.  EPI 1: acc + bias -> packed planes.
 // EPI 2 (round 6, N == 256): out = LayerNorm(fp16(acc + bias + residual)) -- the layer the encoder / decoder blocks put
@@ -408,6 +549,252 @@ __global__ __launch_bounds__(256) void tsgemm_pad_zero_kernel(TsPacked pk, int p
   }
 }
 
+// ---- the weight-stationary flavour for K <= 256 (K = 64 KS).  In tsgemm_f16_kernel every tile pulls its 256 x K weight
+// slice through the CU's load path again (128 KB per 160-row tile at K = 256, next to 80 KB of rows), and load, multiply
+// and store of a tile run one after another.  Here
+//   * a wave keeps ITS 32 weight rows in registers for the whole launch: K / 8 fragments of 16 bytes per lane (64 VGPRs
+//     at K = 256), read once from global memory with the lane -> (row, k-chunk) mapping of the LDS fragment read above;
+//     no weight byte passes through LDS;
+//   * LDS holds whole-K images of 64 activation rows (KS sub-images of 64 x 128 bytes, the same swizzled row image) in
+//     a ring of three, plus the fp32 staging of one 128-column half: the rows of tile t + 2 are requested before tile
+//     t is multiplied, and a wave waits for its pieces of tile t + 1 just before the first store of tile t, so row
+//     loads are in flight during the multiply AND the stores.  Every wave issues exactly KS DMA instructions per tile
+//     (pieces outside the block's rows get an out-of-range offset: the buffer descriptor answers zeros without an
+//     access), so the waits are counted: what is left outstanding is the newest request, the previous tile's stores
+//     and the residual rows of the next tile (read one tile ahead);
+//   * N > 256: one block per (row partition, 256-column chunk), all co-resident; the chunks of a partition sit on the
+//     same XCD (block b runs on XCD b % 8) and walk the same rows at the same time, so the re-read comes from L2.
+// Summation order: k ascending in every block, the same matrix instruction, operand layout, fp32 epilogue and single
+// rounding as above -- an output row depends on its own operands only, not on the block index, M or the CU count.
+constexpr int kWsG = 2;                          // row units per tile (the staging writes below are written for 2)
+constexpr int kWsRows = kWsG * 32;
+constexpr int kWsBufs = 3;
+constexpr int kWsStep = kWsRows * 128;           // one 64-k sub-image of a tile (8 KB)
+constexpr int kWsEpi = kWsRows * kTsEpiStride;   // fp32 staging of a 128-column half (33 KB), at the start of LDS
+constexpr int ws_lds(int ks) { return kWsEpi + kWsBufs * ks * kWsStep; }   // 129 KB at K = 256
+
+template <int EPI, int KS>
+__global__ __launch_bounds__(kTsThreads) void tsgemm_ws_kernel(const __half *__restrict__ x, const __half *__restrict__ w,
+                                                               const __half *__restrict__ bias,
+                                                               const __half *__restrict__ res, __half *__restrict__ out,
+                                                               int M, int N, int relu, int units_total, int parts,
+                                                               int chunks, TsPacked pk) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int K = KS * 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // block -> (row partition, column chunk); the chunks of a partition on one XCD when the grid allows it
+  int part, chunk;
+  if (gridDim.x % (8u * (unsigned)chunks) == 0) {
+    const int i = (int)(blockIdx.x >> 3);
+    chunk = i % chunks;
+    part = (i / chunks) * 8 + (int)(blockIdx.x & 7);
+  } else {
+    chunk = (int)blockIdx.x % chunks;
+    part = (int)blockIdx.x / chunks;
+  }
+  const int n0 = chunk * kTsBN;
+  const int per = units_total / parts, extra = units_total % parts;
+  const int u_begin = part * per + min(part, extra);
+  const int u_end = u_begin + per + (part < extra ? 1 : 0);
+  if (u_begin >= u_end) return;
+  const int ntiles = (u_end - u_begin + kWsG - 1) / kWsG;
+
+  const __amdgpu_buffer_rsrc_t rs_x =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<__half *>(x), 0, (unsigned)((size_t)M * K * 2), 0x00020000);
+  const unsigned hi = (unsigned)(lane >> 5);
+  const unsigned fa = (unsigned)(wave * 32 + (lane & 31));   // weight row of this lane's fragments
+  // the wave's weight rows: fragment 4 kstep + ks holds k = 64 kstep + 16 ks + 8 hi .. + 7 of row n0 + fa
+  f16x8 wr[KS * 4];
+  {
+    const __half *wrow = w + (size_t)(n0 + (int)fa) * K + hi * 8;
+#pragma unroll
+    for (int kk = 0; kk < KS * 4; ++kk) wr[kk] = *reinterpret_cast<const f16x8 *>(wrow + kk * 16);
+  }
+  // column constants of this lane: acc[g][4 rq + e] is column wave * 32 + 8 rq + 4 hi + e
+  float bcol[16];
+  if (bias) {   // four 8-byte loads in flight together
+    uint2 bq[4];
+#pragma unroll
+    for (int rq = 0; rq < 4; ++rq)
+      bq[rq] = *reinterpret_cast<const uint2 *>(bias + n0 + wave * 32 + 8 * rq + 4 * (int)hi);
+#pragma unroll
+    for (int rq = 0; rq < 4; ++rq) {
+      bcol[4 * rq] = h2f_lo(bq[rq].x); bcol[4 * rq + 1] = h2f_hi(bq[rq].x);
+      bcol[4 * rq + 2] = h2f_lo(bq[rq].y); bcol[4 * rq + 3] = h2f_hi(bq[rq].y);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) bcol[i] = 0.f;
+  }
+
+  // DMA role: piece `wave` of a tile = its rows 8 wave .. 8 wave + 7, lane -> (row in piece, 16-byte chunk), the
+  // swizzle on the source chunk; KS instructions per wave and tile, always
+  const unsigned trow = (unsigned)(wave * 8 + (lane >> 3));
+  const unsigned tchunk = (((unsigned)(lane & 7)) ^ swz8(trow)) << 4;
+  auto dma = [&](int t, int buf) {
+    const int row = (u_begin + t * kWsG) * 32 + (int)trow;
+    const bool valid = t < ntiles && u_begin + t * kWsG + (wave >> 2) < u_end && row < M;
+    const unsigned voff = valid ? (unsigned)((size_t)row * K * 2) + tchunk : 0xFFFFFF00u;
+    char *d = smem + kWsEpi + buf * (KS * kWsStep) + wave * 1024;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_t *)(d + ks * kWsStep), 16, (int)voff, ks * 128, 0, 0);
+  };
+  // all but the youngest tile's pieces of this wave have landed
+  auto wait_keep_one_tile = [&]() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KS) : "memory"); };
+  // The same wait inside the loop, where more than the youngest request is younger than the pieces waited for: the
+  // stores of the previous tile and the residual loads of the next one.  The counter retires in order: leaving
+  // exactly those outstanding waits for the pieces and for nothing issued after them (in particular not for the write
+  // acknowledgements of the previous tile).  `younger` is a LOWER bound of their number (waiting for more is safe, for
+  // less is not), wave-uniform.
+  auto wait_for_next_tile = [&](int younger) {
+    switch (younger) {
+      case 0: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KS) : "memory"); break;
+      case 2: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KS + 2) : "memory"); break;
+      case 4: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KS + 4) : "memory"); break;
+      case 6: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KS + 6) : "memory"); break;
+      default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KS + 8) : "memory"); break;   // 8, the most there is
+    }
+  };
+  const int rb = tid >> 4, c8 = tid & 15;   // epilogue role: rows rb, rb + 32 of the tile, 8 columns of a half
+  // residual rows of tile t (rows past the end are clamped, never stored): read one tile AHEAD, so that waiting for
+  // them never waits for the stores of the tile before
+  uint4 rq[2][kWsG];
+  auto load_res = [&](int t, uint4(&q)[2][kWsG]) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half)
+#pragma unroll
+      for (int i = 0; i < kWsG; ++i) {
+        const size_t m = (size_t)min((u_begin + t * kWsG) * 32 + rb + 32 * i, M - 1);
+        q[half][i] = *reinterpret_cast<const uint4 *>(res + m * N + n0 + half * 128 + c8 * 8);
+      }
+  };
+  uint4 gb[4];   // EPI 2: the norm's parameters of this thread's columns, read once (a load inside the loop would have to
+                 // be waited for, and with it every request issued before it)
+  if constexpr (EPI == 2) ts_ln_params(pk, c8, gb);
+  if constexpr (EPI != 1) {
+    if (res) load_res(0, rq);
+  }
+
+  dma(0, 0);
+  dma(1, 1);
+#pragma unroll
+  for (int kk = 0; kk < KS * 4; ++kk) asm volatile("" ::"v"(wr[kk]));   // the weights have arrived HERE, not in the loop
+  wait_keep_one_tile();
+  __builtin_amdgcn_s_barrier();
+
+  int buf = 0;
+  int stores_prev = 0;   // store instructions of this wave in the previous tile, at least
+  for (int t = 0; t < ntiles; ++t) {
+    const int u0 = u_begin + t * kWsG;
+    const int r0 = u0 * 32;
+    const int rows = min(min(kWsRows, (u_end - u0) * 32), M - r0);
+    uint4 rqn[2][kWsG];
+    if constexpr (EPI != 1) {
+      if (res) load_res(t + 1, rqn);
+    }
+    {
+      int b2 = buf + 2;
+      if (b2 >= kWsBufs) b2 -= kWsBufs;
+      dma(t + 2, b2);   // that buffer was multiplied in tile t - 1, before its epilogue's barriers
+    }
+    f32x16 acc[kWsG];
+#pragma unroll
+    for (int g = 0; g < kWsG; ++g)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[g][r] = 0.f;
+    const char *Xt = smem + kWsEpi + buf * (KS * kWsStep);
+#pragma unroll
+    for (int kk = 0; kk < KS * 4; ++kk) {
+      const unsigned c = 2u * (kk & 3) + hi;
+      f16x8 b[kWsG];
+#pragma unroll
+      for (int g = 0; g < kWsG; ++g) {
+        const unsigned xr = (unsigned)(g * 32 + (lane & 31));
+        b[g] = *reinterpret_cast<const f16x8 *>(Xt + (kk >> 2) * kWsStep + xr * 128 + ((c ^ swz8(xr)) << 4));
+      }
+#pragma unroll
+      for (int g = 0; g < kWsG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[kk], b[g], acc[g], 0, 0, 0);
+    }
+    // ---- epilogue through LDS (fp32), two halves of 128 columns: waves 0..3, then waves 4..7
+    uint4 keep[2][kWsG];
+    float rsum[kWsG];
+    if constexpr (EPI == 2) {
+#pragma unroll
+      for (int i = 0; i < kWsG; ++i) rsum[i] = 0.f;
+    }
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      if ((wave >> 2) == half) {
+        const int cw = (wave & 3) * 32;
+#pragma unroll
+        for (int g = 0; g < kWsG; ++g) {
+          const unsigned rowa = lds_addr(smem + (lane & 31) * kTsEpiStride + (cw + 4 * (int)hi) * 4);
+          auto put = [&](auto qc) __attribute__((always_inline)) {
+            constexpr int q = decltype(qc)::value;
+            const f32x4 v = {acc[g][4 * q] + bcol[4 * q], acc[g][4 * q + 1] + bcol[4 * q + 1],
+                             acc[g][4 * q + 2] + bcol[4 * q + 2], acc[g][4 * q + 3] + bcol[4 * q + 3]};
+            if (g == 0) lds_write16<q * 32>(rowa, v);
+            else lds_write16<32 * kTsEpiStride + q * 32>(rowa, v);
+          };
+          put(std::integral_constant<int, 0>{}); put(std::integral_constant<int, 1>{});
+          put(std::integral_constant<int, 2>{}); put(std::integral_constant<int, 3>{});
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      }
+      __builtin_amdgcn_s_barrier();
+      // before the first store of this tile: my pieces of tile t + 1 are in LDS (the barrier that ends the half shows
+      // them to everybody), the request for tile t + 2 stays in flight behind the stores
+      if (half == 0) wait_for_next_tile(stores_prev + ((EPI != 1 && res) ? 4 : 0));
+#pragma unroll
+      for (int i = 0; i < kWsG; ++i) {
+        const int r = rb + 32 * i;
+        if (r < rows) {
+          float v[8];
+          lds_read32(lds_addr(smem + r * kTsEpiStride + c8 * 32), v);
+          const int col = n0 + half * 128 + c8 * 8;
+          const size_t m = (size_t)(r0 + r);
+          if constexpr (EPI == 1) {
+            ts_store_planes(v, pk, m, col, r, rows, c8, smem);
+          } else {
+            if (res) ts_add_res(v, rq[half][i]);
+            if constexpr (EPI == 2) {
+              const uint4 o = ts_pack8(v);
+              keep[half][i] = o;
+              rsum[i] += ts_sum8(o);
+            } else {
+              if (relu) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
+              }
+              *reinterpret_cast<uint4 *>(out + m * N + col) = ts_pack8(v);
+            }
+          }
+        }
+      }
+      __builtin_amdgcn_s_barrier();
+    }
+    if constexpr (EPI == 2) {
+#pragma unroll
+      for (int i = 0; i < kWsG; ++i) {
+        const int r = rb + 32 * i;
+        if (r < rows) ts_ln_row(keep[0][i], keep[1][i], rsum[i], pk.eps, gb, out + (size_t)(r0 + r) * N, c8);
+      }
+    }
+    if constexpr (EPI != 1) {
+      if (res) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+#pragma unroll
+          for (int i = 0; i < kWsG; ++i) rq[half][i] = rqn[half][i];
+      }
+    }
+    // every (half, row pass) with a live row in this wave stored at least once (EPI 2: two stores per live row)
+    stores_prev = __builtin_amdgcn_readfirstlane(2 * ((wave * 4 < rows ? 1 : 0) + (wave * 4 + 32 < rows ? 1 : 0)));
+    if (++buf == kWsBufs) buf = 0;
+  }
+}
+
 // ---- the int8 activation chain's flavour (quantization.Int8ChainBackbone: the 1x1 convolutions of ResNet stages 3 / 4):
 //     out = requant( act( (sum_k a[m, k] w[n, k]) * s_a * s_w[n] + bias[n] (+ identity[m, n]) ) )
 // a [M, K], w [N, K] int8 row-major, int32 sums (exact), fp32 bias, identity rows int8 (with their own scale) or fp16,
@@ -615,10 +1002,61 @@ inline int ts_grid_x(int units, int chunks_n) {
   return units < cus ? units : cus;
 }
 
+// bevops_tsgemm_set_variant: 0 = the weight-stationary kernel inside its domain, 1 = tsgemm_f16_kernel everywhere (A/B
+// partner); BEVOPS_TSGEMM_WS=0 in the environment at library load is variant 1 for every thread.
+thread_local int g_ts_variant = 0;
+const bool g_ts_env_old = [] {
+  const char *e = getenv("BEVOPS_TSGEMM_WS");
+  return e && e[0] == '0' && e[1] == 0;
+}();
+
+// the one predicate of the three fp16 entries (they switch together: the planes of bevops_value_proj_packed are tied
+// byte for byte to bevops_tsgemm_f16, and so is the LayerNorm epilogue)
+inline bool ts_use_ws(int k) { return k <= 256 && g_ts_variant != 1 && !g_ts_env_old; }
+
+template <int EPI, int KS>
+int ws_launch_ks(const void *x, const void *w, const void *bias, const void *res, void *out, long long m, int n, int relu,
+                 const TsPacked &pk, hipStream_t st) {
+  if (!ensure_dynamic_lds<tsgemm_ws_kernel<EPI, KS>>(ws_lds(KS))) return BEVOPS_FAILURE;
+  const int units = (int)((m + 31) / 32), chunks = n / kTsBN;
+  const int cus = ts_grid_x(1 << 30, chunks);
+  int parts = cus / chunks;
+  if (parts < 1) parts = 1;
+  if (parts > units) parts = units;
+  hipLaunchKernelGGL((tsgemm_ws_kernel<EPI, KS>), dim3((unsigned)(parts * chunks)), dim3(kTsThreads), ws_lds(KS), st,
+                     (const __half *)x, (const __half *)w, (const __half *)bias, (const __half *)res, (__half *)out, (int)m,
+                     n, relu, units, parts, chunks, pk);
+  return launch_status();
+}
+
+template <int EPI>
+int ws_launch(const void *x, const void *w, const void *bias, const void *res, void *out, long long m, int n, int k,
+              int relu, const TsPacked &pk, hipStream_t st) {
+  switch (k / 64) {
+    case 1: return ws_launch_ks<EPI, 1>(x, w, bias, res, out, m, n, relu, pk, st);
+    case 2: return ws_launch_ks<EPI, 2>(x, w, bias, res, out, m, n, relu, pk, st);
+    case 3: return ws_launch_ks<EPI, 3>(x, w, bias, res, out, m, n, relu, pk, st);
+    default: return ws_launch_ks<EPI, 4>(x, w, bias, res, out, m, n, relu, pk, st);
+  }
+}
+
 }  // namespace
 }  // namespace bevops
 
 using namespace bevops;
+
+extern "C" int bevops_tsgemm_set_variant(int variant) {
+  const int prev = g_ts_variant;
+  g_ts_variant = variant;
+  return prev;
+}
+
+// rows per tile of the kernel bevops_tsgemm_f16 runs for this k under the current variant (tests size their ragged
+// cases with it); 0 outside the domain
+extern "C" int bevops_tsgemm_tile_rows(int k) {
+  if (k <= 0 || k % 64 != 0) return 0;
+  return ts_use_ws(k) ? kWsRows : kTsG * 32;
+}
 
 extern "C" int bevops_tsgemm_f16(const void *x, const void *weight, const void *bias, const void *residual,
                                  void *out, long long m, int n, int k, int relu, void *stream) {
@@ -628,6 +1066,7 @@ extern "C" int bevops_tsgemm_f16(const void *x, const void *weight, const void *
   if (!aligned16(x) || !aligned16(weight) || !aligned16(out) || (bias && !aligned16(bias)) ||
       (residual && !aligned16(residual)))
     return BEVOPS_BAD_PARAM;
+  if (ts_use_ws(k)) return ws_launch<0>(x, weight, bias, residual, out, m, n, k, relu, TsPacked{}, static_cast<hipStream_t>(stream));
   if (!ensure_dynamic_lds<tsgemm_f16_kernel<0>>(kTsLds)) return BEVOPS_FAILURE;
   const int units = (int)((m + 31) / 32);
   const dim3 grid((unsigned)ts_grid_x(units, n / kTsBN), (unsigned)(n / kTsBN));
@@ -649,13 +1088,14 @@ extern "C" int bevops_tsgemm_f16_ln(const void *x, const void *weight, const voi
   if (!aligned16(x) || !aligned16(weight) || !aligned16(out) || (bias && !aligned16(bias)) ||
       (residual && !aligned16(residual)) || !aligned16(ln_weight) || !aligned16(ln_bias))
     return BEVOPS_BAD_PARAM;
-  if (!ensure_dynamic_lds<tsgemm_f16_kernel<2>>(kTsLds)) return BEVOPS_FAILURE;
-  const int units = (int)((m + 31) / 32);
-  const dim3 grid((unsigned)ts_grid_x(units, 1), 1u);
   TsPacked pk{};
   pk.gset = const_cast<char *>(static_cast<const char *>(ln_weight));
   pk.sset = const_cast<char *>(static_cast<const char *>(ln_bias));
   pk.eps = eps;
+  if (ts_use_ws(k)) return ws_launch<2>(x, weight, bias, residual, out, m, n, k, 0, pk, static_cast<hipStream_t>(stream));
+  if (!ensure_dynamic_lds<tsgemm_f16_kernel<2>>(kTsLds)) return BEVOPS_FAILURE;
+  const int units = (int)((m + 31) / 32);
+  const dim3 grid((unsigned)ts_grid_x(units, 1), 1u);
   hipLaunchKernelGGL(tsgemm_f16_kernel<2>, grid, dim3(kTsThreads), kTsLds, static_cast<hipStream_t>(stream),
                      (const __half *)x, (const __half *)weight, (const __half *)bias, (const __half *)residual,
                      (__half *)out, (int)m, n, k, 0, units, pk);
@@ -738,6 +1178,7 @@ extern "C" int bevops_value_proj_packed(const void *x, const void *weight, const
   pk.heads = heads;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(tsgemm_pad_zero_kernel, dim3(4, (unsigned)(num_cams * heads)), dim3(256), 0, st, pk, num_cams * heads);
+  if (ts_use_ws(k)) return ws_launch_ks<1, 4>(x, weight, bias, nullptr, nullptr, m, n, 0, pk, st);   // K == N == 256 here
   if (!ensure_dynamic_lds<tsgemm_f16_kernel<1>>(kTsLds)) return BEVOPS_FAILURE;
   const int units = (int)((m + 31) / 32);
   const dim3 grid((unsigned)ts_grid_x(units, n / kTsBN), (unsigned)(n / kTsBN));

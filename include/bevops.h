@@ -698,6 +698,15 @@ int bevops_point_sampling(int out_dtype, const float *pillars, const float *lida
  * (the caller keeps its library GEMM). */
 int bevops_tsgemm_f16(const void *x, const void *weight, const void *bias, const void *residual, void *out,
                       long long m, int n, int k, int relu, void *stream);
+/* K <= 256 runs on the weight-stationary flavour of that kernel (weights in registers for the whole launch, activation
+ * rows prefetched two tiles ahead; k ascending in every block, so an output row depends on its own operands only).
+ * bevops_tsgemm_set_variant (thread-local A/B switch, like bevops_stem_set_variant): 0 = default, 1 = the original kernel
+ * for every K; applies to bevops_tsgemm_f16, bevops_tsgemm_f16_ln and bevops_value_proj_packed together.  Returns the
+ * previous value.  BEVOPS_TSGEMM_WS=0 in the environment when the library loads is variant 1 for every thread.
+ * bevops_tsgemm_tile_rows: rows per tile of the kernel that runs for this k under the current variant (0: k outside the
+ * domain). */
+int bevops_tsgemm_set_variant(int variant);
+int bevops_tsgemm_tile_rows(int k);
 /* The same GEMM with the LayerNorm that follows it in every encoder / decoder block (modules/encoder.py:586-636,
  * modules/decoder.py:52-112: attention or FFN with its identity, then `norm`) evaluated in the epilogue:
  *     out = LayerNorm_N(fp16(x w^T + bias (+ residual))) * ln_weight + ln_bias,     N == 256, K % 64 == 0.
