@@ -180,6 +180,13 @@ def _layer_norm(ops, norm, x):
 _FUSED_REFINE = {"enabled": os.environ.get("BEVOPS_FUSED_REFINE", "1") == "1"}   # A/B: decoder refinement as one launch
 _OWN_ATTN = {"enabled": os.environ.get("BEVOPS_OWN_ATTN", "1") == "1"}   # A/B: decoder self-attention on csrc/attention.hip
 _LN_FUSED = {"enabled": os.environ.get("BEVOPS_LN_FUSED", "1") == "1"}   # A/B: LayerNorm in the epilogue of the GEMM in front of it
+# INT8 engine: every encoder block's LayerNorm in the epilogue of the block's last int8 GEMM (bevops_tsgemm_s8_ln).  The FFN
+# keeps its hidden tensor int8 (fc1's epilogue requantises with fc2's input scale): two launches where there are three.
+# The two output_proj sites quantise their fp16 operand in one pass first: two launches for two, fewer bytes.  OFF by
+# default: these paths quantise the GEMM's operand as rne(v / s) where today's path multiplies by fl(1 / s) inside the
+# operand load (the FFN: from the fp32 value instead of its fp16 rounding) -- they differ on near-ties.
+# quantization.build_int8_engine(block_norm_fused=...) sets it per model (ops.int8_ln_fused).
+_INT8_LN_FUSED = {"enabled": os.environ.get("BEVOPS_INT8_LN_FUSED", "0") == "1"}
 # The dense layers behind the backbone (the GEMMs that wrap the samplers, SURVEY.md 8a-5, the decoder, the heads) on the
 # hand-written kernels whatever the dispatch table measured: one kernel per layer with a block-index-only summation order.
 _OWN_ENCODER = {"enabled": os.environ.get("BEVOPS_OWN_ENCODER", "1") == "1"}
@@ -202,7 +209,32 @@ def _dense_norm(ops, lin, x, residual, norm):
         except _lib.BevopsError as exc:
             if exc.status != _lib.NOT_SUPPORTED:
                 raise
+    if _int8_ln_on(ops) and _int8_norm_ok(lin, x, norm):
+        # INT8 engine, switch on: one quantise pass over the fp16 operand, then the int8 GEMM with identity and norm in its
+        # epilogue -- two launches for two, 1 byte per operand element instead of 2 and no [M, 256] round trip
+        # (40 000 x 256 x 256: 25.5-25.7 us against 26.8-26.9, profiles/int8_ln/per_call.jsonl)
+        return lin.forward_norm_from_q(_hip_ops.quantize_rows(x, lin.scale_in), residual, norm)
     return _layer_norm(ops, norm, _dense(ops, lin, x, residual, False))
+
+
+def _int8_ln_on(ops):
+    on = getattr(ops, "int8_ln_fused", None)
+    return _INT8_LN_FUSED["enabled"] if on is None else on
+
+
+def _int8_norm_ok(lin, x, norm):
+    """norm(lin(.) + identity) as ONE int8 launch (bevops_tsgemm_s8_ln): a frozen LinearQ inside the entry's domain
+    (256 columns, K % 128 == 0), fp16 rows on the GPU.  In the float and calibrate phases the ordinary path runs (the
+    calibrator must see the layer's fp16 input)."""
+    return hasattr(lin, "fake_quant_reference") and lin.mode == "int8" \
+        and lin.in_features % 128 == 0 and lin.out_features == EMBED and x.dtype == torch.float16 and x.is_cuda \
+        and isinstance(norm, nn.LayerNorm) and norm.elementwise_affine and norm.normalized_shape == (EMBED,)
+
+
+def _int8_ffn_chain_ok(fc1, fc2, x, norm):
+    """The FFN as fc1 (fp16 in, ReLU, int8 out at fc2's input scale) -> fc2 + identity + norm in one int8 launch."""
+    return hasattr(fc1, "fake_quant_reference") and fc1.mode == "int8" and fc1.in_features % 16 == 0 \
+        and _int8_norm_ok(fc2, x, norm)
 
 
 def _conv1x1_nhwc(ops, x, conv, relu, residual=None):
@@ -464,6 +496,9 @@ class FFN(nn.Module):
 
     def forward(self, x, ops=None, norm=None):
         """`norm`: the block's LayerNorm behind the FFN (then evaluated here, in fc2's epilogue when the operator set can)."""
+        if norm is not None and _int8_ln_on(ops) and _int8_ffn_chain_ok(self.fc1, self.fc2, x, norm):
+            h_q = self.fc1.forward_q(x, self.fc2.scale_in, relu=True)
+            return self.fc2.forward_norm_from_q(h_q, x, norm)
         h = _dense(ops, self.fc1, x, None, True)
         return _dense(ops, self.fc2, h, x, False) if norm is None else _dense_norm(ops, self.fc2, h, x, norm)
 

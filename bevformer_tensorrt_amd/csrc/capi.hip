@@ -80,6 +80,7 @@ const Entry kTable[] = {
     {"bevops_queue_mean2", (void *)&bevops_queue_mean2},
     {"bevops_tsgemm_f16", (void *)&bevops_tsgemm_f16},
     {"bevops_tsgemm_s8", (void *)&bevops_tsgemm_s8},
+    {"bevops_tsgemm_s8_ln", (void *)&bevops_tsgemm_s8_ln},
     {"bevops_tsgemm_tile_rows", (void *)&bevops_tsgemm_tile_rows},
     {"bevops_tsgemm_f16_ln", (void *)&bevops_tsgemm_f16_ln},
     {"bevops_mha_selfattn_f16", (void *)&bevops_mha_selfattn_f16},

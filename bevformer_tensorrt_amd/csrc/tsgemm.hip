@@ -43,6 +43,7 @@ constexpr int kTsStage = kTsW + kTsX;
 constexpr int kTsEpiStride = 128 * 4 + 16; // fp32 staging row (128 columns) + bank pad
 constexpr int kTsStages = 3;               // two k-steps of DMA in flight behind the one being multiplied
 constexpr int kTsLds = kTsStages * kTsStage;   // 156 KB; the epilogue staging (160 x 528 = 82.5 KB) reuses it
+constexpr int kTsS8LnLds = kTsLds + 2 * kTsBN * 2;   // tsgemm_s8_kernel<2>: + the norm's weight and bias, fp16 [256] each
 
 struct TsPacked {   // EPI == 1: destination of the encoder's value projection
   char *gset, *sset;   // (EPI == 2: the LayerNorm's weight and bias, fp16 [N])
@@ -805,6 +806,8 @@ __global__ __launch_bounds__(kTsThreads) void tsgemm_ws_kernel(const __half *__r
 // lanes 32..63 the second 16 of a 32-value sub-step).  Measured (profiles/r04/tsgemm_s8_ab.jsonl): faster than the
 // tiled int8 GEMM on the 256-column layers with K = 1 024 (stage-3 conv1: 21.5 vs 24.6 us), slower for N > 256 (every
 // 256-column chunk re-reads the activation rows): functions/int8_chain.py picks it for the former only.
+// A second flavour (EPI == 2, bevops_tsgemm_s8_ln) puts the LayerNorm that ends every encoder block of the INT8 engine in
+// the epilogue: see the comment at the kernel.
 typedef int i32x4v __attribute__((ext_vector_type(4)));
 typedef int i32x16v __attribute__((ext_vector_type(16)));
 
@@ -817,7 +820,20 @@ struct TsS8Args {
   int M, N, K, relu, units_total, res_i8, out_i8;
 };
 
-__global__ __launch_bounds__(kTsThreads) void tsgemm_s8_kernel(const TsS8Args p) {
+struct TsS8LnArgs : TsS8Args {   // EPI == 2: the LayerNorm's weight and bias (pk.gset / pk.sset, fp16 [256]) and eps
+  TsPacked pk;
+};
+
+// EPI 0: the epilogue above.  EPI 2 (N == 256, one column chunk, fp16 out, no ReLU): the block's LayerNorm in the
+// epilogue, out = LayerNorm_256(fp16(acc * s_a * s_w + bias (+ identity))) * ln_weight + ln_bias, with the row layout of
+// tsgemm_f16_kernel<2>: a thread owns the same 8 columns of the same rows in both 128-column halves, keeps the rounded
+// sums of half 0 in registers (5 row passes x 16 bytes, nothing is stored in half 0) and normalises the row in half 1
+// (ts_ln_row: fp32 mean and centred squares over the 16 lanes of a DPP row, one rounding) -- from exactly the binary16
+// values the pair bevops_tsgemm_s8 (fp16 out) -> bevops_layer_norm would have read back.  The arguments of the two
+// flavours are different types, so the EPI 0 instantiation keeps its argument segment and its code.
+template <int EPI>
+__global__ __launch_bounds__(kTsThreads) void tsgemm_s8_kernel(
+    const std::conditional_t<EPI == 2, TsS8LnArgs, TsS8Args> p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int M = p.M, N = p.N, K = p.K;
@@ -851,6 +867,19 @@ __global__ __launch_bounds__(kTsThreads) void tsgemm_s8_kernel(const TsS8Args p)
       scol[4 * rq + e] = p.wscale ? p.s_aw * p.wscale[col] : p.s_aw;
       bcol[4 * rq + e] = p.bias ? p.bias[col] : 0.f;
     }
+  // EPI 2: the norm's weight and bias (fp16 [256] each) are read from global memory once, before the first tile, into the
+  // 1 KB of LDS behind the three stages; a thread fetches its columns' 64 bytes from there in half 1, where the
+  // accumulators are dead (held in registers for the whole launch they cost 16 VGPRs at the kernel's peak: it spilled)
+  TsPacked ln_lds;
+  if constexpr (EPI == 2) {
+    ln_lds.gset = smem + kTsLds;
+    ln_lds.sset = smem + kTsLds + kTsBN * 2;
+    if (tid < 64) {
+      const char *src = (tid < 32 ? p.pk.gset : p.pk.sset) + (tid & 31) * 16;
+      *reinterpret_cast<uint4 *>(smem + kTsLds + tid * 16) = *reinterpret_cast<const uint4 *>(src);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // written before this wave's first barrier (in the k loop)
+    }
+  }
   for (int u0 = u_begin; u0 < u_end; u0 += kTsG) {
     const int G = min(kTsG, u_end - u0);
     const int r0 = u0 * 32;
@@ -928,6 +957,7 @@ __global__ __launch_bounds__(kTsThreads) void tsgemm_s8_kernel(const TsS8Args p)
     __builtin_amdgcn_s_barrier();
     // ---- epilogue through LDS (fp32: sums already scaled and shifted), two halves of 128 columns
     const int rows = min(G * 32, M - r0);
+    uint4 keep[kTsG];   // EPI 2: the rounded sums of half 0 of this thread's (row, 8 columns), per row pass
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       if ((wave >> 2) == half) {
@@ -948,6 +978,48 @@ __global__ __launch_bounds__(kTsThreads) void tsgemm_s8_kernel(const TsS8Args p)
         }
       }
       __builtin_amdgcn_s_barrier();
+      if constexpr (EPI == 2) {
+        // Row pass `it` of this thread is tile row (tid >> 4) + 32 it: a compile-time index with an `r < rows` guard, so
+        // keep[] / rsum[] are registers, never a dynamically indexed array in scratch.  The 16 threads of a row are 16
+        // consecutive lanes: the guard is uniform over the DPP row ts_ln_row reduces over.
+        auto ln_pass = [&](auto itc) __attribute__((always_inline)) {
+          constexpr int it = decltype(itc)::value;
+          const int r = (tid >> 4) + 32 * it;
+          if (r >= rows) return;
+          const int c8 = tid & 15;
+          const float4 lo = *reinterpret_cast<const float4 *>(smem + r * kTsEpiStride + c8 * 32);
+          const float4 hi4 = *reinterpret_cast<const float4 *>(smem + r * kTsEpiStride + c8 * 32 + 16);
+          float v[8] = {lo.x, lo.y, lo.z, lo.w, hi4.x, hi4.y, hi4.z, hi4.w};
+          const int col = half * 128 + c8 * 8;
+          const size_t m = (size_t)(r0 + r);
+          if (p.res) {
+            if (p.res_i8) {
+              const uint2 q = *reinterpret_cast<const uint2 *>(static_cast<const int8_t *>(p.res) + m * kTsBN + col);
+#pragma unroll
+              for (int c = 0; c < 4; ++c) {
+                v[c] += (float)(int)(signed char)((q.x >> (8 * c)) & 0xffu) * p.s_res;
+                v[4 + c] += (float)(int)(signed char)((q.y >> (8 * c)) & 0xffu) * p.s_res;
+              }
+            } else {
+              ts_add_res(v, *reinterpret_cast<const uint4 *>(static_cast<const __half *>(p.res) + m * kTsBN + col));
+            }
+          }
+          const uint4 o = ts_pack8(v);   // the ONE rounding of the pre-norm value, as the fp16-output path rounds it
+          if (half == 0) {
+            keep[it] = o;
+          } else {
+            uint4 gb[4];
+            ts_ln_params(ln_lds, c8, gb);
+            ts_ln_row(keep[it], o, ts_sum8(keep[it]) + ts_sum8(o), p.pk.eps, gb, static_cast<__half *>(p.out) + m * kTsBN, c8);
+          }
+        };
+        ln_pass(std::integral_constant<int, 0>{}); ln_pass(std::integral_constant<int, 1>{});
+        ln_pass(std::integral_constant<int, 2>{}); ln_pass(std::integral_constant<int, 3>{});
+        ln_pass(std::integral_constant<int, 4>{});
+        // the staging rows are read: half 1 may overwrite them, the next tile's DMA may overwrite stages 0 and 1
+        __builtin_amdgcn_s_barrier();
+        continue;
+      }
       for (int r = tid >> 4; r < rows; r += kTsThreads / 16) {
         const int c8 = tid & 15;
         const float4 lo = *reinterpret_cast<const float4 *>(smem + r * kTsEpiStride + c8 * 32);
@@ -1121,7 +1193,7 @@ extern "C" int bevops_tsgemm_s8(const void *a_q, float scale_a, const void *w_q,
       (residual && (reinterpret_cast<uintptr_t>(residual) & (res_dtype == BEVOPS_I8 ? 7u : 15u))) ||
       (bias && (reinterpret_cast<uintptr_t>(bias) & 3u)) || (w_scales && (reinterpret_cast<uintptr_t>(w_scales) & 3u)))
     return BEVOPS_BAD_PARAM;
-  if (!ensure_dynamic_lds<tsgemm_s8_kernel>(kTsLds)) return BEVOPS_FAILURE;
+  if (!ensure_dynamic_lds<tsgemm_s8_kernel<0>>(kTsLds)) return BEVOPS_FAILURE;
   const int units = (int)((m + 31) / 32);
   const dim3 grid((unsigned)ts_grid_x(units, n / kTsBN), (unsigned)(n / kTsBN));
   TsS8Args p;
@@ -1133,7 +1205,40 @@ extern "C" int bevops_tsgemm_s8(const void *a_q, float scale_a, const void *w_q,
   p.M = (int)m; p.N = n; p.K = k; p.relu = relu; p.units_total = units;
   p.res_i8 = residual && res_dtype == BEVOPS_I8 ? 1 : 0;
   p.out_i8 = out_dtype == BEVOPS_I8 ? 1 : 0;
-  hipLaunchKernelGGL(tsgemm_s8_kernel, grid, dim3(kTsThreads), kTsLds, static_cast<hipStream_t>(stream), p);
+  hipLaunchKernelGGL(tsgemm_s8_kernel<0>, grid, dim3(kTsThreads), kTsLds, static_cast<hipStream_t>(stream), p);
+  return launch_status();
+}
+
+// The int8 GEMM with the block's LayerNorm in its epilogue (tsgemm_s8_kernel<2>): arguments as bevops_tsgemm_s8 with an
+// fp16 output and no ReLU, plus the norm's fp16 [256] weight / bias and eps.  N must be 256, K % 128 == 0; no workspace.
+extern "C" int bevops_tsgemm_s8_ln(const void *a_q, float scale_a, const void *w_q, const float *w_scales, float scale_w,
+                                   const float *bias, const void *residual, int res_dtype, float scale_res,
+                                   const void *ln_weight, const void *ln_bias, float eps, void *out, long long m, int n,
+                                   int k, void *stream) {
+  if (!a_q || !w_q || !out || !ln_weight || !ln_bias || m <= 0 || n <= 0 || k <= 0 || !(eps >= 0.f)) return BEVOPS_BAD_PARAM;
+  if (!(scale_a > 0.f) || (!w_scales && !(scale_w > 0.f))) return BEVOPS_BAD_PARAM;
+  if (k % 128 != 0 || n != kTsBN) return BEVOPS_NOT_SUPPORTED;
+  if (residual && res_dtype != BEVOPS_I8 && res_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  if (residual && res_dtype == BEVOPS_I8 && !(scale_res > 0.f)) return BEVOPS_BAD_PARAM;
+  if ((double)m * k >= 4294967040.0 || m > 0x7fffffff) return BEVOPS_NOT_SUPPORTED;
+  if (!aligned16(a_q) || !aligned16(w_q) || !aligned16(out) || !aligned16(ln_weight) || !aligned16(ln_bias) ||
+      (residual && (reinterpret_cast<uintptr_t>(residual) & (res_dtype == BEVOPS_I8 ? 7u : 15u))) ||
+      (bias && (reinterpret_cast<uintptr_t>(bias) & 3u)) || (w_scales && (reinterpret_cast<uintptr_t>(w_scales) & 3u)))
+    return BEVOPS_BAD_PARAM;
+  if (!ensure_dynamic_lds<tsgemm_s8_kernel<2>>(kTsS8LnLds)) return BEVOPS_FAILURE;
+  const int units = (int)((m + 31) / 32);
+  const dim3 grid((unsigned)ts_grid_x(units, 1), 1u);
+  TsS8LnArgs p{};
+  p.a = static_cast<const int8_t *>(a_q); p.w = static_cast<const int8_t *>(w_q);
+  p.bias = bias; p.wscale = w_scales; p.res = residual; p.out = out;
+  p.s_aw = w_scales ? scale_a : scale_a * scale_w;
+  p.s_res = scale_res;
+  p.M = (int)m; p.N = n; p.K = k; p.units_total = units;
+  p.res_i8 = residual && res_dtype == BEVOPS_I8 ? 1 : 0;
+  p.pk.gset = const_cast<char *>(static_cast<const char *>(ln_weight));
+  p.pk.sset = const_cast<char *>(static_cast<const char *>(ln_bias));
+  p.pk.eps = eps;
+  hipLaunchKernelGGL(tsgemm_s8_kernel<2>, grid, dim3(kTsThreads), kTsS8LnLds, static_cast<hipStream_t>(stream), p);
   return launch_status();
 }
 

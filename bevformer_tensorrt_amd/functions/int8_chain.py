@@ -78,6 +78,48 @@ def linear_int8_chain(a, scale_a, w_q, scale_w, bias=None, residual=None, scale_
     return out.view(*a.shape[:-1], N)
 
 
+def linear_int8_ln(a_q, scale_a, w_q, scale_w, bias=None, residual=None, scale_res=1.0, ln_weight=None, ln_bias=None,
+                   eps=1e-5):
+    """layer_norm((a_q . w_q^T) * scale_a * scale_w + bias + residual) * ln_weight + ln_bias in ONE launch
+    (bevops_tsgemm_s8_ln): the int8 dense layer that ends an encoder block together with the block's norm.  a_q [..., K]
+    int8 (already quantised with scale_a), w_q [256, K] int8, scale_w a float or an fp32 [256] tensor, bias fp32 [256],
+    residual [..., 256] fp16 -- or int8 with scale_res --, ln_weight / ln_bias [256] -> fp16 [..., 256].  Equal to
+    layer_norm(linear_int8_chain(..., out fp16 on bevops_tsgemm_s8)) up to the last bit of the normalisation (same binary16
+    sums, fp32 statistics).  Raises BevopsError (NOT_SUPPORTED) unless N == 256 and K % 128 == 0."""
+    assert a_q.is_cuda and a_q.dtype == torch.int8 and w_q.dtype == torch.int8
+    assert ln_weight is not None and ln_bias is not None
+    K, N = a_q.shape[-1], w_q.shape[0]
+    if w_q.shape[1] != K:
+        raise ValueError(f"w_q {tuple(w_q.shape)} does not match a_q [..., {K}]")
+    a2 = a_q.reshape(-1, K)
+    if not a2.is_contiguous():
+        a2 = a2.contiguous()
+    w_q = w_q.contiguous()
+    M = a2.shape[0]
+    per_channel = torch.is_tensor(scale_w)
+    ws = scale_w.float().contiguous() if per_channel else None
+    b = bias.float().contiguous() if bias is not None else None
+    r = None
+    if residual is not None:
+        assert residual.dtype in (torch.int8, torch.float16) and residual.numel() == M * N
+        r = residual.reshape(M, N)
+        if not r.is_contiguous():
+            r = r.contiguous()
+    g, be = ln_weight.to(torch.float16).contiguous(), ln_bias.to(torch.float16).contiguous()
+    out = torch.empty((M, N), dtype=torch.float16, device=a_q.device)
+    if M == 0:
+        return out.view(*a_q.shape[:-1], N)
+    handle = _lib.load_library()
+    with torch.cuda.device(a_q.device):
+        st = handle.bevops_tsgemm_s8_ln(
+            a2.data_ptr(), float(scale_a), w_q.data_ptr(), ws.data_ptr() if per_channel else None,
+            1.0 if per_channel else float(scale_w), b.data_ptr() if b is not None else None,
+            r.data_ptr() if r is not None else None, _code(r.dtype) if r is not None else _lib.F16, float(scale_res),
+            g.data_ptr(), be.data_ptr(), float(eps), out.data_ptr(), M, N, K, _lib.current_stream_ptr(a_q.device))
+    _lib.check(st, "bevops_tsgemm_s8_ln")
+    return out.view(*a_q.shape[:-1], N)
+
+
 def conv_int8_chain_nhwc(x_q, scale_a, w_q_taps, scale_w, bias=None, relu=False, stride=1, out_dtype=torch.float16,
                          scale_out=1.0):
     """k x k (k in {1, 3}, pad k // 2) convolution of an int8 channels-last activation x_q [B, Cin, H, W] as an

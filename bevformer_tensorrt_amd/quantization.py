@@ -438,6 +438,7 @@ class Int8PluginOps:
         # optional predicate site -> bool: in the int8 phase a site it rejects keeps its fp operator (a layer-precision
         # fallback, as a TensorRT build allows per layer; tools/int8_attribution.py switches groups of sites with it)
         self.site_filter = None
+        self.int8_ln_fused = None      # bevformer._INT8_LN_FUSED for the model on this namespace (None: the switch's value)
 
     def __getattr__(self, name):       # only reached for names this class does not define
         if name in self.__dict__.get("_pass", ()) and hasattr(self.fp, name):
@@ -648,6 +649,24 @@ class LinearQ(torch.nn.Linear):
         a = xh if FUSED_QUANT["enabled"] and xh.shape[-1] % 16 == 0 else _f.quantize_rows(xh, self.scale_in)
         y = _f.linear_int8(a, self.scale_in, self.weight_q, self.scale_w, self.bias_f32, res, relu)
         return y if y.dtype == x.dtype else y.to(x.dtype)
+
+    def forward_q(self, x, scale_out, relu=False):
+        """"int8" mode only: the layer on an fp16 operand with its output requantised to int8 at `scale_out` (a consumer's
+        `scale_in`) in the GEMM's epilogue -- bevops_linear_int8_chain, the operand quantised as rne(x / scale_in) from the
+        fp32 value inside the operand load.  -> int8 [..., out_features]."""
+        assert self.mode == "int8" and x.dtype == torch.float16
+        from .functions import int8_chain as C
+        return C.linear_int8_chain(x, self.scale_in, self.weight_q, self.scale_w, self.bias_f32, None, 1.0, relu,
+                                   torch.int8, scale_out)
+
+    def forward_norm_from_q(self, a_q, residual, norm):
+        """"int8" mode only: norm(layer(a_q) + residual) in ONE launch (bevops_tsgemm_s8_ln) on an operand that is already
+        int8 at this layer's `scale_in` (what `forward_q` of the producer wrote); residual fp16 or None, `norm` an
+        nn.LayerNorm over 256 columns.  -> fp16 [..., 256]."""
+        assert self.mode == "int8" and a_q.dtype == torch.int8
+        from .functions import int8_chain as C
+        return C.linear_int8_ln(a_q, self.scale_in, self.weight_q, self.scale_w, self.bias_f32, residual, 1.0,
+                                norm.weight, norm.bias, norm.eps)
 
 
 class Conv2dQ(torch.nn.Conv2d):
@@ -974,7 +993,7 @@ def engine_dense_select(name, mod):
 
 
 def build_int8_engine(B, name, dev, frames, calibrator="entropy", chain=True, dense_select=None, decoder_int8=False,
-                      sca_int8=False, calibration_cache=None):
+                      sca_int8=False, calibration_cache=None, block_norm_fused=None):
     """The PTQ build of the re-hosted model that bench.py times (`B` = the bevformer module, `frames` = an iterable
     of (image, can_bus, lidar2img) calibration frames of one scene): int8 activation chain through the backbone
     (Int8ChainBackbone; chain=False: Conv2dQ layers with fp16 tensors between them, the round-3 build), encoder
@@ -986,6 +1005,9 @@ def build_int8_engine(B, name, dev, frames, calibrator="entropy", chain=True, de
     calibration_cache (a path; `*_device` calibrators only): a file that does not exist is written after calibrating
     from `frames`; one that exists is loaded INSTEAD of calibrating -- no frame is run, `frames` may be empty -- and
     gives the same scales.  Besides the states it holds the MSDA sites' batch sizes, which `site_filter` reads.
+    block_norm_fused: the encoder blocks of the returned model with their LayerNorm in the epilogue of the block's last
+    int8 GEMM, the FFN's hidden tensor int8 (bevformer._INT8_LN_FUSED; True / False for this model, None = the switch's
+    value, off unless BEVOPS_INT8_LN_FUSED=1).
     Returns (model, qops, note)."""
     dtype = torch.float16
     if calibration_cache is not None:
@@ -994,6 +1016,7 @@ def build_int8_engine(B, name, dev, frames, calibrator="entropy", chain=True, de
             raise ValueError("calibration_cache needs a device calibrator (minmax_device, percentile_device, "
                              "entropy_device)")
     qops = Int8PluginOps(calibrator, channels_last=True, fused_sca=not sca_int8, engine=True)
+    qops.int8_ln_fused = None if block_norm_fused is None else bool(block_norm_fused)
     if sca_int8:
         qops._pass = tuple(n for n in qops._pass if not n.startswith("spatial_cross_attention"))
     model = B.BEVFormer(name, ops=qops, seed=0, backbone_layout="nhwc").to(dev, dtype)

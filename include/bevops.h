@@ -732,6 +732,20 @@ int bevops_mha_selfattn_f16(const void *qkv, void *out, int num_query, int heads
 int bevops_tsgemm_s8(const void *a_q, float scale_a, const void *w_q, const float *w_scales, float scale_w,
                      const float *bias, const void *residual, int res_dtype, float scale_res, int out_dtype,
                      void *out, float scale_out, long long m, int n, int k, int relu, void *stream);
+/* That kernel with the LayerNorm that ends every encoder block in its epilogue (the int8 counterpart of
+ * bevops_tsgemm_f16_ln):
+ *     out = LayerNorm_256(fp16(acc * scale_a * scale_w[n] + bias[n] (+ identity[m, n]))) * ln_weight + ln_bias.
+ * The pre-norm value is rounded to binary16 once, exactly as bevops_tsgemm_s8 rounds its fp16 output; the row is then
+ * normalised from those values with fp32 statistics (mean, centred squares, one rounding): the result is what the pair
+ * bevops_tsgemm_s8 (fp16 out) -> bevops_layer_norm gives, up to the last bit of the normalisation, without the second
+ * launch and the [M, 256] round trip.  No ReLU; identity int8 (with scale_res) or fp16 or NULL; w_scales fp32 [256] or
+ * NULL (then scale_w); ln_weight / ln_bias fp16 [256]; out fp16 [M, 256]; a_q, w_q, ln_weight, ln_bias, out 16-byte
+ * aligned.  No workspace.  BEVOPS_NOT_SUPPORTED when n != 256 or k % 128 != 0; BEVOPS_BAD_PARAM for a missing
+ * ln_weight / ln_bias, !(eps >= 0) or a misaligned operand. */
+int bevops_tsgemm_s8_ln(const void *a_q, float scale_a, const void *w_q, const float *w_scales, float scale_w,
+                        const float *bias, const void *residual, int res_dtype, float scale_res,
+                        const void *ln_weight, const void *ln_bias, float eps, void *out, long long m, int n, int k,
+                        void *stream);
 
 /* The same dense layer for problems with FEW rows (the decoder's 900 object queries: decoder.py:381-471,
  * bevformer_head.py:247-282; csrc/small_gemm.hip): 32 x 64 output tiles, split-K over the four waves of a block, every
