@@ -20,10 +20,97 @@ the bev_pool_v2 plugin:
 BEVDet-R50 config (configs/bevdet/bevdet-r50-cbgs.py:44-104): 6 cameras of 256x704, downsample 16
 (16x44 features), 59 depth bins, 64 channels, 128x128 BEV cells of 0.8 m.
 """
+import contextlib
+import os
+
 import torch
 import torch.nn as nn
 
 from . import functions as _hip_ops
+from .functions.multi_scale_deformable_attn import _TensorCache
+
+# BEVDet(..., bev_half=...): "torch" = the framework statements between the image neck and the detections (depth_net
+# through the library, softmax / slice / layout copies, F.interpolate + torch.cat, the heads' narrow convolutions
+# through the library), "hip" = those on this package's kernels (see BEVDet.prepare_bev_half).  The environment
+# variable overrides the DEFAULT, read at construction.
+BEV_HALF_MODES = ("torch", "hip")
+
+
+def default_bev_half():
+    mode = os.environ.get("BEVOPS_BEVDET_BEV_HALF", "torch")
+    if mode not in BEV_HALF_MODES:
+        raise ValueError(f"BEVOPS_BEVDET_BEV_HALF = {mode!r}: 'torch' or 'hip'")
+    return mode
+
+
+@contextlib.contextmanager
+def _rule_dispatch():
+    """The dense / convolution dispatch by RULE for the calling thread (functions.linear.DETERMINISTIC): this package's
+    kernels whatever the shipped table measured, no measurement at run time, no library fall-back under capture."""
+    from .functions.linear import DETERMINISTIC
+    was, DETERMINISTIC["enabled"] = DETERMINISTIC["enabled"], True
+    try:
+        yield
+    finally:
+        DETERMINISTIC["enabled"] = was
+
+
+DEPTH_NET_COLUMNS = 128   # the merged depth_net GEMM's row: [features | depth logits | zero pad]
+
+
+def merge_depth_net(weight, bias, D, C):
+    """depth_net ([D + C, Cin, 1, 1]: depth logits first, then the context features) as ONE GEMM operand whose output
+    row the split kernel reads in place: weight [128, Cin] and bias [128] with the features in columns 0 .. C, the
+    depth logits in columns `depth_offset` = C rounded up to 8 .. + D, zero columns behind them.  Both ranges start
+    16-byte aligned.  -> (weight, bias, layout) with layout = dict(row_stride, feat_offset, depth_offset)."""
+    cin = weight.shape[1]
+    depth_offset = (C + 7) // 8 * 8
+    if weight.shape[0] != D + C or depth_offset + D > DEPTH_NET_COLUMNS:
+        raise ValueError(f"merge_depth_net: {weight.shape[0]} rows for D = {D}, C = {C} ({DEPTH_NET_COLUMNS} columns)")
+    w2 = weight.detach().reshape(D + C, cin)
+    w = w2.new_zeros((DEPTH_NET_COLUMNS, cin))
+    b = w2.new_zeros((DEPTH_NET_COLUMNS,))
+    w[:C].copy_(w2[D:])
+    w[depth_offset:depth_offset + D].copy_(w2[:D])
+    if bias is not None:
+        b[:C].copy_(bias.detach()[D:])
+        b[depth_offset:depth_offset + D].copy_(bias.detach()[:D])
+    return w, b, dict(row_stride=DEPTH_NET_COLUMNS, feat_offset=0, depth_offset=depth_offset)
+
+
+HEAD_PACK_CHANNELS = 32   # the packed head output: 20 channels in HEADS_R50 order, then zero channels
+
+
+def merge_heads(first, final):
+    """The six two-convolution heads as two convolutions.  first / final: lists of (weight, bias) in head order,
+    weight [64, Cs, 3, 3] and [c_i, 64, 3, 3].  -> (w1 [6 * 64, Cs, 3, 3], b1, w2 [32, 6 * 64, 3, 3], b2, slices):
+    w1 / b1 are the first convolutions stacked along the output channels; w2 is block-diagonal -- head i's final
+    weights on input channels 64 i .. 64 i + 63, its c_i output channels at slices[i] = (start, stop), heads in order,
+    zero rows behind channel sum(c_i).  A zero weight adds an exact zero to the fp32 accumulator, so every head's
+    output is what its own two convolutions give."""
+    mid = first[0][0].shape[0]
+    n_out = sum(w.shape[0] for w, _ in final)
+    if n_out > HEAD_PACK_CHANNELS:
+        raise ValueError(f"merge_heads: {n_out} output channels, the packed output holds {HEAD_PACK_CHANNELS}")
+    w0 = first[0][0].detach()
+    w1 = w0.new_zeros((len(first) * mid,) + tuple(w0.shape[1:]))
+    b1 = w0.new_zeros((len(first) * mid,))
+    w2 = w0.new_zeros((HEAD_PACK_CHANNELS, len(first) * mid) + tuple(final[0][0].shape[2:]))
+    b2 = w0.new_zeros((HEAD_PACK_CHANNELS,))
+    slices, at = [], 0
+    for i, ((wa, ba), (wb, bb)) in enumerate(zip(first, final)):
+        if wa.shape[0] != mid or wb.shape[1] != mid:
+            raise ValueError("merge_heads: every head needs the same middle width")
+        w1[i * mid:(i + 1) * mid].copy_(wa.detach())
+        if ba is not None:
+            b1[i * mid:(i + 1) * mid].copy_(ba.detach())
+        c = wb.shape[0]
+        w2[at:at + c, i * mid:(i + 1) * mid].copy_(wb.detach())
+        if bb is not None:
+            b2[at:at + c].copy_(bb.detach())
+        slices.append((at, at + c))
+        at += c
+    return w1, b1, w2, b2, slices
 
 # data_config of configs/bevdet/bevdet-r50-cbgs.py:44-62, the entries the test pipeline reads
 DATA_CONFIG_R50 = dict(input_size=(256, 704), src_size=(900, 1600), crop_h=(0.0, 0.0), resize_test=0.0)
@@ -34,10 +121,13 @@ BEVDET_R50 = dict(
 
 
 class LSSViewTransformer(nn.Module):
-    def __init__(self, grid_config, input_size, downsample, in_channels, out_channels, ops=None, seed=0):
+    def __init__(self, grid_config, input_size, downsample, in_channels, out_channels, ops=None, seed=0, bev_half=None):
         super().__init__()
         torch.manual_seed(seed)
         self.ops = ops if ops is not None else _hip_ops
+        self.bev_half = default_bev_half() if bev_half is None else bev_half
+        if self.bev_half not in BEV_HALF_MODES:
+            raise ValueError(f"bev_half = {self.bev_half!r}: 'torch' or 'hip'")
         self.create_grid_infos(**grid_config)
         self.frustum = self.create_frustum(grid_config["depth"], input_size, downsample)
         self.out_channels, self.in_channels = out_channels, in_channels
@@ -191,11 +281,57 @@ class LSSViewTransformer(nn.Module):
         return prepare(self._frustum_on(calib.device), calib, self.grid_lower_bound, self.grid_interval, self.grid_size,
                        padded=padded)
 
+    # ---- bev_half = "hip": depth_net as one 128-column GEMM, softmax + split as one launch, no layout copies
+    def _hip_on(self, x):
+        """"hip" takes effect for channels-last fp16 CUDA activations on an operator set that has the new functions and
+        a plain depth_net (an INT8 build's operator set / quantised layer keep the torch statements)."""
+        return self.bev_half == "hip" and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 \
+            and x.is_contiguous(memory_format=torch.channels_last) and type(self.depth_net) is nn.Conv2d \
+            and all(hasattr(self.ops, f) for f in ("lss_depth_split", "dense_auto"))
+
+    def _depth_net_sources(self):
+        return [self.depth_net.weight] + ([] if self.depth_net.bias is None else [self.depth_net.bias])
+
+    def depth_net_merged(self, build=True):
+        """(weight [128, Cin], bias [128], layout) of `merge_depth_net` on the device of depth_net's weight, cached and
+        rebuilt when the weight or bias changes (stamped like functions.conv.pack_taps' cache).  build=False: None when
+        the cached operand is missing or stale."""
+        stamp = tuple(_TensorCache._stamp(t) for t in self._depth_net_sources())
+        hit = self.__dict__.get("_depth_net_merged")
+        if hit is not None and hit[0] == stamp:
+            return hit[1]
+        if not build:
+            return None
+        merged = merge_depth_net(self.depth_net.weight, self.depth_net.bias, self.D, self.out_channels)
+        self.__dict__["_depth_net_merged"] = (stamp, merged)
+        return merged
+
+    def _depth_feat_hip(self, x):
+        """x [N, Cin, H, W] channels-last fp16 -> (depth [N, D, H, W], feat [N, H, W, C]): two launches."""
+        merged = self.depth_net_merged(build=False)
+        if merged is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("LSSViewTransformer: the merged depth_net operand is missing or stale and the stream "
+                                   "is capturing; call BEVDet.prepare_bev_half() (or the model once, eagerly) first")
+            merged = self.depth_net_merged()
+        w, b, lay = merged
+        n, cin, h, wd = x.shape
+        rows = x.permute(0, 2, 3, 1).reshape(n * h * wd, cin)        # (a view: channels-last)
+        with _rule_dispatch():
+            y = self.ops.dense_auto(rows, w, b, None, False)
+        return self.ops.lss_depth_split(y, n, self.D, self.out_channels, lay["depth_offset"], lay["feat_offset"],
+                                        spatial=(h, wd))
+
     @torch.no_grad()
     def view_transform_calibrated(self, x, calib):
         """`view_transform` with the index build on the device: x as there, calib = the packed fp32 buffer of
         `calibration_matrices` on x's device.  No host synchronisation: capturable with the frame."""
         rb, rd, rf, ist, il, counts = self.prepare_calibrated(calib)
+        bev_h, bev_w = int(self.grid_size[1]), int(self.grid_size[0])
+        if self._hip_on(x):
+            depth, tran_feat = self._depth_feat_hip(x)
+            out = self.ops.bev_pool_v2_indirect(depth, tran_feat, rd, rf, rb, ist, il, counts, bev_h, bev_w)
+            return out.permute(0, 3, 1, 2)       # (channels-last view: what bev_encoder takes, no copy either way)
         x = self.depth_net(x)
         depth = x[:, : self.D].softmax(dim=1)
         tran_feat = x[:, self.D: self.D + self.out_channels].permute(0, 2, 3, 1)
@@ -208,6 +344,11 @@ class LSSViewTransformer(nn.Module):
     def view_transform(self, x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths):
         """x [N_cams, in_channels, H_feat, W_feat] (image-neck output) -> BEV features
         [1, out_channels, bev_h, bev_w]: BEVDetTRT.forward_trt, det2trt/models/detector/bevdet.py:50-76."""
+        if self._hip_on(x):
+            depth, tran_feat = self._depth_feat_hip(x)
+            out = self.ops.bev_pool_v2_2(depth, tran_feat, ranks_depth, ranks_feat, ranks_bev, interval_starts,
+                                         interval_lengths, int(self.grid_size[1]), int(self.grid_size[0]))
+            return out.permute(0, 3, 1, 2)
         x = self.depth_net(x)
         depth = x[:, : self.D].softmax(dim=1)
         tran_feat = x[:, self.D: self.D + self.out_channels].permute(0, 2, 3, 1)
@@ -300,16 +441,20 @@ class BEVDet(nn.Module):
     """forward(image [1, 6, 3, H, W], ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths)
     -> (reg, height, dim, rot, vel, heatmap), each [1, c, 128, 128] -- BEVDetTRT.forward_trt."""
 
-    def __init__(self, cfg=None, ops=None, seed=0):
+    def __init__(self, cfg=None, ops=None, seed=0, bev_half=None):
         super().__init__()
         torch.manual_seed(seed)
         cfg = cfg or BEVDET_R50
         self.cfg = cfg
+        self.bev_half = default_bev_half() if bev_half is None else bev_half
+        if self.bev_half not in BEV_HALF_MODES:
+            raise ValueError(f"bev_half = {self.bev_half!r}: 'torch' or 'hip'")
         self.ops = ops = ops if ops is not None else _hip_ops
         self.backbone = _B.ResNet(50, (False,) * 4, (2, 3), ops, "pytorch")
         self.neck = CustomFPN()
         self.view = LSSViewTransformer(**{k: cfg[k] for k in ("grid_config", "input_size", "downsample", "in_channels",
-                                                              "out_channels")}, ops=ops, seed=seed)
+                                                              "out_channels")}, ops=ops, seed=seed,
+                                       bev_half=self.bev_half)
         c = cfg["out_channels"]
         chans, cin, stages = [2 * c, 4 * c, 8 * c], c, []
         for ch in chans:
@@ -323,16 +468,20 @@ class BEVDet(nn.Module):
                                     for k, n in HEADS_R50})
         self.eval()
 
+    def _nhwc_weights(self):
+        """Once per model: the 3x3 / 7x7 filters channels-last, like the activations of the fp16 path."""
+        if not getattr(self, "_nhwc_ready", False):
+            for m in self.modules():
+                if isinstance(m, nn.Conv2d) and m.kernel_size != (1, 1):
+                    m.weight.data = m.weight.data.contiguous(memory_format=torch.channels_last)
+            self._nhwc_ready = True
+
     def image_features(self, image):
         """img_backbone + img_neck: [6, 3, H, W] -> [6, 256, H / 16, W / 16]."""
         ops = self.ops
         nhwc = image.is_cuda and image.dtype == torch.float16 and hasattr(ops, "conv3x3_auto")
         if nhwc:
-            if not getattr(self, "_nhwc_ready", False):
-                for m in self.modules():
-                    if isinstance(m, nn.Conv2d) and m.kernel_size != (1, 1):
-                        m.weight.data = m.weight.data.contiguous(memory_format=torch.channels_last)
-                self._nhwc_ready = True
+            self._nhwc_weights()
             chain = getattr(self, "int8_chain", None)     # quantization.Int8ChainBackbone, after its freeze()
             if chain is not None and chain.ready:
                 return chain(image)
@@ -341,8 +490,74 @@ class BEVDet(nn.Module):
             feats = self.backbone(image)
         return self.neck(feats, ops)
 
+    # ---- bev_half = "hip" (see the section in design/model.md)
+    def _hip_on(self, x):
+        """"hip" takes effect for fp16 CUDA tensors on an operator set that has the new functions; everything else
+        (other dtypes, the CPU, the INT8 plugin set) keeps the torch statements."""
+        return self.bev_half == "hip" and x.is_cuda and x.dtype == torch.float16 \
+            and all(hasattr(self.ops, f) for f in ("upsample_bilinear_concat_nhwc", "lss_depth_split", "conv_nhwc",
+                                                   "conv3x3_auto", "dense_auto")) \
+            and all(type(c) is nn.Conv2d for h in self.heads.values() for c in h)
+
+    def _head_sources(self):
+        return [t for k, _ in HEADS_R50 for c in self.heads[k] for t in (c.weight, c.bias) if t is not None]
+
+    def heads_merged(self, build=True):
+        """(w1, b1, w2, b2, slices) of `merge_heads` for the six heads, on the device of their weights; cached and
+        rebuilt when a source weight or bias changes.  build=False: None when missing or stale."""
+        stamp = tuple(_TensorCache._stamp(t) for t in self._head_sources())
+        hit = self.__dict__.get("_heads_merged")
+        if hit is not None and hit[0] == stamp:
+            return hit[1]
+        if not build:
+            return None
+        hs = [self.heads[k] for k, _ in HEADS_R50]
+        w1, b1, w2, b2, slices = merge_heads([(h[0].weight, h[0].bias) for h in hs], [(h[1].weight, h[1].bias) for h in hs])
+        # (taps-major kernels read channels-last weights; keep the layout the model's own 3x3 weights have)
+        merged = (w1.contiguous(memory_format=torch.channels_last), b1, w2.contiguous(memory_format=torch.channels_last), b2,
+                  slices)
+        self.__dict__["_heads_merged"] = (stamp, merged)
+        return merged
+
+    def prepare_bev_half(self):
+        """Build (or refresh) the merged operands of the "hip" BEV half on the device the weights live on: depth_net as
+        a 128-column GEMM ([features | depth logits | zeros]), the six heads' first convolutions as one 64 -> 384
+        convolution, their final convolutions as one block-diagonal 384 -> 32 convolution.  Allocates and copies, so it
+        must run OUTSIDE stream capture; `forward` / `forward_calibrated` call it themselves when the operands are
+        missing or a source weight changed, and raise RuntimeError when that happens on a capturing stream."""
+        p = next(self.parameters())
+        if p.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("BEVDet.prepare_bev_half() allocates: call it before the capture begins")
+        if p.is_cuda and p.dtype == torch.float16 and hasattr(self.ops, "conv3x3_auto"):
+            self._nhwc_weights()      # (what the first fp16 frame does to the filters; the merged operands follow them)
+        self.view.depth_net_merged()
+        self.heads_merged()
+        return self
+
+    def _bev_half_ready(self, x):
+        """True when the "hip" BEV half runs for activations like `x`, with its merged operands in place."""
+        if not self._hip_on(x):
+            return False
+        if self.view.depth_net_merged(build=False) is None or self.heads_merged(build=False) is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("BEVDet(bev_half='hip'): the merged operands are missing or stale and the stream is "
+                                   "capturing; call prepare_bev_half() (or the model once, eagerly) before the capture")
+            self.prepare_bev_half()
+        return True
+
+    def _heads_hip(self, feat):
+        """shared_conv, then the six heads as two launches of the tiled implicit GEMM BY RULE (functions.conv_nhwc, not
+        the measured dispatch: these shapes are in no table).  -> six channel slices [1, c, H, W] of the packed
+        [1, H, W, 32] result (no copy); functions.centerpoint_decode reads such slices in place."""
+        ops = self.ops
+        w1, b1, w2, b2, slices = self.heads_merged(build=False)
+        s = _conv(ops, feat, self.shared_conv, True)
+        packed = ops.conv_nhwc(ops.conv_nhwc(s, w1, b1, True), w2, b2, False)
+        return tuple(packed[:, a:b] for a, b in slices)
+
     def bev_encoder(self, x):
         ops = self.ops
+        hip = self._hip_on(x) and x.is_contiguous(memory_format=torch.channels_last)
         if x.is_cuda and x.dtype == torch.float16:
             x = x.contiguous(memory_format=torch.channels_last)
         feats = []
@@ -350,6 +565,12 @@ class BEVDet(nn.Module):
             for blk in stage:
                 x = blk(x, ops)
             feats.append(x)
+        if hip:
+            # cat([feats[0], x4 bilinear of feats[2]]) as ONE launch, channels-last, no intermediate; then the x2 step
+            x = ops.upsample_bilinear_concat_nhwc(feats[0], feats[2])
+            x = _conv(ops, _conv(ops, x, self.neck_conv[0], True), self.neck_conv[1], True)
+            x = ops.upsample_bilinear_concat_nhwc(None, x, scale_factor=2)
+            return _conv(ops, _conv(ops, x, self.up2_conv[0], True), self.up2_conv[1])
         x1 = F.interpolate(feats[2], scale_factor=4, mode="bilinear", align_corners=True)
         x = torch.cat([feats[0], x1], dim=1)
         if feats[0].is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous(memory_format=torch.channels_last):
@@ -360,6 +581,12 @@ class BEVDet(nn.Module):
 
     @torch.no_grad()
     def forward(self, image, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths):
+        hip = self._bev_half_ready(image)      # (first: under capture a missing operand raises before anything is launched)
+        if hip:
+            with _rule_dispatch():      # (the image half too: see forward_calibrated)
+                x = self.image_features(image.flatten(0, 1))
+                bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths)
+                return self._heads_hip(self.bev_encoder(bev))
         x = self.image_features(image.flatten(0, 1))
         bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths)
         feat = self.bev_encoder(bev)
@@ -377,7 +604,20 @@ class BEVDet(nn.Module):
     def forward_calibrated(self, image, calib):
         """`forward` from the frame's calibration instead of ready-made ranks: calib = the packed fp32 buffer of
         `view.calibration_matrices` on the image's device; the index build and the pooling run on the device."""
-        x = self.image_features(image.flatten(0, 1))
+        hip = self._bev_half_ready(image)
+        # "hip" also takes the image half's dispatch by rule: two library convolutions of ResNet stage 4 that the shipped
+        # table prefers are not run-to-run reproducible on the MI355X, and the frame's bits would differ between runs
+        with _rule_dispatch() if hip else contextlib.nullcontext():
+            x = self.image_features(image.flatten(0, 1))
+        return self.bev_half_calibrated(x, calib, hip)
+
+    @torch.no_grad()
+    def bev_half_calibrated(self, x, calib, hip=None):
+        """Everything of `forward_calibrated` behind `image_features`: x = its [cams, 256, H / 16, W / 16] result.
+        hip = None: as `bev_half` and the tensors decide."""
+        if self._bev_half_ready(x) if hip is None else hip:
+            with _rule_dispatch():
+                return self._heads_hip(self.bev_encoder(self.view.view_transform_calibrated(x, calib)))
         return self._heads(self.view.view_transform_calibrated(x, calib))
 
     # ---- CenterHead.get_bboxes up to the NMS (centerpoint_head.py:716-746), configs/bevdet/bevdet-r50-cbgs.py:138-147

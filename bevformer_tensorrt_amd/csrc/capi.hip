@@ -76,6 +76,8 @@ const Entry kTable[] = {
     {"bevops_stem_conv_pool", (void *)&bevops_stem_conv_pool},
     {"bevops_stem_set_variant", (void *)&bevops_stem_set_variant},
     {"bevops_upsample_add_nhwc", (void *)&bevops_upsample_add_nhwc},
+    {"bevops_lss_depth_split", (void *)&bevops_lss_depth_split},
+    {"bevops_upsample_bilinear_concat_nhwc", (void *)&bevops_upsample_bilinear_concat_nhwc},
     {"bevops_tsa_split", (void *)&bevops_tsa_split},
     {"bevops_queue_mean2", (void *)&bevops_queue_mean2},
     {"bevops_tsgemm_f16", (void *)&bevops_tsgemm_f16},

@@ -81,12 +81,19 @@ def nms_free_decode(cls_logits, bbox_preds, max_num, post_center_range, score_th
 
 def _map_strides(t, name):
     """(tensor, channel stride, pixel stride) of a [B, C, H, W] map the kernel can read in place: contiguous NCHW or
-    channels-last, every batch item dense; anything else is made contiguous first."""
+    channels-last, every batch item dense; for B == 1 also a channel slice of a wider channels-last tensor (strides
+    (., 1, W * Ct, Ct) with Ct >= C: BEVDet's packed head output), passed with channel stride 1 and pixel stride Ct --
+    the kernel reads the maps element by element and assumes no alignment of a map's base pointer, and with one batch
+    item its batch offset is never applied.  Anything else is made contiguous first."""
     B, C, H, W = t.shape
     if t.is_contiguous():
         return t, H * W, 1
     if t.is_contiguous(memory_format=torch.channels_last):
         return t, 1, C
+    if B == 1 and H * W > 0:
+        ct = t.stride(3) if W > 1 else (t.stride(2) if H > 1 else C)
+        if ct >= C and (C == 1 or t.stride(1) == 1) and (W == 1 or t.stride(3) == ct) and (H == 1 or t.stride(2) == W * ct):
+            return t, 1, ct
     return t.contiguous(), H * W, 1
 
 

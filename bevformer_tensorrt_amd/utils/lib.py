@@ -82,6 +82,8 @@ SIGNATURES = {
     "bevops_tsa_split": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "bevops_queue_mean2": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "bevops_upsample_add_nhwc": (c_int, [c_int, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
+    "bevops_lss_depth_split": (c_int, [c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
+    "bevops_upsample_bilinear_concat_nhwc": (c_int, [c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "bevops_feat_embed_nhwc": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, c_size_t,
                                        c_void_p]),
     "bevops_conv3x3_c32_set_variant": (c_int, [c_int]),

@@ -361,6 +361,28 @@ int bevops_stem_set_variant(int variant);
 int bevops_upsample_add_nhwc(int dtype, void *a, const void *b, int n, int h, int w, int hb, int wb,
                              int channels, void *stream);
 
+/* BEVDet's view transformer between depth_net and the pooling (not a reference plugin;
+ * det2trt/models/detector/bevdet.py:50-76: softmax over the depth bins, the feature slice, their layout copies) as ONE
+ * launch.  x: [n * hw, row_stride] fp16, channels-last pixel rows with the depth logits in columns
+ * depth_offset .. depth_offset + D and the features in feat_offset .. feat_offset + C.  depth: [n, D, hw] fp16 (the
+ * [N, D, H, W] tensor bev_pool_v2 indexes by ranks_depth) = the softmax over each pixel's D logits: maximum subtracted,
+ * exponentials and their sum in fp32, one division, one rounding.  feat: [n, hw, C] fp16, the feature columns bit for
+ * bit.  Domain: BEVOPS_F16 and 1 <= D <= 256 (else NOT_SUPPORTED); C > 0, C % 8 == 0, feat_offset % 8 == 0,
+ * row_stride % 8 == 0, both column ranges inside the row and disjoint, x and feat 16-byte aligned (else BAD_PARAM).
+ * n * hw == 0: success, no launch.  No allocation, no synchronisation; capturable. */
+int bevops_lss_depth_split(int dtype, const void *x, void *depth, void *feat, int n, int hw, int row_stride,
+                           int depth_offset, int D, int feat_offset, int C, void *stream);
+
+/* FPN_LSS's `cat([a, interpolate(b, mode="bilinear", align_corners=True)], 1)` (models/necks/lss_fpn.py) on
+ * channels-last fp16 activations in one pass (not a reference plugin): out [n, h, w, ca + cb]; a [n, h, w, ca] is
+ * copied into the first ca channels (a == NULL with ca == 0: the plain up-sampling); b [n, hb, wb, cb].  Output row y
+ * reads source row y * (hb - 1) / (h - 1) (0 when h == 1), columns likewise, evaluated as an exact fraction: the
+ * first / last outputs are the first / last inputs and an equal-size axis is the identity.  Four corners weighted in
+ * fp32, one rounding.  Any h, w, hb, wb >= 1.  ca % 8, cb % 8, 16-byte alignment, a == NULL with ca > 0: BAD_PARAM;
+ * a dtype other than BEVOPS_F16: NOT_SUPPORTED. */
+int bevops_upsample_bilinear_concat_nhwc(int dtype, const void *a, const void *b, void *out, int n, int h, int w,
+                                         int ca, int hb, int wb, int cb, void *stream);
+
 /* Encoder input assembly (det2trt/models/modules/transformer.py:138-152): dst[n, r, :] = (src[n, r, :] +
  * cam_embed[n, :]) + level_embed[:], both sums rounded to fp16 like the two tensor adds they replace; `dst` is
  * the level's first row inside the concatenated [cams, sum hw, C] feature tensor, `dst_batch_stride` its
