@@ -514,45 +514,57 @@ class TemporalSelfAttention(nn.Module):
         self.value_proj, self.output_proj = nn.Linear(EMBED, EMBED), nn.Linear(EMBED, EMBED)
         self._split = self._pos_term = None
 
-    def _split_projection(self, query, prev0, bev_pos):
+    def _split_projection(self, query, prev0, bev_pos, prev_term=None):
         """sampling_offsets and attention_weights of cat([prev_bev, query + bev_pos]) as ONE stacked
         [192, 512] weight split along K:  prev_bev @ Wa.T + query @ Wb.T + (bev_pos @ Wb.T + b), the last
         term frame-independent (cached per bev_pos storage / version).  Two K=256 GEMMs with the running sum as
         their epilogue's identity replace the add, the [nq, 512] concatenation and two K=512 GEMMs.
-        None -> the caller's module-by-module path (quantised build, fp32, CPU, no algorithm)."""
-        fn = _gemm_entry(self.ops)
-        so, aw = self.sampling_offsets, self.attention_weights
-        if fn is None or not (_R3["enabled"] and _FUSED_LINEAR["enabled"]) or query.dtype != torch.float16 \
-                or not query.is_cuda or type(so) is not nn.Linear or type(aw) is not nn.Linear:
-            return None
-        key = (so.weight._version, aw.weight._version, so.bias._version, aw.bias._version, so.weight.data_ptr())
+        `prev_term`: prev_bev @ Wa.T + the cached term, when the caller evaluated it for all layers at once
+        (_merged_prev_terms).  None -> the caller's module-by-module path (quantised build, fp32, CPU, no algorithm)."""
         try:
-            if self._split is None or self._split[0] != key:
-                w = torch.cat([so.weight, aw.weight]).detach()
-                self._split = (key, w[:, :EMBED].contiguous(), w[:, EMBED:].contiguous(),
-                               torch.cat([so.bias, aw.bias]).detach().contiguous())
-                self._pos_term = None
-            _, wa, wb, b = self._split
-            # keyed on the tensor's storage, not its Python identity: the model passes a fresh VIEW of the cached
-            # positional encoding every frame
-            pkey = (bev_pos.data_ptr(), bev_pos._version, tuple(bev_pos.shape), bev_pos.dtype)
-            if self._pos_term is None or self._pos_term[0] != pkey:
-                self._pos_term = (pkey, fn(bev_pos.reshape(-1, EMBED), wb, b, None, False))
-            t = fn(prev0.reshape(-1, EMBED), wa, None, self._pos_term[1], False)
+            terms = self._split_terms(query, bev_pos)
+            if terms is None:
+                return None
+            fn, wa, wb, pos_term = terms
+            t = prev_term if prev_term is not None else fn(prev0.reshape(-1, EMBED), wa, None, pos_term, False)
             return fn(query.reshape(-1, EMBED), wb, None, t, False)
         except _lib.BevopsError as exc:
             if exc.status != _lib.NOT_SUPPORTED:
                 raise
             return None
 
-    def forward(self, query, value, bev_pos, ref_2d, spatial_shapes, rows=None, norm=None):
+    def _split_terms(self, query, bev_pos):
+        """(GEMM entry, Wa, Wb, bev_pos @ Wb.T + b) of _split_projection, the weights and the frame-independent term from
+        their caches; None outside its domain.  May raise BevopsError (the term's GEMM)."""
+        fn = _gemm_entry(self.ops)
+        so, aw = self.sampling_offsets, self.attention_weights
+        if fn is None or not (_R3["enabled"] and _FUSED_LINEAR["enabled"]) or query.dtype != torch.float16 \
+                or not query.is_cuda or type(so) is not nn.Linear or type(aw) is not nn.Linear:
+            return None
+        key = (so.weight._version, aw.weight._version, so.bias._version, aw.bias._version, so.weight.data_ptr())
+        if self._split is None or self._split[0] != key:
+            w = torch.cat([so.weight, aw.weight]).detach()
+            self._split = (key, w[:, :EMBED].contiguous(), w[:, EMBED:].contiguous(),
+                           torch.cat([so.bias, aw.bias]).detach().contiguous())
+            self._pos_term = None
+        _, wa, wb, b = self._split
+        # keyed on the tensor's storage, not its Python identity: the model passes a fresh VIEW of the cached
+        # positional encoding every frame
+        pkey = (bev_pos.data_ptr(), bev_pos._version, tuple(bev_pos.shape), bev_pos.dtype)
+        if self._pos_term is None or self._pos_term[0] != pkey:
+            self._pos_term = (pkey, fn(bev_pos.reshape(-1, EMBED), wb, b, None, False))
+        return fn, wa, wb, self._pos_term[1]
+
+    def forward(self, query, value, bev_pos, ref_2d, spatial_shapes, rows=None, norm=None, prev_term=None):
         """`norm`: the block's LayerNorm behind this attention (evaluated in output_proj's epilogue when possible).
+        `prev_term`: the prev_bev half of the offsets | weights projection when the caller has evaluated it already
+        (_merged_prev_terms).
         `rows` = (lo, hi): query-range sharding (camera_shard.py, mode "scatter") -- `query`, `bev_pos` and `ref_2d`
         hold rows lo .. hi - 1 of the BEV queries only, `value` (the keys: prev_bev | query stack) is whole."""
         identity = query
         nq, nk = query.shape[1], value.shape[1]
         mine = value if rows is None else value[:, rows[0]:rows[1]]      # the value rows that pair with these queries
-        both = self._split_projection(query, mine[0], bev_pos)
+        both = self._split_projection(query, mine[0], bev_pos, prev_term if rows is None else None)
         split = getattr(self.ops, "tsa_split", None) if _TSA_GLUE["enabled"] else None
         pre = None
         if both is not None and split is not None and self.points == 4:
@@ -597,9 +609,18 @@ class SpatialCrossAttention(nn.Module):
         self.attention_weights = nn.Linear(EMBED, HEADS * levels * points)
         self.value_proj, self.output_proj = nn.Linear(EMBED, EMBED), nn.Linear(EMBED, EMBED)
 
+    def _offsets_weights(self, query, nq, merged):
+        """sampling_offsets(query), attention_weights(query) as [1, nq, heads, .]: both read the same query rows -- one
+        launch with two destinations when the merged route applies (`merged` and _merged_pair), else one launch each."""
+        pair = _merged_pair(self.ops, self, "_so_aw", self.sampling_offsets, self.attention_weights, query) if merged else None
+        if pair is None:
+            pair = (_dense(self.ops, self.sampling_offsets, query), _dense(self.ops, self.attention_weights, query))
+        return pair[0].view(1, nq, HEADS, -1), pair[1].view(1, nq, HEADS, -1)
+
     def forward(self, query, value, reference_points_cam, bev_mask, spatial_shapes, cams=None, gather=None, plan=None,
-                residual=None, norm=None):
-        """`plan`: the visibility plan (functions.spatial_cross_attention_plan) of the bev_mask rows of the cameras
+                residual=None, norm=None, merged=False):
+        """`merged`: the frame runs its merged launches (BEVFormer._transformer: _offsets_weights as one launch).
+        `plan`: the visibility plan (functions.spatial_cross_attention_plan) of the bev_mask rows of the cameras
         sampled here -- all of them, or this rank's -- or None.  `residual`: query-range sharding (exchange mode
         "scatter") -- `query` is the whole gathered tensor (every camera's sampler needs every query's offsets), the
         masked camera sum comes back reduce-SCATTERED to this rank's rows, and `residual` holds those rows of the
@@ -624,8 +645,7 @@ class SpatialCrossAttention(nn.Module):
         elif projected is not None and local_sum and _R3["enabled"] and self._proj_ok and fp16_gpu \
                 and not hasattr(self.value_proj, "fake_quant_reference"):
             # value_proj's GEMM writes the sampler's planes itself; the fused sampling reads them
-            off = _dense(self.ops, self.sampling_offsets, query).view(1, nq, HEADS, -1)
-            w = _dense(self.ops, self.attention_weights, query).view(1, nq, HEADS, -1)
+            off, w = self._offsets_weights(query, nq, merged)
             try:
                 slots = projected(value.reshape(ncam, nk, EMBED), self.value_proj.weight, self.value_proj.bias,
                                   spatial_shapes, ref_l.contiguous(), off, w, mask_l.contiguous(), HEADS,
@@ -637,8 +657,7 @@ class SpatialCrossAttention(nn.Module):
         if slots is None:
             value = _dense(self.ops, self.value_proj, value.reshape(ncam, nk, EMBED)).view(ncam, nk, HEADS, EMBED // HEADS)
             # the per-camera copies of `query` are identical: project once, expand (stride 0)
-            off = _dense(self.ops, self.sampling_offsets, query).view(1, nq, HEADS, -1).expand(ncam, -1, -1, -1)
-            w = _dense(self.ops, self.attention_weights, query).view(1, nq, HEADS, -1).expand(ncam, -1, -1, -1)
+            off, w = (t.expand(ncam, -1, -1, -1) for t in self._offsets_weights(query, nq, merged))
             msda = self.ops.multi_scale_deformable_attn
             if mode == "gather":
                 # camera-sharded, pipelined: camera i's all-gather overlaps the sampling of camera i + 1
@@ -672,7 +691,10 @@ class BEVFormerLayer(nn.Module):
         self.norms = nn.ModuleList(nn.LayerNorm(EMBED) for _ in range(3))
 
     def forward(self, query, value, bev_pos, ref_2d, ref_cam, bev_mask, spatial_shapes, bev_shapes, prev_bev,
-                use_prev_bev, cams, gather, plan=None, rows=None):
+                use_prev_bev, cams, gather, plan=None, rows=None, tsa_prev_term=None, merged=False):
+        """`tsa_prev_term`: the prev_bev half of this layer's offsets | weights projection [nq, 192], when the caller
+        evaluated it for all layers at once (_merged_prev_terms; only with host-known history, where TSA's keys are
+        `prev_bev` itself).  `merged`: the frame runs its merged launches (SCA's pair)."""
         ops = self.tsa.ops
         if rows is not None:
             # query-range sharding (camera_shard.py, mode "scatter"): `query` holds rows lo .. hi - 1 only.  TSA's
@@ -699,8 +721,11 @@ class BEVFormerLayer(nn.Module):
         else:
             prev = prev_bev if use_prev_bev else query.repeat(2, 1, 1)
         # (each block's LayerNorm rides in the epilogue of the block's last GEMM: _dense_norm)
-        query = self.tsa(query, prev, bev_pos, ref_2d, bev_shapes, norm=self.norms[0])
-        query = self.sca(query, value, ref_cam, bev_mask, spatial_shapes, cams, gather, plan, norm=self.norms[1])
+        if prev is not prev_bev:
+            tsa_prev_term = None
+        query = self.tsa(query, prev, bev_pos, ref_2d, bev_shapes, norm=self.norms[0], prev_term=tsa_prev_term)
+        query = self.sca(query, value, ref_cam, bev_mask, spatial_shapes, cams, gather, plan, norm=self.norms[1],
+                         merged=merged)
         return self.ffn(query, ops, norm=self.norms[2])
 
 
@@ -726,6 +751,122 @@ def _versions(*tensors):
     return tuple(t._version for t in tensors) + tuple(t.data_ptr() for t in tensors)
 
 
+# Launches that read the SAME rows with nothing but the weights changing, merged (design/dense.md): the six decoder layers'
+# value_proj of bev_embed as ONE grouped launch (ops.tsgemm_grouped), the six TSA layers' prev_bev @ Wa as ONE launch with
+# a destination and an identity per layer, SCA's sampling_offsets | attention_weights as ONE launch with two destinations
+# (ops.tile_gemm_dst), the decoder's pair likewise on the few-row kernel (ops.small_gemm_dst) -- each result bit for bit the
+# per-layer GEMM's.  (TSA's six value projections of the key stack
+# were merged too, measured and removed: the sampler then reads planes written long before, from HBM, and loses more
+# than the GEMM gains.)  BEVOPS_MERGED_PROJ=0 / _MERGED_PROJ["enabled"] = False: the per-layer launches (A/B).
+_MERGED_PROJ = {"enabled": os.environ.get("BEVOPS_MERGED_PROJ", "1") != "0"}
+
+
+def _merge_ok(ops, x, linears, has_res):
+    """The conditions every merged launch shares: the switches, fp16 rows on the GPU, plain fp16 nn.Linear layers with
+    a bias, and a per-layer route that runs on tile_gemm / tsgemm (functions.linear.own_kernel_choice) -- only then do
+    the merged and the per-layer route give the same bits."""
+    if not (_MERGED_PROJ["enabled"] and _R3["enabled"] and _FUSED_LINEAR["enabled"]) \
+            or getattr(ops, "dense_auto", None) is None or x.dtype != torch.float16 or not x.is_cuda \
+            or not all(type(l) is nn.Linear and l.bias is not None and l.weight.dtype == torch.float16 for l in linears):
+        return False
+    from .functions.linear import OWN_KERNELS
+    if not OWN_KERNELS["enabled"]:
+        return False
+    K = x.shape[-1]
+    return _per_layer_kernels(x.device, x.numel() // K, [l.weight.shape[0] for l in linears], K, not has_res, has_res) == "tiled"
+
+
+def _per_layer_kernels(device, M, widths, K, has_bias, has_res):
+    """Which family the per-layer GEMMs of these problems run on under the own-kernel dispatch: "tiled" (tile_gemm / the
+    weight-stationary tsgemm: the same bits, what tile_gemm_dst and tsgemm_grouped reproduce), "small" (the few-row kernel:
+    small_gemm_dst) or None (mixed, or tsgemm's original kernel -- K > 256, bevops_tsgemm_set_variant(1),
+    BEVOPS_TSGEMM_WS=0 -- which rotates its k start by block index: no merged launch has its bits)."""
+    from .functions.linear import own_kernel_choice, tsgemm_weight_stationary
+    if M <= 0:
+        return None
+    names = {own_kernel_choice(device, M, n, K, False, has_bias, has_res) for n in widths}
+    if names == {"small"}:
+        return "small"
+    if names <= {"tile", "tsgemm"} and ("tsgemm" not in names or tsgemm_weight_stationary(K)):
+        return "tiled"
+    return None
+
+
+def _merged_pair(ops, owner, cache, lin_a, lin_b, x):
+    """(lin_a(x), lin_b(x)) as ONE launch of the tiled GEMM with two destinations (ops.tile_gemm_dst; SCA's
+    sampling_offsets | attention_weights over the same 40 000 query rows), or None: the two per-layer launches."""
+    fn = getattr(ops, "tile_gemm_dst", None)
+    widths = [lin_a.weight.shape[0], lin_b.weight.shape[0]]
+    if fn is None or not _merge_ok(ops, x, (lin_a, lin_b), False) or any(n % 64 for n in widths):
+        return None
+    key = _versions(lin_a.weight, lin_b.weight, lin_a.bias, lin_b.bias)
+    hit = getattr(owner, cache, None)
+    if hit is None or hit[0] != key:
+        hit = (key, torch.cat([lin_a.weight, lin_b.weight]).detach().contiguous(),
+               torch.cat([lin_a.bias, lin_b.bias]).detach().contiguous())
+        setattr(owner, cache, hit)
+    try:
+        return fn(x.reshape(-1, x.shape[-1]), hit[1], hit[2], widths)
+    except _lib.BevopsError as exc:
+        if exc.status != _lib.NOT_SUPPORTED:
+            raise
+        return None
+
+
+def _merged_prev_terms(ops, owner, cache, tsas, query, prev0, bev_pos):
+    """[prev_bev @ Wa_l.T + (bev_pos @ Wb_l.T + b_l) for every TSA l] as ONE launch of the tiled GEMM with one
+    destination and one identity per layer (the first GEMM of TemporalSelfAttention._split_projection: the same
+    prev_bev rows against six different Wa), or None: every layer evaluates its own."""
+    fn = getattr(ops, "tile_gemm_dst", None)
+    if fn is None or not (_MERGED_PROJ["enabled"] and _R3["enabled"] and _FUSED_LINEAR["enabled"]) \
+            or prev0.dtype != torch.float16 or not prev0.is_cuda:
+        return None
+    from .functions.linear import OWN_KERNELS
+    if not OWN_KERNELS["enabled"]:
+        return None
+    try:
+        terms = [t._split_terms(query, bev_pos) for t in tsas]
+        if any(t is None for t in terms):
+            return None
+        widths = [t[1].shape[0] for t in terms]
+        M = prev0.numel() // EMBED
+        if any(n % 64 for n in widths) or _per_layer_kernels(prev0.device, M, widths, EMBED, False, True) != "tiled":
+            return None
+        key = tuple(t._split[0] for t in tsas)
+        hit = getattr(owner, cache, None)
+        if hit is None or hit[0] != key:
+            hit = (key, torch.cat([t[1] for t in terms]).contiguous())
+            setattr(owner, cache, hit)
+        return fn(prev0.reshape(-1, EMBED), hit[1], None, widths, [t[3] for t in terms])
+    except _lib.BevopsError as exc:
+        if exc.status != _lib.NOT_SUPPORTED:
+            raise
+        return None
+
+
+def _merged_value_proj(ops, owner, cache, linears, x):
+    """[lin(x) for lin in linears] as one launch -> [G, M, 256], or None (then every layer projects for itself): plain
+    fp16 nn.Linear 256 -> 256 layers on the GPU, an operator set with the grouped entry, and the per-layer path on the
+    hand-written kernels too (OWN_KERNELS: only then do the two routes give the same bits).  The stacked weights are
+    cached on `owner` under `cache`, keyed on the parameters' versions and storage."""
+    fn = getattr(ops, "tsgemm_grouped", None)
+    if fn is None or not _merge_ok(ops, x, linears, False) \
+            or not all(tuple(l.weight.shape) == (EMBED, EMBED) for l in linears):
+        return None
+    key = _versions(*[l.weight for l in linears], *[l.bias for l in linears])
+    hit = getattr(owner, cache, None)
+    if hit is None or hit[0] != key:
+        hit = (key, torch.cat([l.weight for l in linears]).detach().contiguous(),
+               torch.cat([l.bias for l in linears]).detach().contiguous())
+        setattr(owner, cache, hit)
+    try:
+        return fn(x.reshape(-1, EMBED), hit[1], hit[2])
+    except _lib.BevopsError as exc:
+        if exc.status != _lib.NOT_SUPPORTED:
+            raise
+        return None
+
+
 class CustomMSDeformableAttention(nn.Module):
     """decoder.py:381-471 (1 level, 4 points)."""
 
@@ -735,13 +876,40 @@ class CustomMSDeformableAttention(nn.Module):
         self.sampling_offsets = nn.Linear(EMBED, HEADS * points * 2)
         self.attention_weights = nn.Linear(EMBED, HEADS * points)
         self.value_proj, self.output_proj = nn.Linear(EMBED, EMBED), nn.Linear(EMBED, EMBED)
-        self._pos_so = self._pos_aw = None
+        self._pos_so = self._pos_aw = self._so_aw = None
 
-    def forward(self, query, value, query_pos, reference_points, spatial_shapes, norm=None):
+    def _merged_offsets_weights(self, q2, t_so, t_aw):
+        """sampling_offsets | attention_weights of the query rows `q2` [n, 256] with their cached query_pos terms as
+        identities, as ONE launch of the few-row GEMM with two destinations (ops.small_gemm_dst) -- where the two
+        per-layer launches run on that kernel; None: one launch each."""
+        ops, so, aw = self.ops, self.sampling_offsets, self.attention_weights
+        fn = getattr(ops, "small_gemm_dst", None)
+        widths = [so.weight.shape[0], aw.weight.shape[0]]
+        from .functions.linear import OWN_KERNELS
+        if fn is None or not _MERGED_PROJ["enabled"] or not OWN_KERNELS["enabled"] or widths[0] % 64 or widths[1] % 8 \
+                or so.weight.dtype != torch.float16 or aw.weight.dtype != torch.float16 \
+                or _per_layer_kernels(q2.device, q2.shape[0], widths, EMBED, False, True) != "small":
+            return None
+        key = _versions(so.weight, aw.weight)
+        if self._so_aw is None or self._so_aw[0] != key:
+            self._so_aw = (key, torch.cat([so.weight, aw.weight]).detach().contiguous())
+        try:
+            return fn(q2, self._so_aw[1], None, widths, [t_so, t_aw])
+        except _lib.BevopsError as exc:
+            if exc.status != _lib.NOT_SUPPORTED:
+                raise
+            return None
+
+    def forward(self, query, value, query_pos, reference_points, spatial_shapes, norm=None, projected=None, merged=False):
+        """`projected`: value_proj(value) [nk, 256] when the caller has evaluated it already (_merged_value_proj);
+        `merged`: the frame runs its merged launches (_merged_offsets_weights)."""
         identity = query                               # [900, 1, 256]
         ops, so, aw = self.ops, self.sampling_offsets, self.attention_weights
         n = query.shape[0]
-        value = _dense(ops, self.value_proj, value.view(1, -1, EMBED)).view(1, -1, HEADS, EMBED // HEADS)
+        if projected is not None:
+            value = projected.view(1, -1, HEADS, EMBED // HEADS)
+        else:
+            value = _dense(ops, self.value_proj, value.view(1, -1, EMBED)).view(1, -1, HEADS, EMBED // HEADS)
         off = w = None
         if _fast_dense_ok(ops, query, so, aw):
             # lin(query + query_pos) with the query_pos term frame-independent: no add, bias folded
@@ -749,8 +917,12 @@ class CustomMSDeformableAttention(nn.Module):
             try:
                 t_so = _static_term("_pos_so", self, _versions(so.weight, so.bias), query_pos, fn, so.weight, so.bias)
                 t_aw = _static_term("_pos_aw", self, _versions(aw.weight, aw.bias), query_pos, fn, aw.weight, aw.bias)
-                off = fn(query.view(n, EMBED), so.weight, None, t_so, False).view(1, n, HEADS, -1)
-                w = fn(query.view(n, EMBED), aw.weight, None, t_aw, False).view(1, n, HEADS, -1)
+                pair = self._merged_offsets_weights(query.view(n, EMBED), t_so, t_aw) if merged else None
+                if pair is not None:      # both read the same 900 query rows: one launch, two destinations
+                    off, w = pair[0].view(1, n, HEADS, -1), pair[1].view(1, n, HEADS, -1)
+                else:
+                    off = fn(query.view(n, EMBED), so.weight, None, t_so, False).view(1, n, HEADS, -1)
+                    w = fn(query.view(n, EMBED), aw.weight, None, t_aw, False).view(1, n, HEADS, -1)
             except _lib.BevopsError as exc:
                 if exc.status != _lib.NOT_SUPPORTED:
                     raise
@@ -812,13 +984,14 @@ class DecoderLayer(nn.Module):
             o = o.transpose(1, 2).reshape(n, 1, EMBED)
         return _dense(ops, mha.out_proj, o, query, False) if norm is None else _dense_norm(ops, mha.out_proj, o, query, norm)
 
-    def forward(self, query, value, query_pos, reference_points, spatial_shapes):
+    def forward(self, query, value, query_pos, reference_points, spatial_shapes, projected=None, merged=False):
         ops = self.cross_attn.ops
         query_n = self._self_attention(ops, query, query_pos, norm=self.norms[0])
         if query_n is None:
             qk = query + query_pos
             query_n = _layer_norm(ops, self.norms[0], query + self.self_attn(qk, qk, query, need_weights=False)[0])
-        query = self.cross_attn(query_n, value, query_pos, reference_points, spatial_shapes, norm=self.norms[1])
+        query = self.cross_attn(query_n, value, query_pos, reference_points, spatial_shapes, norm=self.norms[1],
+                                projected=projected, merged=merged)
         return self.ffn(query, ops, norm=self.norms[2])
 
 
@@ -1028,9 +1201,17 @@ class BEVFormer(nn.Module):
             lo, hi, _ = gather.query_range(nq)
             rows = (lo, hi)
             q = q[:, lo:hi].contiguous()
-        for layer in self.encoder:
+        # The merged launches (_MERGED_PROJ) run on frames with host-known history on one device; every other frame --
+        # the first of a scene, the device-side flag, the sharded runners -- keeps one launch per layer.
+        merged = gather is None and not torch.is_tensor(use_prev_bev) and bool(use_prev_bev)
+        tsa_terms = None
+        if merged:     # every layer's TSA multiplies the same prev_bev rows by its own Wa: one launch in front of the loop
+            tsa_terms = _merged_prev_terms(self.ops, self, "_tsa_wacat", [l.tsa for l in self.encoder], q, prev[0], pos)
+        for li, layer in enumerate(self.encoder):
             q = layer(q, feat_flatten, pos, hybrid, ref_cam, bev_mask, spatial_shapes, bev_shapes, prev,
-                      use_prev_bev, cams, gather, plan, rows)
+                      use_prev_bev, cams, gather, plan, rows, None if tsa_terms is None else tsa_terms[li], merged)
+            if tsa_terms is not None:
+                tsa_terms[li] = None      # (92 MB in all: each term is released behind its layer)
         if rows is not None:
             q = gather.all_gather_queries(q, nq)              # the decoder (900 object queries) is replicated
         bev_embed = q.view(nq, 1, EMBED)
@@ -1054,8 +1235,11 @@ class BEVFormer(nn.Module):
         fused_refine = getattr(self.ops, "refine_reference_points", None) if _FUSED_REFINE["enabled"] and _R3["enabled"] \
             and dtype == torch.float16 and dev.type == "cuda" else None
         ref_xy = reference_points[..., :2].unsqueeze(2).contiguous()
+        # all six layers project the same bev_embed: one grouped launch in front of the loop
+        dec_values = _merged_value_proj(self.ops, self, "_dec_vcat", [l.cross_attn.value_proj for l in self.decoder],
+                                        bev_embed) if merged else None
         for lid, layer in enumerate(self.decoder):
-            out = layer(out, bev_embed, query_pos, ref_xy, bev_shapes)
+            out = layer(out, bev_embed, query_pos, ref_xy, bev_shapes, None if dec_values is None else dec_values[lid], merged)
             tmp = _mlp(self.ops, self.reg_branches[lid], out).view(1, -1, 10)
             if fused_refine is not None:
                 reference_points, ref_xy = fused_refine(tmp, reference_points)

@@ -85,6 +85,7 @@ const Entry kTable[] = {
     {"bevops_tsgemm_s8_ln", (void *)&bevops_tsgemm_s8_ln},
     {"bevops_tsgemm_tile_rows", (void *)&bevops_tsgemm_tile_rows},
     {"bevops_tsgemm_f16_ln", (void *)&bevops_tsgemm_f16_ln},
+    {"bevops_tsgemm_f16_grouped", (void *)&bevops_tsgemm_f16_grouped},
     {"bevops_mha_selfattn_f16", (void *)&bevops_mha_selfattn_f16},
     {"bevops_mha_selfattn_max_queries", (void *)&bevops_mha_selfattn_max_queries},
     {"bevops_value_proj_packed_size", (void *)&bevops_value_proj_packed_size},
@@ -104,6 +105,8 @@ const Entry kTable[] = {
     {"bevops_linear_int8", (void *)&bevops_linear_int8},
     {"bevops_linear_int8_fused", (void *)&bevops_linear_int8_fused},
     {"bevops_tile_gemm_f16", (void *)&bevops_tile_gemm_f16},
+    {"bevops_tile_gemm_f16_dst", (void *)&bevops_tile_gemm_f16_dst},
+    {"bevops_small_gemm_f16_dst", (void *)&bevops_small_gemm_f16_dst},
     {"bevops_small_gemm_f16", (void *)&bevops_small_gemm_f16},
     {"bevops_conv_tile_f16", (void *)&bevops_conv_tile_f16},
     {"bevops_conv3x3_c64_f16", (void *)&bevops_conv3x3_c64_f16},

@@ -30,9 +30,18 @@ struct SmallArgs {
   int M, N, K, relu;
 };
 
+// DST (bevops_small_gemm_f16_dst): the output columns go to up to kSgMaxDst destinations, each a column range of the
+// launch written as a pitched matrix of its own with an identity of its own -- layers that read the same rows as ONE
+// launch.  A range begins on a multiple of 64, so a block's 64 columns have one destination, found by compare-and-select
+// over the by-value table with the block's n0 (scalar); columns of the block past the range's end are not stored.
+// Everything in front of the identity add is the code of the plain launch.
+constexpr int kSgMaxDst = 8;
+struct SmallDst { int col_begin, col_end; __half *out; const __half *res; int out_pitch, res_pitch; };
+struct SmallDstTab { int count; SmallDst e[kSgMaxDst]; };
+
 // STEPS = k-steps (of 16 values) per wave = K / 64
-template <int STEPS>
-__global__ __launch_bounds__(256) void small_gemm_f16_kernel(SmallArgs p) {
+template <int STEPS, bool DST>
+__device__ __forceinline__ void small_gemm_body(const SmallArgs &p, const SmallDstTab &d) {
   __shared__ __attribute__((aligned(16))) float part[4][kSgM][kSgStride];   // 34.8 KB
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tiles_n = (p.N + kSgN - 1) / kSgN;
@@ -59,9 +68,27 @@ __global__ __launch_bounds__(256) void small_gemm_f16_kernel(SmallArgs p) {
   const int er = tid >> 3, ec = (tid & 7) * 8;       // epilogue role: row er, columns ec .. ec + 7 of the tile
   const int em = m0 + er, en = n0 + ec;
   const bool vec = (p.N & 7) == 0;
+  // DST: this block's destination (block-uniform); d_out stays null for a block outside every range
+  __half *d_out = nullptr;
+  const __half *d_res = nullptr;
+  int d_c0 = 0, d_c1 = 0, d_op = 0, d_rp = 0;
+  if constexpr (DST) {
+#pragma unroll
+    for (int e = 0; e < kSgMaxDst; ++e) {
+      const bool hit = e < d.count && n0 >= d.e[e].col_begin && n0 < d.e[e].col_end;
+      d_out = hit ? d.e[e].out : d_out;
+      d_res = hit ? d.e[e].res : d_res;
+      d_c0 = hit ? d.e[e].col_begin : d_c0;
+      d_c1 = hit ? d.e[e].col_end : d_c1;
+      d_op = hit ? d.e[e].out_pitch : d_op;
+      d_rp = hit ? d.e[e].res_pitch : d_rp;
+    }
+  }
+  const bool dst_ok = !DST || (d_out != nullptr && en < d_c1);   // (range ends are multiples of 8: a chunk is all in or all out)
+  const __half *res = DST ? d_res : p.res;
   uint4 rres = make_uint4(0u, 0u, 0u, 0u);
-  if (p.res && vec && em < p.M && en < p.N)
-    rres = *reinterpret_cast<const uint4 *>(p.res + (size_t)em * p.N + en);
+  if (res && vec && em < p.M && en < p.N && dst_ok)
+    rres = *reinterpret_cast<const uint4 *>(DST ? res + (size_t)em * d_rp + (en - d_c0) : res + (size_t)em * p.N + en);
   f32x16_t acc0, acc1;
 #pragma unroll
   for (int i = 0; i < 16; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; }
@@ -82,7 +109,7 @@ __global__ __launch_bounds__(256) void small_gemm_f16_kernel(SmallArgs p) {
         f32x4{acc1[4 * g], acc1[4 * g + 1], acc1[4 * g + 2], acc1[4 * g + 3]};
   }
   __syncthreads();
-  if (em >= p.M || en >= p.N) return;
+  if (em >= p.M || en >= p.N || !dst_ok) return;
   float v[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c) v[c] = 0.f;
@@ -96,21 +123,21 @@ __global__ __launch_bounds__(256) void small_gemm_f16_kernel(SmallArgs p) {
 #pragma unroll
   for (int c = 0; c < 8; ++c)
     if (p.bias && en + c < p.N) v[c] += __half2float(p.bias[en + c]);
-  if (p.res) {
+  if (res) {
     if (vec) {
       v[0] += h2f_lo(rres.x); v[1] += h2f_hi(rres.x); v[2] += h2f_lo(rres.y); v[3] += h2f_hi(rres.y);
       v[4] += h2f_lo(rres.z); v[5] += h2f_hi(rres.z); v[6] += h2f_lo(rres.w); v[7] += h2f_hi(rres.w);
     } else {
 #pragma unroll
       for (int c = 0; c < 8; ++c)
-        if (en + c < p.N) v[c] += __half2float(p.res[(size_t)em * p.N + en + c]);
+        if (en + c < p.N) v[c] += __half2float(res[(size_t)em * p.N + en + c]);   // (never with DST: N % 8 == 0 there)
     }
   }
   if (p.relu) {
 #pragma unroll
     for (int c = 0; c < 8; ++c) v[c] = fmaxf(v[c], 0.f);
   }
-  __half *o = p.out + (size_t)em * p.N + en;
+  __half *o = DST ? d_out + (size_t)em * d_op + (en - d_c0) : p.out + (size_t)em * p.N + en;
   if (vec) {
     uint4 q;
     q.x = pack_h2(v[0], v[1]); q.y = pack_h2(v[2], v[3]); q.z = pack_h2(v[4], v[5]); q.w = pack_h2(v[6], v[7]);
@@ -120,6 +147,16 @@ __global__ __launch_bounds__(256) void small_gemm_f16_kernel(SmallArgs p) {
     for (int c = 0; c < 8; ++c)
       if (en + c < p.N) o[c] = __float2half_rn(v[c]);
   }
+}
+
+template <int STEPS>
+__global__ __launch_bounds__(256) void small_gemm_f16_kernel(SmallArgs p) {
+  small_gemm_body<STEPS, false>(p, SmallDstTab{});
+}
+
+template <int STEPS>
+__global__ __launch_bounds__(256) void small_gemm_dst_kernel(SmallArgs p, SmallDstTab d) {
+  small_gemm_body<STEPS, true>(p, d);
 }
 
 }  // namespace
@@ -143,6 +180,48 @@ extern "C" int bevops_small_gemm_f16(const void *x, const void *weight, const vo
   const dim3 grid((unsigned)blocks), blk(256);
   switch (K / 64) {
 #define BEVOPS_SG(S_) case S_: hipLaunchKernelGGL(small_gemm_f16_kernel<S_>, grid, blk, 0, st, p); break
+    BEVOPS_SG(1); BEVOPS_SG(2); BEVOPS_SG(3); BEVOPS_SG(4); BEVOPS_SG(5); BEVOPS_SG(6); BEVOPS_SG(7); BEVOPS_SG(8);
+    BEVOPS_SG(9); BEVOPS_SG(10); BEVOPS_SG(11); BEVOPS_SG(12); BEVOPS_SG(13); BEVOPS_SG(14); BEVOPS_SG(15); BEVOPS_SG(16);
+#undef BEVOPS_SG
+    default: return BEVOPS_NOT_SUPPORTED;
+  }
+  return launch_status();
+}
+
+// bevops_small_gemm_f16 with a destination table (the decoder's sampling_offsets | attention_weights over the same 900
+// queries: N = 64 + 32, the two cached query_pos terms as identities): range [col_begin, col_end) of x @ weight.T + bias
+// goes to the pitched matrix of its destination, plus that destination's identity rows.  Exactly the bytes of the separate
+// launches on weight[col_begin:col_end]; columns outside every range and the bytes between pitched rows are never written.
+extern "C" int bevops_small_gemm_f16_dst(const void *x, const void *weight, const void *bias, const bevops_gemm_dst *dst,
+                                         int num_dst, long long M, int N, int K, int relu, void *stream) {
+  if (!x || !weight || !dst || M < 0 || N <= 0 || K <= 0 || num_dst <= 0) return BEVOPS_BAD_PARAM;
+  if (num_dst > kSgMaxDst || N % 8 != 0) return BEVOPS_NOT_SUPPORTED;
+  if (K % 64 != 0 || K > 1024 || M > 65536 || !aligned16(x) || !aligned16(weight) || (bias && !aligned16(bias)))
+    return BEVOPS_NOT_SUPPORTED;
+  if ((unsigned long long)M * K * 2 >= kSgOob || (unsigned long long)N * K * 2 >= kSgOob) return BEVOPS_NOT_SUPPORTED;
+  SmallDstTab tab{};
+  tab.count = num_dst;
+  for (int i = 0; i < num_dst; ++i) {
+    const bevops_gemm_dst &e = dst[i];
+    const long long width = (long long)e.col_end - e.col_begin;
+    // a range begins on the 64-column block grid and ends on it or on a multiple of 8 (then nothing else may begin in that block: begins are multiples of 64)
+    if (e.col_begin < 0 || e.col_end > N || width <= 0 || e.col_begin % 64 != 0 || e.col_end % 8 != 0) return BEVOPS_BAD_PARAM;
+    if (!e.out || !aligned16(e.out) || e.out_pitch < width || e.out_pitch % 8 != 0 || e.out_pitch > 0x7fffffffLL) return BEVOPS_BAD_PARAM;
+    if (e.res && (!aligned16(e.res) || e.res_pitch < width || e.res_pitch % 8 != 0 || e.res_pitch > 0x7fffffffLL)) return BEVOPS_BAD_PARAM;
+    for (int j = 0; j < i; ++j)   // overlapping ranges, or two ranges inside one 64-column block
+      if (e.col_begin < (dst[j].col_end + 63) / 64 * 64 && dst[j].col_begin < (e.col_end + 63) / 64 * 64) return BEVOPS_BAD_PARAM;
+    tab.e[i] = SmallDst{e.col_begin, e.col_end, static_cast<__half *>(e.out), static_cast<const __half *>(e.res),
+                        (int)e.out_pitch, e.res ? (int)e.res_pitch : 0};
+  }
+  if (M == 0) return BEVOPS_SUCCESS;
+  SmallArgs p{static_cast<const __half *>(x), static_cast<const __half *>(weight), static_cast<const __half *>(bias), nullptr,
+              nullptr, (int)M, N, K, relu};
+  const long long blocks = ((M + kSgM - 1) / kSgM) * ((N + kSgN - 1) / kSgN);
+  if (blocks > 0x7fffffffLL) return BEVOPS_NOT_SUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)blocks), blk(256);
+  switch (K / 64) {
+#define BEVOPS_SG(S_) case S_: hipLaunchKernelGGL(small_gemm_dst_kernel<S_>, grid, blk, 0, st, p, tab); break
     BEVOPS_SG(1); BEVOPS_SG(2); BEVOPS_SG(3); BEVOPS_SG(4); BEVOPS_SG(5); BEVOPS_SG(6); BEVOPS_SG(7); BEVOPS_SG(8);
     BEVOPS_SG(9); BEVOPS_SG(10); BEVOPS_SG(11); BEVOPS_SG(12); BEVOPS_SG(13); BEVOPS_SG(14); BEVOPS_SG(15); BEVOPS_SG(16);
 #undef BEVOPS_SG

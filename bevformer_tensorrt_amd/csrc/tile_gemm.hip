@@ -100,8 +100,18 @@ struct TileArgs {
 constexpr int tile_lds_bytes(int tm) {
   return 2 * (tm + 128) * (64 + 16) > 4 * 32 * kEpiStride ? 2 * (tm + 128) * (64 + 16) : 4 * 32 * kEpiStride;
 }
-template <int MODE, bool OUT8, int NI, bool CONV, bool RES8 = false>
-__global__ __launch_bounds__(256, 3) void tile_gemm_kernel(TileArgs p) {
+// DST (bevops_tile_gemm_f16_dst; F16, NI == 2): the output columns go to up to kMaxDst destinations, each a column range
+// [col_begin, col_end) of the launch written as a pitched matrix of its own with an identity of its own -- several layers
+// that read the same rows as ONE launch.  Range bounds are multiples of 64, so the 32-row x 64-column block a wave's
+// epilogue works on has exactly one destination; it is chosen by scalar compare-and-select over the by-value table (an
+// indexed load would be a vector load behind the k-loop's requests).  Everything in front of the stores is the code of
+// the plain launch: an element's sum, bias, identity and rounding do not depend on where it is stored.
+constexpr int kMaxDst = 8;
+struct TileDst { int col_begin, col_end; __half *out; const __half *res; int out_pitch, res_pitch; };
+struct TileDstTab { int count; TileDst e[kMaxDst]; };
+
+template <int MODE, bool OUT8, int NI, bool CONV, bool RES8, bool DST>
+__device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const TileDstTab &d) {
   constexpr int MJ = 2;                          // 32-row MFMA blocks per wave
   constexpr int KB = 64;                         // bytes of k per row and step
   constexpr int kTN = 64 * NI;
@@ -224,18 +234,37 @@ __global__ __launch_bounds__(256, 3) void tile_gemm_kernel(TileArgs p) {
   constexpr int kIT = kCH / 2;                   // read-back passes over the wave's 32 staged rows (64 / kCH rows each)
   const int c8 = lane & (kCH - 1);               // this lane's 8-column chunk
   const int ncol = n0 + wn * 32 * NI + c8 * 8;
-  const bool col_ok = ncol < N;
+  // DST: this wave's destination (wave-uniform: scalar registers); d_out stays null for a block outside every range
+  __half *d_out = nullptr;
+  const __half *d_res = nullptr;
+  int d_c0 = 0, d_c1 = 0, d_op = 0, d_rp = 0;
+  if constexpr (DST) {
+    const int cb = __builtin_amdgcn_readfirstlane(n0 + wn * 32 * NI);
+#pragma unroll
+    for (int e = 0; e < kMaxDst; ++e) {
+      const bool hit = e < d.count && cb >= d.e[e].col_begin && cb < d.e[e].col_end;
+      d_out = hit ? d.e[e].out : d_out;
+      d_res = hit ? d.e[e].res : d_res;
+      d_c0 = hit ? d.e[e].col_begin : d_c0;
+      d_c1 = hit ? d.e[e].col_end : d_c1;
+      d_op = hit ? d.e[e].out_pitch : d_op;
+      d_rp = hit ? d.e[e].res_pitch : d_rp;
+    }
+  }
+  const bool col_ok = DST ? (d_out != nullptr && ncol < N) : ncol < N;
   const bool vec = (N & 7) == 0;                 // rows 16-byte aligned and the chunk all in or all out; else per element
-  const __half *res = static_cast<const __half *>(p.res);
+  const __half *res = DST ? d_res : static_cast<const __half *>(p.res);
   constexpr int kRB = RES8 ? 1 : 2;              // bytes per identity element
   const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<__half *>(res), 0, res ? (unsigned)((size_t)M * N * kRB) : 0u, 0x00020000);
+      const_cast<__half *>(res), 0,
+      res ? (DST ? (unsigned)(((size_t)(M - 1) * d_rp + (d_c1 - d_c0)) * kRB) : (unsigned)((size_t)M * N * kRB)) : 0u, 0x00020000);
   uint4 rres[MJ][kIT];
   auto res_request = [&](int j) {
 #pragma unroll
     for (int it = 0; it < kIT; ++it) {
       const int m = m0 + wm * 32 * MJ + j * 32 + it * (64 / kCH) + lane / kCH;
-      const unsigned off = (m < M && col_ok) ? (unsigned)(((size_t)m * N + ncol) * kRB) : kOob;
+      const unsigned off = (m < M && col_ok) ? (DST ? (unsigned)(((size_t)m * d_rp + (ncol - d_c0)) * kRB)
+                                                    : (unsigned)(((size_t)m * N + ncol) * kRB)) : kOob;
       if constexpr (RES8) {   // 8 identity bytes of this lane's 8 columns
         const uint2 q = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rs_r, (int)off, 0, 0));
         rres[j][it] = make_uint4(q.x, q.y, 0u, 0u);
@@ -388,7 +417,7 @@ __global__ __launch_bounds__(256, 3) void tile_gemm_kernel(TileArgs p) {
             if (ncol + c < N) o8[c] = (int8_t)((pk[c >> 2] >> (8 * (c & 3))) & 0xffu);
         }
       } else {
-        __half *oh = static_cast<__half *>(p.out) + (size_t)m * N + ncol;
+        __half *oh = DST ? d_out + (size_t)m * d_op + (ncol - d_c0) : static_cast<__half *>(p.out) + (size_t)m * N + ncol;
         if (vec) {
           uint4 o;
           o.x = pack_h2(v[0], v[1]); o.y = pack_h2(v[2], v[3]); o.z = pack_h2(v[4], v[5]); o.w = pack_h2(v[6], v[7]);
@@ -403,6 +432,15 @@ __global__ __launch_bounds__(256, 3) void tile_gemm_kernel(TileArgs p) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
+}
+
+template <int MODE, bool OUT8, int NI, bool CONV, bool RES8 = false>
+__global__ __launch_bounds__(256, 3) void tile_gemm_kernel(TileArgs p) {
+  tile_gemm_body<MODE, OUT8, NI, CONV, RES8, false>(p, TileDstTab{});
+}
+
+__global__ __launch_bounds__(256, 3) void tile_gemm_dst_kernel(TileArgs p, TileDstTab d) {
+  tile_gemm_body<kF16, false, 2, false, false, true>(p, d);
 }
 
 struct ConvGeom { int cin = 0, hin = 0, win = 0, hout = 0, wout = 0, stride = 1, ks = 1; size_t in_elems = 0; };
@@ -503,6 +541,45 @@ extern "C" int bevops_linear_int8_fused(const void *x_f16, float scale_a, const 
 extern "C" int bevops_tile_gemm_f16(const void *x, const void *weight, const void *bias, const void *residual,
                                     void *out, long long M, int N, int K, int relu, void *stream) {
   return launch_tile_gemm<kF16>(x, 1.f, weight, nullptr, 1.f, bias, residual, BEVOPS_F16, out, 1.f, M, N, K, relu, stream);
+}
+
+// bevops_tile_gemm_f16 with a destination table: column range [col_begin, col_end) of x @ weight.T + bias goes to the
+// pitched matrix `out` of its destination (column col_begin at out[m * out_pitch]), plus that destination's identity
+// rows (read with res_pitch).  Exactly the bytes the separate launches on weight[col_begin:col_end] write; columns
+// outside every range and the bytes between pitched rows are never written.
+extern "C" int bevops_tile_gemm_f16_dst(const void *x, const void *weight, const void *bias, const bevops_gemm_dst *dst,
+                                        int num_dst, long long M, int N, int K, int relu, void *stream) {
+  if (!x || !weight || !dst || M < 0 || N <= 0 || K <= 0 || num_dst <= 0) return BEVOPS_BAD_PARAM;
+  if (num_dst > kMaxDst || N <= 64 || N % 8 != 0) return BEVOPS_NOT_SUPPORTED;   // (N <= 64 is the 64-column flavour's)
+  if (K % 8 != 0 || !aligned16(x) || !aligned16(weight) || (bias && !aligned16(bias)) || M > 0x7fffffffLL) return BEVOPS_NOT_SUPPORTED;
+  if ((unsigned long long)M * K * 2 >= kOob || (unsigned long long)N * K * 2 >= kOob) return BEVOPS_NOT_SUPPORTED;
+  TileDstTab tab{};
+  tab.count = num_dst;
+  for (int i = 0; i < num_dst; ++i) {
+    const bevops_gemm_dst &e = dst[i];
+    const long long width = (long long)e.col_end - e.col_begin;
+    if (e.col_begin < 0 || e.col_end > N || width <= 0 || e.col_begin % 64 != 0 || e.col_end % 64 != 0) return BEVOPS_BAD_PARAM;
+    if (!e.out || !aligned16(e.out) || e.out_pitch < width || e.out_pitch % 8 != 0 || e.out_pitch > 0x7fffffffLL) return BEVOPS_BAD_PARAM;
+    if (e.res && (!aligned16(e.res) || e.res_pitch < width || e.res_pitch % 8 != 0 || e.res_pitch > 0x7fffffffLL)) return BEVOPS_BAD_PARAM;
+    if (e.res && (unsigned long long)M * (unsigned long long)e.res_pitch * 2 >= kOob) return BEVOPS_NOT_SUPPORTED;
+    for (int j = 0; j < i; ++j)
+      if (e.col_begin < dst[j].col_end && dst[j].col_begin < e.col_end) return BEVOPS_BAD_PARAM;   // overlapping ranges
+    tab.e[i] = TileDst{e.col_begin, e.col_end, static_cast<__half *>(e.out), static_cast<const __half *>(e.res),
+                       (int)e.out_pitch, e.res ? (int)e.res_pitch : 0};
+  }
+  if (M == 0) return BEVOPS_SUCCESS;
+  TileArgs p{};
+  p.a = x; p.w = weight; p.bias = bias;
+  p.inv_sa = 1.f; p.s_aw = 1.f; p.s_res = 1.f;
+  p.M = (int)M; p.N = N; p.K = K; p.relu = relu;
+  p.a_bytes = (unsigned)((unsigned long long)M * K * 2);
+  p.conv_s = 1; p.conv_ks = 1;
+  p.tiles_n = (N + 127) / 128;
+  const long long tiles = (long long)p.tiles_n * ((M + kTM - 1) / kTM);
+  if (tiles > 0x3fffffffLL) return BEVOPS_NOT_SUPPORTED;
+  p.tiles_total = (int)tiles;
+  hipLaunchKernelGGL(tile_gemm_dst_kernel, dim3((unsigned)((tiles + 7) / 8 * 8)), dim3(256), 0, static_cast<hipStream_t>(stream), p, tab);
+  return launch_status();
 }
 
 static int conv_geometry(ConvGeom &cg, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int step_k) {

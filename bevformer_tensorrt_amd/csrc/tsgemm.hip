@@ -50,6 +50,7 @@ struct TsPacked {   // EPI == 1: destination of the encoder's value projection
   Hm3Tab t;
   int nk, heads;    // rows per camera, heads (N == heads * 32)
   float eps;        // EPI == 2
+  long long gstride;   // grouped EPI 0 (tsgemm_ws_grouped_kernel<KS>): elements between the outputs of two column chunks
 };
 
 // sum over the 16 lanes of a DPP row (= the 16 threads that share an output row in the epilogue), in every lane
@@ -567,6 +568,8 @@ __global__ __launch_bounds__(256) void tsgemm_pad_zero_kernel(TsPacked pk, int p
 //     same XCD (block b runs on XCD b % 8) and walk the same rows at the same time, so the re-read comes from L2.
 // Summation order: k ascending in every block, the same matrix instruction, operand layout, fp32 epilogue and single
 // rounding as above -- an output row depends on its own operands only, not on the block index, M or the CU count.
+// GRP (EPI 0, bevops_tsgemm_f16_grouped): column chunk g is a dense [M, 256] matrix of its own at out + g * pk.gstride --
+// G layers that read the same rows as ONE launch; only the store address differs from the N = G * 256 launch.
 constexpr int kWsG = 2;                          // row units per tile (the staging writes below are written for 2)
 constexpr int kWsRows = kWsG * 32;
 constexpr int kWsBufs = 3;
@@ -574,12 +577,11 @@ constexpr int kWsStep = kWsRows * 128;           // one 64-k sub-image of a tile
 constexpr int kWsEpi = kWsRows * kTsEpiStride;   // fp32 staging of a 128-column half (33 KB), at the start of LDS
 constexpr int ws_lds(int ks) { return kWsEpi + kWsBufs * ks * kWsStep; }   // 129 KB at K = 256
 
-template <int EPI, int KS>
-__global__ __launch_bounds__(kTsThreads) void tsgemm_ws_kernel(const __half *__restrict__ x, const __half *__restrict__ w,
-                                                               const __half *__restrict__ bias,
-                                                               const __half *__restrict__ res, __half *__restrict__ out,
-                                                               int M, int N, int relu, int units_total, int parts,
-                                                               int chunks, TsPacked pk) {
+template <int EPI, int KS, bool GRP>
+__device__ __forceinline__ void tsgemm_ws_body(const __half *__restrict__ x, const __half *__restrict__ w,
+                                               const __half *__restrict__ bias, const __half *__restrict__ res,
+                                               __half *__restrict__ out, int M, int N, int relu, int units_total, int parts,
+                                               int chunks, const TsPacked &pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int K = KS * 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -768,7 +770,10 @@ __global__ __launch_bounds__(kTsThreads) void tsgemm_ws_kernel(const __half *__r
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
               }
-              *reinterpret_cast<uint4 *>(out + m * N + col) = ts_pack8(v);
+              if constexpr (GRP)
+                *reinterpret_cast<uint4 *>(out + (size_t)chunk * (size_t)pk.gstride + m * kTsBN + (col - n0)) = ts_pack8(v);
+              else
+                *reinterpret_cast<uint4 *>(out + m * N + col) = ts_pack8(v);
             }
           }
         }
@@ -794,6 +799,23 @@ __global__ __launch_bounds__(kTsThreads) void tsgemm_ws_kernel(const __half *__r
     stores_prev = __builtin_amdgcn_readfirstlane(2 * ((wave * 4 < rows ? 1 : 0) + (wave * 4 + 32 < rows ? 1 : 0)));
     if (++buf == kWsBufs) buf = 0;
   }
+}
+
+template <int EPI, int KS>
+__global__ __launch_bounds__(kTsThreads) void tsgemm_ws_kernel(const __half *__restrict__ x, const __half *__restrict__ w,
+                                                               const __half *__restrict__ bias,
+                                                               const __half *__restrict__ res, __half *__restrict__ out,
+                                                               int M, int N, int relu, int units_total, int parts,
+                                                               int chunks, TsPacked pk) {
+  tsgemm_ws_body<EPI, KS, false>(x, w, bias, res, out, M, N, relu, units_total, parts, chunks, pk);
+}
+
+template <int KS>
+__global__ __launch_bounds__(kTsThreads) void tsgemm_ws_grouped_kernel(const __half *__restrict__ x, const __half *__restrict__ w,
+                                                                       const __half *__restrict__ bias, __half *__restrict__ out,
+                                                                       int M, int N, int units_total, int parts, int chunks,
+                                                                       TsPacked pk) {
+  tsgemm_ws_body<0, KS, true>(x, w, bias, nullptr, out, M, N, 0, units_total, parts, chunks, pk);
 }
 
 // ---- the int8 activation chain's flavour (quantization.Int8ChainBackbone: the 1x1 convolutions of ResNet stages 3 / 4):
@@ -1086,18 +1108,30 @@ const bool g_ts_env_old = [] {
 // byte for byte to bevops_tsgemm_f16, and so is the LayerNorm epilogue)
 inline bool ts_use_ws(int k) { return k <= 256 && g_ts_variant != 1 && !g_ts_env_old; }
 
-template <int EPI, int KS>
+template <int EPI, int KS, bool GRP = false>
 int ws_launch_ks(const void *x, const void *w, const void *bias, const void *res, void *out, long long m, int n, int relu,
                  const TsPacked &pk, hipStream_t st) {
-  if (!ensure_dynamic_lds<tsgemm_ws_kernel<EPI, KS>>(ws_lds(KS))) return BEVOPS_FAILURE;
+  if constexpr (GRP) {
+    if (!ensure_dynamic_lds<tsgemm_ws_grouped_kernel<KS>>(ws_lds(KS))) return BEVOPS_FAILURE;
+  } else {
+    if (!ensure_dynamic_lds<tsgemm_ws_kernel<EPI, KS>>(ws_lds(KS))) return BEVOPS_FAILURE;
+  }
   const int units = (int)((m + 31) / 32), chunks = n / kTsBN;
   const int cus = ts_grid_x(1 << 30, chunks);
   int parts = cus / chunks;
   if (parts < 1) parts = 1;
+  // grouped: a multiple of 8 partitions, so that the kernel's block -> (partition, chunk) map can put the chunks of a
+  // partition on one XCD for any G (256 CUs / 6 chunks = 42 partitions would scatter them: 40 do not)
+  if (GRP && parts >= 8) parts -= parts % 8;
   if (parts > units) parts = units;
-  hipLaunchKernelGGL((tsgemm_ws_kernel<EPI, KS>), dim3((unsigned)(parts * chunks)), dim3(kTsThreads), ws_lds(KS), st,
-                     (const __half *)x, (const __half *)w, (const __half *)bias, (const __half *)res, (__half *)out, (int)m,
-                     n, relu, units, parts, chunks, pk);
+  if constexpr (GRP)
+    hipLaunchKernelGGL((tsgemm_ws_grouped_kernel<KS>), dim3((unsigned)(parts * chunks)), dim3(kTsThreads), ws_lds(KS), st,
+                       (const __half *)x, (const __half *)w, (const __half *)bias, (__half *)out, (int)m, n, units, parts,
+                       chunks, pk);
+  else
+    hipLaunchKernelGGL((tsgemm_ws_kernel<EPI, KS>), dim3((unsigned)(parts * chunks)), dim3(kTsThreads), ws_lds(KS), st,
+                       (const __half *)x, (const __half *)w, (const __half *)bias, (const __half *)res, (__half *)out, (int)m,
+                       n, relu, units, parts, chunks, pk);
   return launch_status();
 }
 
@@ -1147,6 +1181,38 @@ extern "C" int bevops_tsgemm_f16(const void *x, const void *weight, const void *
                      (const __half *)x, (const __half *)weight, (const __half *)bias, (const __half *)residual,
                      (__half *)out, (int)m, n, k, relu, units, none);
   return launch_status();
+}
+
+// G dense layers of 256 columns over the SAME rows as one launch: out + g * group_stride (elements) receives the dense
+// [M, 256] matrix x @ weight[g * 256 .. g * 256 + 255].T + bias[g * 256 ..], exactly the bytes of G calls of
+// bevops_tsgemm_f16 with n = 256 (same kernel, same per-row arithmetic; a row is read from HBM once, by the chunks of its
+// partition on one XCD).  K % 64 == 0, K <= 256 (the weight-stationary kernel's domain); no residual, no activation.
+extern "C" int bevops_tsgemm_f16_grouped(const void *x, const void *weight, const void *bias, void *out,
+                                         long long group_stride, long long m, int groups, int k, void *stream) {
+  if (!x || !weight || !out || m <= 0 || groups <= 0 || k <= 0) return BEVOPS_BAD_PARAM;
+  if (k % 64 != 0 || k > 256 || groups > 64) return BEVOPS_NOT_SUPPORTED;
+  if ((double)m * k * 2 >= 4294967040.0 || m > 0x7fffffff) return BEVOPS_NOT_SUPPORTED;
+  if (!aligned16(x) || !aligned16(weight) || !aligned16(out) || (bias && !aligned16(bias))) return BEVOPS_BAD_PARAM;
+  if (group_stride < m * kTsBN || group_stride % 8 != 0) return BEVOPS_BAD_PARAM;   // the G outputs would overlap / lose alignment
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!ts_use_ws(k)) {   // the A/B variant: the G launches themselves
+    for (int g = 0; g < groups; ++g) {
+      const int rc = bevops_tsgemm_f16(x, static_cast<const __half *>(weight) + (size_t)g * kTsBN * k,
+                                       bias ? static_cast<const __half *>(bias) + (size_t)g * kTsBN : nullptr, nullptr,
+                                       static_cast<__half *>(out) + (size_t)g * (size_t)group_stride, m, kTsBN, k, 0, stream);
+      if (rc != BEVOPS_SUCCESS) return rc;
+    }
+    return BEVOPS_SUCCESS;
+  }
+  TsPacked pk{};
+  pk.gstride = group_stride;
+  const int n = groups * kTsBN;
+  switch (k / 64) {
+    case 1: return ws_launch_ks<0, 1, true>(x, weight, bias, nullptr, out, m, n, 0, pk, st);
+    case 2: return ws_launch_ks<0, 2, true>(x, weight, bias, nullptr, out, m, n, 0, pk, st);
+    case 3: return ws_launch_ks<0, 3, true>(x, weight, bias, nullptr, out, m, n, 0, pk, st);
+    default: return ws_launch_ks<0, 4, true>(x, weight, bias, nullptr, out, m, n, 0, pk, st);
+  }
 }
 
 // out = LayerNorm_256(fp16(x @ weight.T + bias + residual)) * ln_weight + ln_bias in ONE launch (EPI 2 above).

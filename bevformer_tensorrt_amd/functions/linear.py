@@ -2,6 +2,8 @@
 epilogue in the GEMM: out = act(x @ weight.T + bias + residual) as one `bevops_linear_bias_act`
 call (hipBLASLt MFMA kernel, shift + identity + ReLU in its epilogue).  Not a reference plugin:
 the reference leaves these layers to cuBLAS / TensorRT."""
+import ctypes
+
 import torch
 
 from ..utils import lib as _lib
@@ -200,6 +202,37 @@ def tsgemm(x, weight, bias=None, residual=None, relu=False, out=None):
     return out.view(*x.shape[:-1], N)
 
 
+def tsgemm_grouped(x, weight, bias=None, out=None):
+    """G dense layers of 256 columns over the SAME rows in ONE launch (bevops_tsgemm_f16_grouped): x [..., K] fp16,
+    weight [G * 256, K] (the G layers' weights stacked), bias [G * 256] or None -> out [G, M, 256], out[g] bit for bit
+    tsgemm(x, weight[g * 256:(g + 1) * 256], bias[g * 256:(g + 1) * 256]).  The rows are read from memory once instead
+    of G times.  Raises BevopsError (NOT_SUPPORTED) unless K % 64 == 0 and K <= 256."""
+    assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
+    K, N = x.shape[-1], weight.shape[0]
+    if weight.shape[1] != K or N % 256 != 0 or N == 0:
+        raise ValueError(f"weight {tuple(weight.shape)} must be [G * 256, {K}]")
+    G = N // 256
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    weight = weight.contiguous()
+    M = x2.shape[0]
+    if bias is not None:
+        bias = bias.to(torch.float16).contiguous()
+    if out is None:
+        out = torch.empty((G, M, 256), dtype=x.dtype, device=x.device)
+    else:
+        assert out.is_contiguous() and tuple(out.shape) == (G, M, 256) and out.dtype == x.dtype
+    if M == 0:
+        return out
+    handle = _lib.load_library()
+    with torch.cuda.device(x.device):
+        st = handle.bevops_tsgemm_f16_grouped(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                              out.data_ptr(), M * 256, M, G, K, _lib.current_stream_ptr(x.device))
+    _lib.check(st, "bevops_tsgemm_f16_grouped")
+    return out
+
+
 def tsgemm_ln(x, weight, bias, residual, ln_weight, ln_bias, eps=1e-5):
     """layer_norm(x @ weight.T + bias + residual) * ln_weight + ln_bias in ONE launch (bevops_tsgemm_f16_ln): the dense
     layer that ends an attention / FFN block of the encoder or decoder together with the block's norm
@@ -269,6 +302,67 @@ def tile_gemm(x, weight, bias=None, residual=None, relu=False, out=None):
                                          int(bool(relu)), _lib.current_stream_ptr(x.device))
     _lib.check(st, "bevops_tile_gemm_f16")
     return out.view(*x.shape[:-1], N)
+
+
+class _GemmDst(ctypes.Structure):     # bevops_gemm_dst (include/bevops.h)
+    _fields_ = [("col_begin", ctypes.c_int), ("col_end", ctypes.c_int), ("out", ctypes.c_void_p),
+                ("out_pitch", ctypes.c_longlong), ("res", ctypes.c_void_p), ("res_pitch", ctypes.c_longlong)]
+
+
+def tile_gemm_dst(x, weight, bias, widths, residuals=None, relu=False, outs=None, _entry="bevops_tile_gemm_f16_dst"):
+    """Several layers over the SAME rows in ONE launch of the tiled GEMM (bevops_tile_gemm_f16_dst): weight [N, K] and
+    bias [N] (or None) are the layers' parameters stacked, `widths` their column counts (multiples of 64, sum N);
+    residuals[i] is None or layer i's identity [M, widths[i]] (any row pitch that is a multiple of 8).  Returns the
+    list of dense [M, widths[i]] results -- each bit for bit tile_gemm(x, weight_i, bias_i, residuals[i], relu).
+    `outs`: optional destinations (2-d, unit column stride, row pitch a multiple of 8)."""
+    assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
+    K, N = x.shape[-1], weight.shape[0]
+    if weight.shape[1] != K or sum(widths) != N:
+        raise ValueError(f"weight {tuple(weight.shape)} does not match x [..., {K}] / widths {list(widths)}")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    weight = weight.contiguous()
+    M = x2.shape[0]
+    if bias is not None:
+        bias = bias.to(torch.float16).contiguous()
+    if outs is None:
+        outs = [torch.empty((M, n), dtype=x.dtype, device=x.device) for n in widths]
+    residuals = residuals if residuals is not None else [None] * len(widths)
+    if M == 0:
+        return outs
+    tab = (_GemmDst * len(widths))()
+    col = 0
+    for i, n in enumerate(widths):
+        o, r = outs[i], residuals[i]
+        assert o.dtype == x.dtype and tuple(o.shape) == (M, n) and (n == 1 or o.stride(1) == 1)
+        tab[i].col_begin, tab[i].col_end, tab[i].out, tab[i].out_pitch = col, col + n, o.data_ptr(), o.stride(0) if M > 1 else n
+        if r is not None:
+            if r.dtype != x.dtype or tuple(r.shape) != (M, n) or r.stride(1) != 1:
+                raise ValueError("residual must be fp16 [M, width] with unit column stride")
+            tab[i].res, tab[i].res_pitch = r.data_ptr(), r.stride(0) if M > 1 else n
+        col += n
+    handle = _lib.load_library()
+    with torch.cuda.device(x.device):
+        st = getattr(handle, _entry)(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                     ctypes.addressof(tab), len(widths), M, N, K, int(bool(relu)),
+                                     _lib.current_stream_ptr(x.device))
+    _lib.check(st, _entry)
+    return outs
+
+
+def small_gemm_dst(x, weight, bias, widths, residuals=None, relu=False, outs=None):
+    """tile_gemm_dst's call on the few-row GEMM (bevops_small_gemm_f16_dst): every layer but the last has a width that
+    is a multiple of 64, the last a multiple of 8; each result bit for bit small_gemm(x, weight_i, bias_i, residuals[i])."""
+    if x.numel() // x.shape[-1] > 8192:
+        raise _lib.BevopsError("small_gemm_dst: more than 8192 rows (the tiled GEMMs' domain)", _lib.NOT_SUPPORTED)
+    return tile_gemm_dst(x, weight, bias, widths, residuals, relu, outs, _entry="bevops_small_gemm_f16_dst")
+
+
+def tsgemm_weight_stationary(K):
+    """True when bevops_tsgemm_f16 runs its weight-stationary kernel for this K (K <= 256 under the default variant; not
+    under bevops_tsgemm_set_variant(1) / BEVOPS_TSGEMM_WS=0, whose kernel rotates its k start by block index)."""
+    return _lib.load_library().bevops_tsgemm_tile_rows(int(K)) == 64
 
 
 def small_gemm(x, weight, bias=None, residual=None, relu=False, out=None):
@@ -396,6 +490,15 @@ def _dense_own(key, N, K, M):
     times = _table().get("measured_dense", {}).get(_problem(key), {})
     own = {k: v for k, v in times.items() if k in ("tile", "tsgemm", "small") and k in _DENSE}
     return min(own, key=own.get) if own else _dense_deterministic(N, K, M)
+
+
+def own_kernel_choice(device, M, N, K, relu, has_bias, has_res):
+    """The implementation dense_auto runs for this problem under OWN_KERNELS (a function of the problem and the shipped
+    table alone).  The model's merged launches ask it: they replace a per-layer GEMM only where that GEMM runs on
+    tile_gemm or tsgemm -- tile_gemm and the weight-stationary tsgemm (tsgemm_weight_stationary) share matrix
+    instruction, k order and epilogue arithmetic and give the same bits (tests/test_gemm_grouped_gpu.py); the original
+    tsgemm kernel rotates its k start by block index, small_gemm splits K inside the block: neither does."""
+    return _dense_own((str(device), M, N, K, bool(relu), bool(has_bias), bool(has_res)), N, K, M)
 
 
 def _dense_default(N, K, has_res):

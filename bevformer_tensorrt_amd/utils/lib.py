@@ -70,6 +70,7 @@ SIGNATURES = {
     "bevops_point_sampling": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
                                       c_void_p]),
     "bevops_tsgemm_f16": (c_int, [c_void_p] * 5 + [ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
+    "bevops_tsgemm_f16_grouped": (c_int, [c_void_p] * 4 + [ctypes.c_longlong, ctypes.c_longlong, c_int, c_int, c_void_p]),
     "bevops_tsgemm_set_variant": (c_int, [c_int]),
     "bevops_tsgemm_tile_rows": (c_int, [c_int]),
     "bevops_tsgemm_f16_ln": (c_int, [c_void_p] * 6 + [c_float, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p]),
@@ -116,6 +117,8 @@ SIGNATURES = {
                                          c_float, ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
     "bevops_small_gemm_f16": (c_int, [c_void_p] * 5 + [ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
     "bevops_tile_gemm_f16": (c_int, [c_void_p] * 5 + [ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
+    "bevops_tile_gemm_f16_dst": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
+    "bevops_small_gemm_f16_dst": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
     "bevops_conv_tile_f16": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p]),
     "bevops_conv3x3_c64_f16": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
     "bevops_refine_reference_points": (c_int, [c_int] + [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 3),

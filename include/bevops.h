@@ -463,6 +463,28 @@ int bevops_linear_int8_fused(const void *x_f16, float scale_a, const void *w_q, 
  * next to bevops_tsgemm_f16 and bevops_linear_bias_act. */
 int bevops_tile_gemm_f16(const void *x, const void *weight, const void *bias, const void *residual,
                          void *out, long long M, int N, int K, int relu, void *stream);
+/* Several layers that read the SAME rows as one launch of that kernel: weight [N, K] / bias [N] are the layers'
+ * parameters stacked, and a table of at most 8 destinations says where each column range of the product goes --
+ * columns [col_begin, col_end) as a pitched fp16 matrix of their own (element (m, col_begin + c) at
+ * out[m * out_pitch + c]) with identity rows of their own (res[m * res_pitch + c], or NULL).  Exactly the bytes of
+ * the separate bevops_tile_gemm_f16 launches on weight[col_begin:col_end]; columns outside every range and the bytes
+ * between pitched rows are never written.  Range bounds are multiples of 64, ranges do not overlap, pitches are
+ * multiples of 8 elements and at least the range's width, pointers 16-byte aligned (else BEVOPS_BAD_PARAM); N > 64. */
+typedef struct bevops_gemm_dst {
+  int col_begin, col_end;
+  void *out;
+  long long out_pitch;
+  const void *res;
+  long long res_pitch;
+} bevops_gemm_dst;
+int bevops_tile_gemm_f16_dst(const void *x, const void *weight, const void *bias, const bevops_gemm_dst *dst, int num_dst,
+                             long long M, int N, int K, int relu, void *stream);
+/* The same table on the few-row GEMM (bevops_small_gemm_f16: 32 x 64 tiles, K % 64 == 0, K <= 1024, M <= 65536) -- the
+ * decoder's sampling_offsets | attention_weights over the same 900 queries (N = 64 + 32, the two cached query_pos terms as
+ * identities) as one launch.  Here a range begins on a multiple of 64 and ends on a multiple of 8, and no two ranges share
+ * a 64-column block.  Exactly the bytes of the separate bevops_small_gemm_f16 launches. */
+int bevops_small_gemm_f16_dst(const void *x, const void *weight, const void *bias, const bevops_gemm_dst *dst, int num_dst,
+                              long long M, int N, int K, int relu, void *stream);
 /* Convolution on channels-last fp16 activations as an implicit GEMM on the same tiled skeleton (no column
  * buffer, no strided copy): kernel ksize x ksize in {1, 3}, pad ksize / 2, any stride.  x [B, H, W, Cin],
  * weight_taps [Cout][ksize][ksize][Cin] (= weight.permute(0, 2, 3, 1)), out [B, Hout, Wout, Cout] =
@@ -729,6 +751,14 @@ int bevops_tsgemm_f16(const void *x, const void *weight, const void *bias, const
  * domain). */
 int bevops_tsgemm_set_variant(int variant);
 int bevops_tsgemm_tile_rows(int k);
+/* `groups` dense layers of 256 columns over the SAME rows as ONE launch of the weight-stationary kernel (the six
+ * decoder layers' value_proj of bev_embed): weight
+ * [groups * 256, K], bias [groups * 256] or NULL; layer g's result is the dense [M, 256] matrix at
+ * out + g * group_stride (fp16 elements; >= m * 256, a multiple of 8).  Exactly the bytes of `groups` calls of
+ * bevops_tsgemm_f16 with n = 256 -- the rows are read from HBM once instead of `groups` times.  No residual, no
+ * activation.  BEVOPS_NOT_SUPPORTED unless K % 64 == 0 and K <= 256. */
+int bevops_tsgemm_f16_grouped(const void *x, const void *weight, const void *bias, void *out, long long group_stride,
+                              long long m, int groups, int k, void *stream);
 /* The same GEMM with the LayerNorm that follows it in every encoder / decoder block (modules/encoder.py:586-636,
  * modules/decoder.py:52-112: attention or FFN with its identity, then `norm`) evaluated in the epilogue:
  *     out = LayerNorm_N(fp16(x w^T + bias (+ residual))) * ln_weight + ln_bias,     N == 256, K % 64 == 0.
