@@ -39,6 +39,7 @@ import torch.nn.functional as F
 
 from . import functions as _hip_ops
 from . import geometry as G
+from .functions.linear import DETERMINISTIC, OWN_KERNELS, own_kernel_choice, tsgemm_weight_stationary
 from .utils import lib as _lib
 
 CONFIGS = {
@@ -105,6 +106,17 @@ _TSA_LOCAL = {"enabled": os.environ.get("BEVOPS_TSA_LOCAL", "1") == "1"}
 _TSA_GLUE = {"enabled": os.environ.get("BEVOPS_TSA_GLUE", "1") == "1"}   # A/B: bevops_tsa_split / bevops_queue_mean2 vs the framework copies
 
 
+def _or_none(fn, *args, **kwargs):
+    """fn(*args, **kwargs), or None where the library answers NOT_SUPPORTED (outside the kernel's domain, no algorithm
+    for the shape: the caller's other path runs); every other status stays an error."""
+    try:
+        return fn(*args, **kwargs)
+    except _lib.BevopsError as exc:
+        if exc.status != _lib.NOT_SUPPORTED:
+            raise
+        return None
+
+
 def _fused_linear(ops, x, weight, bias, residual, relu):
     """out = act(x @ weight.T + bias + residual) in ONE GEMM (ops.linear_bias_act: hipBLASLt with
     the shift + identity + ReLU epilogue) -- or None when the operator set has no such entry, the
@@ -116,18 +128,8 @@ def _fused_linear(ops, x, weight, bias, residual, relu):
     auto = getattr(ops, "dense_auto", None)
     if auto is not None and _R3["enabled"]:
         # measured per problem: tsgemm / tile_gemm (hand-written MFMA GEMMs) / hipBLASLt / the framework's addmm
-        try:
-            return auto(x, weight, bias, residual, relu)
-        except _lib.BevopsError as exc:
-            if exc.status != _lib.NOT_SUPPORTED:
-                raise
-            return None
-    try:
-        return fn(x, weight, bias, residual, relu)
-    except _lib.BevopsError as exc:   # only NOT_SUPPORTED (no algorithm for this shape) falls back
-        if exc.status != _lib.NOT_SUPPORTED:
-            raise
-        return None
+        return _or_none(auto, x, weight, bias, residual, relu)
+    return _or_none(fn, x, weight, bias, residual, relu)   # only NOT_SUPPORTED (no algorithm for this shape) falls back
 
 
 def _gemm_entry(ops):
@@ -204,11 +206,9 @@ def _dense_norm(ops, lin, x, residual, norm):
             and x.dtype == torch.float16 and x.is_cuda and lin.out_features == EMBED and lin.in_features % 64 == 0 \
             and isinstance(norm, nn.LayerNorm) and norm.elementwise_affine and norm.normalized_shape == (EMBED,) \
             and x.numel() // x.shape[-1] >= 32:
-        try:
-            return fn(x, lin.weight, lin.bias, residual, norm.weight, norm.bias, norm.eps)
-        except _lib.BevopsError as exc:
-            if exc.status != _lib.NOT_SUPPORTED:
-                raise
+        out = _or_none(fn, x, lin.weight, lin.bias, residual, norm.weight, norm.bias, norm.eps)
+        if out is not None:
+            return out
     if _int8_ln_on(ops) and _int8_norm_ok(lin, x, norm):
         # INT8 engine, switch on: one quantise pass over the fp16 operand, then the int8 GEMM with identity and norm in its
         # epilogue -- two launches for two, 1 byte per operand element instead of 2 and no [M, 256] round trip
@@ -521,17 +521,14 @@ class TemporalSelfAttention(nn.Module):
         their epilogue's identity replace the add, the [nq, 512] concatenation and two K=512 GEMMs.
         `prev_term`: prev_bev @ Wa.T + the cached term, when the caller evaluated it for all layers at once
         (_merged_prev_terms).  None -> the caller's module-by-module path (quantised build, fp32, CPU, no algorithm)."""
-        try:
+        def both_terms():
             terms = self._split_terms(query, bev_pos)
             if terms is None:
                 return None
             fn, wa, wb, pos_term = terms
             t = prev_term if prev_term is not None else fn(prev0.reshape(-1, EMBED), wa, None, pos_term, False)
             return fn(query.reshape(-1, EMBED), wb, None, t, False)
-        except _lib.BevopsError as exc:
-            if exc.status != _lib.NOT_SUPPORTED:
-                raise
-            return None
+        return _or_none(both_terms)
 
     def _split_terms(self, query, bev_pos):
         """(GEMM entry, Wa, Wb, bev_pos @ Wb.T + b) of _split_projection, the weights and the frame-independent term from
@@ -769,7 +766,6 @@ def _merge_ok(ops, x, linears, has_res):
             or getattr(ops, "dense_auto", None) is None or x.dtype != torch.float16 or not x.is_cuda \
             or not all(type(l) is nn.Linear and l.bias is not None and l.weight.dtype == torch.float16 for l in linears):
         return False
-    from .functions.linear import OWN_KERNELS
     if not OWN_KERNELS["enabled"]:
         return False
     K = x.shape[-1]
@@ -781,7 +777,6 @@ def _per_layer_kernels(device, M, widths, K, has_bias, has_res):
     weight-stationary tsgemm: the same bits, what tile_gemm_dst and tsgemm_grouped reproduce), "small" (the few-row kernel:
     small_gemm_dst) or None (mixed, or tsgemm's original kernel -- K > 256, bevops_tsgemm_set_variant(1),
     BEVOPS_TSGEMM_WS=0 -- which rotates its k start by block index: no merged launch has its bits)."""
-    from .functions.linear import own_kernel_choice, tsgemm_weight_stationary
     if M <= 0:
         return None
     names = {own_kernel_choice(device, M, n, K, False, has_bias, has_res) for n in widths}
@@ -805,12 +800,7 @@ def _merged_pair(ops, owner, cache, lin_a, lin_b, x):
         hit = (key, torch.cat([lin_a.weight, lin_b.weight]).detach().contiguous(),
                torch.cat([lin_a.bias, lin_b.bias]).detach().contiguous())
         setattr(owner, cache, hit)
-    try:
-        return fn(x.reshape(-1, x.shape[-1]), hit[1], hit[2], widths)
-    except _lib.BevopsError as exc:
-        if exc.status != _lib.NOT_SUPPORTED:
-            raise
-        return None
+    return _or_none(fn, x.reshape(-1, x.shape[-1]), hit[1], hit[2], widths)
 
 
 def _merged_prev_terms(ops, owner, cache, tsas, query, prev0, bev_pos):
@@ -821,10 +811,10 @@ def _merged_prev_terms(ops, owner, cache, tsas, query, prev0, bev_pos):
     if fn is None or not (_MERGED_PROJ["enabled"] and _R3["enabled"] and _FUSED_LINEAR["enabled"]) \
             or prev0.dtype != torch.float16 or not prev0.is_cuda:
         return None
-    from .functions.linear import OWN_KERNELS
     if not OWN_KERNELS["enabled"]:
         return None
-    try:
+
+    def all_layers():
         terms = [t._split_terms(query, bev_pos) for t in tsas]
         if any(t is None for t in terms):
             return None
@@ -838,10 +828,7 @@ def _merged_prev_terms(ops, owner, cache, tsas, query, prev0, bev_pos):
             hit = (key, torch.cat([t[1] for t in terms]).contiguous())
             setattr(owner, cache, hit)
         return fn(prev0.reshape(-1, EMBED), hit[1], None, widths, [t[3] for t in terms])
-    except _lib.BevopsError as exc:
-        if exc.status != _lib.NOT_SUPPORTED:
-            raise
-        return None
+    return _or_none(all_layers)
 
 
 def _merged_value_proj(ops, owner, cache, linears, x):
@@ -859,12 +846,7 @@ def _merged_value_proj(ops, owner, cache, linears, x):
         hit = (key, torch.cat([l.weight for l in linears]).detach().contiguous(),
                torch.cat([l.bias for l in linears]).detach().contiguous())
         setattr(owner, cache, hit)
-    try:
-        return fn(x.reshape(-1, EMBED), hit[1], hit[2])
-    except _lib.BevopsError as exc:
-        if exc.status != _lib.NOT_SUPPORTED:
-            raise
-        return None
+    return _or_none(fn, x.reshape(-1, EMBED), hit[1], hit[2])
 
 
 class CustomMSDeformableAttention(nn.Module):
@@ -885,7 +867,6 @@ class CustomMSDeformableAttention(nn.Module):
         ops, so, aw = self.ops, self.sampling_offsets, self.attention_weights
         fn = getattr(ops, "small_gemm_dst", None)
         widths = [so.weight.shape[0], aw.weight.shape[0]]
-        from .functions.linear import OWN_KERNELS
         if fn is None or not _MERGED_PROJ["enabled"] or not OWN_KERNELS["enabled"] or widths[0] % 64 or widths[1] % 8 \
                 or so.weight.dtype != torch.float16 or aw.weight.dtype != torch.float16 \
                 or _per_layer_kernels(q2.device, q2.shape[0], widths, EMBED, False, True) != "small":
@@ -893,12 +874,7 @@ class CustomMSDeformableAttention(nn.Module):
         key = _versions(so.weight, aw.weight)
         if self._so_aw is None or self._so_aw[0] != key:
             self._so_aw = (key, torch.cat([so.weight, aw.weight]).detach().contiguous())
-        try:
-            return fn(q2, self._so_aw[1], None, widths, [t_so, t_aw])
-        except _lib.BevopsError as exc:
-            if exc.status != _lib.NOT_SUPPORTED:
-                raise
-            return None
+        return _or_none(fn, q2, self._so_aw[1], None, widths, [t_so, t_aw])
 
     def forward(self, query, value, query_pos, reference_points, spatial_shapes, norm=None, projected=None, merged=False):
         """`projected`: value_proj(value) [nk, 256] when the caller has evaluated it already (_merged_value_proj);
@@ -973,11 +949,9 @@ class DecoderLayer(nn.Module):
         own = getattr(ops, "self_attention_qkv", None) if _OWN_ATTN["enabled"] else None
         o = None
         if own is not None:
-            try:     # one launch on the matrix cores (K / V of a head staged in LDS): 900 queries x 8 heads x 32
-                o = own(qkv.view(n, 3, HEADS, EMBED // HEADS)).view(n, 1, EMBED)
-            except _lib.BevopsError as exc:
-                if exc.status != _lib.NOT_SUPPORTED:
-                    raise
+            # one launch on the matrix cores (K / V of a head staged in LDS): 900 queries x 8 heads x 32
+            o = _or_none(own, qkv.view(n, 3, HEADS, EMBED // HEADS))
+            o = o.view(n, 1, EMBED) if o is not None else None
         if o is None:
             q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))           # [1, heads, 900, 32] views
             o = F.scaled_dot_product_attention(q, k, v)                          # [1, heads, 900, 32]
@@ -1108,7 +1082,6 @@ class BEVFormer(nn.Module):
         mlvl = self.extract_feat(image, cams)
         if _OWN_ENCODER["enabled"] and image.is_cuda and image.dtype == torch.float16:
             # everything behind the backbone on the hand-written GEMMs (fixed summation order): see _OWN_ENCODER
-            from .functions.linear import OWN_KERNELS
             was, OWN_KERNELS["enabled"] = OWN_KERNELS["enabled"], True
             try:
                 return self._transformer(mlvl, image, prev_bev, use_prev_bev, can_bus, lidar2img, cams, gather, shift, proj)
@@ -1430,7 +1403,6 @@ class FrameRunner:
             # the table has not seen, by a rule of the shape alone; the backbone is per-camera work no other rank
             # repeats and keeps the measured dispatch.  Without _OWN_ENCODER (or BEVOPS_SHARDED_RULE_DISPATCH=1, the
             # behaviour of rounds 3-5, 6-9 % slower) the rule-based dispatch is on for the whole forward.
-            from .functions.linear import DETERMINISTIC
             prev, DETERMINISTIC["enabled"] = DETERMINISTIC["enabled"], True
             try:
                 return self._forward_impl()

@@ -13,7 +13,7 @@
 //     bias, identity, ReLU in fp32, one rounding, one 16-byte store.
 // Rows / columns past M / N read as zero through the buffer descriptors' range check and are not stored.
 // Domain: K % 64 == 0 (four k-quarters of whole 16-value steps), K <= 1024 (operand registers), 16-byte aligned rows.
-#include "common.h"
+#include "gemm_host.h"
 
 namespace bevops {
 namespace {
@@ -22,7 +22,6 @@ typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 constexpr int kSgM = 32, kSgN = 64, kSgStride = kSgN + 4;   // partial rows padded by 4 floats (bank spread)
-constexpr unsigned kSgOob = 0xFFFFFF00u;
 
 struct SmallArgs {
   const __half *x, *w, *bias, *res;
@@ -30,18 +29,15 @@ struct SmallArgs {
   int M, N, K, relu;
 };
 
-// DST (bevops_small_gemm_f16_dst): the output columns go to up to kSgMaxDst destinations, each a column range of the
+// DST (bevops_small_gemm_f16_dst): the output columns go to up to kGemmMaxDst destinations, each a column range of the
 // launch written as a pitched matrix of its own with an identity of its own -- layers that read the same rows as ONE
 // launch.  A range begins on a multiple of 64, so a block's 64 columns have one destination, found by compare-and-select
 // over the by-value table with the block's n0 (scalar); columns of the block past the range's end are not stored.
 // Everything in front of the identity add is the code of the plain launch.
-constexpr int kSgMaxDst = 8;
-struct SmallDst { int col_begin, col_end; __half *out; const __half *res; int out_pitch, res_pitch; };
-struct SmallDstTab { int count; SmallDst e[kSgMaxDst]; };
 
 // STEPS = k-steps (of 16 values) per wave = K / 64
 template <int STEPS, bool DST>
-__device__ __forceinline__ void small_gemm_body(const SmallArgs &p, const SmallDstTab &d) {
+__device__ __forceinline__ void small_gemm_body(const SmallArgs &p, const GemmDstTab &d) {
   __shared__ __attribute__((aligned(16))) float part[4][kSgM][kSgStride];   // 34.8 KB
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tiles_n = (p.N + kSgN - 1) / kSgN;
@@ -53,9 +49,9 @@ __device__ __forceinline__ void small_gemm_body(const SmallArgs &p, const SmallD
       const_cast<__half *>(p.w), 0, (unsigned)((size_t)p.N * K * 2), 0x00020000);
   const int r = lane & 31, half = lane >> 5;
   const int kq = wave * (K / 4) + half * 8;          // first k of this lane's fragments in the wave's quarter
-  const unsigned xo = m0 + r < p.M ? (unsigned)(((size_t)(m0 + r) * K + kq) * 2) : kSgOob;
-  const unsigned wo0 = n0 + r < p.N ? (unsigned)(((size_t)(n0 + r) * K + kq) * 2) : kSgOob;
-  const unsigned wo1 = n0 + 32 + r < p.N ? (unsigned)(((size_t)(n0 + 32 + r) * K + kq) * 2) : kSgOob;
+  const unsigned xo = m0 + r < p.M ? (unsigned)(((size_t)(m0 + r) * K + kq) * 2) : kGemmOob;
+  const unsigned wo0 = n0 + r < p.N ? (unsigned)(((size_t)(n0 + r) * K + kq) * 2) : kGemmOob;
+  const unsigned wo1 = n0 + 32 + r < p.N ? (unsigned)(((size_t)(n0 + 32 + r) * K + kq) * 2) : kGemmOob;
   // every operand fragment of the wave's quarter, requested before any is used
   u32x4 fx[STEPS], fw0[STEPS], fw1[STEPS];
 #pragma unroll
@@ -74,7 +70,7 @@ __device__ __forceinline__ void small_gemm_body(const SmallArgs &p, const SmallD
   int d_c0 = 0, d_c1 = 0, d_op = 0, d_rp = 0;
   if constexpr (DST) {
 #pragma unroll
-    for (int e = 0; e < kSgMaxDst; ++e) {
+    for (int e = 0; e < kGemmMaxDst; ++e) {
       const bool hit = e < d.count && n0 >= d.e[e].col_begin && n0 < d.e[e].col_end;
       d_out = hit ? d.e[e].out : d_out;
       d_res = hit ? d.e[e].res : d_res;
@@ -151,12 +147,35 @@ __device__ __forceinline__ void small_gemm_body(const SmallArgs &p, const SmallD
 
 template <int STEPS>
 __global__ __launch_bounds__(256) void small_gemm_f16_kernel(SmallArgs p) {
-  small_gemm_body<STEPS, false>(p, SmallDstTab{});
+  small_gemm_body<STEPS, false>(p, GemmDstTab{});
 }
 
 template <int STEPS>
-__global__ __launch_bounds__(256) void small_gemm_dst_kernel(SmallArgs p, SmallDstTab d) {
+__global__ __launch_bounds__(256) void small_gemm_dst_kernel(SmallArgs p, GemmDstTab d) {
   small_gemm_body<STEPS, true>(p, d);
+}
+
+// the launch of both entries, after their checks
+template <bool DST>
+int small_launch(const GemmCall &c, const GemmDstTab &tab) {
+  if (c.m == 0) return BEVOPS_SUCCESS;
+  SmallArgs p{static_cast<const __half *>(c.x), static_cast<const __half *>(c.w), static_cast<const __half *>(c.bias),
+              static_cast<const __half *>(c.res), static_cast<__half *>(c.out), (int)c.m, c.n, c.k, c.relu};
+  const long long blocks = ((c.m + kSgM - 1) / kSgM) * ((c.n + kSgN - 1) / kSgN);
+  if (blocks > 0x7fffffffLL) return BEVOPS_NOT_SUPPORTED;
+  const dim3 grid((unsigned)blocks), blk(256);
+  const int rc = gemm_k64<16>(c.k / 64, [&](auto steps) {
+    constexpr int S = decltype(steps)::value;
+    if constexpr (DST) hipLaunchKernelGGL(small_gemm_dst_kernel<S>, grid, blk, 0, c.st, p, tab);
+    else hipLaunchKernelGGL(small_gemm_f16_kernel<S>, grid, blk, 0, c.st, p);
+    return BEVOPS_SUCCESS;
+  });
+  return rc != BEVOPS_SUCCESS ? rc : launch_status();
+}
+
+// what both entries ask of the shared operands: K in whole k-quarters of 16-value steps that fit the operand registers
+inline bool small_domain(const GemmCall &c) {
+  return c.k % 64 == 0 && c.k <= 1024 && c.m <= 65536 && !misaligned(c.x, 15u) && !misaligned(c.w, 15u);
 }
 
 }  // namespace
@@ -166,26 +185,12 @@ using namespace bevops;
 
 extern "C" int bevops_small_gemm_f16(const void *x, const void *weight, const void *bias, const void *residual,
                                      void *out, long long M, int N, int K, int relu, void *stream) {
+  const GemmCall c{x, weight, bias, residual, out, M, N, K, relu, static_cast<hipStream_t>(stream)};
   if (!x || !weight || !out || M < 0 || N <= 0 || K <= 0) return BEVOPS_BAD_PARAM;
-  if (K % 64 != 0 || K > 1024 || M > 65536 || !aligned16(x) || !aligned16(weight) || !aligned16(out) ||
-      (residual && !aligned16(residual)) || (bias && (reinterpret_cast<uintptr_t>(bias) & 1u)))
+  if (!small_domain(c) || misaligned(out, 15u) || (residual && misaligned(residual, 15u)) || (bias && misaligned(bias, 1u)))
     return BEVOPS_NOT_SUPPORTED;
-  if ((unsigned long long)M * K * 2 >= kSgOob || (unsigned long long)N * K * 2 >= kSgOob) return BEVOPS_NOT_SUPPORTED;
-  if (M == 0) return BEVOPS_SUCCESS;
-  SmallArgs p{static_cast<const __half *>(x), static_cast<const __half *>(weight), static_cast<const __half *>(bias),
-              static_cast<const __half *>(residual), static_cast<__half *>(out), (int)M, N, K, relu};
-  const long long blocks = ((M + kSgM - 1) / kSgM) * ((N + kSgN - 1) / kSgN);
-  if (blocks > 0x7fffffffLL) return BEVOPS_NOT_SUPPORTED;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)blocks), blk(256);
-  switch (K / 64) {
-#define BEVOPS_SG(S_) case S_: hipLaunchKernelGGL(small_gemm_f16_kernel<S_>, grid, blk, 0, st, p); break
-    BEVOPS_SG(1); BEVOPS_SG(2); BEVOPS_SG(3); BEVOPS_SG(4); BEVOPS_SG(5); BEVOPS_SG(6); BEVOPS_SG(7); BEVOPS_SG(8);
-    BEVOPS_SG(9); BEVOPS_SG(10); BEVOPS_SG(11); BEVOPS_SG(12); BEVOPS_SG(13); BEVOPS_SG(14); BEVOPS_SG(15); BEVOPS_SG(16);
-#undef BEVOPS_SG
-    default: return BEVOPS_NOT_SUPPORTED;
-  }
-  return launch_status();
+  if (gemm_over_limit(M, K, 2) || gemm_over_limit(N, K, 2)) return BEVOPS_NOT_SUPPORTED;
+  return small_launch<false>(c, GemmDstTab{});
 }
 
 // bevops_small_gemm_f16 with a destination table (the decoder's sampling_offsets | attention_weights over the same 900
@@ -194,38 +199,12 @@ extern "C" int bevops_small_gemm_f16(const void *x, const void *weight, const vo
 // launches on weight[col_begin:col_end]; columns outside every range and the bytes between pitched rows are never written.
 extern "C" int bevops_small_gemm_f16_dst(const void *x, const void *weight, const void *bias, const bevops_gemm_dst *dst,
                                          int num_dst, long long M, int N, int K, int relu, void *stream) {
+  const GemmCall c{x, weight, bias, nullptr, nullptr, M, N, K, relu, static_cast<hipStream_t>(stream)};
   if (!x || !weight || !dst || M < 0 || N <= 0 || K <= 0 || num_dst <= 0) return BEVOPS_BAD_PARAM;
-  if (num_dst > kSgMaxDst || N % 8 != 0) return BEVOPS_NOT_SUPPORTED;
-  if (K % 64 != 0 || K > 1024 || M > 65536 || !aligned16(x) || !aligned16(weight) || (bias && !aligned16(bias)))
-    return BEVOPS_NOT_SUPPORTED;
-  if ((unsigned long long)M * K * 2 >= kSgOob || (unsigned long long)N * K * 2 >= kSgOob) return BEVOPS_NOT_SUPPORTED;
-  SmallDstTab tab{};
-  tab.count = num_dst;
-  for (int i = 0; i < num_dst; ++i) {
-    const bevops_gemm_dst &e = dst[i];
-    const long long width = (long long)e.col_end - e.col_begin;
-    // a range begins on the 64-column block grid and ends on it or on a multiple of 8 (then nothing else may begin in that block: begins are multiples of 64)
-    if (e.col_begin < 0 || e.col_end > N || width <= 0 || e.col_begin % 64 != 0 || e.col_end % 8 != 0) return BEVOPS_BAD_PARAM;
-    if (!e.out || !aligned16(e.out) || e.out_pitch < width || e.out_pitch % 8 != 0 || e.out_pitch > 0x7fffffffLL) return BEVOPS_BAD_PARAM;
-    if (e.res && (!aligned16(e.res) || e.res_pitch < width || e.res_pitch % 8 != 0 || e.res_pitch > 0x7fffffffLL)) return BEVOPS_BAD_PARAM;
-    for (int j = 0; j < i; ++j)   // overlapping ranges, or two ranges inside one 64-column block
-      if (e.col_begin < (dst[j].col_end + 63) / 64 * 64 && dst[j].col_begin < (e.col_end + 63) / 64 * 64) return BEVOPS_BAD_PARAM;
-    tab.e[i] = SmallDst{e.col_begin, e.col_end, static_cast<__half *>(e.out), static_cast<const __half *>(e.res),
-                        (int)e.out_pitch, e.res ? (int)e.res_pitch : 0};
-  }
-  if (M == 0) return BEVOPS_SUCCESS;
-  SmallArgs p{static_cast<const __half *>(x), static_cast<const __half *>(weight), static_cast<const __half *>(bias), nullptr,
-              nullptr, (int)M, N, K, relu};
-  const long long blocks = ((M + kSgM - 1) / kSgM) * ((N + kSgN - 1) / kSgN);
-  if (blocks > 0x7fffffffLL) return BEVOPS_NOT_SUPPORTED;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)blocks), blk(256);
-  switch (K / 64) {
-#define BEVOPS_SG(S_) case S_: hipLaunchKernelGGL(small_gemm_dst_kernel<S_>, grid, blk, 0, st, p, tab); break
-    BEVOPS_SG(1); BEVOPS_SG(2); BEVOPS_SG(3); BEVOPS_SG(4); BEVOPS_SG(5); BEVOPS_SG(6); BEVOPS_SG(7); BEVOPS_SG(8);
-    BEVOPS_SG(9); BEVOPS_SG(10); BEVOPS_SG(11); BEVOPS_SG(12); BEVOPS_SG(13); BEVOPS_SG(14); BEVOPS_SG(15); BEVOPS_SG(16);
-#undef BEVOPS_SG
-    default: return BEVOPS_NOT_SUPPORTED;
-  }
-  return launch_status();
+  if (num_dst > kGemmMaxDst || N % 8 != 0) return BEVOPS_NOT_SUPPORTED;
+  if (!small_domain(c) || (bias && misaligned(bias, 15u))) return BEVOPS_NOT_SUPPORTED;
+  if (gemm_over_limit(M, K, 2) || gemm_over_limit(N, K, 2)) return BEVOPS_NOT_SUPPORTED;
+  GemmDstTab tab;
+  const int rc = gemm_dst_table(tab, dst, num_dst, M, N, 8, false);
+  return rc != BEVOPS_SUCCESS ? rc : small_launch<true>(c, tab);
 }

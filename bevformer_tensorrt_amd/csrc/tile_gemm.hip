@@ -36,9 +36,7 @@
 // output row m is pixel (b, yo, xo), its k-values are [tap][Cin]; a tap moves the row's base address by a
 // block-uniform delta and a per-row validity bit (zero padding) selects the beyond-the-buffer address; a stride
 // only changes the row -> pixel map.  No column buffer, no sub-sampled copy.
-#include <type_traits>
-
-#include "common.h"
+#include "gemm_host.h"
 
 namespace bevops {
 namespace {
@@ -54,7 +52,6 @@ constexpr int kTM = 128;   // (bytes of k per row and step: template parameter K
 constexpr float kQMagic = 12582912.f;          // 1.5 * 2^23: bits 0x4B400000, low byte 0
 constexpr int kQMagicBits = 0x4B400000;
 constexpr int kEpiStride = 64 * 4 + 16;        // staging row: 64 x 4 bytes + pad
-constexpr unsigned kOob = 0xFFFFFF00u;         // beyond any buffer: reads as zero
 
 __device__ __forceinline__ unsigned quant4(unsigned h01, unsigned h23, float r) {
   int b0 = __float_as_int(__builtin_fmaf(h2f_lo(h01), r, kQMagic));
@@ -100,18 +97,15 @@ struct TileArgs {
 constexpr int tile_lds_bytes(int tm) {
   return 2 * (tm + 128) * (64 + 16) > 4 * 32 * kEpiStride ? 2 * (tm + 128) * (64 + 16) : 4 * 32 * kEpiStride;
 }
-// DST (bevops_tile_gemm_f16_dst; F16, NI == 2): the output columns go to up to kMaxDst destinations, each a column range
+// DST (bevops_tile_gemm_f16_dst; F16, NI == 2): the output columns go to up to kGemmMaxDst destinations, each a column range
 // [col_begin, col_end) of the launch written as a pitched matrix of its own with an identity of its own -- several layers
 // that read the same rows as ONE launch.  Range bounds are multiples of 64, so the 32-row x 64-column block a wave's
 // epilogue works on has exactly one destination; it is chosen by scalar compare-and-select over the by-value table (an
 // indexed load would be a vector load behind the k-loop's requests).  Everything in front of the stores is the code of
 // the plain launch: an element's sum, bias, identity and rounding do not depend on where it is stored.
-constexpr int kMaxDst = 8;
-struct TileDst { int col_begin, col_end; __half *out; const __half *res; int out_pitch, res_pitch; };
-struct TileDstTab { int count; TileDst e[kMaxDst]; };
 
 template <int MODE, bool OUT8, int NI, bool CONV, bool RES8, bool DST>
-__device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const TileDstTab &d) {
+__device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const GemmDstTab &d) {
   constexpr int MJ = 2;                          // 32-row MFMA blocks per wave
   constexpr int KB = 64;                         // bytes of k per row and step
   constexpr int kTN = 64 * NI;
@@ -153,10 +147,10 @@ __device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const TileDstT
   const int cin = p.conv_cin;
   constexpr bool conv = CONV;
   const int taps = p.conv_ks * p.conv_ks, pad = p.conv_ks >> 1;
-  unsigned a_off0, a_off1 = kOob, tapmask0 = 0, tapmask1 = 0;   // (the second row of a staging thread: 128-row tiles only)
+  unsigned a_off0, a_off1 = kGemmOob, tapmask0 = 0, tapmask1 = 0;   // (the second row of a staging thread: 128-row tiles only)
   if (conv) {
     auto place = [&](int m, unsigned &off, unsigned &mk) {
-      off = kOob; mk = 0;
+      off = kGemmOob; mk = 0;
       if (m >= M) return;
       const int per = p.conv_hout * p.conv_wout;
       const int b = m / per, pix = m - b * per;
@@ -171,12 +165,12 @@ __device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const TileDstT
     place(m0 + r0, a_off0, tapmask0);
     place(m0 + r1, a_off1, tapmask1);
   } else {
-    a_off0 = m0 + r0 < M ? (unsigned)(((size_t)(m0 + r0) * K + kce) * kAB) : kOob;
-    a_off1 = m0 + r1 < M ? (unsigned)(((size_t)(m0 + r1) * K + kce) * kAB) : kOob;
+    a_off0 = m0 + r0 < M ? (unsigned)(((size_t)(m0 + r0) * K + kce) * kAB) : kGemmOob;
+    a_off1 = m0 + r1 < M ? (unsigned)(((size_t)(m0 + r1) * K + kce) * kAB) : kGemmOob;
   }
   int g_tap = 0, g_c = 0;                      // conv mode: the (tap, channel) position of the NEXT gload
-  const unsigned w_off0 = n0 + r0 < N ? (unsigned)(((size_t)(n0 + r0) * K + kce) * kWB) : kOob;
-  const unsigned w_off1 = (NI == 2 && n0 + r1 < N) ? (unsigned)(((size_t)(n0 + r1) * K + kce) * kWB) : kOob;
+  const unsigned w_off0 = n0 + r0 < N ? (unsigned)(((size_t)(n0 + r0) * K + kce) * kWB) : kGemmOob;
+  const unsigned w_off1 = (NI == 2 && n0 + r1 < N) ? (unsigned)(((size_t)(n0 + r1) * K + kce) * kWB) : kGemmOob;
   // register staging: kDepth sets (set = step parity).  Two sets keep the loads of TWO steps in flight per
   // block (the step's latency is what bounds the long-K layers); the fused-quantise flavour stages twice the
   // activation bytes per step and stays at one set (168 VGPRs = three blocks per CU)
@@ -191,8 +185,8 @@ __device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const TileDstT
     const bool kok = ks + kce < K;   // K is a multiple of a thread's chunk (host check)
     if constexpr (CONV) {
       const int delta = ((g_tap / p.conv_ks - pad) * p.conv_win + (g_tap % p.conv_ks - pad)) * cin * kAB;
-      const unsigned v0 = (tapmask0 >> g_tap) & 1u ? a_off0 + (unsigned)delta : kOob;
-      const unsigned v1 = (tapmask1 >> g_tap) & 1u ? a_off1 + (unsigned)delta : kOob;
+      const unsigned v0 = (tapmask0 >> g_tap) & 1u ? a_off0 + (unsigned)delta : kGemmOob;
+      const unsigned v1 = (tapmask1 >> g_tap) & 1u ? a_off1 + (unsigned)delta : kGemmOob;
 #pragma unroll
       for (int h = 0; h < kAV; ++h) {
         ra0[S][h] = bload(rs_a, v0 + 16u * h, g_c * kAB);
@@ -203,12 +197,12 @@ __device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const TileDstT
     } else {
 #pragma unroll
       for (int h = 0; h < kAV; ++h) {
-        ra0[S][h] = bload(rs_a, kok ? a_off0 + 16u * h : kOob, ks * kAB);
-        ra1[S][h] = bload(rs_a, kok ? a_off1 + 16u * h : kOob, ks * kAB);
+        ra0[S][h] = bload(rs_a, kok ? a_off0 + 16u * h : kGemmOob, ks * kAB);
+        ra1[S][h] = bload(rs_a, kok ? a_off1 + 16u * h : kGemmOob, ks * kAB);
       }
     }
-    rb0[S][0] = bload(rs_w, kok ? w_off0 : kOob, ks * kWB);
-    if constexpr (NI == 2) rb1[S][0] = bload(rs_w, kok ? w_off1 : kOob, ks * kWB);
+    rb0[S][0] = bload(rs_w, kok ? w_off0 : kGemmOob, ks * kWB);
+    if constexpr (NI == 2) rb1[S][0] = bload(rs_w, kok ? w_off1 : kGemmOob, ks * kWB);
   };
   const int lchunk = (tid & 3) * 16;           // byte position of the thread's chunk in an LDS row
   auto lstore = [&](int buf, auto setc) {
@@ -241,7 +235,7 @@ __device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const TileDstT
   if constexpr (DST) {
     const int cb = __builtin_amdgcn_readfirstlane(n0 + wn * 32 * NI);
 #pragma unroll
-    for (int e = 0; e < kMaxDst; ++e) {
+    for (int e = 0; e < kGemmMaxDst; ++e) {
       const bool hit = e < d.count && cb >= d.e[e].col_begin && cb < d.e[e].col_end;
       d_out = hit ? d.e[e].out : d_out;
       d_res = hit ? d.e[e].res : d_res;
@@ -264,7 +258,7 @@ __device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const TileDstT
     for (int it = 0; it < kIT; ++it) {
       const int m = m0 + wm * 32 * MJ + j * 32 + it * (64 / kCH) + lane / kCH;
       const unsigned off = (m < M && col_ok) ? (DST ? (unsigned)(((size_t)m * d_rp + (ncol - d_c0)) * kRB)
-                                                    : (unsigned)(((size_t)m * N + ncol) * kRB)) : kOob;
+                                                    : (unsigned)(((size_t)m * N + ncol) * kRB)) : kGemmOob;
       if constexpr (RES8) {   // 8 identity bytes of this lane's 8 columns
         const uint2 q = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rs_r, (int)off, 0, 0));
         rres[j][it] = make_uint4(q.x, q.y, 0u, 0u);
@@ -436,68 +430,71 @@ __device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const TileDstT
 
 template <int MODE, bool OUT8, int NI, bool CONV, bool RES8 = false>
 __global__ __launch_bounds__(256, 3) void tile_gemm_kernel(TileArgs p) {
-  tile_gemm_body<MODE, OUT8, NI, CONV, RES8, false>(p, TileDstTab{});
+  tile_gemm_body<MODE, OUT8, NI, CONV, RES8, false>(p, GemmDstTab{});
 }
 
-__global__ __launch_bounds__(256, 3) void tile_gemm_dst_kernel(TileArgs p, TileDstTab d) {
+__global__ __launch_bounds__(256, 3) void tile_gemm_dst_kernel(TileArgs p, GemmDstTab d) {
   tile_gemm_body<kF16, false, 2, false, false, true>(p, d);
 }
 
 struct ConvGeom { int cin = 0, hin = 0, win = 0, hout = 0, wout = 0, stride = 1, ks = 1; size_t in_elems = 0; };
 
+
+// The kernel arguments and the grid of a launch whose call passed its checks (a_bytes: size of the activation buffer).
+// false: more tiles than a grid numbers.
 template <int MODE>
-int launch_tile_gemm(const void *a, float scale_a, const void *w, const float *w_scales, float scale_w,
-                     const void *bias, const void *residual, int out_dtype, void *out, float scale_out, long long M,
-                     int N, int K, int relu, void *stream, const ConvGeom &cg = ConvGeom(), int res_dtype = BEVOPS_F16,
-                     float scale_res = 1.f) {
-  if (!a || !w || !out || M < 0 || N <= 0 || K <= 0) return BEVOPS_BAD_PARAM;
-  if (MODE != kF16 && (!(scale_a > 0.f) || (!w_scales && !(scale_w > 0.f)))) return BEVOPS_BAD_PARAM;
-  constexpr int kChunk = MODE == kF16 ? 8 : 16;   // k-values a staging thread handles per step
-  const bool res8 = residual != nullptr && res_dtype == BEVOPS_I8;
-  if (residual && res_dtype != BEVOPS_I8 && res_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-  if (res8 && (MODE != kS8 || cg.cin > 0)) return BEVOPS_NOT_SUPPORTED;   // int8 identity rows: the int8-chain GEMM only
-  if (res8 && !(scale_res > 0.f)) return BEVOPS_BAD_PARAM;
-  if (K % kChunk != 0 || !aligned16(a) || !aligned16(w) ||
-      (residual && (reinterpret_cast<uintptr_t>(residual) & (res8 ? 7u : 15u))) ||
-      (reinterpret_cast<uintptr_t>(out) & (out_dtype == BEVOPS_I8 ? 7u : 15u)) || M > 0x7fffffffLL)
-    return BEVOPS_NOT_SUPPORTED;
-  if (out_dtype == BEVOPS_I8 && (MODE == kF16 || !(scale_out > 0.f))) return BEVOPS_BAD_PARAM;
-  if (out_dtype != BEVOPS_I8 && out_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-  // operands (and the identity) are addressed through 32-bit buffer offsets
-  const unsigned long long a_bytes = (cg.cin > 0 ? (unsigned long long)cg.in_elems : (unsigned long long)M * K) *
-                                     (MODE == kS8 ? 1 : 2);
-  if (a_bytes >= kOob || (unsigned long long)N * K * (MODE == kF16 ? 2 : 1) >= kOob ||
-      (residual && (unsigned long long)M * N * (res8 ? 1 : 2) >= kOob))
-    return BEVOPS_NOT_SUPPORTED;
-  if (M == 0) return BEVOPS_SUCCESS;
-  TileArgs p;
-  p.a = a; p.w = w; p.bias = bias; p.res = residual; p.wscale = w_scales; p.out = out;
-  p.inv_sa = MODE == kF16 ? 1.f : 1.0f / scale_a;
-  p.s_aw = MODE == kF16 ? 1.f : (w_scales ? scale_a : scale_a * scale_w);
-  p.inv_s_out = out_dtype == BEVOPS_I8 ? 1.0f / scale_out : 0.f;
-  p.s_res = scale_res;
-  p.M = (int)M; p.N = N; p.K = K; p.relu = relu;
-  p.a_bytes = (unsigned)a_bytes;
+bool tile_plan(TileArgs &p, dim3 &grid, const GemmCallS8 &c, const ConvGeom &cg, unsigned a_bytes) {
+  p.a = c.x; p.w = c.w; p.bias = c.bias; p.res = c.res; p.wscale = c.w_scales; p.out = c.out;
+  p.inv_sa = MODE == kF16 ? 1.f : 1.0f / c.scale_a;
+  p.s_aw = MODE == kF16 ? 1.f : (c.w_scales ? c.scale_a : c.scale_a * c.scale_w);
+  p.inv_s_out = c.out_dtype == BEVOPS_I8 ? 1.0f / c.scale_out : 0.f;
+  p.s_res = c.scale_res;
+  p.M = (int)c.m; p.N = c.n; p.K = c.k; p.relu = c.relu;
+  p.a_bytes = a_bytes;
   p.conv_cin = cg.cin; p.conv_hin = cg.hin; p.conv_win = cg.win; p.conv_hout = cg.hout; p.conv_wout = cg.wout;
   p.conv_s = cg.stride; p.conv_ks = cg.ks;
-  const bool narrow = N <= 64;                    // 64-column tiles: no matrix work on columns that do not exist
-  const int tn = narrow ? 64 : 128;
-  p.tiles_n = (N + tn - 1) / tn;
-  // 128-row tiles, 64-byte k-steps.  Two other builds were measured in round 4 and removed from the library in round
-  // 5 (their template parameters with them): 64-row tiles (four blocks per CU: 3-10 % SLOWER on every
-  // base-model layer and flavour, profiles/r04/tile_rows_ab.jsonl) and 128-byte k-steps for the int8 chain's plain
-  // GEMMs (bit-identical, slower: a step costs 0.53 us whatever it holds, profiles/r04/tile_wide_ab.jsonl)
-  const int tm = kTM;
-  const long long tiles = (long long)p.tiles_n * ((M + tm - 1) / tm);
-  if (tiles > 0x3fffffffLL) return BEVOPS_NOT_SUPPORTED;
+  // 128-row tiles of 128 columns, or of 64 for N <= 64 (no matrix work on columns that do not exist), 64-byte k-steps.
+  // Two other builds were measured in round 4 and removed from the library in round 5 (their template parameters with
+  // them): 64-row tiles (four blocks per CU: 3-10 % SLOWER on every base-model layer and flavour,
+  // profiles/r04/tile_rows_ab.jsonl) and 128-byte k-steps for the int8 chain's plain GEMMs (bit-identical, slower: a
+  // step costs 0.53 us whatever it holds, profiles/r04/tile_wide_ab.jsonl)
+  const int tn = c.n <= 64 ? 64 : 128;
+  p.tiles_n = (c.n + tn - 1) / tn;
+  const long long tiles = (long long)p.tiles_n * ((c.m + kTM - 1) / kTM);
+  if (tiles > 0x3fffffffLL) return false;
   p.tiles_total = (int)tiles;
-  const dim3 grid((unsigned)((tiles + 7) / 8 * 8));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool conv = cg.cin > 0, out8 = out_dtype == BEVOPS_I8;
+  grid = dim3((unsigned)((tiles + 7) / 8 * 8));
+  return true;
+}
+
+template <int MODE>
+int launch_tile_gemm(const GemmCallS8 &c, const ConvGeom &cg = ConvGeom()) {
+  if (!c.x || !c.w || !c.out || c.m < 0 || c.n <= 0 || c.k <= 0) return BEVOPS_BAD_PARAM;
+  if (MODE != kF16 && (!(c.scale_a > 0.f) || (!c.w_scales && !(c.scale_w > 0.f)))) return BEVOPS_BAD_PARAM;
+  constexpr int kChunk = MODE == kF16 ? 8 : 16;   // k-values a staging thread handles per step
+  const bool res8 = c.res != nullptr && c.res_dtype == BEVOPS_I8, out8 = c.out_dtype == BEVOPS_I8, conv = cg.cin > 0;
+  if (c.res && c.res_dtype != BEVOPS_I8 && c.res_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  if (res8 && (MODE != kS8 || conv)) return BEVOPS_NOT_SUPPORTED;   // int8 identity rows: the int8-chain GEMM only
+  if (res8 && !(c.scale_res > 0.f)) return BEVOPS_BAD_PARAM;
+  if (c.k % kChunk != 0 || misaligned(c.x, 15u) || misaligned(c.w, 15u) || (c.res && misaligned(c.res, res8 ? 7u : 15u)) ||
+      misaligned(c.out, out8 ? 7u : 15u) || c.m > 0x7fffffffLL)
+    return BEVOPS_NOT_SUPPORTED;
+  if (out8 && (MODE == kF16 || !(c.scale_out > 0.f))) return BEVOPS_BAD_PARAM;
+  if (!out8 && c.out_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  // operands (and the identity) are addressed through 32-bit buffer offsets
+  const unsigned long long a_elems = conv ? (unsigned long long)cg.in_elems : (unsigned long long)c.m * c.k;
+  if (gemm_over_limit(a_elems, 1, MODE == kS8 ? 1 : 2) || gemm_over_limit(c.n, c.k, MODE == kF16 ? 2 : 1) ||
+      (c.res && gemm_over_limit(c.m, c.n, res8 ? 1 : 2)))
+    return BEVOPS_NOT_SUPPORTED;
+  if (c.m == 0) return BEVOPS_SUCCESS;
+  TileArgs p;
+  dim3 grid;
+  if (!tile_plan<MODE>(p, grid, c, cg, (unsigned)(a_elems * (MODE == kS8 ? 1 : 2)))) return BEVOPS_NOT_SUPPORTED;
+  const bool narrow = c.n <= 64;
 #define BEVOPS_TG(OUT8_, CONV_, RES8_)                                                                                 \
   do {                                                                                                                 \
-    if (narrow) hipLaunchKernelGGL((tile_gemm_kernel<MODE, OUT8_, 1, CONV_, RES8_>), grid, dim3(256), 0, st, p);      \
-    else hipLaunchKernelGGL((tile_gemm_kernel<MODE, OUT8_, 2, CONV_, RES8_>), grid, dim3(256), 0, st, p);             \
+    if (narrow) hipLaunchKernelGGL((tile_gemm_kernel<MODE, OUT8_, 1, CONV_, RES8_>), grid, dim3(256), 0, c.st, p);    \
+    else hipLaunchKernelGGL((tile_gemm_kernel<MODE, OUT8_, 2, CONV_, RES8_>), grid, dim3(256), 0, c.st, p);           \
     return launch_status();                                                                                            \
   } while (0)
   if constexpr (MODE == kF16) {
@@ -519,70 +516,15 @@ int launch_tile_gemm(const void *a, float scale_a, const void *w, const float *w
 #undef BEVOPS_TG
 }
 
-}  // namespace
-}  // namespace bevops
-
-using namespace bevops;
-
-extern "C" int bevops_linear_int8(const void *a_q, float scale_a, const void *w_q, const float *w_scales,
-                                  float scale_w, const float *bias, const void *residual, int out_dtype,
-                                  void *out, float scale_out, long long M, int N, int K, int relu, void *stream) {
-  return launch_tile_gemm<kS8>(a_q, scale_a, w_q, w_scales, scale_w, bias, residual, out_dtype, out, scale_out, M, N, K,
-                               relu, stream);
+// the int8 flavours' call: fp16 or int8 identity and output rows by their dtype codes
+GemmCallS8 tile_call_s8(const void *a, float scale_a, const void *w, const float *w_scales, float scale_w, const void *bias,
+                        const void *res, int res_dtype, float scale_res, int out_dtype, void *out, float scale_out,
+                        long long m, int n, int k, int relu, void *stream) {
+  return GemmCallS8{{a, w, bias, res, out, m, n, k, relu, static_cast<hipStream_t>(stream)},
+                    w_scales, scale_a, scale_w, scale_res, scale_out, res_dtype, out_dtype};
 }
 
-extern "C" int bevops_linear_int8_fused(const void *x_f16, float scale_a, const void *w_q, const float *w_scales,
-                                        float scale_w, const float *bias, const void *residual, int out_dtype,
-                                        void *out, float scale_out, long long M, int N, int K, int relu, void *stream) {
-  return launch_tile_gemm<kF16Q>(x_f16, scale_a, w_q, w_scales, scale_w, bias, residual, out_dtype, out, scale_out, M, N,
-                                 K, relu, stream);
-}
-
-extern "C" int bevops_tile_gemm_f16(const void *x, const void *weight, const void *bias, const void *residual,
-                                    void *out, long long M, int N, int K, int relu, void *stream) {
-  return launch_tile_gemm<kF16>(x, 1.f, weight, nullptr, 1.f, bias, residual, BEVOPS_F16, out, 1.f, M, N, K, relu, stream);
-}
-
-// bevops_tile_gemm_f16 with a destination table: column range [col_begin, col_end) of x @ weight.T + bias goes to the
-// pitched matrix `out` of its destination (column col_begin at out[m * out_pitch]), plus that destination's identity
-// rows (read with res_pitch).  Exactly the bytes the separate launches on weight[col_begin:col_end] write; columns
-// outside every range and the bytes between pitched rows are never written.
-extern "C" int bevops_tile_gemm_f16_dst(const void *x, const void *weight, const void *bias, const bevops_gemm_dst *dst,
-                                        int num_dst, long long M, int N, int K, int relu, void *stream) {
-  if (!x || !weight || !dst || M < 0 || N <= 0 || K <= 0 || num_dst <= 0) return BEVOPS_BAD_PARAM;
-  if (num_dst > kMaxDst || N <= 64 || N % 8 != 0) return BEVOPS_NOT_SUPPORTED;   // (N <= 64 is the 64-column flavour's)
-  if (K % 8 != 0 || !aligned16(x) || !aligned16(weight) || (bias && !aligned16(bias)) || M > 0x7fffffffLL) return BEVOPS_NOT_SUPPORTED;
-  if ((unsigned long long)M * K * 2 >= kOob || (unsigned long long)N * K * 2 >= kOob) return BEVOPS_NOT_SUPPORTED;
-  TileDstTab tab{};
-  tab.count = num_dst;
-  for (int i = 0; i < num_dst; ++i) {
-    const bevops_gemm_dst &e = dst[i];
-    const long long width = (long long)e.col_end - e.col_begin;
-    if (e.col_begin < 0 || e.col_end > N || width <= 0 || e.col_begin % 64 != 0 || e.col_end % 64 != 0) return BEVOPS_BAD_PARAM;
-    if (!e.out || !aligned16(e.out) || e.out_pitch < width || e.out_pitch % 8 != 0 || e.out_pitch > 0x7fffffffLL) return BEVOPS_BAD_PARAM;
-    if (e.res && (!aligned16(e.res) || e.res_pitch < width || e.res_pitch % 8 != 0 || e.res_pitch > 0x7fffffffLL)) return BEVOPS_BAD_PARAM;
-    if (e.res && (unsigned long long)M * (unsigned long long)e.res_pitch * 2 >= kOob) return BEVOPS_NOT_SUPPORTED;
-    for (int j = 0; j < i; ++j)
-      if (e.col_begin < dst[j].col_end && dst[j].col_begin < e.col_end) return BEVOPS_BAD_PARAM;   // overlapping ranges
-    tab.e[i] = TileDst{e.col_begin, e.col_end, static_cast<__half *>(e.out), static_cast<const __half *>(e.res),
-                       (int)e.out_pitch, e.res ? (int)e.res_pitch : 0};
-  }
-  if (M == 0) return BEVOPS_SUCCESS;
-  TileArgs p{};
-  p.a = x; p.w = weight; p.bias = bias;
-  p.inv_sa = 1.f; p.s_aw = 1.f; p.s_res = 1.f;
-  p.M = (int)M; p.N = N; p.K = K; p.relu = relu;
-  p.a_bytes = (unsigned)((unsigned long long)M * K * 2);
-  p.conv_s = 1; p.conv_ks = 1;
-  p.tiles_n = (N + 127) / 128;
-  const long long tiles = (long long)p.tiles_n * ((M + kTM - 1) / kTM);
-  if (tiles > 0x3fffffffLL) return BEVOPS_NOT_SUPPORTED;
-  p.tiles_total = (int)tiles;
-  hipLaunchKernelGGL(tile_gemm_dst_kernel, dim3((unsigned)((tiles + 7) / 8 * 8)), dim3(256), 0, static_cast<hipStream_t>(stream), p, tab);
-  return launch_status();
-}
-
-static int conv_geometry(ConvGeom &cg, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int step_k) {
+int conv_geometry(ConvGeom &cg, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int step_k) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || stride <= 0) return BEVOPS_BAD_PARAM;
   if ((ksize != 1 && ksize != 3) || Cin % step_k != 0) return BEVOPS_NOT_SUPPORTED;   // a k-step must not straddle two taps
   cg.cin = Cin; cg.hin = H; cg.win = W; cg.stride = stride; cg.ks = ksize;
@@ -593,6 +535,53 @@ static int conv_geometry(ConvGeom &cg, int B, int H, int W, int Cin, int Cout, i
   return BEVOPS_SUCCESS;
 }
 
+}  // namespace
+}  // namespace bevops
+
+using namespace bevops;
+
+extern "C" int bevops_linear_int8(const void *a_q, float scale_a, const void *w_q, const float *w_scales,
+                                  float scale_w, const float *bias, const void *residual, int out_dtype,
+                                  void *out, float scale_out, long long M, int N, int K, int relu, void *stream) {
+  return launch_tile_gemm<kS8>(tile_call_s8(a_q, scale_a, w_q, w_scales, scale_w, bias, residual, BEVOPS_F16, 1.f, out_dtype,
+                                            out, scale_out, M, N, K, relu, stream));
+}
+
+extern "C" int bevops_linear_int8_fused(const void *x_f16, float scale_a, const void *w_q, const float *w_scales,
+                                        float scale_w, const float *bias, const void *residual, int out_dtype,
+                                        void *out, float scale_out, long long M, int N, int K, int relu, void *stream) {
+  return launch_tile_gemm<kF16Q>(tile_call_s8(x_f16, scale_a, w_q, w_scales, scale_w, bias, residual, BEVOPS_F16, 1.f,
+                                              out_dtype, out, scale_out, M, N, K, relu, stream));
+}
+
+extern "C" int bevops_tile_gemm_f16(const void *x, const void *weight, const void *bias, const void *residual,
+                                    void *out, long long M, int N, int K, int relu, void *stream) {
+  return launch_tile_gemm<kF16>(gemm_call_f16(x, weight, bias, residual, out, M, N, K, relu, stream));
+}
+
+// bevops_tile_gemm_f16 with a destination table: column range [col_begin, col_end) of x @ weight.T + bias goes to the
+// pitched matrix `out` of its destination (column col_begin at out[m * out_pitch]), plus that destination's identity
+// rows (read with res_pitch).  Exactly the bytes the separate launches on weight[col_begin:col_end] write; columns
+// outside every range and the bytes between pitched rows are never written.
+extern "C" int bevops_tile_gemm_f16_dst(const void *x, const void *weight, const void *bias, const bevops_gemm_dst *dst,
+                                        int num_dst, long long M, int N, int K, int relu, void *stream) {
+  const GemmCallS8 c = gemm_call_f16(x, weight, bias, nullptr, nullptr, M, N, K, relu, stream);
+  if (!x || !weight || !dst || M < 0 || N <= 0 || K <= 0 || num_dst <= 0) return BEVOPS_BAD_PARAM;
+  if (num_dst > kGemmMaxDst || N <= 64 || N % 8 != 0) return BEVOPS_NOT_SUPPORTED;   // (N <= 64 is the 64-column flavour's)
+  if (K % 8 != 0 || misaligned(x, 15u) || misaligned(weight, 15u) || (bias && misaligned(bias, 15u)) || M > 0x7fffffffLL)
+    return BEVOPS_NOT_SUPPORTED;
+  if (gemm_over_limit(M, K, 2) || gemm_over_limit(N, K, 2)) return BEVOPS_NOT_SUPPORTED;
+  GemmDstTab tab;
+  const int rc = gemm_dst_table(tab, dst, num_dst, M, N, 64, true);
+  if (rc != BEVOPS_SUCCESS) return rc;
+  if (M == 0) return BEVOPS_SUCCESS;
+  TileArgs p;
+  dim3 grid;
+  if (!tile_plan<kF16>(p, grid, c, ConvGeom(), (unsigned)((unsigned long long)M * K * 2))) return BEVOPS_NOT_SUPPORTED;
+  hipLaunchKernelGGL(tile_gemm_dst_kernel, grid, dim3(256), 0, c.st, p, tab);
+  return launch_status();
+}
+
 extern "C" int bevops_conv_tile_int8_fused(const void *x_f16, float scale_a, const void *w_q_taps, const float *w_scales,
                                            float scale_w, const float *bias, const void *residual, void *out, int B,
                                            int H, int W, int Cin, int Cout, int ksize, int stride, int relu,
@@ -600,8 +589,9 @@ extern "C" int bevops_conv_tile_int8_fused(const void *x_f16, float scale_a, con
   ConvGeom cg;
   const int rc = conv_geometry(cg, B, H, W, Cin, Cout, ksize, stride, 64);
   if (rc != BEVOPS_SUCCESS) return rc;
-  return launch_tile_gemm<kF16Q>(x_f16, scale_a, w_q_taps, w_scales, scale_w, bias, residual, BEVOPS_F16, out, 1.f,
-                                 (long long)B * cg.hout * cg.wout, Cout, ksize * ksize * Cin, relu, stream, cg);
+  return launch_tile_gemm<kF16Q>(tile_call_s8(x_f16, scale_a, w_q_taps, w_scales, scale_w, bias, residual, BEVOPS_F16, 1.f,
+                                              BEVOPS_F16, out, 1.f, (long long)B * cg.hout * cg.wout, Cout,
+                                              ksize * ksize * Cin, relu, stream), cg);
 }
 
 extern "C" int bevops_conv_tile_f16(const void *x, const void *weight_taps, const void *bias, const void *residual,
@@ -610,21 +600,20 @@ extern "C" int bevops_conv_tile_f16(const void *x, const void *weight_taps, cons
   ConvGeom cg;
   const int rc = conv_geometry(cg, B, H, W, Cin, Cout, ksize, stride, 32);
   if (rc != BEVOPS_SUCCESS) return rc;
-  return launch_tile_gemm<kF16>(x, 1.f, weight_taps, nullptr, 1.f, bias, residual, BEVOPS_F16, out, 1.f,
-                                (long long)B * cg.hout * cg.wout, Cout, ksize * ksize * Cin, relu, stream, cg);
+  return launch_tile_gemm<kF16>(gemm_call_f16(x, weight_taps, bias, residual, out, (long long)B * cg.hout * cg.wout, Cout,
+                                              ksize * ksize * Cin, relu, stream), cg);
 }
 
 extern "C" int bevops_linear_int8_chain(const void *a, int a_dtype, float scale_a, const void *w_q, const float *w_scales,
                                         float scale_w, const float *bias, const void *residual, int res_dtype,
                                         float scale_res, int out_dtype, void *out, float scale_out, long long M, int N,
                                         int K, int relu, void *stream) {
-  if (a_dtype == BEVOPS_I8)
-    return launch_tile_gemm<kS8>(a, scale_a, w_q, w_scales, scale_w, bias, residual, out_dtype, out, scale_out, M, N, K,
-                                 relu, stream, ConvGeom(), res_dtype, scale_res);
+  const GemmCallS8 c = tile_call_s8(a, scale_a, w_q, w_scales, scale_w, bias, residual, res_dtype, scale_res, out_dtype, out,
+                                    scale_out, M, N, K, relu, stream);
+  if (a_dtype == BEVOPS_I8) return launch_tile_gemm<kS8>(c);
   if (a_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
   if (residual && res_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-  return launch_tile_gemm<kF16Q>(a, scale_a, w_q, w_scales, scale_w, bias, residual, out_dtype, out, scale_out, M, N, K,
-                                 relu, stream);
+  return launch_tile_gemm<kF16Q>(c);
 }
 
 extern "C" int bevops_conv_tile_int8(const void *x_q, float scale_a, const void *w_q_taps, const float *w_scales,
@@ -634,6 +623,7 @@ extern "C" int bevops_conv_tile_int8(const void *x_q, float scale_a, const void 
   ConvGeom cg;
   const int rc = conv_geometry(cg, B, H, W, Cin, Cout, ksize, stride, 64);
   if (rc != BEVOPS_SUCCESS) return rc;
-  return launch_tile_gemm<kS8>(x_q, scale_a, w_q_taps, w_scales, scale_w, bias, residual, out_dtype, out, scale_out,
-                               (long long)B * cg.hout * cg.wout, Cout, ksize * ksize * Cin, relu, stream, cg);
+  return launch_tile_gemm<kS8>(tile_call_s8(x_q, scale_a, w_q_taps, w_scales, scale_w, bias, residual, BEVOPS_F16, 1.f,
+                                            out_dtype, out, scale_out, (long long)B * cg.hout * cg.wout, Cout,
+                                            ksize * ksize * Cin, relu, stream), cg);
 }

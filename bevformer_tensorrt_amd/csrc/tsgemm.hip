@@ -27,7 +27,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_host.h"
 #include "mdconv.h"
 #include "msda_pad.h"
 
@@ -1109,14 +1109,13 @@ const bool g_ts_env_old = [] {
 inline bool ts_use_ws(int k) { return k <= 256 && g_ts_variant != 1 && !g_ts_env_old; }
 
 template <int EPI, int KS, bool GRP = false>
-int ws_launch_ks(const void *x, const void *w, const void *bias, const void *res, void *out, long long m, int n, int relu,
-                 const TsPacked &pk, hipStream_t st) {
+int ws_launch_ks(const GemmCall &c, const TsPacked &pk) {
   if constexpr (GRP) {
     if (!ensure_dynamic_lds<tsgemm_ws_grouped_kernel<KS>>(ws_lds(KS))) return BEVOPS_FAILURE;
   } else {
     if (!ensure_dynamic_lds<tsgemm_ws_kernel<EPI, KS>>(ws_lds(KS))) return BEVOPS_FAILURE;
   }
-  const int units = (int)((m + 31) / 32), chunks = n / kTsBN;
+  const int units = (int)((c.m + 31) / 32), chunks = c.n / kTsBN;
   const int cus = ts_grid_x(1 << 30, chunks);
   int parts = cus / chunks;
   if (parts < 1) parts = 1;
@@ -1125,25 +1124,77 @@ int ws_launch_ks(const void *x, const void *w, const void *bias, const void *res
   if (GRP && parts >= 8) parts -= parts % 8;
   if (parts > units) parts = units;
   if constexpr (GRP)
-    hipLaunchKernelGGL((tsgemm_ws_grouped_kernel<KS>), dim3((unsigned)(parts * chunks)), dim3(kTsThreads), ws_lds(KS), st,
-                       (const __half *)x, (const __half *)w, (const __half *)bias, (__half *)out, (int)m, n, units, parts,
-                       chunks, pk);
+    hipLaunchKernelGGL((tsgemm_ws_grouped_kernel<KS>), dim3((unsigned)(parts * chunks)), dim3(kTsThreads), ws_lds(KS), c.st,
+                       (const __half *)c.x, (const __half *)c.w, (const __half *)c.bias, (__half *)c.out, (int)c.m, c.n,
+                       units, parts, chunks, pk);
   else
-    hipLaunchKernelGGL((tsgemm_ws_kernel<EPI, KS>), dim3((unsigned)(parts * chunks)), dim3(kTsThreads), ws_lds(KS), st,
-                       (const __half *)x, (const __half *)w, (const __half *)bias, (const __half *)res, (__half *)out, (int)m,
-                       n, relu, units, parts, chunks, pk);
+    hipLaunchKernelGGL((tsgemm_ws_kernel<EPI, KS>), dim3((unsigned)(parts * chunks)), dim3(kTsThreads), ws_lds(KS), c.st,
+                       (const __half *)c.x, (const __half *)c.w, (const __half *)c.bias, (const __half *)c.res,
+                       (__half *)c.out, (int)c.m, c.n, c.relu, units, parts, chunks, pk);
   return launch_status();
 }
 
+// The launch of the three fp16 entries after their checks: the weight-stationary kernel inside its domain (K <= 256),
+// else tsgemm_f16_kernel<EPI>, one persistent block per CU and 256-column chunk.
 template <int EPI>
-int ws_launch(const void *x, const void *w, const void *bias, const void *res, void *out, long long m, int n, int k,
-              int relu, const TsPacked &pk, hipStream_t st) {
-  switch (k / 64) {
-    case 1: return ws_launch_ks<EPI, 1>(x, w, bias, res, out, m, n, relu, pk, st);
-    case 2: return ws_launch_ks<EPI, 2>(x, w, bias, res, out, m, n, relu, pk, st);
-    case 3: return ws_launch_ks<EPI, 3>(x, w, bias, res, out, m, n, relu, pk, st);
-    default: return ws_launch_ks<EPI, 4>(x, w, bias, res, out, m, n, relu, pk, st);
+int ts_launch_f16(const GemmCall &c, const TsPacked &pk) {
+  if (ts_use_ws(c.k)) {
+    if constexpr (EPI == 1) return ws_launch_ks<1, 4>(c, pk);   // the value projection is 256 -> 256: the one KS built for it
+    else return gemm_k64<4>(c.k / 64, [&](auto ks) { return ws_launch_ks<EPI, decltype(ks)::value>(c, pk); });
   }
+  if (!ensure_dynamic_lds<tsgemm_f16_kernel<EPI>>(kTsLds)) return BEVOPS_FAILURE;
+  const int units = (int)((c.m + 31) / 32);
+  const dim3 grid((unsigned)ts_grid_x(units, c.n / kTsBN), (unsigned)(c.n / kTsBN));
+  hipLaunchKernelGGL(tsgemm_f16_kernel<EPI>, grid, dim3(kTsThreads), kTsLds, c.st, (const __half *)c.x, (const __half *)c.w,
+                     (const __half *)c.bias, (const __half *)c.res, (__half *)c.out, (int)c.m, c.n, c.k, c.relu, units, pk);
+  return launch_status();
+}
+
+// what the three fp16 entries ask of the shared operands, after their null / sign checks (`w_limit`: the weight's byte
+// range too; the one-chunk entries never asked)
+int ts_f16_check(const GemmCall &c, bool w_limit) {
+  if (c.m > 0x7fffffff || gemm_over_limit(c.m, c.k, 2) || (w_limit && gemm_over_limit(c.n, c.k, 2))) return BEVOPS_NOT_SUPPORTED;
+  if (misaligned(c.x, 15u) || misaligned(c.w, 15u) || misaligned(c.out, 15u) || (c.bias && misaligned(c.bias, 15u)) ||
+      (c.res && misaligned(c.res, 15u)))
+    return BEVOPS_BAD_PARAM;
+  return BEVOPS_SUCCESS;
+}
+
+// The checks bevops_tsgemm_s8 and _s8_ln share (`one_chunk`: N == 256 instead of N % 256 == 0, and the weight's byte
+// range is not asked), after the entry's null / sign checks.
+int ts_s8_check(const GemmCallS8 &c, bool one_chunk) {
+  const bool res8 = c.res && c.res_dtype == BEVOPS_I8, out8 = c.out_dtype == BEVOPS_I8;
+  if (!(c.scale_a > 0.f) || (!c.w_scales && !(c.scale_w > 0.f))) return BEVOPS_BAD_PARAM;
+  if (c.k % 128 != 0 || (one_chunk ? c.n != kTsBN : c.n % kTsBN != 0)) return BEVOPS_NOT_SUPPORTED;
+  if (!out8 && c.out_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  if (c.res && !res8 && c.res_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  if (out8 && !(c.scale_out > 0.f)) return BEVOPS_BAD_PARAM;
+  if (res8 && !(c.scale_res > 0.f)) return BEVOPS_BAD_PARAM;
+  if (c.m > 0x7fffffff || gemm_over_limit(c.m, c.k, 1) || (!one_chunk && gemm_over_limit(c.n, c.k, 1))) return BEVOPS_NOT_SUPPORTED;
+  if (misaligned(c.x, 15u) || misaligned(c.w, 15u) || misaligned(c.out, out8 ? 7u : 15u) ||
+      (c.res && misaligned(c.res, res8 ? 7u : 15u)) || (c.bias && misaligned(c.bias, 3u)) ||
+      (c.w_scales && misaligned(c.w_scales, 3u)))
+    return BEVOPS_BAD_PARAM;
+  return BEVOPS_SUCCESS;
+}
+
+void ts_s8_fill(TsS8Args &p, const GemmCallS8 &c) {
+  p.a = static_cast<const int8_t *>(c.x); p.w = static_cast<const int8_t *>(c.w);
+  p.bias = static_cast<const float *>(c.bias); p.wscale = c.w_scales; p.res = c.res; p.out = c.out;
+  p.s_aw = c.w_scales ? c.scale_a : c.scale_a * c.scale_w;
+  p.s_res = c.scale_res;
+  p.inv_s_out = c.out_dtype == BEVOPS_I8 ? 1.0f / c.scale_out : 0.f;
+  p.M = (int)c.m; p.N = c.n; p.K = c.k; p.relu = c.relu; p.units_total = (int)((c.m + 31) / 32);
+  p.res_i8 = c.res && c.res_dtype == BEVOPS_I8 ? 1 : 0;
+  p.out_i8 = c.out_dtype == BEVOPS_I8 ? 1 : 0;
+}
+
+TsPacked ts_ln_params(const void *ln_weight, const void *ln_bias, float eps) {
+  TsPacked pk{};
+  pk.gset = const_cast<char *>(static_cast<const char *>(ln_weight));
+  pk.sset = const_cast<char *>(static_cast<const char *>(ln_bias));
+  pk.eps = eps;
+  return pk;
 }
 
 }  // namespace
@@ -1166,21 +1217,11 @@ extern "C" int bevops_tsgemm_tile_rows(int k) {
 
 extern "C" int bevops_tsgemm_f16(const void *x, const void *weight, const void *bias, const void *residual,
                                  void *out, long long m, int n, int k, int relu, void *stream) {
+  const GemmCall c{x, weight, bias, residual, out, m, n, k, relu, static_cast<hipStream_t>(stream)};
   if (!x || !weight || !out || m <= 0 || n <= 0 || k <= 0) return BEVOPS_BAD_PARAM;
   if (k % 64 != 0 || n % kTsBN != 0) return BEVOPS_NOT_SUPPORTED;
-  if ((double)m * k * 2 >= 4294967040.0 || (double)n * k * 2 >= 4294967040.0 || m > 0x7fffffff) return BEVOPS_NOT_SUPPORTED;
-  if (!aligned16(x) || !aligned16(weight) || !aligned16(out) || (bias && !aligned16(bias)) ||
-      (residual && !aligned16(residual)))
-    return BEVOPS_BAD_PARAM;
-  if (ts_use_ws(k)) return ws_launch<0>(x, weight, bias, residual, out, m, n, k, relu, TsPacked{}, static_cast<hipStream_t>(stream));
-  if (!ensure_dynamic_lds<tsgemm_f16_kernel<0>>(kTsLds)) return BEVOPS_FAILURE;
-  const int units = (int)((m + 31) / 32);
-  const dim3 grid((unsigned)ts_grid_x(units, n / kTsBN), (unsigned)(n / kTsBN));
-  TsPacked none{};
-  hipLaunchKernelGGL(tsgemm_f16_kernel<0>, grid, dim3(kTsThreads), kTsLds, static_cast<hipStream_t>(stream),
-                     (const __half *)x, (const __half *)weight, (const __half *)bias, (const __half *)residual,
-                     (__half *)out, (int)m, n, k, relu, units, none);
-  return launch_status();
+  const int rc = ts_f16_check(c, true);
+  return rc != BEVOPS_SUCCESS ? rc : ts_launch_f16<0>(c, TsPacked{});
 }
 
 // G dense layers of 256 columns over the SAME rows as one launch: out + g * group_stride (elements) receives the dense
@@ -1191,28 +1232,22 @@ extern "C" int bevops_tsgemm_f16_grouped(const void *x, const void *weight, cons
                                          long long group_stride, long long m, int groups, int k, void *stream) {
   if (!x || !weight || !out || m <= 0 || groups <= 0 || k <= 0) return BEVOPS_BAD_PARAM;
   if (k % 64 != 0 || k > 256 || groups > 64) return BEVOPS_NOT_SUPPORTED;
-  if ((double)m * k * 2 >= 4294967040.0 || m > 0x7fffffff) return BEVOPS_NOT_SUPPORTED;
-  if (!aligned16(x) || !aligned16(weight) || !aligned16(out) || (bias && !aligned16(bias))) return BEVOPS_BAD_PARAM;
+  const GemmCall c{x, weight, bias, nullptr, out, m, groups * kTsBN, k, 0, static_cast<hipStream_t>(stream)};
+  const int rc = ts_f16_check(c, false);
+  if (rc != BEVOPS_SUCCESS) return rc;
   if (group_stride < m * kTsBN || group_stride % 8 != 0) return BEVOPS_BAD_PARAM;   // the G outputs would overlap / lose alignment
-  hipStream_t st = static_cast<hipStream_t>(stream);
   if (!ts_use_ws(k)) {   // the A/B variant: the G launches themselves
     for (int g = 0; g < groups; ++g) {
-      const int rc = bevops_tsgemm_f16(x, static_cast<const __half *>(weight) + (size_t)g * kTsBN * k,
-                                       bias ? static_cast<const __half *>(bias) + (size_t)g * kTsBN : nullptr, nullptr,
-                                       static_cast<__half *>(out) + (size_t)g * (size_t)group_stride, m, kTsBN, k, 0, stream);
-      if (rc != BEVOPS_SUCCESS) return rc;
+      const int rc_g = bevops_tsgemm_f16(x, static_cast<const __half *>(weight) + (size_t)g * kTsBN * k,
+                                         bias ? static_cast<const __half *>(bias) + (size_t)g * kTsBN : nullptr, nullptr,
+                                         static_cast<__half *>(out) + (size_t)g * (size_t)group_stride, m, kTsBN, k, 0, stream);
+      if (rc_g != BEVOPS_SUCCESS) return rc_g;
     }
     return BEVOPS_SUCCESS;
   }
   TsPacked pk{};
   pk.gstride = group_stride;
-  const int n = groups * kTsBN;
-  switch (k / 64) {
-    case 1: return ws_launch_ks<0, 1, true>(x, weight, bias, nullptr, out, m, n, 0, pk, st);
-    case 2: return ws_launch_ks<0, 2, true>(x, weight, bias, nullptr, out, m, n, 0, pk, st);
-    case 3: return ws_launch_ks<0, 3, true>(x, weight, bias, nullptr, out, m, n, 0, pk, st);
-    default: return ws_launch_ks<0, 4, true>(x, weight, bias, nullptr, out, m, n, 0, pk, st);
-  }
+  return gemm_k64<4>(k / 64, [&](auto ks) { return ws_launch_ks<0, decltype(ks)::value, true>(c, pk); });
 }
 
 // out = LayerNorm_256(fp16(x @ weight.T + bias + residual)) * ln_weight + ln_bias in ONE launch (EPI 2 above).
@@ -1220,24 +1255,13 @@ extern "C" int bevops_tsgemm_f16_grouped(const void *x, const void *weight, cons
 extern "C" int bevops_tsgemm_f16_ln(const void *x, const void *weight, const void *bias, const void *residual,
                                     const void *ln_weight, const void *ln_bias, float eps, void *out, long long m, int n,
                                     int k, void *stream) {
+  const GemmCall c{x, weight, bias, residual, out, m, n, k, 0, static_cast<hipStream_t>(stream)};
   if (!x || !weight || !out || !ln_weight || !ln_bias || m <= 0 || n <= 0 || k <= 0 || !(eps >= 0.f)) return BEVOPS_BAD_PARAM;
   if (k % 64 != 0 || n != kTsBN) return BEVOPS_NOT_SUPPORTED;
-  if ((double)m * k * 2 >= 4294967040.0 || m > 0x7fffffff) return BEVOPS_NOT_SUPPORTED;
-  if (!aligned16(x) || !aligned16(weight) || !aligned16(out) || (bias && !aligned16(bias)) ||
-      (residual && !aligned16(residual)) || !aligned16(ln_weight) || !aligned16(ln_bias))
-    return BEVOPS_BAD_PARAM;
-  TsPacked pk{};
-  pk.gset = const_cast<char *>(static_cast<const char *>(ln_weight));
-  pk.sset = const_cast<char *>(static_cast<const char *>(ln_bias));
-  pk.eps = eps;
-  if (ts_use_ws(k)) return ws_launch<2>(x, weight, bias, residual, out, m, n, k, 0, pk, static_cast<hipStream_t>(stream));
-  if (!ensure_dynamic_lds<tsgemm_f16_kernel<2>>(kTsLds)) return BEVOPS_FAILURE;
-  const int units = (int)((m + 31) / 32);
-  const dim3 grid((unsigned)ts_grid_x(units, 1), 1u);
-  hipLaunchKernelGGL(tsgemm_f16_kernel<2>, grid, dim3(kTsThreads), kTsLds, static_cast<hipStream_t>(stream),
-                     (const __half *)x, (const __half *)weight, (const __half *)bias, (const __half *)residual,
-                     (__half *)out, (int)m, n, k, 0, units, pk);
-  return launch_status();
+  const int rc = ts_f16_check(c, false);
+  if (rc != BEVOPS_SUCCESS) return rc;
+  if (misaligned(ln_weight, 15u) || misaligned(ln_bias, 15u)) return BEVOPS_BAD_PARAM;
+  return ts_launch_f16<2>(c, ts_ln_params(ln_weight, ln_bias, eps));
 }
 
 // int8 chain flavour of the persistent tall-skinny GEMM (see tsgemm_s8_kernel).  a_q [M, K] / w_q [N, K] int8;
@@ -1247,31 +1271,16 @@ extern "C" int bevops_tsgemm_f16_ln(const void *x, const void *weight, const voi
 extern "C" int bevops_tsgemm_s8(const void *a_q, float scale_a, const void *w_q, const float *w_scales, float scale_w,
                                 const float *bias, const void *residual, int res_dtype, float scale_res, int out_dtype,
                                 void *out, float scale_out, long long m, int n, int k, int relu, void *stream) {
+  const GemmCallS8 c{{a_q, w_q, bias, residual, out, m, n, k, relu, static_cast<hipStream_t>(stream)},
+                     w_scales, scale_a, scale_w, scale_res, scale_out, res_dtype, out_dtype};
   if (!a_q || !w_q || !out || m <= 0 || n <= 0 || k <= 0) return BEVOPS_BAD_PARAM;
-  if (!(scale_a > 0.f) || (!w_scales && !(scale_w > 0.f))) return BEVOPS_BAD_PARAM;
-  if (k % 128 != 0 || n % kTsBN != 0) return BEVOPS_NOT_SUPPORTED;
-  if (out_dtype != BEVOPS_I8 && out_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-  if (residual && res_dtype != BEVOPS_I8 && res_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-  if (out_dtype == BEVOPS_I8 && !(scale_out > 0.f)) return BEVOPS_BAD_PARAM;
-  if (residual && res_dtype == BEVOPS_I8 && !(scale_res > 0.f)) return BEVOPS_BAD_PARAM;
-  if ((double)m * k >= 4294967040.0 || (double)n * k >= 4294967040.0 || m > 0x7fffffff) return BEVOPS_NOT_SUPPORTED;
-  if (!aligned16(a_q) || !aligned16(w_q) || (reinterpret_cast<uintptr_t>(out) & (out_dtype == BEVOPS_I8 ? 7u : 15u)) ||
-      (residual && (reinterpret_cast<uintptr_t>(residual) & (res_dtype == BEVOPS_I8 ? 7u : 15u))) ||
-      (bias && (reinterpret_cast<uintptr_t>(bias) & 3u)) || (w_scales && (reinterpret_cast<uintptr_t>(w_scales) & 3u)))
-    return BEVOPS_BAD_PARAM;
+  const int rc = ts_s8_check(c, false);
+  if (rc != BEVOPS_SUCCESS) return rc;
   if (!ensure_dynamic_lds<tsgemm_s8_kernel<0>>(kTsLds)) return BEVOPS_FAILURE;
-  const int units = (int)((m + 31) / 32);
-  const dim3 grid((unsigned)ts_grid_x(units, n / kTsBN), (unsigned)(n / kTsBN));
   TsS8Args p;
-  p.a = static_cast<const int8_t *>(a_q); p.w = static_cast<const int8_t *>(w_q);
-  p.bias = bias; p.wscale = w_scales; p.res = residual; p.out = out;
-  p.s_aw = w_scales ? scale_a : scale_a * scale_w;
-  p.s_res = scale_res;
-  p.inv_s_out = out_dtype == BEVOPS_I8 ? 1.0f / scale_out : 0.f;
-  p.M = (int)m; p.N = n; p.K = k; p.relu = relu; p.units_total = units;
-  p.res_i8 = residual && res_dtype == BEVOPS_I8 ? 1 : 0;
-  p.out_i8 = out_dtype == BEVOPS_I8 ? 1 : 0;
-  hipLaunchKernelGGL(tsgemm_s8_kernel<0>, grid, dim3(kTsThreads), kTsLds, static_cast<hipStream_t>(stream), p);
+  ts_s8_fill(p, c);
+  const dim3 grid((unsigned)ts_grid_x(p.units_total, n / kTsBN), (unsigned)(n / kTsBN));
+  hipLaunchKernelGGL(tsgemm_s8_kernel<0>, grid, dim3(kTsThreads), kTsLds, c.st, p);
   return launch_status();
 }
 
@@ -1281,30 +1290,17 @@ extern "C" int bevops_tsgemm_s8_ln(const void *a_q, float scale_a, const void *w
                                    const float *bias, const void *residual, int res_dtype, float scale_res,
                                    const void *ln_weight, const void *ln_bias, float eps, void *out, long long m, int n,
                                    int k, void *stream) {
+  const GemmCallS8 c{{a_q, w_q, bias, residual, out, m, n, k, 0, static_cast<hipStream_t>(stream)},
+                     w_scales, scale_a, scale_w, scale_res, 1.f, res_dtype, BEVOPS_F16};
   if (!a_q || !w_q || !out || !ln_weight || !ln_bias || m <= 0 || n <= 0 || k <= 0 || !(eps >= 0.f)) return BEVOPS_BAD_PARAM;
-  if (!(scale_a > 0.f) || (!w_scales && !(scale_w > 0.f))) return BEVOPS_BAD_PARAM;
-  if (k % 128 != 0 || n != kTsBN) return BEVOPS_NOT_SUPPORTED;
-  if (residual && res_dtype != BEVOPS_I8 && res_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-  if (residual && res_dtype == BEVOPS_I8 && !(scale_res > 0.f)) return BEVOPS_BAD_PARAM;
-  if ((double)m * k >= 4294967040.0 || m > 0x7fffffff) return BEVOPS_NOT_SUPPORTED;
-  if (!aligned16(a_q) || !aligned16(w_q) || !aligned16(out) || !aligned16(ln_weight) || !aligned16(ln_bias) ||
-      (residual && (reinterpret_cast<uintptr_t>(residual) & (res_dtype == BEVOPS_I8 ? 7u : 15u))) ||
-      (bias && (reinterpret_cast<uintptr_t>(bias) & 3u)) || (w_scales && (reinterpret_cast<uintptr_t>(w_scales) & 3u)))
-    return BEVOPS_BAD_PARAM;
+  const int rc = ts_s8_check(c, true);
+  if (rc != BEVOPS_SUCCESS) return rc;
+  if (misaligned(ln_weight, 15u) || misaligned(ln_bias, 15u)) return BEVOPS_BAD_PARAM;
   if (!ensure_dynamic_lds<tsgemm_s8_kernel<2>>(kTsS8LnLds)) return BEVOPS_FAILURE;
-  const int units = (int)((m + 31) / 32);
-  const dim3 grid((unsigned)ts_grid_x(units, 1), 1u);
   TsS8LnArgs p{};
-  p.a = static_cast<const int8_t *>(a_q); p.w = static_cast<const int8_t *>(w_q);
-  p.bias = bias; p.wscale = w_scales; p.res = residual; p.out = out;
-  p.s_aw = w_scales ? scale_a : scale_a * scale_w;
-  p.s_res = scale_res;
-  p.M = (int)m; p.N = n; p.K = k; p.units_total = units;
-  p.res_i8 = residual && res_dtype == BEVOPS_I8 ? 1 : 0;
-  p.pk.gset = const_cast<char *>(static_cast<const char *>(ln_weight));
-  p.pk.sset = const_cast<char *>(static_cast<const char *>(ln_bias));
-  p.pk.eps = eps;
-  hipLaunchKernelGGL(tsgemm_s8_kernel<2>, grid, dim3(kTsThreads), kTsS8LnLds, static_cast<hipStream_t>(stream), p);
+  ts_s8_fill(p, c);
+  p.pk = ts_ln_params(ln_weight, ln_bias, eps);
+  hipLaunchKernelGGL(tsgemm_s8_kernel<2>, dim3((unsigned)ts_grid_x(p.units_total, 1)), dim3(kTsThreads), kTsS8LnLds, c.st, p);
   return launch_status();
 }
 
@@ -1320,7 +1316,7 @@ extern "C" size_t bevops_value_proj_packed_size(const int32_t *spatial_shapes_ho
   Hm3Tab tab;
   size_t g_room = 0, s_bytes = 0;
   if (!msda_hm5_layout(d, spatial_shapes_host, &tab, &g_room, &s_bytes)) return 0;
-  if ((double)num_cams * nk * heads * channels * 2 >= 4294967040.0) return 0;
+  if (gemm_over_limit((unsigned long long)num_cams * nk, heads * channels, 2)) return 0;
   return msda_hm5_workspace_bytes(d, spatial_shapes_host);
 }
 
@@ -1338,24 +1334,17 @@ extern "C" int bevops_value_proj_packed(const void *x, const void *weight, const
   const MsdaDims d{num_cams, nk, heads, channels, num_levels, num_query, num_point, 4, 1};
   if (!msda_hm5_layout(d, spatial_shapes_host, &pk.t, &g_room, &s_bytes))
     return BEVOPS_NOT_SUPPORTED;
-  if (packed_bytes < g_room + s_bytes || (reinterpret_cast<uintptr_t>(packed) & 127u)) return BEVOPS_BAD_PARAM;
-  const int n = heads * channels, k = n;   // embed -> embed
-  const long long m = (long long)num_cams * nk;
-  if ((double)m * k * 2 >= 4294967040.0) return BEVOPS_NOT_SUPPORTED;
-  if (!aligned16(x) || !aligned16(weight) || (bias && !aligned16(bias))) return BEVOPS_BAD_PARAM;
+  if (packed_bytes < g_room + s_bytes || misaligned(packed, 127u)) return BEVOPS_BAD_PARAM;
+  const int n = heads * channels;   // embed -> embed: K == N
+  const GemmCall c{x, weight, bias, nullptr, nullptr, (long long)num_cams * nk, n, n, 0, static_cast<hipStream_t>(stream)};
+  const int rc = ts_f16_check(c, false);
+  if (rc != BEVOPS_SUCCESS) return rc;
   pk.gset = static_cast<char *>(packed);
   pk.sset = pk.gset + g_room;
   pk.nk = nk;
   pk.heads = heads;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(tsgemm_pad_zero_kernel, dim3(4, (unsigned)(num_cams * heads)), dim3(256), 0, st, pk, num_cams * heads);
-  if (ts_use_ws(k)) return ws_launch_ks<1, 4>(x, weight, bias, nullptr, nullptr, m, n, 0, pk, st);   // K == N == 256 here
-  if (!ensure_dynamic_lds<tsgemm_f16_kernel<1>>(kTsLds)) return BEVOPS_FAILURE;
-  const int units = (int)((m + 31) / 32);
-  const dim3 grid((unsigned)ts_grid_x(units, n / kTsBN), (unsigned)(n / kTsBN));
-  hipLaunchKernelGGL(tsgemm_f16_kernel<1>, grid, dim3(kTsThreads), kTsLds, st, (const __half *)x, (const __half *)weight,
-                     (const __half *)bias, (const __half *)nullptr, (__half *)nullptr, (int)m, n, k, 0, units, pk);
-  return launch_status();
+  hipLaunchKernelGGL(tsgemm_pad_zero_kernel, dim3(4, (unsigned)(num_cams * heads)), dim3(256), 0, c.st, pk, num_cams * heads);
+  return ts_launch_f16<1>(c, pk);
 }
 
 // The same planes from an already projected value tensor [num_cams, nk, heads, 32] (the re-layout pass of the
@@ -1370,7 +1359,7 @@ extern "C" int bevops_value_pack_planes(const void *value, const int32_t *spatia
   const MsdaDims d{num_cams, nk, heads, channels, num_levels, num_query, num_point, 4, 1};
   if (!msda_hm5_layout(d, spatial_shapes_host, &pk.t, &g_room, &s_bytes))
     return BEVOPS_NOT_SUPPORTED;
-  if (packed_bytes < g_room + s_bytes || (reinterpret_cast<uintptr_t>(packed) & 127u)) return BEVOPS_BAD_PARAM;
+  if (packed_bytes < g_room + s_bytes || misaligned(packed, 127u)) return BEVOPS_BAD_PARAM;
   msda_hm3_repack_launch(value, static_cast<char *>(packed), static_cast<char *>(packed) + g_room, pk.t, num_cams, nk,
                          heads, static_cast<hipStream_t>(stream));
   return launch_status();

@@ -9,6 +9,7 @@ import torch
 
 from ..utils import lib as _lib
 from ..utils import workspace as _ws
+from .linear import _like_rows, _operands, _ptr
 from .multi_scale_deformable_attn import _TensorCache
 
 
@@ -37,45 +38,26 @@ def linear_int8_chain(a, scale_a, w_q, scale_w, bias=None, residual=None, scale_
     bias fp32 [N], residual [..., N] fp16 -- or int8 with scale_res (int8 `a` only) --, output fp16 or int8
     requantised with scale_out (bevops_linear_int8_chain)."""
     assert a.is_cuda and a.dtype in (torch.int8, torch.float16) and w_q.dtype == torch.int8
-    K, N = a.shape[-1], w_q.shape[0]
-    a2 = a.reshape(-1, K)
-    if not a2.is_contiguous():
-        a2 = a2.contiguous()
-    w_q = w_q.contiguous()
-    M = a2.shape[0]
+    a2, w_q, b, r, _, M, N, K = _operands(a, w_q, bias, residual, False, bias_dtype=torch.float32,
+                                          res_dtypes=(torch.int8, torch.float16))
+    out = torch.empty((M, N), dtype=out_dtype, device=a.device)
     per_channel = torch.is_tensor(scale_w)
     ws = scale_w.float().contiguous() if per_channel else None
-    b = bias.float().contiguous() if bias is not None else None
-    r = None
-    if residual is not None:
-        assert residual.dtype in (torch.int8, torch.float16) and residual.numel() == M * N
-        r = residual.reshape(M, N)
-        if not r.is_contiguous():
-            r = r.contiguous()
-    out = torch.empty((M, N), dtype=out_dtype, device=a.device)
     if M == 0:
-        return out.view(*a.shape[:-1], N)
+        return _like_rows(out, a, N)
     handle = _lib.load_library()
-    if a2.dtype == torch.int8 and N % 256 == 0 and K % 128 == 0 and \
-            (_TS_S8["enabled"] or (_TS_S8["enabled"] is None and _ts_s8_pays(M, N, K))):
-        with torch.cuda.device(a.device):
-            st = handle.bevops_tsgemm_s8(
-                a2.data_ptr(), float(scale_a), w_q.data_ptr(), ws.data_ptr() if per_channel else None,
-                1.0 if per_channel else float(scale_w), b.data_ptr() if b is not None else None,
-                r.data_ptr() if r is not None else None, _code(r.dtype) if r is not None else _lib.F16, float(scale_res),
-                _code(out_dtype), out.data_ptr(), float(scale_out), M, N, K, int(bool(relu)),
-                _lib.current_stream_ptr(a.device))
-        _lib.check(st, "bevops_tsgemm_s8")
-        return out.view(*a.shape[:-1], N)
+    ts = a2.dtype == torch.int8 and N % 256 == 0 and K % 128 == 0 and \
+        (_TS_S8["enabled"] or (_TS_S8["enabled"] is None and _ts_s8_pays(M, N, K)))
+    tail = (float(scale_a), w_q.data_ptr(), _ptr(ws), 1.0 if per_channel else float(scale_w), _ptr(b), _ptr(r),
+            _code(r.dtype) if r is not None else _lib.F16, float(scale_res), _code(out_dtype), out.data_ptr(),
+            float(scale_out), M, N, K, int(bool(relu)), _lib.current_stream_ptr(a.device))
     with torch.cuda.device(a.device):
-        st = handle.bevops_linear_int8_chain(
-            a2.data_ptr(), _code(a2.dtype), float(scale_a), w_q.data_ptr(), ws.data_ptr() if per_channel else None,
-            1.0 if per_channel else float(scale_w), b.data_ptr() if b is not None else None,
-            r.data_ptr() if r is not None else None, _code(r.dtype) if r is not None else _lib.F16, float(scale_res),
-            _code(out_dtype), out.data_ptr(), float(scale_out), M, N, K, int(bool(relu)),
-            _lib.current_stream_ptr(a.device))
-    _lib.check(st, "bevops_linear_int8_chain")
-    return out.view(*a.shape[:-1], N)
+        if ts:
+            st = handle.bevops_tsgemm_s8(a2.data_ptr(), *tail)
+        else:
+            st = handle.bevops_linear_int8_chain(a2.data_ptr(), _code(a2.dtype), *tail)
+    _lib.check(st, "bevops_tsgemm_s8" if ts else "bevops_linear_int8_chain")
+    return _like_rows(out, a, N)
 
 
 def linear_int8_ln(a_q, scale_a, w_q, scale_w, bias=None, residual=None, scale_res=1.0, ln_weight=None, ln_bias=None,
@@ -88,36 +70,22 @@ def linear_int8_ln(a_q, scale_a, w_q, scale_w, bias=None, residual=None, scale_r
     sums, fp32 statistics).  Raises BevopsError (NOT_SUPPORTED) unless N == 256 and K % 128 == 0."""
     assert a_q.is_cuda and a_q.dtype == torch.int8 and w_q.dtype == torch.int8
     assert ln_weight is not None and ln_bias is not None
-    K, N = a_q.shape[-1], w_q.shape[0]
-    if w_q.shape[1] != K:
-        raise ValueError(f"w_q {tuple(w_q.shape)} does not match a_q [..., {K}]")
-    a2 = a_q.reshape(-1, K)
-    if not a2.is_contiguous():
-        a2 = a2.contiguous()
-    w_q = w_q.contiguous()
-    M = a2.shape[0]
+    a2, w_q, b, r, _, M, N, K = _operands(a_q, w_q, bias, residual, False, bias_dtype=torch.float32,
+                                          res_dtypes=(torch.int8, torch.float16))
+    out = torch.empty((M, N), dtype=torch.float16, device=a_q.device)
     per_channel = torch.is_tensor(scale_w)
     ws = scale_w.float().contiguous() if per_channel else None
-    b = bias.float().contiguous() if bias is not None else None
-    r = None
-    if residual is not None:
-        assert residual.dtype in (torch.int8, torch.float16) and residual.numel() == M * N
-        r = residual.reshape(M, N)
-        if not r.is_contiguous():
-            r = r.contiguous()
     g, be = ln_weight.to(torch.float16).contiguous(), ln_bias.to(torch.float16).contiguous()
-    out = torch.empty((M, N), dtype=torch.float16, device=a_q.device)
     if M == 0:
-        return out.view(*a_q.shape[:-1], N)
+        return _like_rows(out, a_q, N)
     handle = _lib.load_library()
     with torch.cuda.device(a_q.device):
         st = handle.bevops_tsgemm_s8_ln(
-            a2.data_ptr(), float(scale_a), w_q.data_ptr(), ws.data_ptr() if per_channel else None,
-            1.0 if per_channel else float(scale_w), b.data_ptr() if b is not None else None,
-            r.data_ptr() if r is not None else None, _code(r.dtype) if r is not None else _lib.F16, float(scale_res),
-            g.data_ptr(), be.data_ptr(), float(eps), out.data_ptr(), M, N, K, _lib.current_stream_ptr(a_q.device))
+            a2.data_ptr(), float(scale_a), w_q.data_ptr(), _ptr(ws), 1.0 if per_channel else float(scale_w), _ptr(b),
+            _ptr(r), _code(r.dtype) if r is not None else _lib.F16, float(scale_res), g.data_ptr(), be.data_ptr(),
+            float(eps), out.data_ptr(), M, N, K, _lib.current_stream_ptr(a_q.device))
     _lib.check(st, "bevops_tsgemm_s8_ln")
-    return out.view(*a_q.shape[:-1], N)
+    return _like_rows(out, a_q, N)
 
 
 def conv_int8_chain_nhwc(x_q, scale_a, w_q_taps, scale_w, bias=None, relu=False, stride=1, out_dtype=torch.float16,

@@ -31,52 +31,68 @@ def _tune_once(handle, key, args, x2, out_shape):
     handle.bevops_linear_tune(*a)       # status ignored: the heuristic's choice stays on failure
 
 
+def _operands(x, weight, bias, residual, out, bias_dtype=torch.float16, res_dtypes=None, out_dtype=None):
+    """The operands of a dense call as the C entries take them: x [..., K] as contiguous rows [M, K], weight [N, K]
+    contiguous, bias cast to `bias_dtype`, residual [..., N] as contiguous [M, N], `out` allocated as [M, N] or checked
+    (it may be the residual itself; False: the caller lays out its own destinations).
+    -> (x2, weight, bias, r2, out, M, N, K)"""
+    K, N = x.shape[-1], weight.shape[0]
+    if weight.shape[1] != K:
+        raise ValueError(f"weight {tuple(weight.shape)} does not match x [..., {K}]")
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    if not weight.is_contiguous():
+        weight = weight.contiguous()
+    M = x2.shape[0]
+    r2 = None
+    if residual is not None:
+        if residual.dtype not in (res_dtypes or (x.dtype,)) or residual.numel() != M * N:
+            raise ValueError(f"residual must be {res_dtypes or x.dtype} with M*N elements")
+        r2 = residual.reshape(M, N)
+        if not r2.is_contiguous():
+            r2 = r2.contiguous()
+    if bias is not None and (bias.dtype != bias_dtype or not bias.is_contiguous()):
+        bias = bias.to(bias_dtype).contiguous()
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype or x.dtype, device=x.device)
+    elif out is not False:
+        assert out.is_contiguous() and out.numel() == M * N and out.dtype == (out_dtype or x.dtype)
+    return x2, weight, bias, r2, out, M, N, K
+
+
+def _like_rows(out, x, N):
+    """the [M, N] result with the leading dimensions of x"""
+    return out.view(*x.shape[:-1], N)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def linear_bias_act(x, weight, bias=None, residual=None, relu=False, out=None):
     """x [..., K] fp16 (contiguous rows), weight [N, K], bias [N] or None, residual [..., N] or None
     -> [..., N].  `out` may be given (and may be `residual` itself).  Raises BevopsError with status
     NOT_SUPPORTED when hipBLASLt has no algorithm for the shape (callers fall back to
     mm + bias_act_nhwc_)."""
     assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    K = x.shape[-1]
-    N = weight.shape[0]
-    if weight.shape[1] != K:
-        raise ValueError(f"weight {tuple(weight.shape)} does not match x [..., {K}]")
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    weight = weight.contiguous()
-    M = x2.shape[0]
-    if residual is not None:
-        if residual.dtype != x.dtype or residual.numel() != M * N:
-            raise ValueError("residual must be fp16 with M*N elements")
-        r2 = residual.reshape(M, N)
-        if not r2.is_contiguous():
-            r2 = r2.contiguous()
-    else:
-        r2 = None
-    if bias is not None:
-        bias = bias.to(torch.float16).contiguous()
-    if out is None:
-        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    else:
-        assert out.is_contiguous() and out.numel() == M * N and out.dtype == x.dtype
+    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, out)
     if M == 0:
-        return out.view(*x.shape[:-1], N)
+        return _like_rows(out, x, N)
     handle = _lib.load_library()
     import os
     nbytes = handle.bevops_linear_workspace_size() if os.environ.get("BEVOPS_LINEAR_WS", "1") != "0" else 0
     stream = _lib.current_stream_ptr(x.device)
     ws = _workspace(x.device, nbytes, stream) if nbytes else None
-    args = (_lib.F16, x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-            r2.data_ptr() if r2 is not None else None, out.data_ptr(), M, N, K, int(bool(relu)),
-            ws.data_ptr() if ws is not None else None, nbytes, stream)
+    args = (_lib.F16, x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), out.data_ptr(), M, N, K, int(bool(relu)),
+            _ptr(ws), nbytes, stream)
     with torch.cuda.device(x.device):
         key = (str(x.device), M, N, K, bool(relu), bias is not None, r2 is not None)
         if key not in _TUNED and not torch.cuda.is_current_stream_capturing():
             _tune_once(handle, key, args, x2, (M, N))
         st = handle.bevops_linear_bias_act(*args)
     _lib.check(st, "bevops_linear_bias_act")
-    return out.view(*x.shape[:-1], N)
+    return _like_rows(out, x, N)
 
 
 def layer_norm(x, weight=None, bias=None, eps=1e-5, out=None):
@@ -147,26 +163,20 @@ def linear_int8(a_q, scale_a, w_q, scale_w, bias=None, residual=None, relu=False
     [N], residual fp16 [..., N] -> fp16 (or int8 requantised with scale_out)."""
     assert a_q.is_cuda and a_q.dtype in (torch.int8, torch.float16) and w_q.dtype == torch.int8
     fused = a_q.dtype == torch.float16
-    K, N = a_q.shape[-1], w_q.shape[0]
-    a2 = a_q.reshape(-1, K).contiguous()
-    w_q = w_q.contiguous()
-    M = a2.shape[0]
+    a2, w_q, b, r, out, M, N, K = _operands(a_q, w_q, bias, residual, None, bias_dtype=torch.float32,
+                                            res_dtypes=(torch.float16,), out_dtype=out_dtype)
     per_channel = torch.is_tensor(scale_w)
     ws = scale_w.float().contiguous() if per_channel else None
-    b = bias.float().contiguous() if bias is not None else None
-    r = residual.reshape(M, N).contiguous() if residual is not None else None
-    out = torch.empty((M, N), dtype=out_dtype, device=a_q.device)
     if M == 0:
-        return out.view(*a_q.shape[:-1], N)
+        return _like_rows(out, a_q, N)
     handle = _lib.load_library()
     with torch.cuda.device(a_q.device):
         st = (handle.bevops_linear_int8_fused if fused else handle.bevops_linear_int8)(
-            a2.data_ptr(), float(scale_a), w_q.data_ptr(), ws.data_ptr() if per_channel else None,
-            1.0 if per_channel else float(scale_w), b.data_ptr() if b is not None else None,
-            r.data_ptr() if r is not None else None, _lib.torch_dtype_code(out), out.data_ptr(), float(scale_out),
-            M, N, K, int(bool(relu)), _lib.current_stream_ptr(a_q.device))
+            a2.data_ptr(), float(scale_a), w_q.data_ptr(), _ptr(ws), 1.0 if per_channel else float(scale_w), _ptr(b),
+            _ptr(r), _lib.torch_dtype_code(out), out.data_ptr(), float(scale_out), M, N, K, int(bool(relu)),
+            _lib.current_stream_ptr(a_q.device))
     _lib.check(st, "bevops_linear_int8_fused" if fused else "bevops_linear_int8")
-    return out.view(*a_q.shape[:-1], N)
+    return _like_rows(out, a_q, N)
 
 
 def tsgemm(x, weight, bias=None, residual=None, relu=False, out=None):
@@ -174,32 +184,15 @@ def tsgemm(x, weight, bias=None, residual=None, relu=False, out=None):
     x [..., K] fp16 contiguous rows, weight [N, K], residual / out [..., N].  Raises BevopsError with status
     NOT_SUPPORTED outside its domain (K % 64, N % 256)."""
     assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    K, N = x.shape[-1], weight.shape[0]
-    if weight.shape[1] != K:
-        raise ValueError(f"weight {tuple(weight.shape)} does not match x [..., {K}]")
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    weight = weight.contiguous()
-    M = x2.shape[0]
-    r2 = None
-    if residual is not None:
-        r2 = residual.reshape(M, N)
-        if not r2.is_contiguous():
-            r2 = r2.contiguous()
-    if bias is not None:
-        bias = bias.to(torch.float16).contiguous()
-    if out is None:
-        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, out)
     if M == 0:
-        return out.view(*x.shape[:-1], N)
+        return _like_rows(out, x, N)
     handle = _lib.load_library()
     with torch.cuda.device(x.device):
-        st = handle.bevops_tsgemm_f16(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                      r2.data_ptr() if r2 is not None else None, out.data_ptr(), M, N, K,
-                                      int(bool(relu)), _lib.current_stream_ptr(x.device))
+        st = handle.bevops_tsgemm_f16(x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), out.data_ptr(), M, N, K,
+                                int(bool(relu)), _lib.current_stream_ptr(x.device))
     _lib.check(st, "bevops_tsgemm_f16")
-    return out.view(*x.shape[:-1], N)
+    return _like_rows(out, x, N)
 
 
 def tsgemm_grouped(x, weight, bias=None, out=None):
@@ -208,17 +201,10 @@ def tsgemm_grouped(x, weight, bias=None, out=None):
     tsgemm(x, weight[g * 256:(g + 1) * 256], bias[g * 256:(g + 1) * 256]).  The rows are read from memory once instead
     of G times.  Raises BevopsError (NOT_SUPPORTED) unless K % 64 == 0 and K <= 256."""
     assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    K, N = x.shape[-1], weight.shape[0]
-    if weight.shape[1] != K or N % 256 != 0 or N == 0:
+    x2, weight, bias, _, _, M, N, K = _operands(x, weight, bias, None, False)
+    if N % 256 != 0 or N == 0:
         raise ValueError(f"weight {tuple(weight.shape)} must be [G * 256, {K}]")
     G = N // 256
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    weight = weight.contiguous()
-    M = x2.shape[0]
-    if bias is not None:
-        bias = bias.to(torch.float16).contiguous()
     if out is None:
         out = torch.empty((G, M, 256), dtype=x.dtype, device=x.device)
     else:
@@ -227,8 +213,8 @@ def tsgemm_grouped(x, weight, bias=None, out=None):
         return out
     handle = _lib.load_library()
     with torch.cuda.device(x.device):
-        st = handle.bevops_tsgemm_f16_grouped(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                              out.data_ptr(), M * 256, M, G, K, _lib.current_stream_ptr(x.device))
+        st = handle.bevops_tsgemm_f16_grouped(x2.data_ptr(), weight.data_ptr(), _ptr(bias), out.data_ptr(), M * 256, M, G, K,
+                                              _lib.current_stream_ptr(x.device))
     _lib.check(st, "bevops_tsgemm_f16_grouped")
     return out
 
@@ -240,31 +226,16 @@ def tsgemm_ln(x, weight, bias, residual, ln_weight, ln_bias, eps=1e-5):
     layer_norm(tsgemm(...)) up to the last bit of the normalisation (same binary16 sums, fp32 statistics).  Raises
     BevopsError (NOT_SUPPORTED) unless N == 256 and K % 64 == 0."""
     assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    K, N = x.shape[-1], weight.shape[0]
-    if weight.shape[1] != K:
-        raise ValueError(f"weight {tuple(weight.shape)} does not match x [..., {K}]")
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    weight = weight.contiguous()
-    M = x2.shape[0]
-    r2 = None
-    if residual is not None:
-        r2 = residual.reshape(M, N)
-        if not r2.is_contiguous():
-            r2 = r2.contiguous()
-    bias = None if bias is None else bias.to(torch.float16).contiguous()
+    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, None)
     g, b = ln_weight.to(torch.float16).contiguous(), ln_bias.to(torch.float16).contiguous()
-    out = torch.empty((M, N), dtype=x.dtype, device=x.device)
     if M == 0:
-        return out.view(*x.shape[:-1], N)
+        return _like_rows(out, x, N)
     handle = _lib.load_library()
     with torch.cuda.device(x.device):
-        st = handle.bevops_tsgemm_f16_ln(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                         r2.data_ptr() if r2 is not None else None, g.data_ptr(), b.data_ptr(), float(eps),
-                                         out.data_ptr(), M, N, K, _lib.current_stream_ptr(x.device))
+        st = handle.bevops_tsgemm_f16_ln(x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), g.data_ptr(), b.data_ptr(),
+                                         float(eps), out.data_ptr(), M, N, K, _lib.current_stream_ptr(x.device))
     _lib.check(st, "bevops_tsgemm_f16_ln")
-    return out.view(*x.shape[:-1], N)
+    return _like_rows(out, x, N)
 
 
 def tile_gemm(x, weight, bias=None, residual=None, relu=False, out=None):
@@ -272,36 +243,15 @@ def tile_gemm(x, weight, bias=None, residual=None, relu=False, out=None):
     128 x 128 tiles, three blocks per CU): x [..., K] fp16 contiguous rows, weight [N, K], bias [N] fp16,
     residual / out [..., N].  K % 8 == 0."""
     assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    K, N = x.shape[-1], weight.shape[0]
-    if weight.shape[1] != K:
-        raise ValueError(f"weight {tuple(weight.shape)} does not match x [..., {K}]")
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    weight = weight.contiguous()
-    M = x2.shape[0]
-    r2 = None
-    if residual is not None:
-        if residual.dtype != x.dtype or residual.numel() != M * N:
-            raise ValueError("residual must be fp16 with M*N elements")
-        r2 = residual.reshape(M, N)
-        if not r2.is_contiguous():
-            r2 = r2.contiguous()
-    if bias is not None:
-        bias = bias.to(torch.float16).contiguous()
-    if out is None:
-        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    else:
-        assert out.is_contiguous() and out.numel() == M * N and out.dtype == x.dtype
+    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, out)
     if M == 0:
-        return out.view(*x.shape[:-1], N)
+        return _like_rows(out, x, N)
     handle = _lib.load_library()
     with torch.cuda.device(x.device):
-        st = handle.bevops_tile_gemm_f16(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                         r2.data_ptr() if r2 is not None else None, out.data_ptr(), M, N, K,
-                                         int(bool(relu)), _lib.current_stream_ptr(x.device))
+        st = handle.bevops_tile_gemm_f16(x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), out.data_ptr(), M, N, K,
+                                   int(bool(relu)), _lib.current_stream_ptr(x.device))
     _lib.check(st, "bevops_tile_gemm_f16")
-    return out.view(*x.shape[:-1], N)
+    return _like_rows(out, x, N)
 
 
 class _GemmDst(ctypes.Structure):     # bevops_gemm_dst (include/bevops.h)
@@ -316,16 +266,9 @@ def tile_gemm_dst(x, weight, bias, widths, residuals=None, relu=False, outs=None
     list of dense [M, widths[i]] results -- each bit for bit tile_gemm(x, weight_i, bias_i, residuals[i], relu).
     `outs`: optional destinations (2-d, unit column stride, row pitch a multiple of 8)."""
     assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    K, N = x.shape[-1], weight.shape[0]
-    if weight.shape[1] != K or sum(widths) != N:
-        raise ValueError(f"weight {tuple(weight.shape)} does not match x [..., {K}] / widths {list(widths)}")
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    weight = weight.contiguous()
-    M = x2.shape[0]
-    if bias is not None:
-        bias = bias.to(torch.float16).contiguous()
+    x2, weight, bias, _, _, M, N, K = _operands(x, weight, bias, None, False)
+    if sum(widths) != N:
+        raise ValueError(f"weight {tuple(weight.shape)} does not match widths {list(widths)}")
     if outs is None:
         outs = [torch.empty((M, n), dtype=x.dtype, device=x.device) for n in widths]
     residuals = residuals if residuals is not None else [None] * len(widths)
@@ -344,9 +287,8 @@ def tile_gemm_dst(x, weight, bias, widths, residuals=None, relu=False, outs=None
         col += n
     handle = _lib.load_library()
     with torch.cuda.device(x.device):
-        st = getattr(handle, _entry)(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                     ctypes.addressof(tab), len(widths), M, N, K, int(bool(relu)),
-                                     _lib.current_stream_ptr(x.device))
+        st = getattr(handle, _entry)(x2.data_ptr(), weight.data_ptr(), _ptr(bias), ctypes.addressof(tab), len(widths), M, N, K,
+                                     int(bool(relu)), _lib.current_stream_ptr(x.device))
     _lib.check(st, _entry)
     return outs
 
@@ -371,38 +313,17 @@ def small_gemm(x, weight, bias=None, residual=None, relu=False, out=None):
     operand fragment requested before the first matrix instruction -- one memory round trip per launch instead of a
     chain of dependent k-steps).  x [..., K] fp16, weight [N, K]; K % 64 == 0, K <= 1024; offered up to 8192 rows."""
     assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    K, N = x.shape[-1], weight.shape[0]
-    if weight.shape[1] != K:
-        raise ValueError(f"weight {tuple(weight.shape)} does not match x [..., {K}]")
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    M = x2.shape[0]
+    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, out)
     if M > 8192:
         raise _lib.BevopsError("small_gemm: more than 8192 rows (the tiled GEMMs' domain)", _lib.NOT_SUPPORTED)
-    weight = weight.contiguous()
-    r2 = None
-    if residual is not None:
-        if residual.dtype != x.dtype or residual.numel() != M * N:
-            raise ValueError("residual must be fp16 with M*N elements")
-        r2 = residual.reshape(M, N)
-        if not r2.is_contiguous():
-            r2 = r2.contiguous()
-    if bias is not None:
-        bias = bias.to(torch.float16).contiguous()
-    if out is None:
-        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    else:
-        assert out.is_contiguous() and out.numel() == M * N and out.dtype == x.dtype
     if M == 0:
-        return out.view(*x.shape[:-1], N)
+        return _like_rows(out, x, N)
     handle = _lib.load_library()
     with torch.cuda.device(x.device):
-        st = handle.bevops_small_gemm_f16(x2.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                          r2.data_ptr() if r2 is not None else None, out.data_ptr(), M, N, K,
-                                          int(bool(relu)), _lib.current_stream_ptr(x.device))
+        st = handle.bevops_small_gemm_f16(x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), out.data_ptr(), M, N, K,
+                                    int(bool(relu)), _lib.current_stream_ptr(x.device))
     _lib.check(st, "bevops_small_gemm_f16")
-    return out.view(*x.shape[:-1], N)
+    return _like_rows(out, x, N)
 
 
 # ---- measured choice between the dense-layer implementations -------------------------------------------------
