@@ -6,11 +6,29 @@
 #include "common.h"
 
 namespace bevops {
-// A/B switches of bevops_mdconv_set_variant (defined in mdconv.hip)
-extern thread_local int g_mdconv_variant;
-extern thread_local bool g_mdconv_no_tail;
-extern thread_local bool g_mdconv_wide;
-extern thread_local int g_mdconv_rotate;   // LDS-DMA kernels' wave order: 0 default (round 6), 1 round-2 rotation (fp16), 2 one order
+// The three ways a call can run, and what bevops_mdconv_set_variant can force per dtype family
+enum DcnPath {
+  kDcnAuto = 0,   // (variant only) the plan decides
+  kDcnLds,        // LDS-DMA pipelined implicit GEMM (sections 5c, 6c)
+  kDcnStaged,     // register-staged fused implicit GEMM (sections 5, 6b)
+  kDcnGemm        // im2col + GEMM (sections 3, 4, 6)
+};
+
+// bevops_mdconv_set_variant, decoded once (kDcnVariants in mdconv.hip is the only place that knows the numbers).
+// A value acts on BOTH dtype families:
+//   0      automatic
+//   1 2 3  fp16: im2col + GEMM / register-staged kernel with 256 / with 512 threads;       int8: automatic
+//   4      both: no split-K tail (fp16 also keeps the 64-pixel tiles);   5  both: 128-pixel tiles whatever the tile count
+//   6 8 9  int8: im2col + GEMM / register-staged kernel / LDS-DMA kernel whatever the tile count;
+//          fp16: a call inside the fused domain runs on the 512-thread register-staged kernel, as under 3
+// Any other value selects the automatic choice, exactly as 0 does (the rule of bevops_msda_set_variant).
+struct DcnVariant {
+  int id;            // what bevops_mdconv_set_variant returns as the previous value
+  DcnPath f16, s8;   // forced path of the family, kDcnAuto = none
+  int f16_threads;   // block size of the fp16 register-staged kernel when f16 == kDcnStaged
+  bool no_tail, wide;
+};
+extern thread_local DcnVariant g_dcn_variant;   // defined in mdconv.hip
 
 namespace {
 
@@ -107,8 +125,6 @@ struct TailPlan {
   int out_nhwc, relu;                 // epilogue: output layout [B,Ho,Wo,Cout], fused ReLU
   int om_channels;                    // > 0: `offset` is the raw [B,Ho,Wo,om_channels] output of the pack's
                                       // offset convolution (2*KK offsets, then KK mask logits): sigmoid here
-  int rotate;                         // fp16 kernel: wave halves in opposite phase order (A/B switch, variant 7;
-                                      // measured 4-6 % slower at both ResNet-101 shapes, profiles/r02)
 };
 
 // ---- host side: problem description and workspace layout -------------------------------------------
@@ -143,6 +159,109 @@ inline WsLayout ws_layout(const ConvDims &d, size_t es) {
   w.col = w.wt + align256((size_t)d.Cout * kp * es);
   w.total = w.col + align256((size_t)d.B * d.Ho * d.Wo * d.G * kp * es);
   return w;
+}
+
+// ---- host side: one call descriptor, one plan ------------------------------------------------------
+// Everything a forward call carries.  Every extern "C" entry fills one, validates it and hands it to its family's
+// plan_* / launch_* pair (mdconv.hip: fp32 / fp16, mdconv_s8.hip: int8).
+struct DcnCall {
+  ConvDims d;        // d.B == 0: make_dims rejected the 15 geometry ints
+  int dtype;         // BEVOPS_F32 / BEVOPS_F16 / BEVOPS_I8
+  const void *input, *offset, *mask, *weight, *bias;
+  void *output;
+  bool packed;       // `weight` is the image made by bevops_mdconv_pack_weight
+  bool nhwc;         // channels-last input and output (int8: the engine's block, raw fp16 offsets / mask logits)
+  bool relu;
+  bool exact;        // int8 nhwc: the plugin's two requantisations per column element, not the folded one
+  int om_channels;   // > 0: `offset` is the raw [B, Ho, Wo, om_channels] output of the pack's offset convolution
+  float s_in, s_off, s_mask, s_w, s_out;   // int8: per-tensor scales
+  void *workspace;
+  size_t workspace_bytes;
+  hipStream_t stream;
+};
+
+inline DcnCall dcn_call(int dtype, const void *input, const void *offset, const void *mask, const void *weight,
+                        const void *bias, void *output, void *workspace, size_t workspace_bytes, int B, int Cin, int H,
+                        int W, int Cout, int Kh, int Kw, int sh, int sw, int ph, int pw, int dh, int dw, int G, int DG,
+                        void *stream) {
+  DcnCall c{};
+  (void)make_dims(c.d, B, Cin, H, W, Cout, Kh, Kw, sh, sw, ph, pw, dh, dw, G, DG);
+  c.dtype = dtype;
+  c.input = input, c.offset = offset, c.mask = mask, c.weight = weight, c.bias = bias, c.output = output;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes;
+  c.stream = static_cast<hipStream_t>(stream);
+  return c;
+}
+
+// split-K tail of the LDS-DMA kernels (see TailPlan): `left` tiles of a sparsely filled last round, `split` ways
+struct DcnTail {
+  int tiles, split;
+};
+// blocks = grid.x * grid_y of the untailed launch, slots = resident blocks of the device, room = bytes the workspace
+// can give to the partial sums, block_bytes = what one block parks there (its threads' 32 accumulators)
+inline DcnTail plan_tail(int blocks, int grid_y, int KK, int slots, size_t room, size_t block_bytes) {
+  if (blocks <= slots || grid_y != 1) return DcnTail{0, 1};
+  const int left = blocks % slots;
+  int split = 0;
+  for (int f = KK; f >= 2; --f)
+    if (KK % f == 0 && left * f <= slots) { split = f; break; }
+  if (left > 0 && left * 2 <= slots && split >= 2 && room >= (size_t)split * left * block_bytes) return DcnTail{left, split};
+  return DcnTail{0, 1};
+}
+
+// What a call will launch.  Made by plan_fp / plan_s8 before anything is queued; a rejected call queues nothing.
+enum DcnCopy { kDcnCopyNone, kDcnCopyGeneric, kDcnCopyQuad };   // NCHW -> NHWC: none (nhwc), 32 x 32 tiles, 4 x 4 register transposes
+struct DcnPlan {
+  DcnPath path;     // kDcnLds: every conv group that reads ONE deform group runs the LDS-DMA kernel, any other group
+                    // the register-staged one (int8: kDcnLds only when all groups do)
+  int threads;      // fp16 register-staged kernel: 256 or 512
+  int WN;           // LDS-DMA kernel: wave columns, 2 (64-pixel tiles) or 4 (128-pixel tiles)
+  DcnTail tail;
+  char *partial;    // LDS-DMA kernel: where the tail's partial sums go
+  DcnCopy copy;
+  bool repack;      // weights re-laid out per call (not packed by the caller)
+  bool zero_pad;    // int8, ragged K: packed weights and columns zeroed first
+};
+// the device's CU count, <= 0 when HIP cannot tell; the resident blocks of the LDS-DMA kernel of tile width wn
+typedef int (*DcnCusFn)();
+typedef int (*DcnSlotsFn)(const DcnCall &c, int wn);
+
+// conv group g reads ONE deform group (the LDS-DMA kernels' domain: dg constant over a block's k-loop)
+inline bool one_deform_group(const ConvDims &d, int g) {
+  const int cin_g = d.Cin / d.G, cin_dg = d.Cin / d.DG;
+  return cin_g <= cin_dg && (g * cin_g) / cin_dg == (g * cin_g + cin_g - 1) / cin_dg;
+}
+inline bool one_deform_group(const ConvDims &d) {
+  for (int g = 0; g < d.G; ++g)
+    if (!one_deform_group(d, g)) return false;
+  return true;
+}
+
+inline int device_cus() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return 0;
+  return cus;
+}
+
+// blocks of Kern (threads, dynamic LDS bytes) the device holds at once, 0 on failure; sets the kernel's dynamic LDS
+// limit on the way.  Cached per thread, kernel and device.
+template <auto Kern>
+int resident_blocks(int threads, int lds) {
+  static thread_local int cached_dev = -1, cached = 0;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  if (dev == cached_dev) return cached;
+  int per_cu = 0;
+  const int cus = device_cus();
+  if (cus <= 0 ||
+      hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kern, threads, lds) != hipSuccess)
+    return 0;
+  cached_dev = dev;
+  cached = per_cu * cus;
+  return cached;
 }
 
 }  // namespace

@@ -25,51 +25,25 @@
 #include "mdconv.h"
 
 namespace bevops {
-// A/B switches of bevops_mdconv_set_variant (thread-local; read by mdconv_s8.hip too)
-thread_local int g_mdconv_variant = 0;
-thread_local bool g_mdconv_no_tail = false;
-thread_local bool g_mdconv_wide = false;  // variant 5: 1024-thread blocks, 128-pixel tiles whatever the tile count
-thread_local int g_mdconv_rotate = 0;   // fp16 LDS-DMA kernel: 0 = round 6's wave order; variant 7 -> 1: halves rotated by half an iteration
-                                        // (round 2); variant 13 -> 2: one order for all waves (rounds 2-5, the A/B partner)
+// bevops_mdconv_set_variant: the only place that knows the numbers (effects per dtype family: mdconv.h)
+constexpr DcnVariant kDcnVariants[] = {
+    {0, kDcnAuto, kDcnAuto, 0, false, false},
+    {1, kDcnGemm, kDcnAuto, 0, false, false},
+    {2, kDcnStaged, kDcnAuto, 256, false, false},
+    {3, kDcnStaged, kDcnAuto, 512, false, false},
+    {4, kDcnAuto, kDcnAuto, 0, true, false},
+    {5, kDcnAuto, kDcnAuto, 0, false, true},
+    {6, kDcnStaged, kDcnGemm, 512, false, false},
+    {8, kDcnStaged, kDcnStaged, 512, false, false},
+    {9, kDcnStaged, kDcnLds, 512, false, false},
+};
+thread_local DcnVariant g_dcn_variant = kDcnVariants[0];
 namespace {
-
-// fp16, HW % 8 == 0 and C % 8 == 0: 64 channels x 64 pixels per block, 16-byte global accesses on
-// both sides (8 pixels of a channel in, 8 channels of a pixel out), 2-byte transposed LDS writes
-__global__ __launch_bounds__(256) void nchw_to_nhwc_f16v_kernel(const __half *__restrict__ in,
-                                                                __half *__restrict__ out, int C, int HW) {
-  __shared__ __attribute__((aligned(16))) unsigned short tile[64][72];  // [pixel][channel], padded rows
-  const int b = blockIdx.z;
-  const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-  const __half *ib = in + (size_t)b * C * HW;
-  __half *ob = out + (size_t)b * C * HW;
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int v = threadIdx.x + it * 256;  // 64 channels x 8 pixel-vectors
-    const int c = v >> 3, pv = (v & 7) * 8;
-    if (c0 + c < C && p0 + pv < HW) {
-      const uint4 q = *reinterpret_cast<const uint4 *>(ib + (size_t)(c0 + c) * HW + p0 + pv);
-      const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        tile[pv + 2 * k][c] = (unsigned short)(w[k] & 0xffffu);
-        tile[pv + 2 * k + 1][c] = (unsigned short)(w[k] >> 16);
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int v = threadIdx.x + it * 256;  // 64 pixels x 8 channel-vectors
-    const int p = v >> 3, cv = (v & 7) * 8;
-    if (p0 + p < HW && c0 + cv < C)
-      *reinterpret_cast<uint4 *>(ob + (size_t)(p0 + p) * C + c0 + cv) = *reinterpret_cast<const uint4 *>(&tile[p][cv]);
-  }
-}
 
 // fp16, HW % 4 == 0 and C % 8 == 0: 64 channels x 128 pixels per block; a thread loads a 4 x 4 block of halves
 // (8 bytes from each of 4 channel rows, lanes along the pixels: 256 contiguous bytes per row and half-wave),
 // transposes it with 8 v_perm and writes 4 x 8 bytes (4 channels of one pixel) into the [pixel][channel] tile --
-// a quarter of the LDS write instructions of the 2-byte version above; the tile leaves as 16-byte vectors,
+// a quarter of the LDS write instructions of a 2-byte transposed write; the tile leaves as 16-byte vectors,
 // 128 contiguous bytes per pixel.
 __global__ __launch_bounds__(256) void nchw_to_nhwc_f16q_kernel(const __half *__restrict__ in, __half *__restrict__ out,
                                                                 int C, int HW) {
@@ -521,14 +495,7 @@ __global__ __launch_bounds__(THREADS, 2) void dcn_fused_f16_kernel(
       ra[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, (int)a_off[i], a_s, 0));
   };
 
-#ifdef DCN_PROFILE
-  unsigned long long tacc[5] = {0, 0, 0, 0, 0}, t0 = __builtin_amdgcn_s_memtime(), t1;
-#define TICK(i) { t1 = __builtin_amdgcn_s_memtime(); tacc[i] += t1 - t0; t0 = t1; }
-#else
-#define TICK(i)
-#endif
   prefetch(0);
-  TICK(0)
   for (int step = 0; step < nsteps; ++step) {
     // blend the 4 corners (packed fp16), 8 * NB channels per thread
     uint4 bl[NB];
@@ -542,16 +509,13 @@ __global__ __launch_bounds__(THREADS, 2) void dcn_fused_f16_kernel(
         bl[v].z = pk_fma(rb[q][v].z, fw[q], bl[v].z); bl[v].w = pk_fma(rb[q][v].w, fw[q], bl[v].w);
       }
     }
-    TICK(1)
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NA; ++i) *reinterpret_cast<uint4 *>(&As[ar + RPP * i][ac]) = ra[i];
 #pragma unroll
     for (int v = 0; v < NB; ++v) *reinterpret_cast<uint4 *>(&Bs[tid / LPP][cq * 8 * NB + 8 * v]) = bl[v];
     __syncthreads();
-    TICK(2)
     if (step + 1 < nsteps) prefetch(step + 1);
-    TICK(3)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int kk = ks * 16 + (lane >> 5) * 8;
@@ -568,15 +532,7 @@ __global__ __launch_bounds__(THREADS, 2) void dcn_fused_f16_kernel(
         for (int j = 0; j < NJ; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
     }
-    TICK(4)
   }
-#ifdef DCN_PROFILE
-  if ((tid & 63) == 0 && blockIdx.x < 64) {
-    unsigned long long *dbg = reinterpret_cast<unsigned long long *>(const_cast<__half *>(wt)) + 1000000 +
-                              (blockIdx.x * (THREADS / 64) + wave) * 8;
-    for (int i = 0; i < 5; ++i) dbg[i] = tacc[i];
-  }
-#endif
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int n = n0 + wn * (kFN / WN) + j * 32 + (lane & 31);
@@ -601,7 +557,7 @@ __global__ __launch_bounds__(THREADS, 2) void dcn_fused_f16_kernel(
 // ---- 5c. pipelined fused kernel: weights by LDS-DMA, two LDS buffers, one barrier per k-step ----
 // The register-staged kernel above spends a k-step as  wait loads -> blend -> barrier -> 40 KB of
 // ds_write_b128 (13 cycles per wave-instruction) -> barrier -> MFMA: the phase probe
-// (tools/dcn_phase_probe.py) showed 1/3 of the time in the write + barrier phase and the matrix
+// (profiles/r06/dcn_phase_probe.jsonl) showed 1/3 of the time in the write + barrier phase and the matrix
 // cores 12 % busy.  Here the weight tile (80 % of the staged bytes) goes global -> LDS directly
 // (buffer_load_dwordx4 ... lds, no VGPRs, no ds_write) one step ahead into the other LDS
 // buffer while the MFMAs of the current step run; only the blended pixel tile (8 KB) is
@@ -642,9 +598,7 @@ __device__ __forceinline__ void dcn_store4(__half *__restrict__ out, const __hal
   }
 }
 
-// SCHED: 0 = every wave runs a step's segments in one order (rounds 2-5; tp.rotate == 1: upper half rotated by half an
-// iteration); 4 = round 6's default, see the loop
-template <int WN, int SCHED = 0>
+template <int WN>
 __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel(
     const __half *__restrict__ xt, const __half *__restrict__ offset,
     const __half *__restrict__ mask, const __half *__restrict__ wt,
@@ -684,12 +638,12 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel
       const_cast<__half *>(A), 0, (unsigned)((size_t)cout_g * Kg * 2), 0x00020000);
   const unsigned ximg_off = (unsigned)(((size_t)pb * d.H * d.W * d.Cin + g * cin_g + cq * 8) * 2);
   const unsigned b_dst = (unsigned)(pp * 128 + ((cq ^ swz8(pp)) << 4));
-  // weight DMA role: piece j of this wave = rows (wave*4 + j)*8 .. +8, lane -> (row, chunk)
-  // SCHED 4: the LOWER half of the waves issues ALL the weight pieces (two waves' worth each), the upper half none --
+  // weight DMA role: piece j of this wave = rows (wave*kPcS + j)*8 .. +8, lane -> (row, chunk)
+  // The LOWER half of the waves issues ALL the weight pieces (two waves' worth each), the upper half none --
   // an upper wave then has no vector-memory instruction in front of its matrix segment (phase probe, round 6: with the
   // 16 waves' loads arbitrated oldest first, even the two DMA pieces of an upper wave sat ~1 000 cycles behind the lower
   // waves' gathers before its MFMAs could start)
-  constexpr int kPcS = SCHED == 4 ? 2 * kPc : kPc;
+  constexpr int kPcS = 2 * kPc;
   unsigned a_off[kPcS];
 #pragma unroll
   for (int j = 0; j < kPcS; ++j) {
@@ -803,13 +757,12 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel
     // hand-written store (see dcn_glds_s8_kernel): a compiler-visible LDS store would drain vmcnt to 0
     asm volatile("ds_write_b128 %0, %1" ::"v"(b_lds + (unsigned)(buf * kGB)), "v"(bl) : "memory");
   };
-  constexpr bool kLowerDma = SCHED == 4;
 
   // prologue: step 0 -> buffer 0, corners of step 1 in flight
   gather_next();
   blend_store(0);
   __builtin_amdgcn_sched_barrier(0);
-  if (!kLowerDma || __builtin_amdgcn_readfirstlane(wave) < kTh / 128) weights_next(0);
+  if (__builtin_amdgcn_readfirstlane(wave) < kTh / 128) weights_next(0);
   if (n_my_steps > 1) gather_next();
   if (n_my_steps > 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -830,74 +783,38 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel
       for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b, acc[i], 0, 0, 0);
     }
   };
-  // tp.rotate: the upper half of the waves runs the same loop rotated by half an iteration (its barrier sits
-  // between the blend and the MFMAs, MFMA(0) is peeled): between two barriers one half issues its loads while
-  // the other half reads fragments and feeds the matrix cores (see dcn_glds_s8_kernel)
   const bool upper = __builtin_amdgcn_readfirstlane(wave) >= kTh / 128;
-  const bool late = SCHED == 0 && tp.rotate == 1 && upper;
-  // tp.rotate == 2 (round 6): OPPOSED halves.  Every wave of the block issues 6 vector-memory instructions per step
-  // (2 weight DMA pieces, 4 corner gathers): 96 wave-instructions of 1 KB through a 64 B/clk L1 path = 1 536 cycles in
-  // which, with all 16 waves in the same order, nobody is in its matrix segment (and the round-2 rotation above keeps
-  // "loads, then MFMAs" in both halves).  Here the upper half runs  DMA -> MFMA(step) -> blend(step + 1) -> gathers
-  // while the lower half runs  blend -> DMA -> gathers -> MFMA(step): between two barriers one half occupies the L1
-  // path while the other occupies the matrix cores and the LDS read path, then they swap.  Same barrier per step, same
-  // buffers (a step consumes buffer step & 1 and produces the other), same arithmetic and summation order.
-  if constexpr (SCHED == 4) {
-    // Round 6 (default).  The phase probe of the one-order loop (s_memtime stamps between the segments,
-    // profiles/r06/dcn_phase_probe.jsonl) showed where a step goes: its 96 vector-memory wave-instructions (32 weight
-    // DMA pieces, 64 corner gathers: 768 cache lines) leave the CU's L1 path at ~0.4 lines per clock, arbitrated oldest
-    // wave first -- waves 12-15 sit in their load-issue segment for 58 % of the loop (waves 0-3: 27 %, the rest of
-    // their time at the barrier), and nobody is in a matrix segment meanwhile.  Even the two DMA pieces of an upper
-    // wave queue ~1 000 cycles behind the lower waves' gathers.  Here the LOWER half of the waves issues all the
-    // weight pieces (kPcS = two waves' worth each) and the upper half none:
-    //   lower half: blend -> DMA (all pieces) -> gathers -> MFMA       upper half: MFMA -> blend -> gathers
-    // so an upper wave has no vector-memory instruction in front of its matrix segment.  One loop body, the segments a
-    // half does not run at a position skipped by a wave-uniform branch (two copies of the loop, one per half, cost the
-    // 1 024-thread build ten spilled registers).  Same barrier per step, same buffers, same arithmetic and summation
-    // order: bit-identical.  Measured with it (and removed): both halves issuing their own pieces in opposed order
-    // (+- 1 %), raised priority in the matrix segment (+- 1 %), a second set of corner registers so that a gather has
-    // two iterations to land (no gain): design/dcn.md.
-    for (int step = 0; step < n_my_steps; ++step) {
-      const bool more1 = step + 1 < n_my_steps, more2 = step + 2 < n_my_steps;
-      if (!upper && more1) blend_store((step + 1) & 1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (!upper && more1) weights_next((step + 1) & 1);
-      if (!upper && more2) gather_next();
-      __builtin_amdgcn_sched_barrier(0);
-      mfma_step(step & 1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (upper && more1) blend_store((step + 1) & 1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (upper && more2) gather_next();
-      __builtin_amdgcn_sched_barrier(0);
-      if (more2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-  } else {
-  if (late) {
-    if (n_my_steps > 1) weights_next(1);
-    mfma_step(0);
-  }
+  // The phase probe of a loop in which every wave ran a step's segments in one order (s_memtime stamps between them,
+  // profiles/r06/dcn_phase_probe.jsonl) showed where a step goes: its 96 vector-memory wave-instructions (32 weight
+  // DMA pieces, 64 corner gathers: 768 cache lines) leave the CU's L1 path at ~0.4 lines per clock, arbitrated oldest
+  // wave first -- waves 12-15 sit in their load-issue segment for 58 % of the loop (waves 0-3: 27 %, the rest of
+  // their time at the barrier), and nobody is in a matrix segment meanwhile.  Even the two DMA pieces of an upper
+  // wave queue ~1 000 cycles behind the lower waves' gathers.  Here the LOWER half of the waves issues all the
+  // weight pieces (kPcS = two waves' worth each) and the upper half none:
+  //   lower half: blend -> DMA (all pieces) -> gathers -> MFMA       upper half: MFMA -> blend -> gathers
+  // so an upper wave has no vector-memory instruction in front of its matrix segment.  One loop body, the segments a
+  // half does not run at a position skipped by a wave-uniform branch (two copies of the loop, one per half, cost the
+  // 1 024-thread build ten spilled registers).  Same barrier per step, same buffers, same arithmetic and summation
+  // order: bit-identical.  Measured with it (and removed): both halves issuing their own pieces in opposed order
+  // (+- 1 %), raised priority in the matrix segment (+- 1 %), a second set of corner registers so that a gather has
+  // two iterations to land (no gain): design/dcn.md.
   for (int step = 0; step < n_my_steps; ++step) {
     const bool more1 = step + 1 < n_my_steps, more2 = step + 2 < n_my_steps;
-    if (more1) blend_store((step + 1) & 1);
+    if (!upper && more1) blend_store((step + 1) & 1);
     __builtin_amdgcn_sched_barrier(0);
-    if (late) {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-    if (late ? more2 : more1) weights_next(late ? (step & 1) : ((step + 1) & 1));
-    if (more2) gather_next();
+    if (!upper && more1) weights_next((step + 1) & 1);
+    if (!upper && more2) gather_next();
     __builtin_amdgcn_sched_barrier(0);
-    if (late ? more1 : true) mfma_step(late ? ((step + 1) & 1) : (step & 1));
-    if (!late) {
-      if (more2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
+    mfma_step(step & 1);
+    __builtin_amdgcn_sched_barrier(0);
+    if (upper && more1) blend_store((step + 1) & 1);
+    __builtin_amdgcn_sched_barrier(0);
+    if (upper && more2) gather_next();
+    __builtin_amdgcn_sched_barrier(0);
+    if (more2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
   }
-  }   // (SCHED < 2)
   if (is_tail) {  // fp32 partials, thread-private order (the finish kernel uses the same mapping)
     float4 *pp = reinterpret_cast<float4 *>(tp.partial) +
                  ((((size_t)part * tp.tail_tiles + (ntile - tp.main_tiles)) * gridDim.y + blockIdx.y) * 8) * kTh + tid;
@@ -951,179 +868,169 @@ __global__ __launch_bounds__(256 * WN) void dcn_tail_finish_kernel(const __half 
 }
 
 
-thread_local bool g_mdconv_old_copy = false;   // variant 12: the r01 NCHW -> NHWC copy kernel (A/B)
-
-template <int WN>
-int glds_resident_blocks() {
-  static thread_local int cached_dev = -1, cached = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (dev == cached_dev) return cached;
-  int per_cu = 0, cus = 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_glds_f16_kernel<WN>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, Glds<WN>::kLds) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dcn_glds_f16_kernel<WN>, Glds<WN>::kThreads,
-                                                   Glds<WN>::kLds) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 0;
-  cached_dev = dev;
-  cached = per_cu * cus;
-  return cached;
+// ---- host side: plan, then launch (DcnCall, DcnVariant, DcnPlan: mdconv.h) ------------------------------------
+int lds_f16_slots(const DcnCall &, int wn) {
+  return wn == 4 ? resident_blocks<dcn_glds_f16_kernel<4>>(Glds<4>::kThreads, Glds<4>::kLds)
+                 : resident_blocks<dcn_glds_f16_kernel<2>>(Glds<2>::kThreads, Glds<2>::kLds);
 }
 
-// launch of the LDS-DMA kernel with its tail plan
-template <int WN>
-int launch_glds(const __half *xt, const void *offset, const void *mask, const __half *wt, const void *bias,
-                void *output, const ConvDims &d, int g, char *part_ws, size_t part_room, bool nhwc_io,
-                bool relu, bool allow_tail, int om_channels, hipStream_t st) {
-  const int KK = d.Kh * d.Kw, cout_g = d.Cout / d.G;
+// What an fp32 / fp16 call launches, or the status that rejects it.  Launches nothing; `cus` and `slots` are asked
+// only on the way to the LDS-DMA kernel, after every check that precedes it.
+int plan_fp(const DcnCall &c, const DcnVariant &v, DcnCusFn cus, DcnSlotsFn slots, DcnPlan &p) {
+  const ConvDims &d = c.d;
+  const size_t es = c.dtype == BEVOPS_F32 ? 4 : 2;
+  const int HW = d.H * d.W, KK = d.Kh * d.Kw, cin_g = d.Cin / d.G, cout_g = d.Cout / d.G;
   const size_t N = (size_t)d.B * d.Ho * d.Wo;
-  const dim3 grid((unsigned)((N + Glds<WN>::kN - 1) / Glds<WN>::kN), (cout_g + kFM - 1) / kFM);
-  const int slots = glds_resident_blocks<WN>();
-  if (slots <= 0) return BEVOPS_FAILURE;
-  // tail plan: leftover tiles of a sparsely filled last round are split along K
-  TailPlan tp{0, 1, (int)grid.x, nullptr, nhwc_io ? 1 : 0, relu ? 1 : 0, om_channels, g_mdconv_rotate};
-  const int blocks = (int)(grid.x * grid.y);
-  if (allow_tail && blocks > slots && grid.y == 1) {
-    const int left = blocks % slots;
-    int split = 0;
-    for (int f = KK; f >= 2; --f)
-      if (KK % f == 0 && left * f <= slots) { split = f; break; }
-    const size_t need = (size_t)split * left * Glds<WN>::kThreads * 32 * sizeof(float);
-    if (left > 0 && left * 2 <= slots && split >= 2 && part_room >= need) {
-      tp.tail_tiles = left;
-      tp.split = split;
-      tp.main_tiles = (int)grid.x - left;
-      tp.partial = reinterpret_cast<float *>(part_ws);
+  if (N > 0x7FFFFFFFull || (size_t)d.B * d.Cin * HW > 0x7FFFFFFF00ull) return BEVOPS_NOT_SUPPORTED;
+  const bool fits32 = (size_t)d.B * d.Cin * HW * 2 < 0xFFFFFF00ull && (size_t)d.Cout * cin_g * KK * 2 < 0xFFFFFF00ull;
+  p = DcnPlan{};
+  // nhwc: the caller's tensor already is the [B, H, W, Cin] image the gather wants
+  p.copy = c.nhwc ? kDcnCopyNone
+                  : (es == 2 && HW % 4 == 0 && d.Cin % 8 == 0 && aligned16(c.input) ? kDcnCopyQuad : kDcnCopyGeneric);
+  p.repack = !c.packed;
+  const bool extras = c.nhwc || c.relu || c.om_channels;   // only the LDS-DMA kernel has these
+  // fused implicit GEMM: a 64-channel K chunk must sit inside one group and one deform group
+  if (es == 2 && v.f16 != kDcnGemm && fits32 && cin_g % kFK == 0 && (d.Cin / d.DG) % kFK == 0) {
+    p.path = kDcnStaged;
+    p.threads = v.f16 == kDcnStaged ? v.f16_threads : 512;
+    for (int g = 0; g < d.G; ++g) {
+      const bool lds = v.f16 == kDcnAuto && one_deform_group(d, g);
+      if (extras && !lds) return BEVOPS_NOT_SUPPORTED;
+      if (!lds || p.path == kDcnLds) continue;
+      // the first group the LDS-DMA kernel takes: tile width and tail plan, the same for every group
+      const int n_cus = cus();
+      if (n_cus <= 0) return BEVOPS_FAILURE;
+      // 128-pixel tiles (weights fetched once per 128 pixels) when they still give every CU a block ... or at least
+      // every second CU: base stage 4 (136 blocks of 128 pixels) 105 us vs 118 us with 272 blocks of 64 pixels
+      // (profiles/r02/dcn_time.jsonl) -- 16 waves on half the CUs beat 8 waves on all
+      const size_t wide_blocks = ((N + Glds<4>::kN - 1) / Glds<4>::kN) * ((cout_g + kFM - 1) / kFM);
+      p.WN = v.wide || (!v.no_tail && wide_blocks * 2 >= (size_t)n_cus) ? 4 : 2;
+      const int n_slots = slots(c, p.WN);
+      if (n_slots <= 0) return BEVOPS_FAILURE;
+      const WsLayout w = ws_layout(d, es);
+      const int grid_x = (int)((N + 32 * p.WN - 1) / (32 * p.WN)), grid_y = (cout_g + kFM - 1) / kFM;
+      p.tail = v.no_tail ? DcnTail{0, 1}
+                         : plan_tail(grid_x * grid_y, grid_y, KK, n_slots, w.total - w.col, (size_t)256 * p.WN * 32 * sizeof(float));
+      p.partial = static_cast<char *>(c.workspace) + w.col;
+      p.path = kDcnLds;
     }
+    return BEVOPS_SUCCESS;
   }
-  const dim3 grid2((unsigned)(tp.tail_tiles * tp.split + tp.main_tiles), grid.y);
-  // tp.rotate: 0 = round 6's order (SCHED 4), 1 = the round-2 rotation, 2 = one order for all waves (rounds 2-5)
-  auto kern = tp.rotate == 0 ? dcn_glds_f16_kernel<WN, 4> : dcn_glds_f16_kernel<WN, 0>;
-  if (tp.rotate == 0) {
-    static thread_local int lds_set[2] = {0, 0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (lds_set[WN == 4] != dev + 1) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              Glds<WN>::kLds) != hipSuccess)
-        return BEVOPS_FAILURE;
-      lds_set[WN == 4] = dev + 1;
-    }
-  }
-  hipLaunchKernelGGL(kern, grid2, dim3(Glds<WN>::kThreads), Glds<WN>::kLds, st, xt,
-                     (const __half *)offset, (const __half *)mask, wt, (const __half *)bias, (__half *)output, d,
-                     g, tp);
+  if (extras) return BEVOPS_NOT_SUPPORTED;
+  p.path = kDcnGemm;
+  const int V = es == 2 ? 8 : 4;
+  const bool vec = cin_g % V == 0 && (d.Cin / d.DG) % V == 0;
+  if ((N * KK * (d.Cin / (vec ? V : 1)) + 255) / 256 > 0x7FFFFFFFull) return BEVOPS_NOT_SUPPORTED;
+  // fp16, ragged K: one thread per output element
+  if (es == 2 && (KK * cin_g) % 8 != 0 && ((size_t)cout_g * N + 255) / 256 > 0x7FFFFFFFull) return BEVOPS_NOT_SUPPORTED;
+  return BEVOPS_SUCCESS;
+}
+
+// the LDS-DMA kernel of conv group g with the plan's tail
+template <int WN>
+int launch_lds_f16(const DcnCall &c, const DcnPlan &p, int g, const __half *xt, const __half *wt) {
+  const ConvDims &d = c.d;
+  const size_t N = (size_t)d.B * d.Ho * d.Wo;
+  const dim3 grid((unsigned)((N + Glds<WN>::kN - 1) / Glds<WN>::kN), (d.Cout / d.G + kFM - 1) / kFM);
+  const TailPlan tp{p.tail.tiles, p.tail.split, (int)grid.x - p.tail.tiles,
+                    p.tail.tiles ? reinterpret_cast<float *>(p.partial) : nullptr, c.nhwc ? 1 : 0, c.relu ? 1 : 0,
+                    c.om_channels};
+  hipLaunchKernelGGL(dcn_glds_f16_kernel<WN>, dim3((unsigned)(tp.tail_tiles * tp.split + tp.main_tiles), grid.y),
+                     dim3(Glds<WN>::kThreads), Glds<WN>::kLds, c.stream, xt, (const __half *)c.offset,
+                     (const __half *)c.mask, wt, (const __half *)c.bias, (__half *)c.output, d, g, tp);
   if (tp.tail_tiles)
-    hipLaunchKernelGGL(dcn_tail_finish_kernel<WN>, dim3((unsigned)tp.tail_tiles, grid.y, 8),
-                       dim3(Glds<WN>::kThreads), 0, st, (const __half *)bias, (__half *)output, d, g, tp);
+    hipLaunchKernelGGL(dcn_tail_finish_kernel<WN>, dim3((unsigned)tp.tail_tiles, grid.y, 8), dim3(Glds<WN>::kThreads), 0,
+                       c.stream, (const __half *)c.bias, (__half *)c.output, d, g, tp);
   return launch_status();
 }
 
 template <typename T>
-int run(const void *input, const void *offset, const void *mask, const void *weight,
-        const void *bias, void *output, void *workspace, const ConvDims &d, hipStream_t st,
-        bool weight_is_packed = false, bool nhwc_io = false, bool relu = false, int om_channels = 0) {
+int launch_fp(const DcnCall &c, const DcnPlan &p) {
+  const ConvDims &d = c.d;
+  hipStream_t st = c.stream;
   const WsLayout w = ws_layout(d, sizeof(T));
-  char *ws = static_cast<char *>(workspace);
+  char *ws = static_cast<char *>(c.workspace);
   T *xt = reinterpret_cast<T *>(ws + w.xt);
   T *wt = reinterpret_cast<T *>(ws + w.wt);
   T *col = reinterpret_cast<T *>(ws + w.col);
   const int HW = d.H * d.W, KK = d.Kh * d.Kw, cin_g = d.Cin / d.G, cout_g = d.Cout / d.G;
   const size_t N = (size_t)d.B * d.Ho * d.Wo;
-  if (N > 0x7FFFFFFFull || (size_t)d.B * d.Cin * HW > 0x7FFFFFFF00ull) return BEVOPS_NOT_SUPPORTED;
-  const bool fits32 = (size_t)d.B * d.Cin * HW * 2 < 0xFFFFFF00ull && (size_t)d.Cout * cin_g * KK * 2 < 0xFFFFFF00ull;
-  if (nhwc_io)  // the caller's tensor already is the [B, H, W, Cin] image the gather wants
-    xt = const_cast<T *>(static_cast<const T *>(input));
-  else if (sizeof(T) == 2 && HW % 4 == 0 && d.Cin % 8 == 0 && aligned16(input) && !g_mdconv_old_copy)
+  if (p.copy == kDcnCopyNone)
+    xt = const_cast<T *>(static_cast<const T *>(c.input));
+  else if (p.copy == kDcnCopyQuad)
     hipLaunchKernelGGL(nchw_to_nhwc_f16q_kernel, dim3((HW + 127) / 128, (d.Cin + 63) / 64, d.B), dim3(256), 0, st,
-                       (const __half *)input, (__half *)xt, d.Cin, HW);
-  else if (sizeof(T) == 2 && HW % 8 == 0 && d.Cin % 8 == 0 && aligned16(input))   // variant 12: the r01 copy kernel (A/B)
-    hipLaunchKernelGGL(nchw_to_nhwc_f16v_kernel, dim3((HW + 63) / 64, (d.Cin + 63) / 64, d.B), dim3(256), 0, st,
-                       (const __half *)input, (__half *)xt, d.Cin, HW);
+                       (const __half *)c.input, (__half *)xt, d.Cin, HW);
   else
     hipLaunchKernelGGL((nchw_to_nhwc_kernel<T>), dim3((HW + 31) / 32, (d.Cin + 31) / 32, d.B), dim3(256),
-                       0, st, (const T *)input, xt, d.Cin, HW);
+                       0, st, (const T *)c.input, xt, d.Cin, HW);
   const size_t wtot = (size_t)d.Cout * cin_g * KK;
-  if (weight_is_packed)  // [Cout][tap][Cin/groups] image made by bevops_mdconv_pack_weight
-    wt = const_cast<T *>(static_cast<const T *>(weight));
+  if (!p.repack)  // [Cout][tap][Cin/groups] image made by bevops_mdconv_pack_weight
+    wt = const_cast<T *>(static_cast<const T *>(c.weight));
   else
     hipLaunchKernelGGL((repack_weight_kernel<T>), dim3((unsigned)((wtot + 255) / 256)), dim3(256), 0, st,
-                       (const T *)weight, wt, d.Cout, cin_g, KK, KK * cin_g);
+                       (const T *)c.weight, wt, d.Cout, cin_g, KK, KK * cin_g);
   if constexpr (sizeof(T) == 2) {
-    // fused implicit GEMM: a 64-channel K chunk must sit inside one group and one deform group
-    if (g_mdconv_variant != 1 && fits32 && cin_g % kFK == 0 && (d.Cin / d.DG) % kFK == 0) {
+    if (p.path != kDcnGemm) {
       const dim3 grid((unsigned)((N + kFN - 1) / kFN), (cout_g + kFM - 1) / kFM);
       for (int g = 0; g < d.G; ++g) {
-        const bool one_dg = cin_g <= d.Cin / d.DG && (g * cin_g) / (d.Cin / d.DG) == (g * cin_g + cin_g - 1) / (d.Cin / d.DG);
-        if ((nhwc_io || relu || om_channels) && !(g_mdconv_variant == 0 && one_dg)) return BEVOPS_NOT_SUPPORTED;
-        if (g_mdconv_variant == 0 && one_dg) {
-          // 128-pixel tiles (weights fetched once per 128 pixels) when they still give every CU a block
-          int cus = 0, dev = 0;
-          if (hipGetDevice(&dev) != hipSuccess ||
-              hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            return BEVOPS_FAILURE;
-          const size_t wide_blocks = ((N + Glds<4>::kN - 1) / Glds<4>::kN) * ((cout_g + kFM - 1) / kFM);
-          // ... or at least every second CU: base stage 4 (136 blocks of 128 pixels) 105 us vs 118 us with
-          // 272 blocks of 64 pixels (profiles/r02/dcn_time.jsonl) -- 16 waves on half the CUs beat 8 waves on all
-          const bool wide = g_mdconv_wide || (!g_mdconv_no_tail && wide_blocks * 2 >= (size_t)cus);
-          const int rc = wide
-                             ? launch_glds<4>((const __half *)xt, offset, mask, (const __half *)wt, bias, output, d, g,
-                                              ws + w.col, w.total - w.col, nhwc_io, relu, !g_mdconv_no_tail, om_channels, st)
-                             : launch_glds<2>((const __half *)xt, offset, mask, (const __half *)wt, bias, output, d, g,
-                                              ws + w.col, w.total - w.col, nhwc_io, relu, !g_mdconv_no_tail, om_channels, st);
+        if (p.path == kDcnLds && one_deform_group(d, g)) {
+          const int rc = p.WN == 4 ? launch_lds_f16<4>(c, p, g, (const __half *)xt, (const __half *)wt)
+                                   : launch_lds_f16<2>(c, p, g, (const __half *)xt, (const __half *)wt);
           if (rc != BEVOPS_SUCCESS) return rc;
-        } else if (g_mdconv_variant == 2)  // A/B: the 4-wave block of r01c
-          hipLaunchKernelGGL(dcn_fused_f16_kernel<256>, grid, dim3(256), 0, st, (const __half *)xt,
-                             (const __half *)offset, (const __half *)mask, (const __half *)wt,
-                             (const __half *)bias, (__half *)output, d, g);
-        else
-          hipLaunchKernelGGL(dcn_fused_f16_kernel<512>, grid, dim3(512), 0, st, (const __half *)xt,
-                             (const __half *)offset, (const __half *)mask, (const __half *)wt,
-                             (const __half *)bias, (__half *)output, d, g);
+        } else {
+          auto staged = p.threads == 256 ? dcn_fused_f16_kernel<256> : dcn_fused_f16_kernel<512>;  // 256: the 4-wave block of r01c
+          hipLaunchKernelGGL(staged, grid, dim3(p.threads), 0, st, (const __half *)xt, (const __half *)c.offset,
+                             (const __half *)c.mask, (const __half *)wt, (const __half *)c.bias, (__half *)c.output, d, g);
+        }
       }
       return launch_status();
     }
   }
-  if (nhwc_io || relu || om_channels) return BEVOPS_NOT_SUPPORTED;  // only the fused fp16 kernel has these
   constexpr int VMAX = sizeof(T) == 2 ? 8 : 4;
   const bool vec = cin_g % VMAX == 0 && (d.Cin / d.DG) % VMAX == 0;
-  {
-    const int V = vec ? VMAX : 1;
-    const size_t threads = N * KK * (d.Cin / V);
-    const size_t blocks = (threads + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) return BEVOPS_NOT_SUPPORTED;
-    if (vec)
-      hipLaunchKernelGGL((im2col_nhwc_kernel<T, VMAX>), dim3((unsigned)blocks), dim3(256), 0, st, xt,
-                         (const T *)offset, (const T *)mask, col, d);
-    else
-      hipLaunchKernelGGL((im2col_nhwc_kernel<T, 1>), dim3((unsigned)blocks), dim3(256), 0, st, xt,
-                         (const T *)offset, (const T *)mask, col, d);
-  }
+  const size_t blocks = (N * KK * (d.Cin / (vec ? VMAX : 1)) + 255) / 256;
+  auto im2col = vec ? im2col_nhwc_kernel<T, VMAX> : im2col_nhwc_kernel<T, 1>;
+  hipLaunchKernelGGL(im2col, dim3((unsigned)blocks), dim3(256), 0, st, xt, (const T *)c.offset, (const T *)c.mask, col, d);
   const int Kg = KK * cin_g;
   for (int g = 0; g < d.G; ++g) {
     const GemmEpi e{d.Ho * d.Wo, d.Cout, g * cout_g};
     const T *Ag = wt + (size_t)g * cout_g * Kg;
     const T *Bg = col + (size_t)g * N * Kg;
     if constexpr (sizeof(T) == 2) {
-      if (Kg % 8 == 0) {
+      if (Kg % 8 == 0)
         hipLaunchKernelGGL(gemm_tn_f16_kernel, dim3((unsigned)((N + kBN - 1) / kBN), (cout_g + kBM - 1) / kBM),
-                           dim3(256), 0, st, (const __half *)Ag, (const __half *)Bg, (const __half *)bias,
-                           (__half *)output, cout_g, (int)N, Kg, e);
-        continue;
-      }
-      const size_t outs = (size_t)cout_g * N;  // ragged K: scalar fallback
-      if ((outs + 255) / 256 > 0x7FFFFFFFull) return BEVOPS_NOT_SUPPORTED;
-      hipLaunchKernelGGL(gemm_tn_f16_ragged_kernel, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, st,
-                         (const __half *)Ag, (const __half *)Bg, (const __half *)bias, (__half *)output, cout_g,
-                         (int)N, Kg, e);
+                           dim3(256), 0, st, (const __half *)Ag, (const __half *)Bg, (const __half *)c.bias,
+                           (__half *)c.output, cout_g, (int)N, Kg, e);
+      else  // ragged K: scalar fallback
+        hipLaunchKernelGGL(gemm_tn_f16_ragged_kernel, dim3((unsigned)(((size_t)cout_g * N + 255) / 256)), dim3(256), 0,
+                           st, (const __half *)Ag, (const __half *)Bg, (const __half *)c.bias, (__half *)c.output,
+                           cout_g, (int)N, Kg, e);
     } else {
       hipLaunchKernelGGL(gemm_tn_f32_kernel, dim3((unsigned)((N + 63) / 64), (cout_g + 63) / 64), dim3(256),
-                         0, st, (const float *)Ag, (const float *)Bg, (const float *)bias, (float *)output,
+                         0, st, (const float *)Ag, (const float *)Bg, (const float *)c.bias, (float *)c.output,
                          cout_g, (int)N, Kg, e);
     }
   }
   return launch_status();
+}
+
+// The fp32 / fp16 entries behind their argument lists: validate, plan, launch
+int forward_fp(const DcnCall &c) {
+  if (!c.input || !c.offset || (!c.mask && !c.om_channels) || !c.weight || !c.output || !c.workspace) return BEVOPS_BAD_PARAM;
+  const ConvDims &d = c.d;
+  if (d.B == 0) return BEVOPS_BAD_PARAM;
+  if (c.om_channels && (c.om_channels < d.DG * 3 * d.Kh * d.Kw || (c.om_channels & 1))) return BEVOPS_BAD_PARAM;
+  if (c.dtype != BEVOPS_F32 && c.dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  // the raw offset-convolution output is read as [2 KK offsets | KK mask logits] of ONE deform group (a pack with
+  // several groups lays its channels out differently, and the 32-bit read of an (h, w) pair at half-word
+  // dg * 3 KK + 2 tap would be misaligned for odd dg * KK); bevops_mdconv_forward_int8_nhwc draws the same line
+  if (c.om_channels && d.DG != 1) return BEVOPS_NOT_SUPPORTED;
+  if (c.workspace_bytes < ws_layout(d, c.dtype == BEVOPS_F32 ? 4 : 2).total) return BEVOPS_BAD_PARAM;
+  if (!aligned16(c.workspace) || (c.packed && !aligned16(c.weight))) return BEVOPS_BAD_PARAM;
+  DcnPlan p;
+  const int rc = plan_fp(c, g_dcn_variant, device_cus, lds_f16_slots, p);
+  if (rc != BEVOPS_SUCCESS) return rc;
+  return c.dtype == BEVOPS_F32 ? launch_fp<float>(c, p) : launch_fp<__half>(c, p);
 }
 
 }  // namespace
@@ -1132,12 +1039,10 @@ int run(const void *input, const void *offset, const void *mask, const void *wei
 using namespace bevops;
 
 extern "C" int bevops_mdconv_set_variant(int variant) {
-  const int prev = g_mdconv_no_tail ? 4 : (g_mdconv_wide ? 5 : g_mdconv_variant);
-  g_mdconv_no_tail = variant == 4;
-  g_mdconv_wide = variant == 5;
-  g_mdconv_rotate = variant == 7 ? 1 : (variant == 13 ? 2 : 0);
-  g_mdconv_old_copy = variant == 12;
-  g_mdconv_variant = (variant == 4 || variant == 5 || variant == 7 || variant == 12 || variant == 13) ? 0 : variant;
+  const int prev = g_dcn_variant.id;
+  g_dcn_variant = kDcnVariants[0];
+  for (const DcnVariant &v : kDcnVariants)
+    if (v.id == variant) g_dcn_variant = v;
   return prev;
 }
 
@@ -1185,31 +1090,6 @@ extern "C" int bevops_mdconv_pack_weight(int dtype, const void *weight, void *pa
   return launch_status();
 }
 
-static int mdconv_forward_impl(int dtype, const void *input, const void *offset, const void *mask,
-                               const void *weight, const void *bias, void *output, void *workspace,
-                               size_t workspace_bytes, int B, int Cin, int H, int W, int Cout, int Kh,
-                               int Kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
-                               int dil_w, int groups, int deform_groups, void *stream, bool packed,
-                               bool nhwc_io = false, bool relu = false, int om_channels = 0) {
-  if (!input || !offset || (!mask && !om_channels) || !weight || !output || !workspace) return BEVOPS_BAD_PARAM;
-  if (om_channels && (om_channels < deform_groups * 3 * Kh * Kw || (om_channels & 1))) return BEVOPS_BAD_PARAM;
-  ConvDims d;
-  if (!make_dims(d, B, Cin, H, W, Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w,
-                 groups, deform_groups))
-    return BEVOPS_BAD_PARAM;
-  if (dtype != BEVOPS_F32 && dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
-  // the raw offset-convolution output is read as [2 KK offsets | KK mask logits] of ONE deform group (a pack with
-  // several groups lays its channels out differently, and the 32-bit read of an (h, w) pair at half-word
-  // dg * 3 KK + 2 tap would be misaligned for odd dg * KK); bevops_mdconv_forward_int8_nhwc draws the same line
-  if (om_channels && deform_groups != 1) return BEVOPS_NOT_SUPPORTED;
-  if (workspace_bytes < ws_layout(d, dtype == BEVOPS_F32 ? 4 : 2).total) return BEVOPS_BAD_PARAM;
-  if (!aligned16(workspace) || (packed && !aligned16(weight))) return BEVOPS_BAD_PARAM;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == BEVOPS_F32)
-    return run<float>(input, offset, mask, weight, bias, output, workspace, d, st, packed, nhwc_io, relu, om_channels);
-  return run<__half>(input, offset, mask, weight, bias, output, workspace, d, st, packed, nhwc_io, relu, om_channels);
-}
-
 extern "C" int bevops_mdconv_forward_nhwc(int dtype, const void *input_nhwc, const void *offset,
                                           const void *mask, const void *packed_weight,
                                           const void *bias, void *output_nhwc, int relu,
@@ -1220,10 +1100,13 @@ extern "C" int bevops_mdconv_forward_nhwc(int dtype, const void *input_nhwc, con
                                           int groups, int deform_groups, void *stream) {
   if (dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
   if (input_nhwc && !aligned16(input_nhwc)) return BEVOPS_BAD_PARAM;
-  return mdconv_forward_impl(dtype, input_nhwc, offset, mask, packed_weight, bias, output_nhwc,
-                             workspace, workspace_bytes, B, Cin, H, W, Cout, Kh, Kw, stride_h,
-                             stride_w, pad_h, pad_w, dil_h, dil_w, groups, deform_groups, stream, true,
-                             true, relu != 0, offset_mask_channels);
+  DcnCall c = dcn_call(dtype, input_nhwc, offset, mask, packed_weight, bias, output_nhwc, workspace, workspace_bytes, B,
+                       Cin, H, W, Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, deform_groups,
+                       stream);
+  c.packed = c.nhwc = true;
+  c.relu = relu != 0;
+  c.om_channels = offset_mask_channels;
+  return forward_fp(c);
 }
 
 extern "C" int bevops_mdconv_forward_packed(int dtype, const void *input, const void *offset,
@@ -1233,9 +1116,10 @@ extern "C" int bevops_mdconv_forward_packed(int dtype, const void *input, const 
                                             int Cout, int Kh, int Kw, int stride_h, int stride_w,
                                             int pad_h, int pad_w, int dil_h, int dil_w, int groups,
                                             int deform_groups, void *stream) {
-  return mdconv_forward_impl(dtype, input, offset, mask, packed_weight, bias, output, workspace,
-                             workspace_bytes, B, Cin, H, W, Cout, Kh, Kw, stride_h, stride_w, pad_h,
-                             pad_w, dil_h, dil_w, groups, deform_groups, stream, true);
+  DcnCall c = dcn_call(dtype, input, offset, mask, packed_weight, bias, output, workspace, workspace_bytes, B, Cin, H, W,
+                       Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, deform_groups, stream);
+  c.packed = true;
+  return forward_fp(c);
 }
 
 extern "C" int bevops_mdconv_forward(int dtype, const void *input, const void *offset,
@@ -1244,7 +1128,7 @@ extern "C" int bevops_mdconv_forward(int dtype, const void *input, const void *o
                                      int Cin, int H, int W, int Cout, int Kh, int Kw, int stride_h,
                                      int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
                                      int groups, int deform_groups, void *stream) {
-  return mdconv_forward_impl(dtype, input, offset, mask, weight, bias, output, workspace, workspace_bytes,
-                             B, Cin, H, W, Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w,
-                             groups, deform_groups, stream, false);
+  return forward_fp(dcn_call(dtype, input, offset, mask, weight, bias, output, workspace, workspace_bytes, B, Cin, H, W,
+                             Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, deform_groups,
+                             stream));
 }

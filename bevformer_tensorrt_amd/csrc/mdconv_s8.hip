@@ -529,8 +529,6 @@ __device__ __forceinline__ unsigned s8_mask4(const int (&x)[4], float m) {
   return lo | hi;
 }
 
-// ABL (timing experiments; 1..8 give wrong results): 1 no gathers, 2 no producer VALU, 4 no weight DMA, 8 no MFMA,
-// 16 wave halves in opposite phase order (correct results; measured no faster: the kernel is VALU-bound)
 // ENG (the INT8 engine's channels-last block, bevops_mdconv_forward_int8_nhwc): `xt` is the caller's SIGNED int8
 // [B, H, W, Cin] activation itself (no copy: the +128 bias of the unsigned dot is one v_xor per gathered dword),
 // `offset` is the raw fp16 [B, Ho, Wo, om_channels] output of the pack's offset convolution -- its offsets and the
@@ -569,7 +567,7 @@ __device__ __forceinline__ void s8_store4_nhwc(int8_t *__restrict__ out, const f
   }
 }
 
-template <int WN, int ABL, bool ENG = false, bool FAST = false>
+template <int WN, bool ENG = false, bool FAST = false>
 __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_s8_kernel(
     const int8_t *__restrict__ xt, const int8_t *__restrict__ offset, const int8_t *__restrict__ mask,
     const int8_t *__restrict__ wt, const float *__restrict__ bias, int8_t *__restrict__ out, ConvDims d, int g,
@@ -611,9 +609,8 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_s8_kernel(
   typedef __attribute__((address_space(3))) char lds_char;
   const unsigned b_lds = (unsigned)(size_t)((lds_char *)smem) + (unsigned)(2 * kGA) +
                          (unsigned)(pp * 128 + ((cq ^ swz8(pp)) << 4));   // LDS byte address of the thread's B chunk
-  // ABL & 32 (round 6, the default order: see the loop): the lower half of the waves issues all the weight pieces
-  constexpr bool kLowerDma = (ABL & 32) != 0;
-  constexpr int kPcS = kLowerDma ? 2 * kPc : kPc;
+  // the lower half of the waves issues all the weight pieces (see the loop)
+  constexpr int kPcS = 2 * kPc;
   unsigned a_off[kPcS];
 #pragma unroll
   for (int j = 0; j < kPcS; ++j) {
@@ -675,10 +672,6 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_s8_kernel(
   int f_neg = 0, c_neg = 0;      // -128 * their sum
   float f_m = 0.f, c_m = 0.f;    // mask value
   uint4 rb[4];
-  if constexpr (ABL & 1) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) rb[q] = make_uint4(tid + q, tid * 3u, tid * 5u + q, tid * 7u);
-  }
   auto footprint = [&](int tap) {
     const int i = tap / d.Kw, j = tap - i * d.Kw;
     const int qoh = Om[(2 * tap) * kN + pp], qow = Om[(2 * tap + 1) * kN + pp], qm = Om[(2 * KK + tap) * kN + pp];
@@ -719,22 +712,18 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_s8_kernel(
   int g_tap = tap_begin, g_chunk = 0, w_tap = tap_begin, w_chunk = 0;
   auto gather_next = [&]() {      // corners of the gather pipeline's current step -> rb; then advance
     if (g_chunk == 0) footprint(g_tap);
-    if constexpr (!(ABL & 1)) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        rb[q] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, fidx[q], g_chunk * kStepK, 0));
-    }
+    for (int q = 0; q < 4; ++q)
+      rb[q] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, fidx[q], g_chunk * kStepK, 0));
     if (++g_chunk == chunks) { g_chunk = 0; g_tap = g_tap + 1 < KK ? g_tap + 1 : 0; }
   };
   typedef __attribute__((address_space(3))) void lds_void;
   auto weights_next = [&](int buf) {
     const int a_s = w_tap * cin_g + w_chunk * kStepK;
     char *adst = smem + buf * kGA + wave * (kPcS * 1024);
-    if constexpr (!(ABL & 4)) {
 #pragma unroll
-      for (int j = 0; j < kPcS; ++j)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void *)(adst + j * 1024), 16, (int)a_off[j], a_s, 0, 0);
-    }
+    for (int j = 0; j < kPcS; ++j)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void *)(adst + j * 1024), 16, (int)a_off[j], a_s, 0, 0);
     if (++w_chunk == chunks) { w_chunk = 0; w_tap = w_tap + 1 < KK ? w_tap + 1 : 0; }
   };
   const int magic = 65793, half = 1 << 23;   // round(2^24 / 255): exact T2int8(t / 255), see msda_hm4.hip
@@ -749,19 +738,15 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_s8_kernel(
     unsigned res[4];
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
-      if constexpr (ABL & 2) {
-        res[v] = c0w[v] ^ c1w[v] ^ c2w[v] ^ (c3w[v] + __float_as_uint(c_m));
+      unsigned tr[4];
+      s8_transpose(c0w[v], c1w[v], c2w[v], c3w[v], tr);
+      int xq[4];
+      s8_quad(tr, c_aw, c_neg, magic, half, xq);
+      if constexpr (FAST) {   // the requantised value sits in the top byte of each xq[c]
+        res[v] = __builtin_amdgcn_perm((unsigned)xq[1], (unsigned)xq[0], 0x0c0c0703u) |
+                 __builtin_amdgcn_perm((unsigned)xq[3], (unsigned)xq[2], 0x07030c0cu);
       } else {
-        unsigned tr[4];
-        s8_transpose(c0w[v], c1w[v], c2w[v], c3w[v], tr);
-        int xq[4];
-        s8_quad(tr, c_aw, c_neg, magic, half, xq);
-        if constexpr (FAST) {   // the requantised value sits in the top byte of each xq[c]
-          res[v] = __builtin_amdgcn_perm((unsigned)xq[1], (unsigned)xq[0], 0x0c0c0703u) |
-                   __builtin_amdgcn_perm((unsigned)xq[3], (unsigned)xq[2], 0x07030c0cu);
-        } else {
-          res[v] = s8_mask4(xq, c_m);
-        }
+        res[v] = s8_mask4(xq, c_m);
       }
     }
     // hand-written store: behind a compiler-visible LDS store the waitcnt pass drains vmcnt to 0 (it cannot
@@ -780,7 +765,7 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_s8_kernel(
   produce(0);
   __builtin_amdgcn_sched_barrier(0);
   const bool upper = __builtin_amdgcn_readfirstlane(wave) >= kTh / 128;
-  if (!kLowerDma || !upper) weights_next(0);
+  if (!upper) weights_next(0);
   if (n_my_steps > 1) next_gathers();
   if (n_my_steps > 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -789,13 +774,7 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_s8_kernel(
   // iteration `step`: tiles of `step` in buffer step & 1, raw corners of step + 1 in rb (a step old).  The
   // weight DMA of step + 1 is always issued BEFORE the gathers of step + 2, so vmcnt(4) in front of the
   // barrier retires it and leaves the gathers in flight.
-  // ABL & 16: the two halves of the block's waves run the step's phases in opposite order (every SIMD holds
-  // two waves of each half): while the early half does its VALU work the late half runs the MFMAs + fragment
-  // reads.  Measured no faster (68.6 vs 67.6 us): the producer VALU work is ~70 % of the SIMD time whatever
-  // the order (profiles/r02/int8_dcn_pmc.txt), so the default keeps all waves in the same order.
-  const bool late = (ABL & 16) && __builtin_amdgcn_readfirstlane(wave) >= kTh / 128;
   auto mfma_step = [&](int buf) {
-    if constexpr (ABL & 8) return;
     const char *Ab = smem + buf * kGA;
     const char *Bb = smem + 2 * kGA + buf * kGB;
 #pragma unroll
@@ -810,57 +789,28 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_s8_kernel(
       for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b, acc[i], 0, 0, 0);
     }
   };
-  // ONE code path for both halves: the late half is the same loop rotated by half an iteration -- its barrier
-  // sits between the producer work and the MFMAs, and it runs MFMA(step + 1) where the early half runs
-  // MFMA(step); MFMA(0) is peeled.  Between two barriers the early half does producer(s + 1), DMA, gathers,
-  // MFMA(s); the late half DMA, gathers, MFMA(s), producer(s + 1).
-  if constexpr (kLowerDma) {
-    // Round 6 (the fp16 kernel's finding, mdconv.hip / design/dcn.md): a step's vector-memory instructions leave the
-    // CU's load path oldest wave first at ~0.4 lines per clock, and a wave cannot start its matrix segment before its
-    // own loads are accepted.  The lower half of the waves issues ALL the weight pieces and runs
-    //   producer -> DMA -> gathers -> MFMA,    the upper half    MFMA -> producer -> gathers:
-    // an upper wave has no load in front of its matrix segment.  One loop body; same buffers, same sums (int32: exact).
-    for (int step = 0; step < n_my_steps; ++step) {
-      const bool more1 = step + 1 < n_my_steps, more2 = step + 2 < n_my_steps;
-      if (!upper && more1) produce((step + 1) & 1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (!upper && more1) weights_next((step + 1) & 1);
-      if (!upper && more2) next_gathers();
-      __builtin_amdgcn_sched_barrier(0);
-      mfma_step(step & 1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (upper && more1) produce((step + 1) & 1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (upper && more2) next_gathers();
-      __builtin_amdgcn_sched_barrier(0);
-      if (more2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-  } else {
-  if (late) {
-    if (n_my_steps > 1) weights_next(1);
-    mfma_step(0);
-  }
+  // The fp16 kernel's finding (round 6, mdconv.hip / design/dcn.md): a step's vector-memory instructions leave the
+  // CU's load path oldest wave first at ~0.4 lines per clock, and a wave cannot start its matrix segment before its
+  // own loads are accepted.  The lower half of the waves issues ALL the weight pieces and runs
+  //   producer -> DMA -> gathers -> MFMA,    the upper half    MFMA -> producer -> gathers:
+  // an upper wave has no load in front of its matrix segment.  One loop body; same buffers, same sums (int32: exact).
   for (int step = 0; step < n_my_steps; ++step) {
     const bool more1 = step + 1 < n_my_steps, more2 = step + 2 < n_my_steps;
-    if (more1) produce((step + 1) & 1);
+    if (!upper && more1) produce((step + 1) & 1);
     __builtin_amdgcn_sched_barrier(0);
-    if (late) {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-    if (late ? more2 : more1) weights_next(late ? (step & 1) : ((step + 1) & 1));
-    if (more2) next_gathers();
+    if (!upper && more1) weights_next((step + 1) & 1);
+    if (!upper && more2) next_gathers();
     __builtin_amdgcn_sched_barrier(0);
-    if (late ? more1 : true) mfma_step(late ? ((step + 1) & 1) : (step & 1));
-    if (!late) {
-      if (more2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
+    mfma_step(step & 1);
+    __builtin_amdgcn_sched_barrier(0);
+    if (upper && more1) produce((step + 1) & 1);
+    __builtin_amdgcn_sched_barrier(0);
+    if (upper && more2) next_gathers();
+    __builtin_amdgcn_sched_barrier(0);
+    if (more2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
   }
-  }   // (!kLowerDma)
   if (is_tail) {  // int32 partials (exact in any order), thread-private layout shared with the finish kernel
     int4 *pq = reinterpret_cast<int4 *>(tp.partial) +
                ((((size_t)part * tp.tail_tiles + (ntile - tp.main_tiles)) * gridDim.y + blockIdx.y) * 8) * kTh + tid;
@@ -938,173 +888,209 @@ __global__ __launch_bounds__(256 * WN) void dcn_tail_finish_s8_kernel(const floa
   }
 }
 
-template <int WN, int ABL, bool ENG = false, bool FAST = false>
-int glds_s8_resident_blocks() {
-  static thread_local int cached_dev = -1, cached = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (dev == cached_dev) return cached;
-  int per_cu = 0, cus = 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(dcn_glds_s8_kernel<WN, ABL, ENG, FAST>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, GldsS8<WN>::kLds) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dcn_glds_s8_kernel<WN, ABL, ENG, FAST>, Glds<WN>::kThreads,
-                                                   GldsS8<WN>::kLds) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 0;
-  cached_dev = dev;
-  cached = per_cu * cus;
-  return cached;
+// ---- host side: plan, then launch (DcnCall, DcnVariant, DcnPlan: mdconv.h) ------------------------------------
+// The LDS-DMA instantiation of a call: tile width x {plugin entries, engine block exact, engine block fast}
+typedef void (*LdsS8Kernel)(const int8_t *, const int8_t *, const int8_t *, const int8_t *, const float *, int8_t *,
+                            ConvDims, int, int, float, float, float, float, TailPlan, S8Eng);
+typedef void (*FinishS8Kernel)(const float *, int8_t *, ConvDims, int, float, float, TailPlan, S8Eng);
+struct LdsS8 {
+  LdsS8Kernel kern;
+  FinishS8Kernel finish;
+  int (*slots)(int threads, int lds);
+  int threads, lds;
+};
+template <int WN, bool ENG, bool FAST>
+LdsS8 lds_s8_of() {
+  return LdsS8{dcn_glds_s8_kernel<WN, ENG, FAST>, dcn_tail_finish_s8_kernel<WN, ENG>,
+               resident_blocks<dcn_glds_s8_kernel<WN, ENG, FAST>>, Glds<WN>::kThreads, GldsS8<WN>::kLds};
+}
+LdsS8 lds_s8(const DcnCall &c, int wn) {
+  if (!c.nhwc) return wn == 4 ? lds_s8_of<4, false, false>() : lds_s8_of<2, false, false>();
+  if (c.exact) return wn == 4 ? lds_s8_of<4, true, false>() : lds_s8_of<2, true, false>();
+  return wn == 4 ? lds_s8_of<4, true, true>() : lds_s8_of<2, true, true>();
+}
+int lds_s8_slots(const DcnCall &c, int wn) {
+  const LdsS8 k = lds_s8(c, wn);
+  return k.slots(k.threads, k.lds);
+}
+// the int8 family plans for 256 CUs where HIP cannot tell (the fp family fails the call)
+int device_cus_or_256() {
+  const int cus = device_cus();
+  return cus > 0 ? cus : 256;
 }
 
-// launch of the int8 LDS-DMA kernel with its tail plan (same plan as launch_glds; int32 partials)
-template <int WN, int ABL, bool ENG = false, bool FAST = false>
-int launch_glds_s8(const int8_t *xt, const void *offset, const void *mask, const int8_t *wt, const void *bias,
-                   void *output, const ConvDims &d, int g, int Kp, char *part_ws, size_t part_room, bool allow_tail,
-                   float s_off, float s_mask, float s_iw, float s_out, hipStream_t st, S8Eng eng = S8Eng{0, 0}) {
-  const int KK = d.Kh * d.Kw, cout_g = d.Cout / d.G;
-  const size_t N = (size_t)d.B * d.Ho * d.Wo;
-  const dim3 grid((unsigned)((N + Glds<WN>::kN - 1) / Glds<WN>::kN), (cout_g + kFM - 1) / kFM);
-  const int slots = glds_s8_resident_blocks<WN, ABL, ENG, FAST>();
-  if (slots <= 0) return BEVOPS_FAILURE;
-  TailPlan tp{0, 1, (int)grid.x, nullptr, 0, 0, 0, 0};
-  const int blocks = (int)(grid.x * grid.y);
-  if (allow_tail && blocks > slots && grid.y == 1) {
-    const int left = blocks % slots;
-    int split = 0;
-    for (int f = KK; f >= 2; --f)
-      if (KK % f == 0 && left * f <= slots) { split = f; break; }
-    const size_t need = (size_t)split * left * Glds<WN>::kThreads * 32 * sizeof(int);
-    if (left > 0 && left * 2 <= slots && split >= 2 && part_room >= need) {
-      tp.tail_tiles = left;
-      tp.split = split;
-      tp.main_tiles = (int)grid.x - left;
-      tp.partial = reinterpret_cast<float *>(part_ws);
-    }
+// The checks the three int8 entries share, in the order they answer
+int validate_s8(const DcnCall &c) {
+  if (!c.input || !c.offset || (!c.mask && !c.nhwc) || !c.weight || !c.output || (!c.workspace && !c.nhwc))
+    return BEVOPS_BAD_PARAM;
+  if (!(c.s_in > 0.f) || !(c.s_off > 0.f) || !(c.s_mask > 0.f) || !(c.s_w > 0.f) || !(c.s_out > 0.f))
+    return BEVOPS_BAD_PARAM;
+  const ConvDims &d = c.d;
+  if (d.B == 0) return BEVOPS_BAD_PARAM;
+  if (!c.nhwc) {
+    if (c.workspace_bytes < ws_layout(d, 1).total || !aligned16(c.workspace) || (c.packed && !aligned16(c.weight)))
+      return BEVOPS_BAD_PARAM;
+    return BEVOPS_SUCCESS;
   }
-  const dim3 grid2((unsigned)(tp.tail_tiles * tp.split + tp.main_tiles), grid.y);
-  hipLaunchKernelGGL((dcn_glds_s8_kernel<WN, ABL, ENG, FAST>), grid2, dim3(Glds<WN>::kThreads), GldsS8<WN>::kLds, st, xt,
-                     (const int8_t *)offset, (const int8_t *)mask, wt, (const float *)bias, (int8_t *)output, d, g,
-                     Kp, s_off, s_mask, s_iw, s_out, tp, eng);
+  const int KK = d.Kh * d.Kw;
+  if (c.om_channels < d.DG * 3 * KK) return BEVOPS_BAD_PARAM;
+  // the raw offset-convolution output is read as [2 KK offsets | KK mask logits] of ONE deform group (the layout of
+  // mmcv's cat(o1, o2) | mask for deform_groups == 1, modules/cnn/dcn.py:70-74); several groups interleave differently
+  if (d.DG != 1) return BEVOPS_NOT_SUPPORTED;
+  if (!aligned16(c.input) || !aligned16(c.weight) || (reinterpret_cast<uintptr_t>(c.output) & 3u) ||
+      (reinterpret_cast<uintptr_t>(c.offset) & 1u))
+    return BEVOPS_BAD_PARAM;
+  return BEVOPS_SUCCESS;
+}
+
+// What an int8 call launches, or the status that rejects it.  Launches nothing.
+int plan_s8(const DcnCall &c, const DcnVariant &v, DcnCusFn cus, DcnSlotsFn slots, DcnPlan &p) {
+  const ConvDims &d = c.d;
+  const int HW = d.H * d.W, KK = d.Kh * d.Kw, cin_g = d.Cin / d.G, cout_g = d.Cout / d.G;
+  const size_t N = (size_t)d.B * d.Ho * d.Wo;
+  const int Kg = KK * cin_g, Kp = (int)kpad(d, 1);
+  const bool fits32 = (size_t)d.B * d.H * d.W * d.Cin < 0xFFFFFF00ull && (size_t)cout_g * Kp < 0xFFFFFF00ull;
+  // LDS-DMA pipelined kernel (section 6c): 128-channel k-steps inside one group and ONE deform group per conv group
+  const bool lds_domain = fits32 && one_deform_group(d) && cin_g % 128 == 0 && 3 * KK <= kSOmRows && Kp == Kg;
+  if (N > 0x7FFFFFFFull) return BEVOPS_NOT_SUPPORTED;
+  // multiScale...Plugin-style precondition (modulatedDeformableConv2dPlugin.cpp:217-219); the engine's block has no
+  // other kernel than the LDS-DMA one
+  if (c.nhwc ? (!lds_domain || cout_g % 4 != 0) : (d.Cin % 4 != 0 || cout_g % 4 != 0)) return BEVOPS_NOT_SUPPORTED;
+  p = DcnPlan{};
+  const size_t n_cus = (size_t)cus();
+  // 128-pixel tiles when they give at least every second CU a block (base stage 3: 272 tiles, 67 us kernel vs 100 us
+  // for the register-staged kernel; stage 4: 136 blocks, 95 us per call vs 117 us for the im2col + GEMM pair and 121 us
+  // with 64-pixel tiles, profiles/r02/dcn_time.jsonl)
+  const size_t wide_blocks = ((N + Glds<4>::kN - 1) / Glds<4>::kN) * ((cout_g + kFM - 1) / kFM);
+  const bool enough = wide_blocks * 2 >= n_cus;
+  p.WN = enough || v.wide ? 4 : 2;
+  size_t room;
+  if (c.nhwc) {
+    p.path = kDcnLds;
+    p.copy = kDcnCopyNone;
+    // the split-K tail's int32 partials live in the caller's workspace (none lent: every tile runs its whole k-loop)
+    p.partial = static_cast<char *>(c.workspace);
+    room = (c.workspace && aligned16(c.workspace)) ? c.workspace_bytes : 0;
+  } else {
+    // the LDS-DMA kernel with enough tiles (or forced); else the register-staged fused kernel (no column buffer) when
+    // a 64-channel chunk stays inside one group and one deform group and there are enough 256 x 64 tiles to give every
+    // CU two blocks (or forced): the base stage-3 call (544 tiles) 117 vs 170 us; stage 4 (272 tiles, one 4-wave block
+    // per CU) 138 vs 130 us keeps the im2col + GEMM pair (profiles/r02)
+    const size_t tiles = ((N + kSN - 1) / kSN) * (size_t)((cout_g + kSM - 1) / kSM);
+    const bool lds = v.s8 != kDcnGemm && v.s8 != kDcnStaged && lds_domain && (enough || v.s8 == kDcnLds || v.wide);
+    const bool staged = v.s8 != kDcnGemm && cin_g % kSK == 0 && (d.Cin / d.DG) % kSK == 0 && fits32 &&
+                        (v.s8 == kDcnStaged || tiles >= 2 * n_cus);
+    p.path = lds ? kDcnLds : (staged ? kDcnStaged : kDcnGemm);
+    p.copy = HW % 4 == 0 && d.Cin % 16 == 0 && aligned16(c.input) ? kDcnCopyQuad : kDcnCopyGeneric;
+    p.repack = !c.packed;
+    p.zero_pad = Kp != Kg;
+    if (p.path == kDcnGemm) {
+      const int V = cin_g % 16 == 0 && (d.Cin / d.DG) % 16 == 0 ? 16 : (cin_g % 4 == 0 && (d.Cin / d.DG) % 4 == 0 ? 4 : 1);
+      if ((N * KK * (d.Cin / V) + 255) / 256 > 0x7FFFFFFFull) return BEVOPS_NOT_SUPPORTED;
+    }
+    const WsLayout w = ws_layout(d, 1);
+    p.partial = static_cast<char *>(c.workspace) + w.col;
+    room = w.total - w.col;
+  }
+  if (p.path != kDcnLds) return BEVOPS_SUCCESS;
+  const int n_slots = slots(c, p.WN);
+  if (n_slots <= 0) return BEVOPS_FAILURE;
+  const int grid_x = (int)((N + 32 * p.WN - 1) / (32 * p.WN)), grid_y = (cout_g + kFM - 1) / kFM;
+  p.tail = v.no_tail ? DcnTail{0, 1}
+                     : plan_tail(grid_x * grid_y, grid_y, KK, n_slots, room, (size_t)256 * p.WN * 32 * sizeof(int));
+  return BEVOPS_SUCCESS;
+}
+
+// the LDS-DMA kernel of conv group g with the plan's tail (int32 partials)
+int launch_lds_s8(const DcnCall &c, const DcnPlan &p, int g, const int8_t *xt, const int8_t *wt, int Kp) {
+  const ConvDims &d = c.d;
+  const LdsS8 k = lds_s8(c, p.WN);
+  const size_t N = (size_t)d.B * d.Ho * d.Wo;
+  const dim3 grid((unsigned)((N + 32 * p.WN - 1) / (32 * p.WN)), (d.Cout / d.G + kFM - 1) / kFM);
+  const TailPlan tp{p.tail.tiles, p.tail.split, (int)grid.x - p.tail.tiles,
+                    p.tail.tiles ? reinterpret_cast<float *>(p.partial) : nullptr, 0, 0, 0};
+  const S8Eng eng{c.om_channels, c.relu ? 1 : 0};
+  const float s_iw = c.s_in * c.s_w;
+  hipLaunchKernelGGL(k.kern, dim3((unsigned)(tp.tail_tiles * tp.split + tp.main_tiles), grid.y), dim3(k.threads), k.lds,
+                     c.stream, xt, (const int8_t *)c.offset, (const int8_t *)c.mask, wt, (const float *)c.bias,
+                     (int8_t *)c.output, d, g, Kp, c.s_off, c.s_mask, s_iw, c.s_out, tp, eng);
   if (tp.tail_tiles)
-    hipLaunchKernelGGL((dcn_tail_finish_s8_kernel<WN, ENG>), dim3((unsigned)tp.tail_tiles, grid.y, 8),
-                       dim3(Glds<WN>::kThreads), 0, st, (const float *)bias, (int8_t *)output, d, g, s_iw, s_out, tp,
-                       eng);
+    hipLaunchKernelGGL(k.finish, dim3((unsigned)tp.tail_tiles, grid.y, 8), dim3(k.threads), 0, c.stream,
+                       (const float *)c.bias, (int8_t *)c.output, d, g, s_iw, c.s_out, tp, eng);
   return launch_status();
 }
 
-int run_s8(const void *input, const void *offset, const void *mask, const void *weight,
-           const void *bias, void *output, void *workspace, const ConvDims &d, float s_in, float s_off,
-           float s_mask, float s_w, float s_out, hipStream_t st, bool weight_is_packed) {
-  const WsLayout w = ws_layout(d, 1);
-  char *ws = static_cast<char *>(workspace);
-  int8_t *xt = reinterpret_cast<int8_t *>(ws + w.xt);
-  int8_t *wt = reinterpret_cast<int8_t *>(ws + w.wt);
-  int8_t *col = reinterpret_cast<int8_t *>(ws + w.col);
+int launch_s8(const DcnCall &c, const DcnPlan &p) {
+  const ConvDims &d = c.d;
+  hipStream_t st = c.stream;
   const int HW = d.H * d.W, KK = d.Kh * d.Kw, cin_g = d.Cin / d.G, cout_g = d.Cout / d.G;
   const size_t N = (size_t)d.B * d.Ho * d.Wo;
-  if (N > 0x7FFFFFFFull) return BEVOPS_NOT_SUPPORTED;
-  // multiScale...Plugin-style precondition (modulatedDeformableConv2dPlugin.cpp:217-219)
-  if (d.Cin % 4 != 0 || cout_g % 4 != 0) return BEVOPS_NOT_SUPPORTED;
-  const int Kg = KK * cin_g;
   const int Kp = (int)kpad(d, 1);
-  if (Kp != Kg) {  // zero the padding columns once (packed weights + column buffer)
-    if (hipMemsetAsync(ws + w.wt, 0, w.total - w.wt, st) != hipSuccess) return BEVOPS_FAILURE;
+  const int8_t *xt = static_cast<const int8_t *>(c.input), *wt = static_cast<const int8_t *>(c.weight);
+  int8_t *col = nullptr;
+  if (!c.nhwc) {
+    const WsLayout w = ws_layout(d, 1);
+    char *ws = static_cast<char *>(c.workspace);
+    col = reinterpret_cast<int8_t *>(ws + w.col);
+    // zero the padding columns once (packed weights + column buffer)
+    if (p.zero_pad && hipMemsetAsync(ws + w.wt, 0, w.total - w.wt, st) != hipSuccess) return BEVOPS_FAILURE;
+    // the fused kernels read the copy u8-biased (v + 128)
+    const bool fused = p.path != kDcnGemm;
+    int8_t *xc = reinterpret_cast<int8_t *>(ws + w.xt);
+    if (p.copy == kDcnCopyQuad)
+      hipLaunchKernelGGL(nchw_to_nhwc_s8v_kernel, dim3((HW + 127) / 128, (d.Cin + 127) / 128, d.B), dim3(256), 0, st,
+                         (const int8_t *)c.input, xc, d.Cin, HW, fused ? 0x80808080u : 0u);
+    else
+      hipLaunchKernelGGL((nchw_to_nhwc_kernel<int8_t>), dim3((HW + 31) / 32, (d.Cin + 31) / 32, d.B), dim3(256),
+                         0, st, (const int8_t *)c.input, xc, d.Cin, HW, fused ? 0x80 : 0);
+    xt = xc;
+    if (p.repack) {  // else `weight` is the [Cout][Kp] image made by bevops_mdconv_pack_weight, padding zeroed there
+      int8_t *wc = reinterpret_cast<int8_t *>(ws + w.wt);
+      hipLaunchKernelGGL((repack_weight_kernel<int8_t>), dim3((unsigned)(((size_t)d.Cout * cin_g * KK + 255) / 256)),
+                         dim3(256), 0, st, (const int8_t *)c.weight, wc, d.Cout, cin_g, KK, Kp);
+      wt = wc;
+    }
   }
-  if (weight_is_packed)  // [Cout][Kp] image made by bevops_mdconv_pack_weight(BEVOPS_I8, ...), padding zeroed there
-    wt = const_cast<int8_t *>(static_cast<const int8_t *>(weight));
-  // fused implicit GEMM (no column buffer) when a 64-channel chunk stays inside one group and one
-  // deform group; variant 6 keeps the im2col + GEMM pair (A/B reference)
-  // ... and when there are enough 256 x 64 tiles to give every CU two blocks: the base stage-3 call
-  // (544 tiles) 117 vs 170 us; stage 4 (272 tiles, one 4-wave block per CU) 138 vs 130 us keeps the pair
-  // (profiles/r02).  Variant 8 forces the fused kernel.
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const size_t tiles = ((N + kSN - 1) / kSN) * (size_t)((cout_g + kSM - 1) / kSM);
-  const bool fits32 = (size_t)d.B * d.H * d.W * d.Cin < 0xFFFFFF00ull && (size_t)cout_g * Kp < 0xFFFFFF00ull;
-  // LDS-DMA pipelined kernel (section 6c): 128-channel k-steps inside one group and ONE deform group per
-  // conv group; variants 8 (register-staged fused kernel) and 6 (im2col + GEMM) keep the A/B references,
-  // variants 20 + mask = timing experiments with parts of the kernel removed (wrong results)
-  bool one_dg = cin_g <= d.Cin / d.DG;
-  for (int g = 0; g < d.G && one_dg; ++g)
-    one_dg = (g * cin_g) / (d.Cin / d.DG) == (g * cin_g + cin_g - 1) / (d.Cin / d.DG);
-  // ... and enough 128-pixel tiles to give at least every second CU a block (base stage 3: 272 tiles, 67 us
-  // kernel vs 100 us for the register-staged kernel; stage 4: 136 blocks, 95 us per call vs 117 us for the
-  // im2col + GEMM pair and 121 us with 64-pixel tiles, profiles/r02/dcn_time.jsonl); variant 9 forces it
-  const size_t wide_blocks = ((N + Glds<4>::kN - 1) / Glds<4>::kN) * ((cout_g + kFM - 1) / kFM);
-  const bool glds = g_mdconv_variant != 6 && g_mdconv_variant != 8 && fits32 && one_dg && cin_g % 128 == 0 &&
-                    3 * KK <= kSOmRows && Kp == Kg && (wide_blocks * 2 >= (size_t)cus || g_mdconv_variant == 9 || g_mdconv_wide);
-  const bool fused = glds || (g_mdconv_variant != 6 && cin_g % kSK == 0 && (d.Cin / d.DG) % kSK == 0 && fits32 &&
-                              (g_mdconv_variant == 8 || tiles >= (size_t)2 * cus));
-  if (HW % 4 == 0 && d.Cin % 16 == 0 && aligned16(input))
-    hipLaunchKernelGGL(nchw_to_nhwc_s8v_kernel, dim3((HW + 127) / 128, (d.Cin + 127) / 128, d.B), dim3(256), 0, st,
-                       (const int8_t *)input, xt, d.Cin, HW, fused ? 0x80808080u : 0u);
-  else
-    hipLaunchKernelGGL((nchw_to_nhwc_kernel<int8_t>), dim3((HW + 31) / 32, (d.Cin + 31) / 32, d.B), dim3(256),
-                       0, st, (const int8_t *)input, xt, d.Cin, HW, fused ? 0x80 : 0);
-  const size_t wtot = (size_t)d.Cout * cin_g * KK;
-  if (!weight_is_packed)
-    hipLaunchKernelGGL((repack_weight_kernel<int8_t>), dim3((unsigned)((wtot + 255) / 256)), dim3(256), 0, st,
-                       (const int8_t *)weight, wt, d.Cout, cin_g, KK, Kp);
-  if (glds) {
-    const int abl = g_mdconv_variant >= 20 && g_mdconv_variant <= 36 ? g_mdconv_variant - 20 : 0;   // timing experiments
+  if (p.path == kDcnLds) {
     for (int g = 0; g < d.G; ++g) {
-      int rc = BEVOPS_NOT_SUPPORTED;
-      char *pw = ws + w.col;
-      const size_t room = w.total - w.col;
-      const float s_iw = s_in * s_w;
-#define BEVOPS_S8_GO(WN_, ABL_) \
-  rc = launch_glds_s8<WN_, ABL_>(xt, offset, mask, wt, bias, output, d, g, Kp, pw, room, !g_mdconv_no_tail, s_off, s_mask, s_iw, s_out, st)
-      const bool w4 = wide_blocks * 2 >= (size_t)cus || g_mdconv_wide;
-      const bool one_order = g_mdconv_rotate == 2;     // variant 13: the rounds 2-5 order (A/B partner of the default)
-      if (!w4) { if (one_order) BEVOPS_S8_GO(2, 0); else BEVOPS_S8_GO(2, 32); }
-      else
-        switch (abl) {
-          case 0: if (one_order) BEVOPS_S8_GO(4, 0); else BEVOPS_S8_GO(4, 32); break;
-          case 1: BEVOPS_S8_GO(4, 1); break;
-          case 2: BEVOPS_S8_GO(4, 2); break;
-          case 4: BEVOPS_S8_GO(4, 4); break;
-          case 8: BEVOPS_S8_GO(4, 8); break;
-          case 7: BEVOPS_S8_GO(4, 7); break;
-          case 11: BEVOPS_S8_GO(4, 11); break;
-          case 13: BEVOPS_S8_GO(4, 13); break;
-          case 14: BEVOPS_S8_GO(4, 14); break;
-          case 15: BEVOPS_S8_GO(4, 15); break;
-          case 16: BEVOPS_S8_GO(4, 16); break;
-          default: break;
-        }
-#undef BEVOPS_S8_GO
+      const int rc = launch_lds_s8(c, p, g, xt, wt, Kp);
       if (rc != BEVOPS_SUCCESS) return rc;
     }
     return launch_status();
   }
-  if (fused) {
+  const float s_iw = c.s_in * c.s_w;
+  if (p.path == kDcnStaged) {
     for (int g = 0; g < d.G; ++g)
       hipLaunchKernelGGL(dcn_fused_s8_kernel, dim3((unsigned)((N + kSN - 1) / kSN), (cout_g + kSM - 1) / kSM), dim3(256),
-                         0, st, xt, (const int8_t *)offset, (const int8_t *)mask, wt, (const float *)bias,
-                         (int8_t *)output, d, g, Kp, s_off, s_mask, s_in * s_w, s_out);
+                         0, st, xt, (const int8_t *)c.offset, (const int8_t *)c.mask, wt, (const float *)c.bias,
+                         (int8_t *)c.output, d, g, Kp, c.s_off, c.s_mask, s_iw, c.s_out);
     return launch_status();
   }
   const bool v16 = cin_g % 16 == 0 && (d.Cin / d.DG) % 16 == 0;
   const bool v4 = cin_g % 4 == 0 && (d.Cin / d.DG) % 4 == 0;
   const int V = v16 ? 16 : (v4 ? 4 : 1);
   const size_t blocks = (N * KK * (d.Cin / V) + 255) / 256;
-  if (blocks > 0x7FFFFFFFull) return BEVOPS_NOT_SUPPORTED;
-  if (v16)
-    hipLaunchKernelGGL((im2col_nhwc_s8_kernel<16>), dim3((unsigned)blocks), dim3(256), 0, st, xt,
-                       (const int8_t *)offset, (const int8_t *)mask, col, d, s_off, s_mask, Kp);
-  else if (v4)
-    hipLaunchKernelGGL((im2col_nhwc_s8_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, st, xt,
-                       (const int8_t *)offset, (const int8_t *)mask, col, d, s_off, s_mask, Kp);
-  else
-    hipLaunchKernelGGL((im2col_nhwc_s8_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, st, xt,
-                       (const int8_t *)offset, (const int8_t *)mask, col, d, s_off, s_mask, Kp);
+  auto im2col = v16 ? im2col_nhwc_s8_kernel<16> : (v4 ? im2col_nhwc_s8_kernel<4> : im2col_nhwc_s8_kernel<1>);
+  hipLaunchKernelGGL(im2col, dim3((unsigned)blocks), dim3(256), 0, st, xt, (const int8_t *)c.offset,
+                     (const int8_t *)c.mask, col, d, c.s_off, c.s_mask, Kp);
   for (int g = 0; g < d.G; ++g) {
     const GemmEpi e{d.Ho * d.Wo, d.Cout, g * cout_g};
     hipLaunchKernelGGL(gemm_tn_s8_kernel, dim3((unsigned)((N + kBN - 1) / kBN), (cout_g + kBM - 1) / kBM),
                        dim3(256), 0, st, wt + (size_t)g * cout_g * Kp, col + (size_t)g * N * Kp,
-                       (const float *)bias, (int8_t *)output, cout_g, (int)N, Kp, e, s_in * s_w, s_out);
+                       (const float *)c.bias, (int8_t *)c.output, cout_g, (int)N, Kp, e, s_iw, c.s_out);
   }
   return launch_status();
+}
+
+// The int8 entries behind their argument lists: validate, plan, launch
+int forward_s8(DcnCall c, float s_in, float s_off, float s_mask, float s_w, float s_out) {
+  c.s_in = s_in, c.s_off = s_off, c.s_mask = s_mask, c.s_w = s_w, c.s_out = s_out;
+  int rc = validate_s8(c);
+  if (rc != BEVOPS_SUCCESS) return rc;
+  DcnPlan p;
+  rc = plan_s8(c, g_dcn_variant, device_cus_or_256, lds_s8_slots, p);
+  if (rc != BEVOPS_SUCCESS) return rc;
+  return launch_s8(c, p);
 }
 
 }  // namespace
@@ -1120,17 +1106,10 @@ extern "C" int bevops_mdconv_forward_int8(const void *input, float scale_in, con
                                           int Kh, int Kw, int stride_h, int stride_w, int pad_h, int pad_w,
                                           int dil_h, int dil_w, int groups, int deform_groups,
                                           void *stream) {
-  if (!input || !offset || !mask || !weight || !output || !workspace) return BEVOPS_BAD_PARAM;
-  if (!(scale_in > 0.f) || !(scale_offset > 0.f) || !(scale_mask > 0.f) || !(scale_weight > 0.f) ||
-      !(scale_out > 0.f))
-    return BEVOPS_BAD_PARAM;
-  ConvDims d;
-  if (!make_dims(d, B, Cin, H, W, Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w,
-                 groups, deform_groups))
-    return BEVOPS_BAD_PARAM;
-  if (workspace_bytes < ws_layout(d, 1).total || !aligned16(workspace)) return BEVOPS_BAD_PARAM;
-  return run_s8(input, offset, mask, weight, bias, output, workspace, d, scale_in, scale_offset,
-                scale_mask, scale_weight, scale_out, static_cast<hipStream_t>(stream), false);
+  return forward_s8(dcn_call(BEVOPS_I8, input, offset, mask, weight, bias, output, workspace, workspace_bytes, B, Cin, H,
+                             W, Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, deform_groups,
+                             stream),
+                    scale_in, scale_offset, scale_mask, scale_weight, scale_out);
 }
 
 extern "C" int bevops_mdconv_forward_int8_packed(const void *input, float scale_in, const void *offset,
@@ -1141,18 +1120,10 @@ extern "C" int bevops_mdconv_forward_int8_packed(const void *input, float scale_
                                                  int Kh, int Kw, int stride_h, int stride_w, int pad_h, int pad_w,
                                                  int dil_h, int dil_w, int groups, int deform_groups,
                                                  void *stream) {
-  if (!input || !offset || !mask || !packed_weight || !output || !workspace) return BEVOPS_BAD_PARAM;
-  if (!(scale_in > 0.f) || !(scale_offset > 0.f) || !(scale_mask > 0.f) || !(scale_weight > 0.f) ||
-      !(scale_out > 0.f))
-    return BEVOPS_BAD_PARAM;
-  ConvDims d;
-  if (!make_dims(d, B, Cin, H, W, Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w,
-                 groups, deform_groups))
-    return BEVOPS_BAD_PARAM;
-  if (workspace_bytes < ws_layout(d, 1).total || !aligned16(workspace) || !aligned16(packed_weight))
-    return BEVOPS_BAD_PARAM;
-  return run_s8(input, offset, mask, packed_weight, bias, output, workspace, d, scale_in, scale_offset,
-                scale_mask, scale_weight, scale_out, static_cast<hipStream_t>(stream), true);
+  DcnCall c = dcn_call(BEVOPS_I8, input, offset, mask, packed_weight, bias, output, workspace, workspace_bytes, B, Cin, H,
+                       W, Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, deform_groups, stream);
+  c.packed = true;
+  return forward_s8(c, scale_in, scale_offset, scale_mask, scale_weight, scale_out);
 }
 
 // The INT8 engine's channels-last DCNv2 block (not a reference plugin; its arithmetic is the INT8 plugin's,
@@ -1168,57 +1139,19 @@ extern "C" int bevops_mdconv_forward_int8_nhwc(const void *input_nhwc, float sca
                                                size_t workspace_bytes, int B, int Cin, int H, int W, int Cout, int Kh,
                                                int Kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
                                                int dil_w, int groups, int deform_groups, void *stream) {
-  if (!input_nhwc || !offset_mask_nhwc || !packed_weight || !output_nhwc) return BEVOPS_BAD_PARAM;
-  if (!(scale_in > 0.f) || !(scale_offset > 0.f) || !(scale_mask > 0.f) || !(scale_weight > 0.f) || !(scale_out > 0.f))
-    return BEVOPS_BAD_PARAM;
-  ConvDims d;
-  if (!make_dims(d, B, Cin, H, W, Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups, deform_groups))
-    return BEVOPS_BAD_PARAM;
-  const int KK = Kh * Kw, cin_g = Cin / groups, cout_g = Cout / groups;
-  if (offset_mask_channels < deform_groups * 3 * KK) return BEVOPS_BAD_PARAM;
-  // the raw offset-convolution output is read as [2 KK offsets | KK mask logits] of ONE deform group (the layout of
-  // mmcv's cat(o1, o2) | mask for deform_groups == 1, modules/cnn/dcn.py:70-74); several groups interleave differently
-  if (deform_groups != 1) return BEVOPS_NOT_SUPPORTED;
-  if (!aligned16(input_nhwc) || !aligned16(packed_weight) || (reinterpret_cast<uintptr_t>(output_nhwc) & 3u) ||
-      (reinterpret_cast<uintptr_t>(offset_mask_nhwc) & 1u))
-    return BEVOPS_BAD_PARAM;
-  const size_t N = (size_t)B * d.Ho * d.Wo;
-  const int Kp = (int)kpad(d, 1);
-  bool one_dg = cin_g <= Cin / deform_groups;
-  for (int g = 0; g < groups && one_dg; ++g)
-    one_dg = (g * cin_g) / (Cin / deform_groups) == (g * cin_g + cin_g - 1) / (Cin / deform_groups);
-  const bool fits32 = (size_t)B * H * W * Cin < 0xFFFFFF00ull && (size_t)cout_g * Kp < 0xFFFFFF00ull;
-  if (N > 0x7FFFFFFFull || !fits32 || !one_dg || cin_g % 128 != 0 || 3 * KK > kSOmRows || Kp != KK * cin_g ||
-      cout_g % 4 != 0)
-    return BEVOPS_NOT_SUPPORTED;
-  // the split-K tail's int32 partials live in the caller's workspace (none lent: every tile runs its whole k-loop)
-  char *pw = static_cast<char *>(workspace);
-  const size_t room = (workspace && aligned16(workspace)) ? workspace_bytes : 0;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const size_t wide_blocks = ((N + Glds<4>::kN - 1) / Glds<4>::kN) * ((cout_g + kFM - 1) / kFM);
-  const bool w4 = wide_blocks * 2 >= (size_t)cus || g_mdconv_wide;
-  const S8Eng eng{offset_mask_channels, relu ? 1 : 0};
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  for (int g = 0; g < groups; ++g) {
-#define BEVOPS_S8E(WN_, FAST_) (g_mdconv_rotate == 2 ? BEVOPS_S8E_(WN_, FAST_, 0) : BEVOPS_S8E_(WN_, FAST_, 32))
-#define BEVOPS_S8E_(WN_, FAST_, ABL_)                                                                                \
-  launch_glds_s8<WN_, ABL_, true, FAST_>((const int8_t *)input_nhwc, offset_mask_nhwc, nullptr, (const int8_t *)packed_weight, \
-                                      bias, output_nhwc, d, g, Kp, pw, room, !g_mdconv_no_tail, scale_offset, scale_mask,   \
-                                      scale_in * scale_weight, scale_out, st, eng)
-    const int rc = exact ? (w4 ? BEVOPS_S8E(4, false) : BEVOPS_S8E(2, false)) : (w4 ? BEVOPS_S8E(4, true) : BEVOPS_S8E(2, true));
-#undef BEVOPS_S8E
-#undef BEVOPS_S8E_
-    if (rc != BEVOPS_SUCCESS) return rc;
-  }
-  return launch_status();
+  DcnCall c = dcn_call(BEVOPS_I8, input_nhwc, offset_mask_nhwc, nullptr, packed_weight, bias, output_nhwc, workspace,
+                       workspace_bytes, B, Cin, H, W, Cout, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, groups,
+                       deform_groups, stream);
+  c.packed = c.nhwc = true;
+  c.relu = relu != 0;
+  c.exact = exact != 0;
+  c.om_channels = offset_mask_channels;
+  return forward_s8(c, scale_in, scale_offset, scale_mask, scale_weight, scale_out);
 }
 
 // bytes of workspace bevops_mdconv_forward_int8_nhwc can use for its split-K tail (nothing lent = no tail split):
-// the plan of launch_glds_s8 keeps split x tail tiles within the resident block slots (<= 1024 threads per CU),
+// the tail plan keeps split x tail tiles within the resident block slots (<= 1024 threads per CU),
 // each thread parks 32 int32 partial sums
 extern "C" size_t bevops_mdconv_int8_nhwc_workspace_size(void) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  return (size_t)(cus > 0 ? cus : 256) * 1024 * 32 * sizeof(int);
+  return (size_t)device_cus_or_256() * 1024 * 32 * sizeof(int);
 }

@@ -10,6 +10,7 @@ import torch
 from ..utils import lib as _lib
 from ..utils import workspace as _ws
 from .linear import _like_rows, _operands, _ptr
+from .modulated_deformable_conv2d import _geometry, _packed_weight
 from .multi_scale_deformable_attn import _TensorCache
 
 
@@ -155,21 +156,10 @@ def modulated_deformable_conv2d_int8_nhwc(x_q, scale_in, offset_mask_nhwc, scale
     assert x_q.is_contiguous(memory_format=torch.channels_last)
     assert offset_mask_nhwc.dtype == torch.float16 and offset_mask_nhwc.is_contiguous(memory_format=torch.channels_last)
     handle = _lib.load_library()
-    B, Cin, H, W = x_q.shape
-    Cout, cin_g, Kh, Kw = weight_q.shape
-    Ho = (H + 2 * padding - (dilation * (Kh - 1) + 1)) // stride + 1
-    Wo = (W + 2 * padding - (dilation * (Kw - 1) + 1)) // stride + 1
+    dims, Ho, Wo = _geometry(x_q, weight_q, stride, padding, dilation, groups, deform_groups)
+    B, Cout = dims[0], dims[4]
     assert tuple(offset_mask_nhwc.shape[0:1] + offset_mask_nhwc.shape[2:]) == (B, Ho, Wo)
-    packed = _PACKED_S8.get(weight_q)
-    if packed is None:
-        nbytes = handle.bevops_mdconv_packed_weight_size(_lib.I8, Cout, cin_g, Kh, Kw)
-        packed = torch.empty(nbytes, dtype=torch.uint8, device=weight_q.device)
-        wc = weight_q.contiguous()
-        with torch.cuda.device(weight_q.device):
-            st = handle.bevops_mdconv_pack_weight(_lib.I8, wc.data_ptr(), packed.data_ptr(), Cout, cin_g, Kh, Kw,
-                                                  _lib.current_stream_ptr(weight_q.device))
-        _lib.check(st, "bevops_mdconv_pack_weight")
-        packed = _PACKED_S8.put(weight_q, packed)
+    packed = _packed_weight(handle, weight_q, _lib.I8, cache=_PACKED_S8, empty=torch.empty)   # this module's own
     out = torch.empty((B, Cout, Ho, Wo), dtype=torch.int8, device=x_q.device, memory_format=torch.channels_last)
     if B == 0:
         return out
@@ -182,8 +172,6 @@ def modulated_deformable_conv2d_int8_nhwc(x_q, scale_in, offset_mask_nhwc, scale
             x_q.data_ptr(), float(scale_in), offset_mask_nhwc.data_ptr(), int(offset_mask_nhwc.shape[1]),
             float(scale_offset), float(scale_mask), packed.data_ptr(), float(scale_weight),
             b.data_ptr() if b is not None else None, out.data_ptr(), float(scale_out), int(bool(relu)), int(bool(exact)),
-            ws.data_ptr(),
-            ws_bytes, B, Cin, H, W, Cout, Kh, Kw, stride, stride, padding, padding, dilation, dilation, groups,
-            deform_groups, stream)
+            ws.data_ptr(), ws_bytes, *dims, stream)
     _lib.check(st, "bevops_mdconv_forward_int8_nhwc")
     return out

@@ -11,18 +11,44 @@ from .multi_scale_deformable_attn import _TensorCache
 _PACKED = _TensorCache()
 
 
-def _packed_weight(handle, weight, dt):
-    hit = _PACKED.get(weight)
+def _geometry(input, weight, stride, padding, dilation, groups, deform_groups):
+    """(dims, Ho, Wo): the 15 geometry ints of the C entries and the output size of the usual conv formula"""
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    B, Cin, H, W = input.shape
+    Cout, _, Kh, Kw = weight.shape
+    Ho = (H + 2 * ph - (dh * (Kh - 1) + 1)) // sh + 1
+    Wo = (W + 2 * pw - (dw * (Kw - 1) + 1)) // sw + 1
+    return (B, Cin, H, W, Cout, Kh, Kw, sh, sw, ph, pw, dh, dw, groups, deform_groups), Ho, Wo
+
+
+def _workspace(handle, dt, dims, device, must_size=True):
+    """(scratch tensor, its bytes) of bevops_mdconv_workspace_size; a size of 0 = unsupported arguments raises unless
+    the entry itself is left to answer them (must_size=False)"""
+    ws_bytes = handle.bevops_mdconv_workspace_size(dt, *dims)
+    if ws_bytes == 0 and must_size:
+        raise _lib.BevopsError("bevops_mdconv_workspace_size: unsupported arguments", _lib.NOT_SUPPORTED)
+    return torch.empty(ws_bytes, dtype=torch.uint8, device=device), ws_bytes
+
+
+def _packed_weight(handle, weight, dt, per_call_under_capture=False, cache=_PACKED, empty=None):
+    """The weight's [Cout][tap][Cin/groups] image, re-laid out once per weight tensor (version).
+    per_call_under_capture: a first sighting under stream capture returns None instead -- the caller takes the
+    entry that re-lays the weight out per call, so that no allocation or cache entry is made while capturing.
+    cache / empty: the calling module's own cache and allocator (default: this module's)."""
+    hit = cache.get(weight)
     if hit is not None:
         return hit
+    if per_call_under_capture and torch.cuda.is_current_stream_capturing():
+        return None
     Cout, cin_g, Kh, Kw = weight.shape
     nbytes = handle.bevops_mdconv_packed_weight_size(dt, Cout, cin_g, Kh, Kw)
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    packed = (empty or torch.empty)(nbytes, dtype=torch.uint8, device=weight.device)
+    wc = weight.contiguous()
     with torch.cuda.device(weight.device):
-        st = handle.bevops_mdconv_pack_weight(dt, weight.data_ptr(), packed.data_ptr(), Cout, cin_g, Kh, Kw,
+        st = handle.bevops_mdconv_pack_weight(dt, wc.data_ptr(), packed.data_ptr(), Cout, cin_g, Kh, Kw,
                                               _lib.current_stream_ptr(weight.device))
     _lib.check(st, "bevops_mdconv_pack_weight")
-    return _PACKED.put(weight, packed)
+    return cache.put(weight, packed)
 
 
 def _mdconv(input, offset, mask, weight, bias, stride, padding, dilation, groups, deform_groups):
@@ -38,11 +64,8 @@ def _mdconv(input, offset, mask, weight, bias, stride, padding, dilation, groups
     offset = offset.contiguous()
     if bias is not None:
         bias = bias.type_as(input).contiguous()
-    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
-    B, Cin, H, W = input.shape
-    Cout, _, Kh, Kw = weight.shape
-    Ho = (H + 2 * ph - (dh * (Kh - 1) + 1)) // sh + 1
-    Wo = (W + 2 * pw - (dw * (Kw - 1) + 1)) // sw + 1
+    dims, Ho, Wo = _geometry(input, weight, stride, padding, dilation, groups, deform_groups)
+    B, Cout, Kh, Kw = dims[0], dims[4], dims[5], dims[6]
     if tuple(offset.shape) != (B, deform_groups * 2 * Kh * Kw, Ho, Wo):
         raise ValueError(f"offset shape {tuple(offset.shape)} != {(B, deform_groups * 2 * Kh * Kw, Ho, Wo)}")
     if tuple(mask.shape) != (B, deform_groups * Kh * Kw, Ho, Wo):
@@ -50,19 +73,11 @@ def _mdconv(input, offset, mask, weight, bias, stride, padding, dilation, groups
     dt = _lib.torch_dtype_code(input)
     if B == 0:      # empty batch: nothing to convolve
         return input.new_empty((0, Cout, max(Ho, 0), max(Wo, 0)))
-    dims = (B, Cin, H, W, Cout, Kh, Kw, sh, sw, ph, pw, dh, dw, groups, deform_groups)
-    ws_bytes = handle.bevops_mdconv_workspace_size(dt, *dims)
-    if ws_bytes == 0:
-        raise _lib.BevopsError("bevops_mdconv_workspace_size: unsupported arguments", _lib.NOT_SUPPORTED)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device)
+    ws, ws_bytes = _workspace(handle, dt, dims, input.device)
     out = torch.empty((B, Cout, Ho, Wo), dtype=input.dtype, device=input.device)
     # the cache is keyed on the caller's tensor object; a converted / re-laid-out temporary
     # (weight is not w_src) would never hit, so it takes the per-call path
-    packed = None
-    if weight is w_src:
-        packed = _PACKED.get(weight)
-        if packed is None and not torch.cuda.is_current_stream_capturing():
-            packed = _packed_weight(handle, weight, dt)
+    packed = _packed_weight(handle, weight, dt, per_call_under_capture=True) if weight is w_src else None
     with torch.cuda.device(input.device):
         fn = handle.bevops_mdconv_forward_packed if packed is not None else handle.bevops_mdconv_forward
         st = fn(dt, input.data_ptr(), offset.data_ptr(), mask.data_ptr(),
@@ -99,21 +114,10 @@ def modulated_deformable_conv2d_int8(input, offset, mask, weight, bias, scale_in
             raise TypeError(f"{name} must be int8")
     if bias is not None:
         bias = bias.float().contiguous()
-    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
-    B, Cin, H, W = input.shape
-    Cout, _, Kh, Kw = weight.shape
-    Ho = (H + 2 * ph - (dh * (Kh - 1) + 1)) // sh + 1
-    Wo = (W + 2 * pw - (dw * (Kw - 1) + 1)) // sw + 1
-    dims = (B, Cin, H, W, Cout, Kh, Kw, sh, sw, ph, pw, dh, dw, groups, deform_groups)
-    ws_bytes = handle.bevops_mdconv_workspace_size(_lib.I8, *dims)
-    if ws_bytes == 0:
-        raise _lib.BevopsError("bevops_mdconv_workspace_size: unsupported arguments", _lib.NOT_SUPPORTED)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device)
-    out = torch.empty((B, Cout, Ho, Wo), dtype=torch.int8, device=input.device)
-    # re-laid-out once per weight tensor (version); a first sighting under stream capture takes the per-call path
-    packed = _PACKED.get(weight)
-    if packed is None and not torch.cuda.is_current_stream_capturing():
-        packed = _packed_weight(handle, weight, _lib.I8)
+    dims, Ho, Wo = _geometry(input, weight, stride, padding, dilation, groups, deform_groups)
+    ws, ws_bytes = _workspace(handle, _lib.I8, dims, input.device)
+    out = torch.empty((dims[0], dims[4], Ho, Wo), dtype=torch.int8, device=input.device)
+    packed = _packed_weight(handle, weight, _lib.I8, per_call_under_capture=True)
     with torch.cuda.device(input.device):
         fn = handle.bevops_mdconv_forward_int8_packed if packed is not None else handle.bevops_mdconv_forward_int8
         st = fn(input.data_ptr(), float(scale_in), offset.data_ptr(), float(scale_offset), mask.data_ptr(),
@@ -145,19 +149,12 @@ def modulated_deformable_conv2d_nhwc(input, offset, mask, weight, bias=None, str
         offset, mask = offset_mask_nhwc, None
     else:
         offset, mask = offset.to(input.dtype).contiguous(), mask.to(input.dtype).contiguous()
-    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
-    B, Cin, H, W = input.shape
-    Cout, _, Kh, Kw = weight.shape
-    Ho = (H + 2 * ph - (dh * (Kh - 1) + 1)) // sh + 1
-    Wo = (W + 2 * pw - (dw * (Kw - 1) + 1)) // sw + 1
-    dims = (B, Cin, H, W, Cout, Kh, Kw, sh, sw, ph, pw, dh, dw, groups, deform_groups)
+    dims, Ho, Wo = _geometry(input, weight, stride, padding, dilation, groups, deform_groups)
+    B, Cout = dims[0], dims[4]
     if weight.dtype != torch.float16 or not weight.is_contiguous():
         raise _lib.BevopsError("modulated_deformable_conv2d_nhwc: weight must be a contiguous fp16 tensor", _lib.BAD_PARAM)
-    packed = _PACKED.get(weight)
-    if packed is None:
-        packed = _packed_weight(handle, weight, _lib.F16)
-    ws_bytes = handle.bevops_mdconv_workspace_size(_lib.F16, *dims)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device)
+    packed = _packed_weight(handle, weight, _lib.F16)
+    ws, ws_bytes = _workspace(handle, _lib.F16, dims, input.device, must_size=False)
     out = torch.empty((B, Cout, Ho, Wo), dtype=input.dtype, device=input.device,
                       memory_format=torch.channels_last)
     if bias is not None:

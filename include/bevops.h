@@ -272,14 +272,15 @@ int bevops_sca_forward(int dtype, const void *value, const int32_t *spatial_shap
  * (Cout/groups) % 4 == 0 like ...Plugin.cpp:217-219).
  * bevops_mdconv_workspace_size(BEVOPS_I8, ...) sizes its workspace.
  * ------------------------------------------------------------------------ */
-/* Tuning hook like bevops_msda_set_variant: 0 = automatic (fused implicit GEMM when the
- * channel counts allow), 1 = force the im2col + GEMM pipeline, 2 / 3 = the register-staged
- * fused kernels (256 / 512 threads), 4 = LDS-DMA kernel with 64-pixel tiles and no split-K
- * tail, 5 = LDS-DMA kernel with 128-pixel tiles, 7 / 13 = LDS-DMA kernel with the round-2 wave rotation / with one
- * segment order for all waves (rounds 2-5; the default since round 6 lets the lower half of a block's waves issue all
- * the weight DMA and the upper half run its matrix segment first: same bits); INT8: 6 = im2col + GEMM pair, 8 = register-staged
- * fused kernel, 9 = LDS-DMA kernel whatever the tile count, 20 + mask = timing experiments (wrong
- * results).  Returns the previous value. */
+/* Tuning hook like bevops_msda_set_variant (thread-local; a value acts on both dtype families):
+ *   0 = automatic (fused implicit GEMM when the channel counts allow);
+ *   1 / 2 / 3 = fp16 on the im2col + GEMM pipeline / the register-staged fused kernel with 256 / with 512 threads
+ *               (int8 stays automatic);
+ *   4 = no split-K tail, fp16 also on 64-pixel tiles; 5 = 128-pixel tiles whatever the tile count (fp16 and int8);
+ *   6 / 8 / 9 = int8 on the im2col + GEMM pair / the register-staged fused kernel / the LDS-DMA kernel whatever the
+ *               tile count (an fp16 call inside the fused domain runs on the 512-thread register-staged kernel, as
+ *               under 3).
+ * Any other value selects the automatic choice, exactly as 0 does.  Returns the previous value. */
 int bevops_mdconv_set_variant(int variant);
 size_t bevops_mdconv_workspace_size(int dtype, int B, int Cin, int H, int W, int Cout, int Kh,
                                     int Kw, int stride_h, int stride_w, int pad_h, int pad_w,

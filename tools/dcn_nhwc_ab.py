@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """The channels-last DCNv2 entry the frame calls (bevops_mdconv_forward_nhwc: dcn_glds_f16_kernel + tail finish) at the
-two BEVFormer-base shapes (and one camera of the first), per wave-order build of the kernel, under HIP-graph replay,
-interleaved: variant 0 = the default (round 6: the lower half of the waves issues all the weight DMA, the upper half runs
-its matrix segment first), 13 = all 16 waves in one order (rounds 2-5), 7 = upper half rotated by half an iteration
-(round 2).  Results must be bit-identical.
+two BEVFormer-base shapes (and one camera of the first), per tiling of the kernel, under HIP-graph replay, interleaved:
+variant 0 = the default, 4 = 64-pixel tiles without the split-K tail, 5 = 128-pixel tiles whatever the tile count;
+`identical_to_variant_0` says whether a variant's result has the default's bits (a split-K tail sums in another order).
+(The earlier wave orders this tool compared, variants 7 and 13, left the build; their numbers are
+profiles/r06/dcn_sched_ab*.jsonl.)
 usage: dcn_nhwc_ab.py [variant ...]"""
 import json
 import os
@@ -22,7 +23,7 @@ if "--once" in sys.argv:          # --once K: K plain launches per variant of th
     i = sys.argv.index("--once")
     once = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
-variants = [int(a) for a in sys.argv[1:]] or [0, 13, 7]
+variants = [int(a) for a in sys.argv[1:]] or [0, 4, 5]
 g = torch.Generator().manual_seed(0)
 for (B, C, H, W) in ((6, 256, 58, 100), (6, 512, 29, 50), (1, 256, 58, 100)):
     x = torch.randn(B, C, H, W, generator=g).half().cuda().contiguous(memory_format=torch.channels_last)
