@@ -59,6 +59,11 @@ const Entry kTable[] = {
     {"bevops_bev_nms", (void *)&bevops_bev_nms},
     {"bevops_bev_nms_workspace_size", (void *)&bevops_bev_nms_workspace_size},
     {"bevops_bev_iou", (void *)&bevops_bev_iou},
+    {"bevops_centernet_decode", (void *)&bevops_centernet_decode},
+    {"bevops_centernet_decode_workspace_size", (void *)&bevops_centernet_decode_workspace_size},
+    {"bevops_yolox_decode", (void *)&bevops_yolox_decode},
+    {"bevops_box_nms", (void *)&bevops_box_nms},
+    {"bevops_box_nms_workspace_size", (void *)&bevops_box_nms_workspace_size},
     {"bevops_lss_voxel_prepare", (void *)&bevops_lss_voxel_prepare},
     {"bevops_lss_voxel_prepare_workspace_size", (void *)&bevops_lss_voxel_prepare_workspace_size},
     {"bevops_bev_pool_v2_forward_indirect", (void *)&bevops_bev_pool_v2_forward_indirect},

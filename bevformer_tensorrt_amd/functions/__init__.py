@@ -31,6 +31,7 @@ from .multi_head_attn import qkv, qkv2
 from .inverse import inverse
 from .decode import nms_free_decode, centerpoint_decode
 from .nms import bev_nms, nms_bev, circle_nms, bev_iou
+from .decode2d import centernet_decode, yolox_decode, box_nms
 from .lss_prepare import lss_voxel_prepare, lss_lidar_coor, bev_pool_v2_indirect
 from .calibrate import calib_state_size, calib_collect, calib_threshold
 from .bev_half import lss_depth_split, upsample_bilinear_concat_nhwc
@@ -56,6 +57,7 @@ __all__ = [
     "inverse", "qkv", "qkv2",
     "nms_free_decode", "centerpoint_decode",
     "bev_nms", "nms_bev", "circle_nms", "bev_iou",
+    "centernet_decode", "yolox_decode", "box_nms",
     "lss_voxel_prepare", "lss_lidar_coor", "bev_pool_v2_indirect",
     "calib_state_size", "calib_collect", "calib_threshold",
     "bevdet_test_augmentation", "bevdet_post_transform", "image_resize_plan", "image_resize_crop_normalize",

@@ -264,6 +264,193 @@ def bev_nms_torch(boxes, scores, labels, count=None, *, nms_type="rotate", thres
     return out_b, out_s, out_l, out_c, out_i
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The 2-D heads: CenterNet, YOLOX and the axis-aligned batched NMS (functions/decode2d.py, csrc/decode2d.hip).  Written
+# from the published algorithm of mmdet 2.x (CenterNetHead.get_bboxes / decode_heatmap, YOLOXHead.get_bboxes /
+# _bbox_decode / _bboxes_nms) and mmcv.ops.batched_nms, as the reference's detectors call them
+# (det2trt/models/detector/{centernet,yolox}.py: post_process); parity with the libraries themselves is unpinned.
+def _host_rows(values, batch, width):
+    if values is None:
+        return None
+    t = torch.as_tensor(values, dtype=torch.float32).detach().cpu().reshape(-1, width)
+    return t.expand(batch, width) if t.shape[0] == 1 else t
+
+
+def centernet_decode_torch(heatmap, wh, offset, k, input_shape, kernel=3, border=None, scale_factor=None,
+                           score_threshold=None, return_index=False):
+    """The padded result of `centernet_decode` -- boxes [B, k, 4], scores [B, k], labels int32, count [B] -- in torch ops
+    on the CPU: max_pool2d thinning (-inf padding, hmax == heat, a kept -0 as +0), stable descending sort, the box
+    arithmetic one fp32 tensor op per step.  Defined for maps without NaN."""
+    heat, wh, off = (t.detach().float().cpu() for t in (heatmap, wh, offset))
+    B, C, H, W = heat.shape
+    k = int(k)
+    if not 1 <= k <= C * H * W:
+        raise ValueError(f"k {k} outside 1 .. {C * H * W}")
+    if kernel < 1 or kernel % 2 == 0:
+        raise ValueError(f"kernel {kernel} must be odd")
+    hmax = torch.nn.functional.max_pool2d(heat, kernel, stride=1, padding=(kernel - 1) // 2)
+    thin = torch.where(hmax == heat, heat, torch.zeros_like(heat)) + 0.0
+    flat = thin.reshape(B, -1)
+    index = _rank(flat, k)
+    scores = torch.gather(flat, 1, index)
+    labels = torch.div(index, H * W, rounding_mode="trunc")
+    cell = index % (H * W)
+    ys, xs = torch.div(cell, W, rounding_mode="trunc").float(), (cell % W).float()
+    at = lambda t: torch.gather(t.reshape(B, 2, H * W), 2, cell[:, None, :].expand(B, 2, k))
+    w, o = at(wh), at(off)
+    xs, ys = xs + o[:, 0], ys + o[:, 1]
+    rx = torch.tensor(float(input_shape[1]) / W, dtype=torch.float32)
+    ry = torch.tensor(float(input_shape[0]) / H, dtype=torch.float32)
+    boxes = torch.stack([(xs - w[:, 0] / 2) * rx, (ys - w[:, 1] / 2) * ry, (xs + w[:, 0] / 2) * rx,
+                         (ys + w[:, 1] / 2) * ry], dim=-1)
+    bd, sf = _host_rows(border, B, 2), _host_rows(scale_factor, B, 4)
+    if bd is not None:
+        boxes = boxes - bd[:, None, [0, 1, 0, 1]]
+    if sf is not None:
+        boxes = boxes / sf[:, None, :]
+    keep = torch.ones(B, k, dtype=torch.bool)
+    if score_threshold is not None and score_threshold >= 0:
+        keep = scores > score_threshold
+    out_b, out_s = torch.zeros(B, k, 4), torch.zeros(B, k)
+    out_l, count = torch.zeros(B, k, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)
+    for b in range(B):
+        n = int(keep[b].sum())
+        out_b[b, :n], out_s[b, :n], out_l[b, :n] = boxes[b][keep[b]], scores[b][keep[b]], labels[b][keep[b]].to(torch.int32)
+        count[b] = n
+    out = (out_b, out_s, out_l, count)
+    return out + (index, keep) if return_index else out
+
+
+def yolox_decode_torch(cls_scores, bbox_preds, objectnesses, strides=(8, 16, 32), scale_factor=None):
+    """The result of `yolox_decode` -- boxes [B, P, 4], scores [B, P], labels [B, P] int32 in prior order -- in torch
+    ops on the CPU.  The label is the first maximum of the class LOGITS (the one stated deviation from mmdet, which takes
+    it after the sigmoid)."""
+    boxes, scores, labels = [], [], []
+    for cls, box, obj, stride in zip(cls_scores, bbox_preds, objectnesses, strides):
+        cls, box, obj = (t.detach().float().cpu() for t in (cls, box, obj))
+        B, C, H, W = cls.shape
+        cls = cls.permute(0, 2, 3, 1).reshape(B, H * W, C)
+        p = box.permute(0, 2, 3, 1).reshape(B, H * W, 4)
+        obj = obj.reshape(B, H * W)
+        px = (torch.arange(W) * int(stride)).float().repeat(H)
+        py = (torch.arange(H) * int(stride)).float().repeat_interleave(W)
+        s = float(stride)
+        cx, cy = p[..., 0] * s + px, p[..., 1] * s + py
+        w, h = p[..., 2].exp() * s, p[..., 3].exp() * s
+        boxes.append(torch.stack([cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2], dim=-1))
+        best = cls.max(dim=-1).values
+        first = torch.where(cls == best[..., None], torch.arange(C).expand_as(cls), torch.full_like(cls, C, dtype=torch.long))
+        labels.append(first.min(dim=-1).values.to(torch.int32))
+        scores.append(obj.sigmoid() * best.sigmoid())
+    boxes, scores, labels = torch.cat(boxes, 1), torch.cat(scores, 1), torch.cat(labels, 1)
+    sf = _host_rows(scale_factor, boxes.shape[0], 4)
+    if sf is not None:
+        boxes = boxes / sf[:, None, :]
+    return boxes, scores, labels
+
+
+def box_nms_torch(boxes, scores, labels, count=None, *, score_threshold=None, iou_threshold, class_aware=True,
+                  max_out=None):
+    """The padded result of `box_nms` -- (boxes [B, max_out, 4], scores, labels int32, count, index int32) -- in torch
+    ops on the CPU: candidates score >= score_threshold below count, stable descending sort (equal scores: lower row
+    first), the fp32 pair test in the stated operation order, greedy scan, cut to max_out.  The label test is the
+    definition of class-awareness (mmcv's coordinate offset is not restated); a row with a non-finite coordinate
+    suppresses nothing and is not suppressed."""
+    boxes, scores = boxes.detach().float().cpu(), scores.detach().float().cpu()
+    labels = labels.detach().cpu()
+    if boxes.ndim == 2:
+        boxes, scores, labels = boxes[None], scores[None], labels[None]
+        count = None if count is None else count.reshape(1)
+    B, N = scores.shape
+    post = N if max_out is None else int(max_out)
+    if not 1 <= post <= N:
+        raise ValueError(f"max_out {post} outside 1 .. {N}")
+    thr = float("-inf") if score_threshold is None else float(score_threshold)
+    iou_thr = torch.tensor(float(iou_threshold), dtype=torch.float32)
+    counts = [N] * B if count is None else [min(max(int(c), 0), N) for c in count.tolist()]
+    out_b, out_s = torch.zeros(B, post, 4), torch.zeros(B, post)
+    out_l, out_i = torch.zeros(B, post, dtype=torch.int32), torch.zeros(B, post, dtype=torch.int32)
+    out_c = torch.zeros(B, dtype=torch.int32)
+    nan = torch.tensor(float("nan"))
+    for b in range(B):
+        n = counts[b]
+        sc = scores[b, :n]
+        rows = torch.nonzero(sc >= thr).flatten()
+        if rows.numel() == 0:
+            continue
+        order = rows[torch.sort(sc[rows] + 0.0, descending=True, stable=True).indices]
+        q, lb = boxes[b][order], labels[b][order].long()
+        x1, y1, x2, y2 = q.unbind(-1)
+        area = torch.where(torch.isfinite(q).all(-1), (x2 - x1) * (y2 - y1), nan)
+        M = order.numel()
+        removed = torch.zeros(M, dtype=torch.bool)
+        keep = []
+        for i in range(M):
+            if removed[i]:
+                continue
+            keep.append(i)
+            if len(keep) == post or i + 1 == M:
+                break
+            iw = (torch.minimum(x2[i], x2[i + 1:]) - torch.maximum(x1[i], x1[i + 1:])).clamp(min=0)
+            ih = (torch.minimum(y2[i], y2[i + 1:]) - torch.maximum(y1[i], y1[i + 1:])).clamp(min=0)
+            inter = iw * ih
+            sup = inter / ((area[i] + area[i + 1:]) - inter) > iou_thr          # (NaN compares false)
+            if class_aware:
+                sup &= lb[i + 1:] == lb[i]
+            removed[i + 1:] |= sup
+        kept = order[torch.tensor(keep, dtype=torch.long)]
+        m = kept.numel()
+        out_b[b, :m], out_s[b, :m], out_l[b, :m] = boxes[b][kept], scores[b][kept], labels[b][kept].to(torch.int32)
+        out_i[b, :m], out_c[b] = kept.to(torch.int32), m
+    return out_b, out_s, out_l, out_c, out_i
+
+
+def _meta_rows(img_metas, key, pick=None):
+    rows = []
+    for meta in img_metas:
+        v = [float(x) for x in (meta[key].tolist() if hasattr(meta[key], "tolist") else meta[key])]
+        rows.append([v[i] for i in pick] if pick else v)
+    return rows
+
+
+def _single_level(preds):
+    if torch.is_tensor(preds):
+        return preds
+    assert len(preds) == 1, "CenterNet has one output level"
+    return preds[0]
+
+
+def centernet_get_bboxes(center_heatmap_preds, wh_preds, offset_preds, img_metas, rescale=True, topk=100,
+                         local_maximum_kernel=3):
+    """CenterNetHead.get_bboxes (with_nms=False, the reference's config): the three head outputs (one-level lists, as
+    mmdet passes them, or the tensors themselves; the heat map after its sigmoid) and mmdet's img_metas
+    (`batch_input_shape`, `border` = (top, bottom, left, right) when the test pipeline padded, `scale_factor`).  Returns
+    [(det_bboxes [n, 5] = x1, y1, x2, y2, score, det_labels [n] int64)] per image, n = topk.  Device tensors go to the
+    kernels, CPU tensors to the torch statement."""
+    from .functions.decode2d import centernet_decode
+    heat, wh, off = (_single_level(p) for p in (center_heatmap_preds, wh_preds, offset_preds))
+    border = _meta_rows(img_metas, "border", (2, 0)) if "border" in img_metas[0] else None
+    scale = _meta_rows(img_metas, "scale_factor") if rescale else None
+    boxes, scores, labels, count = centernet_decode(heat, wh, off, topk, img_metas[0]["batch_input_shape"],
+                                                    local_maximum_kernel, border, scale, padded=True)
+    return [(torch.cat([boxes[b, :n], scores[b, :n, None]], dim=-1), labels[b, :n].to(torch.int64))
+            for b, n in enumerate(count.tolist())]
+
+
+def yolox_get_bboxes(cls_scores, bbox_preds, objectnesses, img_metas, rescale=True, score_thr=0.01, iou_threshold=0.65,
+                     strides=(8, 16, 32), max_out=None):
+    """YOLOXHead.get_bboxes: decode every prior, rescale (before the NMS, as mmdet does), then the class-aware NMS over
+    the rows with score >= score_thr.  Returns [(det_bboxes [n, 5], det_labels [n] int64)] per image in descending score
+    order; max_out caps n (None = no cap).  Device tensors go to the kernels, CPU tensors to the torch statements."""
+    from .functions.decode2d import box_nms, yolox_decode
+    scale = _meta_rows(img_metas, "scale_factor") if rescale else None
+    boxes, scores, labels = yolox_decode(cls_scores, bbox_preds, objectnesses, strides, scale)
+    kb, ks, kl, count, _ = box_nms(boxes, scores, labels, score_threshold=score_thr, iou_threshold=iou_threshold,
+                                   class_aware=True, max_out=max_out, padded=True)
+    return [(torch.cat([kb[b, :n], ks[b, :n, None]], dim=-1), kl[b, :n].to(torch.int64))
+            for b, n in enumerate(count.tolist())]
+
+
 def _dicts(padded, columns, label_dtype, device):
     boxes, scores, labels, count = padded
     out = []

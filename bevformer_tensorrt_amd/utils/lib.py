@@ -158,6 +158,13 @@ SIGNATURES = {
     "bevops_bev_nms": (c_int, [c_int] + [c_void_p] * 9 + [c_int] * 4 + [c_float, c_void_p, c_int, c_int, c_void_p,
                                                                         c_size_t, c_void_p]),
     "bevops_bev_iou": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "bevops_centernet_decode_workspace_size": (c_size_t, [c_int] * 5),
+    "bevops_centernet_decode": (c_int, [c_int] + [c_void_p] * 8 + [c_int] * 8 + [c_void_p, c_void_p, c_float, c_void_p,
+                                                                               c_size_t, c_void_p]),
+    "bevops_yolox_decode": (c_int, [c_int] + [c_void_p] * 8 + [c_int] * 3 + [c_void_p, c_void_p]),
+    "bevops_box_nms_workspace_size": (c_size_t, [c_int, c_int]),
+    "bevops_box_nms": (c_int, [c_void_p] * 9 + [c_int, c_int, c_float, c_float, c_int, c_int, c_void_p, c_size_t,
+                                                c_void_p]),
     "bevops_lss_voxel_prepare_workspace_size": (c_size_t, [c_int] * 4),
     "bevops_lss_voxel_prepare": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
     "bevops_bev_pool_v2_forward_indirect": (c_int, [c_int] + [c_void_p] * 9 + [c_int] * 4 + [c_float] * 3 + [c_void_p]),

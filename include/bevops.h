@@ -962,6 +962,96 @@ int bevops_bev_nms(int mode, const float *boxes_in, const float *scores_in, cons
 int bevops_bev_iou(const float *boxes_a, int num_a, const float *boxes_b, int num_b, float *iou, void *stream);
 
 /* ------------------------------------------------------------------------
+ * 2-D detection decode (csrc/decode2d.hip): the post-processing of the reference's two 2-D detectors
+ * (det2trt/models/detector/centernet.py, yolox.py: post_process with rescale=True), which it runs as framework ops with
+ * data-dependent shapes.  The statement below is the published algorithm of mmdet 2.x (CenterNetHead.get_bboxes /
+ * decode_heatmap, YOLOXHead.get_bboxes / _bbox_decode / _bboxes_nms) and of mmcv.ops.batched_nms / nms.  Neither
+ * library is part of this project's test environment, so parity with the libraries themselves is UNPINNED
+ * (design/postprocess.md); what is pinned is this statement, through an independent numpy restatement.
+ *
+ * As the "Detection decode" entries above: FIXED-CAPACITY outputs, no host round trip, no launch sized by a device
+ * value, capturable, bit-reproducible (no atomic whose order can show in a result).  Map inputs are F32 or F16 (F16
+ * values widened), I8 is BEVOPS_NOT_SUPPORTED; all arithmetic and all outputs are F32 (labels, count, index int32).
+ * Each map is dense per batch item and read in place through (channel stride, pixel stride) pairs in elements:
+ * (H * W, 1) for contiguous NCHW, (1, channels) for channels-last.  Inputs need no particular alignment.  F32
+ * arithmetic is written operation by operation, each rounded once, never contracted into an FMA; divisions are IEEE.
+ * `*_host` arrays are read during the call only.  Per-image host values travel as kernel arguments: batch <= 64 for the
+ * two decoders, else BEVOPS_NOT_SUPPORTED.  NULL pointers (where not stated optional) are BEVOPS_BAD_PARAM.  All checks
+ * happen on the host before any device call.
+ *
+ * bevops_centernet_decode.  heatmap [batch, C, H, W] holds SCORES (the head applied the sigmoid; none is applied here),
+ * wh [batch, 2, H, W], offset [batch, 2, H, W]; strides_host[6] = the pairs of heatmap, wh, offset.
+ *   LOCAL MAXIMUM: a cell keeps its value when no cell of its kernel x kernel window, clipped to the image, is greater
+ *   (max_pool2d, stride 1, -inf padding, hmax == heat); otherwise its value is +0.  A kept -0 counts as +0.  kernel is
+ *   1, 3, 5 or 7; other sizes are BEVOPS_NOT_SUPPORTED (even or < 1 included; < 1 is BEVOPS_BAD_PARAM).
+ *   TOP k: the thinned values of the C H W cells under the RANKING RULE above -- larger value first, equal values (the
+ *   many exact zeros included) by lower flat index c H W + y W + x first.  label = index / (H W), y and x from the rest.
+ *   BOX: xs = x + offset0, ys = y + offset1; tl_x = (xs - wh0 / 2) rx, br_x = (xs + wh0 / 2) rx, y likewise with wh1 and
+ *   ry; rx = (float)((double)inp_w / W), ry = (float)((double)inp_h / H).  Then x -= border_host[b][0],
+ *   y -= border_host[b][1] (border_host [batch, 2] = mmdet's border[2], border[0]; NULL = none); then, when
+ *   scale_factor_host [batch, 4] is not NULL, the four columns are divided by it (mmdet's rescale).
+ *   OUTPUT: boxes [batch, k, 4] (tl_x, tl_y, br_x, br_y), scores [batch, k], labels [batch, k], count [batch], in rank
+ *   order.  score_threshold < 0 (mmdet: none): count = k.  Otherwise rows with score > score_threshold are kept,
+ *   compacted to the front, zeros behind.
+ *   NaN: a NaN cell is never greater and nothing is greater than it, so it is kept, suppresses nothing, and ranks by
+ *   its bits (a positive NaN before +inf, a negative NaN last); its score is written as it is.  Stays inside the buffers.
+ *   LIMITS: 1 <= k <= min(4 096, C H W) and C H W <= 2^24, else BEVOPS_NOT_SUPPORTED; a workspace that is NULL,
+ *   shorter than bevops_centernet_decode_workspace_size or not 8-byte aligned, a NaN threshold, a non-finite or zero
+ *   scale factor, a non-finite border, a stride < 1: BEVOPS_BAD_PARAM.  The size query is 0 exactly where the entry
+ *   answers BEVOPS_NOT_SUPPORTED for its dimensions (or the dimensions are < 1).  Two launches.
+ *
+ * bevops_yolox_decode.  num_levels (1 .. 8) levels; level l: cls_host[l] -> [batch, C, H_l, W_l], bbox_host[l] ->
+ * [batch, 4, H_l, W_l], obj_host[l] -> [batch, 1, H_l, W_l] device pointers, all LOGITS; level_shapes_host [L, 3] =
+ * (H_l, W_l, stride_l); strides_host [L, 6] = the pairs of cls, bbox, obj.
+ *   PRIORS: cell (row, col) of level l has the prior (col stride_l, row stride_l) (MlvlPointGenerator, offset 0);
+ *   priors are numbered level-major, then row, then column, P in all (P <= 2^24).
+ *   BOX: cx = p0 stride + prior_x, cy = p1 stride + prior_y, w = exp(p2) stride, h = exp(p3) stride, x1 = cx - w / 2,
+ *   y1 = cy - h / 2, x2 = cx + w / 2, y2 = cy + h / 2; then, when scale_factor_host [batch, 4] is not NULL, divided by
+ *   it (mmdet rescales BEFORE the NMS).
+ *   SCORE: sigmoid(obj) * sigmoid(largest class logit); label = argmax of the F32 class LOGIT, ties to the lower class
+ *   (a NaN logit of a class > 0 never wins).  DEVIATION: mmdet takes the argmax after the sigmoid, which differs only
+ *   where the sigmoid saturates and ties logits that differ.
+ *   OUTPUT, in prior order, no compaction, no threshold (bevops_box_nms applies it): boxes [batch, P, 4], scores
+ *   [batch, P], labels [batch, P].  One launch.
+ *
+ * bevops_box_nms: the axis-aligned batched_nms.
+ *   boxes_in [batch, num, 4] F32 (x1, y1, x2, y2), scores_in [batch, num] F32, labels_in [batch, num] int32, count_in
+ *   [batch] int32 read ON THE DEVICE (NULL = num; above num is read as num, below 0 as 0).
+ *   CANDIDATES: rows below count_in[b] with score >= score_threshold (mmdet's valid_mask; -inf = every row; a NaN
+ *   score is no candidate).  RANK: descending score, equal scores (-0 equals +0) by LOWER INPUT ROW first.
+ *   PAIR TEST, F32, in this order: area = (x2 - x1) (y2 - y1); iw = max(min(x2_i, x2_j) - max(x1_i, x1_j), 0), ih
+ *   likewise; inter = iw ih; iou = inter / ((area_i + area_j) - inter).  Row j is suppressed by an earlier kept row i
+ *   when iou > iou_threshold (strictly; a NaN iou suppresses nothing) and, with class_aware = 1, label_i == label_j.
+ *   A row with a non-finite coordinate suppresses nothing and is not suppressed.
+ *   DEVIATION: mmcv realises class-awareness by adding label (max_coordinate + 1) to the coordinates, which perturbs
+ *   their low bits and lets boxes with negative coordinates leak across classes.  That is NOT restated: the label
+ *   test is the definition here.
+ *   OUTPUT as bevops_bev_nms: kept rows first, in rank order, at most max_out of them, into boxes [batch, max_out, 4],
+ *   scores, labels [batch, max_out], count [batch], index [batch, max_out] (input row numbers; may be NULL);
+ *   everything at and behind count[b] is zero.  Kept rows are copied bits.
+ *   LIMITS: 1 <= num <= 16 384 (above: BEVOPS_NOT_SUPPORTED, and the size query is 0), 1 <= max_out <= num,
+ *   class_aware 0 or 1; a NaN score_threshold, a non-finite iou_threshold, a workspace that is NULL, shorter than
+ *   bevops_box_nms_workspace_size(batch, num) or not 8-byte aligned: BEVOPS_BAD_PARAM.  The workspace holds the
+ *   suppression matrix for the worst case, num^2 / 8 bytes per item (32 MiB at 16 384 rows); only the part the
+ *   candidates need is written and read.  Three launches.
+ * ------------------------------------------------------------------------ */
+size_t bevops_centernet_decode_workspace_size(int batch, int num_classes, int height, int width, int k);
+int bevops_centernet_decode(int dtype, const void *heatmap, const void *wh, const void *offset,
+                            const int32_t *strides_host, float *boxes, float *scores, int32_t *labels, int32_t *count,
+                            int batch, int num_classes, int map_h, int map_w, int k, int kernel, int inp_h, int inp_w,
+                            const float *border_host, const float *scale_factor_host, float score_threshold,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int bevops_yolox_decode(int dtype, const void *const *cls_host, const void *const *bbox_host,
+                        const void *const *obj_host, const int32_t *level_shapes_host, const int32_t *strides_host,
+                        float *boxes, float *scores, int32_t *labels, int batch, int num_levels, int num_classes,
+                        const float *scale_factor_host, void *stream);
+size_t bevops_box_nms_workspace_size(int batch, int num);
+int bevops_box_nms(const float *boxes_in, const float *scores_in, const int32_t *labels_in, const int32_t *count_in,
+                   float *boxes, float *scores, int32_t *labels, int32_t *count, int32_t *index, int batch, int num,
+                   float score_threshold, float iou_threshold, int class_aware, int max_out, void *workspace,
+                   size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
  * BEVDet view-transformer index build (csrc/lss_prepare.hip): LSSViewTransformer.get_lidar_coor followed by
  * voxel_pooling_prepare_v2 (third_party/bev_mmdet3d/models/necks/view_transformer.py:126-168, 239-312) on the device,
  * with fixed-size outputs and no host round trip (capturable), so the five index arrays of bev_pool_v2 can follow the
