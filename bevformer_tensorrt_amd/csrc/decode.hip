@@ -18,7 +18,9 @@
 // NMS-free: one launch, one block per batch item.  CenterPoint with more candidates than one block's chunk: every
 // block selects the top max_num of its chunk into the caller's workspace, then one block per batch item selects among
 // those, sorts, gathers the heads at the winning cells and decodes.
-#include "topk.h"
+// Shared with csrc/decode2d.hip and csrc/nms.hip through csrc/detect.h: the typed loads, the partial-selection kernel,
+// the emit routine behind the selection (compaction, row write, zero tail, count) and the host entries' common checks.
+#include "detect.h"
 
 namespace bevops {
 namespace {
@@ -27,13 +29,6 @@ constexpr int kNmsFreeMaxCand = 16384;      // num_query * num_classes of bevops
 constexpr int kMaxWinners = 16384;          // max_num of bevops_nms_free_decode: 128 KiB of keys in LDS
 constexpr int kCpChunk = 4096;              // candidates per block of the CenterPoint partial selection
 constexpr int kCpMaxWinners = 4096;         // max_num of bevops_centerpoint_decode
-
-template <typename T>
-__device__ __forceinline__ float ld(const T *p, size_t i);
-template <>
-__device__ __forceinline__ float ld<float>(const float *p, size_t i) { return p[i]; }
-template <>
-__device__ __forceinline__ float ld<__half>(const __half *p, size_t i) { return __half2float(p[i]); }
 
 // key sources of block_topk: element i of the block's n candidates
 template <typename T>
@@ -47,65 +42,20 @@ struct LogitSrc {   // logits at p[(i / inner) * outer_stride + (i % inner) * in
     return ((u64)rank_bits(ld(p, at)) << 32) | f;
   }
 };
-struct KeySrc {
-  const u64 *p;
-  __device__ __forceinline__ u64 operator()(unsigned i) const { return p[i]; }
-};
-
-// Position of this thread's row among the kept rows of the block's current 1024 ranks (+ running), and the new running
-// total.  Every thread of the block calls it.
-__device__ __forceinline__ unsigned compact_slot(bool keep, unsigned &running, unsigned *part) {
-  const unsigned t = threadIdx.x;
-  const unsigned long long m = __ballot(keep);
-  const unsigned before = (unsigned)__popcll(m & ((1ull << (t & 63)) - 1ull));
-  if ((t & 63) == 0) part[t >> 6] = (unsigned)__popcll(m);
-  __syncthreads();
-  unsigned off = running, total = running;
-  for (unsigned w = 0; w < (unsigned)kDecWaves; ++w) {
-    const unsigned v = part[w];
-    if (w < (t >> 6)) off += v;
-    total += v;
-  }
-  __syncthreads();   // part is rewritten by the next round
-  running = total;
-  return off + before;
-}
-
 struct Range6 {
   float v[6];
 };
 __device__ __forceinline__ bool in_range(float x, float y, float z, const Range6 &r) {
   return x >= r.v[0] && y >= r.v[1] && z >= r.v[2] && x <= r.v[3] && y <= r.v[4] && z <= r.v[5];
 }
-__device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ void write_row(float *boxes, float *scores, int32_t *labels, size_t row, const float *b,
-                                          float s, int label) {
-#pragma unroll
-  for (int c = 0; c < 9; ++c) boxes[row * 9 + c] = b[c];
-  scores[row] = s;
-  labels[row] = label;
-}
-__device__ __forceinline__ void zero_tail(float *boxes, float *scores, int32_t *labels, size_t row0, unsigned from,
-                                          unsigned to) {
-  for (unsigned r = from + threadIdx.x; r < to; r += kDecThreads) {
-#pragma unroll
-    for (int c = 0; c < 9; ++c) boxes[(row0 + r) * 9 + c] = 0.f;
-    scores[row0 + r] = 0.f;
-    labels[row0 + r] = 0;
-  }
-}
-
-extern __shared__ __attribute__((aligned(16))) char dec_smem[];
-
 template <typename T>
 __global__ __launch_bounds__(kDecThreads) void nms_free_decode_kernel(
     const T *__restrict__ cls, const T *__restrict__ bbox, float *__restrict__ boxes, float *__restrict__ scores,
     int32_t *__restrict__ labels, int32_t *__restrict__ count, unsigned num_query, unsigned num_classes, unsigned K,
     unsigned cap, int idx_bytes, Range6 range, float score_threshold, int bottom_center) {
-  const unsigned b = blockIdx.x, t = threadIdx.x;
+  const unsigned b = blockIdx.x;
   const unsigned n = num_query * num_classes;
-  const DecLds l = carve(dec_smem, cap);
+  const DecLds l = carve(det_smem, cap);
   const LogitSrc<T> src{cls + (size_t)b * n, 0u, n, 0, 1};
   block_topk(src, n, K, cap, idx_bytes, true, l);
 
@@ -132,54 +82,37 @@ __global__ __launch_bounds__(kDecThreads) void nms_free_decode_kernel(
     }
   }
 
-  const size_t row0 = (size_t)b * K;
-  unsigned running = 0;
-  for (unsigned r0 = 0; r0 < K; r0 += kDecThreads) {
-    const unsigned r = r0 + t;
-    bool keep = false;
-    float box[9], s = 0.f;
-    int label = 0;
-    const u64 key = r < K ? l.list[r] : kSentinel;
-    const unsigned idx = (unsigned)key;
-    if (idx < n) {   // (always, for r < K: max_num <= n; a sentinel must never become an address)
-      s = sigmoid_f32(rank_logit((unsigned)(key >> 32)));
-      const unsigned q = idx / num_classes;
-      label = (int)(idx % num_classes);
-      const T *p = bbox + ((size_t)b * num_query + q) * 10;
-      float v[10];
+  emit_ranked<9>(l, K, b, boxes, scores, labels, count,
+                 [&](u64 key, unsigned idx, float *box, float &s, int &label) __attribute__((always_inline)) {
+    if (idx >= n) return false;   // (never, for r < K: max_num <= n; a sentinel must never become an address)
+    s = sigmoid_f32(rank_logit((unsigned)(key >> 32)));
+    const unsigned q = idx / num_classes;
+    label = (int)(idx % num_classes);
+    const T *p = bbox + ((size_t)b * num_query + q) * 10;
+    float v[10];
 #pragma unroll
-      for (int c = 0; c < 10; ++c) v[c] = ld(p, c);
-      box[0] = v[0], box[1] = v[1], box[2] = v[4];
-      box[3] = expf(v[2]), box[4] = expf(v[3]), box[5] = expf(v[5]);
-      box[6] = atan2f(v[6], v[7]);
-      box[7] = v[8], box[8] = v[9];
-      keep = in_range(box[0], box[1], box[2], range) && (mode == 2 || (mode == 0 ? s > thr : s >= thr));
-      if (bottom_center) box[2] = sub_rn(box[2], mul_rn(box[5], 0.5f));
-    }
-    const unsigned slot = compact_slot(keep, running, l.part);
-    if (keep) write_row(boxes, scores, labels, row0 + slot, box, s, label);
-  }
-  zero_tail(boxes, scores, labels, row0, running, K);
-  if (t == 0) count[b] = (int32_t)running;
+    for (int c = 0; c < 10; ++c) v[c] = ld(p, c);
+    box[0] = v[0], box[1] = v[1], box[2] = v[4];
+    box[3] = expf(v[2]), box[4] = expf(v[3]), box[5] = expf(v[5]);
+    box[6] = atan2f(v[6], v[7]);
+    box[7] = v[8], box[8] = v[9];
+    const bool keep = in_range(box[0], box[1], box[2], range) && (mode == 2 || (mode == 0 ? s > thr : s >= thr));
+    if (bottom_center) box[2] = sub_rn(box[2], mul_rn(box[5], 0.5f));
+    return keep;
+  });
 }
 
-// CenterPoint, first launch: block (x, b) selects the top Kslot of its chunk of batch item b's heat map into
-// ws[(b * gridDim.x + x) * Kslot ..]; a chunk with fewer candidates fills up with sentinels.
+// CenterPoint, first launch (partial_topk_kernel of detect.h): a chunk of kCpChunk cells of the heat map itself.
 template <typename T>
-__global__ __launch_bounds__(kDecThreads) void centerpoint_partial_kernel(const T *__restrict__ heat, u64 *__restrict__ ws,
-                                                                           unsigned total, unsigned hw, size_t cs,
-                                                                           size_t ps, unsigned num_classes, unsigned Kslot,
-                                                                           unsigned cap, int idx_bytes) {
-  const unsigned b = blockIdx.y, t = threadIdx.x;
-  const unsigned base = blockIdx.x * (unsigned)kCpChunk;
-  const unsigned n = min((unsigned)kCpChunk, total - base);
-  const DecLds l = carve(dec_smem, cap);
-  const LogitSrc<T> src{heat + (size_t)b * num_classes * hw, base, hw, cs, ps};
-  const unsigned K = min(Kslot, n);
-  block_topk(src, n, K, cap, idx_bytes, false, l);
-  u64 *out = ws + ((size_t)b * gridDim.x + blockIdx.x) * Kslot;
-  for (unsigned i = t; i < Kslot; i += kDecThreads) out[i] = i < K ? l.list[i] : kSentinel;
-}
+struct CpChunk {
+  static constexpr int kChunk = kCpChunk;
+  const T *heat;
+  unsigned hw, num_classes;
+  size_t cs, ps;
+  __device__ __forceinline__ LogitSrc<T> prepare(char *, unsigned b, unsigned base, unsigned) const {
+    return LogitSrc<T>{heat + (size_t)b * num_classes * hw, base, hw, cs, ps};
+  }
+};
 
 struct CpMaps {
   const void *reg, *height, *dim, *rot, *vel, *heat;
@@ -196,9 +129,9 @@ __global__ __launch_bounds__(kDecThreads) void centerpoint_decode_kernel(
     CpMaps m, const u64 *__restrict__ ws, unsigned nkeys, float *__restrict__ boxes, float *__restrict__ scores,
     int32_t *__restrict__ labels, int32_t *__restrict__ count, unsigned num_classes, unsigned H, unsigned W, unsigned K,
     unsigned cap, int idx_bytes, CpGeom g, Range6 range, float score_threshold, int norm_bbox, int heat_is_score) {
-  const unsigned b = blockIdx.x, t = threadIdx.x;
+  const unsigned b = blockIdx.x;
   const unsigned hw = H * W;
-  const DecLds l = carve(dec_smem, cap);
+  const DecLds l = carve(det_smem, cap);
   if (FROM_WS) {
     const KeySrc src{ws + (size_t)b * nkeys};
     block_topk(src, nkeys, K, cap, idx_bytes, true, l);
@@ -210,45 +143,33 @@ __global__ __launch_bounds__(kDecThreads) void centerpoint_decode_kernel(
   const T *reg = static_cast<const T *>(m.reg), *hei = static_cast<const T *>(m.height);
   const T *dim = static_cast<const T *>(m.dim), *rot = static_cast<const T *>(m.rot);
   const T *vel = static_cast<const T *>(m.vel);
-  const size_t row0 = (size_t)b * K;
-  unsigned running = 0;
-  for (unsigned r0 = 0; r0 < K; r0 += kDecThreads) {
-    const unsigned r = r0 + t;
-    bool keep = false;
-    float box[9], s = 0.f;
-    int label = 0;
-    const u64 key = r < K ? l.list[r] : kSentinel;
-    const unsigned idx = (unsigned)key;
-    if (idx < num_classes * hw) {   // (always, for r < K; a sentinel must never become an address)
-      s = rank_logit((unsigned)(key >> 32));
-      if (!heat_is_score) s = sigmoid_f32(s);
-      label = (int)(idx / hw);
-      const unsigned cell = idx % hw;
-      const float col = (float)(cell % W), row = (float)(cell / W);
-      // channel c of a map with C channels at this cell
-      auto at = [&](const T *p, int which, unsigned C, unsigned c) {
-        return ld(p, (size_t)b * C * hw + (size_t)c * m.cs[which] + (size_t)cell * m.ps[which]);
-      };
-      const float rx = reg ? at(reg, 0, 2, 0) : 0.5f, ry = reg ? at(reg, 0, 2, 1) : 0.5f;
-      // (col + reg) * out_size_factor * voxel + pc_range, every step rounded as the reference's tensor ops round it
-      box[0] = add_rn(mul_rn(mul_rn(add_rn(col, rx), g.out_size_factor), g.voxel_x), g.pc_x);
-      box[1] = add_rn(mul_rn(mul_rn(add_rn(row, ry), g.out_size_factor), g.voxel_y), g.pc_y);
-      box[2] = at(hei, 1, 1, 0);
+  emit_ranked<9>(l, K, b, boxes, scores, labels, count,
+                 [&](u64 key, unsigned idx, float *box, float &s, int &label) __attribute__((always_inline)) {
+    if (idx >= num_classes * hw) return false;   // (never, for r < K; a sentinel must never become an address)
+    s = rank_logit((unsigned)(key >> 32));
+    if (!heat_is_score) s = sigmoid_f32(s);
+    label = (int)(idx / hw);
+    const unsigned cell = idx % hw;
+    const float col = (float)(cell % W), row = (float)(cell / W);
+    // channel c of a map with C channels at this cell
+    auto at = [&](const T *p, int which, unsigned C, unsigned c) {
+      return ld(p, (size_t)b * C * hw + (size_t)c * m.cs[which] + (size_t)cell * m.ps[which]);
+    };
+    const float rx = reg ? at(reg, 0, 2, 0) : 0.5f, ry = reg ? at(reg, 0, 2, 1) : 0.5f;
+    // (col + reg) * out_size_factor * voxel + pc_range, every step rounded as the reference's tensor ops round it
+    box[0] = add_rn(mul_rn(mul_rn(add_rn(col, rx), g.out_size_factor), g.voxel_x), g.pc_x);
+    box[1] = add_rn(mul_rn(mul_rn(add_rn(row, ry), g.out_size_factor), g.voxel_y), g.pc_y);
+    box[2] = at(hei, 1, 1, 0);
 #pragma unroll
-      for (unsigned c = 0; c < 3; ++c) {
-        const float d = at(dim, 2, 3, c);
-        box[3 + c] = norm_bbox ? expf(d) : d;
-      }
-      box[6] = atan2f(at(rot, 3, 2, 0), at(rot, 3, 2, 1));
-      box[7] = vel ? at(vel, 4, 2, 0) : 0.f;
-      box[8] = vel ? at(vel, 4, 2, 1) : 0.f;
-      keep = in_range(box[0], box[1], box[2], range) && (score_threshold < 0.f || s > score_threshold);
+    for (unsigned c = 0; c < 3; ++c) {
+      const float d = at(dim, 2, 3, c);
+      box[3 + c] = norm_bbox ? expf(d) : d;
     }
-    const unsigned slot = compact_slot(keep, running, l.part);
-    if (keep) write_row(boxes, scores, labels, row0 + slot, box, s, label);
-  }
-  zero_tail(boxes, scores, labels, row0, running, K);
-  if (t == 0) count[b] = (int32_t)running;
+    box[6] = atan2f(at(rot, 3, 2, 0), at(rot, 3, 2, 1));
+    box[7] = vel ? at(vel, 4, 2, 0) : 0.f;
+    box[8] = vel ? at(vel, 4, 2, 1) : 0.f;
+    return in_range(box[0], box[1], box[2], range) && (score_threshold < 0.f || s > score_threshold);
+  });
 }
 
 inline unsigned cp_blocks(long long total) { return (unsigned)((total + kCpChunk - 1) / kCpChunk); }
@@ -283,11 +204,11 @@ int launch_centerpoint(const CpMaps &m, float *boxes, float *scores, int32_t *la
   const unsigned nblk = cp_blocks(total);
   u64 *ws = static_cast<u64 *>(workspace);
   // K <= kCpMaxWinners = kCpChunk, so a slot holds K keys and the same LDS carve serves both launches
-  if (!ensure_dynamic_lds<centerpoint_partial_kernel<T>>(lds)) return BEVOPS_FAILURE;
+  const CpChunk<T> chunk{static_cast<const T *>(m.heat), hw, (unsigned)nc, (size_t)m.cs[5], (size_t)m.ps[5]};
+  if (!ensure_dynamic_lds<partial_topk_kernel<CpChunk<T>>>(lds)) return BEVOPS_FAILURE;
   if (!ensure_dynamic_lds<centerpoint_decode_kernel<T, true>>(lds)) return BEVOPS_FAILURE;
-  hipLaunchKernelGGL(centerpoint_partial_kernel<T>, dim3(nblk, (unsigned)batch), dim3(kDecThreads), lds, st,
-                     static_cast<const T *>(m.heat), ws, total, hw, (size_t)m.cs[5], (size_t)m.ps[5], (unsigned)nc,
-                     (unsigned)K, cap, ib);
+  hipLaunchKernelGGL(partial_topk_kernel<CpChunk<T>>, dim3(nblk, (unsigned)batch), dim3(kDecThreads), lds, st, chunk, ws,
+                     total, (unsigned)K, cap, ib);
   if (hipGetLastError() != hipSuccess) return BEVOPS_FAILURE;
   hipLaunchKernelGGL((centerpoint_decode_kernel<T, true>), dim3((unsigned)batch), dim3(kDecThreads), lds, st, m, ws,
                      nblk * (unsigned)K, boxes, scores, labels, count, (unsigned)nc, (unsigned)H, (unsigned)W, (unsigned)K,
@@ -307,7 +228,7 @@ extern "C" int bevops_nms_free_decode(int dtype, const void *cls_logits, const v
   if (!cls_logits || !bbox_preds || !boxes || !scores || !labels || !count || !post_center_range_host)
     return BEVOPS_BAD_PARAM;
   if (batch < 1 || num_query < 1 || num_classes < 1 || max_num < 1) return BEVOPS_BAD_PARAM;
-  if (dtype != BEVOPS_F32 && dtype != BEVOPS_F16) return dtype == BEVOPS_I8 ? BEVOPS_NOT_SUPPORTED : BEVOPS_BAD_PARAM;
+  if (const int st = dtype_status(dtype)) return st;
   const long long cand = (long long)num_query * num_classes;
   if (max_num > cand || !(score_threshold <= 3.0e38f)) return BEVOPS_BAD_PARAM;   // (NaN / inf: the relaxation needs a finite start)
   if (cand > kNmsFreeMaxCand || max_num > kMaxWinners || batch > 65535) return BEVOPS_NOT_SUPPORTED;
@@ -340,15 +261,14 @@ extern "C" int bevops_centerpoint_decode(int dtype, const void *reg, const void 
       !post_center_range_host)
     return BEVOPS_BAD_PARAM;
   if (batch < 1 || num_classes < 1 || map_h < 1 || map_w < 1 || max_num < 1) return BEVOPS_BAD_PARAM;
-  if (dtype != BEVOPS_F32 && dtype != BEVOPS_F16) return dtype == BEVOPS_I8 ? BEVOPS_NOT_SUPPORTED : BEVOPS_BAD_PARAM;
+  if (const int st = dtype_status(dtype)) return st;
   const long long total = (long long)num_classes * map_h * map_w;
   if (max_num > total || score_threshold != score_threshold) return BEVOPS_BAD_PARAM;
   for (int i = 0; i < 12; ++i)
     if (strides_host[i] < 1) return BEVOPS_BAD_PARAM;
   if (total > 0x7fffffffLL || max_num > kCpMaxWinners || batch > 65535) return BEVOPS_NOT_SUPPORTED;
   const size_t need = bevops_centerpoint_decode_workspace_size(batch, num_classes, map_h, map_w, max_num);
-  if (need && (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7u)))
-    return BEVOPS_BAD_PARAM;
+  if (need && !workspace_ok(workspace, workspace_bytes, need)) return BEVOPS_BAD_PARAM;
   CpMaps m;
   m.reg = reg, m.height = height, m.dim = dim, m.rot = rot, m.vel = vel, m.heat = heatmap;
   for (int i = 0; i < 6; ++i) m.cs[i] = strides_host[2 * i], m.ps[i] = strides_host[2 * i + 1];

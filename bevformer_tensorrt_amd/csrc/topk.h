@@ -1,5 +1,5 @@
-// Block-wide selection shared by the detection decoders (decode.hip) and the BEV NMS (nms.hip): the 64-bit ranking
-// key, an 8-bit radix select over such keys and a bitonic sort of the winners in LDS.
+// Block-wide selection shared by the detection decoders (decode.hip, decode2d.hip) and the NMS (nms.hip), which reach
+// it through detect.h: the 64-bit ranking key, an 8-bit radix select over such keys and a bitonic sort of the winners in LDS.
 //
 // Ranking rule (include/bevops.h, design/postprocess.md): candidates rank by an fp32 value, larger first; equal values
 // (-0 counts as +0) rank by lower flat index first.  Both go into one 64-bit key,
@@ -45,7 +45,7 @@ __device__ __forceinline__ DecLds carve(char *smem, unsigned cap) {
   l.sel = l.part + kDecWaves;
   return l;
 }
-inline size_t lds_bytes(unsigned cap) { return (size_t)cap * 8 + (256 + kDecWaves + 4) * sizeof(unsigned); }
+__host__ __device__ inline size_t lds_bytes(unsigned cap) { return (size_t)cap * 8 + (256 + kDecWaves + 4) * sizeof(unsigned); }
 inline unsigned pow2_at_least(unsigned v) {
   unsigned p = 1;
   while (p < v) p <<= 1;

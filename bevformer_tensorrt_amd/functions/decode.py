@@ -34,17 +34,24 @@ def _threshold(score_threshold):
     return float(score_threshold) if score_threshold else -1.0
 
 
-def _outputs(batch, max_num, device):
-    return (torch.empty(batch, max_num, 9, dtype=torch.float32, device=device),
-            torch.empty(batch, max_num, dtype=torch.float32, device=device),
-            torch.empty(batch, max_num, dtype=torch.int32, device=device),
-            torch.empty(batch, dtype=torch.int32, device=device))
+def _outputs(empty, batch, cap, cols, device, index=False):
+    """The fixed-size tensors an entry writes: boxes [batch, cap, cols], scores, labels, count and, on request, index.
+    empty: the calling module's torch.empty (every wrapper allocates through its own `torch` name, which the
+    buffer-contract tests replace by an arena)."""
+    cap = max(cap, 0)
+    out = (empty(batch, cap, cols, dtype=torch.float32, device=device), empty(batch, cap, dtype=torch.float32, device=device),
+           empty(batch, cap, dtype=torch.int32, device=device), empty(batch, dtype=torch.int32, device=device))
+    return out + (empty(batch, cap, dtype=torch.int32, device=device),) if index else out
 
 
-def _trim(boxes, scores, labels, count, columns=9):
+def _trim(boxes, scores, labels, count, index=None, columns=None):
+    """Padded tensors -> one dict per batch item, cut at count[b] (one synchronisation) and to `columns` box columns."""
     out = []
     for b, n in enumerate(count.tolist()):
-        out.append({"bboxes": boxes[b, :n, :columns], "scores": scores[b, :n], "labels": labels[b, :n]})
+        d = {"bboxes": boxes[b, :n, :columns], "scores": scores[b, :n], "labels": labels[b, :n]}
+        if index is not None:
+            d["index"] = index[b, :n]
+        out.append(d)
     return out
 
 
@@ -68,7 +75,7 @@ def nms_free_decode(cls_logits, bbox_preds, max_num, post_center_range, score_th
     max_num = int(max_num)
     rng = _range6(post_center_range)
     cls, box = cls_logits.contiguous(), bbox_preds.contiguous()
-    boxes, scores, labels, count = _outputs(B, max(max_num, 0), cls.device)
+    boxes, scores, labels, count = _outputs(torch.empty, B, max_num, 9, cls.device)
     handle = _lib.load_library()
     with torch.cuda.device(cls.device):
         st = handle.bevops_nms_free_decode(dt, cls.data_ptr(), box.data_ptr(), boxes.data_ptr(), scores.data_ptr(),
@@ -132,7 +139,7 @@ def centerpoint_decode(reg, height, dim, rot, vel, heatmap, max_num, post_center
     max_num = int(max_num)
     rng = _range6(post_center_range)
     strides_c = (ctypes.c_int32 * 12)(*strides)
-    boxes, scores, labels, count = _outputs(B, max(max_num, 0), heatmap.device)
+    boxes, scores, labels, count = _outputs(torch.empty, B, max_num, 9, heatmap.device)
     handle = _lib.load_library()
     stream = _lib.current_stream_ptr(heatmap.device)
     nws = handle.bevops_centerpoint_decode_workspace_size(B, nc, H, W, max_num)
@@ -146,4 +153,4 @@ def centerpoint_decode(reg, height, dim, rot, vel, heatmap, max_num, post_center
     _lib.check(st, "bevops_centerpoint_decode")
     if padded:
         return boxes, scores, labels, count
-    return _trim(boxes, scores, labels, count, 9 if vel is not None else 7)
+    return _trim(boxes, scores, labels, count, columns=9 if vel is not None else 7)

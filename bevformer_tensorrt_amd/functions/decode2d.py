@@ -1,4 +1,5 @@
-"""2-D detection decode on the device (csrc/decode2d.hip): CenterNet, YOLOX and the axis-aligned batched NMS.
+"""2-D detection decode on the device: CenterNet and YOLOX (csrc/decode2d.hip) and the axis-aligned batched NMS (the box
+entry of csrc/nms.hip).
 
 `centernet_decode` is mmdet 2.x's CenterNetHead.get_bboxes (decode_heatmap: local maximum, top k, box, border, rescale),
 `yolox_decode` is YOLOXHead.get_bboxes up to the NMS (_bbox_decode, score, label), `box_nms` is mmcv's batched_nms with
@@ -20,36 +21,27 @@ import torch
 
 from ..utils import lib as _lib
 from ..utils import workspace as _ws
-from .decode import _map_strides
+from .decode import _map_strides, _outputs, _trim
+from .nms import _nms_inputs
 
 
 def _rows(values, batch, width, name):
-    """None or [batch, width] host floats (a single row is repeated for every item)."""
+    """None, or host floats as an fp32 CPU tensor [batch, width] (a single row is repeated for every item)."""
     if values is None:
         return None
-    if torch.is_tensor(values):
-        values = values.detach().cpu().tolist()
-    rows = [[float(v) for v in r] for r in (values if hasattr(values[0], "__len__") else [values] * batch)]
-    if len(rows) != batch or any(len(r) != width for r in rows):
+    t = torch.as_tensor(values, dtype=torch.float32).detach().cpu()
+    if t.numel() == width:
+        t = t.reshape(1, width).expand(batch, width)
+    if tuple(t.shape) != (batch, width):
         raise ValueError(f"{name} must be [{batch}, {width}]")
-    return rows
+    return t
 
 
 def _c_rows(rows):
     if rows is None:
         return None
-    flat = [v for r in rows for v in r]
+    flat = rows.flatten().tolist()
     return (ctypes.c_float * len(flat))(*flat)
-
-
-def _trim(boxes, scores, labels, count, index=None):
-    out = []
-    for b, n in enumerate(count.tolist()):
-        d = {"bboxes": boxes[b, :n], "scores": scores[b, :n], "labels": labels[b, :n]}
-        if index is not None:
-            d["index"] = index[b, :n]
-        out.append(d)
-    return out
 
 
 def centernet_decode(heatmap, wh, offset, k, input_shape, kernel=3, border=None, scale_factor=None, score_threshold=None,
@@ -82,11 +74,7 @@ def centernet_decode(heatmap, wh, offset, k, input_shape, kernel=3, border=None,
         ptrs.append(t.data_ptr())
         strides += [cs, ps]
     dev = heatmap.device
-    cap = max(k, 0)
-    boxes = torch.empty(B, cap, 4, dtype=torch.float32, device=dev)
-    scores = torch.empty(B, cap, dtype=torch.float32, device=dev)
-    labels = torch.empty(B, cap, dtype=torch.int32, device=dev)
-    count = torch.empty(B, dtype=torch.int32, device=dev)
+    boxes, scores, labels, count = _outputs(torch.empty, B, k, 4, dev)
     handle = _lib.load_library()
     stream = _lib.current_stream_ptr(dev)
     nws = handle.bevops_centernet_decode_workspace_size(B, C, H, W, k)
@@ -155,12 +143,7 @@ def box_nms(boxes, scores, labels, count=None, *, score_threshold=None, iou_thre
     every row).  Row j is suppressed by an earlier kept row i when IoU > iou_threshold and, with class_aware, the
     labels are equal.  N <= 16 384, 1 <= max_out <= N (None = N).  Returns boxes [B, max_out, 4], scores, labels,
     count [B], index [B, max_out] int32 (input rows), kept rows first in rank order, zero behind count."""
-    if boxes.ndim == 2:
-        boxes, scores, labels = boxes[None], scores[None], labels[None]
-        count = None if count is None else count.reshape(1)
-    if boxes.ndim != 3 or boxes.shape[-1] != 4 or scores.shape != boxes.shape[:2] or labels.shape != boxes.shape[:2]:
-        raise ValueError(f"box_nms: shapes {tuple(boxes.shape)}, {tuple(scores.shape)}, {tuple(labels.shape)} do not "
-                         "match [B, N, 4], [B, N], [B, N]")
+    boxes, scores, labels, count = _nms_inputs("box_nms", 4, boxes, scores, labels, count)
     B, N = scores.shape
     post = N if max_out is None else int(max_out)
     thr = float("-inf") if score_threshold is None else float(score_threshold)
@@ -169,22 +152,8 @@ def box_nms(boxes, scores, labels, count=None, *, score_threshold=None, iou_thre
         out = box_nms_torch(boxes, scores, labels, count, score_threshold=thr, iou_threshold=iou_threshold,
                             class_aware=class_aware, max_out=post)
         return out if padded else _trim(*out)
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or labels.dtype != torch.int32:
-        raise TypeError("box_nms: boxes and scores must be float32, labels int32")
-    if count is not None and (count.dtype != torch.int32 or count.shape != boxes.shape[:1]):
-        raise TypeError("box_nms: count must be int32 [B]")
-    for t in (scores, labels, count):
-        if t is not None and t.device != boxes.device:
-            raise TypeError("box_nms: tensors on different devices")
-    boxes, scores, labels = boxes.contiguous(), scores.contiguous(), labels.contiguous()
-    count = None if count is None else count.contiguous()
     dev = boxes.device
-    cap = max(post, 0)
-    out_b = torch.empty(B, cap, 4, dtype=torch.float32, device=dev)
-    out_s = torch.empty(B, cap, dtype=torch.float32, device=dev)
-    out_l = torch.empty(B, cap, dtype=torch.int32, device=dev)
-    out_i = torch.empty(B, cap, dtype=torch.int32, device=dev)
-    out_c = torch.empty(B, dtype=torch.int32, device=dev)
+    out_b, out_s, out_l, out_c, out_i = _outputs(torch.empty, B, post, 4, dev, index=True)
     handle = _lib.load_library()
     stream = _lib.current_stream_ptr(dev)
     nws = handle.bevops_box_nms_workspace_size(B, N)
@@ -195,6 +164,4 @@ def box_nms(boxes, scores, labels, count=None, *, score_threshold=None, iou_thre
                                    out_l.data_ptr(), out_c.data_ptr(), out_i.data_ptr(), B, N, thr, float(iou_threshold),
                                    int(bool(class_aware)), post, ws.data_ptr(), nws, stream)
     _lib.check(st, "bevops_box_nms")
-    if padded:
-        return out_b, out_s, out_l, out_c, out_i
-    return _trim(out_b, out_s, out_l, out_c, out_i)
+    return (out_b, out_s, out_l, out_c, out_i) if padded else _trim(out_b, out_s, out_l, out_c, out_i)

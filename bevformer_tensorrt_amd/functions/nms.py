@@ -1,4 +1,5 @@
-"""BEV non-maximum suppression on the device (csrc/nms.hip): what CenterHead.get_bboxes does behind the coder.
+"""BEV non-maximum suppression on the device (the BEV entry of csrc/nms.hip): what CenterHead.get_bboxes does behind the
+coder.
 
 `bev_nms` is the batched face of `bevops_bev_nms`: the rotated scale-NMS of CenterHead.get_task_detections
 (third_party/bev_mmdet3d/models/dense_heads/centerpoint_head.py:808-905) or the circle NMS of get_bboxes (:750-773),
@@ -22,6 +23,7 @@ import torch
 
 from ..utils import lib as _lib
 from ..utils import workspace as _ws
+from .decode import _outputs, _trim
 
 _MODES = {"rotate": 0, "circle": 1}
 
@@ -37,11 +39,25 @@ def _factors(rescale_factor):
     return [float(rescale_factor)]
 
 
-def _trim(boxes, scores, labels, count, index):
-    out = []
-    for b, n in enumerate(count.tolist()):
-        out.append({"bboxes": boxes[b, :n], "scores": scores[b, :n], "labels": labels[b, :n], "index": index[b, :n]})
-    return out
+def _nms_inputs(name, width, boxes, scores, labels, count):
+    """What `bev_nms` and `box_nms` do with their inputs: lift a single item to a batch of one, check the shapes
+    [B, N, width], [B, N], [B, N] and, for device tensors, dtypes, count and devices, and make them contiguous."""
+    if boxes.ndim == 2:
+        boxes, scores, labels = boxes[None], scores[None], labels[None]
+        count = None if count is None else count.reshape(1)
+    if boxes.ndim != 3 or boxes.shape[-1] != width or scores.shape != boxes.shape[:2] or labels.shape != boxes.shape[:2]:
+        raise ValueError(f"{name}: shapes {tuple(boxes.shape)}, {tuple(scores.shape)}, {tuple(labels.shape)} do not "
+                         f"match [B, N, {width}], [B, N], [B, N]")
+    if not boxes.is_cuda:   # the torch statement takes them as they are
+        return boxes, scores, labels, count
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or labels.dtype != torch.int32:
+        raise TypeError(f"{name}: boxes and scores must be float32, labels int32")
+    if count is not None and (count.dtype != torch.int32 or count.shape != boxes.shape[:1]):
+        raise TypeError(f"{name}: count must be int32 [B]")
+    for t in (scores, labels, count):
+        if t is not None and t.device != boxes.device:
+            raise TypeError(f"{name}: tensors on different devices")
+    return boxes.contiguous(), scores.contiguous(), labels.contiguous(), None if count is None else count.contiguous()
 
 
 def bev_nms(boxes, scores, labels, count=None, *, nms_type="rotate", threshold, pre_max_size=None, post_max_size,
@@ -54,38 +70,19 @@ def bev_nms(boxes, scores, labels, count=None, *, nms_type="rotate", threshold, 
     multiply and divide leave them.  bottom_center: z -= h / 2 (get_bboxes).  N <= 4 096, 1 <= post_max_size <= N."""
     if nms_type not in _MODES:
         raise ValueError(f"bev_nms: nms_type must be 'rotate' or 'circle', got {nms_type!r}")
-    if boxes.ndim == 2:
-        boxes, scores, labels = boxes[None], scores[None], labels[None]
-        count = None if count is None else count.reshape(1)
-    if boxes.ndim != 3 or boxes.shape[-1] != 9 or scores.shape != boxes.shape[:2] or labels.shape != boxes.shape[:2]:
-        raise ValueError(f"bev_nms: shapes {tuple(boxes.shape)}, {tuple(scores.shape)}, {tuple(labels.shape)} do not "
-                         "match [B, N, 9], [B, N], [B, N]")
+    boxes, scores, labels, count = _nms_inputs("bev_nms", 9, boxes, scores, labels, count)
     if not boxes.is_cuda:
         from ..postprocess import bev_nms_torch
         out = bev_nms_torch(boxes, scores, labels, count, nms_type=nms_type, threshold=threshold,
                             pre_max_size=pre_max_size, post_max_size=post_max_size, rescale_factor=rescale_factor,
                             bottom_center=bottom_center)
         return out if padded else _trim(*out)
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or labels.dtype != torch.int32:
-        raise TypeError("bev_nms: boxes and scores must be float32, labels int32")
-    if count is not None and (count.dtype != torch.int32 or count.shape != boxes.shape[:1]):
-        raise TypeError("bev_nms: count must be int32 [B]")
-    for t in (scores, labels, count):
-        if t is not None and t.device != boxes.device:
-            raise TypeError("bev_nms: tensors on different devices")
     B, N = scores.shape
     post = int(post_max_size)
     fac = _factors(rescale_factor)
     fac_c = (ctypes.c_float * max(len(fac), 1))(*fac)
-    boxes, scores, labels = boxes.contiguous(), scores.contiguous(), labels.contiguous()
-    count = None if count is None else count.contiguous()
     dev = boxes.device
-    cap = max(post, 0)
-    out_b = torch.empty(B, cap, 9, dtype=torch.float32, device=dev)
-    out_s = torch.empty(B, cap, dtype=torch.float32, device=dev)
-    out_l = torch.empty(B, cap, dtype=torch.int32, device=dev)
-    out_i = torch.empty(B, cap, dtype=torch.int32, device=dev)
-    out_c = torch.empty(B, dtype=torch.int32, device=dev)
+    out_b, out_s, out_l, out_c, out_i = _outputs(torch.empty, B, post, 9, dev, index=True)
     handle = _lib.load_library()
     stream = _lib.current_stream_ptr(dev)
     nws = handle.bevops_bev_nms_workspace_size(B, N)
@@ -97,9 +94,7 @@ def bev_nms(boxes, scores, labels, count=None, *, nms_type="rotate", threshold, 
                                    int(pre_max_size) if pre_max_size is not None else 0, post, float(threshold),
                                    fac_c, len(fac), int(bool(bottom_center)), ws.data_ptr(), nws, stream)
     _lib.check(st, "bevops_bev_nms")
-    if padded:
-        return out_b, out_s, out_l, out_c, out_i
-    return _trim(out_b, out_s, out_l, out_c, out_i)
+    return (out_b, out_s, out_l, out_c, out_i) if padded else _trim(out_b, out_s, out_l, out_c, out_i)
 
 
 def _xywhr(boxes, xyxyr2xywhr):

@@ -18,10 +18,11 @@ follow the CenterPoint coder: `bev_nms_torch` below is their CPU statement, with
 definition ("the exact overlapping area of the two boxes", box3d_nms.py:230-231) that the kernel's fp32 evaluation is
 measured against.
 """
-import numpy as np
 import torch
 
 from .functions.decode import nms_free_decode, centerpoint_decode
+from .functions.decode2d import _rows
+from .functions.nms import _factors
 
 
 def _rank(values, max_num):
@@ -193,9 +194,21 @@ def bev_iou_fp64(boxes_a, boxes_b):
     return iou.reshape(M, N)
 
 
-def _factor_list(rescale_factor):
-    from .functions.nms import _factors
-    return _factors(rescale_factor)
+def _greedy_keep(order, suppressed_by, post):
+    """The greedy scan both NMS statements share: walk the ranked rows; a row not yet suppressed is kept and suppresses
+    what suppressed_by(i) -- a bool vector over the ranks behind i, computed when row i is kept and not before -- marks.
+    Stops at `post` kept rows.  Returns the kept rows as entries of `order`."""
+    M = order.numel()
+    removed = torch.zeros(M, dtype=torch.bool)
+    keep = []
+    for i in range(M):
+        if removed[i]:
+            continue
+        keep.append(i)
+        if len(keep) == post or i + 1 == M:
+            break
+        removed[i + 1:] |= suppressed_by(i)
+    return order[torch.tensor(keep, dtype=torch.long)]
 
 
 def bev_nms_torch(boxes, scores, labels, count=None, *, nms_type="rotate", threshold, pre_max_size=None,
@@ -215,7 +228,7 @@ def bev_nms_torch(boxes, scores, labels, count=None, *, nms_type="rotate", thres
         raise ValueError(f"post_max_size {post} outside 1 .. {N}")
     if nms_type not in ("rotate", "circle"):
         raise ValueError(f"nms_type must be 'rotate' or 'circle', got {nms_type!r}")
-    fac = _factor_list(rescale_factor)
+    fac = _factors(rescale_factor)
     counts = [N] * B if count is None else [min(max(int(c), 0), N) for c in count.tolist()]
     pre = N if pre_max_size is None or int(pre_max_size) <= 0 else min(int(pre_max_size), N)
     out_b, out_s = torch.zeros(B, post, 9), torch.zeros(B, post)
@@ -242,17 +255,7 @@ def bev_nms_torch(boxes, scores, labels, count=None, *, nms_type="rotate", thres
             x, y = bx[order, 0], bx[order, 1]
             dx, dy = x[:, None] - x[None, :], y[:, None] - y[None, :]
             sup = (dx * dx + dy * dy) <= thr32
-        sup = sup.numpy()
-        removed = np.zeros(order.numel(), dtype=bool)
-        keep = []
-        for i in range(order.numel()):
-            if removed[i]:
-                continue
-            keep.append(i)
-            if len(keep) == post:
-                break
-            removed[i + 1:] |= sup[i, i + 1:]
-        keep = order[torch.tensor(keep, dtype=torch.long)]
+        keep = _greedy_keep(order, lambda i: sup[i, i + 1:], post)
         k = keep.numel()
         if fac:
             bx[:, 3:6] = scaled / f[:, None]
@@ -269,13 +272,6 @@ def bev_nms_torch(boxes, scores, labels, count=None, *, nms_type="rotate", thres
 # from the published algorithm of mmdet 2.x (CenterNetHead.get_bboxes / decode_heatmap, YOLOXHead.get_bboxes /
 # _bbox_decode / _bboxes_nms) and mmcv.ops.batched_nms, as the reference's detectors call them
 # (det2trt/models/detector/{centernet,yolox}.py: post_process); parity with the libraries themselves is unpinned.
-def _host_rows(values, batch, width):
-    if values is None:
-        return None
-    t = torch.as_tensor(values, dtype=torch.float32).detach().cpu().reshape(-1, width)
-    return t.expand(batch, width) if t.shape[0] == 1 else t
-
-
 def centernet_decode_torch(heatmap, wh, offset, k, input_shape, kernel=3, border=None, scale_factor=None,
                            score_threshold=None, return_index=False):
     """The padded result of `centernet_decode` -- boxes [B, k, 4], scores [B, k], labels int32, count [B] -- in torch ops
@@ -303,7 +299,7 @@ def centernet_decode_torch(heatmap, wh, offset, k, input_shape, kernel=3, border
     ry = torch.tensor(float(input_shape[0]) / H, dtype=torch.float32)
     boxes = torch.stack([(xs - w[:, 0] / 2) * rx, (ys - w[:, 1] / 2) * ry, (xs + w[:, 0] / 2) * rx,
                          (ys + w[:, 1] / 2) * ry], dim=-1)
-    bd, sf = _host_rows(border, B, 2), _host_rows(scale_factor, B, 4)
+    bd, sf = _rows(border, B, 2, "border"), _rows(scale_factor, B, 4, "scale_factor")
     if bd is not None:
         boxes = boxes - bd[:, None, [0, 1, 0, 1]]
     if sf is not None:
@@ -343,7 +339,7 @@ def yolox_decode_torch(cls_scores, bbox_preds, objectnesses, strides=(8, 16, 32)
         labels.append(first.min(dim=-1).values.to(torch.int32))
         scores.append(obj.sigmoid() * best.sigmoid())
     boxes, scores, labels = torch.cat(boxes, 1), torch.cat(scores, 1), torch.cat(labels, 1)
-    sf = _host_rows(scale_factor, boxes.shape[0], 4)
+    sf = _rows(scale_factor, boxes.shape[0], 4, "scale_factor")
     if sf is not None:
         boxes = boxes / sf[:, None, :]
     return boxes, scores, labels
@@ -382,23 +378,15 @@ def box_nms_torch(boxes, scores, labels, count=None, *, score_threshold=None, io
         q, lb = boxes[b][order], labels[b][order].long()
         x1, y1, x2, y2 = q.unbind(-1)
         area = torch.where(torch.isfinite(q).all(-1), (x2 - x1) * (y2 - y1), nan)
-        M = order.numel()
-        removed = torch.zeros(M, dtype=torch.bool)
-        keep = []
-        for i in range(M):
-            if removed[i]:
-                continue
-            keep.append(i)
-            if len(keep) == post or i + 1 == M:
-                break
+
+        def suppressed_by(i):          # row i's pair tests, only once it is kept: never the whole M x M matrix
             iw = (torch.minimum(x2[i], x2[i + 1:]) - torch.maximum(x1[i], x1[i + 1:])).clamp(min=0)
             ih = (torch.minimum(y2[i], y2[i + 1:]) - torch.maximum(y1[i], y1[i + 1:])).clamp(min=0)
             inter = iw * ih
             sup = inter / ((area[i] + area[i + 1:]) - inter) > iou_thr          # (NaN compares false)
-            if class_aware:
-                sup &= lb[i + 1:] == lb[i]
-            removed[i + 1:] |= sup
-        kept = order[torch.tensor(keep, dtype=torch.long)]
+            return sup & (lb[i + 1:] == lb[i]) if class_aware else sup
+
+        kept = _greedy_keep(order, suppressed_by, post)
         m = kept.numel()
         out_b[b, :m], out_s[b, :m], out_l[b, :m] = boxes[b][kept], scores[b][kept], labels[b][kept].to(torch.int32)
         out_i[b, :m], out_c[b] = kept.to(torch.int32), m

@@ -962,7 +962,7 @@ int bevops_bev_nms(int mode, const float *boxes_in, const float *scores_in, cons
 int bevops_bev_iou(const float *boxes_a, int num_a, const float *boxes_b, int num_b, float *iou, void *stream);
 
 /* ------------------------------------------------------------------------
- * 2-D detection decode (csrc/decode2d.hip): the post-processing of the reference's two 2-D detectors
+ * 2-D detection decode (csrc/decode2d.hip; bevops_box_nms in csrc/nms.hip): the post-processing of the reference's two 2-D detectors
  * (det2trt/models/detector/centernet.py, yolox.py: post_process with rescale=True), which it runs as framework ops with
  * data-dependent shapes.  The statement below is the published algorithm of mmdet 2.x (CenterNetHead.get_bboxes /
  * decode_heatmap, YOLOXHead.get_bboxes / _bbox_decode / _bboxes_nms) and of mmcv.ops.batched_nms / nms.  Neither
