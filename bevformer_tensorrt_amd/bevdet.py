@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import functions as _hip_ops
+from .functions import dispatch as _dispatch
 from .functions.multi_scale_deformable_attn import _TensorCache
 
 # BEVDet(..., bev_half=...): "torch" = the framework statements between the image neck and the detections (depth_net
@@ -43,16 +44,10 @@ def default_bev_half():
     return mode
 
 
-@contextlib.contextmanager
 def _rule_dispatch():
-    """The dense / convolution dispatch by RULE for the calling thread (functions.linear.DETERMINISTIC): this package's
+    """The dense / convolution dispatch by RULE for the calling thread (functions.dispatch.DETERMINISTIC): this package's
     kernels whatever the shipped table measured, no measurement at run time, no library fall-back under capture."""
-    from .functions.linear import DETERMINISTIC
-    was, DETERMINISTIC["enabled"] = DETERMINISTIC["enabled"], True
-    try:
-        yield
-    finally:
-        DETERMINISTIC["enabled"] = was
+    return _dispatch.using(rule=True)
 
 
 DEPTH_NET_COLUMNS = 128   # the merged depth_net GEMM's row: [features | depth logits | zero pad]

@@ -39,7 +39,8 @@ import torch.nn.functional as F
 
 from . import functions as _hip_ops
 from . import geometry as G
-from .functions.linear import DETERMINISTIC, OWN_KERNELS, own_kernel_choice, tsgemm_weight_stationary
+from .functions.dispatch import OWN_KERNELS, own_kernel_choice, using as _dispatch_using
+from .functions.linear import tsgemm_weight_stationary
 from .utils import lib as _lib
 
 CONFIGS = {
@@ -1080,14 +1081,10 @@ class BEVFormer(nn.Module):
         the host value is the reference's CPU path bit for bit).  `proj`: optional precomputed `project(lidar2img, ..., cams)`
         (callers that know the calibration to be constant; the frame loop does not: it changes every frame)."""
         mlvl = self.extract_feat(image, cams)
-        if _OWN_ENCODER["enabled"] and image.is_cuda and image.dtype == torch.float16:
-            # everything behind the backbone on the hand-written GEMMs (fixed summation order): see _OWN_ENCODER
-            was, OWN_KERNELS["enabled"] = OWN_KERNELS["enabled"], True
-            try:
-                return self._transformer(mlvl, image, prev_bev, use_prev_bev, can_bus, lidar2img, cams, gather, shift, proj)
-            finally:
-                OWN_KERNELS["enabled"] = was
-        return self._transformer(mlvl, image, prev_bev, use_prev_bev, can_bus, lidar2img, cams, gather, shift, proj)
+        # everything behind the backbone on the hand-written GEMMs (fixed summation order): see _OWN_ENCODER
+        own = _OWN_ENCODER["enabled"] and image.is_cuda and image.dtype == torch.float16
+        with _dispatch_using(own=True if own else None):
+            return self._transformer(mlvl, image, prev_bev, use_prev_bev, can_bus, lidar2img, cams, gather, shift, proj)
 
     def _transformer(self, mlvl, image, prev_bev, use_prev_bev, can_bus, lidar2img, cams, gather, shift, proj):
         """Everything behind the backbone + FPN: embeddings, encoder, decoder, heads."""
@@ -1403,11 +1400,8 @@ class FrameRunner:
             # the table has not seen, by a rule of the shape alone; the backbone is per-camera work no other rank
             # repeats and keeps the measured dispatch.  Without _OWN_ENCODER (or BEVOPS_SHARDED_RULE_DISPATCH=1, the
             # behaviour of rounds 3-5, 6-9 % slower) the rule-based dispatch is on for the whole forward.
-            prev, DETERMINISTIC["enabled"] = DETERMINISTIC["enabled"], True
-            try:
+            with _dispatch_using(rule=True):
                 return self._forward_impl()
-            finally:
-                DETERMINISTIC["enabled"] = prev
         return self._forward_impl()
 
     def _forward_impl(self):

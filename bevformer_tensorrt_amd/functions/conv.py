@@ -11,13 +11,14 @@ import torch
 import torch.nn.functional as F
 
 from ..utils import lib as _lib
+from . import dispatch as _dispatch
+from . import linear as _linear
+from .dispatch import CONV_LOG, CONV_MISSES, _CHOICE, _problem, _table  # noqa: F401
+from .linear import _call, _ptr
 from .modulated_deformable_conv2d import bias_act_nhwc_
 from .multi_scale_deformable_attn import _TensorCache
 
 _PACKED = _TensorCache()   # weight tensor -> taps-major copy (weakly keyed: dies with the model that owns the weight)
-_CHOICE = {}          # problem -> "tile" | "library"
-CONV_LOG = []         # (problem, {name: us})
-CONV_MISSES = []   # problems conv3x3_auto met that dispatch_gfx950.json does not list
 HALO = {"enabled": os.environ.get("BEVOPS_CONV_HALO", "1") == "1"}   # A/B: the LDS-resident 64-channel convolution
 
 
@@ -29,33 +30,38 @@ def pack_taps(weight):
     return hit
 
 
-def conv_nhwc(x, weight, bias=None, relu=False, residual=None, stride=1):
-    """x [B, Cin, H, W] channels-last fp16, weight [Cout, Cin, k, k] with k in {1, 3} -> act(conv2d(x, weight,
-    stride, pad k // 2) + bias + residual) [B, Cout, Hout, Wout] channels-last.  Cin % 32 == 0."""
-    assert x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and weight.shape[2] == weight.shape[3]
+def _conv_call(entry, x, Cout, k, stride, bias, residual, args, bias_dtype=torch.float16):
+    """What the convolution entries share: the channels-last fp16 input checked, the output [B, Cout, Hout, Wout] (pad
+    k // 2) allocated channels-last, the identity rows checked against it, the bias cast, no library for B == 0, the
+    status checked.  `args(out, bias)`: the entry's arguments before the stream."""
+    assert x.is_cuda and x.dtype == torch.float16 and x.dim() == 4
     assert x.is_contiguous(memory_format=torch.channels_last)
-    B, Cin, H, W = x.shape
-    Cout, k = weight.shape[0], weight.shape[2]
-    if weight.shape[1] != Cin:
-        raise ValueError("weight does not match the input channels")
-    wt = pack_taps(weight)
+    B, _, H, W = x.shape
     Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
     out = torch.empty((B, Cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     if residual is not None:
         assert residual.shape == out.shape and residual.dtype == x.dtype
         assert residual.is_contiguous(memory_format=torch.channels_last)
     if bias is not None:
-        bias = bias.to(torch.float16).contiguous()
+        bias = bias.to(bias_dtype).contiguous()
     if B == 0:
         return out
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_conv_tile_f16(x.data_ptr(), wt.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                         residual.data_ptr() if residual is not None else None, out.data_ptr(),
-                                         B, H, W, Cin, Cout, k, int(stride), int(bool(relu)),
-                                         _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_conv_tile_f16")
+    _call(entry, x.device, *args(out, bias))
     return out
+
+
+def conv_nhwc(x, weight, bias=None, relu=False, residual=None, stride=1):
+    """x [B, Cin, H, W] channels-last fp16, weight [Cout, Cin, k, k] with k in {1, 3} -> act(conv2d(x, weight,
+    stride, pad k // 2) + bias + residual) [B, Cout, Hout, Wout] channels-last.  Cin % 32 == 0."""
+    assert x.dim() == 4 and weight.shape[2] == weight.shape[3]
+    B, Cin, H, W = x.shape
+    Cout, k = weight.shape[0], weight.shape[2]
+    if weight.shape[1] != Cin:
+        raise ValueError("weight does not match the input channels")
+    wt = pack_taps(weight)
+    return _conv_call("bevops_conv_tile_f16", x, Cout, k, stride, bias, residual, lambda out, b: (
+        x.data_ptr(), wt.data_ptr(), _ptr(b), _ptr(residual), out.data_ptr(), B, H, W, Cin, Cout, k, int(stride),
+        int(bool(relu))))
 
 
 def conv3x3_c64(x, weight, bias=None, relu=False, residual=None, stride=1):
@@ -63,55 +69,28 @@ def conv3x3_c64(x, weight, bias=None, relu=False, residual=None, stride=1):
     (bevops_conv3x3_c64_f16, csrc/conv_halo.hip): x [B, 64, H, W] channels-last fp16, weight [64, 64, 3, 3] ->
     act(conv2d(x, weight, 1, 1) + bias), bit-identical to conv_nhwc.  Raises BevopsError(NOT_SUPPORTED) for any other
     layer (channel counts, a stride, identity rows)."""
-    assert x.is_cuda and x.dtype == torch.float16 and x.dim() == 4
-    assert x.is_contiguous(memory_format=torch.channels_last)
     B, Cin, H, W = x.shape
     Cout = weight.shape[0]
     if residual is not None or stride != 1 or tuple(weight.shape[1:]) != (Cin, 3, 3):
         raise _lib.BevopsError("bevops_conv3x3_c64_f16: 3x3 / stride 1 layers without identity rows only", _lib.NOT_SUPPORTED)
     wt = pack_taps(weight)
-    out = torch.empty((B, Cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    if bias is not None:
-        bias = bias.to(torch.float16).contiguous()
-    if B == 0:
-        return out
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_conv3x3_c64_f16(x.data_ptr(), wt.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                           out.data_ptr(), B, H, W, Cin, Cout, int(bool(relu)),
-                                           _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_conv3x3_c64_f16")
-    return out
+    return _conv_call("bevops_conv3x3_c64_f16", x, Cout, 3, 1, bias, None, lambda out, b: (
+        x.data_ptr(), wt.data_ptr(), _ptr(b), out.data_ptr(), B, H, W, Cin, Cout, int(bool(relu))))
 
 
 def conv_int8_nhwc(x, scale_a, w_q_taps, scale_w, bias=None, relu=False, residual=None, stride=1):
     """The INT8 flavour (bevops_conv_tile_int8_fused): x [B, Cin, H, W] channels-last fp16, quantised with scale_a
     inside the kernel; w_q_taps [Cout, k, k, Cin] int8 (taps-major), scale_w a float or an fp32 [Cout] tensor; bias
     fp32; residual fp16 channels-last -> fp16 [B, Cout, Hout, Wout] channels-last.  Cin % 64 == 0."""
-    assert x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and w_q_taps.dtype == torch.int8
-    assert x.is_contiguous(memory_format=torch.channels_last) and w_q_taps.is_contiguous()
+    assert x.dim() == 4 and w_q_taps.dtype == torch.int8 and w_q_taps.is_contiguous()
     B, Cin, H, W = x.shape
     Cout, k = w_q_taps.shape[0], w_q_taps.shape[1]
     assert w_q_taps.shape == (Cout, k, k, Cin)
-    Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
-    out = torch.empty((B, Cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    if residual is not None:
-        assert residual.shape == out.shape and residual.dtype == x.dtype
-        assert residual.is_contiguous(memory_format=torch.channels_last)
     per_channel = torch.is_tensor(scale_w)
     ws = scale_w.float().contiguous() if per_channel else None
-    b = bias.float().contiguous() if bias is not None else None
-    if B == 0:
-        return out
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_conv_tile_int8_fused(
-            x.data_ptr(), float(scale_a), w_q_taps.data_ptr(), ws.data_ptr() if per_channel else None,
-            1.0 if per_channel else float(scale_w), b.data_ptr() if b is not None else None,
-            residual.data_ptr() if residual is not None else None, out.data_ptr(), B, H, W, Cin, Cout, k, int(stride),
-            int(bool(relu)), _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_conv_tile_int8_fused")
-    return out
+    return _conv_call("bevops_conv_tile_int8_fused", x, Cout, k, stride, bias, residual, lambda out, b: (
+        x.data_ptr(), float(scale_a), w_q_taps.data_ptr(), _ptr(ws), 1.0 if per_channel else float(scale_w), _ptr(b),
+        _ptr(residual), out.data_ptr(), B, H, W, Cin, Cout, k, int(stride), int(bool(relu))), torch.float32)
 
 
 def conv3x3_nhwc(x, weight, bias=None, relu=False, residual=None, stride=1):
@@ -126,47 +105,31 @@ def _library(x, weight, bias, relu, residual, stride=1):
     return bias_act_nhwc_(y, bias, residual, relu)
 
 
+_CONV = {"tile": conv_nhwc, "halo": conv3x3_c64, "library": _library}
+
+
 def conv3x3_auto(x, weight, bias=None, relu=False, residual=None, stride=1):
-    """conv_nhwc or the library convolution + one epilogue pass, whichever measured faster for the problem."""
+    """conv_nhwc, conv3x3_c64 or the library convolution + one epilogue pass: the shipped table's choice, or whichever
+    measured faster for a problem it does not list (functions/dispatch.py: conv_choice)."""
     B, Cin, H, W = x.shape
     if B == 0 and Cin % 32 == 0:
-        return conv_nhwc(x, weight, bias, relu, residual, stride)      # (empty result, nothing to measure)
+        return _CONV["tile"](x, weight, bias, relu, residual, stride)      # (empty result, nothing to measure)
     key = (str(x.device), B, H, W, Cin, weight.shape[0], weight.shape[2], stride, bool(relu), residual is not None)
-    from .linear import DETERMINISTIC, _problem, _table
-    # 64 -> 64 channels, stride 1, no identity rows (conv2 of the ResNet stage-1 bottlenecks): the LDS-resident kernel
-    # (csrc/conv_halo.hip) -- bit-identical to the tiled implicit GEMM, so also the rule-based dispatch may take it
-    halo_ok = HALO["enabled"] and Cin == 64 and weight.shape[0] == 64 and stride == 1 and residual is None \
-        and weight.shape[2] == 3
-    name = ("halo" if halo_ok else "tile") if (DETERMINISTIC["enabled"] and Cin % 32 == 0) else _CHOICE.get(key)
-    if name is None:      # shipped choice (dispatch_gfx950.json): no measurement, the same kernel on every box
-        name = _table()["conv"].get(_problem(key))
-        if name == "tile" and halo_ok:
-            # (the table was measured before this kernel existed: 47 against 88 us at the base shape, faster at every
-            # shape of the four models, profiles/r06/conv_halo_time.jsonl)
-            name = "halo"
-        if name in ("tile", "library", "halo") and (name == "library" or Cin % 32 == 0) and (name != "halo" or halo_ok):
-            _CHOICE[key] = name
-        else:
-            name = None
-            if _problem(key) not in CONV_MISSES:
-                CONV_MISSES.append(_problem(key))   # a problem the shipped table has never seen (bench.py reports them)
-    if name is None:
-        if Cin % 32 != 0:
-            name = _CHOICE[key] = "library"
-        elif torch.cuda.is_current_stream_capturing() or os.environ.get("BEVOPS_DENSE_TUNE", "1") == "0":
-            name = "library"
-        else:
-            from .linear import graph_time_us
-            times = {}
-            for cand, fn in (("tile", conv_nhwc), ("library", _library)) + ((("halo", conv3x3_c64),) if halo_ok else ()):
-                for _ in range(2):
-                    fn(x, weight, bias, relu, residual, stride)
-                torch.cuda.synchronize()
-                # (under HIP-graph replay: an eager loop would time the host for the small late-stage convolutions)
-                times[cand] = round(graph_time_us(lambda: fn(x, weight, bias, relu, residual, stride), 4, 3), 1)
-            CONV_LOG.append((key, times))
-            name = _CHOICE[key] = min(times, key=times.get)
-    return {"tile": conv_nhwc, "halo": conv3x3_c64, "library": _library}[name](x, weight, bias, relu, residual, stride)
+    # (the table under linear's name for it: tests empty the table by rebinding that name)
+    name, keep, miss = _dispatch.conv_choice(key, _linear.DETERMINISTIC["enabled"], torch.cuda.is_current_stream_capturing,
+                                             _dispatch._tune, _table(_linear._TABLE), HALO["enabled"], _CHOICE.get(key))
+    if miss and _problem(key) not in CONV_MISSES:
+        CONV_MISSES.append(_problem(key))   # a problem the shipped table has never seen (bench.py reports them)
+    if name == "measure":
+        # (under HIP-graph replay: an eager loop would time the host for the small late-stage convolutions)
+        times = _dispatch.measure(_dispatch._CONV_NAMES[:3 if _dispatch.halo_ok(key, HALO["enabled"]) else 2],
+                                  lambda cand: _CONV[cand](x, weight, bias, relu, residual, stride), 4, 3)
+        times = {k: round(v, 1) for k, v in times.items()}
+        CONV_LOG.append((key, times))
+        name = min(times, key=times.get)
+    if keep:
+        _CHOICE[key] = name
+    return _CONV[name](x, weight, bias, relu, residual, stride)
 
 
 _STEM_PACKED = _TensorCache()   # stem weight -> (bias stamp, packed matrix-core operand image)

@@ -3,15 +3,16 @@ epilogue in the GEMM: out = act(x @ weight.T + bias + residual) as one `bevops_l
 call (hipBLASLt MFMA kernel, shift + identity + ReLU in its epilogue).  Not a reference plugin:
 the reference leaves these layers to cuBLAS / TensorRT."""
 import ctypes
+import os
 
 import torch
 
 from ..utils import lib as _lib
 from ..utils import workspace as _ws
-
-def _workspace(device, nbytes, stream):
-    """hipBLASLt workspace per (device, stream): two streams never share one (utils/workspace.py)."""
-    return _ws.lend("linear", nbytes, device, stream)
+from . import dispatch as _dispatch
+from .dispatch import (DENSE_LOG, DENSE_MISSES, DETERMINISTIC, OWN_KERNELS, _DENSE_CHOICE, _TABLE,  # noqa: F401
+                       _dense_default, _dense_deterministic, _dense_own, _problem, _small_pays, _table, graph_time_us,
+                       own_kernel_choice)
 
 
 _TUNED = set()   # problems whose algorithm has been chosen by bevops_linear_tune in this process
@@ -21,7 +22,6 @@ def _tune_once(handle, key, args, x2, out_shape):
     """The library never synchronises inside the operator; algorithm selection by measurement is
     its own BLOCKING entry (bevops_linear_tune), called here once per problem, outside stream
     capture, with a scratch output (BEVOPS_LINEAR_TUNE=0 switches it off)."""
-    import os
     _TUNED.add(key)
     if os.environ.get("BEVOPS_LINEAR_TUNE", "1") == "0":
         return
@@ -70,29 +70,48 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def _call(entry, device, *args):
+    """One call of the library's `entry` on `device` and its current stream (the entry's last argument), status checked."""
+    handle = _lib.load_library()
+    with torch.cuda.device(device):
+        st = getattr(handle, entry)(*args, _lib.current_stream_ptr(device))
+    _lib.check(st, entry)
+
+
+def _gemm_f16(entry, x, weight, bias, residual, relu, out, max_rows=None, launch=None):
+    """One call of an fp16 GEMM entry with the shared signature (x, weight, bias, residual, out, M, N, K, relu, stream):
+    operands through _operands, no library for M == 0, the status checked, the leading dimensions of x back on the
+    result.  `launch(handle, args, stream)`: a caller that passes more than the shared arguments makes the call itself."""
+    assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
+    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, out)
+    if max_rows is not None and M > max_rows:
+        raise _lib.BevopsError(f"{entry}: more than {max_rows} rows (the tiled GEMMs' domain)", _lib.NOT_SUPPORTED)
+    if M == 0:
+        return _like_rows(out, x, N)
+    handle = _lib.load_library()
+    stream = _lib.current_stream_ptr(x.device)
+    args = (x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), out.data_ptr(), M, N, K, int(bool(relu)))
+    with torch.cuda.device(x.device):
+        st = getattr(handle, entry)(*args, stream) if launch is None else launch(handle, args, stream)
+    _lib.check(st, entry)
+    return _like_rows(out, x, N)
+
+
 def linear_bias_act(x, weight, bias=None, residual=None, relu=False, out=None):
     """x [..., K] fp16 (contiguous rows), weight [N, K], bias [N] or None, residual [..., N] or None
     -> [..., N].  `out` may be given (and may be `residual` itself).  Raises BevopsError with status
     NOT_SUPPORTED when hipBLASLt has no algorithm for the shape (callers fall back to
     mm + bias_act_nhwc_)."""
-    assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, out)
-    if M == 0:
-        return _like_rows(out, x, N)
-    handle = _lib.load_library()
-    import os
-    nbytes = handle.bevops_linear_workspace_size() if os.environ.get("BEVOPS_LINEAR_WS", "1") != "0" else 0
-    stream = _lib.current_stream_ptr(x.device)
-    ws = _workspace(x.device, nbytes, stream) if nbytes else None
-    args = (_lib.F16, x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), out.data_ptr(), M, N, K, int(bool(relu)),
-            _ptr(ws), nbytes, stream)
-    with torch.cuda.device(x.device):
-        key = (str(x.device), M, N, K, bool(relu), bias is not None, r2 is not None)
+    def launch(handle, args, stream):
+        nbytes = handle.bevops_linear_workspace_size() if os.environ.get("BEVOPS_LINEAR_WS", "1") != "0" else 0
+        # (the hipBLASLt workspace per (device, stream): two streams never share one, utils/workspace.py)
+        ws = _ws.lend("linear", nbytes, x.device, stream) if nbytes else None
+        full = (_lib.F16,) + args + (_ptr(ws), nbytes, stream)
+        key = (str(x.device),) + args[5:8] + (bool(relu), args[2] is not None, args[3] is not None)
         if key not in _TUNED and not torch.cuda.is_current_stream_capturing():
-            _tune_once(handle, key, args, x2, (M, N))
-        st = handle.bevops_linear_bias_act(*args)
-    _lib.check(st, "bevops_linear_bias_act")
-    return _like_rows(out, x, N)
+            _tune_once(handle, key, full, x, args[5:7])
+        return handle.bevops_linear_bias_act(*full)
+    return _gemm_f16("bevops_linear_bias_act", x, weight, bias, residual, relu, out, launch=launch)
 
 
 def layer_norm(x, weight=None, bias=None, eps=1e-5, out=None):
@@ -111,48 +130,32 @@ def layer_norm(x, weight=None, bias=None, eps=1e-5, out=None):
     b = bias.to(torch.float16).contiguous() if bias is not None else None
     if x2.shape[0] == 0:
         return out.view(x.shape)
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_layer_norm(_lib.F16, x2.data_ptr(), w.data_ptr() if w is not None else None,
-                                      b.data_ptr() if b is not None else None, out.data_ptr(), x2.shape[0], C,
-                                      float(eps), _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_layer_norm")
+    _call("bevops_layer_norm", x.device, _lib.F16, x2.data_ptr(), _ptr(w), _ptr(b), out.data_ptr(), x2.shape[0], C, float(eps))
     return out.view(x.shape)
+
+
+def _scaled_rows(entry, x, scale, out_dtype, out=None):
+    x = x.contiguous()
+    if x.numel() % 8:
+        raise ValueError("element count must be a multiple of 8")
+    if out is None:
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    if x.numel() == 0:
+        return out
+    _call(entry, x.device, _lib.F16, x.data_ptr(), out.data_ptr(), x.numel(), float(scale))
+    return out
 
 
 def quantize_rows(x, scale, out=None):
     """fp16 tensor -> int8 with one per-tensor scale: clamp(rne(x / scale), -127, 127) (bevops_quantize_rows)."""
     assert x.is_cuda and x.dtype == torch.float16
-    x = x.contiguous()
-    if x.numel() % 8:
-        raise ValueError("element count must be a multiple of 8")
-    if out is None:
-        out = torch.empty(x.shape, dtype=torch.int8, device=x.device)
-    if x.numel() == 0:
-        return out
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_quantize_rows(_lib.F16, x.data_ptr(), out.data_ptr(), x.numel(), float(scale),
-                                         _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_quantize_rows")
-    return out
+    return _scaled_rows("bevops_quantize_rows", x, scale, torch.int8, out)
 
 
 def dequantize_rows(q, scale):
     """int8 tensor -> fp16, q * scale with the product in fp32 and one rounding (bevops_dequantize_rows)."""
     assert q.is_cuda and q.dtype == torch.int8
-    q = q.contiguous()
-    if q.numel() % 8:
-        raise ValueError("element count must be a multiple of 8")
-    out = torch.empty(q.shape, dtype=torch.float16, device=q.device)
-    if q.numel() == 0:
-        return out
-    handle = _lib.load_library()
-    with torch.cuda.device(q.device):
-        st = handle.bevops_dequantize_rows(_lib.F16, q.data_ptr(), out.data_ptr(), q.numel(), float(scale),
-                                           _lib.current_stream_ptr(q.device))
-    _lib.check(st, "bevops_dequantize_rows")
-    return out
+    return _scaled_rows("bevops_dequantize_rows", q, scale, torch.float16)
 
 
 def linear_int8(a_q, scale_a, w_q, scale_w, bias=None, residual=None, relu=False, out_dtype=torch.float16,
@@ -169,13 +172,9 @@ def linear_int8(a_q, scale_a, w_q, scale_w, bias=None, residual=None, relu=False
     ws = scale_w.float().contiguous() if per_channel else None
     if M == 0:
         return _like_rows(out, a_q, N)
-    handle = _lib.load_library()
-    with torch.cuda.device(a_q.device):
-        st = (handle.bevops_linear_int8_fused if fused else handle.bevops_linear_int8)(
-            a2.data_ptr(), float(scale_a), w_q.data_ptr(), _ptr(ws), 1.0 if per_channel else float(scale_w), _ptr(b),
-            _ptr(r), _lib.torch_dtype_code(out), out.data_ptr(), float(scale_out), M, N, K, int(bool(relu)),
-            _lib.current_stream_ptr(a_q.device))
-    _lib.check(st, "bevops_linear_int8_fused" if fused else "bevops_linear_int8")
+    _call("bevops_linear_int8_fused" if fused else "bevops_linear_int8", a_q.device,
+          a2.data_ptr(), float(scale_a), w_q.data_ptr(), _ptr(ws), 1.0 if per_channel else float(scale_w), _ptr(b),
+          _ptr(r), _lib.torch_dtype_code(out), out.data_ptr(), float(scale_out), M, N, K, int(bool(relu)))
     return _like_rows(out, a_q, N)
 
 
@@ -183,16 +182,7 @@ def tsgemm(x, weight, bias=None, residual=None, relu=False, out=None):
     """act(x @ weight.T + bias + residual) on the hand-written tall-skinny MFMA GEMM (bevops_tsgemm_f16):
     x [..., K] fp16 contiguous rows, weight [N, K], residual / out [..., N].  Raises BevopsError with status
     NOT_SUPPORTED outside its domain (K % 64, N % 256)."""
-    assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, out)
-    if M == 0:
-        return _like_rows(out, x, N)
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_tsgemm_f16(x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), out.data_ptr(), M, N, K,
-                                int(bool(relu)), _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_tsgemm_f16")
-    return _like_rows(out, x, N)
+    return _gemm_f16("bevops_tsgemm_f16", x, weight, bias, residual, relu, out)
 
 
 def tsgemm_grouped(x, weight, bias=None, out=None):
@@ -211,11 +201,7 @@ def tsgemm_grouped(x, weight, bias=None, out=None):
         assert out.is_contiguous() and tuple(out.shape) == (G, M, 256) and out.dtype == x.dtype
     if M == 0:
         return out
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_tsgemm_f16_grouped(x2.data_ptr(), weight.data_ptr(), _ptr(bias), out.data_ptr(), M * 256, M, G, K,
-                                              _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_tsgemm_f16_grouped")
+    _call("bevops_tsgemm_f16_grouped", x.device, x2.data_ptr(), weight.data_ptr(), _ptr(bias), out.data_ptr(), M * 256, M, G, K)
     return out
 
 
@@ -225,33 +211,16 @@ def tsgemm_ln(x, weight, bias, residual, ln_weight, ln_bias, eps=1e-5):
     (modules/encoder.py:586-636).  x [..., K] fp16, weight [256, K], residual [..., 256] or None.  Equal to
     layer_norm(tsgemm(...)) up to the last bit of the normalisation (same binary16 sums, fp32 statistics).  Raises
     BevopsError (NOT_SUPPORTED) unless N == 256 and K % 64 == 0."""
-    assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, None)
     g, b = ln_weight.to(torch.float16).contiguous(), ln_bias.to(torch.float16).contiguous()
-    if M == 0:
-        return _like_rows(out, x, N)
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_tsgemm_f16_ln(x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), g.data_ptr(), b.data_ptr(),
-                                         float(eps), out.data_ptr(), M, N, K, _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_tsgemm_f16_ln")
-    return _like_rows(out, x, N)
+    return _gemm_f16("bevops_tsgemm_f16_ln", x, weight, bias, residual, False, None, launch=lambda handle, a, stream:
+                     handle.bevops_tsgemm_f16_ln(*a[:4], g.data_ptr(), b.data_ptr(), float(eps), *a[4:8], stream))
 
 
 def tile_gemm(x, weight, bias=None, residual=None, relu=False, out=None):
     """act(x @ weight.T + bias + residual) on the tiled MFMA GEMM (bevops_tile_gemm_f16, csrc/tile_gemm.hip:
     128 x 128 tiles, three blocks per CU): x [..., K] fp16 contiguous rows, weight [N, K], bias [N] fp16,
     residual / out [..., N].  K % 8 == 0."""
-    assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, out)
-    if M == 0:
-        return _like_rows(out, x, N)
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_tile_gemm_f16(x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), out.data_ptr(), M, N, K,
-                                   int(bool(relu)), _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_tile_gemm_f16")
-    return _like_rows(out, x, N)
+    return _gemm_f16("bevops_tile_gemm_f16", x, weight, bias, residual, relu, out)
 
 
 class _GemmDst(ctypes.Structure):     # bevops_gemm_dst (include/bevops.h)
@@ -285,11 +254,8 @@ def tile_gemm_dst(x, weight, bias, widths, residuals=None, relu=False, outs=None
                 raise ValueError("residual must be fp16 [M, width] with unit column stride")
             tab[i].res, tab[i].res_pitch = r.data_ptr(), r.stride(0) if M > 1 else n
         col += n
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = getattr(handle, _entry)(x2.data_ptr(), weight.data_ptr(), _ptr(bias), ctypes.addressof(tab), len(widths), M, N, K,
-                                     int(bool(relu)), _lib.current_stream_ptr(x.device))
-    _lib.check(st, _entry)
+    _call(_entry, x.device, x2.data_ptr(), weight.data_ptr(), _ptr(bias), ctypes.addressof(tab), len(widths), M, N, K,
+          int(bool(relu)))
     return outs
 
 
@@ -312,18 +278,7 @@ def small_gemm(x, weight, bias=None, residual=None, relu=False, out=None):
     no-pipeline MFMA GEMM (bevops_small_gemm_f16, csrc/small_gemm.hip: 32 x 64 tiles, split-K inside the block, every
     operand fragment requested before the first matrix instruction -- one memory round trip per launch instead of a
     chain of dependent k-steps).  x [..., K] fp16, weight [N, K]; K % 64 == 0, K <= 1024; offered up to 8192 rows."""
-    assert x.is_cuda and x.dtype == torch.float16 and weight.dtype == torch.float16
-    x2, weight, bias, r2, out, M, N, K = _operands(x, weight, bias, residual, out)
-    if M > 8192:
-        raise _lib.BevopsError("small_gemm: more than 8192 rows (the tiled GEMMs' domain)", _lib.NOT_SUPPORTED)
-    if M == 0:
-        return _like_rows(out, x, N)
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_small_gemm_f16(x2.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(r2), out.data_ptr(), M, N, K,
-                                    int(bool(relu)), _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_small_gemm_f16")
-    return _like_rows(out, x, N)
+    return _gemm_f16("bevops_small_gemm_f16", x, weight, bias, residual, relu, out, max_rows=8192)
 
 
 # ---- measured choice between the dense-layer implementations -------------------------------------------------
@@ -336,97 +291,6 @@ def _torch_dense(x, weight, bias, residual, relu):
 
 
 _DENSE = {"tsgemm": tsgemm, "tile": tile_gemm, "small": small_gemm, "blaslt": linear_bias_act, "torch": _torch_dense}
-_DENSE_CHOICE = {}     # problem -> name of the fastest implementation measured in this process
-DENSE_LOG = []         # (problem, {name: us}) of every measurement, for tools / profiles
-DENSE_MISSES = []      # problems dense_auto met that dispatch_gfx950.json does not list (measured or defaulted instead)
-# Reproducible mode: no per-process timing, the choice is a function of the problem alone and falls on the two
-# hand-written kernels (fixed summation order, no library heuristic).  The camera-sharded frame loop switches it on:
-# ranks that each measured their own winner would evaluate the REPLICATED layers (TSA, FFN, decoder) in different
-# summation orders and drift apart bitwise.  BEVOPS_DENSE_TUNE=0 is the same switch from the environment.
-class _PerThreadFlag:
-    """`flag["enabled"]` with one value per THREAD (two frame runners on two threads -- a sharded and a plain one --
-    must not see each other's setting; advisor, round 4).  Dict-style access, default False."""
-
-    def __init__(self):
-        import threading
-        self._tls = threading.local()
-
-    def __getitem__(self, key):
-        assert key == "enabled"
-        return getattr(self._tls, "enabled", False)
-
-    def __setitem__(self, key, value):
-        assert key == "enabled"
-        self._tls.enabled = bool(value)
-
-
-DETERMINISTIC = _PerThreadFlag()
-# The hand-written kernels only, the FASTEST of them per problem by the shipped table's own measurements (the rule of
-# DETERMINISTIC for a problem the table has not seen): what the model runs behind its backbone (bevformer.py:
-# _OWN_ENCODER) -- one kernel per layer, summation order a function of the block index, same choice in every process.
-OWN_KERNELS = _PerThreadFlag()
-
-
-# Shipped choices (bevformer_tensorrt_amd/dispatch_gfx950.json, written by tools/dump_dispatch.py from one MI355X's
-# measurements): a problem found there takes its recorded winner WITHOUT a measurement, so the kernel that runs is the
-# same on every box and in every process; only problems the table has never seen are timed (BEVOPS_DENSE_TUNE=1: time
-# everything, i.e. regenerate; =0: no table, no timing -- the reproducible defaults).
-_TABLE = {"loaded": False, "dense": {}, "conv": {}, "measured_dense": {}}
-
-
-def _table():
-    import json
-    import os
-    if not _TABLE["loaded"]:
-        _TABLE["loaded"] = True
-        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dispatch_gfx950.json")
-        if os.path.exists(path) and os.environ.get("BEVOPS_DENSE_TUNE", "") not in ("0", "1"):
-            try:
-                t = json.load(open(path))
-                _TABLE["dense"], _TABLE["conv"] = t.get("dense", {}), t.get("conv", {})
-                _TABLE["measured_dense"] = t.get("measured_us", {}).get("dense", {})
-            except (OSError, ValueError):
-                pass
-    return _TABLE
-
-
-def _problem(key):
-    return ",".join(str(int(v)) if isinstance(v, bool) else str(v) for v in key[1:])   # without the device name
-
-
-def _small_pays(M, N, K):
-    """The no-pipeline few-row GEMM is for problems of a few tiles (the decoder's 900 object queries); the shipped
-    table's own measurements show it 2-3 x slower than the tiled kernels once M x N grows (2 250 x 2 048 x 512: 33.8
-    against 18.0 us)."""
-    return K % 64 == 0 and K <= 1024 and M * N <= 1024 * 512
-
-
-def _dense_deterministic(N, K, M=1 << 30):
-    if _small_pays(M, N, K):
-        return "small"
-    return "tsgemm" if (N % 256 == 0 and K % 64 == 0 and K >= 256) else "tile"
-
-
-def _dense_own(key, N, K, M):
-    times = _table().get("measured_dense", {}).get(_problem(key), {})
-    own = {k: v for k, v in times.items() if k in ("tile", "tsgemm", "small") and k in _DENSE}
-    return min(own, key=own.get) if own else _dense_deterministic(N, K, M)
-
-
-def own_kernel_choice(device, M, N, K, relu, has_bias, has_res):
-    """The implementation dense_auto runs for this problem under OWN_KERNELS (a function of the problem and the shipped
-    table alone).  The model's merged launches ask it: they replace a per-layer GEMM only where that GEMM runs on
-    tile_gemm or tsgemm -- tile_gemm and the weight-stationary tsgemm (tsgemm_weight_stationary) share matrix
-    instruction, k order and epilogue arithmetic and give the same bits (tests/test_gemm_grouped_gpu.py); the original
-    tsgemm kernel rotates its k start by block index, small_gemm splits K inside the block: neither does."""
-    return _dense_own((str(device), M, N, K, bool(relu), bool(has_bias), bool(has_res)), N, K, M)
-
-
-def _dense_default(N, K, has_res):
-    """Choice without a measurement (inside stream capture before the problem was seen, or BEVOPS_DENSE_TUNE=0)."""
-    if N == 256 and K % 64 == 0 and K >= 256:
-        return "tsgemm"
-    return "blaslt"
 
 
 def dense_auto(x, weight, bias=None, residual=None, relu=False):
@@ -435,32 +299,22 @@ def dense_auto(x, weight, bias=None, residual=None, relu=False):
     entry with the fused epilogue (linear_bias_act) or the framework's addmm.  Measured once per
     (M, N, K, epilogue) outside stream capture -- BLOCKING, like bevops_linear_tune: a few launches of each
     candidate into scratch outputs between device synchronisations -- then cached for the process.  All
-    candidates accumulate in fp32 and round once; they differ in summation order only."""
-    import os
+    candidates accumulate in fp32 and round once; they differ in summation order only.  Who decides what:
+    functions/dispatch.py (dense_choice)."""
     K, N = x.shape[-1], weight.shape[0]
     M = x.numel() // K
     if M == 0:          # a rank of the camera-sharded path that owns no camera
         return x.new_empty((*x.shape[:-1], N))
     key = (str(x.device), M, N, K, bool(relu), bias is not None, residual is not None)
-    if DETERMINISTIC["enabled"] and K % 8 == 0:
-        name = _dense_deterministic(N, K, M)
-    elif OWN_KERNELS["enabled"] and K % 8 == 0:
-        name = _dense_own(key, N, K, M)
-    else:
-        name = _DENSE_CHOICE.get(key)
-    if name is None:
-        name = _table()["dense"].get(_problem(key))
-        if name is not None and name in _DENSE:
-            _DENSE_CHOICE[key] = name
-        else:
-            name = None
-            if _problem(key) not in DENSE_MISSES:
-                DENSE_MISSES.append(_problem(key))     # a problem the shipped table has never seen (bench.py reports them)
-    if name is None:
-        if torch.cuda.is_current_stream_capturing() or os.environ.get("BEVOPS_DENSE_TUNE", "1") == "0" or M < 64:
-            name = "small" if _small_pays(M, N, K) else _dense_default(N, K, residual is not None)
-        else:
-            name = _DENSE_CHOICE[key] = _dense_measure(key, x, weight, bias, residual, relu)
+    name, keep, miss = _dispatch.dense_choice(key, DETERMINISTIC["enabled"], OWN_KERNELS["enabled"],
+                                              torch.cuda.is_current_stream_capturing, _dispatch._tune, _table(_TABLE),
+                                              _DENSE_CHOICE.get(key))
+    if miss and _problem(key) not in DENSE_MISSES:
+        DENSE_MISSES.append(_problem(key))     # a problem the shipped table has never seen (bench.py reports them)
+    if name == "measure":
+        name = _dense_measure(key, x, weight, bias, residual, relu)
+    if keep:
+        _DENSE_CHOICE[key] = name
     try:
         return _DENSE[name](x, weight, bias, residual, relu)
     except _lib.BevopsError as exc:
@@ -469,51 +323,11 @@ def dense_auto(x, weight, bias=None, residual=None, relu=False):
         return linear_bias_act(x, weight, bias, residual, relu)
 
 
-def graph_time_us(fn, iters=8, rounds=3):
-    """Microseconds per call of `fn` on the device, measured under HIP-graph replay: `iters` calls are captured once
-    and the replay is timed between two events (best of `rounds`).  Launching the same calls eagerly measures the HOST
-    for anything shorter than the ~12 us a Python operator wrapper takes per call -- the decoder's few-row layers all
-    looked alike (12-13 us) that way, whatever the kernel did."""
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        fn()
-    torch.cuda.current_stream().wait_stream(s)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(iters):
-            fn()
-    g.replay()
-    best = float("inf")
-    for _ in range(rounds):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        g.replay()
-        b.record()
-        b.synchronize()
-        best = min(best, a.elapsed_time(b) * 1e3 / iters)
-    return best
-
-
 def _dense_measure(key, x, weight, bias, residual, relu, rounds=3, iters=8):
-    times = {}
     with torch.cuda.device(x.device):
-        for name, fn in _DENSE.items():
-            try:
-                for _ in range(2):
-                    fn(x, weight, bias, residual, relu)
-                times[name] = float("inf")
-            except _lib.BevopsError as exc:   # outside the candidate's domain / no library algorithm -- and only that:
-                if exc.status != _lib.NOT_SUPPORTED:      # a launch failure must not be mistaken for "not applicable"
-                    raise
-                continue
-        torch.cuda.synchronize()
-        for name in list(times):
-            times[name] = graph_time_us(lambda: _DENSE[name](x, weight, bias, residual, relu), iters, rounds)
+        times = _dispatch.measure(_DENSE, lambda name: _DENSE[name](x, weight, bias, residual, relu), iters, rounds)
     DENSE_LOG.append((key, {k: round(v, 1) for k, v in times.items()}))
-    if not times:
-        return "blaslt"
-    return min(times, key=times.get)
+    return min(times, key=times.get) if times else "blaslt"
 
 
 def tsa_split(both, heads, points):
@@ -526,11 +340,7 @@ def tsa_split(both, heads, points):
     assert both.shape[1] == heads * 2 * points * 3
     off = torch.empty((2, nq, heads, points * 2), dtype=both.dtype, device=both.device)
     w = torch.empty((2, nq, heads, points), dtype=both.dtype, device=both.device)
-    handle = _lib.load_library()
-    with torch.cuda.device(both.device):
-        st = handle.bevops_tsa_split(_lib.F16, both.data_ptr(), off.data_ptr(), w.data_ptr(), nq, heads, points,
-                                     _lib.current_stream_ptr(both.device))
-    _lib.check(st, "bevops_tsa_split")
+    _call("bevops_tsa_split", both.device, _lib.F16, both.data_ptr(), off.data_ptr(), w.data_ptr(), nq, heads, points)
     return off, w
 
 
@@ -540,8 +350,5 @@ def queue_mean2(x):
     out = torch.empty((1,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
     if out.numel() == 0:
         return out
-    handle = _lib.load_library()
-    with torch.cuda.device(x.device):
-        st = handle.bevops_queue_mean2(_lib.F16, x.data_ptr(), out.data_ptr(), out.numel(), _lib.current_stream_ptr(x.device))
-    _lib.check(st, "bevops_queue_mean2")
+    _call("bevops_queue_mean2", x.device, _lib.F16, x.data_ptr(), out.data_ptr(), out.numel())
     return out

@@ -10,8 +10,8 @@ def test_dense_dispatch_default_without_measurement():
     assert L._dense_default(512, 256, False) == "blaslt"
     assert L._dense_default(256, 200, False) == "blaslt"       # outside tsgemm's K % 64 domain
     assert set(L._DENSE) == {"tsgemm", "tile", "small", "blaslt", "torch"}
-    # reproducible mode (camera-sharded runs, BEVOPS_DENSE_TUNE=0 semantics): a function of the problem alone, on the
-    # hand-written kernels only; few rows -> the no-pipeline GEMM
+    # rule mode (DETERMINISTIC: camera-sharded runs; NOT what BEVOPS_DENSE_TUNE=0 selects -- that is the default above):
+    # a function of the problem alone, on the hand-written kernels only; few rows -> the no-pipeline GEMM
     assert L._dense_deterministic(256, 256, 40000) == "tsgemm"
     assert L._dense_deterministic(192, 256, 40000) == "tile"
     assert L._dense_deterministic(256, 256, 900) == "small"
