@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 # single elements, ragged tiles, sharp softmax
 SHAPES = [(64, 960, 960, 32, 1.0), (8, 900, 900, 32, 1.0), (8, 900, 2500, 32, 1.0), (2, 64, 40000, 32, 1.0),
           (16, 1024, 1024, 64, 1.0), (8, 512, 777, 128, 1.0), (3, 1, 1, 16, 1.0), (5, 31, 33, 48, 1.0),
-          (4, 100, 300, 32, 6.0)]
+          (4, 100, 300, 32, 6.0), (3, 45, 77, 80, 1.0), (2, 33, 130, 96, 1.0), (2, 64, 95, 112, 1.0)]
 IDS = ["x".join(map(str, s[:4])) + ("_gain%g" % s[4] if s[4] != 1.0 else "") for s in SHAPES]
 
 
