@@ -109,6 +109,56 @@ def reference_key_map(model):
     return m
 
 
+def centernet_key_map(model):
+    """`reference_key_map` for centernet.CenterNet: {our parameter name: source} from mmdet 2.x's CenterNet state dict
+    (backbone = ResNet-18, neck = CTResNetNeck with use_dcn, bbox_head = CenterNetHead).  Key names as mmdet 2.x's
+    modules register them:
+
+      backbone.conv1 / bn1, backbone.layer{1..4}.{0,1}.conv{1,2} / bn{1,2}, .downsample.{0,1}   (mmdet ResNet, BasicBlock)
+      neck.deconv_layers.{0,2,4}.conv (+ .conv_offset) / .bn     the DCN packs (mmcv ConvModule -> `.conv`, `.bn`)
+      neck.deconv_layers.{1,3,5}.conv / .bn                       the transposed convolutions
+      bbox_head.{heatmap,wh,offset}_head.{0,2}                     Sequential(conv3x3, ReLU, conv1x1)
+
+    ("deconv_bn", conv, bn): the BN behind a ConvTranspose2d, folded with `fold_deconv_bn`.  Neither mmdet nor a
+    checkpoint is available to this repository's tests: parity with the library's names is unpinned."""
+    m = {}
+
+    def fold(ours, conv, bn, tag="conv_bn"):
+        m[ours + ".weight"] = (tag, conv, bn)
+        m[ours + ".bias"] = (tag, conv, bn)
+
+    fold("backbone.stem", "backbone.conv1", "backbone.bn1")
+    for s, stage in enumerate(model.backbone.stages):
+        for j, blk in enumerate(stage):
+            ours, ref = f"backbone.stages.{s}.{j}", f"backbone.layer{s + 1}.{j}"
+            fold(ours + ".conv1", ref + ".conv1", ref + ".bn1")
+            fold(ours + ".conv2", ref + ".conv2", ref + ".bn2")
+            if blk.downsample is not None:
+                fold(ours + ".downsample", ref + ".downsample.0", ref + ".downsample.1")
+    for i in range(len(model.neck.dcn)):
+        ref = f"neck.deconv_layers.{2 * i}"
+        fold(f"neck.dcn.{i}", ref + ".conv", ref + ".bn")
+        for n in ("weight", "bias"):
+            m[f"neck.dcn.{i}.conv_offset.{n}"] = f"{ref}.conv.conv_offset.{n}"
+        ref = f"neck.deconv_layers.{2 * i + 1}"
+        fold(f"neck.deconv.{i}", ref + ".conv", ref + ".bn", "deconv_bn")
+    for k, head in model.heads.items():
+        for ours, ref in ((0, 0), (1, 2)):
+            for n in ("weight", "bias"):
+                m[f"heads.{k}.{ours}.{n}"] = f"bbox_head.{k}_head.{ref}.{n}"
+    return m
+
+
+def fold_deconv_bn(weight, conv_bias, gamma, beta, mean, var, eps=BN_EPS):
+    """`fold_conv_bn` behind a ConvTranspose2d: its weight is [Cin, Cout, kh, kw], so the scale goes to dimension 1."""
+    w = weight.double()
+    scale = gamma.double() / torch.sqrt(var.double() + eps)
+    shift = beta.double() - mean.double() * scale
+    if conv_bias is not None:
+        shift = shift + conv_bias.double() * scale
+    return w * scale.view(1, -1, *([1] * (w.dim() - 2))), shift
+
+
 def fold_conv_bn(weight, conv_bias, gamma, beta, mean, var, eps=BN_EPS):
     """Frozen BatchNorm behind a convolution as the convolution's own scale and shift (float64)."""
     w = weight.double()
@@ -119,13 +169,18 @@ def fold_conv_bn(weight, conv_bias, gamma, beta, mean, var, eps=BN_EPS):
     return w * scale.view(-1, *([1] * (w.dim() - 1))), shift
 
 
-def load_reference_state_dict(model, state_dict, strict=True):
-    """Fill `model` (bevformer.BEVFormer) from a reference checkpoint's state dict (the value of its
-    "state_dict" entry, or the dict itself).  Returns (missing, unexpected): our parameters that found
+def load_centernet_state_dict(model, state_dict, strict=True):
+    """`load_reference_state_dict` for centernet.CenterNet and mmdet's CenterNet checkpoint (`centernet_key_map`)."""
+    return load_reference_state_dict(model, state_dict, strict, centernet_key_map(model))
+
+
+def load_reference_state_dict(model, state_dict, strict=True, key_map=None):
+    """Fill `model` (bevformer.BEVFormer, or another model with its `key_map`) from a reference checkpoint's state
+    dict (the value of its "state_dict" entry, or the dict itself).  Returns (missing, unexpected): our parameters that found
     no source, and reference tensors nothing asked for (BN `num_batches_tracked` and the head's
     `code_weights` buffer are expected leftovers and not reported).  strict: raise on either."""
     sd = state_dict.get("state_dict", state_dict)
-    kmap = reference_key_map(model)
+    kmap = reference_key_map(model) if key_map is None else key_map
     own = dict(model.named_parameters())
     used, missing = set(), []
     with torch.no_grad():
@@ -135,12 +190,13 @@ def load_reference_state_dict(model, state_dict, strict=True):
                 missing.append(name)
                 continue
             if isinstance(src, tuple):
-                _, conv, bn = src
+                tag, conv, bn = src
                 keys = [conv + ".weight", bn + ".weight", bn + ".bias", bn + ".running_mean", bn + ".running_var"]
                 if any(k not in sd for k in keys):
                     missing.append(name)
                     continue
-                w, b = fold_conv_bn(sd[keys[0]], sd.get(conv + ".bias"), *(sd[k] for k in keys[1:]))
+                fold = fold_deconv_bn if tag == "deconv_bn" else fold_conv_bn
+                w, b = fold(sd[keys[0]], sd.get(conv + ".bias"), *(sd[k] for k in keys[1:]))
                 used.update(keys)
                 if conv + ".bias" in sd:
                     used.add(conv + ".bias")

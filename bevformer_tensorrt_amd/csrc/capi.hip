@@ -115,6 +115,9 @@ const Entry kTable[] = {
     {"bevops_small_gemm_f16", (void *)&bevops_small_gemm_f16},
     {"bevops_conv_tile_f16", (void *)&bevops_conv_tile_f16},
     {"bevops_conv3x3_c64_f16", (void *)&bevops_conv3x3_c64_f16},
+    {"bevops_deconv4x4s2_packed_weight_size", (void *)&bevops_deconv4x4s2_packed_weight_size},
+    {"bevops_deconv4x4s2_pack_weight", (void *)&bevops_deconv4x4s2_pack_weight},
+    {"bevops_deconv4x4s2_f16", (void *)&bevops_deconv4x4s2_f16},
     {"bevops_refine_reference_points", (void *)&bevops_refine_reference_points},
     {"bevops_decode_boxes", (void *)&bevops_decode_boxes},
     {"bevops_conv_tile_int8_fused", (void *)&bevops_conv_tile_int8_fused},

@@ -35,6 +35,7 @@ from .decode2d import centernet_decode, yolox_decode, box_nms
 from .lss_prepare import lss_voxel_prepare, lss_lidar_coor, bev_pool_v2_indirect
 from .calibrate import calib_state_size, calib_collect, calib_threshold
 from .bev_half import lss_depth_split, upsample_bilinear_concat_nhwc
+from .deconv import conv_transpose2d_nhwc, pack_deconv4x4s2, deconv_packed_weight
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -66,4 +67,5 @@ __all__ = [
     "msda_pack_value", "multi_scale_deformable_attn_prepacked", "multi_scale_deformable_attn_local", "image_normalize_pad", "padded_size", "quantize_rows", "dequantize_rows", "linear_int8", "tsgemm", "tsgemm_ln", "tsgemm_grouped", "tile_gemm", "tile_gemm_dst", "small_gemm_dst", "small_gemm", "dense_auto", "tsa_split", "queue_mean2", "conv_nhwc", "conv3x3_nhwc", "conv3x3_auto", "conv3x3_c64", "conv_int8_nhwc", "bias_relu_maxpool_nhwc", "stem_conv_pool", "point_sampling", "self_attention_qkv", "refine_reference_points", "decode_boxes",
     "linear_int8_chain", "linear_int8_ln",
     "lss_depth_split", "upsample_bilinear_concat_nhwc",
+    "conv_transpose2d_nhwc", "pack_deconv4x4s2", "deconv_packed_weight",
 ]

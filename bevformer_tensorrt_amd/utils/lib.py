@@ -121,6 +121,9 @@ SIGNATURES = {
     "bevops_small_gemm_f16_dst": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
     "bevops_conv_tile_f16": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p]),
     "bevops_conv3x3_c64_f16": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    "bevops_deconv4x4s2_packed_weight_size": (c_size_t, [c_int] * 3),
+    "bevops_deconv4x4s2_pack_weight": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "bevops_deconv4x4s2_f16": (c_int, [c_int] + [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
     "bevops_refine_reference_points": (c_int, [c_int] + [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 3),
     "bevops_decode_boxes": (c_int, [c_int] + [c_void_p] * 3 + [c_int] + [c_float] * 6 + [c_void_p] * 3),
     "bevops_bias_relu_maxpool_nhwc": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -503,6 +503,22 @@ int bevops_conv_tile_f16(const void *x, const void *weight_taps, const void *bia
  * NOT_SUPPORTED unless Cin == Cout == 64. */
 int bevops_conv3x3_c64_f16(const void *x, const void *weight_taps, const void *bias, void *out, int B, int H, int W,
                            int Cin, int Cout, int relu, void *stream);
+/* ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1) + bias + ReLU on channels-last fp16 activations (the up-sampling
+ * layers of mmdet's CTResNetNeck; csrc/deconv.hip) as four implicit GEMMs on the same tiled skeleton, one per output
+ * parity: no column buffer, no zero-stuffed input.  x [B, H, W, Cin], out [B, 2H, 2W, Cout] =
+ * act(conv_transpose2d(x, weight, stride 2, padding 1) + bias[co]); fp32 accumulation, bias / ReLU in fp32, one
+ * rounding; bias fp16, optional.  `packed_weight` is the layer's [Cin, Cout, 4, 4] weight (PyTorch's layout) in the
+ * order [parity 2 py + px][Cout][dy][dx][Cin], element = weight[ci][co][3 - py - 2 dy][3 - px - 2 dx]:
+ * bevops_deconv4x4s2_pack_weight writes it (once per weight tensor; bevops_deconv4x4s2_packed_weight_size bytes, 0 for
+ * a layer outside the domain).  fp16 only, Cin % 32 == 0 (a k-step never straddles two taps), Cout % 8 == 0, any
+ * other dtype / ksize / stride / pad: BEVOPS_NOT_SUPPORTED.  Non-positive dimensions, NULL operands, x / packed_weight /
+ * out not 16-byte aligned: BEVOPS_BAD_PARAM.  B == 0: nothing launched, BEVOPS_SUCCESS.  x and the packed weight are
+ * addressed through 32-bit byte offsets: each must be smaller than 0xFFFFFF00 bytes (B H W Cin < 2 147 483 520
+ * elements), else BEVOPS_NOT_SUPPORTED; the output is addressed through 64-bit pointers. */
+size_t bevops_deconv4x4s2_packed_weight_size(int dtype, int Cin, int Cout);
+int bevops_deconv4x4s2_pack_weight(int dtype, const void *weight, void *packed, int Cin, int Cout, void *stream);
+int bevops_deconv4x4s2_f16(int dtype, const void *x, const void *packed_weight, const void *bias, void *out, int B, int H,
+                           int W, int Cin, int Cout, int ksize, int stride, int pad, int relu, void *stream);
 /* Decoder reference-point refinement (det2trt/models/modules/decoder.py:24-40, 93-103) as one launch:
  *   new_reference_points[q] = sigmoid((tmp[q][0], tmp[q][1], tmp[q][4]) + inverse_sigmoid(reference_points[q]))
  * on fp16 tensors, every step rounded to binary16 as the framework's op sequence rounds it (the refined points are the
