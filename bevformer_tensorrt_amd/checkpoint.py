@@ -149,6 +149,70 @@ def centernet_key_map(model):
     return m
 
 
+YOLOX_BN_EPS = 1e-3   # norm_cfg=dict(type="BN", momentum=0.03, eps=0.001) of every YOLOX ConvModule
+
+
+def yolox_key_map(model):
+    """`reference_key_map` for yolox.YOLOX: {our parameter name: source} from mmdet 2.x's YOLOX state dict (backbone =
+    CSPDarknet, neck = YOLOXPAFPN, bbox_head = YOLOXHead).  Every ConvModule registers `.conv` and `.bn`; key names as
+    mmdet 2.x's modules register them:
+
+      backbone.stem.conv                                             Focus' ConvModule
+      backbone.stage{1..4}.0                                         the 3x3 / 2 ConvModule
+      backbone.stage4.1.conv{1,2}                                    SPPBottleneck
+      backbone.stage{i}.{1 | 2}.{main,short,final}_conv, .blocks.{j}.conv{1,2}     CSPLayer (index 2 behind the SPP)
+      neck.reduce_layers.{i}, neck.top_down_blocks.{i}, neck.downsamples.{i}, neck.bottom_up_blocks.{i}, neck.out_convs.{i}
+      bbox_head.multi_level_cls_convs.{l}.{0,1}, .multi_level_reg_convs.{l}.{0,1}  the towers
+      bbox_head.multi_level_conv_{cls,reg,obj}.{l}                    the predictors (plain convolutions, copied)
+
+    ("conv_bn_yolox", conv, bn): folded with `fold_conv_bn` at eps 1e-3.  Neither mmdet nor a checkpoint is available
+    to this repository's tests: parity with the library's names is unpinned."""
+    m = {}
+
+    def fold(ours, ref):
+        m[ours + ".weight"] = ("conv_bn_yolox", ref + ".conv", ref + ".bn")
+        m[ours + ".bias"] = ("conv_bn_yolox", ref + ".conv", ref + ".bn")
+
+    def csp(ours, ref, layer):
+        for n in ("main_conv", "short_conv", "final_conv"):
+            fold(f"{ours}.{n}", f"{ref}.{n}")
+        for j in range(len(layer.blocks)):
+            fold(f"{ours}.blocks.{j}.conv1", f"{ref}.blocks.{j}.conv1")
+            fold(f"{ours}.blocks.{j}.conv2", f"{ref}.blocks.{j}.conv2")
+
+    fold("backbone.stem.conv", "backbone.stem.conv")
+    for i, stage in enumerate(model.backbone.stages):
+        ours, ref = f"backbone.stages.{i}", f"backbone.stage{i + 1}"
+        fold(ours + ".0", ref + ".0")
+        if len(stage) == 3:
+            fold(ours + ".1.conv1", ref + ".1.conv1")
+            fold(ours + ".1.conv2", ref + ".1.conv2")
+        k = len(stage) - 1
+        csp(f"{ours}.{k}", f"{ref}.{k}", stage[k])
+    neck = model.neck
+    for i in range(len(neck.reduce_layers)):
+        fold(f"neck.reduce_layers.{i}", f"neck.reduce_layers.{i}")
+        fold(f"neck.downsamples.{i}", f"neck.downsamples.{i}")
+        csp(f"neck.top_down_blocks.{i}", f"neck.top_down_blocks.{i}", neck.top_down_blocks[i])
+        csp(f"neck.bottom_up_blocks.{i}", f"neck.bottom_up_blocks.{i}", neck.bottom_up_blocks[i])
+    for i in range(len(neck.out_convs)):
+        fold(f"neck.out_convs.{i}", f"neck.out_convs.{i}")
+    head = model.bbox_head
+    for l in range(len(head.cls_convs)):
+        for j in range(len(head.cls_convs[l])):
+            fold(f"bbox_head.cls_convs.{l}.{j}", f"bbox_head.multi_level_cls_convs.{l}.{j}")
+            fold(f"bbox_head.reg_convs.{l}.{j}", f"bbox_head.multi_level_reg_convs.{l}.{j}")
+        for k in ("cls", "reg", "obj"):
+            for n in ("weight", "bias"):
+                m[f"bbox_head.conv_{k}.{l}.{n}"] = f"bbox_head.multi_level_conv_{k}.{l}.{n}"
+    return m
+
+
+def load_yolox_state_dict(model, state_dict, strict=True):
+    """`load_reference_state_dict` for yolox.YOLOX and mmdet's YOLOX checkpoint (`yolox_key_map`)."""
+    return load_reference_state_dict(model, state_dict, strict, yolox_key_map(model))
+
+
 def fold_deconv_bn(weight, conv_bias, gamma, beta, mean, var, eps=BN_EPS):
     """`fold_conv_bn` behind a ConvTranspose2d: its weight is [Cin, Cout, kh, kw], so the scale goes to dimension 1."""
     w = weight.double()
@@ -196,7 +260,8 @@ def load_reference_state_dict(model, state_dict, strict=True, key_map=None):
                     missing.append(name)
                     continue
                 fold = fold_deconv_bn if tag == "deconv_bn" else fold_conv_bn
-                w, b = fold(sd[keys[0]], sd.get(conv + ".bias"), *(sd[k] for k in keys[1:]))
+                eps = YOLOX_BN_EPS if tag == "conv_bn_yolox" else BN_EPS
+                w, b = fold(sd[keys[0]], sd.get(conv + ".bias"), *(sd[k] for k in keys[1:]), eps=eps)
                 used.update(keys)
                 if conv + ".bias" in sd:
                     used.add(conv + ".bias")

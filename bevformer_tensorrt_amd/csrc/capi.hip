@@ -118,6 +118,10 @@ const Entry kTable[] = {
     {"bevops_deconv4x4s2_packed_weight_size", (void *)&bevops_deconv4x4s2_packed_weight_size},
     {"bevops_deconv4x4s2_pack_weight", (void *)&bevops_deconv4x4s2_pack_weight},
     {"bevops_deconv4x4s2_f16", (void *)&bevops_deconv4x4s2_f16},
+    {"bevops_conv_slice_f16", (void *)&bevops_conv_slice_f16},
+    {"bevops_focus_nhwc", (void *)&bevops_focus_nhwc},
+    {"bevops_spp_maxpool_nhwc", (void *)&bevops_spp_maxpool_nhwc},
+    {"bevops_upsample_nearest2x_nhwc", (void *)&bevops_upsample_nearest2x_nhwc},
     {"bevops_refine_reference_points", (void *)&bevops_refine_reference_points},
     {"bevops_decode_boxes", (void *)&bevops_decode_boxes},
     {"bevops_conv_tile_int8_fused", (void *)&bevops_conv_tile_int8_fused},

@@ -36,6 +36,8 @@ from .lss_prepare import lss_voxel_prepare, lss_lidar_coor, bev_pool_v2_indirect
 from .calibrate import calib_state_size, calib_collect, calib_threshold
 from .bev_half import lss_depth_split, upsample_bilinear_concat_nhwc
 from .deconv import conv_transpose2d_nhwc, pack_deconv4x4s2, deconv_packed_weight
+from .yolox_ops import (conv_slice_nhwc, conv_slice_taps, conv_slice_packed_weight, focus_nhwc, spp_maxpool_nhwc,
+                        upsample_nearest2x_nhwc, pad_channels, unpad_channels)
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -68,4 +70,6 @@ __all__ = [
     "linear_int8_chain", "linear_int8_ln",
     "lss_depth_split", "upsample_bilinear_concat_nhwc",
     "conv_transpose2d_nhwc", "pack_deconv4x4s2", "deconv_packed_weight",
+    "conv_slice_nhwc", "conv_slice_taps", "conv_slice_packed_weight", "focus_nhwc", "spp_maxpool_nhwc",
+    "upsample_nearest2x_nhwc", "pad_channels", "unpad_channels",
 ]

@@ -124,6 +124,11 @@ SIGNATURES = {
     "bevops_deconv4x4s2_packed_weight_size": (c_size_t, [c_int] * 3),
     "bevops_deconv4x4s2_pack_weight": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "bevops_deconv4x4s2_f16": (c_int, [c_int] + [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
+    "bevops_conv_slice_f16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 9 +
+                              [c_void_p]),
+    "bevops_focus_nhwc": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "bevops_spp_maxpool_nhwc": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 8 + [c_void_p]),
+    "bevops_upsample_nearest2x_nhwc": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p]),
     "bevops_refine_reference_points": (c_int, [c_int] + [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 3),
     "bevops_decode_boxes": (c_int, [c_int] + [c_void_p] * 3 + [c_int] + [c_float] * 6 + [c_void_p] * 3),
     "bevops_bias_relu_maxpool_nhwc": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

@@ -519,6 +519,42 @@ size_t bevops_deconv4x4s2_packed_weight_size(int dtype, int Cin, int Cout);
 int bevops_deconv4x4s2_pack_weight(int dtype, const void *weight, void *packed, int Cin, int Cout, void *stream);
 int bevops_deconv4x4s2_f16(int dtype, const void *x, const void *packed_weight, const void *bias, void *out, int B, int H,
                            int W, int Cin, int Cout, int ksize, int stride, int pad, int relu, void *stream);
+/* Convolution on CHANNEL SLICES of channels-last fp16 tensors with the activation in the epilogue (csrc/conv_slice.hip;
+ * the convolutions of YOLOX's CSPDarknet, PAFPN and head): the same tiled implicit GEMM as bevops_conv_tile_f16, but
+ * x, residual and out each point at the first channel of a slice of a wider channels-last tensor -- element
+ * (b, y, x, c) lives at base + ((b H + y) W + x) pitch + c, every pitch in elements, at least the slice's channel count
+ * and a multiple of 8 -- so a layer reads one operand of a concatenation and writes its share of the next one.
+ *   out = act(conv(x) + bias[co]) + residual     kernel ksize in {1, 3}, pad ksize / 2, stride in {1, 2}
+ * The identity is added AFTER the activation (mmdet's DarknetBottleneck).  act: 0 none, 1 ReLU, 2 SiLU = v * sigmoid(v)
+ * in fp32 (hardware exponential and reciprocal).  fp32 accumulation, bias / activation / identity in fp32, ONE rounding.
+ * weight_taps [Cout][ksize][ksize][Cin] as for bevops_conv_tile_f16; bias fp16 [Cout], optional; residual optional;
+ * out [B, Hout, Wout] pixels of Cout channels.  x and out MAY be disjoint channel slices of one buffer (every access
+ * is a 16-byte vector inside its own slice); out and residual may be the same slice; x must not overlap out.
+ * Cin % 32 == 0, Cout % 8 == 0, ksize / stride / act outside the lists: BEVOPS_NOT_SUPPORTED.  NULL x / weight_taps /
+ * out, non-positive sizes, a pitch below the channel count or no multiple of 8, x / weight_taps / residual / out not
+ * 16-byte aligned: BEVOPS_BAD_PARAM.  x and the weight are addressed through 32-bit byte offsets: B H W x_pitch and
+ * Cout ksize^2 Cin must stay below 0xFFFFFF00 bytes, else BEVOPS_NOT_SUPPORTED.  B == 0: nothing launched,
+ * BEVOPS_SUCCESS.  With pitch == channels, no residual and act in {0, 1} the result equals bevops_conv_tile_f16's bit
+ * for bit. */
+int bevops_conv_slice_f16(const void *x, int x_pitch, const void *weight_taps, const void *bias, const void *residual,
+                          int res_pitch, void *out, int out_pitch, int B, int H, int W, int Cin, int Cout, int ksize,
+                          int stride, int act, void *stream);
+/* The data-movement layers of YOLOX on the same channel slices (csrc/yolox.hip); fp16, exact, 16-byte vectors of 8
+ * channels.  Statuses as bevops_conv_slice_f16: NULL / unaligned operands, non-positive sizes, bad pitches:
+ * BEVOPS_BAD_PARAM; C % 8 != 0, odd H or W (focus), a pool size that is even or above 13, a buffer of 0xFFFFFF00 bytes
+ * or more: BEVOPS_NOT_SUPPORTED; B == 0: BEVOPS_SUCCESS without a launch.
+ * bevops_focus_nhwc: mmdet's Focus.  image planar [B, 3, H, W] -> out [B, H/2, W/2] pixels of 32 channels: channel
+ *   3 p + c = image[b, c, 2 y + (p & 1), 2 x + (p >> 1)] for p = 0 .. 3 (top-left, bottom-left, top-right, bottom-right),
+ *   channels 12 .. 31 = 0 (the stem convolution then is a bevops_conv_slice_f16 with Cin = 32 and zero weight columns).
+ * bevops_spp_maxpool_nhwc: SPPBottleneck's three stride-1 "same" max-pools (odd sizes k0, k1, k2 <= 13, padding -inf)
+ *   of the C-channel slice x, written to the three C-channel slices behind each other at out (out_pitch >= 3 C), one
+ *   launch.  x and out may be slices of one [B, H, W, 4 C] buffer.  A NaN reaches every window that holds it.
+ * bevops_upsample_nearest2x_nhwc: out [B, 2H, 2W, C] = x [B, H, W, C] at (Y / 2, X / 2). */
+int bevops_focus_nhwc(const void *image, void *out, int out_pitch, int B, int H, int W, void *stream);
+int bevops_spp_maxpool_nhwc(const void *x, int x_pitch, void *out, int out_pitch, int B, int H, int W, int C, int k0,
+                            int k1, int k2, void *stream);
+int bevops_upsample_nearest2x_nhwc(const void *x, int x_pitch, void *out, int out_pitch, int B, int H, int W, int C,
+                                   void *stream);
 /* Decoder reference-point refinement (det2trt/models/modules/decoder.py:24-40, 93-103) as one launch:
  *   new_reference_points[q] = sigmoid((tmp[q][0], tmp[q][1], tmp[q][4]) + inverse_sigmoid(reference_points[q]))
  * on fp16 tensors, every step rounded to binary16 as the framework's op sequence rounds it (the refined points are the
