@@ -122,6 +122,10 @@ const Entry kTable[] = {
     {"bevops_focus_nhwc", (void *)&bevops_focus_nhwc},
     {"bevops_spp_maxpool_nhwc", (void *)&bevops_spp_maxpool_nhwc},
     {"bevops_upsample_nearest2x_nhwc", (void *)&bevops_upsample_nearest2x_nhwc},
+    {"bevops_conv_slice_s8", (void *)&bevops_conv_slice_s8},
+    {"bevops_focus_nhwc_q", (void *)&bevops_focus_nhwc_q},
+    {"bevops_spp_maxpool_nhwc_s8", (void *)&bevops_spp_maxpool_nhwc_s8},
+    {"bevops_upsample_nearest2x_nhwc_s8", (void *)&bevops_upsample_nearest2x_nhwc_s8},
     {"bevops_refine_reference_points", (void *)&bevops_refine_reference_points},
     {"bevops_decode_boxes", (void *)&bevops_decode_boxes},
     {"bevops_conv_tile_int8_fused", (void *)&bevops_conv_tile_int8_fused},

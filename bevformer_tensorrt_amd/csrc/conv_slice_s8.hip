@@ -1,0 +1,331 @@
+// Implicit-GEMM convolution on CHANNEL SLICES of channels-last INT8 tensors (bevops_conv_slice_s8): the int8 sibling of
+// bevops_conv_slice_f16 (csrc/conv_slice.hip) for the INT8 build of YOLOX (quantization.build_int8_yolox).
+// Operands: x int8 (real = q scale_a), weights int8 taps-major [Cout][k][k][Cin] (real = q scale_w w_scales[co]), bias
+// fp32, identity int8 with its own scale, output int8 requantised with the consumer's scale or fp16.  k in {1, 3},
+// stride in {1, 2}, x / residual / out point at the first channel of a slice: element (b, y, x, c) at
+// base + ((b H + y) W + x) pitch + c, pitches in elements.
+//
+// EPILOGUE OPERATION ORDER (every step one fp32 operation, written as explicit fma / separate operations, so that the
+// result does not depend on the compiler's contraction choice; include/bevops.h repeats it):
+//   s_aw  = scale_a * scale_w                        on the host, one fp32 rounding
+//   inv   = 1.f / scale_out                          on the host, one fp32 rounding
+//   sc    = s_aw * w_scales[co]                      one rounding (sc = s_aw without w_scales)
+//   v     = fma((float)sum, sc, bias[co])            sum: the exact int32 sum; (float): round to nearest even, exact
+//                                                    for |sum| <= 2^24; ONE rounding for multiply and add
+//   v     = act(v)                                   0 none, 1 max(v, 0), 2 v * rcp(1 + exp(-v)) (silu_f32 of
+//                                                    conv_slice.hip: hardware exponential and reciprocal)
+//   v     = fma((float)res_q, scale_res, v)          with an identity only: BEHIND the activation, ONE rounding
+//   int8:   q = clamp(rne(v * inv), -127, 127)       one rounding for the product, v_rndne_f32, max, min
+//   fp16:   one rounding of v to binary16
+// Non-finite values: a NaN v leaves as -127 (max(NaN, -127) = -127), +inf as 127, -inf as -127 (as SiLU: NaN ->
+// -127); as fp16 they go through as they are.  With ReLU a NaN becomes 0 before the requantisation.
+//
+// MI355X mapping: the skeleton of conv_slice.hip -- 128 x 128 output tiles (128 x 64 for Cout <= 64), 256 threads = 4
+// waves of 64 x 64 (64 x 32), range-checked 16-byte buffer loads into two register sets, two LDS images of 64 bytes of
+// k per row, one barrier per step, XCD-contiguous tile order, epilogue through per-wave LDS staging -- on the int8
+// matrix cores: v_mfma_i32_32x32x32_i8 with the operand layout of tile_gemm.hip's S8 mode, 64 k-values per step.
+//
+// K-CHUNK SCHEME.  Cin % 32 == 0, not 64: a 64-byte step can straddle a tap (Cin 32, 96, 160) and the last step can
+// be half empty (K = 9 * 96 = 13.5 steps).  A thread moves ONE 16-byte chunk per row and step; chunk j of step t holds
+// k = 64 t + 16 j .. + 15.  16 divides Cin, so a chunk never straddles a tap, and the thread derives its own
+// (tap, channel) = (k / Cin, k % Cin) -- kept incrementally: channel += 64 per step, at most two wraps since
+// Cin >= 32.  The tap's address delta and its validity bit (bit `tap` of the row's 9-bit mask) are therefore per
+// thread, not block-uniform.  k >= K means tap >= k^2, whose mask bits are clear: the activation chunk reads zero.
+// The weight's range check is on the whole buffer, so a chunk behind a row's end would read the next row: its offset is
+// replaced by the beyond-the-buffer address when k >= K.  Both operands of a chunk past K are zero.
+// All of an address goes into the buffer load's VGPR offset (the scalar offset takes no part in the range check).
+#include "gemm_host.h"
+
+namespace bevops {
+namespace {
+
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+typedef int i32x16_t __attribute__((ext_vector_type(16)));
+
+constexpr int kTM = 128;                       // rows (output pixels) per tile
+constexpr int kTLd = 64 + 16;                  // LDS row: the step's 64 bytes + 16 (conflict-free 16-byte fragment reads)
+constexpr int kEpiStride = 64 * 4 + 16;        // staging row: 64 x 4 bytes + pad
+constexpr int kLds = 2 * (kTM + 128) * kTLd;   // two images of [A rows | W rows]: 40 960 bytes, the fp16 kernel's
+static_assert(kLds >= 4 * 32 * kEpiStride, "epilogue staging must fit in the operand images");
+
+enum { kActNone = 0, kActRelu = 1, kActSilu = 2 };
+
+struct ConvSliceS8Args {
+  const void *x, *w, *res;
+  const float *bias, *wscale;
+  void *out;
+  int M, N, K, act, tiles_n, tiles_total;
+  unsigned x_bytes, w_bytes;                   // extents of the input slice and the weight (the loads' range check)
+  int x_pitch, res_pitch, out_pitch;           // elements (= bytes for the int8 operands) between two pixels
+  int cin, hin, win, hout, wout, stride, ks;
+  float s_aw, s_res, inv_s_out;
+};
+
+// (conv_slice.hip's, unchanged)
+__device__ __forceinline__ float silu_f32(float v) { return v * __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
+
+__device__ __forceinline__ int s8_at(const unsigned *w, int c) {   // signed byte c of a little-endian word array
+  return (int)(w[c >> 2] << (24 - 8 * (c & 3))) >> 24;
+}
+
+// NI: 32-column MFMA blocks per wave: 2 -> 128-column tiles, 1 -> 64-column tiles (Cout <= 64); OUT8: int8 output
+template <int NI, bool OUT8>
+__global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p) {
+  constexpr int MJ = 2;                        // 32-row MFMA blocks per wave
+  constexpr int kTN = 64 * NI;
+  constexpr int kStepK = 64;                   // k-values (bytes) per step
+  __shared__ __attribute__((aligned(16))) char smem[kLds];
+  const int M = p.M, N = p.N, K = p.K;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int per_xcd = (p.tiles_total + 7) >> 3;
+  const int logical = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+  if (logical >= p.tiles_total) return;
+  const int m0 = (logical / p.tiles_n) * kTM, n0 = (logical % p.tiles_n) * kTN;
+  const int r0 = tid >> 2, r1 = r0 + 64;       // 128 rows x 4 chunks of 16 bytes of k
+  const int lchunk = (tid & 3) * 16;           // this thread's chunk: byte position in a step and in an LDS row
+  i32x16_t acc[NI][MJ];
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int j = 0; j < MJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0;
+  const int nk = (K + kStepK - 1) / kStepK;
+  const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.x), 0, p.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w), 0, p.w_bytes, 0x00020000);
+  // output row m is pixel (b, yo, xo); its k-values are [tap][Cin] with tap (ky, kx) read from input pixel
+  // (s yo + ky - pad, s xo + kx - pad) of the same image, zero outside it
+  const int cin = p.cin, ksz = p.ks, taps = ksz * ksz, pad = ksz >> 1;
+  const int per = p.hout * p.wout;
+  unsigned a_off0, a_off1, tapmask0, tapmask1;
+  auto place = [&](int m, unsigned &off, unsigned &mk) {
+    off = kGemmOob; mk = 0;
+    if (m >= M) return;
+    const int b = m / per, pix = m - b * per;
+    const int yo = pix / p.wout, xo = pix - yo * p.wout;
+    const int y = yo * p.stride, x = xo * p.stride;           // centre tap in the input image
+    off = (unsigned)((((size_t)b * p.hin + y) * p.win + x) * p.x_pitch);
+    for (int t = 0; t < taps; ++t) {
+      const int yy = y + t / ksz - pad, xx = x + t % ksz - pad;
+      mk |= (yy >= 0 && yy < p.hin && xx >= 0 && xx < p.win) ? (1u << t) : 0u;
+    }
+  };
+  place(m0 + r0, a_off0, tapmask0);
+  place(m0 + r1, a_off1, tapmask1);
+  // the position of this thread's chunk in the NEXT gload: global k, and (tap = (ty, tx), channel) = (k / Cin, k % Cin)
+  int g_k = lchunk, g_c = lchunk, g_tap = 0, g_ty = 0, g_tx = 0;
+  const bool w_ok0 = n0 + r0 < N, w_ok1 = NI == 2 && n0 + r1 < N;
+  const unsigned w_row0 = (unsigned)((size_t)(n0 + r0) * K), w_row1 = (unsigned)((size_t)(n0 + r1) * K);
+  uint4 ra0[2], ra1[2], rb0[2], rb1[2];        // two register sets (set = step parity): the loads of two steps in flight
+  auto bload = [](const __amdgpu_buffer_rsrc_t &rs, unsigned voff) {
+    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0));
+  };
+  auto wrap = [&]() {                          // one tap further when the channel left the tap
+    if (g_c >= cin) {
+      g_c -= cin; ++g_tap;
+      if (++g_tx == ksz) { g_tx = 0; ++g_ty; }
+    }
+  };
+  auto gload = [&](auto setc) {
+    constexpr int S = decltype(setc)::value;
+    wrap(); wrap();                            // 64 k-values further: at most two taps, Cin >= 32
+    // (chunks past K: g_tap >= taps, whose mask bits are clear; g_tap stays below 32 -- at most five steps past K)
+    const unsigned delta = (unsigned)(((g_ty - pad) * p.win + (g_tx - pad)) * p.x_pitch + g_c);
+    ra0[S] = bload(rs_a, (tapmask0 >> g_tap) & 1u ? a_off0 + delta : kGemmOob);
+    ra1[S] = bload(rs_a, (tapmask1 >> g_tap) & 1u ? a_off1 + delta : kGemmOob);
+    const bool kok = g_k < K;                  // K % 16 == 0: the chunk is all in or all out
+    rb0[S] = bload(rs_w, (kok && w_ok0) ? w_row0 + (unsigned)g_k : kGemmOob);
+    if constexpr (NI == 2) rb1[S] = bload(rs_w, (kok && w_ok1) ? w_row1 + (unsigned)g_k : kGemmOob);
+    g_k += kStepK; g_c += kStepK;
+  };
+  auto lstore = [&](int buf, auto setc) {
+    constexpr int S = decltype(setc)::value;
+    char *As = smem + buf * (kTM + 128) * kTLd, *Ws = As + kTM * kTLd;
+    *reinterpret_cast<uint4 *>(As + r0 * kTLd + lchunk) = ra0[S];
+    *reinterpret_cast<uint4 *>(As + r1 * kTLd + lchunk) = ra1[S];
+    *reinterpret_cast<uint4 *>(Ws + r0 * kTLd + lchunk) = rb0[S];
+    if constexpr (NI == 2) *reinterpret_cast<uint4 *>(Ws + r1 * kTLd + lchunk) = rb1[S];
+  };
+  auto compute = [&](int kt) {
+    const char *As = smem + (kt & 1) * (kTM + 128) * kTLd, *Ws = As + kTM * kTLd;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int kk = ks * 32 + (lane >> 5) * 16;
+      // MFMA operand A = the weight rows (output channels n), B = the activation rows (m): a lane's 4 consecutive
+      // accumulator rows are then 4 consecutive channels of one output pixel
+      i32x4_t a[NI], b[MJ];
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+        a[i] = *reinterpret_cast<const i32x4_t *>(Ws + (wn * 32 * NI + i * 32 + (lane & 31)) * kTLd + kk);
+#pragma unroll
+      for (int j = 0; j < MJ; ++j)
+        b[j] = *reinterpret_cast<const i32x4_t *>(As + (wm * 32 * MJ + j * 32 + (lane & 31)) * kTLd + kk);
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < MJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+  };
+  using Set0 = std::integral_constant<int, 0>;
+  using Set1 = std::integral_constant<int, 1>;
+  // (loads past the last step are issued too -- beyond-the-buffer addresses, they read as zero -- and so are the LDS writes
+  // of a step that does not exist, into the image nobody reads: no branches, exact wait counts)
+  gload(Set0{});
+  lstore(0, Set0{});
+  gload(Set1{});
+  gload(Set0{});
+  __syncthreads();
+  auto step = [&](int kt, auto next_set) {
+    lstore((kt + 1) & 1, next_set);
+    gload(next_set);
+    compute(kt);
+    __syncthreads();
+  };
+  for (int kt = 0; kt < nk; kt += 2) {         // (an odd step count runs one step on zeros: adds nothing)
+    step(kt, Set1{});
+    step(kt + 1, Set0{});
+  }
+  // ---- epilogue.  acc[i][j][4 g + c]: n = n0 + wn*32*NI + i*32 + 8 g + 4 (lane >> 5) + c,
+  //                                     m = m0 + wm*64 + j*32 + (lane & 31)
+  // (the barrier that ended the last step also freed both LDS images)
+  constexpr int kCW = OUT8 ? 16 : 8;           // consecutive channels a thread owns: one 16-byte store
+  constexpr int kCH = 32 * NI / kCW;           // chunks per row of the wave's 32 NI columns
+  constexpr int kRows = 64 / kCH;              // staged rows per read-back pass
+  constexpr int kIT = 32 / kRows;              // passes over the wave's 32 staged rows
+  const int cc = lane & (kCH - 1);
+  const int ncol = n0 + wn * 32 * NI + cc * kCW;
+  const bool col_ok = ncol < N;                // N % kCW == 0: the chunk is all in or all out
+  char *stage = smem + wave * 32 * kEpiStride;
+  const signed char *res = static_cast<const signed char *>(p.res);
+  const int act = p.act;
+  float sc[kCW], bs[kCW];
+#pragma unroll
+  for (int c = 0; c < kCW; ++c) {
+    sc[c] = (p.wscale && col_ok) ? p.s_aw * p.wscale[ncol + c] : p.s_aw;
+    bs[c] = (p.bias && col_ok) ? p.bias[ncol + c] : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < MJ; ++j) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        *reinterpret_cast<i32x4_t *>(stage + (lane & 31) * kEpiStride + (i * 32 + 8 * g + 4 * (lane >> 5)) * 4) =
+            i32x4_t{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int it = 0; it < kIT; ++it) {
+      const int row = it * kRows + lane / kCH;
+      const int m = m0 + wm * 32 * MJ + j * 32 + row;
+      i32x4_t s[kCW / 4];
+#pragma unroll
+      for (int q = 0; q < kCW / 4; ++q)
+        s[q] = *reinterpret_cast<const i32x4_t *>(stage + row * kEpiStride + cc * kCW * 4 + q * 16);
+      if (m >= M || !col_ok) continue;
+      unsigned rq[kCW / 4] = {};
+      if (res) {
+        if constexpr (OUT8) {
+          const uint4 q = *reinterpret_cast<const uint4 *>(res + (size_t)m * p.res_pitch + ncol);
+          rq[0] = q.x; rq[1] = q.y; rq[2] = q.z; rq[3] = q.w;
+        } else {
+          const uint2 q = *reinterpret_cast<const uint2 *>(res + (size_t)m * p.res_pitch + ncol);
+          rq[0] = q.x; rq[1] = q.y;
+        }
+      }
+      float v[kCW];
+#pragma unroll
+      for (int c = 0; c < kCW; ++c) v[c] = __builtin_fmaf((float)s[c >> 2][c & 3], sc[c], bs[c]);
+      if (act == kActRelu) {
+#pragma unroll
+        for (int c = 0; c < kCW; ++c) v[c] = fmaxf(v[c], 0.f);
+      } else if (act == kActSilu) {
+#pragma unroll
+        for (int c = 0; c < kCW; ++c) v[c] = silu_f32(v[c]);
+      }
+      if (res) {                               // the identity AFTER the activation
+#pragma unroll
+        for (int c = 0; c < kCW; ++c) v[c] = __builtin_fmaf((float)s8_at(rq, c), p.s_res, v[c]);
+      }
+      if constexpr (OUT8) {
+        unsigned pk[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+          const float t = v[c] * p.inv_s_out;
+          pk[c >> 2] |= ((unsigned)(int)fminf(fmaxf(rintf(t), -127.f), 127.f) & 0xffu) << (8 * (c & 3));
+        }
+        *reinterpret_cast<uint4 *>(static_cast<signed char *>(p.out) + (size_t)m * p.out_pitch + ncol) =
+            make_uint4(pk[0], pk[1], pk[2], pk[3]);
+      } else {
+        uint4 o;
+        o.x = pack_h2(v[0], v[1]); o.y = pack_h2(v[2], v[3]); o.z = pack_h2(v[4], v[5]); o.w = pack_h2(v[6], v[7]);
+        *reinterpret_cast<uint4 *>(static_cast<__half *>(p.out) + (size_t)m * p.out_pitch + ncol) = o;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+inline bool bad_scale(float s) { return !(s > 0.f) || !(s <= 3.4028234663852886e38f); }   // non-positive, NaN or inf
+
+}  // namespace
+}  // namespace bevops
+
+using namespace bevops;
+
+extern "C" int bevops_conv_slice_s8(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps,
+                                    const float *w_scales, float scale_w, const float *bias, const void *residual_q,
+                                    int res_pitch, float scale_res, int out_dtype, void *out, int out_pitch,
+                                    float scale_out, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int act,
+                                    void *stream) {
+  if (!x_q || !w_q_taps || !out || B < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return BEVOPS_BAD_PARAM;
+  if (ksize <= 0 || stride <= 0) return BEVOPS_BAD_PARAM;
+  if (out_dtype != BEVOPS_I8 && out_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
+  const bool out8 = out_dtype == BEVOPS_I8;
+  if (x_pitch < Cin || out_pitch < Cout || (residual_q && res_pitch < Cout)) return BEVOPS_BAD_PARAM;
+  // int8 slices: 16-byte vectors, so a pitch that is no multiple of 16 elements leaves every other pixel unaligned
+  if (x_pitch % 16 != 0 || out_pitch % (out8 ? 16 : 8) != 0 || (residual_q && res_pitch % 16 != 0)) return BEVOPS_BAD_PARAM;
+  if (misaligned(x_q, 15u) || misaligned(w_q_taps, 15u) || misaligned(out, 15u) ||
+      (residual_q && misaligned(residual_q, 15u)) || (bias && misaligned(bias, 3u)) || (w_scales && misaligned(w_scales, 3u)))
+    return BEVOPS_BAD_PARAM;
+  if (bad_scale(scale_a) || bad_scale(scale_w) || (residual_q && bad_scale(scale_res)) || (out8 && bad_scale(scale_out)))
+    return BEVOPS_BAD_PARAM;
+  if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || act < kActNone || act > kActSilu) return BEVOPS_NOT_SUPPORTED;
+  if (Cin % 32 != 0 || Cout % (out8 ? 16 : 8) != 0) return BEVOPS_NOT_SUPPORTED;
+  // x and the weight are addressed through 32-bit buffer offsets (identity and output through 64-bit pointers)
+  const unsigned long long rows_in = (unsigned long long)B * H * W;
+  if (gemm_over_limit(rows_in, x_pitch, 1) || gemm_over_limit((unsigned long long)Cout, ksize * ksize * Cin, 1))
+    return BEVOPS_NOT_SUPPORTED;
+  if (B == 0) return BEVOPS_SUCCESS;
+  const int pad = ksize / 2;
+  ConvSliceS8Args p;
+  p.x = x_q; p.w = w_q_taps; p.res = residual_q; p.bias = bias; p.wscale = w_scales; p.out = out;
+  p.hin = H; p.win = W; p.cin = Cin; p.stride = stride; p.ks = ksize;
+  p.hout = (H + 2 * pad - ksize) / stride + 1;
+  p.wout = (W + 2 * pad - ksize) / stride + 1;
+  const unsigned long long rows = (unsigned long long)B * p.hout * p.wout;
+  p.M = (int)rows; p.N = Cout; p.K = ksize * ksize * Cin; p.act = act;
+  p.x_pitch = x_pitch; p.res_pitch = residual_q ? res_pitch : 0; p.out_pitch = out_pitch;
+  p.x_bytes = (unsigned)((rows_in - 1) * x_pitch + Cin);            // the last pixel's slice ends here
+  p.w_bytes = (unsigned)((size_t)Cout * p.K);
+  p.s_aw = scale_a * scale_w;
+  p.s_res = residual_q ? scale_res : 0.f;
+  p.inv_s_out = out8 ? 1.f / scale_out : 1.f;
+  const bool narrow = Cout <= 64;
+  p.tiles_n = (Cout + (narrow ? 64 : 128) - 1) / (narrow ? 64 : 128);
+  const long long tiles = (long long)p.tiles_n * (long long)((rows + kTM - 1) / kTM);
+  if (tiles > 0x3fffffffLL) return BEVOPS_NOT_SUPPORTED;
+  p.tiles_total = (int)tiles;
+  const dim3 grid((unsigned)((tiles + 7) / 8 * 8));
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (out8) {
+    if (narrow) hipLaunchKernelGGL((conv_slice_s8_kernel<1, true>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((conv_slice_s8_kernel<2, true>), grid, dim3(256), 0, st, p);
+  } else {
+    if (narrow) hipLaunchKernelGGL((conv_slice_s8_kernel<1, false>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((conv_slice_s8_kernel<2, false>), grid, dim3(256), 0, st, p);
+  }
+  return launch_status();
+}

@@ -37,7 +37,8 @@ from .calibrate import calib_state_size, calib_collect, calib_threshold
 from .bev_half import lss_depth_split, upsample_bilinear_concat_nhwc
 from .deconv import conv_transpose2d_nhwc, pack_deconv4x4s2, deconv_packed_weight
 from .yolox_ops import (conv_slice_nhwc, conv_slice_taps, conv_slice_packed_weight, focus_nhwc, spp_maxpool_nhwc,
-                        upsample_nearest2x_nhwc, pad_channels, unpad_channels)
+                        upsample_nearest2x_nhwc, pad_channels, unpad_channels, conv_slice_q_taps, focus_nhwc_q,
+                        quantize_weight_taps)
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -72,4 +73,5 @@ __all__ = [
     "conv_transpose2d_nhwc", "pack_deconv4x4s2", "deconv_packed_weight",
     "conv_slice_nhwc", "conv_slice_taps", "conv_slice_packed_weight", "focus_nhwc", "spp_maxpool_nhwc",
     "upsample_nearest2x_nhwc", "pad_channels", "unpad_channels",
+    "conv_slice_q_taps", "focus_nhwc_q", "quantize_weight_taps",
 ]

@@ -10,7 +10,12 @@ copies.  A slice starts on a 16-byte boundary (c0 % 8 == 0) and its pitch is a m
 
 Channel padding: the convolution kernel needs Cin % 32 == 0.  A layer of other width (YOLOX-x's 80-channel layers) runs
 at the next multiple of 32 with zero weight rows and columns and zero bias: `pad_channels`.  A pad channel is
-act(0 + 0) + 0 = 0 exactly, for every activation here, so it stays zero through the network."""
+act(0 + 0) + 0 = 0 exactly, for every activation here, so it stays zero through the network.
+
+The INT8 flavours (the INT8 build of YOLOX, yolox_int8.py) live beside them: `conv_slice_q_taps`
+(bevops_conv_slice_s8, csrc/conv_slice_s8.hip), `focus_nhwc_q`, and `spp_maxpool_nhwc` / `upsample_nearest2x_nhwc`
+routed by dtype; an int8 slice's pitch is a multiple of 16 and c0 % 16 == 0.  `quantize_weight_taps` is their weight
+quantiser."""
 import torch
 
 from ..utils import lib as _lib
@@ -90,14 +95,15 @@ def slice_pitch(t, name="tensor"):
     elif B > 1:
         pitch = t.stride(0)
     else:
-        pitch = padded_width(C, 8)
+        pitch = padded_width(C, 16 // t.element_size())
     ok = pitch >= C and (C == 1 or t.stride(1) == 1) and (W == 1 or t.stride(3) == pitch) and \
         (H == 1 or t.stride(2) == W * pitch) and (B == 1 or t.stride(0) == H * W * pitch)
     if not ok:
         raise ValueError(f"{name}: not a channel slice of a channels-last tensor (shape {tuple(t.shape)}, strides "
                          f"{tuple(t.stride())})")
-    if pitch % 8 or t.data_ptr() % 16:
-        raise ValueError(f"{name}: a slice starts on a 16-byte boundary and its pitch is a multiple of 8 elements "
+    vec = 16 // t.element_size()               # elements per 16-byte vector: 8 (fp16), 16 (int8)
+    if pitch % vec or t.data_ptr() % 16:
+        raise ValueError(f"{name}: a slice starts on a 16-byte boundary and its pitch is a multiple of {vec} elements "
                          f"(pitch {pitch}, address % 16 = {t.data_ptr() % 16})")
     return pitch
 
@@ -109,7 +115,7 @@ def _check_f16(t, name):
 
 def _dest(out, shape, like, name):
     if out is None:
-        return nhwc_empty(*shape, like.device)
+        return nhwc_empty(*shape, like.device, like.dtype)
     if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device:
         raise ValueError(f"{name}: out must be {tuple(shape)} {like.dtype} on {like.device}, got {tuple(out.shape)}")
     return out
@@ -228,7 +234,10 @@ def spp_maxpool_nhwc(x, out=None, kernel_sizes=(5, 9, 13)):
     """SPPBottleneck's pools: x a channel slice [B, C, H, W] -> a slice [B, 3 C, H, W] holding max_pool2d(x, k, stride
     1, padding k // 2) for the three odd k <= 13 behind each other.  x and out may be slices of one [B, 4 C, H, W]
     buffer (x = buf[:, :C], out = buf[:, C:]): the concatenation is then free.  One launch.  A NaN reaches every window
-    that holds it, as in F.max_pool2d."""
+    that holds it, as in F.max_pool2d.  An int8 slice goes to bevops_spp_maxpool_nhwc_s8 (C % 16 == 0, padding -128;
+    exact, the output keeps the input's scale)."""
+    if x.dtype == torch.int8:
+        return _spp_maxpool_s8(x, out, kernel_sizes)
     _check_f16(x, "x")
     B, C, H, W = x.shape
     ks = tuple(int(k) for k in kernel_sizes)
@@ -245,14 +254,142 @@ def spp_maxpool_nhwc(x, out=None, kernel_sizes=(5, 9, 13)):
 
 
 def upsample_nearest2x_nhwc(x, out=None):
-    """x a channel slice [B, C, H, W] -> a slice [B, C, 2H, 2W] = F.interpolate(x, scale_factor=2, mode="nearest")."""
-    _check_f16(x, "x")
+    """x a channel slice [B, C, H, W] -> a slice [B, C, 2H, 2W] = F.interpolate(x, scale_factor=2, mode="nearest").
+    An int8 slice goes to bevops_upsample_nearest2x_nhwc_s8 (C % 16 == 0; a byte copy, the scale is the input's)."""
+    s8 = x.dtype == torch.int8
+    if s8:
+        _check_s8(x, "x")
+    else:
+        _check_f16(x, "x")
+    entry, vec = ("bevops_upsample_nearest2x_nhwc_s8", 16) if s8 else ("bevops_upsample_nearest2x_nhwc", 8)
     B, C, H, W = x.shape
-    if C % 8:
-        raise _lib.BevopsError("bevops_upsample_nearest2x_nhwc: C % 8 == 0", _lib.NOT_SUPPORTED)
+    if C % vec:
+        raise _lib.BevopsError(f"{entry}: C % {vec} == 0", _lib.NOT_SUPPORTED)
     xp = slice_pitch(x, "x")
     out = _dest(out, (B, C, 2 * H, 2 * W), x, "upsample_nearest2x_nhwc")
     op = slice_pitch(out, "out")
     if B:
-        _call("bevops_upsample_nearest2x_nhwc", x.device, x.data_ptr(), xp, out.data_ptr(), op, B, H, W, C)
+        _call(entry, x.device, x.data_ptr(), xp, out.data_ptr(), op, B, H, W, C)
+    return out
+
+
+# ---- the INT8 flavours (the INT8 build of YOLOX, quantization.build_int8_yolox).  An int8 slice starts on a 16-byte
+# boundary and its pitch is a multiple of 16; a tensor carries no scale: the caller passes it.
+
+def _check_s8(t, name):
+    if not (t.is_cuda and t.dtype == torch.int8):
+        raise ValueError(f"{name}: an int8 CUDA tensor")
+
+
+def _scale(v, name):
+    v = float(v)
+    if not (v > 0.0 and v < float("inf")):
+        raise ValueError(f"{name}: a positive finite scale, got {v}")
+    return v
+
+
+def quantize_weight_taps(weight, bias=None, groups_in=None, groups_out=None, multiple=CHANNEL_MULTIPLE):
+    """Per-output-channel min-max quantisation of a convolution weight [Cout, Cin, k, k] for conv_slice_q_taps, after
+    the padding of `pad_channels`: -> (w_q_taps int8 [Pout, k, k, Pin], w_scales fp32 [Pout], bias fp32 [Pout]).
+    scale[co] = amax_co / 127 in fp32 (1 for a row of zeros: the pad rows), q = clamp(rne(w / scale), -127, 127) with
+    the quotient in fp32; pad rows and columns are exact zeros and the pad bias is zero, so a pad channel leaves a layer
+    as q = 0."""
+    wp, bp = pad_channels(weight.detach().float(), None if bias is None else bias.detach().float(), groups_in, groups_out,
+                          multiple)
+    amax = wp.abs().amax(dim=(1, 2, 3))
+    scales = torch.where(amax > 0, amax / 127.0, torch.ones_like(amax))
+    q = torch.clamp(torch.round(wp / scales[:, None, None, None]), -127, 127).to(torch.int8)
+    if bp is None:
+        bp = wp.new_zeros((wp.shape[0],))
+    return q.permute(0, 2, 3, 1).contiguous(), scales.contiguous(), bp.contiguous()
+
+
+def conv_slice_q_taps(x_q, scale_x, w_q_taps, w_scales, bias, act, residual_q=None, scale_res=1.0, stride=1, out=None,
+                      scale_out=None, out_dtype=torch.int8):
+    """bevops_conv_slice_s8: the convolution of an int8 channel slice x_q [B, Cin, H, W] (real = q scale_x) with int8
+    taps-major weights w_q_taps [Cout, k, k, Cin] (real = q w_scales[co]; w_scales fp32 [Cout]), bias fp32 [Cout] or
+    None, act in "none", "relu", "silu", the int8 identity residual_q (real = q scale_res) added BEHIND the
+    activation.  out_dtype torch.int8: requantised with scale_out, q = clamp(rne(v / scale_out), -127, 127);
+    torch.float16: one rounding (scale_out unused).  Cin % 32 == 0, Cout % 16 == 0 (int8 out) or % 8 (fp16 out), k in
+    {1, 3}, stride in {1, 2}, else BevopsError NOT_SUPPORTED.  include/bevops.h states the operation order."""
+    _check_s8(x_q, "x_q")
+    if w_q_taps.dim() != 4 or w_q_taps.shape[1] != w_q_taps.shape[2] or not w_q_taps.is_contiguous() or \
+            w_q_taps.dtype != torch.int8 or w_q_taps.device != x_q.device:
+        raise ValueError("conv_slice_q: w_q_taps [Cout, k, k, Cin] contiguous int8 on the input's device")
+    B, Cin, H, W = x_q.shape
+    Cout, k = w_q_taps.shape[0], w_q_taps.shape[1]
+    if w_q_taps.shape[3] != Cin:
+        raise ValueError(f"conv_slice_q: the weight has {w_q_taps.shape[3]} input channels, x_q has {Cin}")
+    if act not in ACTS:
+        raise ValueError(f"conv_slice_q: act in {sorted(k for k in ACTS if k)}")
+    if out_dtype not in (torch.int8, torch.float16):
+        raise ValueError("conv_slice_q: out_dtype torch.int8 or torch.float16")
+    if out is not None and out.dtype != out_dtype:
+        raise ValueError(f"conv_slice_q: out is {out.dtype}, out_dtype {out_dtype}")
+    out8 = out_dtype == torch.int8
+    if k not in (1, 3) or stride not in (1, 2) or Cin % 32 or Cout % (16 if out8 else 8):
+        raise _lib.BevopsError("bevops_conv_slice_s8: ksize in {1, 3}, stride in {1, 2}, Cin % 32 == 0, Cout % 16 == 0 "
+                               "(int8 out) or % 8 (fp16 out)", _lib.NOT_SUPPORTED)
+    sx = _scale(scale_x, "scale_x")
+    so = _scale(scale_out, "scale_out") if out8 else 1.0
+    for t, name in ((w_scales, "w_scales"), (bias, "bias")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != Cout or
+                              t.device != x_q.device):
+            raise ValueError(f"conv_slice_q: {name} contiguous fp32 [Cout] on the input's device")
+    Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
+    xp = slice_pitch(x_q, "x_q")
+    if out is None:
+        out = nhwc_empty(B, Cout, Ho, Wo, x_q.device, out_dtype)
+    elif tuple(out.shape) != (B, Cout, Ho, Wo) or out.device != x_q.device:
+        raise ValueError(f"conv_slice_q: out must be {(B, Cout, Ho, Wo)} on {x_q.device}, got {tuple(out.shape)}")
+    op = slice_pitch(out, "out")
+    rp, sr = 0, 1.0
+    if residual_q is not None:
+        _check_s8(residual_q, "residual_q")
+        if tuple(residual_q.shape) != tuple(out.shape):
+            raise ValueError("conv_slice_q: the identity has the output's shape")
+        rp, sr = slice_pitch(residual_q, "residual_q"), _scale(scale_res, "scale_res")
+    if B == 0:
+        return out
+    _call("bevops_conv_slice_s8", x_q.device, x_q.data_ptr(), xp, sx, w_q_taps.data_ptr(), _ptr(w_scales), 1.0, _ptr(bias),
+          _ptr(residual_q), rp, sr, _lib.I8 if out8 else _lib.F16, out.data_ptr(), op, so, B, H, W, Cin, Cout, k,
+          int(stride), ACTS[act])
+    return out
+
+
+def focus_nhwc_q(image, scale, out=None):
+    """`focus_nhwc` leaving as int8 (bevops_focus_nhwc_q): image [B, 3, H, W] contiguous fp16 -> an int8 channel slice
+    [B, 32, H/2, W/2], q = clamp(rne(x / scale), -127, 127) (the product x * (1 / scale) in fp32), channels 12 .. 31
+    zero."""
+    _check_f16(image, "image")
+    if image.dim() != 4 or image.shape[1] != 3 or not image.is_contiguous():
+        raise ValueError("focus_nhwc_q: a contiguous [B, 3, H, W] image")
+    B, _, H, W = image.shape
+    if H % 2 or W % 2:
+        raise _lib.BevopsError("bevops_focus_nhwc_q: H and W even", _lib.NOT_SUPPORTED)
+    s = _scale(scale, "scale")
+    shape = (B, FOCUS_CHANNELS, H // 2, W // 2)
+    if out is None:
+        out = nhwc_empty(*shape, image.device, torch.int8)
+    elif tuple(out.shape) != shape or out.dtype != torch.int8 or out.device != image.device:
+        raise ValueError(f"focus_nhwc_q: out must be {shape} int8 on {image.device}, got {tuple(out.shape)}")
+    op = slice_pitch(out, "out")
+    if B:
+        _call("bevops_focus_nhwc_q", image.device, image.data_ptr(), s, out.data_ptr(), op, B, H, W)
+    return out
+
+
+def _spp_maxpool_s8(x, out, kernel_sizes):
+    _check_s8(x, "x")
+    B, C, H, W = x.shape
+    ks = tuple(int(k) for k in kernel_sizes)
+    if len(ks) != 3:
+        raise ValueError("spp_maxpool_nhwc: three kernel sizes")
+    if C % 16 or any(k % 2 == 0 or k > 13 or k < 1 for k in ks):
+        raise _lib.BevopsError("bevops_spp_maxpool_nhwc_s8: C % 16 == 0, odd kernel sizes <= 13", _lib.NOT_SUPPORTED)
+    xp = slice_pitch(x, "x")
+    out = _dest(out, (B, 3 * C, H, W), x, "spp_maxpool_nhwc")
+    op = slice_pitch(out, "out")
+    if B:
+        _call("bevops_spp_maxpool_nhwc_s8", x.device, x.data_ptr(), xp, out.data_ptr(), op, B, H, W, C, *ks)
     return out

@@ -1085,3 +1085,30 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy"):
             "int8_backbone_layers": len(ch.convs) + sum(len(b) for b in ch.plan), "activation_chain": True,
             "calibration_frames": n}
     return model, qops, note
+
+
+def build_int8_yolox(Y, dev, images, calibrator="entropy", calibration_cache=None, cfg=None, ops=None):
+    """The PTQ build of the re-hosted YOLOX (`Y` = the yolox module, or a yolox.YOLOX instance whose weights to
+    quantise; `images` = an iterable of fp16 [B, 3, H, W] calibration images): every convolution of the backbone, the
+    PAFPN and the head on bevops_conv_slice_s8, every tensor between two layers int8 with one scale per buffer
+    (yolox_int8.py, design/yolox_int8.md).  The calibration runs the fp16 fast path and collects every scale group's
+    writes under one site; `calibrator` names any of CALIBRATORS.  calibration_cache: a path -- an existing cache is
+    loaded INSTEAD of running frames, otherwise the collected statistics are saved there (the calibration-cache
+    format of save_calibration / load_calibration).  Returns (model, note): model has forward / get_bboxes / prepare
+    like YOLOX, and YOLOXRunner captures it unchanged."""
+    from . import yolox_int8 as _yi
+    fp = Y if isinstance(Y, torch.nn.Module) else Y.YOLOX(cfg)
+    fp = fp.to(dev, torch.float16)
+    plan = _yi.build_plan(fp)
+    _, num_groups = plan.groups()
+    cal = get_calibrator(calibrator)()
+    n = 0
+    if calibration_cache is not None and os.path.exists(calibration_cache):
+        _yi.load_calibration(cal, calibration_cache, dev if isinstance(cal, _DeviceCalibrator) else None)
+    else:
+        n = _yi.calibrate(fp, images, cal, ops)
+        if calibration_cache is not None:
+            _yi.save_calibration(cal, calibration_cache, {"model": "yolox", "scale_groups": num_groups, "frames": n})
+    model = _yi.Int8YOLOX(fp, _yi.group_scales_from(cal, num_groups), ops)
+    note = {"int8_layers": model.num_int8_layers, "scale_groups": num_groups, "calibration_frames": n}
+    return model, note

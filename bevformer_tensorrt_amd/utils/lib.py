@@ -129,6 +129,11 @@ SIGNATURES = {
     "bevops_focus_nhwc": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "bevops_spp_maxpool_nhwc": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 8 + [c_void_p]),
     "bevops_upsample_nearest2x_nhwc": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p]),
+    "bevops_conv_slice_s8": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
+                                     c_float, c_int, c_void_p, c_int, c_float] + [c_int] * 8 + [c_void_p]),
+    "bevops_focus_nhwc_q": (c_int, [c_void_p, c_float, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "bevops_spp_maxpool_nhwc_s8": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 8 + [c_void_p]),
+    "bevops_upsample_nearest2x_nhwc_s8": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p]),
     "bevops_refine_reference_points": (c_int, [c_int] + [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 3),
     "bevops_decode_boxes": (c_int, [c_int] + [c_void_p] * 3 + [c_int] + [c_float] * 6 + [c_void_p] * 3),
     "bevops_bias_relu_maxpool_nhwc": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

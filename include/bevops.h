@@ -555,6 +555,45 @@ int bevops_spp_maxpool_nhwc(const void *x, int x_pitch, void *out, int out_pitch
                             int k1, int k2, void *stream);
 int bevops_upsample_nearest2x_nhwc(const void *x, int x_pitch, void *out, int out_pitch, int B, int H, int W, int C,
                                    void *stream);
+/* bevops_conv_slice_f16's INT8 sibling (csrc/conv_slice_s8.hip; the convolutions of the INT8 build of YOLOX) on channel
+ * slices of channels-last INT8 tensors, sums exact in int32 on the int8 matrix cores:
+ *   sum = sum_{ky,kx,ci} x_q[b, s yo + ky - k/2, s xo + kx - k/2, ci] w_q[co, ky, kx, ci]          (int32, exact)
+ * and then, every step ONE fp32 operation in exactly this order (s_aw = scale_a * scale_w and inv = 1.f / scale_out
+ * are computed once on the host in fp32):
+ *   sc = s_aw * w_scales[co]                (sc = s_aw when w_scales is NULL)
+ *   v  = fma((float)sum, sc, bias[co])      ((float): round to nearest even, exact for |sum| <= 2^24; bias 0 when NULL)
+ *   v  = act(v)                             act: 0 none, 1 ReLU max(v, 0), 2 SiLU v * rcp(1 + exp(-v)) as
+ *                                           bevops_conv_slice_f16 computes it
+ *   v  = fma((float)res_q, scale_res, v)    with residual_q only: the identity BEHIND the activation
+ *   out_dtype BEVOPS_I8:  q = min(max(rne(v * inv), -127), 127)      BEVOPS_F16: one rounding of v to binary16
+ * A NaN v leaves as -127, +inf as 127, -inf as -127 (int8); as fp16 they go through as they are.
+ * x_q, residual_q and out point at the first channel of a slice (element (b, y, x, c) at base + ((b H + y) W + x)
+ * pitch + c, pitches in elements); int8 slices start on 16-byte boundaries and their pitch is a multiple of 16 (an
+ * fp16 out: 16-byte boundary, pitch a multiple of 8).  Every load and store lies inside its own slice: x and out may
+ * be disjoint slices of one buffer, out and residual_q may be the same slice; x must not overlap out.  w_q_taps int8
+ * [Cout][ksize][ksize][Cin]; w_scales fp32 [Cout], optional; bias fp32 [Cout], optional.  ksize in {1, 3}, pad ksize / 2,
+ * stride in {1, 2}.  Cin % 32 == 0 (NOT 64: a thread derives the tap and channel of its own 16-byte chunk, and chunks
+ * at k >= ksize^2 Cin read zero on both operands), Cout % 16 == 0 for int8 out, % 8 for fp16 out; these, ksize /
+ * stride / act / out_dtype outside the lists, and B H W x_pitch or Cout ksize^2 Cin of 0xFFFFFF00 bytes or more:
+ * BEVOPS_NOT_SUPPORTED.  NULL x_q / w_q_taps / out, non-positive sizes, a pitch below the channel count or no multiple
+ * of 16 (8), unaligned operands, a scale in use (scale_a, scale_w; scale_res with residual_q; scale_out with int8 out)
+ * that is not positive and finite: BEVOPS_BAD_PARAM.  B == 0: BEVOPS_SUCCESS without a launch.  With pitch ==
+ * channels, no identity, act in {0, 1} and Cin % 64 == 0 the sums are bevops_conv_tile_int8's. */
+int bevops_conv_slice_s8(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps, const float *w_scales,
+                         float scale_w, const float *bias, const void *residual_q, int res_pitch, float scale_res,
+                         int out_dtype, void *out, int out_pitch, float scale_out, int B, int H, int W, int Cin, int Cout,
+                         int ksize, int stride, int act, void *stream);
+/* The data-movement layers of YOLOX on INT8 slices (csrc/yolox.hip): 16-byte vectors of 16 channels, pitches multiples
+ * of 16, C % 16 == 0; statuses as the fp16 entries above (a scale that is not positive and finite: BEVOPS_BAD_PARAM).
+ * bevops_focus_nhwc_q: bevops_focus_nhwc from the planar fp16 image to an int8 slice of 32 channels,
+ *   q = min(max(rne(x * (1.f / scale)), -127), 127), the product in fp32; channels 12 .. 31 = 0.
+ * bevops_spp_maxpool_nhwc_s8: the three pools on signed bytes; padding -128 (a window always holds its centre).
+ * bevops_upsample_nearest2x_nhwc_s8: a byte copy.  The pools and the copy are exact and keep their input's scale. */
+int bevops_focus_nhwc_q(const void *image, float scale, void *out, int out_pitch, int B, int H, int W, void *stream);
+int bevops_spp_maxpool_nhwc_s8(const void *x, int x_pitch, void *out, int out_pitch, int B, int H, int W, int C, int k0,
+                               int k1, int k2, void *stream);
+int bevops_upsample_nearest2x_nhwc_s8(const void *x, int x_pitch, void *out, int out_pitch, int B, int H, int W, int C,
+                                      void *stream);
 /* Decoder reference-point refinement (det2trt/models/modules/decoder.py:24-40, 93-103) as one launch:
  *   new_reference_points[q] = sigmoid((tmp[q][0], tmp[q][1], tmp[q][4]) + inverse_sigmoid(reference_points[q]))
  * on fp16 tensors, every step rounded to binary16 as the framework's op sequence rounds it (the refined points are the
