@@ -123,6 +123,8 @@ const Entry kTable[] = {
     {"bevops_spp_maxpool_nhwc", (void *)&bevops_spp_maxpool_nhwc},
     {"bevops_upsample_nearest2x_nhwc", (void *)&bevops_upsample_nearest2x_nhwc},
     {"bevops_conv_slice_s8", (void *)&bevops_conv_slice_s8},
+    {"bevops_conv_slice_s8_ex", (void *)&bevops_conv_slice_s8_ex},
+    {"bevops_deconv4x4s2_s8", (void *)&bevops_deconv4x4s2_s8},
     {"bevops_focus_nhwc_q", (void *)&bevops_focus_nhwc_q},
     {"bevops_spp_maxpool_nhwc_s8", (void *)&bevops_spp_maxpool_nhwc_s8},
     {"bevops_upsample_nearest2x_nhwc_s8", (void *)&bevops_upsample_nearest2x_nhwc_s8},

@@ -15,6 +15,8 @@
 //   v     = act(v)                                   0 none, 1 max(v, 0), 2 v * rcp(1 + exp(-v)) (silu_f32 of
 //                                                    conv_slice.hip: hardware exponential and reciprocal)
 //   v     = fma((float)res_q, scale_res, v)          with an identity only: BEHIND the activation, ONE rounding
+//                                                    (bevops_conv_slice_s8_ex with res_first = 1: this step moves IN
+//                                                    FRONT of the activation -- mmdet's BasicBlock, relu(conv2 + identity))
 //   int8:   q = clamp(rne(v * inv), -127, 127)       one rounding for the product, v_rndne_f32, max, min
 //   fp16:   one rounding of v to binary16
 // Non-finite values: a NaN v leaves as -127 (max(NaN, -127) = -127), +inf as 127, -inf as -127 (as SiLU: NaN ->
@@ -54,7 +56,7 @@ struct ConvSliceS8Args {
   const void *x, *w, *res;
   const float *bias, *wscale;
   void *out;
-  int M, N, K, act, tiles_n, tiles_total;
+  int M, N, K, act, res_first, tiles_n, tiles_total;
   unsigned x_bytes, w_bytes;                   // extents of the input slice and the weight (the loads' range check)
   int x_pitch, res_pitch, out_pitch;           // elements (= bytes for the int8 operands) between two pixels
   int cin, hin, win, hout, wout, stride, ks;
@@ -199,6 +201,7 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
   char *stage = smem + wave * 32 * kEpiStride;
   const signed char *res = static_cast<const signed char *>(p.res);
   const int act = p.act;
+  const bool res_front = res && p.res_first, res_behind = res && !p.res_first;   // block-uniform
   float sc[kCW], bs[kCW];
 #pragma unroll
   for (int c = 0; c < kCW; ++c) {
@@ -237,6 +240,10 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
       float v[kCW];
 #pragma unroll
       for (int c = 0; c < kCW; ++c) v[c] = __builtin_fmaf((float)s[c >> 2][c & 3], sc[c], bs[c]);
+      if (res_front) {                         // the identity IN FRONT of the activation (res_first)
+#pragma unroll
+        for (int c = 0; c < kCW; ++c) v[c] = __builtin_fmaf((float)s8_at(rq, c), p.s_res, v[c]);
+      }
       if (act == kActRelu) {
 #pragma unroll
         for (int c = 0; c < kCW; ++c) v[c] = fmaxf(v[c], 0.f);
@@ -244,7 +251,7 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
 #pragma unroll
         for (int c = 0; c < kCW; ++c) v[c] = silu_f32(v[c]);
       }
-      if (res) {                               // the identity AFTER the activation
+      if (res_behind) {                        // the identity AFTER the activation
 #pragma unroll
         for (int c = 0; c < kCW; ++c) v[c] = __builtin_fmaf((float)s8_at(rq, c), p.s_res, v[c]);
       }
@@ -275,11 +282,11 @@ inline bool bad_scale(float s) { return !(s > 0.f) || !(s <= 3.4028234663852886e
 
 using namespace bevops;
 
-extern "C" int bevops_conv_slice_s8(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps,
-                                    const float *w_scales, float scale_w, const float *bias, const void *residual_q,
-                                    int res_pitch, float scale_res, int out_dtype, void *out, int out_pitch,
-                                    float scale_out, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int act,
-                                    void *stream) {
+extern "C" int bevops_conv_slice_s8_ex(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps,
+                                       const float *w_scales, float scale_w, const float *bias, const void *residual_q,
+                                       int res_pitch, float scale_res, int out_dtype, void *out, int out_pitch,
+                                       float scale_out, int B, int H, int W, int Cin, int Cout, int ksize, int stride,
+                                       int act, int res_first, void *stream) {
   if (!x_q || !w_q_taps || !out || B < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return BEVOPS_BAD_PARAM;
   if (ksize <= 0 || stride <= 0) return BEVOPS_BAD_PARAM;
   if (out_dtype != BEVOPS_I8 && out_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
@@ -294,6 +301,8 @@ extern "C" int bevops_conv_slice_s8(const void *x_q, int x_pitch, float scale_a,
     return BEVOPS_BAD_PARAM;
   if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || act < kActNone || act > kActSilu) return BEVOPS_NOT_SUPPORTED;
   if (Cin % 32 != 0 || Cout % (out8 ? 16 : 8) != 0) return BEVOPS_NOT_SUPPORTED;
+  // the identity in front of the activation: of an identity, and not of SiLU (no layer of the models has it)
+  if (res_first && (!residual_q || act == kActSilu)) return BEVOPS_NOT_SUPPORTED;
   // x and the weight are addressed through 32-bit buffer offsets (identity and output through 64-bit pointers)
   const unsigned long long rows_in = (unsigned long long)B * H * W;
   if (gemm_over_limit(rows_in, x_pitch, 1) || gemm_over_limit((unsigned long long)Cout, ksize * ksize * Cin, 1))
@@ -306,7 +315,7 @@ extern "C" int bevops_conv_slice_s8(const void *x_q, int x_pitch, float scale_a,
   p.hout = (H + 2 * pad - ksize) / stride + 1;
   p.wout = (W + 2 * pad - ksize) / stride + 1;
   const unsigned long long rows = (unsigned long long)B * p.hout * p.wout;
-  p.M = (int)rows; p.N = Cout; p.K = ksize * ksize * Cin; p.act = act;
+  p.M = (int)rows; p.N = Cout; p.K = ksize * ksize * Cin; p.act = act; p.res_first = res_first ? 1 : 0;
   p.x_pitch = x_pitch; p.res_pitch = residual_q ? res_pitch : 0; p.out_pitch = out_pitch;
   p.x_bytes = (unsigned)((rows_in - 1) * x_pitch + Cin);            // the last pixel's slice ends here
   p.w_bytes = (unsigned)((size_t)Cout * p.K);
@@ -328,4 +337,13 @@ extern "C" int bevops_conv_slice_s8(const void *x_q, int x_pitch, float scale_a,
     else hipLaunchKernelGGL((conv_slice_s8_kernel<2, false>), grid, dim3(256), 0, st, p);
   }
   return launch_status();
+}
+
+extern "C" int bevops_conv_slice_s8(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps,
+                                    const float *w_scales, float scale_w, const float *bias, const void *residual_q,
+                                    int res_pitch, float scale_res, int out_dtype, void *out, int out_pitch,
+                                    float scale_out, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int act,
+                                    void *stream) {
+  return bevops_conv_slice_s8_ex(x_q, x_pitch, scale_a, w_q_taps, w_scales, scale_w, bias, residual_q, res_pitch, scale_res,
+                                 out_dtype, out, out_pitch, scale_out, B, H, W, Cin, Cout, ksize, stride, act, 0, stream);
 }

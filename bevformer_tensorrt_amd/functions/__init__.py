@@ -19,7 +19,7 @@ from .spatial_cross_attention import (spatial_cross_attention_sample, spatial_cr
                                       spatial_cross_attention_plan)
 from .linear import (linear_bias_act, layer_norm, quantize_rows, dequantize_rows, linear_int8, tsgemm, tsgemm_ln, tsgemm_grouped, tile_gemm, tile_gemm_dst, small_gemm, small_gemm_dst,
                      dense_auto, tsa_split, queue_mean2)
-from .int8_chain import linear_int8_chain, linear_int8_ln
+from .int8_chain import linear_int8_chain, linear_int8_ln, conv_int8_chain_nhwc, modulated_deformable_conv2d_int8_nhwc
 from .conv import conv_nhwc, conv3x3_nhwc, conv3x3_auto, conv3x3_c64, conv_int8_nhwc, stem_conv_pool
 from .image import (image_normalize_pad, padded_size, bevdet_test_augmentation, bevdet_post_transform, image_resize_plan,
                     image_resize_crop_normalize, BEVFORMER_IMAGE_PIPELINES, scaled_size, scale_lidar2img,
@@ -35,7 +35,7 @@ from .decode2d import centernet_decode, yolox_decode, box_nms
 from .lss_prepare import lss_voxel_prepare, lss_lidar_coor, bev_pool_v2_indirect
 from .calibrate import calib_state_size, calib_collect, calib_threshold
 from .bev_half import lss_depth_split, upsample_bilinear_concat_nhwc
-from .deconv import conv_transpose2d_nhwc, pack_deconv4x4s2, deconv_packed_weight
+from .deconv import conv_transpose2d_nhwc, pack_deconv4x4s2, deconv_packed_weight, conv_transpose2d_q_nhwc, quantize_deconv_weight
 from .yolox_ops import (conv_slice_nhwc, conv_slice_taps, conv_slice_packed_weight, focus_nhwc, spp_maxpool_nhwc,
                         upsample_nearest2x_nhwc, pad_channels, unpad_channels, conv_slice_q_taps, focus_nhwc_q,
                         quantize_weight_taps)
@@ -68,9 +68,9 @@ __all__ = [
     "BEVFORMER_IMAGE_PIPELINES", "scaled_size", "scale_lidar2img", "image_normalize_resize_pad",
     "spatial_cross_attention_sample", "spatial_cross_attention_projected", "spatial_cross_attention_plan", "modulated_deformable_conv2d_nhwc", "bias_act_nhwc_", "linear_bias_act", "layer_norm", "rotate_hwc", "conv_offset_nhwc", "upsample_add_nhwc_", "feat_embed_nhwc",
     "msda_pack_value", "multi_scale_deformable_attn_prepacked", "multi_scale_deformable_attn_local", "image_normalize_pad", "padded_size", "quantize_rows", "dequantize_rows", "linear_int8", "tsgemm", "tsgemm_ln", "tsgemm_grouped", "tile_gemm", "tile_gemm_dst", "small_gemm_dst", "small_gemm", "dense_auto", "tsa_split", "queue_mean2", "conv_nhwc", "conv3x3_nhwc", "conv3x3_auto", "conv3x3_c64", "conv_int8_nhwc", "bias_relu_maxpool_nhwc", "stem_conv_pool", "point_sampling", "self_attention_qkv", "refine_reference_points", "decode_boxes",
-    "linear_int8_chain", "linear_int8_ln",
+    "linear_int8_chain", "linear_int8_ln", "conv_int8_chain_nhwc", "modulated_deformable_conv2d_int8_nhwc",
     "lss_depth_split", "upsample_bilinear_concat_nhwc",
-    "conv_transpose2d_nhwc", "pack_deconv4x4s2", "deconv_packed_weight",
+    "conv_transpose2d_nhwc", "pack_deconv4x4s2", "deconv_packed_weight", "conv_transpose2d_q_nhwc", "quantize_deconv_weight",
     "conv_slice_nhwc", "conv_slice_taps", "conv_slice_packed_weight", "focus_nhwc", "spp_maxpool_nhwc",
     "upsample_nearest2x_nhwc", "pad_channels", "unpad_channels",
     "conv_slice_q_taps", "focus_nhwc_q", "quantize_weight_taps",

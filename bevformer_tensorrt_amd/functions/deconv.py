@@ -69,3 +69,63 @@ def conv_transpose2d_nhwc(x, weight, bias=None, relu=False):
     _call("bevops_deconv4x4s2_f16", x.device, _lib.F16, x.data_ptr(), wp.data_ptr(), _ptr(bias), out.data_ptr(), B, H, W,
           Cin, Cout, 4, 2, 1, int(bool(relu)))
     return out
+
+
+# ---- the INT8 flavour (the INT8 build of CenterNet, quantization.build_int8_centernet)
+
+def quantize_deconv_weight(weight, bias=None):
+    """Per-output-channel min-max quantisation of a transposed convolution's weight [Cin, Cout, 4, 4] (the per-channel
+    axis is dimension 1): -> (weight_q int8 [Cin, Cout, 4, 4], w_scales fp32 [Cout], bias fp32 [Cout]).  scale[co] =
+    amax_co / 127 in fp32 (1 for a channel of zeros), q = clamp(rne(w / scale), -127, 127), the quotient in fp32."""
+    w = weight.detach().float()
+    amax = w.abs().amax(dim=(0, 2, 3))
+    scales = torch.where(amax > 0, amax / 127.0, torch.ones_like(amax))
+    q = torch.clamp(torch.round(w / scales[None, :, None, None]), -127, 127).to(torch.int8)
+    b = w.new_zeros((w.shape[1],)) if bias is None else bias.detach().float()
+    return q.contiguous(), scales.contiguous(), b.contiguous()
+
+
+def conv_transpose2d_q_nhwc(x_q, scale_x, weight_q, w_scales, bias, relu, scale_out=None, out_dtype=torch.int8):
+    """bevops_deconv4x4s2_s8: x_q [B, Cin, H, W] channels-last int8 (real = q scale_x), weight_q int8 [Cin, Cout, 4, 4]
+    (real = q w_scales[co]; w_scales fp32 [Cout] or None), bias fp32 [Cout] or None -> act(conv_transpose2d(x, w, stride 2,
+    padding 1) + bias) [B, Cout, 2H, 2W] channels-last.  out_dtype torch.int8: requantised with scale_out,
+    q = clamp(rne(v / scale_out), -127, 127); torch.float16: one rounding (scale_out unused).  Cin % 64 == 0, Cout % 16
+    == 0 (int8 out) or % 8 (fp16 out), else BevopsError NOT_SUPPORTED.  The parity-major packed int8 weight is cached per
+    weight tensor like the fp16 one (deconv_packed_weight): never built inside a stream capture.  include/bevops.h
+    states the operation order."""
+    if not (x_q.is_cuda and x_q.dtype == torch.int8 and x_q.dim() == 4):
+        raise ValueError("conv_transpose2d_q_nhwc: x_q an int8 CUDA tensor [B, Cin, H, W]")
+    if not x_q.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError("conv_transpose2d_q_nhwc: x_q channels-last")
+    B, Cin, H, W = x_q.shape
+    if weight_q.dim() != 4 or weight_q.shape[0] != Cin or tuple(weight_q.shape[2:]) != (4, 4):
+        raise ValueError("conv_transpose2d_q_nhwc: weight_q [Cin, Cout, 4, 4] matching the input channels")
+    if weight_q.dtype != torch.int8 or weight_q.device != x_q.device:
+        raise ValueError("conv_transpose2d_q_nhwc: an int8 weight on the input's device")
+    if out_dtype not in (torch.int8, torch.float16):
+        raise ValueError("conv_transpose2d_q_nhwc: out_dtype torch.int8 or torch.float16")
+    Cout = weight_q.shape[1]
+    out8 = out_dtype == torch.int8
+    if Cin % 64 or Cout % (16 if out8 else 8):       # (before the pack, which does not care)
+        raise _lib.BevopsError("bevops_deconv4x4s2_s8: Cin % 64 == 0, Cout % 16 == 0 (int8 out) or % 8 (fp16 out)",
+                               _lib.NOT_SUPPORTED)
+
+    def scale(v, name):
+        v = float(v)
+        if not (v > 0.0 and v < float("inf")):
+            raise ValueError(f"conv_transpose2d_q_nhwc: {name} a positive finite scale, got {v}")
+        return v
+
+    sx = scale(scale_x, "scale_x")
+    so = scale(scale_out, "scale_out") if out8 else 1.0
+    for t, name in ((w_scales, "w_scales"), (bias, "bias")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != Cout or
+                              t.device != x_q.device):
+            raise ValueError(f"conv_transpose2d_q_nhwc: {name} contiguous fp32 [Cout] on the input's device")
+    wp = deconv_packed_weight(weight_q)
+    out = torch.empty((B, Cout, 2 * H, 2 * W), dtype=out_dtype, device=x_q.device, memory_format=torch.channels_last)
+    if B == 0:
+        return out
+    _call("bevops_deconv4x4s2_s8", x_q.device, x_q.data_ptr(), sx, wp.data_ptr(), _ptr(w_scales), 1.0, _ptr(bias),
+          _lib.I8 if out8 else _lib.F16, out.data_ptr(), so, B, H, W, Cin, Cout, int(bool(relu)))
+    return out

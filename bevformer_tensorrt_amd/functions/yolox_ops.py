@@ -305,11 +305,12 @@ def quantize_weight_taps(weight, bias=None, groups_in=None, groups_out=None, mul
 
 
 def conv_slice_q_taps(x_q, scale_x, w_q_taps, w_scales, bias, act, residual_q=None, scale_res=1.0, stride=1, out=None,
-                      scale_out=None, out_dtype=torch.int8):
-    """bevops_conv_slice_s8: the convolution of an int8 channel slice x_q [B, Cin, H, W] (real = q scale_x) with int8
+                      scale_out=None, out_dtype=torch.int8, res_first=False):
+    """bevops_conv_slice_s8(_ex): the convolution of an int8 channel slice x_q [B, Cin, H, W] (real = q scale_x) with int8
     taps-major weights w_q_taps [Cout, k, k, Cin] (real = q w_scales[co]; w_scales fp32 [Cout]), bias fp32 [Cout] or
     None, act in "none", "relu", "silu", the int8 identity residual_q (real = q scale_res) added BEHIND the
-    activation.  out_dtype torch.int8: requantised with scale_out, q = clamp(rne(v / scale_out), -127, 127);
+    activation -- or, with res_first=True (act "none" / "relu" and an identity, else BevopsError NOT_SUPPORTED), IN FRONT of
+    it: act(conv + bias + identity), mmdet's BasicBlock.  out_dtype torch.int8: requantised with scale_out, q = clamp(rne(v / scale_out), -127, 127);
     torch.float16: one rounding (scale_out unused).  Cin % 32 == 0, Cout % 16 == 0 (int8 out) or % 8 (fp16 out), k in
     {1, 3}, stride in {1, 2}, else BevopsError NOT_SUPPORTED.  include/bevops.h states the operation order."""
     _check_s8(x_q, "x_q")
@@ -349,11 +350,13 @@ def conv_slice_q_taps(x_q, scale_x, w_q_taps, w_scales, bias, act, residual_q=No
         if tuple(residual_q.shape) != tuple(out.shape):
             raise ValueError("conv_slice_q: the identity has the output's shape")
         rp, sr = slice_pitch(residual_q, "residual_q"), _scale(scale_res, "scale_res")
+    if res_first and (residual_q is None or act == "silu"):
+        raise _lib.BevopsError("bevops_conv_slice_s8_ex: res_first needs an identity and act none / relu", _lib.NOT_SUPPORTED)
     if B == 0:
         return out
-    _call("bevops_conv_slice_s8", x_q.device, x_q.data_ptr(), xp, sx, w_q_taps.data_ptr(), _ptr(w_scales), 1.0, _ptr(bias),
-          _ptr(residual_q), rp, sr, _lib.I8 if out8 else _lib.F16, out.data_ptr(), op, so, B, H, W, Cin, Cout, k,
-          int(stride), ACTS[act])
+    _call("bevops_conv_slice_s8_ex", x_q.device, x_q.data_ptr(), xp, sx, w_q_taps.data_ptr(), _ptr(w_scales), 1.0,
+          _ptr(bias), _ptr(residual_q), rp, sr, _lib.I8 if out8 else _lib.F16, out.data_ptr(), op, so, B, H, W, Cin, Cout, k,
+          int(stride), ACTS[act], int(bool(res_first)))
     return out
 
 

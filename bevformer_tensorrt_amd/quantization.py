@@ -1112,3 +1112,33 @@ def build_int8_yolox(Y, dev, images, calibrator="entropy", calibration_cache=Non
     model = _yi.Int8YOLOX(fp, _yi.group_scales_from(cal, num_groups), ops)
     note = {"int8_layers": model.num_int8_layers, "scale_groups": num_groups, "calibration_frames": n}
     return model, note
+
+
+def build_int8_centernet(C, dev, images, calibrator="entropy", calibration_cache=None, cfg=None, ops=None, neck="int8"):
+    """The PTQ build of the re-hosted CenterNet-R18-DCNv2 (`C` = the centernet module, or a centernet.CenterNet instance
+    whose weights to quantise -- a checkpoint loaded through checkpoint.load_centernet_state_dict; `images` = an
+    iterable of fp16 [B, 3, H, W] calibration images): the stem's pooled output int8, every BasicBlock convolution on
+    bevops_conv_slice_s8(_ex) with the identity in front of the ReLU, the head as two int8 launches, every tensor between
+    two layers int8 with one scale per tensor (centernet_int8.py, design/centernet_int8.md).  neck="int8": the DCNv2 packs
+    on the int8 channels-last block and the up-sampling layers on bevops_deconv4x4s2_s8 (the reference's implicit INT8
+    build); neck="fp16": the neck stays the fp16 CTResNetNeck (the reference's explicit-quantisation config).  The
+    calibration runs the fp16 fast path and collects one site per tensor; `calibrator` names any of CALIBRATORS.
+    calibration_cache: a path -- an existing cache is loaded INSTEAD of running frames, otherwise the collected
+    statistics are saved there (the format of save_calibration / load_calibration; one cache serves both neck modes).
+    Returns (model, note): model has forward / get_bboxes / prepare / cfg like CenterNet, and CenterNetRunner captures it
+    unchanged."""
+    from . import centernet_int8 as _ci
+    fp = C if isinstance(C, torch.nn.Module) else C.CenterNet(cfg)
+    fp = fp.to(dev, torch.float16)
+    cal = get_calibrator(calibrator)()
+    n = 0
+    if calibration_cache is not None and os.path.exists(calibration_cache):
+        _ci.load_calibration(cal, calibration_cache, dev if isinstance(cal, _DeviceCalibrator) else None)
+    else:
+        n = _ci.calibrate(fp, images, cal, ops)
+        if calibration_cache is not None:
+            _ci.save_calibration(cal, calibration_cache, {"model": "centernet", "sites": len(_ci.all_sites(fp)), "frames": n})
+    model = _ci.Int8CenterNet(fp, _ci.scales_from(cal, _ci.build_plan(fp, neck).sites), ops, neck)
+    note = {"int8_layers": model.num_int8_layers, "scale_sites": len(model.plan.sites), "calibration_frames": n,
+            "neck": model.neck_note}
+    return model, note

@@ -131,6 +131,10 @@ SIGNATURES = {
     "bevops_upsample_nearest2x_nhwc": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p]),
     "bevops_conv_slice_s8": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
                                      c_float, c_int, c_void_p, c_int, c_float] + [c_int] * 8 + [c_void_p]),
+    "bevops_conv_slice_s8_ex": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
+                                        c_float, c_int, c_void_p, c_int, c_float] + [c_int] * 9 + [c_void_p]),
+    "bevops_deconv4x4s2_s8": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_float] +
+                              [c_int] * 6 + [c_void_p]),
     "bevops_focus_nhwc_q": (c_int, [c_void_p, c_float, c_void_p] + [c_int] * 4 + [c_void_p]),
     "bevops_spp_maxpool_nhwc_s8": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 8 + [c_void_p]),
     "bevops_upsample_nearest2x_nhwc_s8": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p]),

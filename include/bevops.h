@@ -583,6 +583,38 @@ int bevops_conv_slice_s8(const void *x_q, int x_pitch, float scale_a, const void
                          float scale_w, const float *bias, const void *residual_q, int res_pitch, float scale_res,
                          int out_dtype, void *out, int out_pitch, float scale_out, int B, int H, int W, int Cin, int Cout,
                          int ksize, int stride, int act, void *stream);
+/* bevops_conv_slice_s8 with the identity IN FRONT of the activation when res_first != 0 (mmdet's BasicBlock,
+ * relu(conv2(t) + identity); the INT8 build of CenterNet): the epilogue order becomes
+ *   v = fma((float)sum, sc, bias[co]);  v = fma((float)res_q, scale_res, v);  v = act(v);  requantise / round
+ * -- the same fp32 operations, the identity's fma moved.  res_first == 0 is bevops_conv_slice_s8 bit for bit (that
+ * entry forwards here with 0).  res_first with act == 2 (SiLU) or without residual_q: BEVOPS_NOT_SUPPORTED (answered
+ * after the BAD_PARAM checks and the channel-count checks of bevops_conv_slice_s8).  Everything else as there. */
+int bevops_conv_slice_s8_ex(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps, const float *w_scales,
+                            float scale_w, const float *bias, const void *residual_q, int res_pitch, float scale_res,
+                            int out_dtype, void *out, int out_pitch, float scale_out, int B, int H, int W, int Cin, int Cout,
+                            int ksize, int stride, int act, int res_first, void *stream);
+/* bevops_deconv4x4s2_f16's INT8 sibling (csrc/deconv_s8.hip; the up-sampling layers of the INT8 build of CenterNet):
+ * ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1) + bias + ReLU on channels-last INT8 activations as four implicit
+ * GEMMs on the int8 matrix cores, one per output parity, sums exact in int32:
+ *   sum[b, 2y+py, 2x+px, co] = sum_{dy,dx in {0,1}} sum_ci x_q[b, y-1+py+dy, x-1+px+dx, ci] w_q[ci, co, 3-py-2dy, 3-px-2dx]
+ * and then bevops_conv_slice_s8's epilogue without an identity, every step ONE fp32 operation in exactly this order
+ * (s_aw = scale_a * scale_w and inv = 1.f / scale_out computed once on the host in fp32):
+ *   sc = s_aw * w_scales[co]                (sc = s_aw when w_scales is NULL)
+ *   v  = fma((float)sum, sc, bias[co])      ((float) exact for |sum| <= 2^24; bias 0 when NULL)
+ *   v  = max(v, 0)                          with relu
+ *   out_dtype BEVOPS_I8:  q = min(max(rne(v * inv), -127), 127)      BEVOPS_F16: one rounding of v to binary16
+ * A NaN v leaves as -127, +inf as 127, -inf as -127 (int8); as fp16 they go through as they are.
+ * x_q int8 [B, H, W, Cin]; out [B, 2H, 2W, Cout] int8 or fp16; packed_w_q the int8 weight [Cin, Cout, 4, 4] in the
+ * parity-major order of bevops_deconv4x4s2_f16, [parity 2 py + px][Cout][dy][dx][Cin]; w_scales fp32 [Cout] (the
+ * per-channel axis of a transposed convolution's weight is dimension 1), optional; bias fp32 [Cout], optional.
+ * Cin % 64 == 0 (a 64-byte k-step never straddles two taps), Cout % 16 == 0 for int8 out, % 8 for fp16 out, out_dtype
+ * outside {BEVOPS_I8, BEVOPS_F16}, B H W Cin or the packed weight (16 Cin Cout) of 0xFFFFFF00 bytes or more:
+ * BEVOPS_NOT_SUPPORTED.  NULL or not 16-byte aligned x_q / packed_w_q / out, bias / w_scales not 4-byte aligned,
+ * non-positive sizes, a scale in use (scale_a, scale_w; scale_out with int8 out) that is not positive and finite:
+ * BEVOPS_BAD_PARAM.  B == 0: BEVOPS_SUCCESS without a launch.  (bevops_deconv4x4s2_f16 keeps refusing BEVOPS_I8.) */
+int bevops_deconv4x4s2_s8(const void *x_q, float scale_a, const void *packed_w_q, const float *w_scales, float scale_w,
+                          const float *bias, int out_dtype, void *out, float scale_out, int B, int H, int W, int Cin,
+                          int Cout, int relu, void *stream);
 /* The data-movement layers of YOLOX on INT8 slices (csrc/yolox.hip): 16-byte vectors of 16 channels, pitches multiples
  * of 16, C % 16 == 0; statuses as the fp16 entries above (a scale that is not positive and finite: BEVOPS_BAD_PARAM).
  * bevops_focus_nhwc_q: bevops_focus_nhwc from the planar fp16 image to an int8 slice of 32 channels,
