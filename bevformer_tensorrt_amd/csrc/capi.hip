@@ -138,6 +138,7 @@ const Entry kTable[] = {
     {"bevops_mdconv_forward_int8_nhwc", (void *)&bevops_mdconv_forward_int8_nhwc},
     {"bevops_image_normalize_pad", (void *)&bevops_image_normalize_pad},
     {"bevops_image_normalize_resize_pad", (void *)&bevops_image_normalize_resize_pad},
+    {"bevops_image_letterbox", (void *)&bevops_image_letterbox},
     {"bevops_image_resize_plan_size", (void *)&bevops_image_resize_plan_size},
     {"bevops_image_resize_plan_build", (void *)&bevops_image_resize_plan_build},
     {"bevops_image_resize_crop_normalize", (void *)&bevops_image_resize_crop_normalize},

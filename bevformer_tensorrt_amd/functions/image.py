@@ -3,6 +3,7 @@ reference's NormalizeMultiviewImage + PadMultiViewImage(size_divisor=32) + Defau
 (configs/bevformer/bevformer_base.py:11,228-231) as one HIP pass over the raw images."""
 import ctypes
 
+import numpy as np
 import torch
 
 from ..utils import lib as _lib
@@ -236,3 +237,88 @@ def image_resize_crop_normalize(images, plan, flip=False, mean=None, std=None, t
             int(bool(channels_last)), _lib.current_stream_ptr(images.device))
     _lib.check(st, "bevops_image_resize_crop_normalize")
     return out if canvas is None else (out, canvas)
+
+
+# --------------------------------------------------------------------------- 2-D detectors: keep-ratio resize + paste + normalise
+# (csrc/image_letterbox.hip, design/letterbox.md): mmdet's test pipelines of the two 2-D detectors.  YOLOX
+# (configs/yolox/yolox_x_8x8_300e_coco.py:75-92) resizes the uint8 image (arith 0: cv::resize's 8-bit fixed point), pads
+# with 114 at the bottom / right and only casts; CenterNet (configs/centernet/centernet_resnet18_dcnv2_140e_coco.py:
+# 38-41,69-110) resizes the float32 image (arith 1), pastes it CENTRED into a zero canvas and normalises last.
+DETECT2D_IMAGE_PIPELINES = {
+    "yolox": dict(arith=0, mean=[0.0, 0.0, 0.0], std=[1.0, 1.0, 1.0], to_rgb=False, pad=[114.0, 114.0, 114.0],
+                  img_scale=(640, 640)),
+    "centernet": dict(arith=1, mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True,
+                      pad=[0.0, 0.0, 0.0], img_scale=(640, 640)),
+}
+
+
+def keep_ratio_size(H0, W0, img_scale=(640, 640)):
+    """mmcv.rescale_size for a (long edge, short edge) bound -> (Hs, Ws): the largest factor that keeps the long side
+    within max(img_scale) and the short side within min(img_scale), each size int(x * s + 0.5) in Python floats."""
+    s = min(max(img_scale) / max(H0, W0), min(img_scale) / min(H0, W0))
+    return int(H0 * s + 0.5), int(W0 * s + 0.5)
+
+
+def _geometry(H0, W0, size, canvas, offset, **extra):
+    (Hs, Ws), (Hp, Wp) = size, canvas
+    scale = np.array([Ws / W0, Hs / H0, Ws / W0, Hs / H0], dtype=np.float32)       # mmcv.imresize(return_scale=True)
+    return dict(ori_shape=(int(H0), int(W0), 3), img_shape=(Hs, Ws, 3), pad_shape=(Hp, Wp, 3), batch_input_shape=(Hp, Wp),
+                size=(Hs, Ws), offset=(int(offset[0]), int(offset[1])), scale_factor=scale, **extra)
+
+
+def yolox_test_geometry(H0, W0, img_scale=(640, 640)):
+    """What YOLOX's test pipeline does to an H0 x W0 image: Resize(keep_ratio) to `size` = (Hs, Ws), the square
+    max(Hs, Ws) canvas padded at the bottom / right (`offset` (0, 0)).  The dict is an img_metas entry that
+    yolox_get_bboxes accepts as is (`scale_factor` float32 [w, h, w, h], `img_shape`, `pad_shape`)."""
+    Hs, Ws = keep_ratio_size(H0, W0, img_scale)
+    side = max(Hs, Ws)
+    return _geometry(H0, W0, (Hs, Ws), (side, side), (0, 0))
+
+
+def centernet_test_geometry(H0, W0, img_scale=(640, 640), pad_or=31, add_pix=1):
+    """What CenterNet's test pipeline does to an H0 x W0 image: Resize(keep_ratio), RandomCenterCropPad(test_mode,
+    ("logical_or", pad_or), add_pix): the resized image pasted CENTRED into a ((Hs | pad_or) + add_pix, (Ws | pad_or) +
+    add_pix) canvas, `border` = float32 [top, bottom, left, right] of the paste, then Pad(pad_to_square) at the bottom /
+    right.  The dict is an img_metas entry that centernet_get_bboxes accepts as is."""
+    Hs, Ws = keep_ratio_size(H0, W0, img_scale)
+    th, tw = (Hs | pad_or) + add_pix, (Ws | pad_or) + add_pix
+    cy, cx = Hs // 2, Ws // 2
+    top, bottom = cy - max(0, cy - th // 2), min(cy + th // 2, Hs) - cy
+    left, right = cx - max(0, cx - tw // 2), min(cx + tw // 2, Ws) - cx
+    oy, ox = th // 2 - top, tw // 2 - left
+    border = np.array([oy, th // 2 + bottom, ox, tw // 2 + right], dtype=np.float32)
+    side = max(th, tw)
+    return _geometry(H0, W0, (Hs, Ws), (side, side), (oy, ox), border=border, crop_shape=(th, tw))
+
+
+def image_letterbox(images, geometry, pipeline, dtype=torch.float16, channels_last=False, out=None):
+    """images [N, H0, W0, 3] uint8 on the GPU (BGR, as cv2 loads them) -> [N, 3, Hp, Wp] `dtype` (memory format
+    channels_last if asked): resized to geometry["size"], pasted at geometry["offset"] into the constant canvas
+    geometry["pad_shape"], normalised -- one launch, no allocation when `out` is given.  geometry: yolox_test_geometry /
+    centernet_test_geometry (or any dict with those three keys); pipeline: a name or an entry of
+    DETECT2D_IMAGE_PIPELINES (arith, mean, std, to_rgb, pad; include/bevops.h: bevops_image_letterbox)."""
+    assert images.is_cuda and images.dim() == 4 and images.shape[-1] == 3
+    if images.dtype != torch.uint8:
+        raise TypeError("images must be uint8")
+    p = DETECT2D_IMAGE_PIPELINES[pipeline] if isinstance(pipeline, str) else pipeline
+    N, H0, W0, _ = images.shape
+    if "ori_shape" in geometry and tuple(geometry["ori_shape"][:2]) != (H0, W0):
+        raise ValueError(f"the geometry is for {tuple(geometry['ori_shape'][:2])} images, got {(H0, W0)}")
+    (Hs, Ws), (Hp, Wp), (oy, ox) = geometry["size"], geometry["pad_shape"][:2], geometry["offset"]
+    images = images.contiguous()
+    if out is not None and (tuple(out.shape) != (N, 3, Hp, Wp) or out.device != images.device or not (
+            out.is_contiguous(memory_format=torch.channels_last) if channels_last else out.is_contiguous())):
+        raise ValueError(f"out must be a dense [N, 3, {Hp}, {Wp}] tensor on the GPU in the requested layout")
+    if out is None:
+        out = torch.empty((N, 3, Hp, Wp), dtype=dtype, device=images.device,
+                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    D3 = ctypes.c_double * 3
+    pad, m, s = (D3(*[float(v) for v in p[k]]) for k in ("pad", "mean", "std"))
+    handle = _lib.load_library()
+    with torch.cuda.device(images.device):
+        st = handle.bevops_image_letterbox(
+            int(p["arith"]), images.data_ptr(), _lib.torch_dtype_code(out), out.data_ptr(), N, H0, W0, int(Hs), int(Ws),
+            int(Hp), int(Wp), int(oy), int(ox), pad, m, s, int(bool(p["to_rgb"])), int(bool(channels_last)),
+            _lib.current_stream_ptr(images.device))
+    _lib.check(st, "bevops_image_letterbox")
+    return out

@@ -104,6 +104,8 @@ SIGNATURES = {
     "bevops_image_normalize_resize_pad": (c_int, [c_int, c_void_p, c_int, c_void_p] + [c_int] * 7 +
                                           [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_int, c_int,
                                            c_void_p]),
+    "bevops_image_letterbox": (c_int, [c_int, c_void_p, c_int, c_void_p] + [c_int] * 9 +
+                               [ctypes.POINTER(ctypes.c_double)] * 3 + [c_int, c_int, c_void_p]),
     "bevops_image_resize_plan_size": (c_size_t, [c_int] * 8),
     "bevops_image_resize_plan_build": (c_int, [c_int] * 8 + [c_void_p, c_size_t]),
     "bevops_image_resize_crop_normalize": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p] + [c_int] * 10 +

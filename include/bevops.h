@@ -765,6 +765,40 @@ int bevops_image_resize_crop_normalize(const void *images, const void *plan_dev,
 int bevops_image_normalize_resize_pad(int in_dtype, const void *images, int out_dtype, void *output, int N,
                                       int H0, int W0, int Hs, int Ws, int Hp, int Wp, const double *mean_host,
                                       const double *std_host, int to_rgb, int channels_last, void *stream);
+/* Camera front end of the two 2-D detectors (design/letterbox.md; not a plugin): mmdet's test pipelines of YOLOX
+ * (configs/yolox/yolox_x_8x8_300e_coco.py:75-92: Resize(keep_ratio) -> Pad(pad_to_square, 114)) and CenterNet
+ * (configs/centernet/centernet_resnet18_dcnv2_140e_coco.py:69-110: Resize(keep_ratio) -> RandomCenterCropPad(test_mode,
+ * logical_or 31, a CENTRED paste) -> Pad -> Normalize) in ONE launch: resize, paste at an offset into a constant canvas,
+ * normalise.  `images` [N, H0, W0, 3] BEVOPS_U8 (BGR as loaded) -> bilinear resize to [Hs, Ws] -> rows oy .. oy + Hs and
+ * columns ox .. ox + Ws of `output` [N, 3, Hp, Wp] (channels_last: [N, Hp, Wp, 3]) BEVOPS_F16 or BEVOPS_F32; every other
+ * element is the pad value of its channel.  pad_host: 3 doubles, raw 0 .. 255 domain, in the SOURCE channel order.
+ * The resized value and the pad value are normalised AFTER the resize exactly as bevops_image_normalize_pad does it:
+ * optional BGR -> RGB swap, fl(x - float32(mean)), fl(. * float32(1 / float64(std))); the fp16 output is its own
+ * rounding of the fp32 value.
+ * Tap positions and clamps of both arithmetics are bevops_image_normalize_resize_pad's (scale = 1 / (double(out) /
+ * double(in)), f = float32((d + 0.5) * scale - 0.5) in double with one rounding, i = floor(f), f -= i, both clamps, the
+ * HORIZONTAL pass first).
+ * arith 0 -- cv::resize's 8-bit INTER_LINEAR in fixed point (YOLOX resizes uint8): per axis a0 = rint(fl(fl(1 - f) *
+ *   2048)), a1 = rint(fl(f * 2048)) (float32 products, half to even); horizontal D = S[i] * a0 + S[i1] * a1 (int32);
+ *   vertical R = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2, in 0 .. 255; H0 == 2 * Hs AND
+ *   W0 == 2 * Ws takes the area form (a + b + c + d + 2) >> 2; R -> float32 exactly, then normalised.
+ * arith 1 -- cv::resize's float32 INTER_LINEAR (CenterNet loads to_float32): source -> float32 exactly, one pass =
+ *   fl(fl(a * w0) + fl(b * w1)) with w0 = fl(1 - f), w1 = f, never contracted; the 2 : 1 area form is
+ *   fl(fl(fl(fl(a + b) + c) + d) * 0.25f); then normalised (bevops_image_normalize_resize_pad normalises every tap
+ *   BEFORE the resize: the order is observable).
+ * Parity against cv2 / mmcv / mmdet themselves is UNPINNED; the contract is the numpy restatement of this order in
+ * tests/util_letterbox.py, bit for bit.  One launch, no workspace, no allocation, no synchronisation, capturable;
+ * coefficients are evaluated on the device.
+ * DOMAIN: N in 1 .. 65535; sizes in 1 .. 2^20; 0 <= oy, oy + Hs <= Hp, 0 <= ox, ox + Ws <= Wp; the LDS footprint of one
+ * 64 x 8 tile of the padded output -- its uint8 source window (+ 6 bytes a row) and the horizontal-pass result of that
+ * window's rows (arith 0: 384 bytes a row, arith 1: 768; none in the area form) -- at most 64 KiB: every per-axis ratio
+ * in / out from 1/2 to 4 is inside whatever the image size; larger ratios are inside while the images are small.
+ * BAD_PARAM: null pointers, non-positive sizes, a paste outside the canvas, std <= 0, misaligned output;
+ * NOT_SUPPORTED: other dtypes, another arith, geometry outside the domain; every status is returned before any device
+ * call. */
+int bevops_image_letterbox(int arith, const void *images, int out_dtype, void *output, int N, int H0, int W0, int Hs,
+                           int Ws, int Hp, int Wp, int oy, int ox, const double *pad_host, const double *mean_host,
+                           const double *std_host, int to_rgb, int channels_last, void *stream);
 /* The MSDA call in two halves, for callers that sample ONE value tensor several times or want the
  * re-layout off their critical path (not a reference plugin: the plugin's enqueue is
  * bevops_msda_forward[_ws], which does both).  `packed` = the padded head-major form of `value`
