@@ -357,6 +357,48 @@ class DCNv2Pack(nn.Module):
                                                          1, 1, relu=relu, offset_mask_nhwc=out)
 
 
+# The first bottleneck of a ResNet stage: relu(conv3(h) + downsample(x)) as ONE GEMM over K = K1 + K2 with two activation
+# sources (ops.gemm2, design/dense.md "Downsample inside conv3") -- the identity tensor is neither written nor read back,
+# one launch instead of two, one rounding instead of two (the result differs from the pair's in the last bit).
+# BEVOPS_FUSED_DOWNSAMPLE=0 / _FUSED_DOWNSAMPLE["enabled"] = False: the two launches (A/B).  _FUSED_DOWNSAMPLE_SHAPES: the
+# (K1, K2, stride) classes that passed the keep rule on MI355X (worst fused round below the best round of the pair,
+# profiles/two_source/two_source_time.jsonl); any other first block keeps its two launches.
+_FUSED_DOWNSAMPLE = {"enabled": os.environ.get("BEVOPS_FUSED_DOWNSAMPLE", "1") != "0"}
+_FUSED_DOWNSAMPLE_SHAPES = {(64, 64, 1), (128, 256, 2), (256, 512, 2), (512, 1024, 2)}
+
+
+def _two_source_ok(ops, blk, x):
+    """The fused route's predicate: a first block with a downsample, fp16 channels-last on the GPU, both convolutions
+    plain fp16 nn.Conv2d 1x1 layers (no LinearQ inside), no calibration pass (it collects the identity), the switches,
+    an operator set with the entry, and a shape class that passed the keep rule."""
+    ds, c3 = blk.downsample, blk.conv3
+    if ds is None or not (_FUSED_DOWNSAMPLE["enabled"] and _R3["enabled"] and _FUSED_LINEAR["enabled"]) \
+            or getattr(ops, "gemm2", None) is None or getattr(blk, "chain_cal", None) is not None:
+        return False
+    if type(ds) is not nn.Conv2d or type(c3) is not nn.Conv2d or hasattr(ds, "lin") or hasattr(c3, "lin") \
+            or ds.bias is None or c3.bias is None or ds.weight.dtype != torch.float16 or c3.weight.dtype != torch.float16 \
+            or ds.kernel_size != (1, 1) or c3.kernel_size != (1, 1) or c3.stride != (1, 1) or ds.stride[0] != ds.stride[1]:
+        return False
+    if x.dtype != torch.float16 or not x.is_cuda or x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        return False
+    return (c3.in_channels, ds.in_channels, ds.stride[0]) in _FUSED_DOWNSAMPLE_SHAPES
+
+
+def _stacked_pair(blk):
+    """([W3 | Wd] as [N, K1 + K2], b3 + bd) of a first block, cached on it and keyed on the parameters' versions and
+    storage (as _merged_pair caches its stacked weights)."""
+    ds, c3 = blk.downsample, blk.conv3
+    key = _versions(c3.weight, ds.weight, c3.bias, ds.bias)
+    hit = getattr(blk, "_w3d", None)
+    if hit is None or hit[0] != key:
+        n = c3.out_channels
+        w = torch.cat([c3.weight.detach().reshape(n, -1), ds.weight.detach().reshape(n, -1)], dim=1).contiguous()
+        b = (c3.bias.detach().float() + ds.bias.detach().float()).to(c3.bias.dtype).contiguous()
+        hit = (key, w, b)
+        blk._w3d = hit
+    return hit[1], hit[2]
+
+
 class Bottleneck(nn.Module):
     """ResNet bottleneck (det2trt/models/backbones/resnet.py:106-260), BN folded.  style "caffe": the
     stride sits on the first 1x1, "pytorch": on the 3x3 (resnet.py:163-170)."""
@@ -375,7 +417,22 @@ class Bottleneck(nn.Module):
         out = F.relu(self.conv2(out), inplace=True)
         return F.relu(self.conv3(out) + idt, inplace=True)
 
+    def _hidden_nhwc(self, x, ops):
+        out = _conv1x1_nhwc(ops, x, self.conv1, True)
+        if isinstance(self.conv2, DCNv2Pack):
+            return self.conv2.forward_nhwc(out, True)
+        return _conv_nhwc(ops, out, self.conv2, True)
+
     def forward_nhwc(self, x, ops):
+        if _two_source_ok(ops, self, x):
+            # relu(conv3(h) + downsample(x)) as one two-source GEMM; outside the entry's domain: the pair, on the same h
+            h = self._hidden_nhwc(x, ops)
+            w, b = _stacked_pair(self)
+            n, _, ho, wo = h.shape
+            y = _or_none(ops.gemm2, _rows(h), x, w, b, self.downsample.stride[0], True)
+            if y is not None:
+                return _from_rows(y, n, ho, wo)
+            return _conv1x1_nhwc(ops, h, self.conv3, True, residual=_conv1x1_nhwc(ops, x, self.downsample, False))
         idt = x if self.downsample is None else _conv1x1_nhwc(ops, x, self.downsample, False)
         out = _conv1x1_nhwc(ops, x, self.conv1, True)
         cal = getattr(self, "chain_cal", None)     # calibration of the INT8 engine's activation chain

@@ -111,6 +111,7 @@ const Entry kTable[] = {
     {"bevops_linear_int8_fused", (void *)&bevops_linear_int8_fused},
     {"bevops_tile_gemm_f16", (void *)&bevops_tile_gemm_f16},
     {"bevops_tile_gemm_f16_dst", (void *)&bevops_tile_gemm_f16_dst},
+    {"bevops_gemm2_f16", (void *)&bevops_gemm2_f16},
     {"bevops_small_gemm_f16_dst", (void *)&bevops_small_gemm_f16_dst},
     {"bevops_small_gemm_f16", (void *)&bevops_small_gemm_f16},
     {"bevops_conv_tile_f16", (void *)&bevops_conv_tile_f16},

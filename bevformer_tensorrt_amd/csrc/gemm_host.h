@@ -69,6 +69,41 @@ inline int gemm_dst_table(GemmDstTab &tab, const bevops_gemm_dst *dst, int num_d
   return BEVOPS_SUCCESS;
 }
 
+// bevops_gemm2_f16: one accumulation over two activation sources, as the entry received it.  a2 is a channels-last
+// [B, H, W, k2] tensor whose row m is pixel (b, stride ho, stride wo), m = (b ho_n + ho) wo_n + wo.
+struct Gemm2Call {
+  const void *a1, *a2, *w, *bias;
+  void *out;
+  long long m;
+  int n, k1, k2, B, H, W, stride;
+  int ho, wo;   // filled by gemm2_check
+  int relu;
+  hipStream_t st;
+};
+
+// The entry's checks in their order (no device call): null / sign, domain, geometry, alignment, 32-bit byte ranges.
+inline int gemm2_check(Gemm2Call &g) {
+  if (!g.a1 || !g.a2 || !g.w || !g.out || g.m <= 0 || g.n <= 0 || g.k1 <= 0 || g.k2 <= 0 || g.B <= 0 || g.H <= 0 || g.W <= 0 ||
+      g.stride <= 0)
+    return BEVOPS_BAD_PARAM;
+  if (g.k1 % 64 != 0 || g.k2 % 64 != 0 || g.n % 8 != 0 || g.stride > 2) return BEVOPS_NOT_SUPPORTED;
+  g.ho = (g.H - 1) / g.stride + 1;
+  g.wo = (g.W - 1) / g.stride + 1;
+  if (g.m != (long long)g.B * g.ho * g.wo) return BEVOPS_BAD_PARAM;
+  if (misaligned(g.a1, 15u) || misaligned(g.a2, 15u) || misaligned(g.w, 15u) || misaligned(g.out, 15u) ||
+      (g.bias && misaligned(g.bias, 15u)))
+    return BEVOPS_BAD_PARAM;
+  if (g.m > 0x7fffffffLL || gemm_over_limit((unsigned long long)g.m, g.k1, 2) ||
+      gemm_over_limit((unsigned long long)g.B * g.H * g.W, g.k2, 2) || gemm_over_limit((unsigned long long)g.n, g.k1 + g.k2, 2) ||
+      (long long)g.k1 + g.k2 > 0x7fffffffLL / 4)
+    return BEVOPS_NOT_SUPPORTED;
+  return BEVOPS_SUCCESS;
+}
+
+// tsgemm.hip: the weight-stationary kernel with a second row source -- its domain, and the launch of a checked call
+bool tsgemm_ws2_in_domain(const Gemm2Call &g);
+int tsgemm_ws2_launch(const Gemm2Call &g);
+
 // Kernels instantiated per k / 64: returns f(std::integral_constant<int, S>) for S == steps in 1 .. MAX, and
 // BEVOPS_NOT_SUPPORTED for any other step count.
 template <class F, int... I>

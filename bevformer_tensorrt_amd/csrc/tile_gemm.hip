@@ -104,8 +104,19 @@ constexpr int tile_lds_bytes(int tm) {
 // indexed load would be a vector load behind the k-loop's requests).  Everything in front of the stores is the code of
 // the plain launch: an element's sum, bias, identity and rounding do not depend on where it is stored.
 
-template <int MODE, bool OUT8, int NI, bool CONV, bool RES8, bool DST>
-__device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const GemmDstTab &d) {
+// SRC2 (bevops_gemm2_f16; F16, NI == 2): the k range [0, src2.k1) comes from p.a, rows of src2.k1 values, the rest from a
+// second activation tensor -- channels-last pixels of K - k1 channels, output row m at pixel (b, s yo, s xo): the row map
+// of the convolution mode at ksize 1 (p.conv_* carry its geometry).  k1 is a multiple of a step, so the source of a step
+// is block-uniform: its descriptor is chosen by scalar selects, the loads and everything behind them are the plain
+// launch's -- the bits of the plain launch on the materialised [a | rows of a2].
+struct TileSrc2 {
+  const void *a2;
+  unsigned a2_bytes;
+  int k1;
+};
+
+template <int MODE, bool OUT8, int NI, bool CONV, bool RES8, bool DST, bool SRC2 = false>
+__device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const GemmDstTab &d, const TileSrc2 &src2 = TileSrc2{}) {
   constexpr int MJ = 2;                          // 32-row MFMA blocks per wave
   constexpr int KB = 64;                         // bytes of k per row and step
   constexpr int kTN = 64 * NI;
@@ -165,8 +176,21 @@ __device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const GemmDstT
     place(m0 + r0, a_off0, tapmask0);
     place(m0 + r1, a_off1, tapmask1);
   } else {
-    a_off0 = m0 + r0 < M ? (unsigned)(((size_t)(m0 + r0) * K + kce) * kAB) : kGemmOob;
-    a_off1 = m0 + r1 < M ? (unsigned)(((size_t)(m0 + r1) * K + kce) * kAB) : kGemmOob;
+    const int ka = SRC2 ? src2.k1 : K;          // values per row of p.a
+    a_off0 = m0 + r0 < M ? (unsigned)(((size_t)(m0 + r0) * ka + kce) * kAB) : kGemmOob;
+    a_off1 = m0 + r1 < M ? (unsigned)(((size_t)(m0 + r1) * ka + kce) * kAB) : kGemmOob;
+  }
+  unsigned b_off0 = kGemmOob, b_off1 = kGemmOob;   // SRC2: this thread's two rows in the second source
+  if constexpr (SRC2) {
+    auto place2 = [&](int m) {
+      if (m >= M) return kGemmOob;
+      const int per = p.conv_hout * p.conv_wout;
+      const int b = m / per, pix = m - b * per;
+      const int yo = pix / p.conv_wout, xo = pix - yo * p.conv_wout;
+      return (unsigned)((((size_t)b * p.conv_hin + yo * p.conv_s) * p.conv_win + xo * p.conv_s) * (K - src2.k1) + kce) * kAB;
+    };
+    b_off0 = place2(m0 + r0);
+    b_off1 = place2(m0 + r1);
   }
   int g_tap = 0, g_c = 0;                      // conv mode: the (tap, channel) position of the NEXT gload
   const unsigned w_off0 = n0 + r0 < N ? (unsigned)(((size_t)(n0 + r0) * K + kce) * kWB) : kGemmOob;
@@ -194,6 +218,13 @@ __device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const GemmDstT
       }
       g_c += kStepK;
       if (g_c >= cin) { g_c = 0; ++g_tap; }
+    } else if constexpr (SRC2) {
+      const bool second = ks >= src2.k1;       // block-uniform
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<void *>(second ? src2.a2 : p.a), 0, second ? src2.a2_bytes : p.a_bytes, 0x00020000);
+      const int soff = (second ? ks - src2.k1 : ks) * kAB;
+      ra0[S][0] = bload(rs, kok ? (second ? b_off0 : a_off0) : kGemmOob, soff);
+      ra1[S][0] = bload(rs, kok ? (second ? b_off1 : a_off1) : kGemmOob, soff);
     } else {
 #pragma unroll
       for (int h = 0; h < kAV; ++h) {
@@ -437,6 +468,10 @@ __global__ __launch_bounds__(256, 3) void tile_gemm_dst_kernel(TileArgs p, GemmD
   tile_gemm_body<kF16, false, 2, false, false, true>(p, d);
 }
 
+__global__ __launch_bounds__(256, 3) void tile_gemm_src2_kernel(TileArgs p, TileSrc2 src2) {
+  tile_gemm_body<kF16, false, 2, false, false, false, true>(p, GemmDstTab{}, src2);
+}
+
 struct ConvGeom { int cin = 0, hin = 0, win = 0, hout = 0, wout = 0, stride = 1, ks = 1; size_t in_elems = 0; };
 
 
@@ -579,6 +614,25 @@ extern "C" int bevops_tile_gemm_f16_dst(const void *x, const void *weight, const
   dim3 grid;
   if (!tile_plan<kF16>(p, grid, c, ConvGeom(), (unsigned)((unsigned long long)M * K * 2))) return BEVOPS_NOT_SUPPORTED;
   hipLaunchKernelGGL(tile_gemm_dst_kernel, grid, dim3(256), 0, c.st, p, tab);
+  return launch_status();
+}
+
+// One accumulation over two activation sources (include/bevops.h).  K1 + K2 <= 256 with whole 256-column chunks runs on
+// the weight-stationary kernel of tsgemm.hip, everything else here; the two families give the same bits.
+extern "C" int bevops_gemm2_f16(const void *a1, const void *a2, const void *weight, const void *bias, void *out, long long M,
+                                int N, int K1, int K2, int a2_B, int a2_H, int a2_W, int a2_stride, int relu, void *stream) {
+  Gemm2Call g{a1, a2, weight, bias, out, M, N, K1, K2, a2_B, a2_H, a2_W, a2_stride, 0, 0, relu, static_cast<hipStream_t>(stream)};
+  const int rc = gemm2_check(g);
+  if (rc != BEVOPS_SUCCESS) return rc;
+  if (tsgemm_ws2_in_domain(g)) return tsgemm_ws2_launch(g);
+  const GemmCallS8 c = gemm_call_f16(a1, weight, bias, nullptr, out, M, N, K1 + K2, relu, stream);
+  ConvGeom cg;   // carries the second source's row map only: the kernel is not in convolution mode
+  cg.hin = a2_H; cg.win = a2_W; cg.hout = g.ho; cg.wout = g.wo; cg.stride = a2_stride;
+  TileArgs p;
+  dim3 grid;
+  if (!tile_plan<kF16>(p, grid, c, cg, (unsigned)((unsigned long long)M * K1 * 2))) return BEVOPS_NOT_SUPPORTED;
+  const TileSrc2 src2{a2, (unsigned)((unsigned long long)a2_B * a2_H * a2_W * K2 * 2), K1};
+  hipLaunchKernelGGL(tile_gemm_src2_kernel, grid, dim3(256), 0, c.st, p, src2);
   return launch_status();
 }
 

@@ -577,13 +577,25 @@ constexpr int kWsStep = kWsRows * 128;           // one 64-k sub-image of a tile
 constexpr int kWsEpi = kWsRows * kTsEpiStride;   // fp32 staging of a 128-column half (33 KB), at the start of LDS
 constexpr int ws_lds(int ks) { return kWsEpi + kWsBufs * ks * kWsStep; }   // 129 KB at K = 256
 
-template <int EPI, int KS, bool GRP>
+// KS2 > 0 (EPI 0, bevops_gemm2_f16): the last KS2 of a tile's KS sub-images come from a second activation tensor --
+// channels-last pixels of 64 KS2 channels, output row m at pixel (b, s yo, s xo) -- and x holds rows of 64 (KS - KS2)
+// values.  A wave still issues exactly KS DMA instructions per tile, in the same order, each through the descriptor of its
+// source: the counted waits, the ring and the multiply are the plain kernel's, and so are the bits on the materialised
+// [x | rows of x2] (k ascending: source 1, then source 2).
+struct TsSrc2 {
+  const __half *x2;
+  unsigned bytes;                          // size of the second tensor
+  int hin, win, hout, wout, stride;
+};
+
+template <int EPI, int KS, bool GRP, int KS2 = 0>
 __device__ __forceinline__ void tsgemm_ws_body(const __half *__restrict__ x, const __half *__restrict__ w,
                                                const __half *__restrict__ bias, const __half *__restrict__ res,
                                                __half *__restrict__ out, int M, int N, int relu, int units_total, int parts,
-                                               int chunks, const TsPacked &pk) {
+                                               int chunks, const TsPacked &pk, const TsSrc2 &src2 = TsSrc2{}) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int K = KS * 64;
+  constexpr int KS1 = KS - KS2, K1 = KS1 * 64, K2 = KS2 * 64;   // (KS2 == 0: KS1 == KS, K1 == K)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // block -> (row partition, column chunk); the chunks of a partition on one XCD when the grid allows it
   int part, chunk;
@@ -603,7 +615,9 @@ __device__ __forceinline__ void tsgemm_ws_body(const __half *__restrict__ x, con
   const int ntiles = (u_end - u_begin + kWsG - 1) / kWsG;
 
   const __amdgpu_buffer_rsrc_t rs_x =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<__half *>(x), 0, (unsigned)((size_t)M * K * 2), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<__half *>(x), 0, (unsigned)((size_t)M * K1 * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x2 =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<__half *>(src2.x2), 0, KS2 > 0 ? src2.bytes : 0u, 0x00020000);
   const unsigned hi = (unsigned)(lane >> 5);
   const unsigned fa = (unsigned)(wave * 32 + (lane & 31));   // weight row of this lane's fragments
   // the wave's weight rows: fragment 4 kstep + ks holds k = 64 kstep + 16 ks + 8 hi .. + 7 of row n0 + fa
@@ -637,11 +651,28 @@ __device__ __forceinline__ void tsgemm_ws_body(const __half *__restrict__ x, con
   auto dma = [&](int t, int buf) {
     const int row = (u_begin + t * kWsG) * 32 + (int)trow;
     const bool valid = t < ntiles && u_begin + t * kWsG + (wave >> 2) < u_end && row < M;
-    const unsigned voff = valid ? (unsigned)((size_t)row * K * 2) + tchunk : 0xFFFFFF00u;
+    const unsigned voff = valid ? (unsigned)((size_t)row * K1 * 2) + tchunk : 0xFFFFFF00u;
     char *d = smem + kWsEpi + buf * (KS * kWsStep) + wave * 1024;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
+    for (int ks = 0; ks < KS1; ++ks)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_t *)(d + ks * kWsStep), 16, (int)voff, ks * 128, 0, 0);
+    if constexpr (KS2 > 0) {
+      unsigned voff2 = 0xFFFFFF00u;
+      if (valid) {
+        size_t pix = (size_t)row;            // stride 1: the rows ARE the pixels
+        if (src2.stride != 1) {
+          const int per = src2.hout * src2.wout;
+          const int b = row / per, q = row - b * per;
+          const int yo = q / src2.wout, xo = q - yo * src2.wout;
+          pix = ((size_t)b * src2.hin + (size_t)(yo * src2.stride)) * src2.win + (size_t)(xo * src2.stride);
+        }
+        voff2 = (unsigned)(pix * K2 * 2) + tchunk;
+      }
+#pragma unroll
+      for (int ks = 0; ks < KS2; ++ks)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x2, (lds_void_t *)(d + (KS1 + ks) * kWsStep), 16, (int)voff2, ks * 128,
+                                                 0, 0);
+    }
   };
   // all but the youngest tile's pieces of this wave have landed
   auto wait_keep_one_tile = [&]() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KS) : "memory"); };
@@ -816,6 +847,14 @@ __global__ __launch_bounds__(kTsThreads) void tsgemm_ws_grouped_kernel(const __h
                                                                        int M, int N, int units_total, int parts, int chunks,
                                                                        TsPacked pk) {
   tsgemm_ws_body<0, KS, true>(x, w, bias, nullptr, out, M, N, 0, units_total, parts, chunks, pk);
+}
+
+template <int KS, int KS2>
+__global__ __launch_bounds__(kTsThreads) void tsgemm_ws2_kernel(const __half *__restrict__ x, const __half *__restrict__ w,
+                                                                const __half *__restrict__ bias, __half *__restrict__ out,
+                                                                int M, int N, int relu, int units_total, int parts, int chunks,
+                                                                TsSrc2 src2) {
+  tsgemm_ws_body<0, KS, false, KS2>(x, w, bias, nullptr, out, M, N, relu, units_total, parts, chunks, TsPacked{}, src2);
 }
 
 // ---- the int8 activation chain's flavour (quantization.Int8ChainBackbone: the 1x1 convolutions of ResNet stages 3 / 4):
@@ -1197,7 +1236,34 @@ TsPacked ts_ln_params(const void *ln_weight, const void *ln_bias, float eps) {
   return pk;
 }
 
+// the partition of ws_launch_ks (not grouped) for a two-source call
+template <int KS, int KS2>
+int ws2_launch_ks(const Gemm2Call &g) {
+  if (!ensure_dynamic_lds<tsgemm_ws2_kernel<KS, KS2>>(ws_lds(KS))) return BEVOPS_FAILURE;
+  const int units = (int)((g.m + 31) / 32), chunks = g.n / kTsBN;
+  int parts = ts_grid_x(1 << 30, chunks) / chunks;
+  if (parts < 1) parts = 1;
+  if (parts > units) parts = units;
+  const TsSrc2 src2{(const __half *)g.a2, (unsigned)((unsigned long long)g.B * g.H * g.W * g.k2 * 2), g.H, g.W, g.ho, g.wo,
+                    g.stride};
+  hipLaunchKernelGGL((tsgemm_ws2_kernel<KS, KS2>), dim3((unsigned)(parts * chunks)), dim3(kTsThreads), ws_lds(KS), g.st,
+                     (const __half *)g.a1, (const __half *)g.w, (const __half *)g.bias, (__half *)g.out, (int)g.m, g.n, g.relu,
+                     units, parts, chunks, src2);
+  return launch_status();
+}
+
 }  // namespace
+
+// (gemm_host.h) K1 + K2 <= 256 and whole 256-column chunks, under the variant that runs the weight-stationary kernel
+bool tsgemm_ws2_in_domain(const Gemm2Call &g) { return g.n % kTsBN == 0 && g.k1 + g.k2 <= 256 && ts_use_ws(g.k1 + g.k2); }
+
+int tsgemm_ws2_launch(const Gemm2Call &g) {
+  return gemm_k64<4>((g.k1 + g.k2) / 64, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    return gemm_k64<KS - 1>(g.k2 / 64, [&](auto ks2) { return ws2_launch_ks<KS, decltype(ks2)::value>(g); });
+  });
+}
+
 }  // namespace bevops
 
 using namespace bevops;

@@ -259,6 +259,39 @@ def tile_gemm_dst(x, weight, bias, widths, residuals=None, relu=False, outs=None
     return outs
 
 
+def gemm2(a1, a2, weight, bias=None, stride=1, relu=False, out=None):
+    """act(a1 @ W1.T + rows(a2) @ W2.T + bias) as ONE accumulation (bevops_gemm2_f16): a1 [..., K1] fp16 contiguous rows,
+    a2 a [B, K2, H, W] fp16 tensor in channels-last memory whose row m is pixel (b, stride * ho, stride * wo), weight
+    [N, K1 + K2] = [W1 | W2], bias [N] -> [M, N] with M = B * Ho * Wo.  The first bottleneck of a ResNet stage: conv3 on
+    the block's hidden rows and the (strided) downsample convolution on the block's input, no identity tensor in
+    between.  k order: source 1, then source 2; one rounding.  Raises BevopsError (NOT_SUPPORTED) unless K1 and K2 are
+    multiples of 64, N % 8 == 0 and stride is 1 or 2."""
+    assert a1.is_cuda and a1.dtype == torch.float16 and a2.dtype == torch.float16 and weight.dtype == torch.float16
+    if a2.dim() != 4 or not a2.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError("a2 must be a 4-d tensor in channels-last memory")
+    B, K2, H, W = a2.shape
+    K1, N = a1.shape[-1], weight.shape[0]
+    if weight.shape[1] != K1 + K2:
+        raise ValueError(f"weight {tuple(weight.shape)} does not match [N, {K1} + {K2}]")
+    x1 = a1.reshape(-1, K1)
+    if not x1.is_contiguous():
+        x1 = x1.contiguous()
+    if not weight.is_contiguous():
+        weight = weight.contiguous()
+    if bias is not None and (bias.dtype != torch.float16 or not bias.is_contiguous()):
+        bias = bias.to(torch.float16).contiguous()
+    M = x1.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=a1.dtype, device=a1.device)
+    else:
+        assert out.is_contiguous() and out.numel() == M * N and out.dtype == a1.dtype
+    if M == 0:
+        return out
+    _call("bevops_gemm2_f16", a1.device, x1.data_ptr(), a2.data_ptr(), weight.data_ptr(), _ptr(bias), out.data_ptr(), M, N,
+          K1, K2, B, H, W, int(stride), int(bool(relu)))
+    return out
+
+
 def small_gemm_dst(x, weight, bias, widths, residuals=None, relu=False, outs=None):
     """tile_gemm_dst's call on the few-row GEMM (bevops_small_gemm_f16_dst): every layer but the last has a width that
     is a multiple of 64, the last a multiple of 8; each result bit for bit small_gemm(x, weight_i, bias_i, residuals[i])."""

@@ -120,6 +120,7 @@ SIGNATURES = {
     "bevops_small_gemm_f16": (c_int, [c_void_p] * 5 + [ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
     "bevops_tile_gemm_f16": (c_int, [c_void_p] * 5 + [ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
     "bevops_tile_gemm_f16_dst": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
+    "bevops_gemm2_f16": (c_int, [c_void_p] * 5 + [ctypes.c_longlong] + [c_int] * 8 + [c_void_p]),
     "bevops_small_gemm_f16_dst": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
     "bevops_conv_tile_f16": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p]),
     "bevops_conv3x3_c64_f16": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),

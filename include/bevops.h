@@ -464,6 +464,21 @@ int bevops_linear_int8_fused(const void *x_f16, float scale_a, const void *w_q, 
  * next to bevops_tsgemm_f16 and bevops_linear_bias_act. */
 int bevops_tile_gemm_f16(const void *x, const void *weight, const void *bias, const void *residual,
                          void *out, long long M, int N, int K, int relu, void *stream);
+/* One GEMM over TWO activation sources (the first bottleneck of a ResNet stage: conv3 and the downsample convolution
+ * as one accumulation, no identity tensor written and read back):
+ *     out[m, n] = act( sum_{k < K1} a1[m, k] w[n, k] + sum_{k < K2} a2row(m)[k] w[n, K1 + k] + bias[n] )
+ * a1 [M, K1] fp16 rows; a2 a channels-last [a2_B, a2_H, a2_W, K2] fp16 tensor whose row m is pixel
+ * (b, a2_stride * ho, a2_stride * wo) with m = (b * Ho + ho) * Wo + wo, Ho = (a2_H - 1) / a2_stride + 1 (Wo alike): the
+ * row addressing of bevops_conv_tile_f16 with ksize 1 (a2_stride 1: a plain [M, K2] matrix); weight [N, K1 + K2] the
+ * two layers' weights side by side, bias fp16 [N] (their sum) or NULL; out [M, N] fp16.  k runs over source 1 ascending,
+ * then source 2 ascending, in fp32, ONE rounding: bit for bit the single-source entry of the same kernel family on the
+ * materialised [a1 | rows of a2] -- bevops_tsgemm_f16 (weight-stationary kernel) for K1 + K2 <= 256 and N % 256 == 0,
+ * bevops_tile_gemm_f16 otherwise.  An output row depends on its own operands only.  No workspace.
+ * K1 or K2 no positive multiple of 64, N % 8 != 0, a2_stride outside {1, 2}, a byte range of a1 / a2 / weight from
+ * 0xFFFFFF00 on: BEVOPS_NOT_SUPPORTED.  NULL a1 / a2 / weight / out, non-positive sizes, M != a2_B * Ho * Wo, pointers
+ * not 16-byte aligned: BEVOPS_BAD_PARAM.  Nothing is queued unless BEVOPS_SUCCESS is returned. */
+int bevops_gemm2_f16(const void *a1, const void *a2, const void *weight, const void *bias, void *out, long long M, int N,
+                     int K1, int K2, int a2_B, int a2_H, int a2_W, int a2_stride, int relu, void *stream);
 /* Several layers that read the SAME rows as one launch of that kernel: weight [N, K] / bias [N] are the layers'
  * parameters stacked, and a table of at most 8 destinations says where each column range of the product goes --
  * columns [col_begin, col_end) as a pitched fp16 matrix of their own (element (m, col_begin + c) at
