@@ -83,6 +83,8 @@ const Entry kTable[] = {
     {"bevops_upsample_add_nhwc", (void *)&bevops_upsample_add_nhwc},
     {"bevops_lss_depth_split", (void *)&bevops_lss_depth_split},
     {"bevops_upsample_bilinear_concat_nhwc", (void *)&bevops_upsample_bilinear_concat_nhwc},
+    {"bevops_lss_depth_split_s8", (void *)&bevops_lss_depth_split_s8},
+    {"bevops_upsample_bilinear_s8", (void *)&bevops_upsample_bilinear_s8},
     {"bevops_tsa_split", (void *)&bevops_tsa_split},
     {"bevops_queue_mean2", (void *)&bevops_queue_mean2},
     {"bevops_tsgemm_f16", (void *)&bevops_tsgemm_f16},

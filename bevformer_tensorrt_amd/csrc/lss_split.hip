@@ -10,6 +10,7 @@
 //  * upsample_bilinear_concat: FPN_LSS's cat([a, interpolate(b, bilinear, align_corners=True)], 1)
 //    (models/necks/lss_fpn.py) in one pass with no up-sampled intermediate.  thread = 8 channels of one output pixel.
 #include "common.h"
+#include "lss_pos.h"
 
 namespace bevops {
 namespace {
@@ -71,22 +72,6 @@ __global__ __launch_bounds__(256) void lss_depth_split_kernel(const __half *__re
 __device__ __forceinline__ void unpack8(const uint4 v, float *f) {
   f[0] = h2f_lo(v.x); f[1] = h2f_hi(v.x); f[2] = h2f_lo(v.y); f[3] = h2f_hi(v.y);
   f[4] = h2f_lo(v.z); f[5] = h2f_hi(v.z); f[6] = h2f_lo(v.w); f[7] = h2f_hi(v.w);
-}
-
-// Source position of output index o on an axis of `dst` outputs over `src` inputs, align_corners=True:
-// o * (src - 1) / (dst - 1) as an exact fraction -- integer part i0, remainder / (dst - 1) as the weight of i0 + 1 -- so
-// the first and last outputs sit exactly on the first and last inputs and an equal-size axis is the identity.
-__device__ __forceinline__ void source_pos(unsigned o, unsigned src, unsigned dst, unsigned &i0, unsigned &i1, float &l) {
-  if (dst <= 1u) {
-    i0 = i1 = 0u;
-    l = 0.f;
-    return;
-  }
-  const unsigned num = o * (src - 1u), den = dst - 1u;
-  i0 = num / den;
-  const unsigned rem = num - i0 * den;
-  i1 = min(i0 + 1u, src - 1u);
-  l = (float)rem / (float)den;
 }
 
 __global__ __launch_bounds__(256) void upsample_bilinear_concat_f16_kernel(const __half *__restrict__ a,

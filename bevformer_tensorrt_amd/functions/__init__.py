@@ -35,7 +35,7 @@ from .nms import bev_nms, nms_bev, circle_nms, bev_iou
 from .decode2d import centernet_decode, yolox_decode, box_nms
 from .lss_prepare import lss_voxel_prepare, lss_lidar_coor, bev_pool_v2_indirect
 from .calibrate import calib_state_size, calib_collect, calib_threshold
-from .bev_half import lss_depth_split, upsample_bilinear_concat_nhwc
+from .bev_half import lss_depth_split, upsample_bilinear_concat_nhwc, lss_depth_split_q, upsample_bilinear_nhwc_q
 from .deconv import conv_transpose2d_nhwc, pack_deconv4x4s2, deconv_packed_weight, conv_transpose2d_q_nhwc, quantize_deconv_weight
 from .yolox_ops import (conv_slice_nhwc, conv_slice_taps, conv_slice_packed_weight, focus_nhwc, spp_maxpool_nhwc,
                         upsample_nearest2x_nhwc, pad_channels, unpad_channels, conv_slice_q_taps, focus_nhwc_q,
@@ -71,7 +71,7 @@ __all__ = [
     "spatial_cross_attention_sample", "spatial_cross_attention_projected", "spatial_cross_attention_plan", "modulated_deformable_conv2d_nhwc", "bias_act_nhwc_", "linear_bias_act", "layer_norm", "rotate_hwc", "conv_offset_nhwc", "upsample_add_nhwc_", "feat_embed_nhwc",
     "msda_pack_value", "multi_scale_deformable_attn_prepacked", "multi_scale_deformable_attn_local", "image_normalize_pad", "padded_size", "quantize_rows", "dequantize_rows", "linear_int8", "tsgemm", "tsgemm_ln", "tsgemm_grouped", "tile_gemm", "tile_gemm_dst", "gemm2", "small_gemm_dst", "small_gemm", "dense_auto", "tsa_split", "queue_mean2", "conv_nhwc", "conv3x3_nhwc", "conv3x3_auto", "conv3x3_c64", "conv_int8_nhwc", "bias_relu_maxpool_nhwc", "stem_conv_pool", "point_sampling", "self_attention_qkv", "refine_reference_points", "decode_boxes",
     "linear_int8_chain", "linear_int8_ln", "conv_int8_chain_nhwc", "modulated_deformable_conv2d_int8_nhwc",
-    "lss_depth_split", "upsample_bilinear_concat_nhwc",
+    "lss_depth_split", "upsample_bilinear_concat_nhwc", "lss_depth_split_q", "upsample_bilinear_nhwc_q",
     "conv_transpose2d_nhwc", "pack_deconv4x4s2", "deconv_packed_weight", "conv_transpose2d_q_nhwc", "quantize_deconv_weight",
     "conv_slice_nhwc", "conv_slice_taps", "conv_slice_packed_weight", "focus_nhwc", "spp_maxpool_nhwc",
     "upsample_nearest2x_nhwc", "pad_channels", "unpad_channels",

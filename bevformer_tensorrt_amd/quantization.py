@@ -1065,14 +1065,37 @@ def build_int8_engine(B, name, dev, frames, calibrator="entropy", chain=True, de
     return model, qops, note
 
 
-def build_int8_bevdet(D, dev, frames, calibrator="entropy"):
-    """The PTQ build of the re-hosted BEVDet-R50 (BASELINE config 5; `D` = the bevdet module, `frames` = an iterable
-    of (image, ranks...) calibration inputs): ResNet-50 + FPN laterals as the int8 activation chain, bev_pool_v2 on
-    its INT8 plugin flavour; the small BEV encoder / head convolutions stay fp16.  Returns (model, qops, note)."""
+BEVDET_BEV_HALF_BUILDS = ("fp16", "int8")
+
+
+def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", calibration_cache=None):
+    """The PTQ build of the re-hosted BEVDet-R50 (BASELINE config 5; `D` = the bevdet module, or a bevdet.BEVDet
+    instance whose weights to quantise; `frames` = an iterable of (image, ranks...) calibration inputs): ResNet-50 + FPN
+    laterals as the int8 activation chain, bev_pool_v2 on its INT8 plugin flavour.  bev_half="fp16" (the default): the
+    small BEV encoder / head convolutions stay fp16.  bev_half="int8": everything behind the image neck runs the int8
+    plan of bevdet_int8.py (design/bevdet_int8.md) -- depth_net, the softmax + split and the pooling leaving as int8,
+    every BasicBlock, the two bilinear up-samplers, neck, heads; its sites are calibrated during the same frames, on
+    the fp16 kernels of BEVDet(bev_half="hip") from each frame's fp16 image features.  calibration_cache (bev_half="int8"):
+    a path -- an existing cache is loaded INSTEAD of running frames, otherwise the collected statistics of every site
+    (image chain, pooling and BEV half) are saved there (the format of save_calibration / load_calibration).
+    Returns (model, qops, note); with bev_half="int8" the model is a bevdet_int8.Int8BEVDet (forward,
+    forward_calibrated, bev_half_calibrated, get_candidates, get_bboxes, prepare_bev_half: BEVDetRunner captures it
+    unchanged)."""
+    if bev_half not in BEVDET_BEV_HALF_BUILDS:
+        raise ValueError(f"bev_half = {bev_half!r}: one of {BEVDET_BEV_HALF_BUILDS}")
+    if calibration_cache is not None and bev_half != "int8":
+        raise ValueError("build_int8_bevdet: calibration_cache goes with bev_half='int8'")
+    src = D if isinstance(D, torch.nn.Module) else None
+    if src is not None:
+        from . import bevdet as D
     qops = Int8PluginOps(calibrator, channels_last=True)
     model = D.BEVDet(ops=qops, seed=0).to(dev, torch.float16)
+    if src is not None:
+        model.load_state_dict(src.state_dict())
     model.view.ops = qops
     ch = Int8ChainBackbone(model, qops.cal)
+    if bev_half == "int8":
+        return _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache)
     n = 0
     for f in frames:
         qops.begin_frame()
@@ -1085,6 +1108,43 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy"):
             "int8_backbone_layers": len(ch.convs) + sum(len(b) for b in ch.plan), "activation_chain": True,
             "calibration_frames": n}
     return model, qops, note
+
+
+def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache):
+    """build_int8_bevdet(bev_half="int8") behind the construction of the image chain: the calibration frames (or the
+    cache), the freeze, the Int8BEVDet around the model."""
+    from . import bevdet_int8 as _bi
+    cal = qops.cal
+    n = 0
+    if calibration_cache is not None and os.path.exists(calibration_cache):
+        _bi.load_calibration(cal, calibration_cache, dev if isinstance(cal, _DeviceCalibrator) else None)
+    else:
+        inner, seen = model.image_features, {}
+
+        def image_features(image):        # (keeps each frame's fp16 image features for the BEV half's calibration)
+            seen["x"] = inner(image)
+            return seen["x"]
+
+        model.image_features = image_features
+        try:
+            for f in frames:
+                qops.begin_frame()
+                model(*f)
+                _bi.calibrate_frame(model, seen.pop("x"), f[1:], cal)
+                n += 1
+        finally:
+            del model.image_features
+        if calibration_cache is not None:
+            _bi.save_calibration(cal, calibration_cache, {"model": "bevdet", "bev_half": "int8", "frames": n})
+    scales = qops.freeze()
+    ch.freeze()
+    model.register_forward_pre_hook(lambda m, args: qops.begin_frame())
+    q = _bi.Int8BEVDet(model, _bi.scales_from(cal, _bi.build_plan(model).sites))
+    note = {"int8_plugin_sites": sum(1 for k in scales if k.startswith("bev_pool") and k.endswith(".out")),
+            "int8_backbone_layers": len(ch.convs) + sum(len(b) for b in ch.plan), "activation_chain": True,
+            "calibration_frames": n, "bev_half": "int8", "int8_bev_half_layers": q.num_int8_layers,
+            "bev_half_scale_sites": len(q.plan.sites)}
+    return q, qops, note
 
 
 def build_int8_yolox(Y, dev, images, calibrator="entropy", calibration_cache=None, cfg=None, ops=None):

@@ -85,6 +85,9 @@ SIGNATURES = {
     "bevops_upsample_add_nhwc": (c_int, [c_int, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "bevops_lss_depth_split": (c_int, [c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "bevops_upsample_bilinear_concat_nhwc": (c_int, [c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
+    "bevops_lss_depth_split_s8": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_float, c_float, c_void_p]),
+    "bevops_upsample_bilinear_s8": (c_int, [c_void_p, c_int, c_float, c_void_p, c_int, c_float] + [c_int] * 6 +
+                                    [c_void_p]),
     "bevops_feat_embed_nhwc": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, c_size_t,
                                        c_void_p]),
     "bevops_conv3x3_c32_set_variant": (c_int, [c_int]),

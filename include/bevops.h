@@ -384,6 +384,44 @@ int bevops_lss_depth_split(int dtype, const void *x, void *depth, void *feat, in
 int bevops_upsample_bilinear_concat_nhwc(int dtype, const void *a, const void *b, void *out, int n, int h, int w,
                                          int ca, int hb, int wb, int cb, void *stream);
 
+/* bevops_lss_depth_split's INT8 sibling (csrc/lss_split_s8.hip; the BEV half of the INT8 build of BEVDet): the fp16
+ * rows [n * hw, row_stride] depth_net wrote -> depth_q int8 [n, D, hw] (plane-major) and feat_q int8 [n, hw, C], exactly
+ * the operands bevops_bev_pool_v2_forward takes in BEVOPS_I8.  Every step ONE fp32 operation in exactly this order
+ * (inv_d = 1.f / scale_depth and inv_f = 1.f / scale_feat are computed once on the host in fp32):
+ *   m      = maximum of the pixel's D logits                          (exact)
+ *   e_d    = expf(x_d - m)
+ *   sum    : four lanes per pixel; lane j adds its bins j, j + 4, j + 8, ... in ascending order to 0.f, then
+ *            s = s + s[lane ^ 1]; s = s + s[lane ^ 2], i.e. (s0 + s1) + (s2 + s3) of the four lane sums
+ *   p      = e_d / sum                                                (IEEE division; the build has no fast-math)
+ *   q      = min(max(rne(p * inv_d), -127), 127)
+ *   feat_q = min(max(rne((float)x * inv_f), -127), 127)
+ * A NaN leaves as -127 (as in bevops_conv_slice_s8's epilogue).  A non-finite logit spoils its own pixel's D bytes and
+ * nothing else.  Domain: 1 <= D <= 256 (else NOT_SUPPORTED); C > 0, C % 16 == 0, feat_offset % 8 == 0,
+ * row_stride % 8 == 0, both column ranges inside the row and disjoint, x_f16 and feat_q 16-byte aligned (depth_q any
+ * address: a plane leaves as whole dwords where its address allows, as bytes otherwise), both scales positive and
+ * finite (else BAD_PARAM; NULL pointers, n < 0, hw < 0 too).  n == 0 or hw == 0: SUCCESS without a launch.  One launch,
+ * no atomics, no scratch, no allocation, no synchronisation; capturable. */
+int bevops_lss_depth_split_s8(const void *x_f16, void *depth_q, void *feat_q, int n, int hw, int row_stride,
+                              int depth_offset, int D, int feat_offset, int C, float scale_depth, float scale_feat,
+                              void *stream);
+
+/* out[n, y, x, 0 .. C) = F.interpolate(b, (h, w), mode="bilinear", align_corners=True) on the INT8 channel slice b,
+ * requantised (csrc/lss_split_s8.hip).  b_q [n, hb, wb] pixels and out_q [n, h, w] pixels point at the first channel of
+ * a slice; pitches in elements, as in bevops_conv_slice_s8 and bevops_upsample_nearest2x_nhwc.  FPN_LSS's concatenation
+ * disappears: the producer of the other channels writes its slice of the consumer's buffer itself, this entry writes
+ * the rest; there is no `a` operand and no copy.  The source position is bevops_upsample_bilinear_concat_nhwc's exact
+ * fraction.  On the four corners converted exactly to fp32, in this order, with r = scale_b * (1.f / scale_out)
+ * computed on the host in fp32:
+ *   hx = 1 - lx, hy = 1 - ly
+ *   t = hx * v00;  t = fma(lx, v01, t);  u = hx * v10;  u = fma(lx, v11, u);  o = hy * t;  o = fma(ly, u, o);  v = o * r
+ *   q = min(max(rne(v), -127), 127)
+ * Domain: C > 0 and C % 16 == 0, pitches multiples of 16 and at least C, slices on 16-byte boundaries, b not overlapping
+ * out (disjoint channel slices of one buffer with equal pitches are accepted), n >= 0, h, w, hb, wb >= 1, scales
+ * positive and finite (else BAD_PARAM); h * hb or w * wb of 2^31 or more, n hb wb or n h w of 2^31 or more:
+ * NOT_SUPPORTED.  n == 0: SUCCESS without a launch. */
+int bevops_upsample_bilinear_s8(const void *b_q, int b_pitch, float scale_b, void *out_q, int out_pitch, float scale_out,
+                                int n, int h, int w, int hb, int wb, int C, void *stream);
+
 /* Encoder input assembly (det2trt/models/modules/transformer.py:138-152): dst[n, r, :] = (src[n, r, :] +
  * cam_embed[n, :]) + level_embed[:], both sums rounded to fp16 like the two tensor adds they replace; `dst` is
  * the level's first row inside the concatenated [cams, sum hw, C] feature tensor, `dst_batch_stride` its
