@@ -210,10 +210,23 @@ class LSSViewTransformer(nn.Module):
                              sensor2ego[:, :, :3, 3].reshape(N, 3)), 1)
         return torch.cat((per_cam.reshape(-1), bda.reshape(-1)[:9])).contiguous()
 
+    def calibration_matrices_batched(self, sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda):
+        """`calibration_matrices` for B samples: [B, N * 24 + 9], row b the packed buffer of sample b (its own cameras
+        and its own bda), each row evaluated by that sample's own call -- so row 0 at B = 1 equals
+        `calibration_matrices`, and a sample's row does not depend on its neighbours in the batch."""
+        B = sensor2ego.shape[0]
+        if B < 1 or any(t.shape[0] != B for t in (cam2imgs, post_rots, post_trans, bda)):
+            raise ValueError("calibration_matrices_batched: every tensor carries the same leading B >= 1")
+        return torch.stack([self.calibration_matrices(sensor2ego[b:b + 1], None, cam2imgs[b:b + 1], post_rots[b:b + 1],
+                                                      post_trans[b:b + 1], bda[b:b + 1]) for b in range(B)]).contiguous()
+
     def lidar_coor_plain(self, calib):
         """get_lidar_coor from the packed `calibration_matrices` buffer in plain order: fp32, every product and sum
         rounded on its own, each 3x3 . 3x1 product summed in ascending k ((m0 p0 + m1 p1) + m2 p2).  This is the
-        arithmetic of the device kernel; on the CPU it equals get_lidar_coor bit for bit.  -> [1, N, D, H, W, 3]."""
+        arithmetic of the device kernel; on the CPU it equals get_lidar_coor bit for bit.  -> [1, N, D, H, W, 3];
+        the 2-D buffer [B, N * 24 + 9] of `calibration_matrices_batched` -> [B, N, D, H, W, 3]."""
+        if calib.dim() == 2:
+            return torch.cat([self.lidar_coor_plain(row) for row in calib], 0).contiguous()
         calib = calib.detach().to("cpu", torch.float32).view(-1)
         N = (calib.numel() - 9) // 24
         cam = calib[:N * 24].view(N, 1, 1, 1, 24)
@@ -271,8 +284,10 @@ class LSSViewTransformer(nn.Module):
 
     def prepare_calibrated(self, calib, padded=True):
         """The five index arrays (+ counts when padded) from the packed calibration buffer ON THE DEVICE `calib` lives
-        on: functions.lss_voxel_prepare with this transformer's frustum and grid."""
-        prepare = getattr(self.ops, "lss_voxel_prepare", _hip_ops.lss_voxel_prepare)   # (an INT8 operator set has none)
+        on: functions.lss_voxel_prepare with this transformer's frustum and grid.  A 2-D calib [B, N * 24 + 9]: the
+        batched arrays of functions.lss_voxel_prepare_batched."""
+        name = "lss_voxel_prepare_batched" if calib.dim() == 2 else "lss_voxel_prepare"
+        prepare = getattr(self.ops, name, getattr(_hip_ops, name))   # (an INT8 operator set has none)
         return prepare(self._frustum_on(calib.device), calib, self.grid_lower_bound, self.grid_interval, self.grid_size,
                        padded=padded)
 
@@ -320,19 +335,24 @@ class LSSViewTransformer(nn.Module):
     @torch.no_grad()
     def view_transform_calibrated(self, x, calib):
         """`view_transform` with the index build on the device: x as there, calib = the packed fp32 buffer of
-        `calibration_matrices` on x's device.  No host synchronisation: capturable with the frame."""
+        `calibration_matrices` on x's device.  No host synchronisation: capturable with the frame.
+        calib [B, N * 24 + 9] (`calibration_matrices_batched`) with x [B * N_cams, ...]: B samples -> [B, C, h, w]."""
         rb, rd, rf, ist, il, counts = self.prepare_calibrated(calib)
         bev_h, bev_w = int(self.grid_size[1]), int(self.grid_size[0])
+        # (batch is passed only when there is one, so an operator set written for one sample serves a 1-D calib as before)
+        kw = dict(batch=calib.shape[0]) if calib.dim() == 2 else {}
+        if calib.dim() == 2 and x.shape[0] * 24 != calib.shape[0] * (calib.shape[1] - 9):
+            raise ValueError(f"calib {tuple(calib.shape)} does not describe the {x.shape[0]} camera images of x")
         if self._hip_on(x):
             depth, tran_feat = self._depth_feat_hip(x)
-            out = self.ops.bev_pool_v2_indirect(depth, tran_feat, rd, rf, rb, ist, il, counts, bev_h, bev_w)
+            out = self.ops.bev_pool_v2_indirect(depth, tran_feat, rd, rf, rb, ist, il, counts, bev_h, bev_w, **kw)
             return out.permute(0, 3, 1, 2)       # (channels-last view: what bev_encoder takes, no copy either way)
         x = self.depth_net(x)
         depth = x[:, : self.D].softmax(dim=1)
         tran_feat = x[:, self.D: self.D + self.out_channels].permute(0, 2, 3, 1)
         depth, tran_feat = depth.contiguous(), tran_feat.contiguous()
         bev_h, bev_w = int(self.grid_size[1]), int(self.grid_size[0])
-        out = self.ops.bev_pool_v2_indirect(depth, tran_feat, rd, rf, rb, ist, il, counts, bev_h, bev_w)
+        out = self.ops.bev_pool_v2_indirect(depth, tran_feat, rd, rf, rb, ist, il, counts, bev_h, bev_w, **kw)
         return out.permute(0, 3, 1, 2).contiguous()
 
     @torch.no_grad()
@@ -598,7 +618,11 @@ class BEVDet(nn.Module):
     @torch.no_grad()
     def forward_calibrated(self, image, calib):
         """`forward` from the frame's calibration instead of ready-made ranks: calib = the packed fp32 buffer of
-        `view.calibration_matrices` on the image's device; the index build and the pooling run on the device."""
+        `view.calibration_matrices` on the image's device; the index build and the pooling run on the device.
+        B samples at once: image [B, N, 3, H, W] with calib [B, N * 24 + 9] (`view.calibration_matrices_batched`) ->
+        six maps [B, c, h, w]; a 1-D calib is the one-sample call, unchanged."""
+        if calib.dim() == 2 and image.shape[0] != calib.shape[0]:
+            raise ValueError(f"image holds {image.shape[0]} samples, calib {calib.shape[0]}")
         hip = self._bev_half_ready(image)
         # "hip" also takes the image half's dispatch by rule: two library convolutions of ResNet stage 4 that the shipped
         # table prefers are not run-to-run reproducible on the MI355X, and the frame's bits would differ between runs
@@ -609,7 +633,7 @@ class BEVDet(nn.Module):
     @torch.no_grad()
     def bev_half_calibrated(self, x, calib, hip=None):
         """Everything of `forward_calibrated` behind `image_features`: x = its [cams, 256, H / 16, W / 16] result.
-        hip = None: as `bev_half` and the tensors decide."""
+        hip = None: as `bev_half` and the tensors decide.  calib [B, N * 24 + 9]: x holds B * cams images."""
         if self._bev_half_ready(x) if hip is None else hip:
             with _rule_dispatch():
                 return self._heads_hip(self.bev_encoder(self.view.view_transform_calibrated(x, calib)))
@@ -676,13 +700,22 @@ class BEVDetRunner:
     graph (functions.image_resize_crop_normalize, bit-exact to PIL), reading the static uint8 `raw_buffer` and writing
     `image_buffer`; flip / scale are sample_augmentation's arguments, data_config defaults to DATA_CONFIG_R50 with
     the model's input size.  `step` is unchanged and keeps its own graph, so a runner on which both `step` and
-    `step_raw` are called holds two graphs and the frame's activations twice (see `step_raw`)."""
+    `step_raw` are called holds two graphs and the frame's activations twice (see `step_raw`).
+
+    batch=B > 1 (fixed at construction) runs B samples per graph: `step` / `step_raw` take a leading B on the image
+    [B, cams, 3, H, W] (raw frames [B, cams, H0, W0, 3]) and on every calibration tensor; the static buffers are
+    [B, cams, 3, H, W], [B * cams, H0, W0, 3] and calib [B, cams * 24 + 9]; still one upload through the ring and one
+    graph per entry point; the maps come back as [B, c, h, w], the padded post-processing as [B, 500, ...] and count
+    [B].  Another B raises ValueError.  batch=1 is the runner described above, unchanged."""
     RING = 4
 
     def __init__(self, model, device, graph=True, post=None, clone_outputs=True, raw_size=None, flip=None, scale=None,
-                 data_config=None):
+                 data_config=None, batch=1):
         if post not in (None, "candidates", "bboxes"):
             raise ValueError(f"post = {post!r}: None, 'candidates' or 'bboxes'")
+        if int(batch) != batch or batch < 1:
+            raise ValueError(f"batch = {batch!r}: a positive integer")
+        self.batch = int(batch)
         self.model, self.device, self.use_graph, self.post, self.clone_outputs = model, device, graph, post, clone_outputs
         dtype = next(model.parameters()).dtype
         H, W = view_input_size(model.view)
@@ -706,20 +739,20 @@ class BEVDetRunner:
 
     @property
     def image_buffer(self):
-        """The static [1, cams, 3, H, W] input buffer (after the first `step`): a caller that writes its images here
+        """The static [batch, cams, 3, H, W] input buffer (after the first `step`): a caller that writes its images here
         and passes this very tensor to `step` saves the per-frame copy."""
         return None if self._in is None else self._in["image"]
 
     @property
     def raw_buffer(self):
-        """The static [cams, H0, W0, 3] uint8 buffer `step_raw` reads (after its first call): a caller that decodes its
+        """The static [batch * cams, H0, W0, 3] uint8 buffer `step_raw` reads (after its first call): a caller that decodes its
         camera frames into it and passes this very tensor to `step_raw` saves the per-frame copy."""
         return None if self._in is None else self._in.get("raw")
 
     def _forward(self, raw=False):
         if raw:
             fn = getattr(self.model.ops, "image_resize_crop_normalize", _hip_ops.image_resize_crop_normalize)
-            fn(self._in["raw"], self._plan, flip=self.flip, out=self._in["image"][0])
+            fn(self._in["raw"], self._plan, flip=self.flip, out=self._in["image"].flatten(0, 1))
         out = self.model.forward_calibrated(self._in["image"], self._in["calib"])
         if self.post == "candidates":
             return out + tuple(self.model.get_candidates(out, padded=True))
@@ -752,18 +785,30 @@ class BEVDetRunner:
         first call of its entry point, so a runner that only ever calls one of them pays for one."""
         if self.raw_size is None:
             raise RuntimeError("step_raw needs BEVDetRunner(..., raw_size=(H0, W0))")
-        n = sensor2ego.shape[1]
-        if raw.dtype != torch.uint8 or tuple(raw.shape) != (n,) + self.raw_size + (3,):
-            raise ValueError(f"raw must be uint8 [{n}, {self.raw_size[0]}, {self.raw_size[1]}, 3]")
-        post_rots = self.post_rot.view(1, 1, 3, 3).repeat(1, n, 1, 1)
-        post_trans = self.post_tran.view(1, 1, 3).repeat(1, n, 1)
-        host = self.model.view.calibration_matrices(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
+        n, B = sensor2ego.shape[1], self.batch
+        lead = (n,) if B == 1 else (B, n)
+        if raw.dtype != torch.uint8 or tuple(raw.shape) != lead + self.raw_size + (3,):
+            raise ValueError(f"raw must be uint8 {list(lead) + [self.raw_size[0], self.raw_size[1], 3]}")
+        post_rots = self.post_rot.view(1, 1, 3, 3).repeat(B, n, 1, 1)
+        post_trans = self.post_tran.view(1, 1, 3).repeat(B, n, 1)
+        host = self._host_calib(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
         return self._run_frame("raw", raw, host, n)
+
+    def _host_calib(self, sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda):
+        """The packed host buffer of the frame: 1-D at batch 1, [B, cams * 24 + 9] otherwise."""
+        B = self.batch
+        if any(t.shape[0] != B for t in (sensor2ego, cam2imgs, post_rots, post_trans, bda)):
+            raise ValueError(f"this runner was built for batch = {B}: every calibration tensor carries that leading B")
+        if B == 1:
+            return self.model.view.calibration_matrices(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
+        return self.model.view.calibration_matrices_batched(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
 
     def step(self, image, sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda):
         """-> (reg, height, dim, rot, vel, heatmap) of `BEVDet.forward`, followed by the padded outputs of
         `get_candidates` (post="candidates") or `get_bboxes` (post="bboxes")."""
-        host = self.model.view.calibration_matrices(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
+        host = self._host_calib(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
+        if image.shape[0] != self.batch:
+            raise ValueError(f"this runner was built for batch = {self.batch}, the image holds {image.shape[0]} samples")
         return self._run_frame("image", image, host, sensor2ego.shape[1])
 
     def _run_frame(self, key, source, host, n_cams):
@@ -771,16 +816,18 @@ class BEVDetRunner:
         calibration upload, the replay of that entry point's graph."""
         if self._in is None:
             self.n_cams = n_cams
-            self._in = dict(image=torch.zeros((1, self.n_cams) + self._image_shape, device=self.device, dtype=self._dtype),
-                            calib=torch.zeros(host.numel(), device=self.device))
-            self._ring = [(torch.zeros(host.numel()).pin_memory(), torch.cuda.Event()) for _ in range(self.RING)]
+            self._in = dict(image=torch.zeros((self.batch, self.n_cams) + self._image_shape, device=self.device,
+                                              dtype=self._dtype),
+                            calib=torch.zeros(host.shape, device=self.device))
+            self._ring = [(torch.zeros(host.shape).pin_memory(), torch.cuda.Event()) for _ in range(self.RING)]
             if self.raw_size is not None:
-                self._in["raw"] = torch.zeros((self.n_cams,) + self.raw_size + (3,), device=self.device, dtype=torch.uint8)
+                self._in["raw"] = torch.zeros((self.batch * self.n_cams,) + self.raw_size + (3,), device=self.device,
+                                              dtype=torch.uint8)
         i = self._in
         if host.numel() != i["calib"].numel():
             raise ValueError("the number of cameras is fixed by the first frame")
         if source.data_ptr() != i[key].data_ptr():          # (the caller may have filled the static buffer itself)
-            i[key].copy_(source, non_blocking=True)
+            i[key].copy_(source.reshape(i[key].shape), non_blocking=True)
         staged, done = self._ring[self._frame % self.RING]
         self._frame += 1
         done.synchronize()                                  # (returns at once unless the host is RING frames ahead)

@@ -388,12 +388,19 @@ class Int8BEVDet(nn.Module):
     @torch.no_grad()
     def bev_half_calibrated(self, x, calib):
         """Everything behind `image_features`: x = its fp16 [cams, 256, H / 16, W / 16] channels-last result; the index
-        build and the pooling run on the device from the packed calibration buffer."""
+        build and the pooling run on the device from the packed calibration buffer.  calib [B, cams * 24 + 9] with x
+        [B * cams, ...]: the plan runs for B samples -- the pooled view [B, h, w, C], every later tensor with B items (the
+        concatenation buffer [B, 64, 64, 640]); same operands, same scales."""
         table = self._ready(x)
         ops = self.bev_ops
         rb, rd, rf, ist, il, counts = self.view.prepare_calibrated(calib)
         h, w = int(self.view.grid_size[1]), int(self.view.grid_size[0])
-        pool = lambda d, f, s: ops.bev_pool_v2_indirect(d, f, rd, rf, rb, ist, il, counts, h, w, scales=s)
+        kw = {}
+        if calib.dim() == 2:
+            if x.shape[0] * 24 != calib.shape[0] * (calib.shape[1] - 9):
+                raise ValueError(f"calib {tuple(calib.shape)} does not describe the {x.shape[0]} camera images of x")
+            kw["batch"] = calib.shape[0]
+        pool = lambda d, f, s: ops.bev_pool_v2_indirect(d, f, rd, rf, rb, ist, il, counts, h, w, scales=s, **kw)
         with _dispatch.using(rule=True):
             return self._heads(self.run(x, pool, table, ops), table)
 

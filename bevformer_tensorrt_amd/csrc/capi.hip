@@ -55,6 +55,7 @@ const Entry kTable[] = {
     {"InverseTRT", (void *)&bevops_inverse_forward},
     {"bevops_nms_free_decode", (void *)&bevops_nms_free_decode},
     {"bevops_centerpoint_decode", (void *)&bevops_centerpoint_decode},
+    {"bevops_centerpoint_decode_ex", (void *)&bevops_centerpoint_decode_ex},
     {"bevops_centerpoint_decode_workspace_size", (void *)&bevops_centerpoint_decode_workspace_size},
     {"bevops_bev_nms", (void *)&bevops_bev_nms},
     {"bevops_bev_nms_workspace_size", (void *)&bevops_bev_nms_workspace_size},
@@ -66,6 +67,8 @@ const Entry kTable[] = {
     {"bevops_box_nms_workspace_size", (void *)&bevops_box_nms_workspace_size},
     {"bevops_lss_voxel_prepare", (void *)&bevops_lss_voxel_prepare},
     {"bevops_lss_voxel_prepare_workspace_size", (void *)&bevops_lss_voxel_prepare_workspace_size},
+    {"bevops_lss_voxel_prepare_batched", (void *)&bevops_lss_voxel_prepare_batched},
+    {"bevops_lss_voxel_prepare_batched_workspace_size", (void *)&bevops_lss_voxel_prepare_batched_workspace_size},
     {"bevops_bev_pool_v2_forward_indirect", (void *)&bevops_bev_pool_v2_forward_indirect},
     // entries that are not reference plugins: workspace-lending / channels-last / fused forms
     {"bevops_grid_sampler_2d_forward_ws", (void *)&bevops_grid_sampler_2d_forward_ws},

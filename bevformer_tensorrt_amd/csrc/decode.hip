@@ -108,15 +108,16 @@ struct CpChunk {
   static constexpr int kChunk = kCpChunk;
   const T *heat;
   unsigned hw, num_classes;
-  size_t cs, ps;
+  size_t cs, ps, is;   // channel, pixel, batch-item stride in elements
   __device__ __forceinline__ LogitSrc<T> prepare(char *, unsigned b, unsigned base, unsigned) const {
-    return LogitSrc<T>{heat + (size_t)b * num_classes * hw, base, hw, cs, ps};
+    return LogitSrc<T>{heat + (size_t)b * is, base, hw, cs, ps};
   }
 };
 
 struct CpMaps {
   const void *reg, *height, *dim, *rot, *vel, *heat;
   int cs[6], ps[6];   // channel / pixel strides in elements, order reg, height, dim, rot, vel, heatmap
+  long long is[6];    // batch-item strides in elements: channels * H * W for a map that is dense per item
 };
 struct CpGeom {
   float out_size_factor, voxel_x, voxel_y, pc_x, pc_y;
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(kDecThreads) void centerpoint_decode_kernel(
     const KeySrc src{ws + (size_t)b * nkeys};
     block_topk(src, nkeys, K, cap, idx_bytes, true, l);
   } else {
-    const LogitSrc<T> src{static_cast<const T *>(m.heat) + (size_t)b * num_classes * hw, 0u, hw, (size_t)m.cs[5],
+    const LogitSrc<T> src{static_cast<const T *>(m.heat) + (size_t)b * (size_t)m.is[5], 0u, hw, (size_t)m.cs[5],
                           (size_t)m.ps[5]};
     block_topk(src, num_classes * hw, K, cap, idx_bytes, true, l);
   }
@@ -151,23 +152,23 @@ __global__ __launch_bounds__(kDecThreads) void centerpoint_decode_kernel(
     label = (int)(idx / hw);
     const unsigned cell = idx % hw;
     const float col = (float)(cell % W), row = (float)(cell / W);
-    // channel c of a map with C channels at this cell
-    auto at = [&](const T *p, int which, unsigned C, unsigned c) {
-      return ld(p, (size_t)b * C * hw + (size_t)c * m.cs[which] + (size_t)cell * m.ps[which]);
+    // channel c of a map at this cell
+    auto at = [&](const T *p, int which, unsigned c) {
+      return ld(p, (size_t)b * (size_t)m.is[which] + (size_t)c * m.cs[which] + (size_t)cell * m.ps[which]);
     };
-    const float rx = reg ? at(reg, 0, 2, 0) : 0.5f, ry = reg ? at(reg, 0, 2, 1) : 0.5f;
+    const float rx = reg ? at(reg, 0, 0) : 0.5f, ry = reg ? at(reg, 0, 1) : 0.5f;
     // (col + reg) * out_size_factor * voxel + pc_range, every step rounded as the reference's tensor ops round it
     box[0] = add_rn(mul_rn(mul_rn(add_rn(col, rx), g.out_size_factor), g.voxel_x), g.pc_x);
     box[1] = add_rn(mul_rn(mul_rn(add_rn(row, ry), g.out_size_factor), g.voxel_y), g.pc_y);
-    box[2] = at(hei, 1, 1, 0);
+    box[2] = at(hei, 1, 0);
 #pragma unroll
     for (unsigned c = 0; c < 3; ++c) {
-      const float d = at(dim, 2, 3, c);
+      const float d = at(dim, 2, c);
       box[3 + c] = norm_bbox ? expf(d) : d;
     }
-    box[6] = atan2f(at(rot, 3, 2, 0), at(rot, 3, 2, 1));
-    box[7] = vel ? at(vel, 4, 2, 0) : 0.f;
-    box[8] = vel ? at(vel, 4, 2, 1) : 0.f;
+    box[6] = atan2f(at(rot, 3, 0), at(rot, 3, 1));
+    box[7] = vel ? at(vel, 4, 0) : 0.f;
+    box[8] = vel ? at(vel, 4, 1) : 0.f;
     return in_range(box[0], box[1], box[2], range) && (score_threshold < 0.f || s > score_threshold);
   });
 }
@@ -204,7 +205,8 @@ int launch_centerpoint(const CpMaps &m, float *boxes, float *scores, int32_t *la
   const unsigned nblk = cp_blocks(total);
   u64 *ws = static_cast<u64 *>(workspace);
   // K <= kCpMaxWinners = kCpChunk, so a slot holds K keys and the same LDS carve serves both launches
-  const CpChunk<T> chunk{static_cast<const T *>(m.heat), hw, (unsigned)nc, (size_t)m.cs[5], (size_t)m.ps[5]};
+  const CpChunk<T> chunk{static_cast<const T *>(m.heat), hw, (unsigned)nc, (size_t)m.cs[5], (size_t)m.ps[5],
+                           (size_t)m.is[5]};
   if (!ensure_dynamic_lds<partial_topk_kernel<CpChunk<T>>>(lds)) return BEVOPS_FAILURE;
   if (!ensure_dynamic_lds<centerpoint_decode_kernel<T, true>>(lds)) return BEVOPS_FAILURE;
   hipLaunchKernelGGL(partial_topk_kernel<CpChunk<T>>, dim3(nblk, (unsigned)batch), dim3(kDecThreads), lds, st, chunk, ws,
@@ -250,13 +252,14 @@ extern "C" size_t bevops_centerpoint_decode_workspace_size(int batch, int num_cl
   return (size_t)batch * cp_blocks(total) * (size_t)max_num * sizeof(u64);
 }
 
-extern "C" int bevops_centerpoint_decode(int dtype, const void *reg, const void *height, const void *dim,
-                                         const void *rot, const void *vel, const void *heatmap,
-                                         const int32_t *strides_host, float *boxes, float *scores, int32_t *labels,
-                                         int32_t *count, int batch, int num_classes, int map_h, int map_w, int max_num,
-                                         float out_size_factor, float voxel_x, float voxel_y, float pc_x, float pc_y,
-                                         const float *post_center_range_host, float score_threshold, int norm_bbox,
-                                         int heatmap_is_score, void *workspace, size_t workspace_bytes, void *stream) {
+extern "C" int bevops_centerpoint_decode_ex(int dtype, const void *reg, const void *height, const void *dim,
+                                            const void *rot, const void *vel, const void *heatmap,
+                                            const int64_t *strides_host, float *boxes, float *scores, int32_t *labels,
+                                            int32_t *count, int batch, int num_classes, int map_h, int map_w,
+                                            int max_num, float out_size_factor, float voxel_x, float voxel_y, float pc_x,
+                                            float pc_y, const float *post_center_range_host, float score_threshold,
+                                            int norm_bbox, int heatmap_is_score, void *workspace, size_t workspace_bytes,
+                                            void *stream) {
   if (!height || !dim || !rot || !heatmap || !strides_host || !boxes || !scores || !labels || !count ||
       !post_center_range_host)
     return BEVOPS_BAD_PARAM;
@@ -264,14 +267,15 @@ extern "C" int bevops_centerpoint_decode(int dtype, const void *reg, const void 
   if (const int st = dtype_status(dtype)) return st;
   const long long total = (long long)num_classes * map_h * map_w;
   if (max_num > total || score_threshold != score_threshold) return BEVOPS_BAD_PARAM;
-  for (int i = 0; i < 12; ++i)
-    if (strides_host[i] < 1) return BEVOPS_BAD_PARAM;
+  for (int i = 0; i < 18; ++i)
+    if (strides_host[i] < 1 || (i % 3 != 2 && strides_host[i] > 0x7fffffffLL)) return BEVOPS_BAD_PARAM;
   if (total > 0x7fffffffLL || max_num > kCpMaxWinners || batch > 65535) return BEVOPS_NOT_SUPPORTED;
   const size_t need = bevops_centerpoint_decode_workspace_size(batch, num_classes, map_h, map_w, max_num);
   if (need && !workspace_ok(workspace, workspace_bytes, need)) return BEVOPS_BAD_PARAM;
   CpMaps m;
   m.reg = reg, m.height = height, m.dim = dim, m.rot = rot, m.vel = vel, m.heat = heatmap;
-  for (int i = 0; i < 6; ++i) m.cs[i] = strides_host[2 * i], m.ps[i] = strides_host[2 * i + 1];
+  for (int i = 0; i < 6; ++i)
+    m.cs[i] = (int)strides_host[3 * i], m.ps[i] = (int)strides_host[3 * i + 1], m.is[i] = strides_host[3 * i + 2];
   const CpGeom g{out_size_factor, voxel_x, voxel_y, pc_x, pc_y};
   Range6 range;
   for (int i = 0; i < 6; ++i) range.v[i] = post_center_range_host[i];
@@ -281,4 +285,27 @@ extern "C" int bevops_centerpoint_decode(int dtype, const void *reg, const void 
                                      range, score_threshold, norm_bbox, heatmap_is_score, workspace, st);
   return launch_centerpoint<__half>(m, boxes, scores, labels, count, batch, num_classes, map_h, map_w, max_num, g, range,
                                     score_threshold, norm_bbox, heatmap_is_score, workspace, st);
+}
+
+extern "C" int bevops_centerpoint_decode(int dtype, const void *reg, const void *height, const void *dim,
+                                         const void *rot, const void *vel, const void *heatmap,
+                                         const int32_t *strides_host, float *boxes, float *scores, int32_t *labels,
+                                         int32_t *count, int batch, int num_classes, int map_h, int map_w, int max_num,
+                                         float out_size_factor, float voxel_x, float voxel_y, float pc_x, float pc_y,
+                                         const float *post_center_range_host, float score_threshold, int norm_bbox,
+                                         int heatmap_is_score, void *workspace, size_t workspace_bytes, void *stream) {
+  if (!strides_host) return BEVOPS_BAD_PARAM;
+  if (batch < 1 || num_classes < 1 || map_h < 1 || map_w < 1 || max_num < 1) return BEVOPS_BAD_PARAM;
+  // every map dense per batch item: item stride = channels * H * W
+  const long long chans[6] = {2, 1, 3, 2, 2, num_classes};
+  int64_t ex[18];
+  for (int i = 0; i < 6; ++i) {
+    ex[3 * i] = strides_host[2 * i];
+    ex[3 * i + 1] = strides_host[2 * i + 1];
+    ex[3 * i + 2] = chans[i] * map_h * map_w;
+  }
+  return bevops_centerpoint_decode_ex(dtype, reg, height, dim, rot, vel, heatmap, ex, boxes, scores, labels, count,
+                                      batch, num_classes, map_h, map_w, max_num, out_size_factor, voxel_x, voxel_y, pc_x,
+                                      pc_y, post_center_range_host, score_threshold, norm_bbox, heatmap_is_score,
+                                      workspace, workspace_bytes, stream);
 }

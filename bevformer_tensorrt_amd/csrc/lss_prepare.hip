@@ -19,6 +19,10 @@
 // order.  Stable by construction, correct for any interval length up to all points in one cell; two passes at the
 // 16 384 cells of BEVDet-R50.  Intervals are the run-length encoding of the sorted keys (flag, scan, ordered
 // compaction).  ranks_feat and ranks_bev are derived after the sort.  Every launch is sized by host values only.
+//
+// A batch of samples (bevops_lss_voxel_prepare_batched) is the same launches over batch * n_cams cameras: sample b
+// reads row b of calib (its own cameras and bda), the key is b * cells + cell (batch * cells for a dropped point), and
+// the digit count follows batch * cells.  At batch = 1 that is the single-sample build, launch for launch.
 #include <math.h>
 
 #include "common.h"
@@ -51,21 +55,25 @@ __device__ __forceinline__ void lss_mat3(const float *__restrict__ m, float &x, 
   x = ox; y = oy; z = oz;
 }
 
-// calib: per camera 24 floats [inverse(post_rots) 9 | post_trans 3 | combine 9 | trans 3], then bda 9.
-// keys[i] = cell of point i, or g.cells when it is dropped; hist[digit * nblocks + block] = digit-0 counts of the tile.
+// calib: one row of calib_stride floats per sample; per camera 24 floats [inverse(post_rots) 9 | post_trans 3 |
+// combine 9 | trans 3], then bda 9.  keys[i] = sample * g.cells + cell of point i, or `dropped` (= batch * g.cells) when
+// it is dropped; hist[digit * nblocks + block] = digit-0 counts of the tile.
 __global__ __launch_bounds__(kLssBlock) void lss_cell_kernel(
-    const float *__restrict__ frustum, const float *__restrict__ calib, LssGrid g, int n_cams, int dhw, int n,
-    unsigned *__restrict__ keys, int *__restrict__ hist, int nblocks, float *__restrict__ coor_out) {
+    const float *__restrict__ frustum, const float *__restrict__ calib, LssGrid g, int n_cams, int calib_stride,
+    unsigned dropped, int dhw, int n, unsigned *__restrict__ keys, int *__restrict__ hist, int nblocks,
+    float *__restrict__ coor_out) {
   __shared__ int h[256];
   h[threadIdx.x] = 0;
   __syncthreads();
-  const float *bda = calib + (size_t)n_cams * 24;
   for (int j = 0; j < kLssItems; ++j) {
     const int i = blockIdx.x * kLssTile + j * kLssBlock + threadIdx.x;
     if (i >= n) break;
-    const int cam = i / dhw;
-    const int f = i - cam * dhw;
-    const float *c = calib + (size_t)cam * 24;
+    const int gcam = i / dhw;        // camera over the batch
+    const int f = i - gcam * dhw;
+    const int b = gcam / n_cams;
+    const float *row = calib + (size_t)b * calib_stride;
+    const float *c = row + (size_t)(gcam - b * n_cams) * 24;
+    const float *bda = row + (size_t)n_cams * 24;
     float x = sub_rn(frustum[(size_t)f * 3 + 0], c[9]);
     float y = sub_rn(frustum[(size_t)f * 3 + 1], c[10]);
     float z = sub_rn(frustum[(size_t)f * 3 + 2], c[11]);
@@ -86,7 +94,8 @@ __global__ __launch_bounds__(kLssBlock) void lss_cell_kernel(
     const float ty = truncf(lss_div(sub_rn(y, g.lower[1]), g.interval[1]));
     const float tz = truncf(lss_div(sub_rn(z, g.lower[2]), g.interval[2]));
     const bool kept = tx >= 0.f && tx < g.size[0] && ty >= 0.f && ty < g.size[1] && tz >= 0.f && tz < g.size[2];
-    const unsigned key = kept ? (unsigned)((int)tz * g.nxy + (int)ty * g.nx + (int)tx) : (unsigned)g.cells;
+    const unsigned key =
+        kept ? (unsigned)b * (unsigned)g.cells + (unsigned)((int)tz * g.nxy + (int)ty * g.nx + (int)tx) : dropped;
     keys[i] = key;
     atomicAdd(&h[key & 255u], 1);
   }
@@ -299,31 +308,15 @@ inline bool lss_sizes_ok(int n_cams, int d, int h, int w, long &num_points) {
   return (long)d * h * w <= kLssMaxPoints && num_points <= kLssMaxPoints;
 }
 
-}  // namespace
-}  // namespace bevops
-
-using namespace bevops;
-
-extern "C" size_t bevops_lss_voxel_prepare_workspace_size(int n_cams, int d, int h, int w) {
-  if (n_cams <= 0 || d <= 0 || h <= 0 || w <= 0) return 0;
-  if ((long)n_cams * d > kLssMaxPoints || (long)h * w > kLssMaxPoints) return 0;
-  long np;
-  if (!lss_sizes_ok(n_cams, d, h, w, np)) return 0;
-  const size_t nblocks = ((size_t)np + kLssTile - 1) / kLssTile;
-  // two (key, payload) buffers, the digit counts [256][nblocks], their 256 row sums, the run starts per block
-  return (4 * lss_round((size_t)np) + lss_round(256 * nblocks) + 256 + lss_round(nblocks)) * sizeof(int32_t);
+// bytes for num_points points: two (key, payload) buffers, the digit counts [256][nblocks], their 256 row sums, the
+// run starts per block
+inline size_t lss_workspace_bytes(size_t np) {
+  const size_t nblocks = (np + kLssTile - 1) / kLssTile;
+  return (4 * lss_round(np) + lss_round(256 * nblocks) + 256 + lss_round(nblocks)) * sizeof(int32_t);
 }
 
-extern "C" int bevops_lss_voxel_prepare(const float *frustum, const float *calib, const float *grid_host,
-                                        int32_t *ranks_bev, int32_t *ranks_depth, int32_t *ranks_feat,
-                                        int32_t *interval_starts, int32_t *interval_lengths, int32_t *counts,
-                                        float *coor, int batch, int n_cams, int d, int h, int w, void *workspace,
-                                        size_t workspace_bytes, void *stream) {
-  if (!frustum || !calib || !grid_host || !ranks_bev || !ranks_depth || !ranks_feat || !interval_starts ||
-      !interval_lengths || !counts || !workspace)
-    return BEVOPS_BAD_PARAM;
-  if (batch <= 0 || n_cams <= 0 || d <= 0 || h <= 0 || w <= 0) return BEVOPS_BAD_PARAM;
-  LssGrid g;
+// grid_host -> g (nx, nxy, cells excepted); BEVOPS_BAD_PARAM for a value no grid can hold
+inline int lss_read_grid(const float *grid_host, LssGrid &g) {
   for (int a = 0; a < 3; ++a) {
     g.lower[a] = grid_host[a];
     g.interval[a] = grid_host[3 + a];
@@ -331,26 +324,29 @@ extern "C" int bevops_lss_voxel_prepare(const float *frustum, const float *calib
     if (!isfinite(g.lower[a]) || !isfinite(g.interval[a]) || !(g.interval[a] > 0.f)) return BEVOPS_BAD_PARAM;
     if (!isfinite(g.size[a]) || !(g.size[a] >= 1.f)) return BEVOPS_BAD_PARAM;
   }
-  if (batch != 1) return BEVOPS_NOT_SUPPORTED;
-  if ((long)n_cams * d > kLssMaxPoints || (long)h * w > kLssMaxPoints) return BEVOPS_NOT_SUPPORTED;
-  long np;
-  if (!lss_sizes_ok(n_cams, d, h, w, np)) return BEVOPS_NOT_SUPPORTED;
+  return BEVOPS_SUCCESS;
+}
+
+// cells = nx ny nz, or -1 when a size is not integral or the product exceeds kLssMaxCells
+inline double lss_cells(const LssGrid &g) {
   double cells = 1.0;
   for (int a = 0; a < 3; ++a) {
-    if (g.size[a] != floorf(g.size[a]) || g.size[a] > (float)kLssMaxCells) return BEVOPS_NOT_SUPPORTED;
+    if (g.size[a] != floorf(g.size[a]) || g.size[a] > (float)kLssMaxCells) return -1.0;
     cells *= (double)g.size[a];
   }
-  if (cells > (double)kLssMaxCells) return BEVOPS_NOT_SUPPORTED;
-  if (workspace_bytes < bevops_lss_voxel_prepare_workspace_size(n_cams, d, h, w) || !aligned16(workspace))
-    return BEVOPS_BAD_PARAM;
-  g.nx = (int)g.size[0];
-  g.nxy = g.nx * (int)g.size[1];
-  g.cells = (int)cells;
+  return cells > (double)kLssMaxCells ? -1.0 : cells;
+}
 
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int n = (int)np, dhw = d * h * w, hw = h * w;
+// The launches of both entries; every limit has been checked: n = batch * n_cams * d * h * w <= kLssMaxPoints,
+// batch * g.cells <= kLssMaxCells, the workspace holds lss_workspace_bytes(n).
+int lss_launch(const float *frustum, const float *calib, const LssGrid &g, int32_t *ranks_bev, int32_t *ranks_depth,
+               int32_t *ranks_feat, int32_t *interval_starts, int32_t *interval_lengths, int32_t *counts, float *coor,
+               int batch, int n_cams, int d, int h, int w, void *workspace, hipStream_t st) {
+  const int dhw = d * h * w, hw = h * w, n = batch * n_cams * dhw;
+  const int calib_stride = n_cams * 24 + 9;
+  const unsigned all_cells = (unsigned)batch * (unsigned)g.cells;
   const int nblocks = (n + kLssTile - 1) / kLssTile;
-  const int cap = n < g.cells ? n : g.cells;
+  const int cap = (unsigned)n < all_cells ? n : (int)all_cells;
   int32_t *ws = static_cast<int32_t *>(workspace);
   unsigned *keys[2] = {(unsigned *)ws, (unsigned *)(ws + 2 * lss_round(n))};
   int *vals[2] = {ws + lss_round(n), ws + 3 * lss_round(n)};
@@ -358,11 +354,11 @@ extern "C" int bevops_lss_voxel_prepare(const float *frustum, const float *calib
   int *totals = hist + lss_round((size_t)256 * nblocks);
   int *block_count = totals + 256;
 
-  int passes = 1;   // digits that hold the value `cells` (the key of a dropped point)
-  while (passes < 4 && ((unsigned)g.cells >> (8 * passes)) != 0) ++passes;
+  int passes = 1;   // digits that hold the value `all_cells` (the key of a dropped point)
+  while (passes < 4 && (all_cells >> (8 * passes)) != 0) ++passes;
 
-  hipLaunchKernelGGL(lss_cell_kernel, dim3(nblocks), dim3(kLssBlock), 0, st, frustum, calib, g, n_cams, dhw, n,
-                     keys[0], hist, nblocks, coor);
+  hipLaunchKernelGGL(lss_cell_kernel, dim3(nblocks), dim3(kLssBlock), 0, st, frustum, calib, g, n_cams, calib_stride,
+                     all_cells, dhw, n, keys[0], hist, nblocks, coor);
   int src = 0;
   for (int p = 0; p < passes; ++p) {
     if (p > 0)
@@ -376,13 +372,94 @@ extern "C" int bevops_lss_voxel_prepare(const float *frustum, const float *calib
                          keys[src ^ 1], vals[src ^ 1], hist, totals, n, 8 * p, nblocks);
     src ^= 1;
   }
-  hipLaunchKernelGGL(lss_flag_count_kernel, dim3(nblocks), dim3(kLssBlock), 0, st, keys[src], n, (unsigned)g.cells,
+  hipLaunchKernelGGL(lss_flag_count_kernel, dim3(nblocks), dim3(kLssBlock), 0, st, keys[src], n, all_cells,
                      block_count);
   hipLaunchKernelGGL(lss_scan_kernel, dim3(1), dim3(kLssScanBlock), 0, st, block_count, nblocks, counts);
-  hipLaunchKernelGGL(lss_emit_kernel, dim3(nblocks), dim3(kLssBlock), 0, st, keys[src], vals[src], n,
-                     (unsigned)g.cells, dhw, hw, block_count, ranks_bev, ranks_depth, ranks_feat, interval_starts, cap,
-                     counts);
+  hipLaunchKernelGGL(lss_emit_kernel, dim3(nblocks), dim3(kLssBlock), 0, st, keys[src], vals[src], n, all_cells, dhw,
+                     hw, block_count, ranks_bev, ranks_depth, ranks_feat, interval_starts, cap, counts);
   hipLaunchKernelGGL(lss_lengths_kernel, dim3((cap + kLssBlock - 1) / kLssBlock), dim3(kLssBlock), 0, st,
                      interval_starts, interval_lengths, cap, counts);
   return launch_status();
+}
+
+}  // namespace
+}  // namespace bevops
+
+using namespace bevops;
+
+extern "C" size_t bevops_lss_voxel_prepare_workspace_size(int n_cams, int d, int h, int w) {
+  if (n_cams <= 0 || d <= 0 || h <= 0 || w <= 0) return 0;
+  if ((long)n_cams * d > kLssMaxPoints || (long)h * w > kLssMaxPoints) return 0;
+  long np;
+  if (!lss_sizes_ok(n_cams, d, h, w, np)) return 0;
+  return lss_workspace_bytes((size_t)np);
+}
+
+extern "C" int bevops_lss_voxel_prepare(const float *frustum, const float *calib, const float *grid_host,
+                                        int32_t *ranks_bev, int32_t *ranks_depth, int32_t *ranks_feat,
+                                        int32_t *interval_starts, int32_t *interval_lengths, int32_t *counts,
+                                        float *coor, int batch, int n_cams, int d, int h, int w, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+  if (!frustum || !calib || !grid_host || !ranks_bev || !ranks_depth || !ranks_feat || !interval_starts ||
+      !interval_lengths || !counts || !workspace)
+    return BEVOPS_BAD_PARAM;
+  if (batch <= 0 || n_cams <= 0 || d <= 0 || h <= 0 || w <= 0) return BEVOPS_BAD_PARAM;
+  LssGrid g;
+  if (lss_read_grid(grid_host, g) != BEVOPS_SUCCESS) return BEVOPS_BAD_PARAM;
+  if (batch != 1) return BEVOPS_NOT_SUPPORTED;
+  if ((long)n_cams * d > kLssMaxPoints || (long)h * w > kLssMaxPoints) return BEVOPS_NOT_SUPPORTED;
+  long np;
+  if (!lss_sizes_ok(n_cams, d, h, w, np)) return BEVOPS_NOT_SUPPORTED;
+  const double cells = lss_cells(g);
+  if (cells < 0.0) return BEVOPS_NOT_SUPPORTED;
+  if (workspace_bytes < bevops_lss_voxel_prepare_workspace_size(n_cams, d, h, w) || !aligned16(workspace))
+    return BEVOPS_BAD_PARAM;
+  g.nx = (int)g.size[0];
+  g.nxy = g.nx * (int)g.size[1];
+  g.cells = (int)cells;
+  return lss_launch(frustum, calib, g, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, counts,
+                    coor, 1, n_cams, d, h, w, workspace, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+// num_points over the batch, or -1 beyond kLssMaxPoints (every partial product is tested, so nothing overflows)
+long lss_batched_points(int batch, int n_cams, int d, int h, int w) {
+  long np = 1;
+  const int f[5] = {batch, n_cams, d, h, w};
+  for (int v : f) {
+    np *= v;
+    if (np > kLssMaxPoints) return -1;
+  }
+  return np;
+}
+}  // namespace
+
+extern "C" size_t bevops_lss_voxel_prepare_batched_workspace_size(int batch, int n_cams, int d, int h, int w) {
+  if (batch <= 0 || n_cams <= 0 || d <= 0 || h <= 0 || w <= 0) return 0;
+  const long np = lss_batched_points(batch, n_cams, d, h, w);
+  return np < 0 ? 0 : lss_workspace_bytes((size_t)np);
+}
+
+extern "C" int bevops_lss_voxel_prepare_batched(const float *frustum, const float *calib, const float *grid_host,
+                                                int32_t *ranks_bev, int32_t *ranks_depth, int32_t *ranks_feat,
+                                                int32_t *interval_starts, int32_t *interval_lengths, int32_t *counts,
+                                                float *coor, int batch, int n_cams, int d, int h, int w,
+                                                void *workspace, size_t workspace_bytes, void *stream) {
+  if (!frustum || !calib || !grid_host || !ranks_bev || !ranks_depth || !ranks_feat || !interval_starts ||
+      !interval_lengths || !counts || !workspace)
+    return BEVOPS_BAD_PARAM;
+  if (batch <= 0 || n_cams <= 0 || d <= 0 || h <= 0 || w <= 0) return BEVOPS_BAD_PARAM;
+  LssGrid g;
+  if (lss_read_grid(grid_host, g) != BEVOPS_SUCCESS) return BEVOPS_BAD_PARAM;
+  if (lss_batched_points(batch, n_cams, d, h, w) < 0) return BEVOPS_NOT_SUPPORTED;
+  const double cells = lss_cells(g);
+  if (cells < 0.0 || cells * (double)batch > (double)kLssMaxCells) return BEVOPS_NOT_SUPPORTED;
+  if (workspace_bytes < bevops_lss_voxel_prepare_batched_workspace_size(batch, n_cams, d, h, w) ||
+      !aligned16(workspace))
+    return BEVOPS_BAD_PARAM;
+  g.nx = (int)g.size[0];
+  g.nxy = g.nx * (int)g.size[1];
+  g.cells = (int)cells;
+  return lss_launch(frustum, calib, g, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, counts,
+                    coor, batch, n_cams, d, h, w, workspace, static_cast<hipStream_t>(stream));
 }

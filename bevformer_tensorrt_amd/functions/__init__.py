@@ -33,7 +33,8 @@ from .inverse import inverse
 from .decode import nms_free_decode, centerpoint_decode
 from .nms import bev_nms, nms_bev, circle_nms, bev_iou
 from .decode2d import centernet_decode, yolox_decode, box_nms
-from .lss_prepare import lss_voxel_prepare, lss_lidar_coor, bev_pool_v2_indirect
+from .lss_prepare import (lss_voxel_prepare, lss_lidar_coor, bev_pool_v2_indirect, lss_voxel_prepare_batched,
+                          lss_lidar_coor_batched)
 from .calibrate import calib_state_size, calib_collect, calib_threshold
 from .bev_half import lss_depth_split, upsample_bilinear_concat_nhwc, lss_depth_split_q, upsample_bilinear_nhwc_q
 from .deconv import conv_transpose2d_nhwc, pack_deconv4x4s2, deconv_packed_weight, conv_transpose2d_q_nhwc, quantize_deconv_weight
@@ -63,7 +64,7 @@ __all__ = [
     "nms_free_decode", "centerpoint_decode",
     "bev_nms", "nms_bev", "circle_nms", "bev_iou",
     "centernet_decode", "yolox_decode", "box_nms",
-    "lss_voxel_prepare", "lss_lidar_coor", "bev_pool_v2_indirect",
+    "lss_voxel_prepare", "lss_lidar_coor", "bev_pool_v2_indirect", "lss_voxel_prepare_batched", "lss_lidar_coor_batched",
     "calib_state_size", "calib_collect", "calib_threshold",
     "bevdet_test_augmentation", "bevdet_post_transform", "image_resize_plan", "image_resize_crop_normalize",
     "BEVFORMER_IMAGE_PIPELINES", "scaled_size", "scale_lidar2img", "image_normalize_resize_pad",

@@ -104,6 +104,20 @@ def _map_strides(t, name):
     return t.contiguous(), H * W, 1
 
 
+def _slice_strides(t):
+    """(channel, pixel, item) strides of a [B, C, H, W] map with B > 1 that is a channel slice of ONE wider
+    channels-last tensor [B, H, W, Ct] (strides (H * W * Ct, 1, W * Ct, Ct), Ct > C) -- a batch of BEVDet's packed head
+    output -- for bevops_centerpoint_decode_ex; None for anything else (dense maps keep the plain entry)."""
+    B, C, H, W = t.shape
+    if B < 2 or H * W == 0 or t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last):
+        return None
+    ct = t.stride(3) if W > 1 else (t.stride(2) if H > 1 else 0)
+    if ct > C and (C == 1 or t.stride(1) == 1) and (W == 1 or t.stride(3) == ct) and (H == 1 or t.stride(2) == W * ct) \
+            and t.stride(0) == H * W * ct:
+        return 1, ct, H * W * ct
+    return None
+
+
 def centerpoint_decode(reg, height, dim, rot, vel, heatmap, max_num, post_center_range, pc_range, out_size_factor,
                        voxel_size, score_threshold=None, norm_bbox=True, heatmap_is_score=False, padded=False):
     """The six head maps of BEVDet.forward, [B, c, H, W] with c = 2, 1, 3, 2, 2, num_classes, fp32 or fp16 on the GPU,
@@ -121,31 +135,45 @@ def centerpoint_decode(reg, height, dim, rot, vel, heatmap, max_num, post_center
         raise ValueError(f"centerpoint_decode: heatmap must be [B, num_classes, H, W], got {tuple(heatmap.shape)}")
     B, nc, H, W = heatmap.shape
     dt = _lib.torch_dtype_code(heatmap)
-    ptrs, strides = [], []
+    ptrs, strides, items = [], [], []
     keep = []
     for t, name, c in zip(maps, names, chans):
         if t is None:
             ptrs.append(None)
-            strides += [1, 1]
+            strides.append((1, 1))
+            items.append(c * H * W)
             continue
         if tuple(t.shape) != (B, c, H, W):
             raise ValueError(f"centerpoint_decode: {name} must be {(B, c, H, W)}, got {tuple(t.shape)}")
         if t.dtype != heatmap.dtype or t.device != heatmap.device:
             raise TypeError(f"centerpoint_decode: {name} differs from heatmap in dtype or device")
-        t, cs, ps = _map_strides(t, name)
+        sliced = _slice_strides(t)
+        if sliced is not None:
+            cs, ps, item = sliced
+        else:
+            t, cs, ps = _map_strides(t, name)
+            item = None
         keep.append(t)
         ptrs.append(t.data_ptr())
-        strides += [cs, ps]
+        strides.append((cs, ps))
+        items.append(item)
+    # B > 1 channel slices of a wider channels-last tensor carry their own batch-item stride: the _ex entry
+    ex = any(s is not None for s, t in zip(items, maps) if t is not None)
     max_num = int(max_num)
     rng = _range6(post_center_range)
-    strides_c = (ctypes.c_int32 * 12)(*strides)
+    if ex:
+        flat = [v for (cs, ps), item, c in zip(strides, items, chans) for v in (cs, ps, c * H * W if item is None else item)]
+        strides_c = (ctypes.c_int64 * 18)(*flat)
+    else:
+        strides_c = (ctypes.c_int32 * 12)(*(v for pair in strides for v in pair))
     boxes, scores, labels, count = _outputs(torch.empty, B, max_num, 9, heatmap.device)
     handle = _lib.load_library()
     stream = _lib.current_stream_ptr(heatmap.device)
     nws = handle.bevops_centerpoint_decode_workspace_size(B, nc, H, W, max_num)
     ws = _ws.lend("centerpoint_decode", nws, heatmap.device, stream) if nws else None
+    entry = handle.bevops_centerpoint_decode_ex if ex else handle.bevops_centerpoint_decode
     with torch.cuda.device(heatmap.device):
-        st = handle.bevops_centerpoint_decode(
+        st = entry(
             dt, *ptrs, strides_c, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), B, nc, H, W,
             max_num, float(out_size_factor), float(voxel_size[0]), float(voxel_size[1]), float(pc_range[0]),
             float(pc_range[1]), rng, _threshold(score_threshold), int(bool(norm_bbox)), int(bool(heatmap_is_score)),

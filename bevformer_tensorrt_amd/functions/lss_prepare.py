@@ -5,7 +5,9 @@ the reference's registry (the reference evaluates the ranks with host-side torch
 tools/bevdet/evaluate_trt.py:107-127), so TRT_FUNCTIONS does not list them.
 
 `calib` is the packed fp32 buffer of LSSViewTransformer.calibration_matrices: per camera
-[inverse(post_rots) 9 | post_trans 3 | combine 9 | trans 3], then bda 9."""
+[inverse(post_rots) 9 | post_trans 3 | combine 9 | trans 3], then bda 9.  The `_batched` calls take one such row per sample,
+calib [B, n_cams * 24 + 9] (LSSViewTransformer.calibration_matrices_batched), and return the reference's batched arrays:
+ranks_bev = b * cells + cell, ranks_depth / ranks_feat over B * n_cams cameras."""
 import ctypes
 
 import torch
@@ -29,7 +31,7 @@ def _grid9(grid_lower_bound, grid_interval, grid_size):
     return (ctypes.c_float * 9)(*vals), vals
 
 
-def _prepare(frustum, calib, grid_lower_bound, grid_interval, grid_size, want_coor):
+def _prepare(frustum, calib, grid_lower_bound, grid_interval, grid_size, want_coor, batched=False):
     assert frustum.is_cuda and calib.is_cuda, "lss_voxel_prepare: frustum / calib must be on the GPU"
     if frustum.dtype != torch.float32 or calib.dtype != torch.float32:
         raise TypeError("lss_voxel_prepare: frustum and calib are float32")
@@ -37,26 +39,39 @@ def _prepare(frustum, calib, grid_lower_bound, grid_interval, grid_size, want_co
         raise ValueError(f"frustum is [D, H, W, 3], got {tuple(frustum.shape)}")
     handle = _lib.load_library()
     dev = frustum.device
-    frustum, calib = frustum.contiguous(), calib.contiguous().view(-1)
-    n = calib_cameras(calib)
+    if batched:
+        if calib.dim() != 2 or calib.shape[0] < 1:
+            raise ValueError(f"calib is [B, n_cams * {CALIB_PER_CAMERA} + {CALIB_TAIL}], got {tuple(calib.shape)}")
+        batch = calib.shape[0]
+        frustum, calib = frustum.contiguous(), calib.contiguous()
+        n = calib_cameras(calib[0])
+    else:
+        batch = 1
+        frustum, calib = frustum.contiguous(), calib.contiguous().view(-1)
+        n = calib_cameras(calib)
     d, h, w, _ = frustum.shape
     grid, vals = _grid9(grid_lower_bound, grid_interval, grid_size)
-    num_points = n * d * h * w
-    cells = vals[6] * vals[7] * vals[8]
+    num_points = batch * n * d * h * w
+    cells = batch * vals[6] * vals[7] * vals[8]
     cap = int(min(num_points, cells)) if cells == cells and cells >= 1 else 1
     i32 = dict(dtype=torch.int32, device=dev)
     rb, rd, rf = (torch.empty(num_points, **i32) for _ in range(3))
     ist, il = torch.empty(cap, **i32), torch.empty(cap, **i32)
     counts = torch.empty(2, **i32)
-    coor = torch.empty(1, n, d, h, w, 3, dtype=torch.float32, device=dev) if want_coor else None
-    ws_bytes = handle.bevops_lss_voxel_prepare_workspace_size(n, d, h, w)
+    coor = torch.empty(batch, n, d, h, w, 3, dtype=torch.float32, device=dev) if want_coor else None
+    if batched:
+        name, entry = "bevops_lss_voxel_prepare_batched", handle.bevops_lss_voxel_prepare_batched
+        ws_bytes = handle.bevops_lss_voxel_prepare_batched_workspace_size(batch, n, d, h, w)
+    else:
+        name, entry = "bevops_lss_voxel_prepare", handle.bevops_lss_voxel_prepare
+        ws_bytes = handle.bevops_lss_voxel_prepare_workspace_size(n, d, h, w)
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        st = handle.bevops_lss_voxel_prepare(
+        st = entry(
             frustum.data_ptr(), calib.data_ptr(), ctypes.cast(grid, ctypes.c_void_p), rb.data_ptr(), rd.data_ptr(),
             rf.data_ptr(), ist.data_ptr(), il.data_ptr(), counts.data_ptr(), coor.data_ptr() if want_coor else None,
-            1, n, d, h, w, ws.data_ptr(), ws_bytes, _lib.current_stream_ptr(dev))
-    _lib.check(st, "bevops_lss_voxel_prepare")
+            batch, n, d, h, w, ws.data_ptr(), ws_bytes, _lib.current_stream_ptr(dev))
+    _lib.check(st, name)
     return (rb, rd, rf, ist, il, counts), coor
 
 
@@ -68,13 +83,30 @@ def lss_voxel_prepare(frustum, calib, grid_lower_bound, grid_interval, grid_size
     padded=False: the counts are read once and the five tensors come back trimmed, in the reference's form and argument
     order -- or five None when no point is kept, as the reference returns.  Inside a cell the points are in ascending
     point index (the stable order; the reference's argsort leaves it unspecified)."""
-    out, _ = _prepare(frustum, calib, grid_lower_bound, grid_interval, grid_size, False)
+    return _trimmed(_prepare(frustum, calib, grid_lower_bound, grid_interval, grid_size, False)[0], padded)
+
+
+def _trimmed(out, padded):
     if padded:
         return out
     n_pts, n_int = out[5].tolist()
     if n_int == 0:
         return None, None, None, None, None
     return out[0][:n_pts], out[1][:n_pts], out[2][:n_pts], out[3][:n_int], out[4][:n_int]
+
+
+def lss_voxel_prepare_batched(frustum, calib, grid_lower_bound, grid_interval, grid_size, padded=True):
+    """`lss_voxel_prepare` for B samples in one call: calib [B, n_cams * 24 + 9], one packed row per sample (its own
+    cameras and bda).  The reference's batched arrays: ranks_bev = b * cells + cell, ranks_depth the point index over
+    B N D H W, ranks_feat the index into [B N, H, W]; interval arrays of capacity min(points, B * cells); counts [2] =
+    the totals over the batch.  Same kernels and order rule; at B = 1 bit-identical to `lss_voxel_prepare`.
+    B N D H W <= 2^22 and B * cells <= 2^24."""
+    return _trimmed(_prepare(frustum, calib, grid_lower_bound, grid_interval, grid_size, False, batched=True)[0], padded)
+
+
+def lss_lidar_coor_batched(frustum, calib, grid_lower_bound, grid_interval, grid_size):
+    """The lidar-frame coordinates [B, N, D, H, W, 3] fp32 of the batched index build (calib [B, n_cams * 24 + 9])."""
+    return _prepare(frustum, calib, grid_lower_bound, grid_interval, grid_size, True, batched=True)[1]
 
 
 def lss_lidar_coor(frustum, calib, grid_lower_bound, grid_interval, grid_size):
@@ -84,10 +116,12 @@ def lss_lidar_coor(frustum, calib, grid_lower_bound, grid_interval, grid_size):
 
 
 def bev_pool_v2_indirect(depth, feat, ranks_depth, ranks_feat, ranks_bev, interval_starts, interval_lengths, counts,
-                         out_height=128, out_width=128, scales=None):
+                         out_height=128, out_width=128, scales=None, batch=1):
     """bev_pool_v2 (any of its three flavours, by dtype; int8 takes scales = (depth, feat, out)) on the PADDED arrays
     of lss_voxel_prepare: the interval count is counts[1], read on the device; the capacity of interval_starts sizes
-    the launch.  Bit-identical to bev_pool_v2 on the trimmed arrays."""
+    the launch.  Bit-identical to bev_pool_v2 on the trimmed arrays.  batch = B with the arrays of
+    lss_voxel_prepare_batched (depth / feat over B * n_cams cameras) returns [B, out_height, out_width, C]: the same C
+    entry with out_height = B * out_height, since the batched ranks_bev carry b * out_height * out_width."""
     assert depth.is_cuda and feat.is_cuda, "bev_pool_v2_indirect: depth/feat must be on the GPU"
     if depth.dtype != feat.dtype:
         raise TypeError(f"depth dtype {depth.dtype} != feat dtype {feat.dtype}")
@@ -103,12 +137,15 @@ def bev_pool_v2_indirect(depth, feat, ranks_depth, ranks_feat, ranks_bev, interv
         raise ValueError("counts holds {n_points, n_intervals}; interval_starts / interval_lengths share one capacity")
     scales = scales or (1.0, 1.0, 1.0)
     c = feat.shape[-1]
-    out = torch.empty((1, out_height, out_width, c), dtype=feat.dtype, device=dev)
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f"bev_pool_v2_indirect: batch = {batch}")
+    out = torch.empty((batch, out_height, out_width, c), dtype=feat.dtype, device=dev)
     with torch.cuda.device(dev):
         st = handle.bevops_bev_pool_v2_forward_indirect(
             _lib.torch_dtype_code(feat), depth.data_ptr(), feat.data_ptr(), ranks_depth.data_ptr(),
             ranks_feat.data_ptr(), ranks_bev.data_ptr(), interval_starts.data_ptr(), interval_lengths.data_ptr(),
-            counts.data_ptr() + 4, out.data_ptr(), c, interval_starts.numel(), out_height, out_width,
+            counts.data_ptr() + 4, out.data_ptr(), c, interval_starts.numel(), batch * out_height, out_width,
             float(scales[0]), float(scales[1]), float(scales[2]), _lib.current_stream_ptr(dev))
     _lib.check(st, "bevops_bev_pool_v2_forward_indirect")
     return out

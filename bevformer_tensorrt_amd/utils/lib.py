@@ -177,6 +177,8 @@ SIGNATURES = {
     "bevops_centerpoint_decode_workspace_size": (c_size_t, [c_int] * 5),
     "bevops_centerpoint_decode": (c_int, [c_int] + [c_void_p] * 11 + [c_int] * 5 + [c_float] * 5 +
                                   [c_void_p, c_float, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "bevops_centerpoint_decode_ex": (c_int, [c_int] + [c_void_p] * 11 + [c_int] * 5 + [c_float] * 5 +
+                                     [c_void_p, c_float, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "bevops_bev_nms_workspace_size": (c_size_t, [c_int, c_int]),
     "bevops_bev_nms": (c_int, [c_int] + [c_void_p] * 9 + [c_int] * 4 + [c_float, c_void_p, c_int, c_int, c_void_p,
                                                                         c_size_t, c_void_p]),
@@ -190,6 +192,8 @@ SIGNATURES = {
                                                 c_void_p]),
     "bevops_lss_voxel_prepare_workspace_size": (c_size_t, [c_int] * 4),
     "bevops_lss_voxel_prepare": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
+    "bevops_lss_voxel_prepare_batched_workspace_size": (c_size_t, [c_int] * 5),
+    "bevops_lss_voxel_prepare_batched": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
     "bevops_bev_pool_v2_forward_indirect": (c_int, [c_int] + [c_void_p] * 9 + [c_int] * 4 + [c_float] * 3 + [c_void_p]),
     "bevops_calib_state_size": (c_size_t, []),
     "bevops_calib_collect": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_void_p]),

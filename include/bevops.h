@@ -1109,6 +1109,12 @@ int bevops_inverse_forward(int dtype, const void *input, void *output, int batch
  * zero), reg may be NULL (+ 0.5).  max_num <= 4 096, else BEVOPS_NOT_SUPPORTED.  workspace:
  * bevops_centerpoint_decode_workspace_size bytes, 8-byte aligned (0 = none needed: the heat map fits one
  * workgroup's selection, one launch; otherwise two launches); a NULL or short one is BEVOPS_BAD_PARAM.
+ *
+ * bevops_centerpoint_decode_ex: the same call with strides_host[18] (int64) = (channel stride, pixel stride, ITEM
+ * stride) in elements per map, so a batch of maps that are channel slices of one wider channels-last tensor
+ * [batch, H, W, Ct] -- BEVDet's packed head output -- is read in place: (1, Ct, H * W * Ct).  Every stride >= 1, channel
+ * and pixel strides below 2^31, else BEVOPS_BAD_PARAM.  bevops_centerpoint_decode is this entry with item stride =
+ * channels * H * W; same kernels, same bits.
  * ------------------------------------------------------------------------ */
 int bevops_nms_free_decode(int dtype, const void *cls_logits, const void *bbox_preds, float *boxes, float *scores,
                            int32_t *labels, int32_t *count, int batch, int num_query, int num_classes, int max_num,
@@ -1121,6 +1127,13 @@ int bevops_centerpoint_decode(int dtype, const void *reg, const void *height, co
                               int map_w, int max_num, float out_size_factor, float voxel_x, float voxel_y, float pc_x,
                               float pc_y, const float *post_center_range_host, float score_threshold, int norm_bbox,
                               int heatmap_is_score, void *workspace, size_t workspace_bytes, void *stream);
+int bevops_centerpoint_decode_ex(int dtype, const void *reg, const void *height, const void *dim, const void *rot,
+                                 const void *vel, const void *heatmap, const int64_t *strides_host, float *boxes,
+                                 float *scores, int32_t *labels, int32_t *count, int batch, int num_classes, int map_h,
+                                 int map_w, int max_num, float out_size_factor, float voxel_x, float voxel_y,
+                                 float pc_x, float pc_y, const float *post_center_range_host, float score_threshold,
+                                 int norm_bbox, int heatmap_is_score, void *workspace, size_t workspace_bytes,
+                                 void *stream);
 
 /* ------------------------------------------------------------------------
  * BEV non-maximum suppression (csrc/nms.hip): what CenterHead.get_bboxes does behind the coder
@@ -1297,16 +1310,35 @@ int bevops_box_nms(const float *boxes_in, const float *scores_in, const int32_t 
  *   Launches: 1 (cells + first digit counts) + 2 or 3 per 8-bit digit of `cells` (two digits up to 65 535 cells) + 4
  *   (run starts, scan, emit, lengths); none sized by a device value.
  *
+ * bevops_lss_voxel_prepare_batched: the reference's batched form (get_lidar_coor and voxel_pooling_prepare_v2 carry B
+ *   through) for `batch` samples in one call, same kernels, same arithmetic, same stable sort and run-length pass.
+ *   calib [batch][n_cams * 24 + 9]: each row is the packed buffer above, so every sample has its own cameras and bda.
+ *   Key of a kept point = b * cells + cell (batch * cells for a dropped one); the number of 8-bit passes follows
+ *   batch * cells.  OUTPUTS: ranks_bev = b * cells + cell; ranks_depth = the point index over batch n_cams d h w;
+ *   ranks_feat = (ranks_depth / (d h w)) (h w) + ranks_depth % (h w) (the reference's index into [B N, h, w]);
+ *   num_points = batch n_cams d h w entries each; interval arrays: min(num_points, batch * cells) entries; counts[2] =
+ *   the totals over the batch; zero behind the counts; coor NULL or [batch, n_cams, d, h, w, 3].
+ *   LIMITS: as above, with num_points <= 2^22 and batch * cells <= 2^24, else BEVOPS_NOT_SUPPORTED (size query 0;
+ *   BEVDet-R50 fits up to batch 16); batch <= 0 is BEVOPS_BAD_PARAM.  At batch = 1 every output is bit-identical to
+ *   bevops_lss_voxel_prepare's.
+ *
  * bevops_bev_pool_v2_forward_indirect: bevops_bev_pool_v2_forward with the interval count read on the device:
  *   n_intervals_dev[0] (clamped to [0, max_intervals]); max_intervals, a host value, sizes the grid and is the
  *   capacity of interval_starts / interval_lengths.  Same kernels and per-interval arithmetic: for equal index arrays
- *   the output is bit-identical to bevops_bev_pool_v2_forward in F32, F16 and I8.
+ *   the output is bit-identical to bevops_bev_pool_v2_forward in F32, F16 and I8.  A batch of B grids is this call
+ *   with out_height = B * H: the batched ranks_bev already carry b * H * W, so the output is [B, H, W, channels].
  * ------------------------------------------------------------------------ */
 size_t bevops_lss_voxel_prepare_workspace_size(int n_cams, int d, int h, int w);
 int bevops_lss_voxel_prepare(const float *frustum, const float *calib, const float *grid_host, int32_t *ranks_bev,
                              int32_t *ranks_depth, int32_t *ranks_feat, int32_t *interval_starts,
                              int32_t *interval_lengths, int32_t *counts, float *coor, int batch, int n_cams, int d,
                              int h, int w, void *workspace, size_t workspace_bytes, void *stream);
+size_t bevops_lss_voxel_prepare_batched_workspace_size(int batch, int n_cams, int d, int h, int w);
+int bevops_lss_voxel_prepare_batched(const float *frustum, const float *calib, const float *grid_host,
+                                     int32_t *ranks_bev, int32_t *ranks_depth, int32_t *ranks_feat,
+                                     int32_t *interval_starts, int32_t *interval_lengths, int32_t *counts, float *coor,
+                                     int batch, int n_cams, int d, int h, int w, void *workspace,
+                                     size_t workspace_bytes, void *stream);
 int bevops_bev_pool_v2_forward_indirect(int dtype, const void *depth, const void *feat, const int32_t *ranks_depth,
                                         const int32_t *ranks_feat, const int32_t *ranks_bev,
                                         const int32_t *interval_starts, const int32_t *interval_lengths,
