@@ -1,0 +1,300 @@
+"""BEVDepth's view transformer: the camera-aware DepthNet with ASPP in front of the LSS pooling
+(third_party/bev_mmdet3d/models/necks/view_transformer.py: DepthNet :534-712, ASPP :417-481, Mlp :492, SELayer :519,
+LSSViewTransformerBEVDepth :781-895), re-hosted without mmcv / mmdet with the reference's attribute names.  Frozen
+BatchNorm2d is folded into the convolution in front of it, as everywhere in bevdet.py (checkpoint.py folds while
+loading); Dropout is the identity.  design/bevdepth.md has the operation orders and what was left out.
+
+Two data paths through the same weights:
+  * plain (`DepthNet.forward`): the reference's op sequence in torch -- F.conv2d(dilation=), adaptive_avg_pool2d,
+    interpolate, cat, x * gate -- on any device and dtype;
+  * fast (`DepthNet.forward_hip`): channels-last fp16 CUDA tensors with bev_half="hip".  The camera gates in one
+    launch from the fp32 calibration values (functions.lss_camera_gate), reduce_conv and the three BasicBlocks on the
+    tiled convolution, both gated copies in one launch (se_gate2_nhwc), the four ASPP branches into four slices of ONE
+    buffer (conv_slice_nhwc, three of them dilated), ASPP's pooled branch as a per-image bias of conv1
+    (global_avgpool_nhwc + two few-row GEMMs: a bilinear up-sampling of a 1 x 1 map is a constant), context_conv and
+    the last 1 x 1 into the feature / depth-logit columns of the row buffer lss_depth_split reads.  No library
+    convolution, pooling, interpolation, torch.cat or layout copy."""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .bevdet import BasicBlock, LSSViewTransformer, _rule_dispatch
+from .functions.multi_scale_deformable_attn import _TensorCache
+
+MLP_INPUTS = 27
+ASPP_DILATIONS = (1, 6, 12, 18)
+
+
+class Mlp(nn.Module):
+    def __init__(self, in_features, hidden_features, out_features):
+        super().__init__()
+        self.fc1, self.fc2 = nn.Linear(in_features, hidden_features), nn.Linear(hidden_features, out_features)
+
+    def forward(self, x):
+        return self.fc2(F.relu(self.fc1(x)))
+
+
+class SELayer(nn.Module):
+    def __init__(self, channels):
+        super().__init__()
+        self.conv_reduce, self.conv_expand = nn.Conv2d(channels, channels, 1), nn.Conv2d(channels, channels, 1)
+
+    def gate(self, x_se):
+        return torch.sigmoid(self.conv_expand(F.relu(self.conv_reduce(x_se))))
+
+    def forward(self, x, x_se):
+        return x * self.gate(x_se)
+
+
+class ASPP(nn.Module):
+    """aspp1 .. aspp4, global_avg_pool and conv1 each stand for the reference's convolution WITH its BatchNorm (and
+    ReLU): _ASPPModule.atrous_conv + bn, global_avg_pool[1] + [2], conv1 + bn1."""
+
+    def __init__(self, inplanes, mid_channels):
+        super().__init__()
+        d = ASPP_DILATIONS
+        self.aspp1 = nn.Conv2d(inplanes, mid_channels, 1)
+        self.aspp2 = nn.Conv2d(inplanes, mid_channels, 3, 1, d[1], d[1])
+        self.aspp3 = nn.Conv2d(inplanes, mid_channels, 3, 1, d[2], d[2])
+        self.aspp4 = nn.Conv2d(inplanes, mid_channels, 3, 1, d[3], d[3])
+        self.global_avg_pool = nn.Conv2d(inplanes, mid_channels, 1)
+        self.conv1 = nn.Conv2d(5 * mid_channels, inplanes, 1)
+
+    def branches(self):
+        return (self.aspp1, self.aspp2, self.aspp3, self.aspp4)
+
+    def forward(self, x):
+        xs = [F.relu(F.conv2d(x, m.weight, m.bias, 1, m.padding, m.dilation)) for m in self.branches()]
+        x5 = F.relu(self.global_avg_pool(F.adaptive_avg_pool2d(x, (1, 1))))
+        xs.append(F.interpolate(x5, size=x.shape[2:], mode="bilinear", align_corners=True))
+        return F.relu(self.conv1(torch.cat(xs, dim=1)))
+
+
+def fold_pooled_branch(aspp, pooled):
+    """ASPP's fifth branch as a per-image bias of conv1: pooled [n, inplanes] (the global average) ->
+    conv1.weight[:, 4 mid:] @ relu(global_avg_pool(pooled)) + conv1.bias, [n, inplanes].  In the tensors' dtype; the
+    statement the fast path's two few-row GEMMs evaluate."""
+    mid = aspp.aspp1.out_channels
+    g = F.relu(F.linear(pooled, aspp.global_avg_pool.weight.flatten(1), aspp.global_avg_pool.bias))
+    return F.linear(g, aspp.conv1.weight.flatten(1)[:, 4 * mid:], aspp.conv1.bias)
+
+
+class DepthNet(nn.Module):
+    def __init__(self, in_channels, mid_channels, context_channels, depth_channels, use_aspp=True, aspp_mid_channels=-1,
+                 use_dcn=False, stereo=False):
+        super().__init__()
+        if use_dcn:
+            raise NotImplementedError("DepthNet(use_dcn=True): the reference's mmcv DCN (DCNv1, groups=4) has no "
+                                      "channels-last kernel and no CPU statement in this package (DESIGN.md section 8)")
+        if stereo:
+            raise NotImplementedError("DepthNet(stereo=True): the BEVStereo cost volume is not built (DESIGN.md section 8)")
+        self.mid_channels, self.context_channels, self.depth_channels = mid_channels, context_channels, depth_channels
+        self.reduce_conv = nn.Conv2d(in_channels, mid_channels, 3, 1, 1)
+        self.context_conv = nn.Conv2d(mid_channels, context_channels, 1)
+        self.bn = nn.BatchNorm1d(MLP_INPUTS)
+        self.depth_mlp, self.depth_se = Mlp(MLP_INPUTS, mid_channels, mid_channels), SELayer(mid_channels)
+        self.context_mlp, self.context_se = Mlp(MLP_INPUTS, mid_channels, mid_channels), SELayer(mid_channels)
+        layers = [BasicBlock(mid_channels, mid_channels, 1, False) for _ in range(3)]
+        if use_aspp:
+            layers.append(ASPP(mid_channels, mid_channels if aspp_mid_channels < 0 else aspp_mid_channels))
+        layers.append(nn.Conv2d(mid_channels, depth_channels, 1))
+        self.depth_conv = nn.ModuleList(layers)          # (the reference's nn.Sequential: the same indices)
+        self.use_aspp = use_aspp
+
+    @property
+    def aspp(self):
+        return self.depth_conv[3] if self.use_aspp else None
+
+    # ---- plain: DepthNet.forward :680-712
+    def gates(self, mlp_input):
+        """(depth gate, context gate), each [n, mid, 1, 1], in mlp_input's dtype."""
+        v = self.bn(mlp_input.reshape(-1, mlp_input.shape[-1]))
+        return (self.depth_se.gate(self.depth_mlp(v)[..., None, None]),
+                self.context_se.gate(self.context_mlp(v)[..., None, None]))
+
+    def forward(self, x, mlp_input):
+        gate_d, gate_c = self.gates(mlp_input.to(x.dtype))
+        x = F.relu(self.reduce_conv(x))
+        context = self.context_conv(x * gate_c)
+        depth = x * gate_d
+        for m in self.depth_conv:
+            if isinstance(m, BasicBlock):
+                depth = F.relu(m.conv2(F.relu(m.conv1(depth))) + depth)
+            else:
+                depth = m(depth)
+        return torch.cat([depth, context], dim=1)
+
+    # ---- fast
+    def row_layout(self):
+        """The row buffer lss_depth_split reads: features in columns 0 .. C, the depth logits from C rounded up to 8,
+        D padded to a multiple of 8 with zero weight rows (exact zero columns): `merge_depth_net`'s layout."""
+        off = (self.context_channels + 7) // 8 * 8
+        dpad = (self.depth_channels + 7) // 8 * 8
+        return dict(row_stride=off + dpad, feat_offset=0, depth_offset=off, depth_padded=dpad)
+
+    def fast_operands(self, build=True):
+        """The derived operands of `forward_hip` on the weights' device: the packed gate block, conv1 split into its
+        four-branch part and the pooled branch's columns, the padded last convolution, and the taps-major weights of
+        every conv_slice layer.  Cached on the stamps of every parameter and buffer, rebuilt when one changes.
+        build=False: None when missing or stale.  Never built under capture (RuntimeError)."""
+        from .functions import lss_depthnet as G
+        from .functions import yolox_ops as Y
+        stamp = tuple(_TensorCache._stamp(t) for t in list(self.parameters()) + list(self.buffers()))
+        hit = self.__dict__.get("_fast_operands")
+        if hit is not None and hit[0] == stamp:
+            return hit[1]
+        if not build:
+            return None
+        w = self.reduce_conv.weight
+        if w.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DepthNet: the packed operands are missing or stale and the stream is capturing; call "
+                               "BEVDet.prepare_bev_half() (or the model once, eagerly) before the capture")
+        lay, mid = self.row_layout(), self.mid_channels
+        last = self.depth_conv[-1]
+        wd = w.new_zeros((lay["depth_padded"], mid, 1, 1))
+        wd[:self.depth_channels] = last.weight.detach()
+        bd = w.new_zeros((lay["depth_padded"],))
+        bd[:self.depth_channels] = last.bias.detach()
+        ops = dict(gate=G.camera_gate_packed(self.bn, self.depth_mlp, self.depth_se, self.context_mlp, self.context_se),
+                   wd=wd, bd=bd, layout=lay)
+        slices = [(self.context_conv.weight, mid, lay["depth_offset"]), (wd, mid, lay["depth_padded"])]
+        if self.use_aspp:
+            a = self.aspp
+            amid = a.aspp1.out_channels
+            if amid % 8:
+                raise NotImplementedError("DepthNet fast path: aspp_mid_channels must be a multiple of 8")
+            ops["conv1_main"] = a.conv1.weight.detach()[:, :4 * amid].contiguous()
+            ops["conv1_pool"] = a.conv1.weight.detach().flatten(1)[:, 4 * amid:].contiguous()
+            ops["pool_w"] = a.global_avg_pool.weight.detach().flatten(1).contiguous()
+            slices += [(m.weight, mid, amid) for m in a.branches()] + [(ops["conv1_main"], 4 * amid, mid)]
+        if w.is_cuda and w.dtype == torch.float16:
+            for t, cin, cout in slices:
+                Y.conv_slice_packed_weight(t, cin, cout)
+        self.__dict__["_fast_operands"] = (stamp, ops)
+        return ops
+
+    def forward_hip(self, x, mlp_input, ops):
+        """x [n, Cin, H, W] channels-last fp16, mlp_input [n, 27] fp32 on x's device -> (rows [n H W, row_stride] fp16,
+        layout): the operand of lss_depth_split."""
+        from .functions.yolox_ops import nhwc_empty
+        P = self.fast_operands(build=False)
+        if P is None:
+            P = self.fast_operands()
+        lay, mid = P["layout"], self.mid_channels
+        n, _, H, W = x.shape
+        gates = ops.lss_camera_gate(mlp_input, P["gate"], mid)                                    # 1 launch
+        r = ops.conv_nhwc(x, self.reduce_conv.weight, self.reduce_conv.bias, True)
+        depth, context = ops.se_gate2_nhwc(r, gates)                                              # 1 launch
+        rows = nhwc_empty(n, lay["row_stride"], H, W, x.device)
+        o = lay["depth_offset"]             # (the feature columns up to here: zero weight rows behind channel C)
+        ops.conv_slice_nhwc(context, self.context_conv.weight, self.context_conv.bias, "none", out=rows[:, :o])
+        for m in self.depth_conv[:3]:
+            t = ops.conv_nhwc(depth, m.conv1.weight, m.conv1.bias, True)
+            depth = ops.conv_nhwc(t, m.conv2.weight, m.conv2.bias, True, depth)
+        if self.use_aspp:
+            a = self.aspp
+            amid = a.aspp1.out_channels
+            cat = nhwc_empty(n, 4 * amid, H, W, x.device)
+            for i, (m, d) in enumerate(zip(a.branches(), ASPP_DILATIONS)):
+                ops.conv_slice_nhwc(depth, m.weight, m.bias, "relu", out=cat[:, i * amid:(i + 1) * amid], dilation=d)
+            pooled = ops.global_avgpool_nhwc(depth)                                               # [n, mid]
+            g = ops.dense_auto(pooled, P["pool_w"], a.global_avg_pool.bias, None, True)           # [n, amid]
+            image_bias = ops.dense_auto(g, P["conv1_pool"], a.conv1.bias, None, False)            # [n, mid]
+            depth = ops.conv_slice_nhwc(cat, P["conv1_main"], None, "relu", image_bias=image_bias)
+        ops.conv_slice_nhwc(depth, P["wd"], P["bd"], "none", out=rows[:, o:o + lay["depth_padded"]])
+        return rows.permute(0, 2, 3, 1).reshape(n * H * W, lay["row_stride"]), lay
+
+
+class LSSViewTransformerBEVDepth(LSSViewTransformer):
+    """LSSViewTransformer with the DepthNet as depth_net.  The calibration row carries the DepthNet's inputs behind
+    the parent's: `calibration_matrices` -> [N * 24 + 9 | N * 27] = [N * 51 + 9] floats (batched: [B, N * 51 + 9]), so
+    BEVDetRunner still uploads ONE row per frame; the transformer splits it."""
+
+    def __init__(self, grid_config, input_size, downsample, in_channels, out_channels, ops=None, seed=0, bev_half=None,
+                 depthnet_cfg=None):
+        super().__init__(grid_config, input_size, downsample, in_channels, out_channels, ops=ops, seed=seed,
+                         bev_half=bev_half)
+        self.depth_net = DepthNet(in_channels, in_channels, out_channels, self.D, **(depthnet_cfg or {}))
+
+    # ---- view_transformer.py:793-818 (pure gathers)
+    def get_mlp_input(self, sensor2ego, ego2global, intrin, post_rot, post_tran, bda):
+        B, N, _, _ = sensor2ego.shape
+        bda = bda.view(B, 1, 3, 3).repeat(1, N, 1, 1)
+        mlp_input = torch.stack([intrin[:, :, 0, 0], intrin[:, :, 1, 1], intrin[:, :, 0, 2], intrin[:, :, 1, 2],
+                                 post_rot[:, :, 0, 0], post_rot[:, :, 0, 1], post_tran[:, :, 0], post_rot[:, :, 1, 0],
+                                 post_rot[:, :, 1, 1], post_tran[:, :, 1], bda[:, :, 0, 0], bda[:, :, 0, 1],
+                                 bda[:, :, 1, 0], bda[:, :, 1, 1], bda[:, :, 2, 2]], dim=-1)
+        sensor2ego = sensor2ego[:, :, :3, :].reshape(B, N, -1)
+        return torch.cat([mlp_input, sensor2ego], dim=-1)
+
+    def calibration_matrices(self, sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda):
+        geo = super().calibration_matrices(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
+        s2e, K, pr, pt, b = (t.detach().to("cpu", torch.float32) for t in (sensor2ego, cam2imgs, post_rots, post_trans, bda))
+        mlp = self.get_mlp_input(s2e, None, K, pr, pt, b)
+        return torch.cat((geo, mlp.reshape(-1))).contiguous()
+
+    @staticmethod
+    def split_calibration(calib):
+        """The packed row(s) -> (the parent's [N * 24 + 9] part, the MLP inputs [B * N, 27]).  1-D: two views.  2-D: the
+        index build needs dense rows and the gate a dense [B * N, 27] table: two small device copies."""
+        L = calib.shape[-1]
+        if (L - 9) % 51:
+            raise ValueError(f"a BEVDepth calibration row holds N * 51 + 9 floats, got {L}")
+        cut = (L - 9) // 51 * 24 + 9
+        if calib.dim() == 1:
+            return calib[:cut], calib[cut:].view(-1, MLP_INPUTS)
+        return calib[:, :cut].contiguous(), calib[:, cut:].reshape(-1, MLP_INPUTS)
+
+    def lidar_coor_plain(self, calib):
+        return super().lidar_coor_plain(self.split_calibration(calib)[0])
+
+    def prepare_calibrated(self, calib, padded=True):
+        return super().prepare_calibrated(self.split_calibration(calib)[0], padded=padded)
+
+    # ---- the fast path's switches: the parent's names, so that BEVDet.prepare_bev_half / _bev_half_ready serve both
+    def _hip_on(self, x):
+        return self.bev_half == "hip" and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 \
+            and x.is_contiguous(memory_format=torch.channels_last) \
+            and all(hasattr(self.ops, f) for f in ("lss_depth_split", "dense_auto", "conv_nhwc", "conv_slice_nhwc",
+                                                   "lss_camera_gate", "se_gate2_nhwc", "global_avgpool_nhwc"))
+
+    def depth_net_merged(self, build=True):
+        return self.depth_net.fast_operands(build=build)
+
+    def _depth_feat(self, x, mlp_input):
+        """-> (depth [n, D, H, W] softmax, feat [n, H, W, C], fast?)"""
+        n, _, h, w = x.shape
+        if self._hip_on(x):
+            if self.depth_net.fast_operands(build=False) is None and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("LSSViewTransformerBEVDepth: the DepthNet's packed operands are missing or stale and "
+                                   "the stream is capturing; call BEVDet.prepare_bev_half() first")
+            with _rule_dispatch():
+                rows, lay = self.depth_net.forward_hip(x, mlp_input.to(x.device, torch.float32), self.ops)
+            depth, feat = self.ops.lss_depth_split(rows, n, self.D, self.out_channels, lay["depth_offset"],
+                                                   lay["feat_offset"], spatial=(h, w))
+            return depth, feat, True
+        y = self.depth_net(x, mlp_input.to(x.device))
+        depth = y[:, :self.D].softmax(dim=1)
+        feat = y[:, self.D:self.D + self.out_channels].permute(0, 2, 3, 1)
+        return depth.contiguous(), feat.contiguous(), False
+
+    @torch.no_grad()
+    def view_transform_calibrated(self, x, calib):
+        geo, mlp = self.split_calibration(calib)
+        if mlp.shape[0] != x.shape[0]:
+            raise ValueError(f"calib {tuple(calib.shape)} does not describe the {x.shape[0]} camera images of x")
+        rb, rd, rf, ist, il, counts = super().prepare_calibrated(geo)
+        bev_h, bev_w = int(self.grid_size[1]), int(self.grid_size[0])
+        kw = dict(batch=calib.shape[0]) if calib.dim() == 2 else {}
+        depth, feat, fast = self._depth_feat(x, mlp)
+        out = self.ops.bev_pool_v2_indirect(depth, feat, rd, rf, rb, ist, il, counts, bev_h, bev_w, **kw).permute(0, 3, 1, 2)
+        return out if fast else out.contiguous()
+
+    @torch.no_grad()
+    def view_transform(self, x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, mlp_input=None):
+        if mlp_input is None:
+            raise ValueError("LSSViewTransformerBEVDepth.view_transform needs mlp_input (get_mlp_input of the frame)")
+        depth, feat, fast = self._depth_feat(x, mlp_input.reshape(-1, MLP_INPUTS))
+        out = self.ops.bev_pool_v2_2(depth, feat, ranks_depth, ranks_feat, ranks_bev, interval_starts, interval_lengths,
+                                     int(self.grid_size[1]), int(self.grid_size[0])).permute(0, 3, 1, 2)
+        return out if fast else out.contiguous()

@@ -113,6 +113,9 @@ DATA_CONFIG_R50 = dict(input_size=(256, 704), src_size=(900, 1600), crop_h=(0.0,
 BEVDET_R50 = dict(
     grid_config=dict(x=[-51.2, 51.2, 0.8], y=[-51.2, 51.2, 0.8], z=[-5, 3, 8], depth=[1.0, 60.0, 1.0]),
     input_size=(256, 704), downsample=16, in_channels=256, out_channels=64)
+# BEVDepth-R50: the same detector with the camera-aware DepthNet + ASPP in front of the pooling (bevdepth.py); the
+# reference's DCN layer (DepthNet's default use_dcn=True) is not built
+BEVDEPTH_R50 = dict(BEVDET_R50, view_transformer="bevdepth", depthnet_cfg=dict(use_dcn=False))
 
 
 class LSSViewTransformer(nn.Module):
@@ -467,9 +470,15 @@ class BEVDet(nn.Module):
         self.ops = ops = ops if ops is not None else _hip_ops
         self.backbone = _B.ResNet(50, (False,) * 4, (2, 3), ops, "pytorch")
         self.neck = CustomFPN()
-        self.view = LSSViewTransformer(**{k: cfg[k] for k in ("grid_config", "input_size", "downsample", "in_channels",
-                                                              "out_channels")}, ops=ops, seed=seed,
-                                       bev_half=self.bev_half)
+        view_kw = dict({k: cfg[k] for k in ("grid_config", "input_size", "downsample", "in_channels", "out_channels")},
+                       ops=ops, seed=seed, bev_half=self.bev_half)
+        if cfg.get("view_transformer") == "bevdepth":      # BEVDEPTH_R50: the camera-aware DepthNet (bevdepth.py)
+            from .bevdepth import LSSViewTransformerBEVDepth
+            self.view = LSSViewTransformerBEVDepth(**view_kw, depthnet_cfg=cfg.get("depthnet_cfg"))
+        elif cfg.get("view_transformer") not in (None, "lss"):
+            raise ValueError(f"view_transformer = {cfg.get('view_transformer')!r}: 'lss' or 'bevdepth'")
+        else:
+            self.view = LSSViewTransformer(**view_kw)
         c = cfg["out_channels"]
         chans, cin, stages = [2 * c, 4 * c, 8 * c], c, []
         for ch in chans:
@@ -595,15 +604,17 @@ class BEVDet(nn.Module):
         return _conv(ops, _conv(ops, x, self.up2_conv[0], True), self.up2_conv[1])
 
     @torch.no_grad()
-    def forward(self, image, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths):
+    def forward(self, image, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, mlp_input=None):
+        """mlp_input: the BEVDepth transformer's `get_mlp_input` of the frame (view_transformer="bevdepth" only)."""
+        kw = {} if mlp_input is None else dict(mlp_input=mlp_input)
         hip = self._bev_half_ready(image)      # (first: under capture a missing operand raises before anything is launched)
         if hip:
             with _rule_dispatch():      # (the image half too: see forward_calibrated)
                 x = self.image_features(image.flatten(0, 1))
-                bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths)
+                bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, **kw)
                 return self._heads_hip(self.bev_encoder(bev))
         x = self.image_features(image.flatten(0, 1))
-        bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths)
+        bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, **kw)
         feat = self.bev_encoder(bev)
         ops = self.ops
         s = _conv(ops, feat, self.shared_conv, True)

@@ -287,3 +287,71 @@ def load_reference_state_dict(model, state_dict, strict=True, key_map=None):
                        f"unexpected {unexpected[:8]}{'...' if len(unexpected) > 8 else ''}")
     model._static = None          # cached geometry / packed weights are rebuilt on the next frame
     return missing, unexpected
+
+
+def depthnet_key_map(depth_net, prefix="img_view_transformer.depth_net."):
+    """`reference_key_map` for bevdepth.DepthNet: {our parameter name: source} from the names the reference's classes
+    spell (view_transformer.py: DepthNet, mmdet's BasicBlock, ASPP / _ASPPModule, Mlp, SELayer) under `prefix`.  Every
+    BatchNorm2d is folded into the convolution in front of it; the BatchNorm1d of the camera inputs stays a module
+    (its running statistics are buffers: `load_depthnet_state_dict` copies them)."""
+    m = {}
+
+    def fold(ours, conv, bn):
+        m[ours + ".weight"] = m[ours + ".bias"] = _conv_bn(prefix + conv, prefix + bn)
+
+    def copy(name):
+        for n in ("weight", "bias"):
+            m[f"{name}.{n}"] = f"{prefix}{name}.{n}"
+
+    fold("reduce_conv", "reduce_conv.0", "reduce_conv.1")
+    for name in ("context_conv", "bn"):
+        copy(name)
+    for br in ("depth", "context"):
+        for name in (f"{br}_mlp.fc1", f"{br}_mlp.fc2", f"{br}_se.conv_reduce", f"{br}_se.conv_expand"):
+            copy(name)
+    for i in range(3):
+        fold(f"depth_conv.{i}.conv1", f"depth_conv.{i}.conv1", f"depth_conv.{i}.bn1")
+        fold(f"depth_conv.{i}.conv2", f"depth_conv.{i}.conv2", f"depth_conv.{i}.bn2")
+    last = 3
+    if depth_net.use_aspp:
+        for k in (1, 2, 3, 4):
+            fold(f"depth_conv.3.aspp{k}", f"depth_conv.3.aspp{k}.atrous_conv", f"depth_conv.3.aspp{k}.bn")
+        fold("depth_conv.3.global_avg_pool", "depth_conv.3.global_avg_pool.1", "depth_conv.3.global_avg_pool.2")
+        fold("depth_conv.3.conv1", "depth_conv.3.conv1", "depth_conv.3.bn1")
+        last = 4
+    copy(f"depth_conv.{last}")
+    return m
+
+
+def depthnet_reference_keys(depth_net, prefix="img_view_transformer.depth_net."):
+    """Every tensor name a reference checkpoint holds for this DepthNet (num_batches_tracked left out), sorted."""
+    keys = set()
+    for src in depthnet_key_map(depth_net, prefix).values():
+        if isinstance(src, tuple):
+            _, conv, bn = src
+            keys.update([conv + ".weight"] + [f"{bn}.{n}" for n in ("weight", "bias", "running_mean", "running_var")])
+            if conv.endswith("reduce_conv.0"):
+                keys.add(conv + ".bias")          # (the only folded convolution that has a bias of its own)
+        else:
+            keys.add(src)
+    keys.update(f"{prefix}bn.{n}" for n in ("running_mean", "running_var"))
+    return sorted(keys)
+
+
+def load_depthnet_state_dict(depth_net, state_dict, strict=True, prefix="img_view_transformer.depth_net."):
+    """Fill a bevdepth.DepthNet from a reference checkpoint's state dict: `depthnet_key_map`, plus the running
+    statistics of the BatchNorm1d.  Returns (missing, unexpected) among the keys under `prefix`."""
+    sd = state_dict.get("state_dict", state_dict)
+    sd = {k: v for k, v in sd.items() if k.startswith(prefix)}
+    missing, unexpected = load_reference_state_dict(depth_net, sd, False, depthnet_key_map(depth_net, prefix))
+    with torch.no_grad():
+        for n in ("running_mean", "running_var"):
+            k = f"{prefix}bn.{n}"
+            if k in sd:
+                getattr(depth_net.bn, n).copy_(sd[k].to(getattr(depth_net.bn, n).dtype))
+                unexpected.remove(k)
+            else:
+                missing.append("bn." + n)
+    if strict and (missing or unexpected):
+        raise KeyError(f"missing {missing[:8]}; unexpected {unexpected[:8]}")
+    return missing, unexpected

@@ -23,6 +23,12 @@
 // SiLU is v * sigmoid(v) = v * rcp(1 + exp(-v)) with the hardware exponential (v_exp_f32 on the scaled argument) and
 // the hardware reciprocal (v_rcp_f32, 1 ulp): exp(-v) overflows to +inf for v < -88.7, where the result is -0 (the
 // true value is below 2^-120); for v > 88 it is v.  design/yolox.md derives the error bound the tests assert.
+//
+// bevops_conv_slice_f16_ex (the ASPP block of BEVDepth's DepthNet, design/bevdepth.md) adds two block-uniform runtime
+// values to the same two kernels: a DILATION (3 x 3, stride 1: the tap's address delta and validity bit scale with it)
+// and a PER-IMAGE bias (bias_pitch != 0: the epilogue reads the 8 bias values of every row's own image, since a row
+// tile may hold pixels of several images).  With (1, 0) every output bit is the parent entry's, which forwards here.
+// A tap that lies outside the image for every row of a tile is still multiplied (by zeros): not skipped.
 #include "gemm_host.h"
 
 namespace bevops {
@@ -47,6 +53,8 @@ struct ConvSliceArgs {
   unsigned x_bytes, w_bytes;                   // extents of the input slice and the weight (the loads' range check)
   int x_pitch, res_pitch, out_pitch;           // elements between two pixels
   int cin, hin, win, hout, wout, stride, ks;
+  int dil;                                     // tap (ky, kx) reads pixel (y + (ky - pad) dil, x + (kx - pad) dil)
+  int bias_pitch;                              // 0: bias[co]; else the bias of output row m is bias[(m / per) bias_pitch + co]
 };
 
 __device__ __forceinline__ float silu_f32(float v) { return v * __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
@@ -78,8 +86,8 @@ __global__ __launch_bounds__(256, 3) void conv_slice_kernel(ConvSliceArgs p) {
   const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.x), 0, p.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w), 0, p.w_bytes, 0x00020000);
   // output row m is pixel (b, yo, xo); its k-values are [tap][Cin] with tap (ky, kx) read from input pixel
-  // (s yo + ky - pad, s xo + kx - pad) of the same image, zero outside it
-  const int cin = p.cin, ksz = p.ks, taps = ksz * ksz, pad = ksz >> 1;
+  // (s yo + (ky - pad) dil, s xo + (kx - pad) dil) of the same image, zero outside it (dil > 1: ksize 3, stride 1)
+  const int cin = p.cin, ksz = p.ks, taps = ksz * ksz, pad = ksz >> 1, dil = p.dil;
   const int per = p.hout * p.wout;
   unsigned a_off0, a_off1, tapmask0, tapmask1;
   auto place = [&](int m, unsigned &off, unsigned &mk) {
@@ -90,7 +98,7 @@ __global__ __launch_bounds__(256, 3) void conv_slice_kernel(ConvSliceArgs p) {
     const int y = yo * p.stride, x = xo * p.stride;           // centre tap in the input image
     off = (unsigned)((((size_t)b * p.hin + y) * p.win + x) * p.x_pitch + kce) * 2u;
     for (int t = 0; t < taps; ++t) {
-      const int yy = y + t / ksz - pad, xx = x + t % ksz - pad;
+      const int yy = y + (t / ksz - pad) * dil, xx = x + (t % ksz - pad) * dil;
       mk |= (yy >= 0 && yy < p.hin && xx >= 0 && xx < p.win) ? (1u << t) : 0u;
     }
   };
@@ -107,7 +115,7 @@ __global__ __launch_bounds__(256, 3) void conv_slice_kernel(ConvSliceArgs p) {
     constexpr int S = decltype(setc)::value;
     const int ks = kt * kStepK;
     const bool kok = ks < K;
-    const int delta = ((g_tap / ksz - pad) * p.win + (g_tap % ksz - pad)) * p.x_pitch * 2;
+    const int delta = ((g_tap / ksz - pad) * p.win + (g_tap % ksz - pad)) * dil * p.x_pitch * 2;
     // (steps past the last one: g_tap >= taps, whose mask bits are clear)
     ra0[S] = bload(rs_a, (tapmask0 >> g_tap) & 1u ? a_off0 + (unsigned)delta : kGemmOob, g_c * 2);
     ra1[S] = bload(rs_a, (tapmask1 >> g_tap) & 1u ? a_off1 + (unsigned)delta : kGemmOob, g_c * 2);
@@ -176,7 +184,7 @@ __global__ __launch_bounds__(256, 3) void conv_slice_kernel(ConvSliceArgs p) {
   const bool col_ok = ncol < N;                // N % 8 == 0: the chunk is all in or all out
   char *stage = smem + wave * 32 * kEpiStride;
   const __half *res = static_cast<const __half *>(p.res);
-  const int act = p.act;
+  const int act = p.act, bias_pitch = p.bias_pitch;
   float bs[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c)
@@ -200,6 +208,12 @@ __global__ __launch_bounds__(256, 3) void conv_slice_kernel(ConvSliceArgs p) {
       if (m >= M || !col_ok) continue;
       uint4 q = make_uint4(0u, 0u, 0u, 0u);
       if (res) q = *reinterpret_cast<const uint4 *>(res + (size_t)m * p.res_pitch + ncol);
+      if (bias_pitch) {                        // a per-image bias: the tile's rows may belong to several images
+        const uint4 bq = *reinterpret_cast<const uint4 *>(static_cast<const __half *>(p.bias) +
+                                                          (size_t)(m / per) * bias_pitch + ncol);
+        bs[0] = h2f_lo(bq.x); bs[1] = h2f_hi(bq.x); bs[2] = h2f_lo(bq.y); bs[3] = h2f_hi(bq.y);
+        bs[4] = h2f_lo(bq.z); bs[5] = h2f_hi(bq.z); bs[6] = h2f_lo(bq.w); bs[7] = h2f_hi(bq.w);
+      }
       float v[8];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -231,28 +245,36 @@ __global__ __launch_bounds__(256, 3) void conv_slice_kernel(ConvSliceArgs p) {
 
 using namespace bevops;
 
-extern "C" int bevops_conv_slice_f16(const void *x, int x_pitch, const void *weight_taps, const void *bias,
-                                     const void *residual, int res_pitch, void *out, int out_pitch, int B, int H, int W,
-                                     int Cin, int Cout, int ksize, int stride, int act, void *stream) {
+extern "C" int bevops_conv_slice_f16_ex(const void *x, int x_pitch, const void *weight_taps, const void *bias,
+                                        const void *residual, int res_pitch, void *out, int out_pitch, int B, int H, int W,
+                                        int Cin, int Cout, int ksize, int stride, int act, int dilation, int bias_pitch,
+                                        void *stream) {
   if (!x || !weight_taps || !out || B < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return BEVOPS_BAD_PARAM;
-  if (ksize <= 0 || stride <= 0) return BEVOPS_BAD_PARAM;
+  if (ksize <= 0 || stride <= 0 || dilation <= 0) return BEVOPS_BAD_PARAM;
   if (x_pitch < Cin || out_pitch < Cout || (residual && res_pitch < Cout)) return BEVOPS_BAD_PARAM;
   // a pitch that is no multiple of 8 elements leaves every other pixel's vectors unaligned
   if (x_pitch % 8 != 0 || out_pitch % 8 != 0 || (residual && res_pitch % 8 != 0)) return BEVOPS_BAD_PARAM;
   if (misaligned(x, 15u) || misaligned(weight_taps, 15u) || misaligned(out, 15u) || (residual && misaligned(residual, 15u)) ||
       (bias && misaligned(bias, 1u)))
     return BEVOPS_BAD_PARAM;
+  // a per-image bias: rows of bias_pitch halves, each read as 16-byte vectors
+  if (bias_pitch != 0 && (!bias || bias_pitch < Cout || bias_pitch % 8 != 0 || misaligned(bias, 15u))) return BEVOPS_BAD_PARAM;
   if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || act < kActNone || act > kActSilu) return BEVOPS_NOT_SUPPORTED;
   if (Cin % 32 != 0 || Cout % 8 != 0) return BEVOPS_NOT_SUPPORTED;
+  if (dilation > 1 && (ksize != 3 || stride != 1)) return BEVOPS_NOT_SUPPORTED;
   // x and the weight are addressed through 32-bit buffer offsets (identity and output through 64-bit pointers)
   const unsigned long long rows_in = (unsigned long long)B * H * W;
   if (gemm_over_limit(rows_in, x_pitch, 2) || gemm_over_limit((unsigned long long)Cout, ksize * ksize * Cin, 2))
     return BEVOPS_NOT_SUPPORTED;
+  // the displacement of a tap is a signed 32-bit byte count, computed for taps outside the image too
+  if (dilation > 1 && (unsigned long long)dilation * ((unsigned long long)W + 1) * (unsigned long long)x_pitch * 2 > 0x7fffffffull)
+    return BEVOPS_NOT_SUPPORTED;
   if (B == 0) return BEVOPS_SUCCESS;
-  const int pad = ksize / 2;
+  const int pad = ksize / 2;                   // at stride 1 a dilated 3 x 3 with pad = dilation keeps the size too
   ConvSliceArgs p;
   p.x = x; p.w = weight_taps; p.bias = bias; p.res = residual; p.out = out;
   p.hin = H; p.win = W; p.cin = Cin; p.stride = stride; p.ks = ksize;
+  p.dil = dilation; p.bias_pitch = bias_pitch;
   p.hout = (H + 2 * pad - ksize) / stride + 1;
   p.wout = (W + 2 * pad - ksize) / stride + 1;
   const unsigned long long rows = (unsigned long long)B * p.hout * p.wout;
@@ -269,4 +291,11 @@ extern "C" int bevops_conv_slice_f16(const void *x, int x_pitch, const void *wei
   if (narrow) hipLaunchKernelGGL(conv_slice_kernel<1>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
   else hipLaunchKernelGGL(conv_slice_kernel<2>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
   return launch_status();
+}
+
+extern "C" int bevops_conv_slice_f16(const void *x, int x_pitch, const void *weight_taps, const void *bias,
+                                     const void *residual, int res_pitch, void *out, int out_pitch, int B, int H, int W,
+                                     int Cin, int Cout, int ksize, int stride, int act, void *stream) {
+  return bevops_conv_slice_f16_ex(x, x_pitch, weight_taps, bias, residual, res_pitch, out, out_pitch, B, H, W, Cin, Cout,
+                                  ksize, stride, act, 1, 0, stream);
 }

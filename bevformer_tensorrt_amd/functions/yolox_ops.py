@@ -147,9 +147,11 @@ def conv_slice_packed_weight(weight, cin=None, cout=None, build=True):
     return wp
 
 
-def conv_slice_taps(x, weight_taps, bias=None, act="silu", residual=None, stride=1, out=None):
+def conv_slice_taps(x, weight_taps, bias=None, act="silu", residual=None, stride=1, out=None, dilation=1,
+                    image_bias=None):
     """`conv_slice_nhwc` on an operand that already is taps-major: weight_taps [Cout, k, k, Cin] contiguous fp16 with
-    Cin == x.shape[1] (callers that merge or pad their weights themselves: yolox.py)."""
+    Cin == x.shape[1] (callers that merge or pad their weights themselves: yolox.py).  dilation / image_bias as there
+    (image_bias [B, P] fp16 with P >= Cout, P % 8 == 0, rows contiguous; it replaces `bias`)."""
     _check_f16(x, "x")
     if weight_taps.dim() != 4 or weight_taps.shape[1] != weight_taps.shape[2] or not weight_taps.is_contiguous() or \
             weight_taps.dtype != torch.float16 or weight_taps.device != x.device:
@@ -163,6 +165,22 @@ def conv_slice_taps(x, weight_taps, bias=None, act="silu", residual=None, stride
     if k not in (1, 3) or stride not in (1, 2) or Cin % 32 or Cout % 8:
         raise _lib.BevopsError("bevops_conv_slice_f16: ksize in {1, 3}, stride in {1, 2}, Cin % 32 == 0, Cout % 8 == 0",
                                _lib.NOT_SUPPORTED)
+    dilation = int(dilation)
+    if dilation < 1:
+        raise ValueError("conv_slice: dilation >= 1")
+    if dilation > 1 and (k != 3 or stride != 1):
+        raise _lib.BevopsError("bevops_conv_slice_f16_ex: dilation > 1 needs ksize 3 and stride 1", _lib.NOT_SUPPORTED)
+    bp = 0
+    if image_bias is not None:
+        if bias is not None:
+            raise ValueError("conv_slice: image_bias replaces bias, pass one of them")
+        _check_f16(image_bias, "image_bias")
+        if image_bias.dim() != 2 or image_bias.shape[0] != B or image_bias.shape[1] < Cout or \
+                (image_bias.shape[1] > 1 and image_bias.stride(1) != 1):
+            raise ValueError(f"conv_slice: image_bias [B, >= Cout] with contiguous rows, got {tuple(image_bias.shape)}")
+        bp = image_bias.stride(0) if B > 1 else padded_width(image_bias.shape[1], 8)
+        if bp < Cout or bp % 8 or image_bias.data_ptr() % 16:
+            raise ValueError(f"conv_slice: image_bias rows start on 16-byte boundaries, pitch a multiple of 8 (pitch {bp})")
     Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
     xp = slice_pitch(x, "x")
     out = _dest(out, (B, Cout, Ho, Wo), x, "conv_slice")
@@ -180,13 +198,21 @@ def conv_slice_taps(x, weight_taps, bias=None, act="silu", residual=None, stride
             bias = bias.to(torch.float16).contiguous()
     if B == 0:
         return out
-    _call("bevops_conv_slice_f16", x.device, x.data_ptr(), xp, weight_taps.data_ptr(), _ptr(bias), _ptr(residual), rp,
-          out.data_ptr(), op, B, H, W, Cin, Cout, k, int(stride), ACTS[act])
+    if dilation == 1 and image_bias is None:
+        _call("bevops_conv_slice_f16", x.device, x.data_ptr(), xp, weight_taps.data_ptr(), _ptr(bias), _ptr(residual), rp,
+              out.data_ptr(), op, B, H, W, Cin, Cout, k, int(stride), ACTS[act])
+    else:
+        _call("bevops_conv_slice_f16_ex", x.device, x.data_ptr(), xp, weight_taps.data_ptr(),
+              _ptr(bias if image_bias is None else image_bias), _ptr(residual), rp, out.data_ptr(), op, B, H, W, Cin, Cout,
+              k, int(stride), ACTS[act], dilation, bp)
     return out
 
 
-def conv_slice_nhwc(x, weight, bias=None, act="silu", residual=None, stride=1, out=None):
-    """out = act(conv2d(x, weight, stride, pad k // 2) + bias) + residual, the identity AFTER the activation.
+def conv_slice_nhwc(x, weight, bias=None, act="silu", residual=None, stride=1, out=None, dilation=1, image_bias=None):
+    """out = act(conv2d(x, weight, stride, pad dilation * (k // 2), dilation) + bias) + residual, the identity AFTER the
+    activation.  dilation > 1: k == 3 and stride == 1 (else BevopsError NOT_SUPPORTED).  image_bias [B, P] fp16 (P >= the
+    output slice's channels, P % 8 == 0): a bias per IMAGE in place of `bias` -- output pixel (b, y, x) takes
+    image_bias[b, co] (ASPP's pooled branch folded through its 1 x 1 convolution, design/bevdepth.md).
     x [B, Cx, H, W], residual and out [B, Co, Hout, Wout]: fp16 channel slices of channels-last tensors; weight
     [Cout, Cin, k, k] fp16 with k in {1, 3}; stride in {1, 2}; act in "none", "relu", "silu".  Cx >= Cin and, with
     `out=`, Co >= Cout: the layer runs at the tensors' widths with zero weight columns / rows (and zero bias) behind
@@ -207,7 +233,9 @@ def conv_slice_nhwc(x, weight, bias=None, act="silu", residual=None, stride=1, o
         b = bias.detach().new_zeros((cout,))
         b[:bias.numel()] = bias.detach()
         bias = b
-    return conv_slice_taps(x, wp, bias, act, residual, stride, out)
+    if image_bias is not None and image_bias.dim() == 2 and image_bias.shape[1] < cout:
+        raise ValueError("conv_slice_nhwc: image_bias has fewer columns than the output slice has channels")
+    return conv_slice_taps(x, wp, bias, act, residual, stride, out, dilation, image_bias)
 
 
 FOCUS_CHANNELS = 32

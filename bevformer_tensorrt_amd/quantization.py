@@ -1086,6 +1086,9 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
     if calibration_cache is not None and bev_half != "int8":
         raise ValueError("build_int8_bevdet: calibration_cache goes with bev_half='int8'")
     src = D if isinstance(D, torch.nn.Module) else None
+    if src is not None and getattr(src, "cfg", {}).get("view_transformer") == "bevdepth":
+        raise NotImplementedError("build_int8_bevdet: INT8 BEVDepth is not built (the DepthNet has no int8 plan); "
+                                  "see design/bevdepth.md")
     if src is not None:
         from . import bevdet as D
     qops = Int8PluginOps(calibrator, channels_last=True)

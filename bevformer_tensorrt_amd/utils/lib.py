@@ -132,6 +132,12 @@ SIGNATURES = {
     "bevops_deconv4x4s2_f16": (c_int, [c_int] + [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
     "bevops_conv_slice_f16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 9 +
                               [c_void_p]),
+    "bevops_conv_slice_f16_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 11 +
+                                 [c_void_p]),
+    "bevops_lss_camera_gate_packed_size": (c_size_t, [c_int]),
+    "bevops_lss_camera_gate": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "bevops_se_gate2_nhwc": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "bevops_global_avgpool_nhwc": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
     "bevops_focus_nhwc": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "bevops_spp_maxpool_nhwc": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 8 + [c_void_p]),
     "bevops_upsample_nearest2x_nhwc": (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p]),

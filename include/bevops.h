@@ -592,6 +592,64 @@ int bevops_deconv4x4s2_f16(int dtype, const void *x, const void *packed_weight, 
 int bevops_conv_slice_f16(const void *x, int x_pitch, const void *weight_taps, const void *bias, const void *residual,
                           int res_pitch, void *out, int out_pitch, int B, int H, int W, int Cin, int Cout, int ksize,
                           int stride, int act, void *stream);
+/* bevops_conv_slice_f16 with a DILATION and an optional PER-IMAGE bias (the ASPP block of BEVDepth's DepthNet;
+ * csrc/conv_slice.hip, the same kernels: both are block-uniform runtime values).  bevops_conv_slice_f16 forwards here
+ * with (dilation, bias_pitch) = (1, 0) and keeps its bits.
+ *   dilation >= 1, pad = dilation * (ksize / 2): tap (ky, kx) of output pixel (y, x) reads input pixel
+ *     (y + (ky - 1) dilation, x + (kx - 1) dilation), zero outside the image; stride 1 keeps the size.
+ *   bias_pitch == 0: the shared bias[co].  bias_pitch != 0: bias is fp16 [B][bias_pitch] and output row m = pixel
+ *     (b, y, x) takes bias[b * bias_pitch + co] -- the image of every ROW, a row tile may hold several images.
+ * Statuses, in this order: everything BEVOPS_BAD_PARAM of bevops_conv_slice_f16, and dilation <= 0; bias_pitch != 0
+ * with a NULL bias, bias_pitch < Cout, bias_pitch % 8 != 0 or a bias not 16-byte aligned: BEVOPS_BAD_PARAM.  Then
+ * everything BEVOPS_NOT_SUPPORTED of bevops_conv_slice_f16; dilation > 1 with ksize != 3 or stride != 1:
+ * BEVOPS_NOT_SUPPORTED.  32-bit byte offsets: B H W x_pitch and Cout ksize^2 Cin below 0xFFFFFF00 bytes as there (a tap
+ * inside the image lies inside that extent), and with dilation > 1 the displacement of a tap, computed for taps
+ * outside the image too, must fit a signed 32-bit byte count: dilation (W + 1) x_pitch 2 <= 0x7FFFFFFF, else
+ * BEVOPS_NOT_SUPPORTED.  B == 0: BEVOPS_SUCCESS without a launch. */
+int bevops_conv_slice_f16_ex(const void *x, int x_pitch, const void *weight_taps, const void *bias, const void *residual,
+                             int res_pitch, void *out, int out_pitch, int B, int H, int W, int Cin, int Cout, int ksize,
+                             int stride, int act, int dilation, int bias_pitch, void *stream);
+/* The layers of BEVDepth's DepthNet that are no convolution (csrc/lss_depthnet.hip; LSSViewTransformerBEVDepth,
+ * bevformer_tensorrt_amd/bevdepth.py).  None allocates, synchronises or uses atomics; n == 0: BEVOPS_SUCCESS without a
+ * launch.
+ *
+ * bevops_lss_camera_gate: the camera-aware squeeze-excite gates.  mlp_input fp32, camera i's 27 calibration values at
+ *   mlp_input + i * in_pitch (in_pitch >= 27, in floats); gates fp32 [2][n][mid], branch 0 = depth, 1 = context:
+ *     gates[br][i][:] = sigmoid(expand(relu(reduce(fc2(relu(fc1(bn(v_i))))))))
+ *   All arithmetic fp32.  Every layer: acc = 0; for k = 0, 1, ...: acc = fma(w[k][j], in[k], acc); y[j] = acc + b[j]
+ *   (ONE fused multiply-add per term, ascending k, the bias added last with one rounding); relu = max(y, 0);
+ *   sigmoid(y) = 1 / (1 + exp(-y)) with expf and an IEEE division.
+ *   packed: one fp32 block of bevops_lss_camera_gate_packed_size(mid) bytes (0 outside the domain), branch 0 then
+ *   branch 1, each branch
+ *     W1 [27][mid]   b1 [mid]     fc1 with the frozen BatchNorm1d(27) folded in: W1[k][j] = fc1.w[j][k] s[k],
+ *                                 b1[j] = fc1.b[j] + sum_k fc1.w[j][k] t[k], s = gamma / sqrt(var + eps), t = beta - mean s
+ *     W2 [mid][mid]  b2 [mid]     fc2,         W2[k][j] = fc2.w[j][k]        (every matrix K-MAJOR: [input k][output j])
+ *     Wr [mid][mid]  br [mid]     conv_reduce, Wr[k][j] = conv_reduce.w[j][k]
+ *     We [mid][mid]  be [mid]     conv_expand, We[k][j] = conv_expand.w[j][k]
+ *   = mid (3 mid + 31) words per branch.  One block per (camera, branch).
+ *   Statuses, in this order: NULL mlp_input / packed / gates, n < 0, mid <= 0, in_pitch < 27, a pointer not 4-byte
+ *   aligned: BEVOPS_BAD_PARAM; mid % 8 != 0, mid < 8, mid > 512, n > 0x3FFFFFFF: BEVOPS_NOT_SUPPORTED.
+ * bevops_se_gate2_nhwc: x fp16, n images of hw pixels of c channels (pixel p of image i at x + (i hw + p) x_pitch);
+ *     out_a[i, p, ch] = fp16(float(x[i, p, ch]) * gates[0][i][ch])      out_b: the same with gates[1]
+ *   gates fp32 [2][n][c] as bevops_lss_camera_gate writes them (mid == c).  One fp32 product, one rounding; x is read
+ *   once; 16-byte vectors.  x, out_a, out_b are channel slices as in bevops_conv_slice_f16 (pitches in elements, >= c,
+ *   multiples of 8); out_a / out_b must not overlap x or each other.
+ *   Statuses, in this order: NULL operands, n < 0, hw <= 0, c <= 0, a pitch below c or no multiple of 8, x / gates /
+ *   out_a / out_b not 16-byte aligned: BEVOPS_BAD_PARAM; c % 8 != 0, more than 2^31 - 1 blocks of 256 vectors:
+ *   BEVOPS_NOT_SUPPORTED.
+ * bevops_global_avgpool_nhwc: out[i, ch] = fp16((sum_p float(x[i, p, ch])) / float(hw)), out fp16 [n][out_pitch].
+ *   The fp32 sum has a FIXED order that depends on (hw, c) alone: s_l = x[l] + x[l + 32] + x[l + 64] + ... (ascending,
+ *   from 0.f) for l = 0 .. 31, total = (((s_0 + s_1) + s_2) + ... ) + s_31; then one IEEE division and one rounding.  Two
+ *   calls give equal bits.
+ *   Statuses, in this order: NULL operands, n < 0, hw <= 0, c <= 0, x_pitch below c or no multiple of 8, out_pitch < c,
+ *   x not 16-byte aligned, out not 2-byte aligned: BEVOPS_BAD_PARAM; c % 8 != 0, n ceil(c / 64) > 2^31 - 1:
+ *   BEVOPS_NOT_SUPPORTED. */
+size_t bevops_lss_camera_gate_packed_size(int mid);
+int bevops_lss_camera_gate(const float *mlp_input, int in_pitch, const void *packed, float *gates, int n, int mid,
+                           void *stream);
+int bevops_se_gate2_nhwc(const void *x, int x_pitch, const float *gates, void *out_a, int a_pitch, void *out_b,
+                         int b_pitch, int n, int hw, int c, void *stream);
+int bevops_global_avgpool_nhwc(const void *x, int x_pitch, void *out, int out_pitch, int n, int hw, int c, void *stream);
 /* The data-movement layers of YOLOX on the same channel slices (csrc/yolox.hip); fp16, exact, 16-byte vectors of 8
  * channels.  Statuses as bevops_conv_slice_f16: NULL / unaligned operands, non-positive sizes, bad pitches:
  * BEVOPS_BAD_PARAM; C % 8 != 0, odd H or W (focus), a pool size that is even or above 13, a buffer of 0xFFFFFF00 bytes
