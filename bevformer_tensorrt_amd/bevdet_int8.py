@@ -171,12 +171,14 @@ def pool_statement(depth_q, feat_q, ranks, sio, cells):
     return torch.trunc(a + torch.where(a > 0, 0.5, -0.5))
 
 
-def emulate(model, plan, x, ranks, table, scales, tensors=None):
+def emulate(model, plan, x, ranks, table, scales, tensors=None, layers=None):
     """The fp32 torch statement of the int8 BEV half from the fp16 image features x [cams, Cin, H, W]: NCHW fp32 tensors
     holding q * scale, fake quantisation (`_fq`: the kernels' clamp(rne(v * (1 / scale)), -127, 127) * scale) at every
     int8 tensor of the plan, depth_net's logits rounded to binary16, the pooling's integer sums and its own rounding.
     scales None: nothing is quantised or rounded (then `table` = the fp32 operands) -- the fp32 plain path.
-    ranks = (ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths) trimmed.  -> the packed [1, 32, h, w]."""
+    ranks = (ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths) trimmed.  -> the packed [1, 32, h, w].
+    layers: the part of plan.layers to run on the tensors already in `tensors` (bevdepth_int8.py: everything from the split
+    on, behind its own DepthNet statement); None: all of them."""
     live = {} if tensors is None else tensors
     view = model.view
     D, C = view.D, view.out_channels
@@ -188,7 +190,7 @@ def emulate(model, plan, x, ranks, table, scales, tensors=None):
         return v if scales is None or plan.tensors[name] != "q" else _fq(v, sc(name))
 
     live["x.f16"] = x.float()
-    for l in plan.layers:
+    for l in (plan.layers if layers is None else layers):
         src = live[l.src]
         if l.op == "quantize":
             v = fq(src, l.dst)
@@ -243,7 +245,7 @@ class Int8BEVDet(nn.Module):
         self.fp = fp
         self.cfg = fp.cfg
         self.bev_ops = ops if ops is not None else _hip_ops
-        self.plan = build_plan(fp)
+        self.plan = self._plan_of(fp)
         missing = [s for s in self.plan.sites if s not in scales]
         if missing:
             raise ValueError(f"Int8BEVDet: no scale for the sites {missing}")
@@ -251,6 +253,11 @@ class Int8BEVDet(nn.Module):
         if not all(0.0 < v < float("inf") for v in self.scales.values()):
             raise ValueError("Int8BEVDet: every scale is positive and finite")
         self.eval()
+
+    # ---- the plan and its statements (bevdepth_int8.Int8BEVDepth puts its own in their place)
+    _plan_of = staticmethod(build_plan)
+    _quantize = staticmethod(quantize_operands)
+    _floats = staticmethod(_float_operands)
 
     # ---- what BEVDetRunner and the post-processing read
     @property
@@ -295,7 +302,7 @@ class Int8BEVDet(nn.Module):
             return hit[1]
         if not build:
             return None
-        table = quantize_operands(self.fp, self.plan)
+        table = self._quantize(self.fp, self.plan)
         self.__dict__["_operands"] = (stamp, table)
         return table
 
@@ -320,15 +327,16 @@ class Int8BEVDet(nn.Module):
         return self.operands(build=False)
 
     # ---- the int8 run
-    def run(self, x, pool, table, ops, tensors=None):
+    def run(self, x, pool, table, ops, tensors=None, layers=None):
         """The layers of the plan on `ops` from the fp16 image features x [cams, Cin, H, W] (channels-last); pool(depth_q,
-        feat_q, scales) runs the pooling.  -> the packed head output [1, 32, h, w] fp16 channels-last."""
+        feat_q, scales) runs the pooling.  -> the packed head output [1, 32, h, w] fp16 channels-last.  layers: the part
+        of the plan to run on the tensors already in `tensors` (None: all of it)."""
         live = {} if tensors is None else tensors
         i8, f16 = torch.int8, torch.float16
         view = self.fp.view
         lay = table["layout"]
         live["x.f16"] = x
-        for l in self.plan.layers:
+        for l in (self.plan.layers if layers is None else layers):
             src = live[l.src]
             q_out = self.plan.tensors[l.dst] == "q"
             s_out = self.scale(l.dst) if q_out else None
@@ -359,7 +367,7 @@ class Int8BEVDet(nn.Module):
             else:   # "upsample"
                 y = ops.upsample_bilinear_nhwc_q(src, self.scale(l.src), s_out, scale_factor=l.factor, out=out)
             live[l.dst] = y
-        return live["head.packed"]
+        return live.get("head.packed")              # (None when `layers` ends in front of the heads)
 
     def _heads(self, packed, table):
         return tuple(packed[:, a:b] for a, b in table["slices"])
@@ -413,7 +421,7 @@ class Int8BEVDet(nn.Module):
         if quantize:
             table, scales = self.operands(), self.scales
         else:
-            table, scales = _float_operands(self.fp, self.plan), None
+            table, scales = self._floats(self.fp, self.plan), None
         return self._heads(emulate(self.fp, self.plan, x, ranks, table, scales, tensors), table)
 
 
@@ -435,6 +443,17 @@ def calibrate_frame(fp, x, ranks, cal, ops=None):
         y = ops.dense_auto(x.permute(0, 2, 3, 1).reshape(n * h * wd, cin), w, b, None, False)
         depth, feat = ops.lss_depth_split(y, n, view.D, view.out_channels, lay["depth_offset"], lay["feat_offset"],
                                           spatial=(h, wd))
+    calibrate_behind_split(fp, depth, feat, ranks, cal, ops)
+
+
+def calibrate_behind_split(fp, depth, feat, ranks, cal, ops):
+    """`calibrate_frame` from the softmax + split on: depth [n, D, h, w] and feat [n, h, w, C] fp16 as lss_depth_split
+    leaves them (bevdepth_int8.calibrate_frame arrives here from its own DepthNet)."""
+    view = fp.view
+    site = lambda name, t: cal.collect(SITE_PREFIX + name, t)
+    rb, rd, rf, ist, il = ranks
+    conv = lambda t, c, relu=False, res=None: _bd._conv(ops, t, c, relu, res)
+    with torch.no_grad(), _dispatch.using(rule=True):
         site("depth", depth)
         site("feat", feat)
         x = ops.bev_pool_v2_2(depth, feat, rd, rf, rb, ist, il, int(view.grid_size[1]), int(view.grid_size[0]))

@@ -19,6 +19,14 @@
 //                                                    FRONT of the activation -- mmdet's BasicBlock, relu(conv2 + identity))
 //   int8:   q = clamp(rne(v * inv), -127, 127)       one rounding for the product, v_rndne_f32, max, min
 //   fp16:   one rounding of v to binary16
+// bevops_conv_slice_s8_ex2 adds two block-uniform runtime values to the same four kernels (the ASPP block of the INT8
+// build of BEVDepth's DepthNet; the siblings of conv_slice.hip's _ex):
+//   dilation d: tap (ky, kx) reads input pixel (y + (ky - pad) d, x + (kx - pad) d): the validity bit in place() and the
+//     per-thread delta in gload scale with d (the host passes d x_pitch); nothing else of the k-chunk scheme changes.
+//   a PER-IMAGE bias, fp16 [B][image_bias_pitch], in place of bias: the thread that owns the 16 (8) channels of output
+//     row m loads them from image m / (Hout Wout) -- per ROW, a 128-row tile can hold pixels of several images -- and
+//     v = fma((float)sum, sc, (float)image_bias[b][co]); everything behind it is unchanged.
+// bevops_conv_slice_s8_ex forwards with (1, no image bias) and keeps its bits.
 // Non-finite values: a NaN v leaves as -127 (max(NaN, -127) = -127), +inf as 127, -inf as -127 (as SiLU: NaN ->
 // -127); as fp16 they go through as they are.  With ReLU a NaN becomes 0 before the requantisation.
 //
@@ -55,11 +63,13 @@ enum { kActNone = 0, kActRelu = 1, kActSilu = 2 };
 struct ConvSliceS8Args {
   const void *x, *w, *res;
   const float *bias, *wscale;
+  const __half *ibias;                         // per-image bias [B][ibias_pitch] (fp16), or nullptr
   void *out;
   int M, N, K, act, res_first, tiles_n, tiles_total;
   unsigned x_bytes, w_bytes;                   // extents of the input slice and the weight (the loads' range check)
   int x_pitch, res_pitch, out_pitch;           // elements (= bytes for the int8 operands) between two pixels
   int cin, hin, win, hout, wout, stride, ks;
+  int dil, dpitch, ibias_pitch;                // dilation, dilation * x_pitch; halves between two images' bias rows
   float s_aw, s_res, inv_s_out;
 };
 
@@ -97,8 +107,8 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
   const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.x), 0, p.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w), 0, p.w_bytes, 0x00020000);
   // output row m is pixel (b, yo, xo); its k-values are [tap][Cin] with tap (ky, kx) read from input pixel
-  // (s yo + ky - pad, s xo + kx - pad) of the same image, zero outside it
-  const int cin = p.cin, ksz = p.ks, taps = ksz * ksz, pad = ksz >> 1;
+  // (s yo + (ky - pad) dil, s xo + (kx - pad) dil) of the same image, zero outside it (dil > 1: ksize 3, stride 1)
+  const int cin = p.cin, ksz = p.ks, taps = ksz * ksz, pad = ksz >> 1, dil = p.dil;
   const int per = p.hout * p.wout;
   unsigned a_off0, a_off1, tapmask0, tapmask1;
   auto place = [&](int m, unsigned &off, unsigned &mk) {
@@ -109,7 +119,7 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
     const int y = yo * p.stride, x = xo * p.stride;           // centre tap in the input image
     off = (unsigned)((((size_t)b * p.hin + y) * p.win + x) * p.x_pitch);
     for (int t = 0; t < taps; ++t) {
-      const int yy = y + t / ksz - pad, xx = x + t % ksz - pad;
+      const int yy = y + (t / ksz - pad) * dil, xx = x + (t % ksz - pad) * dil;
       mk |= (yy >= 0 && yy < p.hin && xx >= 0 && xx < p.win) ? (1u << t) : 0u;
     }
   };
@@ -133,7 +143,11 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
     constexpr int S = decltype(setc)::value;
     wrap(); wrap();                            // 64 k-values further: at most two taps, Cin >= 32
     // (chunks past K: g_tap >= taps, whose mask bits are clear; g_tap stays below 32 -- at most five steps past K)
-    const unsigned delta = (unsigned)(((g_ty - pad) * p.win + (g_tx - pad)) * p.x_pitch + g_c);
+    // (in unsigned arithmetic: for a valid tap |.| <= dil (W + 1) x_pitch, which the entry keeps inside 31 bits, and the
+    // sum with a_off is the tap's offset modulo 2^32; chunks past K and invalid taps compute a value too, of any size,
+    // and drop it)
+    const unsigned delta = ((unsigned)(g_ty - pad) * (unsigned)p.win + (unsigned)(g_tx - pad)) * (unsigned)p.dpitch +
+                           (unsigned)g_c;
     ra0[S] = bload(rs_a, (tapmask0 >> g_tap) & 1u ? a_off0 + delta : kGemmOob);
     ra1[S] = bload(rs_a, (tapmask1 >> g_tap) & 1u ? a_off1 + delta : kGemmOob);
     const bool kok = g_k < K;                  // K % 16 == 0: the chunk is all in or all out
@@ -202,6 +216,7 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
   const signed char *res = static_cast<const signed char *>(p.res);
   const int act = p.act;
   const bool res_front = res && p.res_first, res_behind = res && !p.res_first;   // block-uniform
+  const __half *ibias = p.ibias;               // block-uniform
   float sc[kCW], bs[kCW];
 #pragma unroll
   for (int c = 0; c < kCW; ++c) {
@@ -238,8 +253,22 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
         }
       }
       float v[kCW];
+      if (ibias) {                             // a per-image bias: the tile's rows may belong to several images
+        const uint4 *bp = reinterpret_cast<const uint4 *>(ibias + (size_t)(m / per) * p.ibias_pitch + ncol);
 #pragma unroll
-      for (int c = 0; c < kCW; ++c) v[c] = __builtin_fmaf((float)s[c >> 2][c & 3], sc[c], bs[c]);
+        for (int q = 0; q < kCW / 8; ++q) {
+          const uint4 h = bp[q];
+          const unsigned hw[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {
+            const int cq = 8 * q + c;
+            v[cq] = __builtin_fmaf((float)s[cq >> 2][cq & 3], sc[cq], (c & 1) ? h2f_hi(hw[c >> 1]) : h2f_lo(hw[c >> 1]));
+          }
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < kCW; ++c) v[c] = __builtin_fmaf((float)s[c >> 2][c & 3], sc[c], bs[c]);
+      }
       if (res_front) {                         // the identity IN FRONT of the activation (res_first)
 #pragma unroll
         for (int c = 0; c < kCW; ++c) v[c] = __builtin_fmaf((float)s8_at(rq, c), p.s_res, v[c]);
@@ -282,11 +311,12 @@ inline bool bad_scale(float s) { return !(s > 0.f) || !(s <= 3.4028234663852886e
 
 using namespace bevops;
 
-extern "C" int bevops_conv_slice_s8_ex(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps,
-                                       const float *w_scales, float scale_w, const float *bias, const void *residual_q,
-                                       int res_pitch, float scale_res, int out_dtype, void *out, int out_pitch,
-                                       float scale_out, int B, int H, int W, int Cin, int Cout, int ksize, int stride,
-                                       int act, int res_first, void *stream) {
+extern "C" int bevops_conv_slice_s8_ex2(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps,
+                                        const float *w_scales, float scale_w, const float *bias, const void *residual_q,
+                                        int res_pitch, float scale_res, int out_dtype, void *out, int out_pitch,
+                                        float scale_out, int B, int H, int W, int Cin, int Cout, int ksize, int stride,
+                                        int act, int res_first, int dilation, const void *image_bias_f16,
+                                        int image_bias_pitch, void *stream) {
   if (!x_q || !w_q_taps || !out || B < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return BEVOPS_BAD_PARAM;
   if (ksize <= 0 || stride <= 0) return BEVOPS_BAD_PARAM;
   if (out_dtype != BEVOPS_I8 && out_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
@@ -299,6 +329,10 @@ extern "C" int bevops_conv_slice_s8_ex(const void *x_q, int x_pitch, float scale
     return BEVOPS_BAD_PARAM;
   if (bad_scale(scale_a) || bad_scale(scale_w) || (residual_q && bad_scale(scale_res)) || (out8 && bad_scale(scale_out)))
     return BEVOPS_BAD_PARAM;
+  if (dilation < 1) return BEVOPS_BAD_PARAM;
+  // a per-image bias: in place of bias; rows of image_bias_pitch halves, each read as 16-byte vectors
+  if (image_bias_f16 && (bias || image_bias_pitch < Cout || image_bias_pitch % 8 != 0 || misaligned(image_bias_f16, 15u)))
+    return BEVOPS_BAD_PARAM;
   if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || act < kActNone || act > kActSilu) return BEVOPS_NOT_SUPPORTED;
   if (Cin % 32 != 0 || Cout % (out8 ? 16 : 8) != 0) return BEVOPS_NOT_SUPPORTED;
   // the identity in front of the activation: of an identity, and not of SiLU (no layer of the models has it)
@@ -307,11 +341,17 @@ extern "C" int bevops_conv_slice_s8_ex(const void *x_q, int x_pitch, float scale
   const unsigned long long rows_in = (unsigned long long)B * H * W;
   if (gemm_over_limit(rows_in, x_pitch, 1) || gemm_over_limit((unsigned long long)Cout, ksize * ksize * Cin, 1))
     return BEVOPS_NOT_SUPPORTED;
+  if (dilation > 1 && (ksize != 3 || stride != 1)) return BEVOPS_NOT_SUPPORTED;
+  // the displacement of a tap, computed for taps outside the image too, is a signed 32-bit byte count
+  if (dilation > 1 && (unsigned long long)dilation * ((unsigned long long)W + 1) * (unsigned long long)x_pitch > 0x7fffffffull)
+    return BEVOPS_NOT_SUPPORTED;
   if (B == 0) return BEVOPS_SUCCESS;
-  const int pad = ksize / 2;
+  const int pad = ksize / 2;                   // at stride 1 a dilated 3 x 3 with pad = dilation keeps the size too
   ConvSliceS8Args p;
   p.x = x_q; p.w = w_q_taps; p.res = residual_q; p.bias = bias; p.wscale = w_scales; p.out = out;
   p.hin = H; p.win = W; p.cin = Cin; p.stride = stride; p.ks = ksize;
+  p.dil = dilation; p.dpitch = dilation * x_pitch;
+  p.ibias = static_cast<const __half *>(image_bias_f16); p.ibias_pitch = image_bias_f16 ? image_bias_pitch : 0;
   p.hout = (H + 2 * pad - ksize) / stride + 1;
   p.wout = (W + 2 * pad - ksize) / stride + 1;
   const unsigned long long rows = (unsigned long long)B * p.hout * p.wout;
@@ -337,6 +377,16 @@ extern "C" int bevops_conv_slice_s8_ex(const void *x_q, int x_pitch, float scale
     else hipLaunchKernelGGL((conv_slice_s8_kernel<2, false>), grid, dim3(256), 0, st, p);
   }
   return launch_status();
+}
+
+extern "C" int bevops_conv_slice_s8_ex(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps,
+                                       const float *w_scales, float scale_w, const float *bias, const void *residual_q,
+                                       int res_pitch, float scale_res, int out_dtype, void *out, int out_pitch,
+                                       float scale_out, int B, int H, int W, int Cin, int Cout, int ksize, int stride,
+                                       int act, int res_first, void *stream) {
+  return bevops_conv_slice_s8_ex2(x_q, x_pitch, scale_a, w_q_taps, w_scales, scale_w, bias, residual_q, res_pitch, scale_res,
+                                  out_dtype, out, out_pitch, scale_out, B, H, W, Cin, Cout, ksize, stride, act, res_first, 1,
+                                  nullptr, 0, stream);
 }
 
 extern "C" int bevops_conv_slice_s8(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps,

@@ -41,7 +41,8 @@ from .deconv import conv_transpose2d_nhwc, pack_deconv4x4s2, deconv_packed_weigh
 from .yolox_ops import (conv_slice_nhwc, conv_slice_taps, conv_slice_packed_weight, focus_nhwc, spp_maxpool_nhwc,
                         upsample_nearest2x_nhwc, pad_channels, unpad_channels, conv_slice_q_taps, focus_nhwc_q,
                         quantize_weight_taps)
-from .lss_depthnet import (lss_camera_gate, se_gate2_nhwc, global_avgpool_nhwc, pack_camera_gate, camera_gate_packed)
+from .lss_depthnet import (lss_camera_gate, se_gate2_nhwc, global_avgpool_nhwc, pack_camera_gate, camera_gate_packed,
+                           se_gate2_nhwc_q, global_avgpool_nhwc_q)
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -79,4 +80,5 @@ __all__ = [
     "upsample_nearest2x_nhwc", "pad_channels", "unpad_channels",
     "conv_slice_q_taps", "focus_nhwc_q", "quantize_weight_taps",
     "lss_camera_gate", "se_gate2_nhwc", "global_avgpool_nhwc", "pack_camera_gate", "camera_gate_packed",
+    "se_gate2_nhwc_q", "global_avgpool_nhwc_q",
 ]

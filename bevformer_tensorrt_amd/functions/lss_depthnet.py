@@ -1,7 +1,8 @@
 """The layers of BEVDepth's DepthNet that are no convolution (csrc/lss_depthnet.hip): the camera-aware squeeze-excite
 gates from the 27 calibration values of every camera (`lss_camera_gate`, fp32 throughout), the gate applied to the depth
-and the context branch in one pass (`se_gate2_nhwc`) and ASPP's global average pool (`global_avgpool_nhwc`).  Not
-reference plugins (TensorRT owns these layers there), so none is in TRT_FUNCTIONS.
+and the context branch in one pass (`se_gate2_nhwc`) and ASPP's global average pool (`global_avgpool_nhwc`), and
+the INT8 siblings of those two on int8 channel slices (`se_gate2_nhwc_q`, `global_avgpool_nhwc_q`;
+csrc/lss_depthnet_s8.hip).  Not reference plugins (TensorRT owns these layers there), so none is in TRT_FUNCTIONS.
 
 `pack_camera_gate` builds the one fp32 parameter block `lss_camera_gate` reads -- the frozen BatchNorm1d(27) folded
 into fc1, every matrix k-major; include/bevops.h states the layout.  `camera_gate_packed` caches it per weight stamp
@@ -11,7 +12,7 @@ import torch
 from ..utils import lib as _lib
 from .linear import _call
 from .multi_scale_deformable_attn import _TensorCache
-from .yolox_ops import _check_f16, _dest, slice_pitch
+from .yolox_ops import _check_f16, _check_s8, _dest, _scale, slice_pitch
 
 GATE_INPUTS = 27
 _GATE_PACKED = _TensorCache()    # depth branch's fc1 weight -> (stamps of all sixteen tensors, block)
@@ -152,4 +153,50 @@ def global_avgpool_nhwc(x, out=None):
     op = out.stride(0) if n > 1 else out.shape[1]
     if n:
         _call("bevops_global_avgpool_nhwc", x.device, x.data_ptr(), xp, out.data_ptr(), op, n, H * W, c)
+    return out
+
+
+def se_gate2_nhwc_q(x_q, scale_x, gates, scale_a, scale_b, out_a=None, out_b=None):
+    """bevops_se_gate2_nhwc_s8: x_q an int8 channel slice [n, c, H, W] (real = q scale_x), gates [2, n, c] fp32
+    contiguous -> (x * gates[0], x * gates[1]) as int8 slices requantised with scale_a / scale_b:
+    q = clamp(rne(((float(q) * scale_x) * gate) * (1 / scale_out)), -127, 127), every step one fp32 product
+    (include/bevops.h); a NaN gate leaves as -127.  x read once, one launch.  c % 16 == 0."""
+    _check_s8(x_q, "x_q")
+    n, c, H, W = x_q.shape
+    if not (torch.is_tensor(gates) and gates.is_cuda and gates.dtype == torch.float32 and gates.is_contiguous() and
+            tuple(gates.shape) == (2, n, c) and gates.device == x_q.device):
+        raise ValueError(f"se_gate2_nhwc_q: gates a contiguous fp32 {(2, n, c)} tensor on the input's device")
+    if c % 16:
+        raise _lib.BevopsError("bevops_se_gate2_nhwc_s8: c % 16 == 0", _lib.NOT_SUPPORTED)
+    sx, sa, sb = _scale(scale_x, "scale_x"), _scale(scale_a, "scale_a"), _scale(scale_b, "scale_b")
+    xp = slice_pitch(x_q, "x_q")
+    out_a = _dest(out_a, (n, c, H, W), x_q, "se_gate2_nhwc_q")
+    out_b = _dest(out_b, (n, c, H, W), x_q, "se_gate2_nhwc_q")
+    ap, bp = slice_pitch(out_a, "out_a"), slice_pitch(out_b, "out_b")
+    if n and H * W:
+        _call("bevops_se_gate2_nhwc_s8", x_q.device, x_q.data_ptr(), xp, sx, gates.data_ptr(), out_a.data_ptr(), ap, sa,
+              out_b.data_ptr(), bp, sb, n, H * W, c)
+    return out_a, out_b
+
+
+def global_avgpool_nhwc_q(x_q, scale_x, out=None):
+    """bevops_global_avgpool_nhwc_s8: x_q an int8 channel slice [n, c, H, W] (real = q scale_x) -> [n, c] fp16 =
+    fp16((float(sum) * scale_x) / float(H W)) with the exact int32 sum over the map: independent of the summation order.
+    out: [n, >= c] fp16 rows to write the first c columns of.  c % 16 == 0, H W <= 2^24."""
+    _check_s8(x_q, "x_q")
+    n, c, H, W = x_q.shape
+    if c % 16 or H * W > 1 << 24:
+        raise _lib.BevopsError("bevops_global_avgpool_nhwc_s8: c % 16 == 0 and H W <= 2^24", _lib.NOT_SUPPORTED)
+    if H * W == 0:
+        raise ValueError("global_avgpool_nhwc_q: an empty map has no mean")
+    sx = _scale(scale_x, "scale_x")
+    xp = slice_pitch(x_q, "x_q")
+    if out is None:
+        out = torch.empty((n, c), dtype=torch.float16, device=x_q.device)
+    elif out.dim() != 2 or out.shape[0] != n or out.shape[1] < c or out.dtype != torch.float16 or \
+            out.device != x_q.device or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise ValueError(f"global_avgpool_nhwc_q: out [n, >= c] fp16 rows on the input's device, got {tuple(out.shape)}")
+    op = out.stride(0) if n > 1 else out.shape[1]
+    if n:
+        _call("bevops_global_avgpool_nhwc_s8", x_q.device, x_q.data_ptr(), xp, sx, out.data_ptr(), op, n, H * W, c)
     return out

@@ -333,14 +333,17 @@ def quantize_weight_taps(weight, bias=None, groups_in=None, groups_out=None, mul
 
 
 def conv_slice_q_taps(x_q, scale_x, w_q_taps, w_scales, bias, act, residual_q=None, scale_res=1.0, stride=1, out=None,
-                      scale_out=None, out_dtype=torch.int8, res_first=False):
-    """bevops_conv_slice_s8(_ex): the convolution of an int8 channel slice x_q [B, Cin, H, W] (real = q scale_x) with int8
+                      scale_out=None, out_dtype=torch.int8, res_first=False, dilation=1, image_bias=None):
+    """bevops_conv_slice_s8(_ex, _ex2): the convolution of an int8 channel slice x_q [B, Cin, H, W] (real = q scale_x) with int8
     taps-major weights w_q_taps [Cout, k, k, Cin] (real = q w_scales[co]; w_scales fp32 [Cout]), bias fp32 [Cout] or
     None, act in "none", "relu", "silu", the int8 identity residual_q (real = q scale_res) added BEHIND the
     activation -- or, with res_first=True (act "none" / "relu" and an identity, else BevopsError NOT_SUPPORTED), IN FRONT of
     it: act(conv + bias + identity), mmdet's BasicBlock.  out_dtype torch.int8: requantised with scale_out, q = clamp(rne(v / scale_out), -127, 127);
     torch.float16: one rounding (scale_out unused).  Cin % 32 == 0, Cout % 16 == 0 (int8 out) or % 8 (fp16 out), k in
-    {1, 3}, stride in {1, 2}, else BevopsError NOT_SUPPORTED.  include/bevops.h states the operation order."""
+    {1, 3}, stride in {1, 2}, else BevopsError NOT_SUPPORTED.  include/bevops.h states the operation order.
+    dilation > 1 (bevops_conv_slice_s8_ex2): k == 3 and stride == 1, pad = dilation, else BevopsError NOT_SUPPORTED.
+    image_bias [B, P] fp16 (P >= Cout, P % 8 == 0, rows contiguous): a bias per IMAGE in place of `bias` -- output pixel
+    (b, y, x) takes image_bias[b, co].  With the defaults the call is bevops_conv_slice_s8_ex's."""
     _check_s8(x_q, "x_q")
     if w_q_taps.dim() != 4 or w_q_taps.shape[1] != w_q_taps.shape[2] or not w_q_taps.is_contiguous() or \
             w_q_taps.dtype != torch.int8 or w_q_taps.device != x_q.device:
@@ -380,7 +383,28 @@ def conv_slice_q_taps(x_q, scale_x, w_q_taps, w_scales, bias, act, residual_q=No
         rp, sr = slice_pitch(residual_q, "residual_q"), _scale(scale_res, "scale_res")
     if res_first and (residual_q is None or act == "silu"):
         raise _lib.BevopsError("bevops_conv_slice_s8_ex: res_first needs an identity and act none / relu", _lib.NOT_SUPPORTED)
+    dilation = int(dilation)
+    if dilation < 1:
+        raise ValueError("conv_slice_q: dilation >= 1")
+    if dilation > 1 and (k != 3 or stride != 1):
+        raise _lib.BevopsError("bevops_conv_slice_s8_ex2: dilation > 1 needs ksize 3 and stride 1", _lib.NOT_SUPPORTED)
+    bp = 0
+    if image_bias is not None:
+        if bias is not None:
+            raise ValueError("conv_slice_q: image_bias replaces bias, pass one of them")
+        _check_f16(image_bias, "image_bias")
+        if image_bias.dim() != 2 or image_bias.shape[0] != B or image_bias.shape[1] < Cout or \
+                (image_bias.shape[1] > 1 and image_bias.stride(1) != 1) or image_bias.device != x_q.device:
+            raise ValueError(f"conv_slice_q: image_bias [B, >= Cout] with contiguous rows, got {tuple(image_bias.shape)}")
+        bp = image_bias.stride(0) if B > 1 else padded_width(image_bias.shape[1], 8)
+        if bp < Cout or bp % 8 or image_bias.data_ptr() % 16:
+            raise ValueError(f"conv_slice_q: image_bias rows start on 16-byte boundaries, pitch a multiple of 8 (pitch {bp})")
     if B == 0:
+        return out
+    if dilation > 1 or image_bias is not None:
+        _call("bevops_conv_slice_s8_ex2", x_q.device, x_q.data_ptr(), xp, sx, w_q_taps.data_ptr(), _ptr(w_scales), 1.0,
+              _ptr(bias), _ptr(residual_q), rp, sr, _lib.I8 if out8 else _lib.F16, out.data_ptr(), op, so, B, H, W, Cin,
+              Cout, k, int(stride), ACTS[act], int(bool(res_first)), dilation, _ptr(image_bias), bp)
         return out
     _call("bevops_conv_slice_s8_ex", x_q.device, x_q.data_ptr(), xp, sx, w_q_taps.data_ptr(), _ptr(w_scales), 1.0,
           _ptr(bias), _ptr(residual_q), rp, sr, _lib.I8 if out8 else _lib.F16, out.data_ptr(), op, so, B, H, W, Cin, Cout, k,

@@ -1068,7 +1068,7 @@ def build_int8_engine(B, name, dev, frames, calibrator="entropy", chain=True, de
 BEVDET_BEV_HALF_BUILDS = ("fp16", "int8")
 
 
-def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", calibration_cache=None):
+def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", calibration_cache=None, cfg=None):
     """The PTQ build of the re-hosted BEVDet-R50 (BASELINE config 5; `D` = the bevdet module, or a bevdet.BEVDet
     instance whose weights to quantise; `frames` = an iterable of (image, ranks...) calibration inputs): ResNet-50 + FPN
     laterals as the int8 activation chain, bev_pool_v2 on its INT8 plugin flavour.  bev_half="fp16" (the default): the
@@ -1080,25 +1080,37 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
     (image chain, pooling and BEV half) are saved there (the format of save_calibration / load_calibration).
     Returns (model, qops, note); with bev_half="int8" the model is a bevdet_int8.Int8BEVDet (forward,
     forward_calibrated, bev_half_calibrated, get_candidates, get_bboxes, prepare_bev_half: BEVDetRunner captures it
-    unchanged)."""
+    unchanged).
+    A BEVDepth model (cfg["view_transformer"] == "bevdepth"; `cfg`: the configuration to ask a module `D` for, forwarded
+    only when given) is built with bev_half="int8" only: the DepthNet's int8 plan of bevdepth_int8.py in front of the same
+    BEV half (design/bevdepth_int8.md), frames = (image, ranks_bev, ranks_depth, ranks_feat, interval_starts,
+    interval_lengths, mlp_input), the model a bevdepth_int8.Int8BEVDepth.  The default bev_half="fp16" build of a BEVDepth
+    model is not built: NotImplementedError."""
     if bev_half not in BEVDET_BEV_HALF_BUILDS:
         raise ValueError(f"bev_half = {bev_half!r}: one of {BEVDET_BEV_HALF_BUILDS}")
     if calibration_cache is not None and bev_half != "int8":
         raise ValueError("build_int8_bevdet: calibration_cache goes with bev_half='int8'")
     src = D if isinstance(D, torch.nn.Module) else None
-    if src is not None and getattr(src, "cfg", {}).get("view_transformer") == "bevdepth":
-        raise NotImplementedError("build_int8_bevdet: INT8 BEVDepth is not built (the DepthNet has no int8 plan); "
-                                  "see design/bevdepth.md")
+    depthnet = ((getattr(src, "cfg", None) if src is not None else cfg) or {}).get("view_transformer") == "bevdepth"
+    if depthnet and bev_half != "int8":
+        raise NotImplementedError("build_int8_bevdet: the bev_half='fp16' build of a BEVDepth model is not built (its "
+                                  "DepthNet has an int8 plan only in front of the int8 BEV half); pass bev_half=\"int8\" "
+                                  "(design/bevdepth_int8.md)")
     if src is not None:
         from . import bevdet as D
+    kw = {}
+    if src is not None and depthnet:
+        kw["cfg"] = src.cfg
+    elif src is None and cfg is not None:
+        kw["cfg"] = cfg
     qops = Int8PluginOps(calibrator, channels_last=True)
-    model = D.BEVDet(ops=qops, seed=0).to(dev, torch.float16)
+    model = D.BEVDet(ops=qops, seed=0, **kw).to(dev, torch.float16)
     if src is not None:
         model.load_state_dict(src.state_dict())
     model.view.ops = qops
     ch = Int8ChainBackbone(model, qops.cal)
     if bev_half == "int8":
-        return _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache)
+        return _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache, depthnet)
     n = 0
     for f in frames:
         qops.begin_frame()
@@ -1113,10 +1125,14 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
     return model, qops, note
 
 
-def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache):
+def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache, depthnet=False):
     """build_int8_bevdet(bev_half="int8") behind the construction of the image chain: the calibration frames (or the
-    cache), the freeze, the Int8BEVDet around the model."""
+    cache), the freeze, the Int8BEVDet (depthnet: the Int8BEVDepth) around the model."""
     from . import bevdet_int8 as _bi
+    if depthnet:
+        from . import bevdepth_int8 as _plan
+    else:
+        _plan = _bi
     cal = qops.cal
     n = 0
     if calibration_cache is not None and os.path.exists(calibration_cache):
@@ -1133,20 +1149,28 @@ def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache)
             for f in frames:
                 qops.begin_frame()
                 model(*f)
-                _bi.calibrate_frame(model, seen.pop("x"), f[1:], cal)
+                _plan.calibrate_frame(model, seen.pop("x"), f[1:], cal)
                 n += 1
         finally:
             del model.image_features
         if calibration_cache is not None:
-            _bi.save_calibration(cal, calibration_cache, {"model": "bevdet", "bev_half": "int8", "frames": n})
+            _bi.save_calibration(cal, calibration_cache, {"model": "bevdepth" if depthnet else "bevdet", "bev_half": "int8",
+                                                         "frames": n})
     scales = qops.freeze()
     ch.freeze()
     model.register_forward_pre_hook(lambda m, args: qops.begin_frame())
-    q = _bi.Int8BEVDet(model, _bi.scales_from(cal, _bi.build_plan(model).sites))
+    if depthnet:
+        q = _plan.Int8BEVDepth(model, _bi.scales_from(cal, _plan.build_plan(model).sites))
+    else:
+        q = _bi.Int8BEVDet(model, _bi.scales_from(cal, _bi.build_plan(model).sites))
     note = {"int8_plugin_sites": sum(1 for k in scales if k.startswith("bev_pool") and k.endswith(".out")),
             "int8_backbone_layers": len(ch.convs) + sum(len(b) for b in ch.plan), "activation_chain": True,
             "calibration_frames": n, "bev_half": "int8", "int8_bev_half_layers": q.num_int8_layers,
             "bev_half_scale_sites": len(q.plan.sites)}
+    if depthnet:
+        front = q.plan.layers[:q.plan.tail]
+        note["depthnet_int8_layers"] = sum(1 for l in front if l.op == "conv")
+        note["depthnet_scale_sites"] = len([s for s in q.plan.sites if s.startswith(_bi.SITE_PREFIX + "dn.")])
     return q, qops, note
 
 

@@ -145,6 +145,11 @@ SIGNATURES = {
                                      c_float, c_int, c_void_p, c_int, c_float] + [c_int] * 8 + [c_void_p]),
     "bevops_conv_slice_s8_ex": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
                                         c_float, c_int, c_void_p, c_int, c_float] + [c_int] * 9 + [c_void_p]),
+    "bevops_conv_slice_s8_ex2": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
+                                         c_float, c_int, c_void_p, c_int, c_float] + [c_int] * 10 + [c_void_p, c_int, c_void_p]),
+    "bevops_se_gate2_nhwc_s8": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int,
+                                        c_float] + [c_int] * 3 + [c_void_p]),
+    "bevops_global_avgpool_nhwc_s8": (c_int, [c_void_p, c_int, c_float, c_void_p] + [c_int] * 4 + [c_void_p]),
     "bevops_deconv4x4s2_s8": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_float] +
                               [c_int] * 6 + [c_void_p]),
     "bevops_focus_nhwc_q": (c_int, [c_void_p, c_float, c_void_p] + [c_int] * 4 + [c_void_p]),

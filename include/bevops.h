@@ -704,6 +704,57 @@ int bevops_conv_slice_s8_ex(const void *x_q, int x_pitch, float scale_a, const v
                             float scale_w, const float *bias, const void *residual_q, int res_pitch, float scale_res,
                             int out_dtype, void *out, int out_pitch, float scale_out, int B, int H, int W, int Cin, int Cout,
                             int ksize, int stride, int act, int res_first, void *stream);
+/* bevops_conv_slice_s8_ex with a DILATION and an optional PER-IMAGE bias (the ASPP block of the INT8 build of BEVDepth's
+ * DepthNet; csrc/conv_slice_s8.hip, the same four kernels: both are block-uniform runtime values, the siblings of
+ * bevops_conv_slice_f16_ex's).  bevops_conv_slice_s8_ex forwards here with (1, NULL, 0) and keeps its bits.
+ *   dilation >= 1, pad = dilation * (ksize / 2): tap (ky, kx) of output pixel (y, x) reads input pixel
+ *     (y + (ky - 1) dilation, x + (kx - 1) dilation), zero outside the image; stride 1 keeps the size.
+ *   image_bias_f16 != NULL: fp16 [B][image_bias_pitch] in place of bias (fp16 because the few-row GEMM that makes it
+ *     writes fp16, as on the fp16 path).  Output row m = pixel (b, y, x) takes the row of ITS image, b = m / (Hout Wout)
+ *     -- a row tile may hold pixels of several images -- and the epilogue's first step becomes
+ *       v = fma((float)sum, sc, (float)image_bias_f16[b * image_bias_pitch + co])
+ *     ((float) of a binary16 value is exact); every step behind it is bevops_conv_slice_s8_ex's.
+ * Statuses, in this order: everything BEVOPS_BAD_PARAM of bevops_conv_slice_s8 (NULL operands, sizes, pitches,
+ * alignments, scales; out_dtype outside the list is BEVOPS_NOT_SUPPORTED in front of the pitch checks, as there);
+ * dilation < 1: BEVOPS_BAD_PARAM; image_bias_f16 together with bias, image_bias_pitch < Cout, image_bias_pitch % 8 != 0 or
+ * image_bias_f16 not 16-byte aligned: BEVOPS_BAD_PARAM.  Then everything BEVOPS_NOT_SUPPORTED of
+ * bevops_conv_slice_s8_ex; dilation > 1 with ksize != 3 or stride != 1: BEVOPS_NOT_SUPPORTED; with dilation > 1 the
+ * displacement of a tap, computed for taps outside the image too, must fit a signed 32-bit byte count:
+ * dilation (W + 1) x_pitch <= 0x7FFFFFFF, else BEVOPS_NOT_SUPPORTED.  dilation == 1 is EXEMPT from this rule, so that
+ * bevops_conv_slice_s8 and bevops_conv_slice_s8_ex, which forward here, keep every status they had: at dilation 1 a tap
+ * inside the image lies inside the extent B H W x_pitch < 0xFFFFFF00 that is checked anyway, the kernel adds the
+ * displacement to the centre pixel's offset in unsigned 32-bit arithmetic (the sum is the tap's true offset modulo
+ * 2^32, whatever the displacement's size), and the value computed for a tap outside the image is never used as an
+ * address.  B == 0: BEVOPS_SUCCESS without a launch. */
+int bevops_conv_slice_s8_ex2(const void *x_q, int x_pitch, float scale_a, const void *w_q_taps, const float *w_scales,
+                             float scale_w, const float *bias, const void *residual_q, int res_pitch, float scale_res,
+                             int out_dtype, void *out, int out_pitch, float scale_out, int B, int H, int W, int Cin, int Cout,
+                             int ksize, int stride, int act, int res_first, int dilation, const void *image_bias_f16,
+                             int image_bias_pitch, void *stream);
+/* The INT8 siblings of bevops_se_gate2_nhwc and bevops_global_avgpool_nhwc (csrc/lss_depthnet_s8.hip; the INT8 build of
+ * BEVDepth's DepthNet) on int8 channel slices as in bevops_conv_slice_s8 (16-byte boundary, pitch a multiple of 16
+ * elements, real = q scale).  Neither allocates, synchronises or uses atomics; n == 0: BEVOPS_SUCCESS without a launch.
+ * bevops_se_gate2_nhwc_s8: x_q int8, n images of hw pixels of c channels; gates fp32 [2][n][c] as
+ *   bevops_lss_camera_gate writes them.  For out_a with (gates[0], scale_a) and out_b with (gates[1], scale_b), every
+ *   step ONE fp32 operation in exactly this order, none of them an addition (nothing to contract into an fma):
+ *     t = (float)x_q * scale_x;   v = t * gate[i][ch];   r = v * inv_out;   q = min(max(rne(r), -127), 127)
+ *   with inv_out = 1.f / scale_out computed once on the host in fp32.  A NaN r (a NaN gate) leaves as -127.  x is read
+ *   once (16 bytes per thread), two 16-byte stores.  out_a / out_b must not overlap x_q or each other.
+ *   Statuses, in this order: NULL operands, n < 0, hw <= 0, c <= 0; a pitch below c or no multiple of 16; x_q / gates /
+ *   out_a / out_b not 16-byte aligned; a scale that is not positive and finite: BEVOPS_BAD_PARAM.  c % 16 != 0, more
+ *   than 2^31 - 1 blocks of 256 vectors: BEVOPS_NOT_SUPPORTED.
+ * bevops_global_avgpool_nhwc_s8: out fp16 [n][out_pitch],
+ *     out[i, ch] = fp16(((float)sum * scale_x) / (float)hw),   sum = sum_p x_q[i, p, ch]   (int32, EXACT)
+ *   (float)sum rounds to nearest even (exact for |sum| <= 2^24), one fp32 product, one IEEE division, one rounding to
+ *   binary16.  hw <= 2^24, so |sum| <= 127 * 2^24 < 2^31.  Integer sums: the result depends on neither the order nor the
+ *   grid.
+ *   Statuses, in this order: NULL operands, n < 0, hw <= 0, c <= 0; x_pitch below c or no multiple of 16, out_pitch < c;
+ *   x_q not 16-byte aligned, out not 2-byte aligned; scale_x not positive and finite: BEVOPS_BAD_PARAM.  c % 16 != 0,
+ *   hw > 2^24, n ceil(c / 64) > 2^31 - 1: BEVOPS_NOT_SUPPORTED. */
+int bevops_se_gate2_nhwc_s8(const void *x_q, int x_pitch, float scale_x, const float *gates, void *out_a, int a_pitch,
+                            float scale_a, void *out_b, int b_pitch, float scale_b, int n, int hw, int c, void *stream);
+int bevops_global_avgpool_nhwc_s8(const void *x_q, int x_pitch, float scale_x, void *out, int out_pitch, int n, int hw,
+                                  int c, void *stream);
 /* bevops_deconv4x4s2_f16's INT8 sibling (csrc/deconv_s8.hip; the up-sampling layers of the INT8 build of CenterNet):
  * ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1) + bias + ReLU on channels-last INT8 activations as four implicit
  * GEMMs on the int8 matrix cores, one per output parity, sums exact in int32:
