@@ -13,7 +13,11 @@ Two data paths through the same weights:
     buffer (conv_slice_nhwc, three of them dilated), ASPP's pooled branch as a per-image bias of conv1
     (global_avgpool_nhwc + two few-row GEMMs: a bilinear up-sampling of a 1 x 1 map is a constant), context_conv and
     the last 1 x 1 into the feature / depth-logit columns of the row buffer lss_depth_split reads.  No library
-    convolution, pooling, interpolation, torch.cat or layout copy."""
+    convolution, pooling, interpolation, torch.cat or layout copy.
+
+DepthNet(use_dcn=True) puts the reference's DCN layer (mmcv's DCNv1 pack, groups = 4; `DeformConv2dPack`) between the
+ASPP and the last convolution: functions.deform_conv2d on the plain path, conv_offset_nhwc + deform_conv2d_nhwc (two
+launches) on the fast one.  design/bevdepth_dcn.md."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -79,13 +83,61 @@ def fold_pooled_branch(aspp, pooled):
     return F.linear(g, aspp.conv1.weight.flatten(1)[:, 4 * mid:], aspp.conv1.bias)
 
 
+DCN_GROUPS = 4
+DCN_WIDTH_MULTIPLE = 32 * DCN_GROUPS     # csrc/deform_conv.hip: (channels / groups) % 32 == 0
+
+
+class DeformConv2dPack(nn.Module):
+    """mmcv's `DCN` (DeformConv2dPack, DCNv1) as DepthNet builds it: `conv_offset` (3 x 3, 18 channels, zero-initialised:
+    an untrained pack is a plain grouped convolution) and an UNMODULATED deformable 3 x 3 convolution with groups = 4,
+    deform_groups = 1, no bias; no BatchNorm or ReLU behind it.  mmcv's attribute names."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, dilation=1, groups=DCN_GROUPS,
+                 deform_groups=1):
+        super().__init__()
+        if (kernel_size, stride, padding, dilation, deform_groups) != (3, 1, 1, 1, 1):
+            raise NotImplementedError("DeformConv2dPack: 3 x 3 / stride 1 / padding 1 / dilation 1 / one deform group only")
+        if in_channels % groups or out_channels % groups:
+            raise ValueError("DeformConv2dPack: channels must divide into the groups")
+        self.in_channels, self.out_channels, self.groups, self.deform_groups = in_channels, out_channels, groups, deform_groups
+        self.kernel_size, self.stride, self.padding, self.dilation = (3, 3), (1, 1), (1, 1), (1, 1)
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels // groups, 3, 3))
+        stdv = 1.0 / (in_channels * 9) ** 0.5                       # (mmcv DeformConv2d.reset_parameters)
+        nn.init.uniform_(self.weight, -stdv, stdv)
+        self.conv_offset = nn.Conv2d(in_channels, deform_groups * 18, 3, 1, 1)
+        nn.init.zeros_(self.conv_offset.weight)
+        nn.init.zeros_(self.conv_offset.bias)
+
+    def forward(self, x):
+        from .functions.deform_conv import deform_conv2d
+        offset = self.conv_offset(x)
+        return deform_conv2d(x, offset, self.weight, 1, 1, 1, self.groups, self.deform_groups)
+
+    def prepack(self):
+        """Both packed operands of `forward_hip` (never under capture)."""
+        from .functions.deform_conv import deform_conv_packed_weight
+        from .functions.modulated_deformable_conv2d import conv_offset_nhwc
+        w = self.conv_offset.weight
+        deform_conv_packed_weight(self.weight)
+        # an empty batch: the wrapper packs the offset weight and pads the bias, and launches nothing
+        conv_offset_nhwc(w.new_empty((0, self.in_channels, 1, 1)).contiguous(memory_format=torch.channels_last), w,
+                         self.conv_offset.bias)
+
+    def forward_hip(self, x, ops):
+        """Two launches: the offset convolution ([n, 32, H, W] channels-last, offsets in channels 0 .. 18) and the
+        deformable convolution that reads its rows in place."""
+        om = ops.conv_offset_nhwc(x, self.conv_offset.weight, self.conv_offset.bias)
+        return ops.deform_conv2d_nhwc(x, om, self.weight, None, self.groups)
+
+
 class DepthNet(nn.Module):
     def __init__(self, in_channels, mid_channels, context_channels, depth_channels, use_aspp=True, aspp_mid_channels=-1,
                  use_dcn=False, stereo=False):
         super().__init__()
-        if use_dcn:
-            raise NotImplementedError("DepthNet(use_dcn=True): the reference's mmcv DCN (DCNv1, groups=4) has no "
-                                      "channels-last kernel and no CPU statement in this package (DESIGN.md section 8)")
+        if use_dcn and mid_channels % DCN_WIDTH_MULTIPLE:
+            raise NotImplementedError(f"DepthNet(use_dcn=True): the DCN layer (mmcv DCN: DCNv1, groups={DCN_GROUPS}) is built "
+                                      f"for mid_channels % {DCN_WIDTH_MULTIPLE} == 0 only (mid_channels / {DCN_GROUPS} a multiple "
+                                      f"of 32, on both data paths); got {mid_channels} (design/bevdepth_dcn.md)")
         if stereo:
             raise NotImplementedError("DepthNet(stereo=True): the BEVStereo cost volume is not built (DESIGN.md section 8)")
         self.mid_channels, self.context_channels, self.depth_channels = mid_channels, context_channels, depth_channels
@@ -97,13 +149,19 @@ class DepthNet(nn.Module):
         layers = [BasicBlock(mid_channels, mid_channels, 1, False) for _ in range(3)]
         if use_aspp:
             layers.append(ASPP(mid_channels, mid_channels if aspp_mid_channels < 0 else aspp_mid_channels))
+        if use_dcn:
+            layers.append(DeformConv2dPack(mid_channels, mid_channels))
         layers.append(nn.Conv2d(mid_channels, depth_channels, 1))
         self.depth_conv = nn.ModuleList(layers)          # (the reference's nn.Sequential: the same indices)
-        self.use_aspp = use_aspp
+        self.use_aspp, self.use_dcn = use_aspp, bool(use_dcn)
 
     @property
     def aspp(self):
         return self.depth_conv[3] if self.use_aspp else None
+
+    @property
+    def dcn(self):
+        return self.depth_conv[-2] if self.use_dcn else None
 
     # ---- plain: DepthNet.forward :680-712
     def gates(self, mlp_input):
@@ -170,6 +228,8 @@ class DepthNet(nn.Module):
         if w.is_cuda and w.dtype == torch.float16:
             for t, cin, cout in slices:
                 Y.conv_slice_packed_weight(t, cin, cout)
+            if self.use_dcn:
+                self.dcn.prepack()
         self.__dict__["_fast_operands"] = (stamp, ops)
         return ops
 
@@ -201,6 +261,8 @@ class DepthNet(nn.Module):
             g = ops.dense_auto(pooled, P["pool_w"], a.global_avg_pool.bias, None, True)           # [n, amid]
             image_bias = ops.dense_auto(g, P["conv1_pool"], a.conv1.bias, None, False)            # [n, mid]
             depth = ops.conv_slice_nhwc(cat, P["conv1_main"], None, "relu", image_bias=image_bias)
+        if self.use_dcn:
+            depth = self.dcn.forward_hip(depth, ops)                                              # 2 launches
         ops.conv_slice_nhwc(depth, P["wd"], P["bd"], "none", out=rows[:, o:o + lay["depth_padded"]])
         return rows.permute(0, 2, 3, 1).reshape(n * H * W, lay["row_stride"]), lay
 
@@ -253,10 +315,12 @@ class LSSViewTransformerBEVDepth(LSSViewTransformer):
 
     # ---- the fast path's switches: the parent's names, so that BEVDet.prepare_bev_half / _bev_half_ready serve both
     def _hip_on(self, x):
+        need = ("lss_depth_split", "dense_auto", "conv_nhwc", "conv_slice_nhwc", "lss_camera_gate", "se_gate2_nhwc",
+                "global_avgpool_nhwc")
+        if self.depth_net.use_dcn:
+            need += ("conv_offset_nhwc", "deform_conv2d_nhwc")
         return self.bev_half == "hip" and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 \
-            and x.is_contiguous(memory_format=torch.channels_last) \
-            and all(hasattr(self.ops, f) for f in ("lss_depth_split", "dense_auto", "conv_nhwc", "conv_slice_nhwc",
-                                                   "lss_camera_gate", "se_gate2_nhwc", "global_avgpool_nhwc"))
+            and x.is_contiguous(memory_format=torch.channels_last) and all(hasattr(self.ops, f) for f in need)
 
     def depth_net_merged(self, build=True):
         return self.depth_net.fast_operands(build=build)

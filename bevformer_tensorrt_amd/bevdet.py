@@ -113,9 +113,10 @@ DATA_CONFIG_R50 = dict(input_size=(256, 704), src_size=(900, 1600), crop_h=(0.0,
 BEVDET_R50 = dict(
     grid_config=dict(x=[-51.2, 51.2, 0.8], y=[-51.2, 51.2, 0.8], z=[-5, 3, 8], depth=[1.0, 60.0, 1.0]),
     input_size=(256, 704), downsample=16, in_channels=256, out_channels=64)
-# BEVDepth-R50: the same detector with the camera-aware DepthNet + ASPP in front of the pooling (bevdepth.py); the
-# reference's DCN layer (DepthNet's default use_dcn=True) is not built
+# BEVDepth-R50: the same detector with the camera-aware DepthNet + ASPP in front of the pooling (bevdepth.py), without
+# and with the reference's DCN layer behind the ASPP (DepthNet's default use_dcn=True: mmcv's DCNv1 pack, groups = 4)
 BEVDEPTH_R50 = dict(BEVDET_R50, view_transformer="bevdepth", depthnet_cfg=dict(use_dcn=False))
+BEVDEPTH_R50_DCN = dict(BEVDET_R50, view_transformer="bevdepth", depthnet_cfg=dict(use_dcn=True))
 
 
 class LSSViewTransformer(nn.Module):

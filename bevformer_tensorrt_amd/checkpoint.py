@@ -319,6 +319,10 @@ def depthnet_key_map(depth_net, prefix="img_view_transformer.depth_net."):
         fold("depth_conv.3.global_avg_pool", "depth_conv.3.global_avg_pool.1", "depth_conv.3.global_avg_pool.2")
         fold("depth_conv.3.conv1", "depth_conv.3.conv1", "depth_conv.3.bn1")
         last = 4
+    if getattr(depth_net, "use_dcn", False):      # mmcv's DCN pack: weight (no bias) and conv_offset, no BatchNorm behind it
+        m[f"depth_conv.{last}.weight"] = f"{prefix}depth_conv.{last}.weight"
+        copy(f"depth_conv.{last}.conv_offset")
+        last += 1
     copy(f"depth_conv.{last}")
     return m
 

@@ -1091,7 +1091,12 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
     if calibration_cache is not None and bev_half != "int8":
         raise ValueError("build_int8_bevdet: calibration_cache goes with bev_half='int8'")
     src = D if isinstance(D, torch.nn.Module) else None
-    depthnet = ((getattr(src, "cfg", None) if src is not None else cfg) or {}).get("view_transformer") == "bevdepth"
+    model_cfg = (getattr(src, "cfg", None) if src is not None else cfg) or {}
+    depthnet = model_cfg.get("view_transformer") == "bevdepth"
+    if depthnet and ((model_cfg.get("depthnet_cfg") or {}).get("use_dcn", False)
+                     or getattr(getattr(getattr(src, "view", None), "depth_net", None), "use_dcn", False)):
+        raise NotImplementedError("build_int8_bevdet: the DepthNet's DCN layer (use_dcn=True) has no INT8 form; build "
+                                  "the model with use_dcn=False (BEVDEPTH_R50) for an INT8 BEVDepth (design/bevdepth_dcn.md)")
     if depthnet and bev_half != "int8":
         raise NotImplementedError("build_int8_bevdet: the bev_half='fp16' build of a BEVDepth model is not built (its "
                                   "DepthNet has an int8 plan only in front of the int8 BEV half); pass bev_half=\"int8\" "

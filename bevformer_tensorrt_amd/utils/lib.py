@@ -211,6 +211,8 @@ SIGNATURES = {
     "bevops_calib_threshold_workspace_size": (c_size_t, [c_int]),
     "bevops_calib_threshold": (c_int, [c_int, ctypes.c_double, c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p,
                                        c_size_t, c_void_p]),
+    "bevops_deform_conv3x3_nhwc_f16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 7 +
+                                       [c_void_p]),
 }
 
 F32, F16, I8, U8 = 0, 1, 2, 3

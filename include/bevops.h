@@ -1501,6 +1501,34 @@ size_t bevops_calib_threshold_workspace_size(int num_states);
 int bevops_calib_threshold(int method, double percentile, const void *states, int num_states, size_t state_stride,
                            int32_t *bins, double *kl, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Grouped, UNMODULATED deformable convolution (DCNv1; csrc/deform_conv.hip, design/bevdepth_dcn.md): the deformable
+ * convolution of mmcv's `DCN` pack as BEVDepth's DepthNet places it behind its ASPP block (groups = 4, deform_groups = 1;
+ * third_party/bev_mmdet3d/models/necks/view_transformer.py:590-601).  Not a reference plugin.  3 x 3, stride 1,
+ * padding 1, dilation 1, ONE deform group, channels-last fp16:
+ *   input_nhwc  [B, H, W, Cin], output_nhwc [B, H, W, Cout];
+ *   offset_nhwc [B, H, W, offset_channels]: the raw output of the pack's offset convolution (what
+ *               bevops_conv3x3_c32_forward_nhwc writes: offset_channels = 32).  Channels [0, 18) are the offsets, (h, w)
+ *               per tap, taps row-major; channels >= 18 are never read;
+ *   packed_weight: bevops_mdconv_pack_weight(BEVOPS_F16, ...) of weight [Cout, Cin / groups, 3, 3];
+ *   bias [Cout] fp16 or NULL; relu 0 or 1.
+ * The DCNv2 sampling rules of bevops_mdconv_forward with the mask identically 1: h = y - 1 + i + off_h, w = x - 1 + j +
+ * off_w in fp32; a tap contributes iff h > -1 && w > -1 && h < H && w < W; bilinear, corners outside the image
+ * contribute zero (and are not read), corners inside are multiplied even by a zero weight; the sample is
+ * fma(w11, v11, fma(w10, v10, fma(w01, v01, w00 * v00))) in fp32, rounded once to fp16; fp32 accumulation on the fp16
+ * matrix cores over k = (tap, channel); bias and ReLU in fp32; one rounding at the store.
+ * One launch for all groups; no workspace, no atomics, no allocation, no synchronisation; capturable.
+ * Status, in this order:
+ *   BAD_PARAM      a NULL input / offset / weight / output; any pointer (bias included) off a 16-byte boundary; B < 0;
+ *                  H, W, Cin, Cout or groups <= 0; relu not 0 / 1; offset_channels < 18 or odd
+ *   NOT_SUPPORTED  Cin % groups, Cout % groups, (Cin / groups) % 32 or (Cout / groups) % 32 non-zero;
+ *                  B H W > 2^31 - 65 (32-bit pixel index); groups * ceil(Cout / groups / 64) > 65535 (grid rows)
+ *   SUCCESS        B == 0, without a launch
+ * ------------------------------------------------------------------------ */
+int bevops_deform_conv3x3_nhwc_f16(const void *input_nhwc, const void *offset_nhwc, int offset_channels,
+                                   const void *packed_weight, const void *bias, void *output_nhwc, int relu,
+                                   int B, int H, int W, int Cin, int Cout, int groups, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
