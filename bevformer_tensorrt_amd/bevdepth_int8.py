@@ -25,52 +25,48 @@ import torch.nn.functional as F
 from . import bevdet_int8 as _bi
 from . import functions as _hip_ops
 from .bevdepth import ASPP_DILATIONS, MLP_INPUTS
-from .bevdet_int8 import CAT, SITE_PREFIX, Layer, Plan, _fq, load_calibration, save_calibration, scales_from   # noqa: F401
+from .bevdet_int8 import CAT, SITE_PREFIX   # noqa: F401
 from .functions import dispatch as _dispatch
 from .functions import yolox_ops as _Y
+from .int8_plan import (Layer, Plan, basic_block_layers, float_operands, load_calibration, save_calibration,   # noqa: F401
+                        scales_from, stored)
 
 ASPP_CAT = "dn.aspp.cat"
 ROWS = "dn.rows"
 
 
-class DLayer(Layer):
-    """bevdet_int8.Layer with a dilation and the name of the fp16 per-image bias tensor; further ops "gate" (dst and
-    extra[0]: the depth and the context copy) and "avgpool" (pool + the two fp16 GEMMs of the pooled branch)."""
-
-    def __init__(self, op, key, src, dst, dilation=1, image_bias=None, **kw):
-        super().__init__(op, key, src, dst, **kw)
-        self.dilation, self.image_bias = dilation, image_bias
+# Layer ops beside bevdet_int8's: "gate" (dst and extra[0]: the depth and the context copy) and "avgpool" (the pool + the
+# two fp16 GEMMs of the pooled branch).
 
 
 def depthnet_layers(P, dn, x):
     """The DepthNet's layers on the plan P from the int8 tensor `x`; the last one writes "depth_net", the fp16 row buffer."""
     lay = dn.row_layout()
     P.buffers[ROWS] = lay["row_stride"]
-    r = P.add(DLayer("conv", "dn.reduce_conv", x, "dn.r", act="relu"))
-    P.add(DLayer("gate", None, r, "dn.depth0", extra=("dn.context",)))
-    P.add(DLayer("conv", "dn.context_conv", "dn.context", "dn.feat_cols", into=(ROWS, lay["feat_offset"])), "f16")
+    r = P.add(Layer("conv", "dn.reduce_conv", x, "dn.r", act="relu"))
+    P.add(Layer("gate", None, r, "dn.depth0", extra=("dn.context",)))
+    P.add(Layer("conv", "dn.context_conv", "dn.context", "dn.feat_cols", into=(ROWS, lay["feat_offset"])), "f16")
     d = "dn.depth0"
-    for i in range(3):
-        t = P.add(DLayer("conv", f"dn.b{i}.conv1", d, f"dn.b{i}.t1", act="relu"))
-        d = P.add(DLayer("conv", f"dn.b{i}.conv2", t, f"dn.b{i}.out", res=d, act="relu"))
+    for i, blk in enumerate(dn.depth_conv[:3]):
+        d = basic_block_layers(P, blk, f"dn.b{i}", d)
     if dn.use_aspp:
         amid = dn.aspp.aspp1.out_channels
         if amid % 16:
             raise NotImplementedError("INT8 DepthNet: aspp_mid_channels must be a multiple of 16 (int8 channel slices)")
         P.buffers[ASPP_CAT] = 4 * amid
         for i, dil in enumerate(ASPP_DILATIONS):
-            P.add(DLayer("conv", f"dn.aspp{i + 1}", d, f"dn.aspp.b{i}", act="relu", dilation=dil, into=(ASPP_CAT, i * amid)))
-        P.tensors[ASPP_CAT], P.group[ASPP_CAT] = "q", ASPP_CAT
-        P.add(DLayer("avgpool", None, d, "dn.image_bias"), "f16")
-        d = P.add(DLayer("conv", "dn.aspp.conv1", ASPP_CAT, "dn.aspp.out", act="relu", image_bias="dn.image_bias"))
-    return P.add(DLayer("conv", "dn.last", d, "depth_net", into=(ROWS, lay["depth_offset"])), "f16")
+            P.add(Layer("conv", f"dn.aspp{i + 1}", d, f"dn.aspp.b{i}", act="relu", dilation=dil, into=(ASPP_CAT, i * amid)))
+        P.readable(ASPP_CAT)
+        P.add(Layer("avgpool", None, d, "dn.image_bias"), "f16")
+        d = P.add(Layer("conv", "dn.aspp.conv1", ASPP_CAT, "dn.aspp.out", act="relu", image_bias="dn.image_bias"))
+    return P.add(Layer("conv", "dn.last", d, "depth_net", into=(ROWS, lay["depth_offset"])), "f16")
 
 
 def build_plan(model):
     """bevdet_int8.build_plan(model) with the DepthNet's layers in place of the `depth_net` layer.  plan.tail: the index
     of the softmax + split, where bevdet_int8's own layers begin."""
     base = _bi.build_plan(model)
-    P = Plan()
+    P = Plan(base.prefix, base.int8_ops)
     P.buffers.update(base.buffers)
     x = P.add(base.layers[0])
     assert base.layers[0].op == "quantize" and base.layers[1].key == "depth_net" and base.layers[2].op == "split"
@@ -78,7 +74,7 @@ def build_plan(model):
     P.tail = len(P.layers)
     for l in base.layers[2:]:
         P.add(l, base.tensors[l.dst])
-    P.tensors[CAT], P.group[CAT] = "q", CAT
+    P.readable(CAT)
     return P
 
 
@@ -140,10 +136,7 @@ def quantize_operands(model, plan):
 
 def _float_operands(model, plan):
     src, lay, slices = _sources(model, plan)
-    table = {k: (w.detach().float().permute(0, 2, 3, 1), torch.ones(w.shape[0], device=w.device),
-                 torch.zeros(w.shape[0], device=w.device) if b is None else b.detach().float()) for k, (w, b) in src.items()}
-    table["layout"], table["slices"], table["fast"] = lay, slices, model.view.depth_net.fast_operands()
-    return table
+    return dict(float_operands(src), layout=lay, slices=slices, fast=model.view.depth_net.fast_operands())
 
 
 # ---- the fp32 statement
@@ -173,41 +166,20 @@ def emulate(model, plan, x, ranks, table, scales, tensors=None, mlp_input=None):
         raise ValueError("the BEVDepth statement needs mlp_input")
     dn, fast = model.view.depth_net, table["fast"]
     h16 = (lambda v: v.half().float()) if scales is not None else (lambda v: v)
-
-    def fq(v, name):
-        return v if scales is None or plan.tensors[name] != "q" else _fq(v, scales[plan.site(name)])
-
-    live["x.f16"] = x.float()
+    fq = lambda v, name: stored(plan, name, v, scales, round_f16=True)
     gates = gates_statement(dn, mlp_input.to(x.device))
-    for l in plan.layers[:plan.tail]:
-        src = live[l.src]
-        if l.op == "quantize":
-            v = fq(src, l.dst)
-        elif l.op == "gate":
-            v = fq(src * gates[0][:, :, None, None], l.dst)
+
+    def other(l, src, live):
+        if l.op == "gate":
             live[l.extra[0]] = fq(src * gates[1][:, :, None, None], l.extra[0])
-        elif l.op == "avgpool":
-            pooled = h16(src.mean(dim=(2, 3)))
-            a = dn.aspp
-            g = h16(F.relu(F.linear(pooled, fast["pool_w"].float(), a.global_avg_pool.bias.detach().float())))
-            v = h16(F.linear(g, fast["conv1_pool"].float(), a.conv1.bias.detach().float()))
-        else:
-            w, ws, b = table[l.key]
-            wf = (w.float() * ws[:, None, None, None]).permute(0, 3, 1, 2)
-            k = w.shape[1]
-            v = F.conv2d(src, wf, b if l.image_bias is None else None, 1, (k // 2) * l.dilation, l.dilation)
-            if l.image_bias is not None:
-                v = v + live[l.image_bias][:, :, None, None]
-            if l.res is not None:
-                v = v + live[l.res]
-            v = F.relu(v) if l.act == "relu" else v
-            v = h16(v) if plan.tensors[l.dst] == "f16" else fq(v, l.dst)
-        if l.into is not None:
-            buf, c0 = l.into
-            if buf not in live:
-                live[buf] = v.new_zeros((v.shape[0], plan.buffers[buf]) + tuple(v.shape[2:]))
-            live[buf][:, c0:c0 + v.shape[1]] = v
-        live[l.dst] = v
+            return fq(src * gates[0][:, :, None, None], l.dst)
+        assert l.op == "avgpool"
+        pooled = h16(src.mean(dim=(2, 3)))
+        a = dn.aspp
+        g = h16(F.relu(F.linear(pooled, fast["pool_w"].float(), a.global_avg_pool.bias.detach().float())))
+        return h16(F.linear(g, fast["conv1_pool"].float(), a.conv1.bias.detach().float()))
+
+    _bi.emulate(model, plan, x, ranks, table, scales, live, layers=plan.layers[:plan.tail], other=other)
     live["depth_net"] = live[ROWS]
     return _bi.emulate(model, plan, x, ranks, table, scales, live, layers=plan.layers[plan.tail:])
 
@@ -220,48 +192,30 @@ class Int8BEVDepth(_bi.Int8BEVDet):
     and replays it unchanged."""
 
     _plan_of = staticmethod(build_plan)
-    _quantize = staticmethod(quantize_operands)
+    _quantize_of = staticmethod(quantize_operands)
     _floats = staticmethod(_float_operands)
 
-    def _bev_parameters(self):
-        return super()._bev_parameters() + list(self.fp.view.depth_net.buffers())
+    def _stamped(self):
+        return super()._stamped() + list(self.fp.view.depth_net.buffers())
 
     def run(self, x, pool, table, ops, tensors=None, layers=None, mlp_input=None):
         live = {} if tensors is None else tensors
         if mlp_input is None:
             raise ValueError("Int8BEVDepth: the DepthNet needs mlp_input")
-        i8, f16 = torch.int8, torch.float16
         plan, dn, fast = self.plan, self.fp.view.depth_net, table["fast"]
-        n, _, H, W = x.shape
-        live["x.f16"] = x
         gates = ops.lss_camera_gate(mlp_input.to(x.device, torch.float32), fast["gate"], dn.mid_channels)
-        for l in plan.layers[:plan.tail]:
-            src = live[l.src]
-            q_out = plan.tensors[l.dst] == "q"
-            s_out = self.scale(l.dst) if q_out else None
-            out = None
-            if l.into is not None:
-                buf, c0 = l.into
-                if buf not in live:
-                    live[buf] = _Y.nhwc_empty(n, plan.buffers[buf], H, W, x.device, i8 if q_out else f16)
-                out = live[buf][:, c0:c0 + table[l.key][0].shape[0]]
-            if l.op == "quantize":
-                y = ops.quantize_rows(src.permute(0, 2, 3, 1), s_out).permute(0, 3, 1, 2)
-            elif l.op == "gate":
+
+        def other(l, src, live, s_out):
+            if l.op == "gate":
                 y, live[l.extra[0]] = ops.se_gate2_nhwc_q(src, self.scale(l.src), gates, s_out, self.scale(l.extra[0]))
-            elif l.op == "avgpool":
-                a = dn.aspp
-                pooled = ops.global_avgpool_nhwc_q(src, self.scale(l.src))
-                g = ops.dense_auto(pooled, fast["pool_w"], a.global_avg_pool.bias, None, True)
-                y = ops.dense_auto(g, fast["conv1_pool"], a.conv1.bias, None, False)
-            else:
-                w, ws, b = table[l.key]
-                res = None if l.res is None else live[l.res]
-                ib = None if l.image_bias is None else live[l.image_bias]
-                y = ops.conv_slice_q_taps(src, self.scale(l.src), w, ws, b if ib is None else None, l.act, res,
-                                          1.0 if res is None else self.scale(l.res), 1, out, s_out, i8 if q_out else f16,
-                                          res_first=res is not None, dilation=l.dilation, image_bias=ib)
-            live[l.dst] = y
+                return y
+            assert l.op == "avgpool"
+            a = dn.aspp
+            pooled = ops.global_avgpool_nhwc_q(src, self.scale(l.src))
+            g = ops.dense_auto(pooled, fast["pool_w"], a.global_avg_pool.bias, None, True)
+            return ops.dense_auto(g, fast["conv1_pool"], a.conv1.bias, None, False)
+
+        super().run(x, pool, table, ops, live, layers=plan.layers[:plan.tail], other=other)
         live["depth_net"] = live[ROWS]
         return super().run(x, pool, table, ops, live, layers=plan.layers[plan.tail:] if layers is None else layers)
 

@@ -22,59 +22,26 @@ two writers, stage 1's last block and the x 4 up-sampler: both requantise with t
 stays fp16: depth_net's logits (the softmax input; 59 bins of exponentials do not survive 8 bits) and the packed head
 output (what centerpoint_decode / get_candidates / get_bboxes read; post-processing is untouched)."""
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from . import bevdet as _bd
 from . import functions as _hip_ops
 from .functions import dispatch as _dispatch
 from .functions import yolox_ops as _Y
-from .functions.multi_scale_deformable_attn import _TensorCache
-from .yolox_int8 import _fq, load_calibration, save_calibration   # noqa: F401  (the calibration-cache format)
+from .int8_plan import (Int8Model, Layer, Plan, basic_block_conv, basic_block_layers, conv_call, conv_statement,   # noqa: F401
+                        float_operands, load_calibration, out_slice, place, save_calibration, scales_from, stored)
 
 SITE_PREFIX = "bevdet."
 CAT = "cat"
 
 
-class Layer:
-    """op in "quantize", "conv", "split", "pool", "upsample"; src / dst / res: tensor names; into = (buffer, first
-    channel): dst is that channel slice of `buffer`; extra: further int8 tensors the layer writes."""
-
-    def __init__(self, op, key, src, dst, res=None, act="none", stride=1, into=None, extra=(), factor=1):
-        self.op, self.key, self.src, self.dst, self.res, self.act, self.stride = op, key, src, dst, res, act, stride
-        self.into, self.extra, self.factor = into, extra, factor
-
-
-class Plan:
-    def __init__(self):
-        self.layers, self.tensors, self.group, self.buffers = [], {}, {}, {}   # tensors: name -> "q" | "f16", in write order
-
-    def add(self, layer, kind="q"):
-        self.layers.append(layer)
-        for name in layer.extra + (layer.dst,):
-            self.tensors[name] = kind if name == layer.dst else "q"
-            self.group[name] = layer.into[0] if (layer.into is not None and name == layer.dst) else name
-        return layer.dst
-
-    @property
-    def int8_layers(self):
-        return sum(1 for l in self.layers if l.op in ("conv", "pool"))
-
-    def site(self, tensor):
-        return SITE_PREFIX + self.group[tensor]
-
-    @property
-    def sites(self):
-        out = []
-        for n, kind in self.tensors.items():
-            if kind == "q" and self.site(n) not in out:
-                out.append(self.site(n))
-        return out
+# Layer ops: "quantize", "conv", "split", "pool", "upsample" (bevdepth_int8.py adds "gate" and "avgpool").
+INT8_OPS = ("conv", "pool")
 
 
 def build_plan(model):
     """The layers of `model`'s (a bevdet.BEVDet) BEV half in the order of its fast path."""
-    P = Plan()
+    P = Plan(SITE_PREFIX, INT8_OPS)
     x = P.add(Layer("quantize", None, "x.f16", "x"))
     dn = P.add(Layer("conv", "depth_net", x, "depth_net"), "f16")
     P.add(Layer("split", None, dn, "feat", extra=("depth",)))
@@ -85,14 +52,7 @@ def build_plan(model):
     feats = []
     for i, stage in enumerate(model.bev_stages):
         for j, blk in enumerate(stage):
-            name = f"s{i}.b{j}"
-            s = blk.conv1.stride[0]
-            idt = x
-            if blk.downsample is not None:
-                idt = P.add(Layer("conv", name + ".down", x, name + ".idt", stride=s))
-            t = P.add(Layer("conv", name + ".conv1", x, name + ".t1", act="relu", stride=s))
-            into = (CAT, 0) if i == 0 and j == len(stage) - 1 else None
-            x = P.add(Layer("conv", name + ".conv2", t, name + ".out", res=idt, act="relu", into=into))
+            x = basic_block_layers(P, blk, f"s{i}.b{j}", x, into=(CAT, 0) if i == 0 and j == len(stage) - 1 else None)
         feats.append(x)
     P.add(Layer("upsample", None, feats[-1], "up4", into=(CAT, widths[0]), factor=4))
     x = P.add(Layer("conv", "neck_conv.0", CAT, "neck0", act="relu"))
@@ -103,15 +63,13 @@ def build_plan(model):
     x = P.add(Layer("conv", "shared_conv", x, "shared", act="relu"))
     h = P.add(Layer("conv", "head.first", x, "head.hidden", act="relu"))
     P.add(Layer("conv", "head.final", h, "head.packed"), "f16")
-    # the buffer as a readable tensor: its group is itself
-    P.tensors[CAT], P.group[CAT] = "q", CAT
+    P.readable(CAT)
     return P
 
 
 def _conv_of(model, key):
     if key[0] == "s" and key[1].isdigit():
-        blk = model.bev_stages[int(key[1])][int(key[4])]
-        return {"down": blk.downsample, "conv1": blk.conv1, "conv2": blk.conv2}[key[6:]]
+        return basic_block_conv(model.bev_stages[int(key[1])][int(key[4])], key[6:])
     if key == "shared_conv":
         return model.shared_conv
     name, i = key.split(".")
@@ -149,10 +107,7 @@ def quantize_operands(model, plan):
 def _float_operands(model, plan):
     """The un-quantised fp32 operands in the layouts of `quantize_operands` with unit scales."""
     src, lay, slices = _sources(model, plan)
-    table = {k: (w.detach().float().permute(0, 2, 3, 1), torch.ones(w.shape[0], device=w.device),
-                 torch.zeros(w.shape[0], device=w.device) if b is None else b.detach().float()) for k, (w, b) in src.items()}
-    table["layout"], table["slices"] = lay, slices
-    return table
+    return dict(float_operands(src), layout=lay, slices=slices)
 
 
 def pool_statement(depth_q, feat_q, ranks, sio, cells):
@@ -171,39 +126,29 @@ def pool_statement(depth_q, feat_q, ranks, sio, cells):
     return torch.trunc(a + torch.where(a > 0, 0.5, -0.5))
 
 
-def emulate(model, plan, x, ranks, table, scales, tensors=None, layers=None):
+def emulate(model, plan, x, ranks, table, scales, tensors=None, layers=None, other=None):
     """The fp32 torch statement of the int8 BEV half from the fp16 image features x [cams, Cin, H, W]: NCHW fp32 tensors
-    holding q * scale, fake quantisation (`_fq`: the kernels' clamp(rne(v * (1 / scale)), -127, 127) * scale) at every
-    int8 tensor of the plan, depth_net's logits rounded to binary16, the pooling's integer sums and its own rounding.
+    holding q * scale, fake quantisation (`fake_quant`: the kernels' clamp(rne(v * (1 / scale)), -127, 127) * scale) at
+    every int8 tensor of the plan, depth_net's logits rounded to binary16, the pooling's integer sums and its own rounding.
     scales None: nothing is quantised or rounded (then `table` = the fp32 operands) -- the fp32 plain path.
     ranks = (ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths) trimmed.  -> the packed [1, 32, h, w].
     layers: the part of plan.layers to run on the tensors already in `tensors` (bevdepth_int8.py: everything from the split
-    on, behind its own DepthNet statement); None: all of them."""
+    on, behind its own DepthNet statement); None: all of them.  other(layer, src, live) -> the value of a layer whose op this
+    plan does not have (bevdepth_int8.py: "gate", "avgpool")."""
     live = {} if tensors is None else tensors
     view = model.view
     D, C = view.D, view.out_channels
     bev_h, bev_w = int(view.grid_size[1]), int(view.grid_size[0])
     lay = table["layout"]
     sc = (lambda name: scales[plan.site(name)]) if scales is not None else None
-
-    def fq(v, name):
-        return v if scales is None or plan.tensors[name] != "q" else _fq(v, sc(name))
-
+    fq = lambda v, name: stored(plan, name, v, scales, round_f16=True)
     live["x.f16"] = x.float()
     for l in (plan.layers if layers is None else layers):
         src = live[l.src]
         if l.op == "quantize":
             v = fq(src, l.dst)
         elif l.op == "conv":
-            w, ws, b = table[l.key]
-            wf = (w.float() * ws[:, None, None, None]).permute(0, 3, 1, 2)
-            v = F.conv2d(src, wf, b, l.stride, w.shape[1] // 2)
-            if l.res is not None:
-                v = v + live[l.res]                  # the identity in front of the activation
-            v = F.relu(v) if l.act == "relu" else v
-            if plan.tensors[l.dst] == "f16" and scales is not None:
-                v = v.half().float()
-            v = fq(v, l.dst)
+            v = fq(conv_statement(l, src, table[l.key], live.get(l.res), live.get(l.image_bias)), l.dst)
         elif l.op == "split":
             do, fo = lay["depth_offset"], lay["feat_offset"]
             live["depth"] = fq(src[:, do:do + D].softmax(dim=1), "depth")
@@ -222,18 +167,15 @@ def emulate(model, plan, x, ranks, table, scales, tensors=None, layers=None):
                 q = pool_statement(torch.round(depth / sd), torch.round(feat / sf), ranks[:3], sio, bev_h * bev_w)
                 v = q * so
             v = v.view(1, bev_h, bev_w, C).permute(0, 3, 1, 2)
-        else:   # "upsample"
+        elif l.op == "upsample":
             v = fq(F.interpolate(src, scale_factor=l.factor, mode="bilinear", align_corners=True), l.dst)
-        if l.into is not None:
-            buf, c0 = l.into
-            if buf not in live:
-                live[buf] = v.new_zeros((v.shape[0], plan.buffers[buf]) + tuple(v.shape[2:]))
-            live[buf][:, c0:c0 + v.shape[1]] = v
-        live[l.dst] = v
-    return live["head.packed"]
+        else:
+            v = other(l, src, live)
+        live[l.dst] = place(plan, l, live, v)
+    return live.get("head.packed")                  # (None when `layers` ends in front of the heads)
 
 
-class Int8BEVDet(nn.Module):
+class Int8BEVDet(Int8Model):
     """The INT8 BEVDet: the image half is `fp`'s int8 activation chain (quantization.Int8ChainBackbone, frozen), the BEV
     half the int8 plan above.  fp: the bevdet.BEVDet whose weights it quantises (kept: its parameters are this module's,
     and a weight reload rebuilds the int8 operands); scales: {site: scale} for every site of the plan.  `forward`,
@@ -241,22 +183,14 @@ class Int8BEVDet(nn.Module):
     BEVDetRunner captures and replays it unchanged."""
 
     def __init__(self, fp, scales, ops=None):
-        super().__init__()
-        self.fp = fp
-        self.cfg = fp.cfg
+        super().__init__(fp)
         self.bev_ops = ops if ops is not None else _hip_ops
         self.plan = self._plan_of(fp)
-        missing = [s for s in self.plan.sites if s not in scales]
-        if missing:
-            raise ValueError(f"Int8BEVDet: no scale for the sites {missing}")
-        self.scales = {s: float(scales[s]) for s in self.plan.sites}
-        if not all(0.0 < v < float("inf") for v in self.scales.values()):
-            raise ValueError("Int8BEVDet: every scale is positive and finite")
-        self.eval()
+        self._set_scales(scales, self.plan.sites)
 
     # ---- the plan and its statements (bevdepth_int8.Int8BEVDepth puts its own in their place)
     _plan_of = staticmethod(build_plan)
-    _quantize = staticmethod(quantize_operands)
+    _quantize_of = staticmethod(quantize_operands)
     _floats = staticmethod(_float_operands)
 
     # ---- what BEVDetRunner and the post-processing read
@@ -280,83 +214,47 @@ class Int8BEVDet(nn.Module):
     def get_bboxes(self, outputs, padded=False):
         return _bd.BEVDet.get_bboxes(self, outputs, padded)
 
-    @property
-    def num_int8_layers(self):
-        return self.plan.int8_layers
+    # ---- the cached operands (Int8Model.operands: stamped with every BEV-half parameter)
+    PREPARE, OPERAND = "prepare_bev_half", "merged or quantised"
 
-    def scale(self, tensor):
-        return self.scales[self.plan.site(tensor)]
-
-    # ---- the cached operands
-    def _bev_parameters(self):
+    def _stamped(self):
         fp = self.fp
         mods = [fp.view.depth_net, fp.bev_stages, fp.neck_conv, fp.up2_conv, fp.shared_conv, fp.heads]
         return [p for m in mods for p in m.parameters()]
 
-    def operands(self, build=True):
-        """The merged and quantised operands on the device of the weights; cached, stamped with every BEV-half
-        parameter's version and rebuilt when one changes.  build=False: None when missing or stale."""
-        stamp = tuple(_TensorCache._stamp(p) for p in self._bev_parameters())
-        hit = self.__dict__.get("_operands")
-        if hit is not None and hit[0] == stamp:
-            return hit[1]
-        if not build:
-            return None
-        table = self._quantize(self.fp, self.plan)
-        self.__dict__["_operands"] = (stamp, table)
-        return table
+    def _quantize(self):
+        return self._quantize_of(self.fp, self.plan)
 
     def prepare_bev_half(self):
         """Build (or refresh) the merged int8 operands; allocates, so it must run OUTSIDE stream capture."""
-        p = next(self.fp.parameters())
-        if p.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("Int8BEVDet.prepare_bev_half() allocates: call it before the capture begins")
+        p = self._outside_capture()
         if p.is_cuda and p.dtype == torch.float16:
             self.fp._nhwc_weights()   # (what the first fp16 frame does to the filters; the operands' stamps follow them)
         self.operands()
         return self
 
-    def _ready(self, like):
-        if not (like.is_cuda and like.dtype == torch.float16):
-            raise ValueError("Int8BEVDet: fp16 CUDA tensors (the int8 path has no plain fallback)")
-        if self.operands(build=False) is None:   # (first: under capture a missing operand raises before any launch)
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("Int8BEVDet: a merged or quantised operand is missing or stale and the stream is "
-                                   "capturing; call prepare_bev_half() (or the model once, eagerly) before the capture")
-            self.prepare_bev_half()
-        return self.operands(build=False)
-
     # ---- the int8 run
-    def run(self, x, pool, table, ops, tensors=None, layers=None):
+    def run(self, x, pool, table, ops, tensors=None, layers=None, other=None):
         """The layers of the plan on `ops` from the fp16 image features x [cams, Cin, H, W] (channels-last); pool(depth_q,
         feat_q, scales) runs the pooling.  -> the packed head output [1, 32, h, w] fp16 channels-last.  layers: the part
-        of the plan to run on the tensors already in `tensors` (None: all of it)."""
+        of the plan to run on the tensors already in `tensors` (None: all of it); other(layer, src, live, scale_out) runs a
+        layer whose op this plan does not have (bevdepth_int8.py: "gate", "avgpool")."""
         live = {} if tensors is None else tensors
-        i8, f16 = torch.int8, torch.float16
         view = self.fp.view
         lay = table["layout"]
+        scale_of = lambda name: None if name is None else self.scale(name)
         live["x.f16"] = x
         for l in (self.plan.layers if layers is None else layers):
             src = live[l.src]
             q_out = self.plan.tensors[l.dst] == "q"
             s_out = self.scale(l.dst) if q_out else None
-            out = None
-            if l.into is not None:
-                buf, c0 = l.into
-                if buf not in live:
-                    n, _, h, w = src.shape
-                    f = l.factor if l.op == "upsample" else 1
-                    live[buf] = _Y.nhwc_empty(n, self.plan.buffers[buf], (h - 1) // l.stride * f + f, (w - 1) // l.stride * f + f,
-                                              src.device, i8)
-                width = table[l.key][0].shape[0] if l.op == "conv" else src.shape[1]
-                out = live[buf][:, c0:c0 + width]
+            out = out_slice(self.plan, l, live, src, table[l.key][0].shape[0] if l.op == "conv" else src.shape[1],
+                            torch.int8 if q_out else torch.float16)
             if l.op == "quantize":
                 y = ops.quantize_rows(src.permute(0, 2, 3, 1), s_out).permute(0, 3, 1, 2)
             elif l.op == "conv":
-                w, ws, b = table[l.key]
-                res = None if l.res is None else live[l.res]
-                y = ops.conv_slice_q_taps(src, self.scale(l.src), w, ws, b, l.act, res, 1.0 if res is None else self.scale(l.res),
-                                          l.stride, out, s_out, i8 if q_out else f16, res_first=res is not None)
+                y = conv_call(ops, l, src, self.scale(l.src), table[l.key], live.get(l.res), scale_of(l.res), out, s_out,
+                              live.get(l.image_bias))
             elif l.op == "split":
                 n, c, h, w = src.shape
                 rows = src.permute(0, 2, 3, 1).reshape(n * h * w, c)          # (a view: channels-last)
@@ -364,8 +262,10 @@ class Int8BEVDet(nn.Module):
                                                          lay["feat_offset"], self.scale("depth"), s_out, spatial=(h, w))
             elif l.op == "pool":
                 y = pool(src, live[l.res], (self.scale(l.src), self.scale(l.res), s_out)).permute(0, 3, 1, 2)
-            else:   # "upsample"
+            elif l.op == "upsample":
                 y = ops.upsample_bilinear_nhwc_q(src, self.scale(l.src), s_out, scale_factor=l.factor, out=out)
+            else:
+                y = other(l, src, live, s_out)
             live[l.dst] = y
         return live.get("head.packed")              # (None when `layers` ends in front of the heads)
 
@@ -489,11 +389,3 @@ def calibrate_behind_split(fp, depth, feat, ranks, cal, ops):
         site("shared", x)
         w1, b1, _, _, _ = fp.heads_merged()
         site("head.hidden", ops.conv_nhwc(x, w1, b1, True))
-
-
-def scales_from(cal, sites):
-    missing = [s for s in sites if not cal.has(s)]
-    if missing:
-        raise ValueError(f"build_int8_bevdet: no calibration data for the sites {missing}")
-    # (the scales as fp32 numbers: what the kernels receive)
-    return {s: float(torch.tensor(cal.scale(s), dtype=torch.float32)) for s in sites}

@@ -3,8 +3,8 @@ samples/centernet/onnx2trt_int8.sh (implicit quantisation: every layer it can, t
 neck="int8") and from configs/centernet/centernet_resnet18_dcnv2_140e_coco_trt_q.py (`ResNetQ` / `Conv2dQ` backbone,
 `CenterNetHeadQ`, the neck left in float: its quantised neck line is commented out; neck="fp16").  design/centernet_int8.md.
 
-THE PLAN (`build_plan`) is a list of layers on NAMED tensors, so that one description serves the layer and site counts
-(no tensor needed), the int8 run and the fp32 fake-quant statement of the tests:
+THE PLAN (`build_plan`) is a list of layers on NAMED tensors (int8_plan.py: Layer, Plan), so that one description serves
+the layer and site counts (no tensor needed), the int8 run and the fp32 fake-quant statement of the tests:
 
   stem       7x7 / 2 + ReLU + 3x3 / 2 max-pool, fp16 arithmetic, int8 out        stem_conv_pool (csrc/stem.hip)
   BasicBlock conv1 3x3 / s + ReLU; downsample 1x1 / s (a stage's first block); conv2 3x3 + identity + ReLU with the
@@ -20,7 +20,6 @@ requantises with that scale and every consumer reads with it (there are no conca
 mask of a DCN pack are two more int8 tensors: the kernel quantises them from the fp16 output of the offset convolution
 while it stages them."""
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from . import bevformer as _B
@@ -29,38 +28,17 @@ from . import functions as _hip_ops
 from .functions import dispatch as _dispatch
 from .functions import yolox_ops as _Y
 from .functions.deconv import deconv_packed_weight, quantize_deconv_weight
-from .functions.multi_scale_deformable_attn import _TensorCache
-from .yolox_int8 import _fq, load_calibration, save_calibration   # noqa: F401  (the calibration-cache format)
+from .int8_plan import (Int8Model, Layer, Plan, basic_block_conv, basic_block_layers, conv_call, conv_statement,   # noqa: F401
+                        float_operands, load_calibration, save_calibration, scales_from, stored)
 
 SITE_PREFIX = "centernet."
 NECK_MODES = ("int8", "fp16")
 DCN_INT8_CIN_MULTIPLE = 128     # bevops_mdconv_forward_int8_nhwc: 128-channel k-steps (csrc/mdconv_s8.hip, plan_s8)
 
 
-class Layer:
-    """op in "stem", "conv", "offset", "dcn", "deconv", "neck_fp16", "quantize"; src / dst / res: tensor names."""
-
-    def __init__(self, op, key, src, dst, res=None, act="none", stride=1, extra=()):
-        self.op, self.key, self.src, self.dst, self.res, self.act, self.stride, self.extra = op, key, src, dst, res, act, stride, extra
-
-
-class Plan:
-    def __init__(self):
-        self.layers, self.tensors, self.neck = [], {}, None      # tensors: name -> "q" | "f16", in the order of their writes
-
-    def add(self, layer, kind="q"):
-        self.layers.append(layer)
-        for name in layer.extra + (layer.dst,):
-            self.tensors[name] = kind if name == layer.dst else "q"
-        return layer.dst
-
-    @property
-    def int8_layers(self):
-        return sum(1 for l in self.layers if l.op in ("conv", "offset", "dcn", "deconv"))
-
-    @property
-    def sites(self):
-        return [SITE_PREFIX + n for n, kind in self.tensors.items() if kind == "q"]
+# Layer ops: "stem", "conv", "offset", "dcn", "deconv", "neck_fp16", "quantize".  No layer writes `into` a buffer, so every
+# tensor is its own scale group and plan.sites is one site per int8 tensor.
+INT8_OPS = ("conv", "offset", "dcn", "deconv")
 
 
 def dcn_int8_domain(model):
@@ -75,7 +53,7 @@ def build_plan(model, neck="int8"):
     """The layers of `model` (a centernet.CenterNet) in the order of its fast path.  neck: "int8" | "fp16"."""
     if neck not in NECK_MODES:
         raise ValueError(f"neck in {NECK_MODES}")
-    P = Plan()
+    P = Plan(SITE_PREFIX, INT8_OPS)
     P.neck = neck
     x = P.add(Layer("stem", "stem", None, "stem"))
     stages = model.backbone.stages
@@ -83,13 +61,7 @@ def build_plan(model, neck="int8"):
         for j, blk in enumerate(stage):
             name = f"s{i}.b{j}"
             last = i == len(stages) - 1 and j == len(stage) - 1
-            s = blk.conv1.stride[0]
-            idt = x
-            if blk.downsample is not None:
-                idt = P.add(Layer("conv", name + ".down", x, name + ".idt", stride=s))
-            t = P.add(Layer("conv", name + ".conv1", x, name + ".t1", act="relu", stride=s))
-            x = P.add(Layer("conv", name + ".conv2", t, name + ".out", res=idt, act="relu"),
-                      "f16" if last and neck == "fp16" else "q")
+            x = basic_block_layers(P, blk, name, x, "f16" if last and neck == "fp16" else "q")
     if neck == "int8":
         for l in range(len(model.neck.dcn)):
             name = f"neck{l}"
@@ -106,9 +78,23 @@ def build_plan(model, neck="int8"):
 
 
 def _conv_of(model, key):
-    i, j, which = int(key[1]), int(key[4]), key[6:]
-    blk = model.backbone.stages[i][j]
-    return {"down": blk.downsample, "conv1": blk.conv1, "conv2": blk.conv2}[which]
+    return basic_block_conv(model.backbone.stages[int(key[1])][int(key[4])], key[6:])
+
+
+def _sources(model, plan):
+    """{key: (weight [Cout, Cin, k, k], bias)} of every "conv" and "offset" layer of `plan`.  -> (table, head slices)."""
+    w1, b1, w2, b2, slices = model.heads_merged()
+    table = {}
+    for l in plan.layers:
+        if l.op == "offset":
+            co = model.neck.dcn[int(l.key[4])].conv_offset
+            table[l.key] = (co.weight, co.bias)
+        elif l.op == "conv" and l.key.startswith("head."):
+            table[l.key] = (w1, b1) if l.key == "head.first" else (w2, b2)
+        elif l.op == "conv":
+            c = _conv_of(model, l.key)
+            table[l.key] = (c.weight, c.bias)
+    return table, slices
 
 
 def quantize_operands(model, plan):
@@ -116,28 +102,21 @@ def quantize_operands(model, plan):
     w_scales fp32, bias fp32) per output channel (functions.yolox_ops.quantize_weight_taps); "offset": the same with the
     27 filters padded to 32 (Int8ChainBackbone's recipe); "dcn": (weight_q int8 [Cout, Cin, 3, 3], ONE scale, bias fp32);
     "deconv": (weight_q int8 [Cin, Cout, 4, 4], w_scales fp32 [Cout], bias fp32); "slices": the head's channel slices."""
-    table = {}
-    w1, b1, w2, b2, slices = model.heads_merged()
-    table["slices"] = slices
+    src, slices = _sources(model, plan)
+    table = {"slices": slices}
     for l in plan.layers:
-        if l.op == "conv" and l.key.startswith("head."):
-            w, b = (w1, b1) if l.key == "head.first" else (w2, b2)
-            table[l.key] = _Y.quantize_weight_taps(w, b, multiple=_cn.HEAD_PACK_MULTIPLE)
-        elif l.op == "conv":
-            c = _conv_of(model, l.key)
-            table[l.key] = _Y.quantize_weight_taps(c.weight, c.bias)
-        elif l.op in ("offset", "dcn"):
+        if l.op in ("conv", "offset"):
+            if l.op == "offset" and src[l.key][0].shape[0] != 27:
+                raise NotImplementedError("Int8CenterNet: DCNv2 packs other than 3x3 / deform_groups=1")
+            # (the head's operands in the pack of merge_centernet_heads; the 27 offset filters padded to 32)
+            kw = {"multiple": _cn.HEAD_PACK_MULTIPLE} if l.key.startswith("head.") else {"multiple": 32} if l.op == "offset" else {}
+            table[l.key] = _Y.quantize_weight_taps(*src[l.key], **kw)
+        elif l.op == "dcn":
             d = model.neck.dcn[int(l.key[4])]
-            if l.op == "offset":
-                co = d.conv_offset
-                if co.out_channels != 27:
-                    raise NotImplementedError("Int8CenterNet: DCNv2 packs other than 3x3 / deform_groups=1")
-                table[l.key] = _Y.quantize_weight_taps(co.weight, co.bias, multiple=32)
-            else:
-                w = d.weight.detach().float()
-                s = float(torch.tensor(max(float(w.abs().max()), 1e-12) / 127.0, dtype=torch.float32))
-                q = torch.clamp(torch.round(w / s), -127, 127).to(torch.int8).contiguous()
-                table[l.key] = (q, s, d.bias.detach().float().contiguous())
+            w = d.weight.detach().float()
+            s = float(torch.tensor(max(float(w.abs().max()), 1e-12) / 127.0, dtype=torch.float32))
+            q = torch.clamp(torch.round(w / s), -127, 127).to(torch.int8).contiguous()
+            table[l.key] = (q, s, d.bias.detach().float().contiguous())
         elif l.op == "deconv":
             up = model.neck.deconv[int(l.key[4])]
             table[l.key] = quantize_deconv_weight(up.weight, up.bias)
@@ -147,20 +126,12 @@ def quantize_operands(model, plan):
 def _float_operands(model, plan):
     """The un-quantised fp32 operands in the layouts of `quantize_operands` with unit scales (the statement with the
     quantisation disabled)."""
-    table = {}
-    w1, b1, w2, b2, slices = model.heads_merged()
-    table["slices"] = slices
-    taps = lambda w, b: (w.detach().float().permute(0, 2, 3, 1), torch.ones(w.shape[0], device=w.device), b.detach().float())
+    src, slices = _sources(model, plan)
+    table = dict(float_operands(src), slices=slices)
     for l in plan.layers:
-        if l.op == "conv" and l.key.startswith("head."):
-            table[l.key] = taps(*((w1, b1) if l.key == "head.first" else (w2, b2)))
-        elif l.op == "conv":
-            c = _conv_of(model, l.key)
-            table[l.key] = taps(c.weight, c.bias)
-        elif l.op in ("offset", "dcn"):
+        if l.op == "dcn":
             d = model.neck.dcn[int(l.key[4])]
-            table[l.key] = taps(d.conv_offset.weight, d.conv_offset.bias) if l.op == "offset" else \
-                (d.weight.detach().float(), 1.0, d.bias.detach().float())
+            table[l.key] = (d.weight.detach().float(), 1.0, d.bias.detach().float())
         elif l.op == "deconv":
             up = model.neck.deconv[int(l.key[4])]
             table[l.key] = (up.weight.detach().float(), torch.ones(up.weight.shape[1], device=up.weight.device),
@@ -179,29 +150,22 @@ def _neck_float(model, x, mdconv):
 
 
 def emulate(model, plan, image, table, scales, mdconv=None, tensors=None):
-    """The fp32 torch statement of the int8 run: NCHW fp32 tensors holding q * scale, fake quantisation (`_fq`: the
-    kernels' clamp(rne(v * (1 / scale)), -127, 127) * scale) at every int8 tensor of the plan.  scales None: nothing is
-    quantised (then `table` = the fp32 operands).  The DCN is the package's float `modulated_deformable_conv2d` on the
-    fake-quantised input, offsets, mask and weight.  tensors: a dict that receives every tensor by name.
-    -> (heat map after the sigmoid, wh, offset), fp32."""
+    """The fp32 torch statement of the int8 run: NCHW fp32 tensors holding q * scale, fake quantisation
+    (int8_plan.fake_quant: the kernels' clamp(rne(v * (1 / scale)), -127, 127) * scale) at every int8 tensor of the plan;
+    the fp16 tensors (the offset convolution's output, the packed head output) are stated WITHOUT their rounding to
+    binary16.  scales None: nothing is quantised (then `table` = the fp32 operands).  The DCN is the package's float
+    `modulated_deformable_conv2d` on the fake-quantised input, offsets, mask and weight.  tensors: a dict that receives
+    every tensor by name.  -> (heat map after the sigmoid, wh, offset), fp32."""
     mdconv = mdconv if mdconv is not None else _hip_ops.modulated_deformable_conv2d
     live = {} if tensors is None else tensors
     stem = model.backbone.stem
-
-    def fq(v, name):
-        return v if scales is None or plan.tensors[name] != "q" else _fq(v, scales[SITE_PREFIX + name])
-
+    fq = lambda v, name: stored(plan, name, v, scales, round_f16=False)
     for l in plan.layers:
         x = None if l.src is None else live[l.src]
         if l.op == "stem":
             v = F.max_pool2d(F.relu(F.conv2d(image.float(), stem.weight.float(), stem.bias.float(), 2, 3)), 3, 2, 1)
         elif l.op in ("conv", "offset"):
-            w, ws, b = table[l.key]
-            wf = (w.float() * ws[:, None, None, None]).permute(0, 3, 1, 2)
-            v = F.conv2d(x, wf, b, l.stride, w.shape[1] // 2)
-            if l.res is not None:
-                v = v + live[l.res]                  # the identity in front of the activation
-            v = F.relu(v) if l.act == "relu" else v
+            v = conv_statement(l, x, table[l.key], None if l.res is None else live[l.res])
         elif l.op == "dcn":
             w, sw, b = table[l.key]
             om = live[l.res]
@@ -221,7 +185,7 @@ def emulate(model, plan, image, table, scales, mdconv=None, tensors=None):
     return torch.sigmoid(heat), wh, off
 
 
-class Int8CenterNet(nn.Module):
+class Int8CenterNet(Int8Model):
     """`forward(image fp16 [B, 3, H, W])` -> CenterNet.forward's three outputs (fp16, the heat map after the sigmoid:
     three channel slices of the packed [B, H/4, W/4, 88] tensor) through the int8 plan.  fp: the fp16 centernet.CenterNet
     whose weights it quantises (kept: its parameters are this module's, and a weight reload rebuilds the int8
@@ -229,9 +193,7 @@ class Int8CenterNet(nn.Module):
     CenterNet: CenterNetRunner captures and replays it unchanged."""
 
     def __init__(self, fp, scales, ops=None, neck="int8"):
-        super().__init__()
-        self.fp = fp
-        self.cfg = fp.cfg
+        super().__init__(fp)
         self.ops = ops if ops is not None else _hip_ops
         self.neck_note = neck
         outside = dcn_int8_domain(fp) if neck == "int8" else []
@@ -240,35 +202,13 @@ class Int8CenterNet(nn.Module):
             self.neck_note = f"fp16 (DCN packs {outside} are outside the int8 block's domain: input channels % 128)"
         self.neck = neck
         self.plan = build_plan(fp, neck)
-        missing = [s for s in self.plan.sites if s not in scales]
-        if missing:
-            raise ValueError(f"Int8CenterNet: no scale for the sites {missing}")
-        self.scales = {s: float(scales[s]) for s in self.plan.sites}
-        if not all(0.0 < v < float("inf") for v in self.scales.values()):
-            raise ValueError("Int8CenterNet: every scale is positive and finite")
-        self.eval()
+        self._set_scales(scales, self.plan.sites)
 
-    @property
-    def num_int8_layers(self):
-        return self.plan.int8_layers
+    # ---- the cached operands (Int8Model.operands: stamped with every parameter of fp)
+    OPERAND = "quantised or packed"
 
-    def scale(self, tensor):
-        return self.scales[SITE_PREFIX + tensor]
-
-    # ---- the cached operands
-    def operands(self, build=True):
-        """The quantised operands on the device of the weights; cached, stamped with every parameter's version and
-        rebuilt when one changes.  build=False: None when missing or stale."""
-        stamp = tuple(_TensorCache._stamp(p) for p in self.fp.parameters())
-        hit = self.__dict__.get("_operands")
-        if hit is not None and hit[0] == stamp and self._packs_ready(hit[1]):
-            return hit[1]
-        if not build:
-            return None
-        table = quantize_operands(self.fp, self.plan)
-        self.__dict__["_operands"] = (stamp, table)
-        self._packs(table, build=True)
-        return table
+    def _quantize(self):
+        return quantize_operands(self.fp, self.plan)
 
     def _packs(self, table, build):
         """The parity-major packed int8 deconvolution weights and the int8 DCN weight images of `table` (and, for the
@@ -290,14 +230,9 @@ class Int8CenterNet(nn.Module):
                 ok &= self.fp._operands_ready()
         return ok
 
-    def _packs_ready(self, table):
-        return self._packs(table, build=False)
-
     def prepare(self):
         """Build (or refresh) the int8 operands and their packed images; allocates, so it must run OUTSIDE stream capture."""
-        p = next(self.fp.parameters())
-        if p.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("Int8CenterNet.prepare() allocates: call it before the capture begins")
+        self._outside_capture()
         self.operands()
         return self
 
@@ -307,6 +242,7 @@ class Int8CenterNet(nn.Module):
         live = {} if tensors is None else tensors
         i8, f16 = torch.int8, torch.float16
         stem = self.fp.backbone.stem
+        scale_of = lambda name: None if name is None else self.scale(name)
         for l in self.plan.layers:
             x = None if l.src is None else live[l.src]
             q_out = self.plan.tensors[l.dst] == "q"
@@ -314,10 +250,7 @@ class Int8CenterNet(nn.Module):
             if l.op == "stem":
                 y = ops.stem_conv_pool(image, stem.weight, stem.bias, s_out)
             elif l.op == "conv":
-                w, ws, b = table[l.key]
-                res = None if l.res is None else live[l.res]
-                y = ops.conv_slice_q_taps(x, self.scale(l.src), w, ws, b, l.act, res, 1.0 if res is None else self.scale(l.res),
-                                          l.stride, None, s_out, i8 if q_out else f16, res_first=res is not None)
+                y = conv_call(ops, l, x, self.scale(l.src), table[l.key], live.get(l.res), scale_of(l.res), None, s_out)
             elif l.op == "offset":
                 w, ws, b = table[l.key]
                 y = ops.conv_int8_chain_nhwc(x, self.scale(l.src), w, ws, b, False, 1, f16)
@@ -339,14 +272,7 @@ class Int8CenterNet(nn.Module):
     def forward(self, image):
         if image.dim() != 4 or image.shape[1] != 3 or image.shape[2] % 32 or image.shape[3] % 32:
             raise ValueError(f"CenterNet: image [B, 3, H, W] with H and W multiples of 32, got {tuple(image.shape)}")
-        if not (image.is_cuda and image.dtype == torch.float16):
-            raise ValueError("Int8CenterNet: an fp16 CUDA image (the int8 path has no plain fallback)")
-        if self.operands(build=False) is None:   # (first: under capture a missing operand raises before any launch)
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("Int8CenterNet: a quantised or packed operand is missing or stale and the stream is "
-                                   "capturing; call prepare() (or the model once, eagerly) before the capture")
-            self.prepare()
-        table = self.operands(build=False)
+        table = self._ready(image, "an fp16 CUDA image")
         with _dispatch.using(rule=True):
             packed = self.run(image.contiguous(), table, self.ops)
         heat, wh, off = (packed[:, a:b] for a, b in table["slices"])
@@ -411,11 +337,3 @@ def calibrate(fp, images, cal, ops=None):
             site("head.hidden", ops.conv_nhwc(x, w1, b1, True))
             n += 1
     return n
-
-
-def scales_from(cal, sites):
-    missing = [s for s in sites if not cal.has(s)]
-    if missing:
-        raise ValueError(f"build_int8_centernet: no calibration data for the sites {missing}")
-    # (the scales as fp32 numbers: what the kernels receive)
-    return {s: float(torch.tensor(cal.scale(s), dtype=torch.float32)) for s in sites}

@@ -1065,6 +1065,20 @@ def build_int8_engine(B, name, dev, frames, calibrator="entropy", chain=True, de
     return model, qops, note
 
 
+def _calibrated(cal, cache, dev, run, extra):
+    """The statistics of a PTQ build in `cal`: an existing calibration cache `cache` is loaded INSTEAD of running frames;
+    otherwise run() calibrates (-> the number of frames n) and, given a path, the statistics are saved there with
+    extra(n).  -> the number of frames run (0 when the cache was loaded)."""
+    from .int8_plan import load_calibration, save_calibration
+    if cache is not None and os.path.exists(cache):
+        load_calibration(cal, cache, dev if isinstance(cal, _DeviceCalibrator) else None)
+        return 0
+    n = run()
+    if cache is not None:
+        save_calibration(cal, cache, extra(n))
+    return n
+
+
 BEVDET_BEV_HALF_BUILDS = ("fp16", "int8")
 
 
@@ -1139,11 +1153,9 @@ def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache,
     else:
         _plan = _bi
     cal = qops.cal
-    n = 0
-    if calibration_cache is not None and os.path.exists(calibration_cache):
-        _bi.load_calibration(cal, calibration_cache, dev if isinstance(cal, _DeviceCalibrator) else None)
-    else:
-        inner, seen = model.image_features, {}
+
+    def run():
+        inner, seen, n = model.image_features, {}, 0
 
         def image_features(image):        # (keeps each frame's fp16 image features for the BEV half's calibration)
             seen["x"] = inner(image)
@@ -1158,16 +1170,15 @@ def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache,
                 n += 1
         finally:
             del model.image_features
-        if calibration_cache is not None:
-            _bi.save_calibration(cal, calibration_cache, {"model": "bevdepth" if depthnet else "bevdet", "bev_half": "int8",
-                                                         "frames": n})
+        return n
+
+    n = _calibrated(cal, calibration_cache, dev, run,
+                    lambda n: {"model": "bevdepth" if depthnet else "bevdet", "bev_half": "int8", "frames": n})
     scales = qops.freeze()
     ch.freeze()
     model.register_forward_pre_hook(lambda m, args: qops.begin_frame())
-    if depthnet:
-        q = _plan.Int8BEVDepth(model, _bi.scales_from(cal, _plan.build_plan(model).sites))
-    else:
-        q = _bi.Int8BEVDet(model, _bi.scales_from(cal, _bi.build_plan(model).sites))
+    q = (_plan.Int8BEVDepth if depthnet else _bi.Int8BEVDet)(
+        model, _bi.scales_from(cal, _plan.build_plan(model).sites, "build_int8_bevdet"))
     note = {"int8_plugin_sites": sum(1 for k in scales if k.startswith("bev_pool") and k.endswith(".out")),
             "int8_backbone_layers": len(ch.convs) + sum(len(b) for b in ch.plan), "activation_chain": True,
             "calibration_frames": n, "bev_half": "int8", "int8_bev_half_layers": q.num_int8_layers,
@@ -1194,13 +1205,8 @@ def build_int8_yolox(Y, dev, images, calibrator="entropy", calibration_cache=Non
     plan = _yi.build_plan(fp)
     _, num_groups = plan.groups()
     cal = get_calibrator(calibrator)()
-    n = 0
-    if calibration_cache is not None and os.path.exists(calibration_cache):
-        _yi.load_calibration(cal, calibration_cache, dev if isinstance(cal, _DeviceCalibrator) else None)
-    else:
-        n = _yi.calibrate(fp, images, cal, ops)
-        if calibration_cache is not None:
-            _yi.save_calibration(cal, calibration_cache, {"model": "yolox", "scale_groups": num_groups, "frames": n})
+    n = _calibrated(cal, calibration_cache, dev, lambda: _yi.calibrate(fp, images, cal, ops),
+                    lambda n: {"model": "yolox", "scale_groups": num_groups, "frames": n})
     model = _yi.Int8YOLOX(fp, _yi.group_scales_from(cal, num_groups), ops)
     note = {"int8_layers": model.num_int8_layers, "scale_groups": num_groups, "calibration_frames": n}
     return model, note
@@ -1223,14 +1229,9 @@ def build_int8_centernet(C, dev, images, calibrator="entropy", calibration_cache
     fp = C if isinstance(C, torch.nn.Module) else C.CenterNet(cfg)
     fp = fp.to(dev, torch.float16)
     cal = get_calibrator(calibrator)()
-    n = 0
-    if calibration_cache is not None and os.path.exists(calibration_cache):
-        _ci.load_calibration(cal, calibration_cache, dev if isinstance(cal, _DeviceCalibrator) else None)
-    else:
-        n = _ci.calibrate(fp, images, cal, ops)
-        if calibration_cache is not None:
-            _ci.save_calibration(cal, calibration_cache, {"model": "centernet", "sites": len(_ci.all_sites(fp)), "frames": n})
-    model = _ci.Int8CenterNet(fp, _ci.scales_from(cal, _ci.build_plan(fp, neck).sites), ops, neck)
+    n = _calibrated(cal, calibration_cache, dev, lambda: _ci.calibrate(fp, images, cal, ops),
+                    lambda n: {"model": "centernet", "sites": len(_ci.all_sites(fp)), "frames": n})
+    model = _ci.Int8CenterNet(fp, _ci.scales_from(cal, _ci.build_plan(fp, neck).sites, "build_int8_centernet"), ops, neck)
     note = {"int8_layers": model.num_int8_layers, "scale_sites": len(model.plan.sites), "calibration_frames": n,
             "neck": model.neck_note}
     return model, note

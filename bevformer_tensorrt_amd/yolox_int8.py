@@ -16,13 +16,12 @@ of its source joins the group of its destination (-> [up(high5) | c4] and [down1
 quarter of.  A group's calibration statistic is collected under ONE site name from every slice written into it, so it
 is the joint statistic of the union.  The three packed predictor outputs are fp16 and belong to no group."""
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from . import functions as _hip_ops
 from . import yolox as _yx
 from .functions import yolox_ops as _Y
-from .functions.multi_scale_deformable_attn import _TensorCache
+from .int8_plan import Int8Model, fake_quant, load_calibration, save_calibration, scales_from   # noqa: F401
 
 
 class Ref:
@@ -167,12 +166,6 @@ def quantize_operands(model):
     return table
 
 
-def _fq(t, scale):
-    """Quantise and dequantise: clamp(rne(t * (1 / scale)), -127, 127) * scale with the kernels' fp32 reciprocal."""
-    inv = (torch.ones((), dtype=torch.float32) / torch.tensor(scale, dtype=torch.float32)).item()
-    return torch.clamp(torch.round(t * inv), -127, 127) * scale
-
-
 def run_plan(plan, image, mode, ops, table, scales=None, collect=None):
     """One forward of `plan`.  mode "fp16": the fp16 fast path's calls (`table` = YOLOX.operands()); "int8": the int8
     operators (`table` = quantize_operands(), scales[g] per group); "emulate": the fp32 fake-quant statement of the int8
@@ -204,7 +197,7 @@ def run_plan(plan, image, mode, ops, table, scales=None, collect=None):
         return None if g is None else scales[g]
 
     def fq(v, r):                              # "emulate" without scales: the plan in fp32, nothing quantised
-        return v if scales is None else _fq(v, scale_of(r))
+        return v if scales is None else fake_quant(v, scale_of(r))
 
     for i, s in enumerate(plan.steps):
         dst = view(s.dst)
@@ -269,48 +262,33 @@ def split_outputs(packed, slices):
     return tuple(cls + reg + obj)
 
 
-class Int8YOLOX(nn.Module):
+class Int8YOLOX(Int8Model):
     """`forward(image fp16 [B, 3, H, W])` -> YOLOX.forward's nine outputs (fp16 logits) through the int8 plan.
     fp: the fp16 yolox.YOLOX whose weights it quantises (kept: its parameters are this module's, and a weight reload
     rebuilds the int8 operands); group_scales: one scale per scale group.  `forward`, `get_bboxes` and `prepare` as
     YOLOX: YOLOXRunner captures and replays it unchanged."""
 
     def __init__(self, fp, group_scales, ops=None):
-        super().__init__()
-        self.fp = fp
-        self.cfg = fp.cfg
+        super().__init__(fp)
         self.ops = ops if ops is not None else _hip_ops
         self.plan = build_plan(fp)
         self.group_of, self.num_groups = self.plan.groups()
         if len(group_scales) != self.num_groups:
             raise ValueError(f"Int8YOLOX: {self.num_groups} scale groups, {len(group_scales)} scales")
-        self.group_scales = [float(s) for s in group_scales]
-        if not all(0.0 < s < float("inf") for s in self.group_scales):
-            raise ValueError("Int8YOLOX: every group scale is positive and finite")
-        self.eval()
+        sites = [group_site(g) for g in range(self.num_groups)]
+        self._set_scales(dict(zip(sites, group_scales)), sites, what="group scale")
+        self.group_scales = [self.scales[s] for s in sites]
 
     @property
     def num_int8_layers(self):
         return sum(1 for s in self.plan.steps if s.op == "conv")
 
-    def operands(self, build=True):
-        """The quantised operands on the device of the weights; cached, stamped with every parameter's version and
-        rebuilt when one changes.  build=False: None when missing or stale."""
-        stamp = tuple(_TensorCache._stamp(p) for p in self.fp.parameters())
-        hit = self.__dict__.get("_operands")
-        if hit is not None and hit[0] == stamp:
-            return hit[1]
-        if not build:
-            return None
-        table = quantize_operands(self.fp)
-        self.__dict__["_operands"] = (stamp, table)
-        return table
+    def _quantize(self):
+        return quantize_operands(self.fp)
 
     def prepare(self):
         """Build (or refresh) the int8 operands; allocates, so it must run OUTSIDE stream capture."""
-        p = next(self.fp.parameters())
-        if p.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("Int8YOLOX.prepare() allocates: call it before the capture begins")
+        self._outside_capture()
         self.operands()
         return self
 
@@ -318,14 +296,7 @@ class Int8YOLOX(nn.Module):
     def forward(self, image):
         if image.dim() != 4 or image.shape[1] != 3 or image.shape[2] % 32 or image.shape[3] % 32:
             raise ValueError(f"YOLOX: image [B, 3, H, W] with H and W multiples of 32, got {tuple(image.shape)}")
-        if not (image.is_cuda and image.dtype == torch.float16):
-            raise ValueError("Int8YOLOX: an fp16 CUDA image (the int8 path has no plain fallback)")
-        if self.operands(build=False) is None:   # (first: under capture a missing operand raises before any launch)
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("Int8YOLOX: a quantised operand is missing or stale and the stream is capturing; "
-                                   "call prepare() (or the model once, eagerly) before the capture")
-            self.prepare()
-        table = self.operands(build=False)
+        table = self._ready(image, "an fp16 CUDA image")
         packed = run_plan(self.plan, image.contiguous(), "int8", self.ops, table, self.group_scales)
         return split_outputs(packed, table["slices"])
 
@@ -343,53 +314,6 @@ class Int8YOLOX(nn.Module):
 
 # ---- calibration
 
-def _save_host_calibration(cal, path, extra):
-    """A host calibrator's statistics in the calibration-cache format of the device calibrators
-    (quantization.write_calibration_cache): histogram calibrators fill `range` and `hist`, min-max fills `amax`."""
-    import numpy as np
-    from . import quantization as _q
-    names = list(cal._stats)
-    n = len(names)
-    fields = {k: np.zeros(n, dtype=np.float32) for k in ("range", "amax")}
-    fields.update({k: np.zeros(n, dtype=np.uint64) for k in ("count", "nonfinite")})
-    fields["batches"] = np.zeros(n, dtype=np.uint32)
-    fields["hist"] = np.zeros((n, _q._NUM_BINS), dtype=np.uint64)
-    for i, name in enumerate(names):
-        st = cal._stats[name]
-        if isinstance(st, dict):
-            fields["range"][i] = fields["amax"][i] = st["range"]
-            fields["hist"][i] = st["hist"].numpy().astype(np.uint64)
-            fields["count"][i] = int(fields["hist"][i].sum())
-        else:
-            fields["range"][i] = fields["amax"][i] = st
-    _q.write_calibration_cache(path, names, fields, extra)
-
-
-def _load_host_calibration(cal, path):
-    from . import quantization as _q
-    names, fields, extra = _q.read_calibration_cache(path)
-    cal._stats = {}
-    for i, name in enumerate(names):
-        if isinstance(cal, _q._Histogram):
-            cal._stats[name] = {"hist": torch.from_numpy(fields["hist"][i].astype("float64")), "range": float(fields["range"][i])}
-        else:
-            cal._stats[name] = float(fields["amax"][i])
-    return extra
-
-
-def save_calibration(cal, path, extra=None):
-    if hasattr(cal, "save_calibration"):
-        cal.save_calibration(path, extra)
-    else:
-        _save_host_calibration(cal, path, extra)
-
-
-def load_calibration(cal, path, device=None):
-    if hasattr(cal, "load_calibration"):
-        return cal.load_calibration(path, device)
-    return _load_host_calibration(cal, path)
-
-
 def calibrate(fp, images, cal, ops=None):
     """Run the fp16 fast path of `fp` on `images` (an iterable of fp16 CUDA images), collecting every write into an
     int8 group's buffer under the group's site.  -> the number of frames."""
@@ -406,8 +330,6 @@ def calibrate(fp, images, cal, ops=None):
 
 
 def group_scales_from(cal, num_groups):
-    missing = [g for g in range(num_groups) if not cal.has(group_site(g))]
-    if missing:
-        raise ValueError(f"build_int8_yolox: no calibration data for scale groups {missing}")
-    # (the scales as fp32 numbers: what the kernels receive)
-    return [float(torch.tensor(cal.scale(group_site(g)), dtype=torch.float32)) for g in range(num_groups)]
+    """One scale per scale group, in the order of the groups."""
+    sites = [group_site(g) for g in range(num_groups)]
+    return list(scales_from(cal, sites, "build_int8_yolox").values())

@@ -281,3 +281,16 @@ def test_capture_guard_and_weight_reload(built):
         model(img.float())
     with pytest.raises(ValueError):
         model(img[:, :, :100])
+
+
+# sha-256 (tests/test_int8_plan_gpu.py's scale_list_digest) of the sorted (site, scale) list of `built`'s two models (the second one built from the first one's cache), taken from
+# a build of the commit before int8_plan.py on an MI355X (two runs, one value): the calibrate-or-cache path of
+# quantization.build_int8_centernet keeps its statistics and its scales
+PARENT_SCALE_LIST_DIGEST = "4b88b482d69189bbf147ecd221531e065436d63188ad40d87b8bdb8aa4b1f53b"
+
+
+def test_the_calibrated_scales_keep_the_parent_commits_values(built):
+    from test_int8_plan_gpu import scale_list_digest
+    got = scale_list_digest(built["models"]["int8"].scales, built["models"]["fp16"].scales)
+    print("scale list:", got)
+    assert got == PARENT_SCALE_LIST_DIGEST

@@ -326,3 +326,17 @@ def test_capture_guard_weight_reload_and_device_calibrator_cache(built, tmp_path
     assert model.operands(build=False) is not ops0 and bool((new[7] == 0.5).all())
     for i in (0, 1, 2, 3, 4, 5, 6, 8):
         assert torch.equal(_bits(new[i]), _bits(eager[i])), NAMES[i]
+
+
+# sha-256 (tests/test_int8_plan_gpu.py's scale_list_digest) of the sorted (site, scale) list of `built`'s model, taken from
+# a build of the commit before int8_plan.py on an MI355X (two runs, one value): the calibrate-or-cache path of
+# quantization.build_int8_yolox keeps its statistics and its scales
+PARENT_SCALE_LIST_DIGEST = "20453094692e5ee341ac57e83579acba2a0c0a27b9eebe3966ce7a2c492a6e51"
+
+
+def test_the_calibrated_scales_keep_the_parent_commits_values(built):
+    from test_int8_plan_gpu import scale_list_digest
+    from bevformer_tensorrt_amd.yolox_int8 import group_site
+    got = scale_list_digest({group_site(g): s for g, s in enumerate(built["model"].group_scales)})
+    print("scale list:", got)
+    assert got == PARENT_SCALE_LIST_DIGEST
