@@ -816,6 +816,43 @@ def _versions(*tensors):
 _MERGED_PROJ = {"enabled": os.environ.get("BEVOPS_MERGED_PROJ", "1") != "0"}
 
 
+# Row chains (design/model.md "Row chains"): dense layers that follow each other on the decoder's 900 query rows as ONE
+# launch (ops.row_chain, csrc/row_chain.hip) -- a decoder layer's tail (cross-attention output_proj + norm, the FFN + norm,
+# the layer's regression branch, the next layer's self-attention in-projection) and the six levels' classification
+# branches.  Rule-based (plain fp16 nn.Linear layers on the device under the own-kernel dispatch: every rank of a sharded
+# runner decides alike); the INT8 engine, the reference operator set, fp32 and the CPU keep one launch per layer.
+# BEVOPS_ROW_CHAIN=0 / _ROW_CHAIN["enabled"] = False: the per-layer launches (A/B).
+_ROW_CHAIN = {"enabled": os.environ.get("BEVOPS_ROW_CHAIN", "1") != "0"}
+
+
+def _chain_ok(ops, x, linears, norms=()):
+    return _ROW_CHAIN["enabled"] and getattr(ops, "row_chain", None) is not None and OWN_KERNELS["enabled"] \
+        and _fast_dense_ok(ops, x, *linears) \
+        and all(type(l) is nn.Linear and l.bias is not None and l.weight.dtype == torch.float16 for l in linears) \
+        and all(isinstance(n, nn.LayerNorm) and n.elementwise_affine and n.weight.dtype == torch.float16 for n in norms)
+
+
+def _packed_weights(ops, owner, cache, weights):
+    """ops.pack_chain_weight of every weight (the order the chain's matrix instruction reads: one contiguous kilobyte
+    per request), cached on `owner` under `cache`, keyed on the parameters' versions and storage."""
+    key = _versions(*weights)
+    hit = getattr(owner, cache, None)
+    if hit is None or hit[0] != key:
+        hit = (key, [ops.pack_chain_weight(w) for w in weights])
+        setattr(owner, cache, hit)
+    return hit[1]
+
+
+def _chain_stage(lin, norm=None, packed=None, **kw):
+    st = {"weight": lin.weight, "bias": lin.bias}
+    if packed is not None:
+        st["weight"], st["packed"] = packed, tuple(lin.weight.shape)
+    if norm is not None:
+        st["norm"] = (norm.weight, norm.bias, norm.eps)
+    st.update(kw)
+    return st
+
+
 def _merge_ok(ops, x, linears, has_res):
     """The conditions every merged launch shares: the switches, fp16 rows on the GPU, plain fp16 nn.Linear layers with
     a bias, and a per-layer route that runs on tile_gemm / tsgemm (functions.linear.own_kernel_choice) -- only then do
@@ -934,9 +971,11 @@ class CustomMSDeformableAttention(nn.Module):
             self._so_aw = (key, torch.cat([so.weight, aw.weight]).detach().contiguous())
         return _or_none(fn, q2, self._so_aw[1], None, widths, [t_so, t_aw])
 
-    def forward(self, query, value, query_pos, reference_points, spatial_shapes, norm=None, projected=None, merged=False):
+    def forward(self, query, value, query_pos, reference_points, spatial_shapes, norm=None, projected=None, merged=False,
+                sample_only=False):
         """`projected`: value_proj(value) [nk, 256] when the caller has evaluated it already (_merged_value_proj);
-        `merged`: the frame runs its merged launches (_merged_offsets_weights)."""
+        `merged`: the frame runs its merged launches (_merged_offsets_weights); `sample_only`: the sampled rows
+        [900, 256] in front of output_proj (the caller runs the layer's tail as a row chain)."""
         identity = query                               # [900, 1, 256]
         ops, so, aw = self.ops, self.sampling_offsets, self.attention_weights
         n = query.shape[0]
@@ -967,6 +1006,8 @@ class CustomMSDeformableAttention(nn.Module):
             w = aw(q).view(1, n, HEADS, -1)
         out = ops.multi_scale_deformable_attn(value, spatial_shapes, reference_points, off, w).flatten(2)
         # [1, 900, 256] -> [900, 1, 256] is the same memory: the identity goes into the GEMM epilogue
+        if sample_only:
+            return out.view(n, EMBED)
         if norm is not None:
             return _dense_norm(ops, self.output_proj, out.view(n, 1, EMBED), identity, norm)
         return _dense(ops, self.output_proj, out.view(n, 1, EMBED), identity, False)
@@ -980,26 +1021,34 @@ class DecoderLayer(nn.Module):
         self.norms = nn.ModuleList(nn.LayerNorm(EMBED) for _ in range(3))
         self._pos_qkv = None
 
-    def _self_attention(self, ops, query, query_pos, norm=None):
+    def _qkv_term(self, ops, query, query_pos):
+        """The frame-independent identity term [900, 768] of the in-projection (q and k see query_pos, v does not: its
+        columns are the bias alone), cached on the parameters' versions and the query_pos tensor.  May raise BevopsError."""
+        fn, n = _gemm_entry(ops), query.shape[0]
+        w, b = self.self_attn.in_proj_weight, self.self_attn.in_proj_bias
+        key = _versions(w, b)
+        hit = self._pos_qkv
+        if hit is None or hit[0] != key or hit[1] is not query_pos:
+            term = torch.empty(n, 3 * EMBED, dtype=query.dtype, device=query.device)
+            term[:, :2 * EMBED] = fn(query_pos.reshape(n, EMBED), w[:2 * EMBED], b[:2 * EMBED], None, False)
+            term[:, 2 * EMBED:] = b[2 * EMBED:]
+            hit = self._pos_qkv = (key, query_pos, term)
+        return hit[2]
+
+    def _self_attention(self, ops, query, query_pos, norm=None, qkv=None):
         """query + MultiheadAttention(q = k = query + query_pos, v = query) (mmcv MultiheadAttention
         with its identity, decoder layer operation order) as: ONE [900, 768] in-projection whose
         query_pos part is a cached identity term, the fused attention kernel on head-strided views,
-        and the out-projection with the residual in its epilogue.  None -> nn.MultiheadAttention."""
+        and the out-projection with the residual in its epilogue.  None -> nn.MultiheadAttention.
+        `qkv`: the in-projection [900, 768] when the layer in front evaluated it in its tail (`tail`)."""
         mha = self.self_attn
         if not _fast_dense_ok(ops, query, mha.out_proj) or mha.in_proj_weight is None:
             return None
         fn, n = _gemm_entry(ops), query.shape[0]
-        w, b = mha.in_proj_weight, mha.in_proj_bias
-        key = _versions(w, b)
-        hit = self._pos_qkv
         try:
-            if hit is None or hit[0] != key or hit[1] is not query_pos:
-                # q and k see query_pos, v does not: its rows of the static term are the bias alone
-                term = torch.empty(n, 3 * EMBED, dtype=query.dtype, device=query.device)
-                term[:, :2 * EMBED] = fn(query_pos.reshape(n, EMBED), w[:2 * EMBED], b[:2 * EMBED], None, False)
-                term[:, 2 * EMBED:] = b[2 * EMBED:]
-                hit = self._pos_qkv = (key, query_pos, term)
-            qkv = fn(query.view(n, EMBED), w, None, hit[2], False).view(1, n, 3, HEADS, EMBED // HEADS)
+            if qkv is None:
+                qkv = fn(query.view(n, EMBED), mha.in_proj_weight, None, self._qkv_term(ops, query, query_pos), False)
+            qkv = qkv.view(1, n, 3, HEADS, EMBED // HEADS)
         except _lib.BevopsError as exc:
             if exc.status != _lib.NOT_SUPPORTED:
                 raise
@@ -1016,12 +1065,56 @@ class DecoderLayer(nn.Module):
             o = o.transpose(1, 2).reshape(n, 1, EMBED)
         return _dense(ops, mha.out_proj, o, query, False) if norm is None else _dense_norm(ops, mha.out_proj, o, query, norm)
 
-    def forward(self, query, value, query_pos, reference_points, spatial_shapes, projected=None, merged=False):
+    def _tail(self, ops, sampled, query_n, query_pos, reg, nxt, out, reg_out):
+        """The layer behind its cross-attention sampler as ONE launch (ops.row_chain): output_proj + identity + norms[1],
+        fc1 + ReLU, fc2 + identity + norms[2] (stored: the layer's output, `out`), the regression branch `reg`
+        (Linear-ReLU-Linear-ReLU-Linear, stored: `reg_out`) and -- with a next layer `nxt` -- that layer's self-attention
+        in-projection with its cached query_pos term as identity (stored).  -> (out, reg_out, qkv or None), or None:
+        the per-layer launches."""
+        n = sampled.shape[0]
+        cross, ffn = self.cross_attn, self.ffn
+        lins = [cross.output_proj, ffn.fc1, ffn.fc2, reg[0], reg[2], reg[4]]
+        if not _chain_ok(ops, sampled, lins, (self.norms[1], self.norms[2])):
+            return None
+
+        def launch():
+            mha = nxt.self_attn if nxt is not None else None
+            if mha is not None and (mha.in_proj_weight is None or mha.in_proj_weight.dtype != torch.float16
+                                    or not _fast_dense_ok(ops, sampled, mha.out_proj)):
+                mha = None
+            pk = _packed_weights(ops, self, "_tail_packed", [l.weight for l in lins] + ([mha.in_proj_weight] if mha else []))
+            stages = [_chain_stage(cross.output_proj, self.norms[1], pk[0], res=query_n.view(n, EMBED)),
+                      _chain_stage(ffn.fc1, None, pk[1], relu=True),
+                      _chain_stage(ffn.fc2, self.norms[2], pk[2], res_stage=1, store=out),
+                      _chain_stage(reg[0], None, pk[3], relu=True), _chain_stage(reg[2], None, pk[4], relu=True),
+                      _chain_stage(reg[4], None, pk[5], store=reg_out)]
+            if mha is not None:
+                stages.append({"weight": pk[6], "packed": tuple(mha.in_proj_weight.shape), "bias": None, "input": 2,
+                               "res": nxt._qkv_term(ops, sampled, query_pos), "store": True})
+            got = ops.row_chain(sampled, stages)
+            return got[0], got[1], got[2] if len(got) > 2 else None
+        return _or_none(launch)
+
+    def forward(self, query, value, query_pos, reference_points, spatial_shapes, projected=None, merged=False, qkv=None,
+                tail=None):
+        """`qkv`: this layer's self-attention in-projection, evaluated by the tail of the layer in front.  `tail` =
+        (reg_branch, next layer or None, out [900, 256], reg_out [900, 10]): the caller wants the layer's tail as one
+        launch with its regression branch -- then the result is (out [900, 1, 256], reg [1, 900, 10] or None (the tail
+        ran per layer: the caller evaluates the branch), next layer's qkv or None)."""
         ops = self.cross_attn.ops
-        query_n = self._self_attention(ops, query, query_pos, norm=self.norms[0])
+        query_n = self._self_attention(ops, query, query_pos, norm=self.norms[0], qkv=qkv)
         if query_n is None:
             qk = query + query_pos
             query_n = _layer_norm(ops, self.norms[0], query + self.self_attn(qk, qk, query, need_weights=False)[0])
+        if tail is not None:
+            reg, nxt, out, reg_out = tail
+            sampled = self.cross_attn(query_n, value, query_pos, reference_points, spatial_shapes, projected=projected,
+                                      merged=merged, sample_only=True)
+            done = self._tail(ops, sampled, query_n, query_pos, reg, nxt, out, reg_out)
+            if done is not None:
+                return done[0].view(-1, 1, EMBED), done[1].view(1, -1, 10), done[2]
+            query = _dense_norm(ops, self.cross_attn.output_proj, sampled.view(-1, 1, EMBED), query_n, self.norms[1])
+            return self.ffn(query, ops, norm=self.norms[2]), None, None
         query = self.cross_attn(query_n, value, query_pos, reference_points, spatial_shapes, norm=self.norms[1],
                                 projected=projected, merged=merged)
         return self.ffn(query, ops, norm=self.norms[2])
@@ -1265,9 +1358,26 @@ class BEVFormer(nn.Module):
         # all six layers project the same bev_embed: one grouped launch in front of the loop
         dec_values = _merged_value_proj(self.ops, self, "_dec_vcat", [l.cross_attn.value_proj for l in self.decoder],
                                         bev_embed) if merged else None
+        # Row chains: a layer's tail, its regression branch and the next layer's in-projection are ONE launch that writes
+        # the layer's rows of hs_all / reg_all (the head's [6, 900, .] operands: no stack afterwards)
+        chained = _ROW_CHAIN["enabled"] and _fast_dense_ok(self.ops, out) and OWN_KERNELS["enabled"] \
+            and getattr(self.ops, "row_chain", None) is not None and all(len(b) == 5 for b in self.reg_branches)
+        hs_all = reg_all = qkv = None
+        if chained:
+            hs_all = torch.empty(6, NUM_QUERY, EMBED, dtype=dtype, device=dev)
+            reg_all = torch.empty(6, NUM_QUERY, 10, dtype=dtype, device=dev)
         for lid, layer in enumerate(self.decoder):
-            out = layer(out, bev_embed, query_pos, ref_xy, bev_shapes, None if dec_values is None else dec_values[lid], merged)
-            tmp = _mlp(self.ops, self.reg_branches[lid], out).view(1, -1, 10)
+            tmp = None
+            if chained:
+                out, tmp, qkv = layer(out, bev_embed, query_pos, ref_xy, bev_shapes, None if dec_values is None else dec_values[lid],
+                                      merged, qkv, (self.reg_branches[lid], self.decoder[lid + 1] if lid < 5 else None,
+                                                    hs_all[lid], reg_all[lid]))
+                if tmp is None:         # (a layer ran per layer: so do the others, and the head stacks as before)
+                    chained, hs_all = False, None
+            else:
+                out = layer(out, bev_embed, query_pos, ref_xy, bev_shapes, None if dec_values is None else dec_values[lid], merged)
+            if tmp is None:
+                tmp = _mlp(self.ops, self.reg_branches[lid], out).view(1, -1, 10)
             if fused_refine is not None:
                 reference_points, ref_xy = fused_refine(tmp, reference_points)
             else:
@@ -1295,9 +1405,10 @@ class BEVFormer(nn.Module):
                 classes.append(self.cls_branches[lvl](hs))
                 coords.append(crd)
             return bev_embed, torch.stack(classes), torch.stack(coords)
-        crd = torch.stack(regs)                                                        # [6, 1, 900, 10]
+        # (every layer's tail ran as a row chain: the rows are in hs_all / reg_all already)
+        crd = reg_all.view(6, 1, NUM_QUERY, 10) if hs_all is not None else torch.stack(regs)   # [6, 1, 900, 10]
         decode = getattr(self.ops, "decode_boxes", None) if fused_refine is not None else None
-        hs = torch.stack(inter).view(6, NUM_QUERY, EMBED)
+        hs = hs_all if hs_all is not None else torch.stack(inter).view(6, NUM_QUERY, EMBED)
         if decode is not None:      # the ~20 element-wise launches below as ONE, bit-exact (functions/refine.py)
             crd = decode(crd, torch.stack([init_reference] + inter_refs[:-1]), PC_RANGE)
             return bev_embed, self._cls_batched(hs).view(6, 1, NUM_QUERY, -1), crd
@@ -1334,6 +1445,23 @@ class BEVFormer(nn.Module):
         """cls_branches[l](hs[l]) for the six decoder levels as batched GEMMs: Linear -> LayerNorm -> ReLU ->
         Linear -> LayerNorm -> ReLU -> Linear with the per-level parameters stacked along the batch."""
         key = tuple(p._version for p in self.cls_branches.parameters()) + (hs.dtype, hs.device)
+        b0 = self.cls_branches[0]
+        if hs.is_contiguous() and all(len(b) == 7 and (b[1].eps, b[4].eps) == (b0[1].eps, b0[4].eps) for b in self.cls_branches) \
+                and _chain_ok(self.ops, hs, [b[k] for b in self.cls_branches for k in (0, 3, 6)],
+                              [b[k] for b in self.cls_branches for k in (1, 4)]):
+            # ONE launch of the row chain in its grouped form: level l's rows against level l's stacked parameters
+            ckey = key + tuple(p.data_ptr() for p in self.cls_branches.parameters())
+            if getattr(self, "_cls_chain", None) is None or self._cls_chain[0] != ckey:
+                st = lambda k, attr: torch.stack([getattr(b[k], attr).detach() for b in self.cls_branches]).contiguous()
+                pk = lambda k: {"weight": self.ops.pack_chain_weight(st(k, "weight")), "packed": tuple(b0[k].weight.shape),
+                                "bias": st(k, "bias")}
+                self._cls_chain = (ckey, [
+                    dict(pk(0), norm=(st(1, "weight"), st(1, "bias"), b0[1].eps), relu=True),
+                    dict(pk(3), norm=(st(4, "weight"), st(4, "bias"), b0[4].eps), relu=True),
+                    dict(pk(6), store=True)])
+            got = _or_none(self.ops.row_chain, hs.view(-1, hs.shape[-1]), self._cls_chain[1], len(self.cls_branches))
+            if got is not None:
+                return got[0].view(len(self.cls_branches), hs.shape[1], -1)
         if getattr(self, "_cls_stack", None) is None or self._cls_stack[0] != key:
             st = lambda k, attr: torch.stack([getattr(b[k], attr).detach() for b in self.cls_branches]).to(hs.dtype)
             self._cls_stack = (key, [(st(k, "weight").transpose(1, 2).contiguous(), st(k, "bias").unsqueeze(1)) for k in (0, 3, 6)],

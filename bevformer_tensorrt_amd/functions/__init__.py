@@ -18,7 +18,7 @@ from .modulated_deformable_conv2d import (modulated_deformable_conv2d, modulated
 from .spatial_cross_attention import (spatial_cross_attention_sample, spatial_cross_attention_projected,
                                       spatial_cross_attention_plan)
 from .linear import (linear_bias_act, layer_norm, quantize_rows, dequantize_rows, linear_int8, tsgemm, tsgemm_ln, tsgemm_grouped, tile_gemm, tile_gemm_dst, gemm2, small_gemm, small_gemm_dst,
-                     dense_auto, tsa_split, queue_mean2)
+                     dense_auto, tsa_split, queue_mean2, row_chain, pack_chain_weight)
 from .int8_chain import linear_int8_chain, linear_int8_ln, conv_int8_chain_nhwc, modulated_deformable_conv2d_int8_nhwc
 from .conv import conv_nhwc, conv3x3_nhwc, conv3x3_auto, conv3x3_c64, conv_int8_nhwc, stem_conv_pool
 from .image import (image_normalize_pad, padded_size, bevdet_test_augmentation, bevdet_post_transform, image_resize_plan,
@@ -73,7 +73,7 @@ __all__ = [
     "BEVFORMER_IMAGE_PIPELINES", "scaled_size", "scale_lidar2img", "image_normalize_resize_pad",
     "DETECT2D_IMAGE_PIPELINES", "keep_ratio_size", "yolox_test_geometry", "centernet_test_geometry", "image_letterbox",
     "spatial_cross_attention_sample", "spatial_cross_attention_projected", "spatial_cross_attention_plan", "modulated_deformable_conv2d_nhwc", "bias_act_nhwc_", "linear_bias_act", "layer_norm", "rotate_hwc", "conv_offset_nhwc", "upsample_add_nhwc_", "feat_embed_nhwc",
-    "msda_pack_value", "multi_scale_deformable_attn_prepacked", "multi_scale_deformable_attn_local", "image_normalize_pad", "padded_size", "quantize_rows", "dequantize_rows", "linear_int8", "tsgemm", "tsgemm_ln", "tsgemm_grouped", "tile_gemm", "tile_gemm_dst", "gemm2", "small_gemm_dst", "small_gemm", "dense_auto", "tsa_split", "queue_mean2", "conv_nhwc", "conv3x3_nhwc", "conv3x3_auto", "conv3x3_c64", "conv_int8_nhwc", "bias_relu_maxpool_nhwc", "stem_conv_pool", "point_sampling", "self_attention_qkv", "refine_reference_points", "decode_boxes",
+    "msda_pack_value", "multi_scale_deformable_attn_prepacked", "multi_scale_deformable_attn_local", "image_normalize_pad", "padded_size", "quantize_rows", "dequantize_rows", "linear_int8", "tsgemm", "tsgemm_ln", "tsgemm_grouped", "tile_gemm", "tile_gemm_dst", "gemm2", "small_gemm_dst", "small_gemm", "row_chain", "pack_chain_weight", "dense_auto", "tsa_split", "queue_mean2", "conv_nhwc", "conv3x3_nhwc", "conv3x3_auto", "conv3x3_c64", "conv_int8_nhwc", "bias_relu_maxpool_nhwc", "stem_conv_pool", "point_sampling", "self_attention_qkv", "refine_reference_points", "decode_boxes",
     "linear_int8_chain", "linear_int8_ln", "conv_int8_chain_nhwc", "modulated_deformable_conv2d_int8_nhwc",
     "lss_depth_split", "upsample_bilinear_concat_nhwc", "lss_depth_split_q", "upsample_bilinear_nhwc_q",
     "conv_transpose2d_nhwc", "pack_deconv4x4s2", "deconv_packed_weight", "conv_transpose2d_q_nhwc", "quantize_deconv_weight",

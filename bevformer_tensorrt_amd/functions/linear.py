@@ -300,6 +300,94 @@ def small_gemm_dst(x, weight, bias, widths, residuals=None, relu=False, outs=Non
     return tile_gemm_dst(x, weight, bias, widths, residuals, relu, outs, _entry="bevops_small_gemm_f16_dst")
 
 
+class _ChainDst(ctypes.Structure):    # bevops_chain_dst (include/bevops.h)
+    _fields_ = [("col_begin", ctypes.c_int), ("col_end", ctypes.c_int), ("out", ctypes.c_void_p), ("pitch", ctypes.c_longlong)]
+
+
+class _ChainStage(ctypes.Structure):  # bevops_chain_stage
+    _fields_ = [("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("K", ctypes.c_int), ("N", ctypes.c_int),
+                ("input", ctypes.c_int), ("act", ctypes.c_int), ("packed", ctypes.c_int), ("res", ctypes.c_void_p), ("res_pitch", ctypes.c_longlong),
+                ("res_stage", ctypes.c_int), ("norm", ctypes.c_int), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("eps", ctypes.c_float), ("num_dst", ctypes.c_int), ("dst", _ChainDst * 2)]
+
+
+def pack_chain_weight(weight):
+    """weight [..., N, K] fp16 (K % 32 == 0) in the order bevops_row_chain_f16 reads a `packed` stage: whole 16-row tiles
+    (zero rows behind N), per tile and 32-value k-step the 64 lanes' 8 values each -- [..., ceil(N / 16) * 16 * K]."""
+    *lead, N, K = weight.shape
+    assert weight.dtype == torch.float16 and K % 32 == 0
+    T = (N + 15) // 16
+    w = torch.zeros(*lead, T * 16, K, dtype=weight.dtype, device=weight.device)
+    w[..., :N, :] = weight.detach()
+    w = w.view(*lead, T, 16, K // 32, 4, 8)           # tile, row, k-step, lane group, value
+    d = len(lead)
+    return w.permute(*range(d), d, d + 2, d + 3, d + 1, d + 4).reshape(*lead, T * 16 * K).contiguous()
+
+
+def row_chain(x, stages, groups=1):
+    """A chain of dense stages over the same rows as ONE launch (bevops_row_chain_f16, csrc/row_chain.hip): the rows of
+    the intermediate stages never leave the chip.  x [groups * M, K0] fp16 (unit column stride, any row pitch that is a
+    multiple of 8); `stages` a list of dicts:
+        weight [N, K] (groups > 1: [G, N, K]), bias [N] / [G, N] or None, relu (False),
+        packed (N, K): `weight` is pack_chain_weight of that matrix (one contiguous kilobyte per request: the fast form),
+        input (-1: the stage in front; s: the output of stage s),
+        res (identity tensor [groups * M, N]) or res_stage (s: the INPUT rows of stage s as identity),
+        norm (gamma, beta, eps) or None: LayerNorm behind bias and identity, in front of the ReLU,
+        store: False (nothing leaves the chip), True (a new dense [groups * M, N] tensor), a tensor to write, or a list
+               of column widths (at most two, from column 0 on, every start a multiple of 8): one dense tensor each.
+    Returns the list of stored tensors in stage order (a width list contributes one tensor per width).  Raises
+    BevopsError (NOT_SUPPORTED) outside the entry's domain: K % 32 == 0, K <= 768, N <= 768, at most 8 stages."""
+    assert x.is_cuda and x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1
+    rows = x.shape[0]
+    assert rows % groups == 0
+    M = rows // groups
+    tab = (_ChainStage * len(stages))()
+    outs, keep = [], []
+    for i, st in enumerate(stages):
+        w, b = st["weight"], st.get("bias")
+        assert w.dtype == torch.float16 and w.is_contiguous() and (b is None or (b.dtype == torch.float16 and b.is_contiguous()))
+        e = tab[i]
+        e.weight, e.bias = w.data_ptr(), _ptr(b)
+        e.N, e.K = st["packed"] if st.get("packed") else (w.shape[-2], w.shape[-1])
+        e.packed = int(bool(st.get("packed")))
+        if e.packed and w.numel() != groups * ((e.N + 15) // 16) * 16 * e.K:
+            raise ValueError("packed weight does not match (N, K)")
+        e.input, e.act = int(st.get("input", -1)), int(bool(st.get("relu", False)))
+        res = st.get("res")
+        e.res_stage = int(st.get("res_stage", -1))
+        if res is not None:
+            if res.dtype != torch.float16 or tuple(res.shape) != (rows, e.N) or res.stride(1) != 1:
+                raise ValueError("res must be fp16 [rows, N] with unit column stride")
+            e.res, e.res_pitch = res.data_ptr(), res.stride(0) if rows > 1 else e.N
+        norm = st.get("norm")
+        if norm is not None:
+            gamma, beta, eps = norm
+            assert gamma.dtype == torch.float16 and beta.dtype == torch.float16 and gamma.is_contiguous() and beta.is_contiguous()
+            e.norm, e.gamma, e.beta, e.eps = 1, gamma.data_ptr(), beta.data_ptr(), float(eps)
+            keep += [gamma, beta]
+        store = st.get("store", False)
+        if store is True:
+            store = torch.empty((rows, e.N), dtype=x.dtype, device=x.device)
+        if torch.is_tensor(store):
+            assert store.dtype == x.dtype and tuple(store.shape) == (rows, e.N) and (e.N == 1 or store.stride(1) == 1)
+            e.num_dst = 1
+            e.dst[0].col_begin, e.dst[0].col_end, e.dst[0].out = 0, e.N, store.data_ptr()
+            e.dst[0].pitch = store.stride(0) if rows > 1 else e.N
+            outs.append(store)
+        elif store:
+            col = 0
+            e.num_dst = len(store)
+            for d, n in enumerate(store):
+                o = torch.empty((rows, n), dtype=x.dtype, device=x.device)
+                e.dst[d].col_begin, e.dst[d].col_end, e.dst[d].out, e.dst[d].pitch = col, col + n, o.data_ptr(), n
+                col += n
+                outs.append(o)
+    if M:
+        _call("bevops_row_chain_f16", x.device, x.data_ptr(), x.stride(0) if rows > 1 else x.shape[1],
+              ctypes.addressof(tab), len(stages), M, int(groups))
+    return outs
+
+
 def tsgemm_weight_stationary(K):
     """True when bevops_tsgemm_f16 runs its weight-stationary kernel for this K (K <= 256 under the default variant; not
     under bevops_tsgemm_set_variant(1) / BEVOPS_TSGEMM_WS=0, whose kernel rotates its k start by block index)."""

@@ -125,6 +125,7 @@ SIGNATURES = {
     "bevops_tile_gemm_f16_dst": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
     "bevops_gemm2_f16": (c_int, [c_void_p] * 5 + [ctypes.c_longlong] + [c_int] * 8 + [c_void_p]),
     "bevops_small_gemm_f16_dst": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
+    "bevops_row_chain_f16": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, ctypes.c_longlong, c_int, c_void_p]),
     "bevops_conv_tile_f16": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p]),
     "bevops_conv3x3_c64_f16": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
     "bevops_deconv4x4s2_packed_weight_size": (c_size_t, [c_int] * 3),

@@ -539,6 +539,43 @@ int bevops_tile_gemm_f16_dst(const void *x, const void *weight, const void *bias
  * a 64-column block.  Exactly the bytes of the separate bevops_small_gemm_f16 launches. */
 int bevops_small_gemm_f16_dst(const void *x, const void *weight, const void *bias, const bevops_gemm_dst *dst, int num_dst,
                               long long M, int N, int K, int relu, void *stream);
+/* A CHAIN of up to 8 dense stages over the same M rows as ONE launch (the decoder's 900 object queries: the rows of
+ * the intermediate stages never leave the chip; csrc/row_chain.hip, design/model.md "Row chains"):
+ *     y_s = act( LayerNorm( in_s @ weight_s.T + bias_s + identity_s ) ),  fp16 operands, fp32 sums, ONE rounding per stage.
+ * in_s is the output of stage `input` (-1: the stage in front; for stage 0: x [M, K_0], row pitch x_pitch).  identity_s
+ * is `res` (rows of pitch res_pitch) or, with res_stage = r <= s, the INPUT rows of stage r, or absent.  `norm` != 0:
+ * LayerNorm over the N columns (gamma, beta [N], eps; mean and centred squares in fp32 over the unrounded row) in front
+ * of `act` (0 none, 1 ReLU).  Columns [col_begin, col_end) of the stage go to dst[i].out (pitched, num_dst <= 2,
+ * col_begin % 8 == 0, ranges ascending); a stage with num_dst == 0 stores nothing.  A row's results depend on that
+ * row's operands only.  packed != 0: `weight` is in the order the matrix instruction reads it -- element (n, k) of the
+ * [N, K] matrix at ((((n / 16) * (K / 32) + k / 32) * 64 + n % 16 + 16 * ((k % 32) / 8)) * 8 + k % 8, N rounded up to whole
+ * 16-row tiles with zero rows -- so that a wave's request is one contiguous kilobyte; the bits are those of the
+ * row-major call.  groups = G > 1: every row operand holds G * M rows and weight / bias / gamma / beta are stacked
+ * [G, N, K] / [G, N]; rows g * M .. (g + 1) * M - 1 use group g.
+ * Domain: K % 32 == 0, K <= 768, N <= 768, at most 8 stages, 16-byte aligned pointers, x_pitch % 8 == 0, a tensor
+ * identity with N % 4 == 0 and res_pitch % 4 == 0, row operands below 0xFFFFFF00 bytes, the stages' row tiles
+ * within 160 KB of LDS -- else BEVOPS_NOT_SUPPORTED.  NULL / inconsistent arguments (a stage's K against its input's
+ * width, an identity's width against N, ranges outside N): BEVOPS_BAD_PARAM.  Nothing is queued unless BEVOPS_SUCCESS. */
+typedef struct bevops_chain_dst {
+  int col_begin, col_end;
+  void *out;
+  long long pitch;
+} bevops_chain_dst;
+typedef struct bevops_chain_stage {
+  const void *weight, *bias;
+  int K, N;
+  int input, act;
+  int packed;
+  const void *res;
+  long long res_pitch;
+  int res_stage, norm;
+  const void *gamma, *beta;
+  float eps;
+  int num_dst;
+  bevops_chain_dst dst[2];
+} bevops_chain_stage;
+int bevops_row_chain_f16(const void *x, long long x_pitch, const bevops_chain_stage *stages, int num_stages, long long M,
+                         int groups, void *stream);
 /* Convolution on channels-last fp16 activations as an implicit GEMM on the same tiled skeleton (no column
  * buffer, no strided copy): kernel ksize x ksize in {1, 3}, pad ksize / 2, any stride.  x [B, H, W, Cin],
  * weight_taps [Cout][ksize][ksize][Cin] (= weight.permute(0, 2, 3, 1)), out [B, Hout, Wout, Cout] =
