@@ -15,6 +15,9 @@ the order of DepthNet.forward_hip; everything from the softmax + split on is bev
   pooled branch global average of dn.b2.out (exact integer sums) -> fp16; the two few-row
                 GEMMs stay fp16 -> image_bias [n, mid] fp16                             global_avgpool_nhwc_q, dense_auto
   conv1         1 x 1 over 4 mid + the per-image bias + ReLU         -> dn.aspp.out      conv_slice_q_taps(image_bias=)
+  DCN layer     (use_dcn=True, depthnet_dcn="int8") the pack's conv_offset as an int8 3 x 3 with
+                FP16 out (18 rows padded to 24; the offsets are never quantised) -> dn.dcn.om;
+                the grouped deformable convolution, int8 out                 -> dn.dcn    conv_slice_q_taps, deform_conv2d_q_nhwc
   last          1 x 1 mid -> D (padded to 8), FP16 out into the logit columns           conv_slice_q_taps
 
 ONE SCALE PER TENSOR; `dn.aspp.cat` is one group with four writers (the rule of `cat`).  The logits and the feature
@@ -28,15 +31,17 @@ from .bevdepth import ASPP_DILATIONS, MLP_INPUTS
 from .bevdet_int8 import CAT, SITE_PREFIX   # noqa: F401
 from .functions import dispatch as _dispatch
 from .functions import yolox_ops as _Y
-from .int8_plan import (Layer, Plan, basic_block_layers, float_operands, load_calibration, save_calibration,   # noqa: F401
-                        scales_from, stored)
+from .int8_plan import (Layer, Plan, basic_block_layers, fake_quant, float_operands, load_calibration,   # noqa: F401
+                        save_calibration, scales_from, stored)
 
 ASPP_CAT = "dn.aspp.cat"
 ROWS = "dn.rows"
 
 
-# Layer ops beside bevdet_int8's: "gate" (dst and extra[0]: the depth and the context copy) and "avgpool" (the pool + the
-# two fp16 GEMMs of the pooled branch).
+# Layer ops beside bevdet_int8's: "gate" (dst and extra[0]: the depth and the context copy), "avgpool" (the pool + the
+# two fp16 GEMMs of the pooled branch) and "dcn" (the DCN layer's deformable convolution; res: its fp16 offset rows --
+# an int8 layer of a plan with the layer).
+DCN, DCN_OFFSET = "dn.dcn", "dn.dcn.offset"
 
 
 def depthnet_layers(P, dn, x):
@@ -59,6 +64,9 @@ def depthnet_layers(P, dn, x):
         P.readable(ASPP_CAT)
         P.add(Layer("avgpool", None, d, "dn.image_bias"), "f16")
         d = P.add(Layer("conv", "dn.aspp.conv1", ASPP_CAT, "dn.aspp.out", act="relu", image_bias="dn.image_bias"))
+    if dn.use_dcn:
+        om = P.add(Layer("conv", DCN_OFFSET, d, "dn.dcn.om"), "f16")        # no site: the offsets stay fp16
+        d = P.add(Layer("dcn", DCN, d, DCN, res=om))
     return P.add(Layer("conv", "dn.last", d, "depth_net", into=(ROWS, lay["depth_offset"])), "f16")
 
 
@@ -66,7 +74,8 @@ def build_plan(model):
     """bevdet_int8.build_plan(model) with the DepthNet's layers in place of the `depth_net` layer.  plan.tail: the index
     of the softmax + split, where bevdet_int8's own layers begin."""
     base = _bi.build_plan(model)
-    P = Plan(base.prefix, base.int8_ops)
+    dcn = model.view.depth_net.use_dcn
+    P = Plan(base.prefix, base.int8_ops + (("dcn",) if dcn else ()))
     P.buffers.update(base.buffers)
     x = P.add(base.layers[0])
     assert base.layers[0].op == "quantize" and base.layers[1].key == "depth_net" and base.layers[2].op == "split"
@@ -104,7 +113,16 @@ def _dn_sources(dn):
         for i, m in enumerate(dn.aspp.branches()):
             table[f"dn.aspp{i + 1}"] = (m.weight, m.bias)
         table["dn.aspp.conv1"] = (fast["conv1_main"], None)
+    if dn.use_dcn:
+        table[DCN_OFFSET] = (dn.dcn.conv_offset.weight, dn.dcn.conv_offset.bias)
     return table
+
+
+def _dcn_source(model):
+    """{"dn.dcn": (weight [Cout, Cin / groups, 3, 3], None)} of a DepthNet with the DCN layer, else {}.  Per-output-channel
+    scales are legal with groups: the epilogue is per output channel."""
+    dn = model.view.depth_net
+    return {DCN: (dn.dcn.weight, None)} if dn.use_dcn else {}
 
 
 def _sources(model, plan):
@@ -126,16 +144,20 @@ def _sources(model, plan):
 
 def quantize_operands(model, plan):
     """bevdet_int8.quantize_operands for the plan with the DepthNet: per-output-channel int8 taps-major weights, scales and
-    fp32 biases (the zero pad rows of the last convolution and of context_conv get scale 1 and stay exact zeros); "fast":
+    fp32 biases (the zero pad rows of the last convolution, of context_conv and of the DCN layer's offset convolution --
+    18 rows padded to 24 -- get scale 1 and stay exact zeros); "dn.dcn": the deformable convolution's
+    [Cout, 3, 3, Cin / groups]; "fast":
     the DepthNet's fp16 operands -- the packed gate block and the pooled branch's two GEMM weights."""
     src, lay, slices = _sources(model, plan)
     table = {k: _Y.quantize_weight_taps(w, b, multiple=8) for k, (w, b) in src.items()}
+    table.update({k: _Y.quantize_weight_taps(w, None) for k, (w, _) in _dcn_source(model).items()})
     table["layout"], table["slices"], table["fast"] = lay, slices, model.view.depth_net.fast_operands()
     return table
 
 
 def _float_operands(model, plan):
     src, lay, slices = _sources(model, plan)
+    src.update(_dcn_source(model))
     return dict(float_operands(src), layout=lay, slices=slices, fast=model.view.depth_net.fast_operands())
 
 
@@ -160,7 +182,10 @@ def emulate(model, plan, x, ranks, table, scales, tensors=None, mlp_input=None):
     """bevdet_int8.emulate with the DepthNet in front: fake quantisation at every int8 tensor (both gate products
     included), the dilated convolutions, the average pool of the dequantised tensor, the pooled branch's two GEMMs and
     the resulting per-image bias each rounded to binary16 where the kernels round, the feature and logit columns rounded
-    to binary16.  scales None: nothing is quantised or rounded -- the fp32 plain path."""
+    to binary16.  The DCN layer: the offsets rounded to binary16 (its convolution's fp16 out), the sampled column built
+    with deform_conv2d's rules in fp32 and fake-quantised with the SOURCE tensor's scale -- the kernel rounds the column
+    to int8 there -- then the grouped product with the dequantised weights.  scales None: nothing is quantised or
+    rounded -- the fp32 plain path."""
     live = {} if tensors is None else tensors
     if mlp_input is None:
         raise ValueError("the BEVDepth statement needs mlp_input")
@@ -173,6 +198,12 @@ def emulate(model, plan, x, ranks, table, scales, tensors=None, mlp_input=None):
         if l.op == "gate":
             live[l.extra[0]] = fq(src * gates[1][:, :, None, None], l.extra[0])
             return fq(src * gates[0][:, :, None, None], l.dst)
+        if l.op == "dcn":
+            from .functions.deform_conv import _deform_conv2d_cpu
+            w, ws, _ = table[l.key]
+            wf = (w.float() * ws[:, None, None, None]).permute(0, 3, 1, 2).contiguous()
+            column = None if scales is None else (lambda c: fake_quant(c, scales[plan.site(l.src)]))
+            return fq(_deform_conv2d_cpu(src, live[l.res][:, :18], wf, 1, 1, 1, dn.dcn.groups, 1, column=column), l.dst)
         assert l.op == "avgpool"
         pooled = h16(src.mean(dim=(2, 3)))
         a = dn.aspp
@@ -209,6 +240,9 @@ class Int8BEVDepth(_bi.Int8BEVDet):
             if l.op == "gate":
                 y, live[l.extra[0]] = ops.se_gate2_nhwc_q(src, self.scale(l.src), gates, s_out, self.scale(l.extra[0]))
                 return y
+            if l.op == "dcn":
+                w, ws, _ = table[l.key]
+                return ops.deform_conv2d_q_nhwc(src, self.scale(l.src), live[l.res], w, ws, None, dn.dcn.groups, None, s_out)
             assert l.op == "avgpool"
             a = dn.aspp
             pooled = ops.global_avgpool_nhwc_q(src, self.scale(l.src))
@@ -270,7 +304,7 @@ def calibrate_frame(fp, x, rest, cal, ops=None):
     """One calibration frame of a BEVDepth model from its fp16 image features x: rest = (ranks_bev, ranks_depth,
     ranks_feat, interval_starts, interval_lengths, mlp_input).  The DepthNet runs layer by layer on the fp16 fast path's
     kernels (DepthNet.forward_hip's calls) and every tensor the plan quantises is collected under its site, the ASPP
-    buffer as ONE tensor; from the split on, bevdet_int8.calibrate_behind_split."""
+    buffer as ONE tensor, the DCN layer's output behind its two fp16 launches; from the split on, bevdet_int8.calibrate_behind_split."""
     ops = ops if ops is not None else _hip_ops
     ranks, mlp_input = tuple(rest[:5]), rest[5]
     view = fp.view
@@ -308,6 +342,9 @@ def calibrate_frame(fp, x, rest, cal, ops=None):
             image_bias = ops.dense_auto(g, P["conv1_pool"], a.conv1.bias, None, False)
             depth = ops.conv_slice_nhwc(cat, P["conv1_main"], None, "relu", image_bias=image_bias)
             site("dn.aspp.out", depth)
+        if dn.use_dcn:
+            depth = dn.dcn.forward_hip(depth, ops)                  # the two fp16 launches
+            site(DCN, depth)
         ops.conv_slice_nhwc(depth, P["wd"], P["bd"], "none", out=rows[:, o:o + lay["depth_padded"]])
         d, f = ops.lss_depth_split(rows.permute(0, 2, 3, 1).reshape(n * H * W, lay["row_stride"]), n, view.D,
                                    view.out_channels, lay["depth_offset"], lay["feat_offset"], spatial=(H, W))

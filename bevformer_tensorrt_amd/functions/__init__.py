@@ -43,7 +43,7 @@ from .yolox_ops import (conv_slice_nhwc, conv_slice_taps, conv_slice_packed_weig
                         quantize_weight_taps)
 from .lss_depthnet import (lss_camera_gate, se_gate2_nhwc, global_avgpool_nhwc, pack_camera_gate, camera_gate_packed,
                            se_gate2_nhwc_q, global_avgpool_nhwc_q)
-from .deform_conv import deform_conv2d, deform_conv2d_nhwc, deform_conv_packed_weight
+from .deform_conv import deform_conv2d, deform_conv2d_nhwc, deform_conv2d_q_nhwc, deform_conv_packed_weight
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -82,5 +82,5 @@ __all__ = [
     "conv_slice_q_taps", "focus_nhwc_q", "quantize_weight_taps",
     "lss_camera_gate", "se_gate2_nhwc", "global_avgpool_nhwc", "pack_camera_gate", "camera_gate_packed",
     "se_gate2_nhwc_q", "global_avgpool_nhwc_q",
-    "deform_conv2d", "deform_conv2d_nhwc", "deform_conv_packed_weight",
+    "deform_conv2d", "deform_conv2d_nhwc", "deform_conv2d_q_nhwc", "deform_conv_packed_weight",
 ]

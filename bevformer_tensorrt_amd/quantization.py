@@ -1080,9 +1080,11 @@ def _calibrated(cal, cache, dev, run, extra):
 
 
 BEVDET_BEV_HALF_BUILDS = ("fp16", "int8")
+BEVDET_DEPTHNET_DCN_BUILDS = (None, "int8")
 
 
-def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", calibration_cache=None, cfg=None):
+def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", calibration_cache=None, cfg=None,
+                      depthnet_dcn=None):
     """The PTQ build of the re-hosted BEVDet-R50 (BASELINE config 5; `D` = the bevdet module, or a bevdet.BEVDet
     instance whose weights to quantise; `frames` = an iterable of (image, ranks...) calibration inputs): ResNet-50 + FPN
     laterals as the int8 activation chain, bev_pool_v2 on its INT8 plugin flavour.  bev_half="fp16" (the default): the
@@ -1099,18 +1101,31 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
     only when given) is built with bev_half="int8" only: the DepthNet's int8 plan of bevdepth_int8.py in front of the same
     BEV half (design/bevdepth_int8.md), frames = (image, ranks_bev, ranks_depth, ranks_feat, interval_starts,
     interval_lengths, mlp_input), the model a bevdepth_int8.Int8BEVDepth.  The default bev_half="fp16" build of a BEVDepth
-    model is not built: NotImplementedError."""
+    model is not built: NotImplementedError.
+    depthnet_dcn: what to do with the DCN layer of a BEVDepth model's DepthNet (use_dcn=True, BEVDEPTH_R50_DCN).  None
+    (the default): such a model is refused, NotImplementedError, before any frame runs.  "int8" (with bev_half="int8"):
+    the layer joins the plan as two int8 layers -- the pack's offset convolution with fp16 out (the offsets are never
+    quantised) and the int8 grouped deformable convolution deform_conv2d_q_nhwc with its own site "dn.dcn"
+    (design/bevdepth_dcn_int8.md); note["depthnet_dcn"] = "int8".  "int8" on a model without the layer, or any other
+    value: ValueError."""
     if bev_half not in BEVDET_BEV_HALF_BUILDS:
         raise ValueError(f"bev_half = {bev_half!r}: one of {BEVDET_BEV_HALF_BUILDS}")
+    if depthnet_dcn not in BEVDET_DEPTHNET_DCN_BUILDS:
+        raise ValueError(f"depthnet_dcn = {depthnet_dcn!r}: one of {BEVDET_DEPTHNET_DCN_BUILDS}")
     if calibration_cache is not None and bev_half != "int8":
         raise ValueError("build_int8_bevdet: calibration_cache goes with bev_half='int8'")
     src = D if isinstance(D, torch.nn.Module) else None
     model_cfg = (getattr(src, "cfg", None) if src is not None else cfg) or {}
     depthnet = model_cfg.get("view_transformer") == "bevdepth"
-    if depthnet and ((model_cfg.get("depthnet_cfg") or {}).get("use_dcn", False)
-                     or getattr(getattr(getattr(src, "view", None), "depth_net", None), "use_dcn", False)):
-        raise NotImplementedError("build_int8_bevdet: the DepthNet's DCN layer (use_dcn=True) has no INT8 form; build "
-                                  "the model with use_dcn=False (BEVDEPTH_R50) for an INT8 BEVDepth (design/bevdepth_dcn.md)")
+    has_dcn = bool(depthnet and ((model_cfg.get("depthnet_cfg") or {}).get("use_dcn", False)
+                                 or getattr(getattr(getattr(src, "view", None), "depth_net", None), "use_dcn", False)))
+    if has_dcn and depthnet_dcn is None:
+        raise NotImplementedError("build_int8_bevdet: the DepthNet's DCN layer (use_dcn=True) is built in INT8 on request "
+                                  "only: pass depthnet_dcn=\"int8\" with bev_half=\"int8\" (design/bevdepth_dcn_int8.md), or "
+                                  "build the model with use_dcn=False (BEVDEPTH_R50)")
+    if depthnet_dcn is not None and not has_dcn:
+        raise ValueError(f"build_int8_bevdet: depthnet_dcn = {depthnet_dcn!r}, but the model's DepthNet has no DCN layer "
+                         "(a BEVDepth model with depthnet_cfg use_dcn=True, BEVDEPTH_R50_DCN)")
     if depthnet and bev_half != "int8":
         raise NotImplementedError("build_int8_bevdet: the bev_half='fp16' build of a BEVDepth model is not built (its "
                                   "DepthNet has an int8 plan only in front of the int8 BEV half); pass bev_half=\"int8\" "
@@ -1129,7 +1144,7 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
     model.view.ops = qops
     ch = Int8ChainBackbone(model, qops.cal)
     if bev_half == "int8":
-        return _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache, depthnet)
+        return _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache, depthnet, depthnet_dcn)
     n = 0
     for f in frames:
         qops.begin_frame()
@@ -1144,7 +1159,7 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
     return model, qops, note
 
 
-def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache, depthnet=False):
+def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache, depthnet=False, depthnet_dcn=None):
     """build_int8_bevdet(bev_half="int8") behind the construction of the image chain: the calibration frames (or the
     cache), the freeze, the Int8BEVDet (depthnet: the Int8BEVDepth) around the model."""
     from . import bevdet_int8 as _bi
@@ -1185,8 +1200,10 @@ def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache,
             "bev_half_scale_sites": len(q.plan.sites)}
     if depthnet:
         front = q.plan.layers[:q.plan.tail]
-        note["depthnet_int8_layers"] = sum(1 for l in front if l.op == "conv")
+        note["depthnet_int8_layers"] = sum(1 for l in front if l.op in ("conv", "dcn"))
         note["depthnet_scale_sites"] = len([s for s in q.plan.sites if s.startswith(_bi.SITE_PREFIX + "dn.")])
+    if depthnet_dcn is not None:
+        note["depthnet_dcn"] = depthnet_dcn
     return q, qops, note
 
 

@@ -1566,6 +1566,49 @@ int bevops_deform_conv3x3_nhwc_f16(const void *input_nhwc, const void *offset_nh
                                    const void *packed_weight, const void *bias, void *output_nhwc, int relu,
                                    int B, int H, int W, int Cin, int Cout, int groups, void *stream);
 
+/* ------------------------------------------------------------------------
+ * The INT8 form of the convolution above (csrc/deform_conv_s8.hip, design/bevdepth_dcn_int8.md): grouped, unmodulated,
+ * deformable, 3 x 3, stride 1, padding 1, dilation 1, ONE deform group, any number of conv groups in ONE launch, on
+ * channels-last int8 slices and the int8 matrix cores (v_mfma_i32_32x32x32_i8).  Not a reference plugin.
+ *   x_q     int8, real = q scale_a; element (b, y, x, c) at base + ((b H + y) W + x) x_pitch + c, the pitch in elements as
+ *           in bevops_conv_slice_s8; x_q and out may be channel slices of wider buffers;
+ *   out     int8 (out_dtype BEVOPS_I8, real = q scale_out) or fp16 (BEVOPS_F16), the same addressing with out_pitch;
+ *   offset_nhwc_f16 [B, H, W, offset_channels] fp16: the raw rows of the offset convolution, exactly as the fp16 entry
+ *           reads them: channels [0, 18) are the offsets, (h, w) per tap, taps row-major; channels >= 18 are never read.
+ *           The offsets are NOT quantised;
+ *   w_q_taps int8 [Cout][3][3][Cin / groups] (real = q scale_w w_scales[co]): what quantize_weight_taps makes of
+ *           [Cout, Cin / groups, 3, 3]; no pack entry, no packed-weight cache;
+ *   w_scales fp32 [Cout] or NULL (then 1); bias fp32 [Cout] or NULL; relu 0 or 1.
+ * THE ARITHMETIC (every step one fp32 operation):
+ *   1. positions  h = (float)(y - 1 + i) + (float)off_h is one fp32 add, w likewise.  A tap is live iff h > -1 && w > -1
+ *      && h < H && w < W: a NaN or infinite offset contributes nothing.  lh = h - floorf(h), hh = 1 - lh, likewise for w;
+ *      the four corner weights are one fp32 product each, hh hw, hh lw, lh hw, lh lw.  A corner outside the image is not
+ *      read and contributes +0.
+ *   2. sample     s = w00 * (float)v00; s = fma(w01, (float)v01, s); s = fma(w10, (float)v10, s);
+ *      s = fma(w11, (float)v11, s) in fp32; the column byte is c = min(max(rne(s), -127), 127).  The column has the
+ *      INPUT's scale (bilinear interpolation is convex): no second scale, no 8-bit area weights -- deliberately not the
+ *      DCNv2 plugin's u8 x 255 arithmetic.
+ *   3. sum        sum = sum over (tap, ci in group) of c * w_q, exact in int32.
+ *   4. epilogue   bevops_conv_slice_s8's order, without an identity: sc = (scale_a * scale_w) * w_scales[co], the product
+ *      in parentheses taken on the host; v = fma((float)sum, sc, bias[co]); ReLU if asked for;
+ *      int8 out: min(max(rne(v * inv), -127), 127) with inv = 1.f / scale_out taken on the host (a NaN leaves as -127);
+ *      fp16 out: one rounding.
+ * Byte offsets are 64-bit.  No workspace, no atomics, no allocation, no synchronisation; capturable.
+ * Status, in this order:
+ *   BAD_PARAM      a NULL x_q / offset / weight / out; any pointer (w_scales and bias included) off a 16-byte boundary;
+ *                  B < 0; H, W, Cin, Cout or groups <= 0; relu not 0 / 1; offset_channels < 18 or odd; x_pitch < Cin or
+ *                  not a multiple of 16; out_pitch < Cout or not a multiple of 16 (8 for fp16 out); a scale in use
+ *                  (scale_a, scale_w; scale_out for int8 out) that is not positive and finite
+ *   NOT_SUPPORTED  out_dtype outside {BEVOPS_I8, BEVOPS_F16}; Cin % groups, Cout % groups, (Cin / groups) % 32 or
+ *                  (Cout / groups) % 32 non-zero; B H W > 2^31 - 65 (32-bit pixel index);
+ *                  groups * ceil(Cout / groups / 64) > 65535 (grid rows)
+ *   SUCCESS        B == 0, without a launch
+ * ------------------------------------------------------------------------ */
+int bevops_deform_conv3x3_nhwc_s8(const void *x_q, int x_pitch, float scale_a, const void *offset_nhwc_f16,
+                                  int offset_channels, const void *w_q_taps, const float *w_scales, float scale_w,
+                                  const float *bias, int out_dtype, void *out, int out_pitch, float scale_out, int relu,
+                                  int B, int H, int W, int Cin, int Cout, int groups, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
