@@ -21,12 +21,22 @@ enum DcnPath {
 //   4      both: no split-K tail (fp16 also keeps the 64-pixel tiles);   5  both: 128-pixel tiles whatever the tile count
 //   6 8 9  int8: im2col + GEMM / register-staged kernel / LDS-DMA kernel whatever the tile count;
 //          fp16: a call inside the fused domain runs on the 512-thread register-staged kernel, as under 3
+//   10 14 15  as 0 / 4 / 5, the fp16 LDS-DMA kernel with the skeleton it had before the footprint table: every thread
+//          computes its pixel's sampling footprint per tap, channels-last outputs leave by 8-byte stores per lane.  The
+//          A/B partner of the default: the same bits, in one process (tests/test_mdconv_skeleton_gpu.py, tools/dcn_time.py)
+//   20 24 25  as 0 / 4 / 5 with the footprint table but the per-lane stores (the table's share of the gain alone)
 // Any other value selects the automatic choice, exactly as 0 does (the rule of bevops_msda_set_variant).
+enum DcnSkeleton {
+  kDcnSkelFull = 0,   // footprint table in LDS (128-pixel tiles, <= kDcnTabTaps taps) + row-wide channels-last stores
+  kDcnSkelParent,     // per-thread footprints, per-lane stores
+  kDcnSkelTable       // footprint table, per-lane stores
+};
 struct DcnVariant {
   int id;            // what bevops_mdconv_set_variant returns as the previous value
   DcnPath f16, s8;   // forced path of the family, kDcnAuto = none
   int f16_threads;   // block size of the fp16 register-staged kernel when f16 == kDcnStaged
   bool no_tail, wide;
+  DcnSkeleton skel;  // fp16 LDS-DMA kernel only
 };
 extern thread_local DcnVariant g_dcn_variant;   // defined in mdconv.hip
 
@@ -102,7 +112,8 @@ constexpr int kFM = 256, kFN = 64, kFK = 64, kFLd = kFK + 8;
 constexpr int kGA = kFM * kFK * 2;  // 32 KB weight tile image
 // WN = wave columns (each 32 pixels): 2 -> 512 threads, 64-pixel tile, 80 KB LDS, 2 blocks per CU;
 //                                      4 -> 1024 threads, 128-pixel tile, 96 KB LDS, 1 block per CU
-//                                           (the weight tile is fetched once per 128 pixels)
+//                                           (the weight tile is fetched once per 128 pixels; fp16: + 4 KB per tap of
+//                                           footprint table behind it, kDcnTabTap)
 template <int WN> struct Glds {
   static constexpr int kN = 32 * WN;          // pixels per tile
   static constexpr int kThreads = 256 * WN;
@@ -110,6 +121,15 @@ template <int WN> struct Glds {
   static constexpr int kLds = 2 * (kGA + kB);
   static constexpr int kPieces = 32 / (4 * WN);  // 1 KB weight DMA pieces per wave
 };
+
+// Footprint table of the fp16 LDS-DMA kernel (128-pixel tiles only: two 64-pixel blocks already fill the CU's 160 KB):
+// per tap 128 records of 4 corner byte offsets, then 128 records of 4 packed blend weights, behind the A/B buffers.
+constexpr int kDcnTabTap = 2 * Glds<4>::kN * 16;                 // bytes per tap
+constexpr int kDcnTabTaps = (160 * 1024 - Glds<4>::kLds) / kDcnTabTap;   // 16: a 5 x 5 kernel keeps the per-thread footprint
+// channels-last epilogue image [pixel][kFM halves]: rows padded by 16 bytes (b128 row reads stay aligned and
+// conflict-free, the 8-byte accumulator writes are 2-way conflicted instead of 16-way)
+constexpr int kDcnEpiRow = kFM * 2 + 16;
+static_assert(Glds<4>::kN * kDcnEpiRow <= Glds<4>::kLds && Glds<2>::kN * kDcnEpiRow <= Glds<2>::kLds, "epilogue image");
 
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned swz8(unsigned r) { return (r ^ (r >> 3)) & 7u; }
@@ -125,6 +145,7 @@ struct TailPlan {
   int out_nhwc, relu;                 // epilogue: output layout [B,Ho,Wo,Cout], fused ReLU
   int om_channels;                    // > 0: `offset` is the raw [B,Ho,Wo,om_channels] output of the pack's
                                       // offset convolution (2*KK offsets, then KK mask logits): sigmoid here
+  int row_store;                      // fp16 channels-last: main blocks stage the tile in LDS and store whole pixel rows
 };
 
 // ---- host side: problem description and workspace layout -------------------------------------------
@@ -221,6 +242,8 @@ struct DcnPlan {
   DcnCopy copy;
   bool repack;      // weights re-laid out per call (not packed by the caller)
   bool zero_pad;    // int8, ragged K: packed weights and columns zeroed first
+  bool table;       // fp16 LDS-DMA kernel: sampling footprints from the block's LDS table (else per thread)
+  bool row_store;   // fp16 LDS-DMA kernel, channels-last: row-wide stores through LDS (else per lane)
 };
 // the device's CU count, <= 0 when HIP cannot tell; the resident blocks of the LDS-DMA kernel of tile width wn
 typedef int (*DcnCusFn)();

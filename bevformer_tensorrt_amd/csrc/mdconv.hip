@@ -27,15 +27,21 @@
 namespace bevops {
 // bevops_mdconv_set_variant: the only place that knows the numbers (effects per dtype family: mdconv.h)
 constexpr DcnVariant kDcnVariants[] = {
-    {0, kDcnAuto, kDcnAuto, 0, false, false},
-    {1, kDcnGemm, kDcnAuto, 0, false, false},
-    {2, kDcnStaged, kDcnAuto, 256, false, false},
-    {3, kDcnStaged, kDcnAuto, 512, false, false},
-    {4, kDcnAuto, kDcnAuto, 0, true, false},
-    {5, kDcnAuto, kDcnAuto, 0, false, true},
-    {6, kDcnStaged, kDcnGemm, 512, false, false},
-    {8, kDcnStaged, kDcnStaged, 512, false, false},
-    {9, kDcnStaged, kDcnLds, 512, false, false},
+    {0, kDcnAuto, kDcnAuto, 0, false, false, kDcnSkelFull},
+    {1, kDcnGemm, kDcnAuto, 0, false, false, kDcnSkelFull},
+    {2, kDcnStaged, kDcnAuto, 256, false, false, kDcnSkelFull},
+    {3, kDcnStaged, kDcnAuto, 512, false, false, kDcnSkelFull},
+    {4, kDcnAuto, kDcnAuto, 0, true, false, kDcnSkelFull},
+    {5, kDcnAuto, kDcnAuto, 0, false, true, kDcnSkelFull},
+    {6, kDcnStaged, kDcnGemm, 512, false, false, kDcnSkelFull},
+    {8, kDcnStaged, kDcnStaged, 512, false, false, kDcnSkelFull},
+    {9, kDcnStaged, kDcnLds, 512, false, false, kDcnSkelFull},
+    {10, kDcnAuto, kDcnAuto, 0, false, false, kDcnSkelParent},
+    {14, kDcnAuto, kDcnAuto, 0, true, false, kDcnSkelParent},
+    {15, kDcnAuto, kDcnAuto, 0, false, true, kDcnSkelParent},
+    {20, kDcnAuto, kDcnAuto, 0, false, false, kDcnSkelTable},
+    {24, kDcnAuto, kDcnAuto, 0, true, false, kDcnSkelTable},
+    {25, kDcnAuto, kDcnAuto, 0, false, true, kDcnSkelTable},
 };
 thread_local DcnVariant g_dcn_variant = kDcnVariants[0];
 namespace {
@@ -565,6 +571,10 @@ __global__ __launch_bounds__(THREADS, 2) void dcn_fused_f16_kernel(
 // by (row ^ row >> 3) & 7 -- the DMA is lane-linear, so the swizzle is applied to the SOURCE
 // address; fragment reads (ds_read_b128) are bank-conflict free.
 //   512 threads = 8 waves, 4 (Cout) x 2 (pixels), wave tile 64 x 32; 80 KB LDS -> 2 blocks per CU.
+// Around the loop (design/dcn.md, "The skeleton"): with 128-pixel tiles the sampling footprints come from a table in
+// LDS that the block builds once, one thread per (pixel, tap), instead of once per thread and tap (8 threads share a
+// pixel); a channels-last tile leaves through LDS as whole pixel rows.  bevops_mdconv_set_variant(10) keeps the
+// per-thread footprints and per-lane stores: the same bits.
 // Domain: one deform group per conv group (dg constant over a block's k-loop); else the
 // register-staged kernel runs.
 // 4 consecutive output channels m..m+3 of pixel (b, pix): bias, optional ReLU, NCHW or NHWC store
@@ -598,12 +608,42 @@ __device__ __forceinline__ void dcn_store4(__half *__restrict__ out, const __hal
   }
 }
 
-template <int WN>
+// Sampling footprint of output pixel (pho, pwo) at `tap`: byte offsets of the 4 bilinear corners from `img_off` (the
+// pixel's image and channel slice) and their packed blend weights (w, w) = bilinear weight * mask; a corner that is not
+// sampled gets `skip`, an offset past the descriptor's end (reads as zero), and weight 0.  ONE body for the per-thread
+// footprint and the table record, so that both hold the same bits.
+__device__ __forceinline__ void dcn_footprint(const ConvDims &d, bool pvalid, int pho, int pwo, unsigned img_off, int tap,
+                                              float off_h, float off_w, float m, unsigned skip, int (&fidx)[4],
+                                              unsigned (&fw)[4]) {
+  const int i = tap / d.Kw, j = tap - i * d.Kw;
+  const float h_im = (float)(pho * d.sh - d.ph + i * d.dh) + off_h;
+  const float w_im = (float)(pwo * d.sw - d.pw + j * d.dw) + off_w;
+  const bool in = pvalid && h_im > -1.f && w_im > -1.f && h_im < (float)d.H && w_im < (float)d.W;
+  const float hf = floorf(h_im), wf = floorf(w_im);
+  const int h0 = (int)hf, w0 = (int)wf;
+  const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
+  const float wq[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
+  const int hs[4] = {h0, h0, h0 + 1, h0 + 1}, ws[4] = {w0, w0 + 1, w0, w0 + 1};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const bool ok = in && hs[q] >= 0 && hs[q] <= d.H - 1 && ws[q] >= 0 && ws[q] <= d.W - 1;
+    fidx[q] = ok ? (int)(img_off + (unsigned)(hs[q] * d.W + ws[q]) * (unsigned)(d.Cin * 2)) : (int)skip;
+    const float w = ok ? wq[q] * m : 0.f;
+    fw[q] = pack_h2(w, w);
+  }
+}
+// A table record holds the offsets of channel chunk 0; the reader adds its chunk's (cq * 16 <= 112) bytes to all four, so
+// a skipped corner sits that much lower than kDcnSkipOff: still past every descriptor plan_fp admits (fits32)
+constexpr unsigned kDcnSkipTab = 0xFFFFFF00u;
+
+// TAB: sampling footprints from a table in LDS behind the A/B buffers, built once per block (WN == 4 only)
+template <int WN, bool TAB>
 __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel(
     const __half *__restrict__ xt, const __half *__restrict__ offset,
     const __half *__restrict__ mask, const __half *__restrict__ wt,
     const __half *__restrict__ bias, __half *__restrict__ out, ConvDims d, int g, TailPlan tp) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // [A0][A1][B0][B1]
+  static_assert(!TAB || WN == 4, "the footprint table needs the LDS a second 64-pixel block would take");
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [A0][A1][B0][B1][footprint table]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 3, wn = wave >> 2;
   const int KK = d.Kh * d.Kw, cin_g = d.Cin / d.G, cout_g = d.Cout / d.G;
@@ -689,33 +729,27 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel
   const bool stagger = (size_t)cout_g * Kg * 2 <= (size_t)(2 << 20);
   const int tap_begin = is_tail ? part * taps_per_part : (stagger ? ntile % KK : 0);
   const int n_my_steps = taps_per_part * chunks;
+  // mask value of a tap: the planar mask as it is, or the sigmoid of the raw logit rounded to binary16
+  auto mask_value = [&](__half mm) {
+    return tp.om_channels ? __half2float(__float2half_rn(1.f / (1.f + __expf(-__half2float(mm))))) : __half2float(mm);
+  };
   __half n_oh, n_ow, n_mm;
-  load_om(tap_begin, n_oh, n_ow, n_mm);
+  if constexpr (!TAB) load_om(tap_begin, n_oh, n_ow, n_mm);
   int fidx[4];
   unsigned fw[4];
   uint4 rb[4];
   auto footprint = [&](int tap) {
     const float off_h = __half2float(n_oh), off_w = __half2float(n_ow);
-    const float m = tp.om_channels ? __half2float(__float2half_rn(1.f / (1.f + __expf(-__half2float(n_mm))))) : __half2float(n_mm);
+    const float m = mask_value(n_mm);
     load_om(tap + 1 < KK ? tap + 1 : 0, n_oh, n_ow, n_mm);
-    const int i = tap / d.Kw, j = tap - i * d.Kw;
-    const float h_im = (float)(pho * d.sh - d.ph + i * d.dh) + off_h;
-    const float w_im = (float)(pwo * d.sw - d.pw + j * d.dw) + off_w;
-    const bool in = pvalid && h_im > -1.f && w_im > -1.f && h_im < (float)d.H && w_im < (float)d.W;
-    const float hf = floorf(h_im), wf = floorf(w_im);
-    const int h0 = (int)hf, w0 = (int)wf;
-    const float lh = h_im - hf, lw = w_im - wf, hh = 1.f - lh, hw = 1.f - lw;
-    const float wq[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-    const int hs[4] = {h0, h0, h0 + 1, h0 + 1}, ws[4] = {w0, w0 + 1, w0, w0 + 1};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const bool ok = in && hs[q] >= 0 && hs[q] <= d.H - 1 && ws[q] >= 0 && ws[q] <= d.W - 1;
-      fidx[q] = ok ? (int)(ximg_off + (unsigned)(hs[q] * d.W + ws[q]) * (unsigned)(d.Cin * 2)) : (int)kDcnSkipOff;
-      const float w = ok ? wq[q] * m : 0.f;
-      fw[q] = pack_h2(w, w);
-    }
+    dcn_footprint(d, pvalid, pho, pwo, ximg_off, tap, off_h, off_w, m, kDcnSkipOff, fidx, fw);
   };
   typedef __attribute__((address_space(3))) void lds_void;
+  typedef __attribute__((address_space(3))) char lds_char;
+  // footprint table: record (tap - tab_tap0, pixel) = 16 bytes of corner offsets at [tap][0][pixel], 16 bytes of blend
+  // weights at [tap][1][pixel]; a main block holds all KK taps, a tail block its own taps_per_part
+  const int tab_tap0 = is_tail ? tap_begin : 0;
+  const unsigned tab_lds = (unsigned)(size_t)((lds_char *)smem) + (unsigned)Glds<WN>::kLds + (unsigned)(pp * 16);
   // The gathers run TWO steps ahead of the MFMAs (their corners are blended one step ahead), the weight
   // DMA one step ahead; each pipeline walks (tap, chunk) with its own counters.  Iteration `step` (tiles of
   // `step` in buffer step & 1, raw corners of step + 1 in rb, a step old):
@@ -725,8 +759,25 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel
   int g_tap = tap_begin, g_chunk = 0, w_tap = tap_begin, w_chunk = 0;
   unsigned c_fw[4] = {0u, 0u, 0u, 0u};   // blend weights of the corners held in rb
   auto gather_next = [&]() {
-    if (g_chunk == 0) footprint(g_tap);   // (also requests the offsets / mask of the tap after it: younger than the
-                                          // step's weight DMA, older than the gathers -- retired by the same vmcnt(4))
+    if constexpr (TAB) {
+      if (g_chunk == 0) {
+        // the pixel's record of g_tap (its 8 threads read the same address: a broadcast).  Hand-written like the
+        // ds_write_b128 of blend_store: a compiler-visible LDS read would drain vmcnt to 0; only lgkmcnt is waited on
+        u32x4_t ri, rw;
+        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:%3\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(ri), "=&v"(rw)
+                     : "v"(tab_lds + (unsigned)((g_tap - tab_tap0) * kDcnTabTap)), "n"(kDcnTabTap / 2)
+                     : "memory");
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          fidx[q] = (int)(ri[q] + (unsigned)(cq * 16));
+          fw[q] = rw[q];
+        }
+      }
+    } else {
+      if (g_chunk == 0) footprint(g_tap);   // (also requests the offsets / mask of the tap after it: younger than the
+                                            // step's weight DMA, older than the gathers -- retired by the same vmcnt(4))
+    }
     const int c0 = g_chunk * kFK;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -743,7 +794,6 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void *)(adst + j * 1024), 16, (int)a_off[j], a_s, 0, 0);
     if (++w_chunk == chunks) { w_chunk = 0; w_tap = w_tap + 1 < KK ? w_tap + 1 : 0; }
   };
-  typedef __attribute__((address_space(3))) char lds_char;
   const unsigned b_lds = (unsigned)(size_t)((lds_char *)smem) + (unsigned)(2 * kGA) + b_dst;
   auto blend_store = [&](int buf) {
     u32x4_t bl;
@@ -759,10 +809,49 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel
   };
 
   // prologue: step 0 -> buffer 0, corners of step 1 in flight
-  gather_next();
-  blend_store(0);
-  __builtin_amdgcn_sched_barrier(0);
-  if (__builtin_amdgcn_readfirstlane(wave) < kTh / 128) weights_next(0);
+  if constexpr (TAB) {
+    // step 0's weight DMA first: it is in flight while the table is built.  One thread per (pixel, tap) record: its
+    // three offset / mask values in one round trip for the whole block (the per-thread path pays one per tap, the
+    // first in front of the first gathers), the footprint arithmetic once instead of once per channel chunk (8 x)
+    if (__builtin_amdgcn_readfirstlane(wave) < kTh / 128) weights_next(0);
+    for (int r = tid; r < taps_per_part * kN; r += kTh) {
+      const int t = r / kN, p = r - t * kN, tap = tab_tap0 + t;
+      const int rn = n0 + p;
+      const bool rvalid = rn < N;
+      const int rb_ = rvalid ? rn / HoWo : 0;
+      const int rpix = rvalid ? rn - rb_ * HoWo : 0;
+      const int rho = rpix / d.Wo, rwo = rpix - rho * d.Wo;
+      __half oh, ow, mm;
+      if (tp.om_channels) {
+        const size_t o = ((size_t)rb_ * HoWo + rpix) * (size_t)tp.om_channels + (size_t)dg * 3 * KK;
+        const unsigned o2 = *reinterpret_cast<const unsigned *>(offset + o + 2 * tap);
+        oh = __ushort_as_half((unsigned short)(o2 & 0xffffu));
+        ow = __ushort_as_half((unsigned short)(o2 >> 16));
+        mm = offset[o + 2 * KK + tap];
+      } else {
+        const size_t o = (((size_t)rb_ * d.DG + dg) * 2 * KK) * HoWo + rpix;
+        oh = offset[o + (size_t)(2 * tap) * HoWo];
+        ow = offset[o + (size_t)(2 * tap + 1) * HoWo];
+        mm = mask[(((size_t)rb_ * d.DG + dg) * KK) * HoWo + rpix + (size_t)tap * HoWo];
+      }
+      int ri[4];
+      unsigned rw[4];
+      dcn_footprint(d, rvalid, rho, rwo, (unsigned)(((size_t)rb_ * d.H * d.W * d.Cin + g * cin_g) * 2), tap,
+                    __half2float(oh), __half2float(ow), mask_value(mm), kDcnSkipTab, ri, rw);
+      char *rec = smem + Glds<WN>::kLds + t * kDcnTabTap + p * 16;
+      *reinterpret_cast<uint4 *>(rec) = make_uint4((unsigned)ri[0], (unsigned)ri[1], (unsigned)ri[2], (unsigned)ri[3]);
+      *reinterpret_cast<uint4 *>(rec + kDcnTabTap / 2) = make_uint4(rw[0], rw[1], rw[2], rw[3]);
+    }
+    __syncthreads();
+    gather_next();
+    blend_store(0);
+    __builtin_amdgcn_sched_barrier(0);
+  } else {
+    gather_next();
+    blend_store(0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (__builtin_amdgcn_readfirstlane(wave) < kTh / 128) weights_next(0);
+  }
   if (n_my_steps > 1) gather_next();
   if (n_my_steps > 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -825,6 +914,38 @@ __global__ __launch_bounds__(256 * WN, WN == 2 ? 2 : 1) void dcn_glds_f16_kernel
         pp[(i * 4 + r) * kTh] = make_float4(acc[i][4 * r], acc[i][4 * r + 1], acc[i][4 * r + 2], acc[i][4 * r + 3]);
     return;
   }
+  if (tp.row_store) {
+    // channels-last, cout_g % 8 == 0, 16-byte aligned output (plan_fp): per-lane stores would put 32 pixels = 32 cache
+    // lines with 16 bytes each under one instruction.  Every wave has passed the last step's barrier, so the A/B
+    // buffers are free: the tile goes there as [pixel][kFM halves] (values exactly as dcn_store4 rounds them) and leaves
+    // as 16-byte pieces of whole pixel rows, consecutive lanes on consecutive pieces, rows in pixel order.
+    char *row = smem + (wn * 32 + (lane & 31)) * kDcnEpiRow;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        const int ml = wm * 64 + i * 32 + 8 * rq + 4 * (lane >> 5), m = m0 + ml;
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          o[e] = acc[i][4 * rq + e];
+          if (bias && m + e < cout_g) o[e] += __half2float(bias[g * cout_g + m + e]);
+          if (tp.relu) o[e] = fmaxf(o[e], 0.f);
+        }
+        *reinterpret_cast<uint2 *>(row + ml * 2) = make_uint2(pack_h2(o[0], o[1]), pack_h2(o[2], o[3]));
+      }
+    __syncthreads();
+    const int pieces = (cout_g - m0 < kFM ? cout_g - m0 : kFM) / 8;   // of this Cout tile's rows, 8 channels each
+    __half *ob = out + g * cout_g + m0;
+    for (int r = tid; r < kN * (kFM / 8); r += kTh) {
+      const int p = r / (kFM / 8), pc = r % (kFM / 8);
+      const int n = n0 + p;
+      if (n < N && pc < pieces)
+        *reinterpret_cast<uint4 *>(ob + (size_t)n * d.Cout + pc * 8) =
+            *reinterpret_cast<const uint4 *>(smem + p * kDcnEpiRow + pc * 16);
+    }
+    return;
+  }
   {
     const int n = n0 + wn * 32 + (lane & 31);
     if (n < N) {
@@ -870,8 +991,12 @@ __global__ __launch_bounds__(256 * WN) void dcn_tail_finish_kernel(const __half 
 
 // ---- host side: plan, then launch (DcnCall, DcnVariant, DcnPlan: mdconv.h) ------------------------------------
 int lds_f16_slots(const DcnCall &, int wn) {
-  return wn == 4 ? resident_blocks<dcn_glds_f16_kernel<4>>(Glds<4>::kThreads, Glds<4>::kLds)
-                 : resident_blocks<dcn_glds_f16_kernel<2>>(Glds<2>::kThreads, Glds<2>::kLds);
+  if (wn != 4) return resident_blocks<dcn_glds_f16_kernel<2, false>>(Glds<2>::kThreads, Glds<2>::kLds);
+  // the 128-pixel tile has two builds, with and without the footprint table: one block per CU either way.  Asking
+  // both also raises each one's dynamic LDS limit, whichever the plan then launches.
+  const int plain = resident_blocks<dcn_glds_f16_kernel<4, false>>(Glds<4>::kThreads, Glds<4>::kLds);
+  const int table = resident_blocks<dcn_glds_f16_kernel<4, true>>(Glds<4>::kThreads, Glds<4>::kLds + kDcnTabTaps * kDcnTabTap);
+  return plain < table ? plain : table;
 }
 
 // What an fp32 / fp16 call launches, or the status that rejects it.  Launches nothing; `cus` and `slots` are asked
@@ -912,6 +1037,10 @@ int plan_fp(const DcnCall &c, const DcnVariant &v, DcnCusFn cus, DcnSlotsFn slot
       p.tail = v.no_tail ? DcnTail{0, 1}
                          : plan_tail(grid_x * grid_y, grid_y, KK, n_slots, w.total - w.col, (size_t)256 * p.WN * 32 * sizeof(float));
       p.partial = static_cast<char *>(c.workspace) + w.col;
+      // skeleton (block-uniform: a template build and one branch outside the k-loop).  Table: 128-pixel tiles whose
+      // taps fit behind the A/B buffers.  Row-wide stores: channels-last with whole 16-byte pieces per group
+      p.table = v.skel != kDcnSkelParent && p.WN == 4 && KK <= kDcnTabTaps;
+      p.row_store = v.skel == kDcnSkelFull && c.nhwc && cout_g % 8 == 0 && aligned16(c.output);
       p.path = kDcnLds;
     }
     return BEVOPS_SUCCESS;
@@ -934,9 +1063,17 @@ int launch_lds_f16(const DcnCall &c, const DcnPlan &p, int g, const __half *xt, 
   const dim3 grid((unsigned)((N + Glds<WN>::kN - 1) / Glds<WN>::kN), (d.Cout / d.G + kFM - 1) / kFM);
   const TailPlan tp{p.tail.tiles, p.tail.split, (int)grid.x - p.tail.tiles,
                     p.tail.tiles ? reinterpret_cast<float *>(p.partial) : nullptr, c.nhwc ? 1 : 0, c.relu ? 1 : 0,
-                    c.om_channels};
-  hipLaunchKernelGGL(dcn_glds_f16_kernel<WN>, dim3((unsigned)(tp.tail_tiles * tp.split + tp.main_tiles), grid.y),
-                     dim3(Glds<WN>::kThreads), Glds<WN>::kLds, c.stream, xt, (const __half *)c.offset,
+                    c.om_channels, p.row_store ? 1 : 0};
+  auto kern = dcn_glds_f16_kernel<WN, false>;
+  int lds = Glds<WN>::kLds;
+  if constexpr (WN == 4) {
+    if (p.table) {
+      kern = dcn_glds_f16_kernel<4, true>;
+      lds += d.Kh * d.Kw * kDcnTabTap;
+    }
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)(tp.tail_tiles * tp.split + tp.main_tiles), grid.y),
+                     dim3(Glds<WN>::kThreads), lds, c.stream, xt, (const __half *)c.offset,
                      (const __half *)c.mask, wt, (const __half *)c.bias, (__half *)c.output, d, g, tp);
   if (tp.tail_tiles)
     hipLaunchKernelGGL(dcn_tail_finish_kernel<WN>, dim3((unsigned)tp.tail_tiles, grid.y, 8), dim3(Glds<WN>::kThreads), 0,

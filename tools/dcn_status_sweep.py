@@ -25,7 +25,7 @@ import sys
 os.environ["HIP_VISIBLE_DEVICES"] = os.environ["CUDA_VISIBLE_DEVICES"] = "-1"
 
 F32, F16, I8 = 0, 1, 2            # bevops_dtype_t
-VARIANTS = [0, 1, 2, 3, 4, 5, 6, 8, 9]
+VARIANTS = [0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 14, 15, 20, 24, 25]
 P, I, F, SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 CTYPES = dict(p=P, stream=P, i=I, f=F, ws_bytes=SZ)
 
