@@ -117,6 +117,10 @@ BEVDET_R50 = dict(
 # and with the reference's DCN layer behind the ASPP (DepthNet's default use_dcn=True: mmcv's DCNv1 pack, groups = 4)
 BEVDEPTH_R50 = dict(BEVDET_R50, view_transformer="bevdepth", depthnet_cfg=dict(use_dcn=False))
 BEVDEPTH_R50_DCN = dict(BEVDET_R50, view_transformer="bevdepth", depthnet_cfg=dict(use_dcn=True))
+# BEVStereo-R50: BEVDepth's DepthNet with the temporal-stereo cost volume of the previous frame's stride-4 backbone
+# features (bevdepth.LSSViewTransformerBEVStereo).  The reference tree has no BEVStereo config: bias = 5.0 and the finer
+# depth grid of the original BEVStereo configs are recalled, not read from it; this keeps BEVDET_R50's grid (D = 59).
+BEVSTEREO_R50 = dict(BEVDET_R50, view_transformer="bevstereo", depthnet_cfg=dict(use_dcn=False, stereo=True, bias=5.0))
 
 
 class LSSViewTransformer(nn.Module):
@@ -469,15 +473,20 @@ class BEVDet(nn.Module):
         if self.bev_half not in BEV_HALF_MODES:
             raise ValueError(f"bev_half = {self.bev_half!r}: 'torch' or 'hip'")
         self.ops = ops = ops if ops is not None else _hip_ops
-        self.backbone = _B.ResNet(50, (False,) * 4, (2, 3), ops, "pytorch")
+        self.stereo = cfg.get("view_transformer") == "bevstereo"
+        # (BEVStereo: the stride-4 stage too, the features the cost volume is built from)
+        self.backbone = _B.ResNet(50, (False,) * 4, (0, 2, 3) if self.stereo else (2, 3), ops, "pytorch")
         self.neck = CustomFPN()
         view_kw = dict({k: cfg[k] for k in ("grid_config", "input_size", "downsample", "in_channels", "out_channels")},
                        ops=ops, seed=seed, bev_half=self.bev_half)
         if cfg.get("view_transformer") == "bevdepth":      # BEVDEPTH_R50: the camera-aware DepthNet (bevdepth.py)
             from .bevdepth import LSSViewTransformerBEVDepth
             self.view = LSSViewTransformerBEVDepth(**view_kw, depthnet_cfg=cfg.get("depthnet_cfg"))
+        elif self.stereo:                                  # BEVSTEREO_R50: the cost volume in front of the DepthNet's blocks
+            from .bevdepth import LSSViewTransformerBEVStereo
+            self.view = LSSViewTransformerBEVStereo(**view_kw, depthnet_cfg=cfg.get("depthnet_cfg"))
         elif cfg.get("view_transformer") not in (None, "lss"):
-            raise ValueError(f"view_transformer = {cfg.get('view_transformer')!r}: 'lss' or 'bevdepth'")
+            raise ValueError(f"view_transformer = {cfg.get('view_transformer')!r}: 'lss', 'bevdepth' or 'bevstereo'")
         else:
             self.view = LSSViewTransformer(**view_kw)
         c = cfg["out_channels"]
@@ -501,8 +510,12 @@ class BEVDet(nn.Module):
                     m.weight.data = m.weight.data.contiguous(memory_format=torch.channels_last)
             self._nhwc_ready = True
 
-    def image_features(self, image):
-        """img_backbone + img_neck: [6, 3, H, W] -> [6, 256, H / 16, W / 16]."""
+    def image_features(self, image, stereo=False):
+        """img_backbone + img_neck: [6, 3, H, W] -> [6, 256, H / 16, W / 16].  stereo=True (a BEVStereo model;
+        image_encoder, third_party/bev_mmdet3d/models/detectors/bevdet.py:35-50): -> (that, the backbone's stride-4
+        features [6, 256, H / 4, W / 4])."""
+        if stereo and not self.stereo:
+            raise ValueError("image_features(stereo=True): a BEVStereo model (cfg view_transformer='bevstereo')")
         ops = self.ops
         nhwc = image.is_cuda and image.dtype == torch.float16 and hasattr(ops, "conv3x3_auto")
         if nhwc:
@@ -513,7 +526,23 @@ class BEVDet(nn.Module):
             feats = self.backbone.forward_nhwc(image, ops)
         else:
             feats = self.backbone(image)
+        if self.stereo:
+            x = self.neck(feats[1:], ops)
+            return (x, feats[0]) if stereo else x
         return self.neck(feats, ops)
+
+    def _frame_features(self, image, stereo_metas):
+        """-> (image features, the view transformer's keyword arguments).  A BEVStereo model: the metas' current
+        features (cv_feat_list[1]) are this frame's stride-4 features when the caller left them None."""
+        if not self.stereo:
+            if stereo_metas is not None:
+                raise ValueError("stereo_metas: a BEVStereo model (cfg view_transformer='bevstereo')")
+            return self.image_features(image), {}
+        if stereo_metas is None:
+            raise ValueError("a BEVStereo model needs stereo_metas (view.stereo_metas(prev, None, ...) of the frame)")
+        x, feat = self.image_features(image, stereo=True)
+        prev, curr = stereo_metas["cv_feat_list"]
+        return x, dict(stereo_metas=dict(stereo_metas, cv_feat_list=[prev, feat if curr is None else curr]))
 
     # ---- bev_half = "hip" (see the section in design/model.md)
     def _hip_on(self, x):
@@ -605,16 +634,20 @@ class BEVDet(nn.Module):
         return _conv(ops, _conv(ops, x, self.up2_conv[0], True), self.up2_conv[1])
 
     @torch.no_grad()
-    def forward(self, image, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, mlp_input=None):
-        """mlp_input: the BEVDepth transformer's `get_mlp_input` of the frame (view_transformer="bevdepth" only)."""
+    def forward(self, image, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, mlp_input=None,
+                stereo_metas=None):
+        """mlp_input: the BEVDepth transformer's `get_mlp_input` of the frame (view_transformer="bevdepth" /
+        "bevstereo" only); stereo_metas: the BEVStereo transformer's (view_transformer="bevstereo" only)."""
         kw = {} if mlp_input is None else dict(mlp_input=mlp_input)
         hip = self._bev_half_ready(image)      # (first: under capture a missing operand raises before anything is launched)
         if hip:
             with _rule_dispatch():      # (the image half too: see forward_calibrated)
-                x = self.image_features(image.flatten(0, 1))
-                bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, **kw)
+                x, skw = self._frame_features(image.flatten(0, 1), stereo_metas)
+                bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths,
+                                               **kw, **skw)
                 return self._heads_hip(self.bev_encoder(bev))
-        x = self.image_features(image.flatten(0, 1))
+        x, skw = self._frame_features(image.flatten(0, 1), stereo_metas)
+        kw.update(skw)
         bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, **kw)
         feat = self.bev_encoder(bev)
         ops = self.ops
@@ -628,28 +661,31 @@ class BEVDet(nn.Module):
         return tuple(_conv(ops, _conv(ops, s, h[0], True), h[1]) for h in (self.heads[k] for k, _ in HEADS_R50))
 
     @torch.no_grad()
-    def forward_calibrated(self, image, calib):
+    def forward_calibrated(self, image, calib, stereo_metas=None):
         """`forward` from the frame's calibration instead of ready-made ranks: calib = the packed fp32 buffer of
         `view.calibration_matrices` on the image's device; the index build and the pooling run on the device.
         B samples at once: image [B, N, 3, H, W] with calib [B, N * 24 + 9] (`view.calibration_matrices_batched`) ->
-        six maps [B, c, h, w]; a 1-D calib is the one-sample call, unchanged."""
+        six maps [B, c, h, w]; a 1-D calib is the one-sample call, unchanged.  stereo_metas (a BEVStereo model only):
+        view.stereo_metas(prev, None, ...) -- the current stride-4 features are this frame's own."""
         if calib.dim() == 2 and image.shape[0] != calib.shape[0]:
             raise ValueError(f"image holds {image.shape[0]} samples, calib {calib.shape[0]}")
         hip = self._bev_half_ready(image)
         # "hip" also takes the image half's dispatch by rule: two library convolutions of ResNet stage 4 that the shipped
         # table prefers are not run-to-run reproducible on the MI355X, and the frame's bits would differ between runs
         with _rule_dispatch() if hip else contextlib.nullcontext():
-            x = self.image_features(image.flatten(0, 1))
-        return self.bev_half_calibrated(x, calib, hip)
+            x, skw = self._frame_features(image.flatten(0, 1), stereo_metas)
+        return self.bev_half_calibrated(x, calib, hip, **skw)
 
     @torch.no_grad()
-    def bev_half_calibrated(self, x, calib, hip=None):
+    def bev_half_calibrated(self, x, calib, hip=None, stereo_metas=None):
         """Everything of `forward_calibrated` behind `image_features`: x = its [cams, 256, H / 16, W / 16] result.
-        hip = None: as `bev_half` and the tensors decide.  calib [B, N * 24 + 9]: x holds B * cams images."""
+        hip = None: as `bev_half` and the tensors decide.  calib [B, N * 24 + 9]: x holds B * cams images.
+        stereo_metas (a BEVStereo model): complete, cv_feat_list = [previous or None, current]."""
+        skw = {} if stereo_metas is None else dict(stereo_metas=stereo_metas)
         if self._bev_half_ready(x) if hip is None else hip:
             with _rule_dispatch():
-                return self._heads_hip(self.bev_encoder(self.view.view_transform_calibrated(x, calib)))
-        return self._heads(self.view.view_transform_calibrated(x, calib))
+                return self._heads_hip(self.bev_encoder(self.view.view_transform_calibrated(x, calib, **skw)))
+        return self._heads(self.view.view_transform_calibrated(x, calib, **skw))
 
     # ---- CenterHead.get_bboxes up to the NMS (centerpoint_head.py:716-746), configs/bevdet/bevdet-r50-cbgs.py:138-147
     @property

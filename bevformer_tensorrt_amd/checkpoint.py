@@ -324,6 +324,10 @@ def depthnet_key_map(depth_net, prefix="img_view_transformer.depth_net."):
         copy(f"depth_conv.{last}.conv_offset")
         last += 1
     copy(f"depth_conv.{last}")
+    if getattr(depth_net, "stereo", False):       # BEVStereo: two stride-2 convolutions with their BatchNorms, a biased 1 x 1
+        fold("cost_volumn_net.0", "cost_volumn_net.0", "cost_volumn_net.1")
+        fold("cost_volumn_net.1", "cost_volumn_net.2", "cost_volumn_net.3")
+        copy("depth_conv.0.downsample")
     return m
 
 
@@ -334,8 +338,8 @@ def depthnet_reference_keys(depth_net, prefix="img_view_transformer.depth_net.")
         if isinstance(src, tuple):
             _, conv, bn = src
             keys.update([conv + ".weight"] + [f"{bn}.{n}" for n in ("weight", "bias", "running_mean", "running_var")])
-            if conv.endswith("reduce_conv.0"):
-                keys.add(conv + ".bias")          # (the only folded convolution that has a bias of its own)
+            if conv.endswith("reduce_conv.0") or "cost_volumn_net." in conv:
+                keys.add(conv + ".bias")          # (the only folded convolutions that have a bias of their own)
         else:
             keys.add(src)
     keys.update(f"{prefix}bn.{n}" for n in ("running_mean", "running_var"))

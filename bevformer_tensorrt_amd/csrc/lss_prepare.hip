@@ -26,6 +26,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "lss_pos.h"
 
 namespace bevops {
 namespace {
@@ -42,18 +43,6 @@ struct LssGrid {
   float lower[3], interval[3], size[3];
   int nx, nxy, cells;
 };
-
-__device__ __forceinline__ float lss_div(float a, float b) {   // IEEE division, never a reciprocal multiply
-#pragma clang fp reciprocal(off) contract(off)
-  return __fdiv_rn(a, b);
-}
-
-__device__ __forceinline__ void lss_mat3(const float *__restrict__ m, float &x, float &y, float &z) {
-  const float ox = add_rn(add_rn(mul_rn(m[0], x), mul_rn(m[1], y)), mul_rn(m[2], z));
-  const float oy = add_rn(add_rn(mul_rn(m[3], x), mul_rn(m[4], y)), mul_rn(m[5], z));
-  const float oz = add_rn(add_rn(mul_rn(m[6], x), mul_rn(m[7], y)), mul_rn(m[8], z));
-  x = ox; y = oy; z = oz;
-}
 
 // calib: one row of calib_stride floats per sample; per camera 24 floats [inverse(post_rots) 9 | post_trans 3 |
 // combine 9 | trans 3], then bda 9.  keys[i] = sample * g.cells + cell of point i, or `dropped` (= batch * g.cells) when

@@ -44,6 +44,8 @@ from .yolox_ops import (conv_slice_nhwc, conv_slice_taps, conv_slice_packed_weig
 from .lss_depthnet import (lss_camera_gate, se_gate2_nhwc, global_avgpool_nhwc, pack_camera_gate, camera_gate_packed,
                            se_gate2_nhwc_q, global_avgpool_nhwc_q)
 from .deform_conv import deform_conv2d, deform_conv2d_nhwc, deform_conv2d_q_nhwc, deform_conv_packed_weight
+from .stereo import (stereo_calibration, stereo_frustum_tables, stereo_grid, stereo_grid_plain, stereo_cost_volume,
+                     stereo_cost_volume_plain)
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -83,4 +85,6 @@ __all__ = [
     "lss_camera_gate", "se_gate2_nhwc", "global_avgpool_nhwc", "pack_camera_gate", "camera_gate_packed",
     "se_gate2_nhwc_q", "global_avgpool_nhwc_q",
     "deform_conv2d", "deform_conv2d_nhwc", "deform_conv2d_q_nhwc", "deform_conv_packed_weight",
+    "stereo_calibration", "stereo_frustum_tables", "stereo_grid", "stereo_grid_plain", "stereo_cost_volume",
+    "stereo_cost_volume_plain",
 ]

@@ -1116,6 +1116,9 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
         raise ValueError("build_int8_bevdet: calibration_cache goes with bev_half='int8'")
     src = D if isinstance(D, torch.nn.Module) else None
     model_cfg = (getattr(src, "cfg", None) if src is not None else cfg) or {}
+    if model_cfg.get("view_transformer") == "bevstereo" or (model_cfg.get("depthnet_cfg") or {}).get("stereo", False):
+        raise NotImplementedError("build_int8_bevdet: the BEVStereo model (DepthNet(stereo=True): the temporal-stereo cost "
+                                  "volume) has no INT8 build (design/bevstereo.md)")
     depthnet = model_cfg.get("view_transformer") == "bevdepth"
     has_dcn = bool(depthnet and ((model_cfg.get("depthnet_cfg") or {}).get("use_dcn", False)
                                  or getattr(getattr(getattr(src, "view", None), "depth_net", None), "use_dcn", False)))

@@ -216,6 +216,9 @@ SIGNATURES = {
                                        [c_void_p]),
     "bevops_deform_conv3x3_nhwc_s8": (c_int, [c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_float,
                                               c_void_p, c_int, c_void_p, c_int, c_float] + [c_int] * 7 + [c_void_p]),
+    "bevops_stereo_grid": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
+    "bevops_stereo_cost_volume_f16": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 7 +
+                                      [c_float, c_void_p]),
 }
 
 F32, F16, I8, U8 = 0, 1, 2, 3

@@ -1608,6 +1608,34 @@ int bevops_deform_conv3x3_nhwc_s8(const void *x_q, int x_pitch, float scale_a, c
                                   int offset_channels, const void *w_q_taps, const float *w_scales, float scale_w,
                                   const float *bias, int out_dtype, void *out, int out_pitch, float scale_out, int relu,
                                   int B, int H, int W, int Cin, int Cout, int groups, void *stream);
+/* BEVStereo's temporal-stereo cost volume (csrc/stereo_cost.hip; DepthNet.gen_grid + calculate_cost_volumn of the
+ * reference's view_transformer.py, bevformer_tensorrt_amd/functions/stereo.py) in ONE launch, no workspace, no atomics:
+ *   out[n, h, w, :D] = softmax over d of -( sum_c |curr[n,h,w,c] - warp(prev)[n,d,h,w,c]| + bias * [gate == 0] )
+ * warp = grid_sample(bilinear, zeros padding, align_corners=True) of prev at grid[n, d, h, w]; gate = the warped value
+ * of channel C - 4 (channel 0 of the last group of four), tested for exact equality with zero, skipped when bias == 0.
+ * prev, curr: channels-last fp16 [n, Hc, Wc, C] channel slices as in bevops_conv_slice_f16 (pitches in elements, >= C,
+ * multiples of 8).  out: channels-last fp16 [n, Hc, Wc, Dpad] slice (out_pitch >= Dpad), columns D .. Dpad written as
+ * exact zeros.  The blend, the sum and the softmax run in fp32 in the fixed order csrc/stereo_cost.hip states; ONE
+ * rounding.  A corner outside the image counts as zero and is not read; a NaN or infinite grid value is outside.
+ * grid != NULL: fp32 [n, D, Hc, Wc, 2], normalised (x, y) as gen_grid returns it.  grid == NULL: the kernel computes
+ * the same values from consts (fp32, 40 floats per camera: inverse(post_rots) 9 | post_trans 3 | k2s_R @ inverse(K) 9 |
+ * k2s_t 3 | K 9 | post_rots[:2,:2] 4 | post_trans[:2] 2 | pad 1) and the frustum tables xs[Wc], ys[Hc], ds[D] (the
+ * values of create_frustum(..., downsample=4)): the reference's fp32 op sequence, every product, sum and quotient
+ * rounded on its own, points with z < 1e-3 sent to (-2, -2), normalised by the image size (4 Hc, 4 Wc).
+ * bevops_stereo_grid writes exactly those values as fp32 [n, D, Hc, Wc, 2]; the fused entry with grid == NULL equals
+ * itself fed with that grid bit for bit.
+ * Statuses, in this order (bevops_conv_slice_f16's): NULL prev / curr / out, n < 0, non-positive Hc / Wc / C / D / Dpad;
+ * grid == NULL with a NULL consts / xs / ys / ds; a pitch below its channel count, Dpad < D; a pitch that is no
+ * multiple of 8; prev / curr / out not 16-byte aligned, grid not 8-byte, a table not 4-byte aligned; a NaN bias:
+ * BEVOPS_BAD_PARAM.  C % 8 != 0 (the reference silently drops C % 4 trailing channels; this entry refuses), D > 128,
+ * Dpad % 8 != 0, n Hc Wc > 0x3fffffff, Hc or Wc above 0xffffff: BEVOPS_NOT_SUPPORTED.  n == 0: BEVOPS_SUCCESS without a
+ * launch.  bevops_stereo_grid: NULL operands, n < 0, non-positive D / Hc / Wc, misaligned pointers: BEVOPS_BAD_PARAM;
+ * D > 128 and the same size limits: BEVOPS_NOT_SUPPORTED. */
+int bevops_stereo_grid(const float *consts, const float *xs, const float *ys, const float *ds, float *grid, int n, int D,
+                       int Hc, int Wc, void *stream);
+int bevops_stereo_cost_volume_f16(const void *prev, int prev_pitch, const void *curr, int curr_pitch, const float *grid,
+                                  const float *consts, const float *xs, const float *ys, const float *ds, void *out,
+                                  int out_pitch, int n, int Hc, int Wc, int C, int D, int Dpad, float bias, void *stream);
 
 #ifdef __cplusplus
 }
