@@ -13,7 +13,7 @@
 //   v     = fma((float)sum, sc, bias[co])            sum: the exact int32 sum; (float): round to nearest even, exact
 //                                                    for |sum| <= 2^24; ONE rounding for multiply and add
 //   v     = act(v)                                   0 none, 1 max(v, 0), 2 v * rcp(1 + exp(-v)) (silu_f32 of
-//                                                    conv_slice.hip: hardware exponential and reciprocal)
+//                                                    tile_mma.h: hardware exponential and reciprocal)
 //   v     = fma((float)res_q, scale_res, v)          with an identity only: BEHIND the activation, ONE rounding
 //                                                    (bevops_conv_slice_s8_ex with res_first = 1: this step moves IN
 //                                                    FRONT of the activation -- mmdet's BasicBlock, relu(conv2 + identity))
@@ -30,10 +30,8 @@
 // Non-finite values: a NaN v leaves as -127 (max(NaN, -127) = -127), +inf as 127, -inf as -127 (as SiLU: NaN ->
 // -127); as fp16 they go through as they are.  With ReLU a NaN becomes 0 before the requantisation.
 //
-// MI355X mapping: the skeleton of conv_slice.hip -- 128 x 128 output tiles (128 x 64 for Cout <= 64), 256 threads = 4
-// waves of 64 x 64 (64 x 32), range-checked 16-byte buffer loads into two register sets, two LDS images of 64 bytes of
-// k per row, one barrier per step, XCD-contiguous tile order, epilogue through per-wave LDS staging -- on the int8
-// matrix cores: v_mfma_i32_32x32x32_i8 with the operand layout of tile_gemm.hip's S8 mode, 64 k-values per step.
+// On the 128-row tile skeleton of csrc/tile_mma.h, on the int8 matrix cores: 64 k-values per step.  Its own: the k-chunk
+// scheme below, and a thread of the epilogue owns 16 (int8 out) or 8 (fp16 out) consecutive channels of one pixel.
 //
 // K-CHUNK SCHEME.  Cin % 32 == 0, not 64: a 64-byte step can straddle a tap (Cin 32, 96, 160) and the last step can
 // be half empty (K = 9 * 96 = 13.5 steps).  A thread moves ONE 16-byte chunk per row and step; chunk j of step t holds
@@ -44,21 +42,10 @@
 // The weight's range check is on the whole buffer, so a chunk behind a row's end would read the next row: its offset is
 // replaced by the beyond-the-buffer address when k >= K.  Both operands of a chunk past K are zero.
 // All of an address goes into the buffer load's VGPR offset (the scalar offset takes no part in the range check).
-#include "gemm_host.h"
+#include "tile_mma.h"
 
 namespace bevops {
 namespace {
-
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef int i32x16_t __attribute__((ext_vector_type(16)));
-
-constexpr int kTM = 128;                       // rows (output pixels) per tile
-constexpr int kTLd = 64 + 16;                  // LDS row: the step's 64 bytes + 16 (conflict-free 16-byte fragment reads)
-constexpr int kEpiStride = 64 * 4 + 16;        // staging row: 64 x 4 bytes + pad
-constexpr int kLds = 2 * (kTM + 128) * kTLd;   // two images of [A rows | W rows]: 40 960 bytes, the fp16 kernel's
-static_assert(kLds >= 4 * 32 * kEpiStride, "epilogue staging must fit in the operand images");
-
-enum { kActNone = 0, kActRelu = 1, kActSilu = 2 };
 
 struct ConvSliceS8Args {
   const void *x, *w, *res;
@@ -73,37 +60,16 @@ struct ConvSliceS8Args {
   float s_aw, s_res, inv_s_out;
 };
 
-// (conv_slice.hip's, unchanged)
-__device__ __forceinline__ float silu_f32(float v) { return v * __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
-
-__device__ __forceinline__ int s8_at(const unsigned *w, int c) {   // signed byte c of a little-endian word array
-  return (int)(w[c >> 2] << (24 - 8 * (c & 3))) >> 24;
-}
-
 // NI: 32-column MFMA blocks per wave: 2 -> 128-column tiles, 1 -> 64-column tiles (Cout <= 64); OUT8: int8 output
 template <int NI, bool OUT8>
 __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p) {
-  constexpr int MJ = 2;                        // 32-row MFMA blocks per wave
-  constexpr int kTN = 64 * NI;
   constexpr int kStepK = 64;                   // k-values (bytes) per step
   __shared__ __attribute__((aligned(16))) char smem[kLds];
   const int M = p.M, N = p.N, K = p.K;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int per_xcd = (p.tiles_total + 7) >> 3;
-  const int logical = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
-  if (logical >= p.tiles_total) return;
-  const int m0 = (logical / p.tiles_n) * kTM, n0 = (logical % p.tiles_n) * kTN;
-  const int r0 = tid >> 2, r1 = r0 + 64;       // 128 rows x 4 chunks of 16 bytes of k
-  const int lchunk = (tid & 3) * 16;           // this thread's chunk: byte position in a step and in an LDS row
-  i32x16_t acc[NI][MJ];
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < MJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0;
-  const int nk = (K + kStepK - 1) / kStepK;
+  const TilePos t(p.tiles_total, p.tiles_n);
+  if (!t.valid) return;
+  const int m0 = t.row_tile * kTM, n0 = t.col * 64 * NI;
+  const int r0 = t.r0, r1 = t.r1, lchunk = t.lchunk;   // lchunk: this thread's chunk, byte position in a step too
   const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.x), 0, p.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w), 0, p.w_bytes, 0x00020000);
   // output row m is pixel (b, yo, xo); its k-values are [tap][Cin] with tap (ky, kx) read from input pixel
@@ -118,29 +84,24 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
     const int yo = pix / p.wout, xo = pix - yo * p.wout;
     const int y = yo * p.stride, x = xo * p.stride;           // centre tap in the input image
     off = (unsigned)((((size_t)b * p.hin + y) * p.win + x) * p.x_pitch);
-    for (int t = 0; t < taps; ++t) {
-      const int yy = y + (t / ksz - pad) * dil, xx = x + (t % ksz - pad) * dil;
-      mk |= (yy >= 0 && yy < p.hin && xx >= 0 && xx < p.win) ? (1u << t) : 0u;
+    for (int tap = 0; tap < taps; ++tap) {
+      const int yy = y + (tap / ksz - pad) * dil, xx = x + (tap % ksz - pad) * dil;
+      mk |= (yy >= 0 && yy < p.hin && xx >= 0 && xx < p.win) ? (1u << tap) : 0u;
     }
   };
   place(m0 + r0, a_off0, tapmask0);
   place(m0 + r1, a_off1, tapmask1);
-  // the position of this thread's chunk in the NEXT gload: global k, and (tap = (ty, tx), channel) = (k / Cin, k % Cin)
+  // the position of this thread's chunk in the NEXT load: global k, and (tap = (ty, tx), channel) = (k / Cin, k % Cin)
   int g_k = lchunk, g_c = lchunk, g_tap = 0, g_ty = 0, g_tx = 0;
   const bool w_ok0 = n0 + r0 < N, w_ok1 = NI == 2 && n0 + r1 < N;
   const unsigned w_row0 = (unsigned)((size_t)(n0 + r0) * K), w_row1 = (unsigned)((size_t)(n0 + r1) * K);
-  uint4 ra0[2], ra1[2], rb0[2], rb1[2];        // two register sets (set = step parity): the loads of two steps in flight
-  auto bload = [](const __amdgpu_buffer_rsrc_t &rs, unsigned voff) {
-    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0));
-  };
   auto wrap = [&]() {                          // one tap further when the channel left the tap
     if (g_c >= cin) {
       g_c -= cin; ++g_tap;
       if (++g_tx == ksz) { g_tx = 0; ++g_ty; }
     }
   };
-  auto gload = [&](auto setc) {
-    constexpr int S = decltype(setc)::value;
+  auto load = [&](TileStage &s) {
     wrap(); wrap();                            // 64 k-values further: at most two taps, Cin >= 32
     // (chunks past K: g_tap >= taps, whose mask bits are clear; g_tap stays below 32 -- at most five steps past K)
     // (in unsigned arithmetic: for a valid tap |.| <= dil (W + 1) x_pitch, which the entry keeps inside 31 bits, and the
@@ -148,63 +109,19 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
     // and drop it)
     const unsigned delta = ((unsigned)(g_ty - pad) * (unsigned)p.win + (unsigned)(g_tx - pad)) * (unsigned)p.dpitch +
                            (unsigned)g_c;
-    ra0[S] = bload(rs_a, (tapmask0 >> g_tap) & 1u ? a_off0 + delta : kGemmOob);
-    ra1[S] = bload(rs_a, (tapmask1 >> g_tap) & 1u ? a_off1 + delta : kGemmOob);
+    s.a0 = bload(rs_a, (tapmask0 >> g_tap) & 1u ? a_off0 + delta : kGemmOob);
+    s.a1 = bload(rs_a, (tapmask1 >> g_tap) & 1u ? a_off1 + delta : kGemmOob);
     const bool kok = g_k < K;                  // K % 16 == 0: the chunk is all in or all out
-    rb0[S] = bload(rs_w, (kok && w_ok0) ? w_row0 + (unsigned)g_k : kGemmOob);
-    if constexpr (NI == 2) rb1[S] = bload(rs_w, (kok && w_ok1) ? w_row1 + (unsigned)g_k : kGemmOob);
+    s.b0 = bload(rs_w, (kok && w_ok0) ? w_row0 + (unsigned)g_k : kGemmOob);
+    if constexpr (NI == 2) s.b1 = bload(rs_w, (kok && w_ok1) ? w_row1 + (unsigned)g_k : kGemmOob);
     g_k += kStepK; g_c += kStepK;
   };
-  auto lstore = [&](int buf, auto setc) {
-    constexpr int S = decltype(setc)::value;
-    char *As = smem + buf * (kTM + 128) * kTLd, *Ws = As + kTM * kTLd;
-    *reinterpret_cast<uint4 *>(As + r0 * kTLd + lchunk) = ra0[S];
-    *reinterpret_cast<uint4 *>(As + r1 * kTLd + lchunk) = ra1[S];
-    *reinterpret_cast<uint4 *>(Ws + r0 * kTLd + lchunk) = rb0[S];
-    if constexpr (NI == 2) *reinterpret_cast<uint4 *>(Ws + r1 * kTLd + lchunk) = rb1[S];
-  };
-  auto compute = [&](int kt) {
-    const char *As = smem + (kt & 1) * (kTM + 128) * kTLd, *Ws = As + kTM * kTLd;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int kk = ks * 32 + (lane >> 5) * 16;
-      // MFMA operand A = the weight rows (output channels n), B = the activation rows (m): a lane's 4 consecutive
-      // accumulator rows are then 4 consecutive channels of one output pixel
-      i32x4_t a[NI], b[MJ];
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-        a[i] = *reinterpret_cast<const i32x4_t *>(Ws + (wn * 32 * NI + i * 32 + (lane & 31)) * kTLd + kk);
-#pragma unroll
-      for (int j = 0; j < MJ; ++j)
-        b[j] = *reinterpret_cast<const i32x4_t *>(As + (wm * 32 * MJ + j * 32 + (lane & 31)) * kTLd + kk);
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-  };
-  using Set0 = std::integral_constant<int, 0>;
-  using Set1 = std::integral_constant<int, 1>;
-  // (loads past the last step are issued too -- beyond-the-buffer addresses, they read as zero -- and so are the LDS writes
-  // of a step that does not exist, into the image nobody reads: no branches, exact wait counts)
-  gload(Set0{});
-  lstore(0, Set0{});
-  gload(Set1{});
-  gload(Set0{});
-  __syncthreads();
-  auto step = [&](int kt, auto next_set) {
-    lstore((kt + 1) & 1, next_set);
-    gload(next_set);
-    compute(kt);
-    __syncthreads();
-  };
-  for (int kt = 0; kt < nk; kt += 2) {         // (an odd step count runs one step on zeros: adds nothing)
-    step(kt, Set1{});
-    step(kt + 1, Set0{});
-  }
-  // ---- epilogue.  acc[i][j][4 g + c]: n = n0 + wn*32*NI + i*32 + 8 g + 4 (lane >> 5) + c,
-  //                                     m = m0 + wm*64 + j*32 + (lane & 31)
+  BEVOPS_TILE_K_LOOP(smem, t, i32x16_t, NI, (K + kStepK - 1) / kStepK, acc, load)
+  // ---- epilogue, the transpose of tile_mma.h's tile_epilogue STATED HERE: through the template the int8 epilogue compiles
+  // to 50 - 120 more instructions and the short 1 x 1 layers lose 0.2 us (design/dense.md).
+  // acc[i][j][4 g + c]: n = n0 + wn*32*NI + i*32 + 8 g + 4 (lane >> 5) + c, m = m0 + wm*64 + j*32 + (lane & 31)
   // (the barrier that ended the last step also freed both LDS images)
+  const int lane = t.lane, wave = t.wave, wm = t.wm, wn = t.wn;
   constexpr int kCW = OUT8 ? 16 : 8;           // consecutive channels a thread owns: one 16-byte store
   constexpr int kCH = 32 * NI / kCW;           // chunks per row of the wave's 32 NI columns
   constexpr int kRows = 64 / kCH;              // staged rows per read-back pass
@@ -224,7 +141,7 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
     bs[c] = (p.bias && col_ok) ? p.bias[ncol + c] : 0.f;
   }
 #pragma unroll
-  for (int j = 0; j < MJ; ++j) {
+  for (int j = 0; j < kTMJ; ++j) {
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -236,7 +153,7 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
 #pragma unroll
     for (int it = 0; it < kIT; ++it) {
       const int row = it * kRows + lane / kCH;
-      const int m = m0 + wm * 32 * MJ + j * 32 + row;
+      const int m = m0 + wm * 32 * kTMJ + j * 32 + row;
       i32x4_t s[kCW / 4];
 #pragma unroll
       for (int q = 0; q < kCW / 4; ++q)
@@ -285,12 +202,8 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
         for (int c = 0; c < kCW; ++c) v[c] = __builtin_fmaf((float)s8_at(rq, c), p.s_res, v[c]);
       }
       if constexpr (OUT8) {
-        unsigned pk[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-          const float t = v[c] * p.inv_s_out;
-          pk[c >> 2] |= ((unsigned)(int)fminf(fmaxf(rintf(t), -127.f), 127.f) & 0xffu) << (8 * (c & 3));
-        }
+        unsigned pk[4];
+        requant_s8_pack(v, p.inv_s_out, pk);
         *reinterpret_cast<uint4 *>(static_cast<signed char *>(p.out) + (size_t)m * p.out_pitch + ncol) =
             make_uint4(pk[0], pk[1], pk[2], pk[3]);
       } else {
@@ -303,8 +216,6 @@ __global__ __launch_bounds__(256, 3) void conv_slice_s8_kernel(ConvSliceS8Args p
     __builtin_amdgcn_wave_barrier();
   }
 }
-
-inline bool bad_scale(float s) { return !(s > 0.f) || !(s <= 3.4028234663852886e38f); }   // non-positive, NaN or inf
 
 }  // namespace
 }  // namespace bevops
@@ -362,12 +273,9 @@ extern "C" int bevops_conv_slice_s8_ex2(const void *x_q, int x_pitch, float scal
   p.s_aw = scale_a * scale_w;
   p.s_res = residual_q ? scale_res : 0.f;
   p.inv_s_out = out8 ? 1.f / scale_out : 1.f;
+  dim3 grid;
+  if (!tile_grid(rows, Cout, 1, &p.tiles_n, &p.tiles_total, &grid)) return BEVOPS_NOT_SUPPORTED;
   const bool narrow = Cout <= 64;
-  p.tiles_n = (Cout + (narrow ? 64 : 128) - 1) / (narrow ? 64 : 128);
-  const long long tiles = (long long)p.tiles_n * (long long)((rows + kTM - 1) / kTM);
-  if (tiles > 0x3fffffffLL) return BEVOPS_NOT_SUPPORTED;
-  p.tiles_total = (int)tiles;
-  const dim3 grid((unsigned)((tiles + 7) / 8 * 8));
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (out8) {
     if (narrow) hipLaunchKernelGGL((conv_slice_s8_kernel<1, true>), grid, dim3(256), 0, st, p);

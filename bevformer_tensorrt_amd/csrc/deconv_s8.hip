@@ -19,29 +19,15 @@
 // Non-finite values as bevops_conv_slice_s8: a NaN v leaves as -127, +inf as 127, -inf as -127 (int8); as fp16 they go
 // through as they are; with ReLU a NaN becomes 0 before the requantisation.
 //
-// MI355X mapping: deconv.hip's geometry on conv_slice_s8.hip's operands.  128 x 128 output tiles (128 x 64 for
-// Cout <= 64), 256 threads = 4 waves of 64 x 64 (64 x 32), v_mfma_i32_32x32x32_i8, 64 int8 k-values per step and row;
-// operands register-staged through range-checked 16-byte buffer loads (rows past M / N and taps outside the image read
-// as zero, no branches) in two register sets, written to the other of two LDS images of (128 + 128) rows x (64 + 16)
-// bytes while the current one is multiplied: one barrier per step.  Cin % 64 == 0, so a step never straddles a tap: a
-// tap is a block-uniform address delta plus a per-row validity bit.  All of an address goes into the buffer load's VGPR
-// offset (the scalar offset takes no part in the range check).  Tile order [row tile][parity][column tile], the 8 XCDs
-// taking contiguous runs of it: the 4 * tiles_n blocks that read the same 128 input pixels run back to back on one XCD.
-// Epilogue through per-wave LDS staging: a thread owns 16 (int8 out) or 8 (fp16 out) consecutive channels of one
-// output pixel and stores them as one 16-byte vector.
-#include "gemm_host.h"
+// deconv.hip's geometry on conv_slice_s8.hip's operands, on the 128-row tile skeleton of csrc/tile_mma.h: 64 int8 k-values
+// per step.  Cin % 64 == 0, so a step never straddles a tap: a tap is a block-uniform address delta plus a per-row
+// validity bit.  All of an address goes into the buffer load's VGPR offset (the scalar offset takes no part in the range
+// check).  Tile order [row tile][parity][column tile] as deconv.hip.  A thread of the epilogue owns 16 (int8 out) or 8
+// (fp16 out) consecutive channels of one output pixel and stores them as one 16-byte vector.
+#include "tile_mma.h"
 
 namespace bevops {
 namespace {
-
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef int i32x16_t __attribute__((ext_vector_type(16)));
-
-constexpr int kTM = 128;                       // rows (input pixels) per tile
-constexpr int kTLd = 64 + 16;                  // LDS row: the step's 64 bytes + 16 (conflict-free 16-byte fragment reads)
-constexpr int kEpiStride = 64 * 4 + 16;        // staging row: 64 x 4 bytes + pad
-constexpr int kLds = 2 * (kTM + 128) * kTLd;   // two images of [A rows | W rows]; the epilogue's 4 x 32 staging rows fit
-static_assert(kLds >= 4 * 32 * kEpiStride, "epilogue staging must fit in the operand images");
 
 struct DeconvS8Args {
   const void *x, *w;
@@ -56,32 +42,17 @@ struct DeconvS8Args {
 // NI: 32-column MFMA blocks per wave: 2 -> 128-column tiles, 1 -> 64-column tiles (Cout <= 64); OUT8: int8 output
 template <int NI, bool OUT8>
 __global__ __launch_bounds__(256, 3) void deconv4x4s2_s8_kernel(DeconvS8Args p) {
-  constexpr int MJ = 2;                        // 32-row MFMA blocks per wave
-  constexpr int kTN = 64 * NI;
   constexpr int kStepK = 64;                   // k-values (bytes) per step
   __shared__ __attribute__((aligned(16))) char smem[kLds];
   const int M = p.M, N = p.N, K = p.K;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int per_xcd = (p.tiles_total + 7) >> 3;
-  const int logical = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
-  if (logical >= p.tiles_total) return;
-  const int ct = logical % p.tiles_n, rp = logical / p.tiles_n;
-  const int par = rp & 3, py = par >> 1, px = par & 1;
-  const int m0 = (rp >> 2) * kTM, n0 = ct * kTN;
-  const int r0 = tid >> 2, r1 = r0 + 64;       // 128 rows x 4 chunks of 16 bytes of k
-  const int lchunk = (tid & 3) * 16;           // this thread's chunk: byte position in a step and in an LDS row
-  i32x16_t acc[NI][MJ];
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < MJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0;
-  const int nk = K / kStepK;                   // a multiple of 4 (K = 4 Cin, Cin % 64 == 0)
+  const TilePos t(p.tiles_total, p.tiles_n);    // [row tile][parity][column tile]: row_tile counts (row tile, parity)
+  if (!t.valid) return;
+  const int par = t.row_tile & 3, py = par >> 1, px = par & 1;
+  const int m0 = (t.row_tile >> 2) * kTM, n0 = t.col * 64 * NI;
+  const int r0 = t.r0, r1 = t.r1, lchunk = t.lchunk;   // lchunk: this thread's chunk, byte position in a step too
   const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.x), 0, p.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w), 0, p.w_bytes, 0x00020000);
-  // row m is input pixel (b, y, x); tap t = (dy, dx) of this block's parity reads pixel (y - 1 + py + dy, x - 1 + px + dx),
+  // row m is input pixel (b, y, x); tap (dy, dx) of this block's parity reads pixel (y - 1 + py + dy, x - 1 + px + dx),
   // zero outside the image
   const int cin = p.cin, per = p.h * p.wd;
   unsigned a_off0, a_off1, tapmask0, tapmask1;
@@ -92,83 +63,34 @@ __global__ __launch_bounds__(256, 3) void deconv4x4s2_s8_kernel(DeconvS8Args p) 
     const int y = pix / p.wd, x = pix - y * p.wd;
     off = (unsigned)((((size_t)b * p.h + y) * p.wd + x) * cin + lchunk);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int yy = y - 1 + py + (t >> 1), xx = x - 1 + px + (t & 1);
-      mk |= (yy >= 0 && yy < p.h && xx >= 0 && xx < p.wd) ? (1u << t) : 0u;
+    for (int tap = 0; tap < 4; ++tap) {
+      const int yy = y - 1 + py + (tap >> 1), xx = x - 1 + px + (tap & 1);
+      mk |= (yy >= 0 && yy < p.h && xx >= 0 && xx < p.wd) ? (1u << tap) : 0u;
     }
   };
   place(m0 + r0, a_off0, tapmask0);
   place(m0 + r1, a_off1, tapmask1);
-  int g_tap = 0, g_c = 0, g_k = 0;             // the (tap, channel) position and the k of the NEXT gload
+  int g_tap = 0, g_c = 0, g_k = 0;             // the (tap, channel) position and the k of the NEXT load
   const size_t wrow = (size_t)par * N;         // first weight row of this parity class
   const bool w_ok0 = n0 + r0 < N, w_ok1 = NI == 2 && n0 + r1 < N;
   const unsigned w_off0 = (unsigned)((wrow + n0 + r0) * K + lchunk), w_off1 = (unsigned)((wrow + n0 + r1) * K + lchunk);
-  uint4 ra0[2], ra1[2], rb0[2], rb1[2];        // two register sets (set = step parity): the loads of two steps in flight
-  auto bload = [](const __amdgpu_buffer_rsrc_t &rs, unsigned voff) {
-    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0));
-  };
-  auto gload = [&](auto setc) {
-    constexpr int S = decltype(setc)::value;
+  auto load = [&](TileStage &s) {
     // (steps past the last one: g_tap >= 4, whose mask bits are clear; g_tap stays below 8 -- three steps past K)
     const unsigned delta = (unsigned)((((g_tap >> 1) + py - 1) * p.wd + ((g_tap & 1) + px - 1)) * cin + g_c);
-    ra0[S] = bload(rs_a, (tapmask0 >> g_tap) & 1u ? a_off0 + delta : kGemmOob);
-    ra1[S] = bload(rs_a, (tapmask1 >> g_tap) & 1u ? a_off1 + delta : kGemmOob);
+    s.a0 = bload(rs_a, (tapmask0 >> g_tap) & 1u ? a_off0 + delta : kGemmOob);
+    s.a1 = bload(rs_a, (tapmask1 >> g_tap) & 1u ? a_off1 + delta : kGemmOob);
     const bool kok = g_k < K;                  // a step behind a row's end would read the next row
-    rb0[S] = bload(rs_w, (kok && w_ok0) ? w_off0 + (unsigned)g_k : kGemmOob);
-    if constexpr (NI == 2) rb1[S] = bload(rs_w, (kok && w_ok1) ? w_off1 + (unsigned)g_k : kGemmOob);
+    s.b0 = bload(rs_w, (kok && w_ok0) ? w_off0 + (unsigned)g_k : kGemmOob);
+    if constexpr (NI == 2) s.b1 = bload(rs_w, (kok && w_ok1) ? w_off1 + (unsigned)g_k : kGemmOob);
     g_k += kStepK; g_c += kStepK;
     if (g_c >= cin) { g_c = 0; ++g_tap; }
   };
-  auto lstore = [&](int buf, auto setc) {
-    constexpr int S = decltype(setc)::value;
-    char *As = smem + buf * (kTM + 128) * kTLd, *Ws = As + kTM * kTLd;
-    *reinterpret_cast<uint4 *>(As + r0 * kTLd + lchunk) = ra0[S];
-    *reinterpret_cast<uint4 *>(As + r1 * kTLd + lchunk) = ra1[S];
-    *reinterpret_cast<uint4 *>(Ws + r0 * kTLd + lchunk) = rb0[S];
-    if constexpr (NI == 2) *reinterpret_cast<uint4 *>(Ws + r1 * kTLd + lchunk) = rb1[S];
-  };
-  auto compute = [&](int kt) {
-    const char *As = smem + (kt & 1) * (kTM + 128) * kTLd, *Ws = As + kTM * kTLd;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int kk = ks * 32 + (lane >> 5) * 16;
-      // MFMA operand A = the weight rows (output channels n), B = the activation rows (m): a lane's 4 consecutive
-      // accumulator rows are then 4 consecutive channels of one output pixel
-      i32x4_t a[NI], b[MJ];
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-        a[i] = *reinterpret_cast<const i32x4_t *>(Ws + (wn * 32 * NI + i * 32 + (lane & 31)) * kTLd + kk);
-#pragma unroll
-      for (int j = 0; j < MJ; ++j)
-        b[j] = *reinterpret_cast<const i32x4_t *>(As + (wm * 32 * MJ + j * 32 + (lane & 31)) * kTLd + kk);
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-  };
-  using Set0 = std::integral_constant<int, 0>;
-  using Set1 = std::integral_constant<int, 1>;
-  // (loads past the last step are issued too -- beyond-the-buffer addresses, they read as zero -- and so are the LDS writes
-  // of a step that does not exist, into the image nobody reads: no branches, exact wait counts)
-  gload(Set0{});
-  lstore(0, Set0{});
-  gload(Set1{});
-  gload(Set0{});
-  __syncthreads();
-  auto step = [&](int kt, auto next_set) {
-    lstore((kt + 1) & 1, next_set);
-    gload(next_set);
-    compute(kt);
-    __syncthreads();
-  };
-  for (int kt = 0; kt < nk; kt += 2) {
-    step(kt, Set1{});
-    step(kt + 1, Set0{});
-  }
-  // ---- epilogue.  acc[i][j][4 g + c]: n = n0 + wn*32*NI + i*32 + 8 g + 4 (lane >> 5) + c,
-  //                                     m = m0 + wm*64 + j*32 + (lane & 31)
+  BEVOPS_TILE_K_LOOP(smem, t, i32x16_t, NI, K / kStepK, acc, load)   // a multiple of 4 steps (K = 4 Cin, Cin % 64 == 0)
+  // ---- epilogue, the transpose of tile_mma.h's tile_epilogue STATED HERE: through the template the int8 epilogue compiles
+  // to 50 - 120 more instructions and the short 1 x 1 layers lose 0.2 us (design/dense.md).
+  // acc[i][j][4 g + c]: n = n0 + wn*32*NI + i*32 + 8 g + 4 (lane >> 5) + c, m = m0 + wm*64 + j*32 + (lane & 31)
   // (the barrier that ended the last step also freed both LDS images)
+  const int lane = t.lane, wave = t.wave, wm = t.wm, wn = t.wn;
   constexpr int kCW = OUT8 ? 16 : 8;           // consecutive channels a thread owns: one 16-byte store
   constexpr int kCH = 32 * NI / kCW;           // chunks per row of the wave's 32 NI columns
   constexpr int kRows = 64 / kCH;              // staged rows per read-back pass
@@ -184,7 +106,7 @@ __global__ __launch_bounds__(256, 3) void deconv4x4s2_s8_kernel(DeconvS8Args p) 
     bs[c] = (p.bias && col_ok) ? p.bias[ncol + c] : 0.f;
   }
 #pragma unroll
-  for (int j = 0; j < MJ; ++j) {
+  for (int j = 0; j < kTMJ; ++j) {
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -196,7 +118,7 @@ __global__ __launch_bounds__(256, 3) void deconv4x4s2_s8_kernel(DeconvS8Args p) 
 #pragma unroll
     for (int it = 0; it < kIT; ++it) {
       const int row = it * kRows + lane / kCH;
-      const int m = m0 + wm * 32 * MJ + j * 32 + row;
+      const int m = m0 + wm * 32 * kTMJ + j * 32 + row;
       i32x4_t s[kCW / 4];
 #pragma unroll
       for (int q = 0; q < kCW / 4; ++q)
@@ -213,12 +135,8 @@ __global__ __launch_bounds__(256, 3) void deconv4x4s2_s8_kernel(DeconvS8Args p) 
       const int y = pix / p.wd, x = pix - y * p.wd;
       const size_t opix = ((size_t)b * (2 * p.h) + 2 * y + py) * (2 * p.wd) + 2 * x + px;
       if constexpr (OUT8) {
-        unsigned pk[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-          const float t = v[c] * p.inv_s_out;
-          pk[c >> 2] |= ((unsigned)(int)fminf(fmaxf(rintf(t), -127.f), 127.f) & 0xffu) << (8 * (c & 3));
-        }
+        unsigned pk[4];
+        requant_s8_pack(v, p.inv_s_out, pk);
         *reinterpret_cast<uint4 *>(static_cast<signed char *>(p.out) + opix * N + ncol) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
       } else {
         uint4 o;
@@ -230,8 +148,6 @@ __global__ __launch_bounds__(256, 3) void deconv4x4s2_s8_kernel(DeconvS8Args p) 
     __builtin_amdgcn_wave_barrier();
   }
 }
-
-inline bool bad_scale(float s) { return !(s > 0.f) || !(s <= 3.4028234663852886e38f); }   // non-positive, NaN or inf
 
 }  // namespace
 }  // namespace bevops
@@ -261,12 +177,9 @@ extern "C" int bevops_deconv4x4s2_s8(const void *x_q, float scale_a, const void 
   p.cin = Cin; p.h = H; p.wd = W;
   p.s_aw = scale_a * scale_w;
   p.inv_s_out = out8 ? 1.f / scale_out : 1.f;
+  dim3 grid;
+  if (!tile_grid(rows, Cout, 4, &p.tiles_n, &p.tiles_total, &grid)) return BEVOPS_NOT_SUPPORTED;
   const bool narrow = Cout <= 64;
-  p.tiles_n = (Cout + (narrow ? 64 : 128) - 1) / (narrow ? 64 : 128);
-  const long long tiles = 4ll * p.tiles_n * (long long)((rows + kTM - 1) / kTM);
-  if (tiles > 0x3fffffffLL) return BEVOPS_NOT_SUPPORTED;
-  p.tiles_total = (int)tiles;
-  const dim3 grid((unsigned)((tiles + 7) / 8 * 8));
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (out8) {
     if (narrow) hipLaunchKernelGGL((deconv4x4s2_s8_kernel<1, true>), grid, dim3(256), 0, st, p);

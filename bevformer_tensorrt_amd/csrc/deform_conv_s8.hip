@@ -28,6 +28,7 @@
 // the 16 rows a ds_read_b128 lane group touches start on 16 different slots of the 64-bank row.
 // The epilogue goes through LDS into whole 16-byte channel vectors.  Every byte offset is 64-bit.
 #include "common.h"
+#include "gemm_host.h"
 
 namespace bevops {
 namespace {
@@ -226,8 +227,6 @@ __global__ __launch_bounds__(kDfqThreads) void deform_conv3x3_s8_kernel(const si
   }
 }
 
-inline bool dfq_bad_scale(float s) { return !(s > 0.f) || !(s <= 3.4028234663852886e38f); }   // non-positive, NaN or inf
-
 }  // namespace
 }  // namespace bevops
 
@@ -247,7 +246,7 @@ extern "C" int bevops_deform_conv3x3_nhwc_s8(const void *x_q, int x_pitch, float
   if (x_pitch < Cin || x_pitch % 16 != 0) return BEVOPS_BAD_PARAM;
   // (16-byte output vectors: 8 elements of fp16, 16 of int8 -- and of a dtype the next check refuses)
   if (out_pitch < Cout || out_pitch % (out_dtype == BEVOPS_F16 ? 8 : 16) != 0) return BEVOPS_BAD_PARAM;
-  if (dfq_bad_scale(scale_a) || dfq_bad_scale(scale_w) || (out_dtype == BEVOPS_I8 && dfq_bad_scale(scale_out)))
+  if (bad_scale(scale_a) || bad_scale(scale_w) || (out_dtype == BEVOPS_I8 && bad_scale(scale_out)))
     return BEVOPS_BAD_PARAM;
   if (out_dtype != BEVOPS_I8 && out_dtype != BEVOPS_F16) return BEVOPS_NOT_SUPPORTED;
   const bool out8 = out_dtype == BEVOPS_I8;

@@ -40,6 +40,9 @@ inline bool gemm_over_limit(unsigned long long rows, int cols, int elem_bytes) {
 
 inline bool misaligned(const void *p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
+// a quantisation scale the int8 entries refuse: non-positive, NaN or inf
+inline bool bad_scale(float s) { return !(s > 0.f) || !(s <= 3.4028234663852886e38f); }
+
 // Destination table of the _dst launches: column range [col_begin, col_end) of the launch is a pitched matrix of its own
 // with an identity of its own.  Passed to the kernels by value.
 constexpr int kGemmMaxDst = 8;

@@ -13,6 +13,7 @@
 //    in LDS.  (float)sum rounds to nearest even (exact for |sum| <= 2^24), then one fp32 product, one IEEE division and
 //    one rounding to binary16.
 #include "common.h"
+#include "gemm_host.h"
 
 namespace bevops {
 namespace {
@@ -89,7 +90,6 @@ __global__ __launch_bounds__(256) void global_avgpool_s8_kernel(const signed cha
 
 inline bool off16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 inline bool bad_pitch16(int pitch, int c) { return pitch < c || pitch % 16 != 0; }
-inline bool bad_scale(float s) { return !(s > 0.f) || !(s <= 3.4028234663852886e38f); }   // non-positive, NaN or inf
 
 }  // namespace
 }  // namespace bevops

@@ -36,22 +36,18 @@
 // output row m is pixel (b, yo, xo), its k-values are [tap][Cin]; a tap moves the row's base address by a
 // block-uniform delta and a per-row validity bit (zero padding) selects the beyond-the-buffer address; a stride
 // only changes the row -> pixel map.  No column buffer, no sub-sampled copy.
-#include "gemm_host.h"
+#include "tile_mma.h"
 
 namespace bevops {
 namespace {
 
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef int i32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
 enum { kS8 = 0, kF16Q = 1, kF16 = 2 };
 
-constexpr int kTM = 128;   // (bytes of k per row and step: template parameter KB; LDS rows are KB + 16: conflict-free b128 reads)
+// From tile_mma.h: the layout constants, the vector types, mma, sum_bits and the grid.  This file keeps its own loop
+// (F16Q's single set and quantise-on-store, the early identity request, DST, SRC2), and its own statement of the tile
+// position, bload and the requantise-and-pack loop: through the header's they compile to reordered, not identical, code.
 constexpr float kQMagic = 12582912.f;          // 1.5 * 2^23: bits 0x4B400000, low byte 0
 constexpr int kQMagicBits = 0x4B400000;
-constexpr int kEpiStride = 64 * 4 + 16;        // staging row: 64 x 4 bytes + pad
 
 __device__ __forceinline__ unsigned quant4(unsigned h01, unsigned h23, float r) {
   int b0 = __float_as_int(__builtin_fmaf(h2f_lo(h01), r, kQMagic));
@@ -66,9 +62,6 @@ __device__ __forceinline__ unsigned quant4(unsigned h01, unsigned h23, float r) 
   return __builtin_amdgcn_perm((unsigned)b1, (unsigned)b0, 0x0c0c0400u) |
          __builtin_amdgcn_perm((unsigned)b3, (unsigned)b2, 0x04000c0cu);
 }
-
-__device__ __forceinline__ int sum_bits(float v) { return __float_as_int(v); }
-__device__ __forceinline__ int sum_bits(int v) { return v; }
 
 __device__ __forceinline__ uint4 quant16(const uint4 &lo, const uint4 &hi, float r) {
   return make_uint4(quant4(lo.x, lo.y, r), quant4(lo.z, lo.w, r), quant4(hi.x, hi.y, r), quant4(hi.z, hi.w, r));
@@ -321,13 +314,7 @@ __device__ __forceinline__ void tile_gemm_body(const TileArgs &p, const GemmDstT
 #pragma unroll
       for (int i = 0; i < NI; ++i)
 #pragma unroll
-        for (int j = 0; j < MJ; ++j) {
-          if constexpr (MODE == kF16)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[i]),
-                                                               __builtin_bit_cast(f16x8_t, b[j]), acc[i][j], 0, 0, 0);
-          else
-            acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < MJ; ++j) acc[i][j] = mma(a[i], b[j], acc[i][j]);
     }
   };
   // (loads past the last step are issued too -- beyond-the-buffer addresses, they read as zero -- and so are
@@ -493,13 +480,7 @@ bool tile_plan(TileArgs &p, dim3 &grid, const GemmCallS8 &c, const ConvGeom &cg,
   // them): 64-row tiles (four blocks per CU: 3-10 % SLOWER on every base-model layer and flavour,
   // profiles/r04/tile_rows_ab.jsonl) and 128-byte k-steps for the int8 chain's plain GEMMs (bit-identical, slower: a
   // step costs 0.53 us whatever it holds, profiles/r04/tile_wide_ab.jsonl)
-  const int tn = c.n <= 64 ? 64 : 128;
-  p.tiles_n = (c.n + tn - 1) / tn;
-  const long long tiles = (long long)p.tiles_n * ((c.m + kTM - 1) / kTM);
-  if (tiles > 0x3fffffffLL) return false;
-  p.tiles_total = (int)tiles;
-  grid = dim3((unsigned)((tiles + 7) / 8 * 8));
-  return true;
+  return tile_grid((unsigned long long)c.m, c.n, 1, &p.tiles_n, &p.tiles_total, &grid);
 }
 
 template <int MODE>
