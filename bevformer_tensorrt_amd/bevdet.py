@@ -29,6 +29,7 @@ import torch.nn as nn
 from . import functions as _hip_ops
 from .functions import dispatch as _dispatch
 from .functions.multi_scale_deformable_attn import _TensorCache
+from .graph_runner import capture
 
 # BEVDet(..., bev_half=...): "torch" = the framework statements between the image neck and the detections (depth_net
 # through the library, softmax / slice / layout copies, F.interpolate + torch.cat, the heads' narrow convolutions
@@ -809,15 +810,7 @@ class BEVDetRunner:
         return out
 
     def _capture(self, raw=False):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):       # warm-up on the capture stream (allocations, library algorithm search)
-            for _ in range(2):
-                self._forward(raw)
-        torch.cuda.current_stream().wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            outs = self._forward(raw)
+        graph, outs = capture(lambda: self._forward(raw))
         if raw:
             self._graph_raw, self._outs_raw = graph, outs
         else:

@@ -30,6 +30,8 @@ from . import functions as _hip_ops
 from .functions import dispatch as _dispatch
 from .functions.deconv import deconv_packed_weight
 from .functions.multi_scale_deformable_attn import _TensorCache
+from .functions.image import centernet_test_geometry
+from .graph_runner import Detect2DRunner
 
 # model / test_cfg of configs/centernet/centernet_resnet18_dcnv2_140e_coco.py:9-36
 CENTERNET_R18 = dict(blocks=(2, 2, 2, 2), neck_channels=(256, 128, 64), num_classes=80, feat_channel=64,
@@ -258,7 +260,7 @@ class CenterNet(nn.Module):
                                     local_maximum_kernel=cfg["local_maximum_kernel"])
 
 
-class CenterNetRunner:
+class CenterNetRunner(Detect2DRunner):
     """`forward` + `centernet_decode(padded=True)` captured once for images of one shape: `step(image)` copies the image
     into the static input buffer (unless it IS that buffer), replays the graph and returns the fixed-size (boxes
     [B, topk, 4], scores [B, topk], labels [B, topk] int32, count [B] int32) with no host synchronisation; the boxes are
@@ -271,23 +273,8 @@ class CenterNetRunner:
     must be that pipeline's padded size.  Its boxes are in the RAW image's pixels: the geometry's border and
     scale_factor go to centernet_decode."""
 
-    def __init__(self, model, batch, height, width, graph=True, clone_outputs=True, raw_size=None, img_scale=None):
-        if height % 32 or width % 32:
-            raise ValueError("CenterNetRunner: height and width are multiples of 32")
-        p = next(model.parameters())
-        self.model, self.use_graph, self.clone_outputs = model, graph, clone_outputs
-        self.image_buffer = torch.zeros((batch, 3, height, width), device=p.device, dtype=p.dtype)
-        self._graph, self._outs, self._last = None, None, None
-        self.raw_size, self.geometry, self.raw_buffer, self._graph_raw, self._outs_raw = None, None, None, None, None
-        if raw_size is not None:
-            from .functions.image import DETECT2D_IMAGE_PIPELINES, centernet_test_geometry
-            self.pipeline = DETECT2D_IMAGE_PIPELINES["centernet"]
-            self.raw_size = (int(raw_size[0]), int(raw_size[1]))
-            self.geometry = centernet_test_geometry(*self.raw_size, img_scale or self.pipeline["img_scale"])
-            if tuple(self.geometry["pad_shape"][:2]) != (height, width):
-                raise ValueError(f"raw_size {self.raw_size}: CenterNet's test pipeline gives a network input of "
-                                 f"{tuple(self.geometry['pad_shape'][:2])}, the runner was asked for {(height, width)}")
-            self.raw_buffer = torch.zeros((batch,) + self.raw_size + (3,), device=p.device, dtype=torch.uint8)
+    _detector, _heads, _pipeline = "CenterNet", 3, "centernet"   # (heat, wh, off, then the four of the decode)
+    _geometry = staticmethod(centernet_test_geometry)
 
     def _forward(self, raw=False):
         from .functions.decode2d import centernet_decode
@@ -301,59 +288,3 @@ class CenterNetRunner:
         heat, wh, off = self.model(self.image_buffer)
         return (heat, wh, off) + tuple(centernet_decode(heat, wh, off, cfg["topk"], self.image_buffer.shape[2:],
                                                         cfg["local_maximum_kernel"], border, scale, padded=True))
-
-    def _capture(self, raw=False):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):       # warm-up on the capture stream (allocations, packed and merged operands)
-            for _ in range(2):
-                self._forward(raw)
-        torch.cuda.current_stream().wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            outs = self._forward(raw)
-        if raw:
-            self._graph_raw, self._outs_raw = graph, outs
-        else:
-            self._graph, self._outs = graph, outs
-
-    def step(self, image):
-        if tuple(image.shape) != tuple(self.image_buffer.shape):
-            raise ValueError(f"the runner was built for images {tuple(self.image_buffer.shape)}")
-        if image.data_ptr() != self.image_buffer.data_ptr():
-            self.image_buffer.copy_(image, non_blocking=True)
-        if not self.use_graph:
-            self._outs = self._forward()
-        else:
-            if self._graph is None:
-                self._capture()
-            self._graph.replay()
-        self._last = self._outs
-        outs = self._outs[3:]
-        return tuple(t.clone() for t in outs) if self.clone_outputs and self.use_graph else outs
-
-    def step_raw(self, raw):
-        """`step` from the RAW camera images [B, H0, W0, 3] uint8 BGR on the device (raw_size=(H0, W0) at construction;
-        passing `raw_buffer` itself saves the copy): the letterbox launch, the network and the decode with the
-        geometry's border and scale_factor as one graph of its own.  The boxes are in the raw image's pixels."""
-        if self.raw_size is None:
-            raise RuntimeError("step_raw needs CenterNetRunner(..., raw_size=(H0, W0))")
-        if raw.dtype != torch.uint8 or tuple(raw.shape) != tuple(self.raw_buffer.shape):
-            raise ValueError(f"raw must be uint8 {tuple(self.raw_buffer.shape)}")
-        if raw.data_ptr() != self.raw_buffer.data_ptr():
-            self.raw_buffer.copy_(raw, non_blocking=True)
-        if not self.use_graph:
-            self._outs_raw = self._forward(True)
-        else:
-            if self._graph_raw is None:
-                self._capture(True)
-            self._graph_raw.replay()
-        self._last = self._outs_raw
-        outs = self._outs_raw[3:]
-        return tuple(t.clone() for t in outs) if self.clone_outputs and self.use_graph else outs
-
-    @property
-    def head_outputs(self):
-        """(center_heatmap_preds, wh_preds, offset_preds) of the last `step` / `step_raw`: the graph's static tensors,
-        overwritten by the next one."""
-        return None if self._last is None else self._last[:3]

@@ -6,20 +6,10 @@
 // BGR -> RGB swap), zero padding at the bottom / right to [Hp, Wp], channel-first planes or
 // channels-last rows, fp16 or fp32 out.  53 MB written per base frame instead of four
 // host-side numpy passes and a host-to-device copy of fp32 planes.  Not a reference plugin.
-#include "common.h"
+#include "image_resample.h"   // to_out
 
 namespace bevops {
 namespace {
-
-// float -> output type as its OWN rounding step: a plain cast lets the compiler fold the multiply and
-// the conversion into one v_fma_mixlo_f16 (single rounding of the exact product), while the
-// reference multiplies in float32 and converts afterwards
-__device__ __forceinline__ float to_out(float v, float *) { return v; }
-__device__ __forceinline__ __half to_out(float v, __half *) {
-  unsigned r;
-  asm("v_cvt_f16_f32 %0, %1" : "=v"(r) : "v"(v));
-  return __ushort_as_half((unsigned short)r);
-}
 
 template <typename In, typename Out, bool NHWC>
 __global__ __launch_bounds__(256) void image_normalize_pad_kernel(const In *__restrict__ img, Out *__restrict__ out,

@@ -13,7 +13,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "common.h"
+#include "image_resample.h"   // to_out
 
 namespace bevops {
 namespace {
@@ -145,13 +145,6 @@ size_t plan_words(const Geometry &g) {
 }
 
 // ---------------------------------------------------------------- device
-__device__ __forceinline__ float to_out(float v, float *) { return v; }
-__device__ __forceinline__ __half to_out(float v, __half *) {   // a rounding step of its own (csrc/image.hip)
-  unsigned r;
-  asm("v_cvt_f16_f32 %0, %1" : "=v"(r) : "v"(v));
-  return __ushort_as_half((unsigned short)r);
-}
-
 __device__ __forceinline__ int clip8(int acc) {
   const int v = acc >> kPrecBits;                  // arithmetic shift, as C's on Pillow's int
   return v < 0 ? 0 : (v > 255 ? 255 : v);

@@ -16,6 +16,22 @@ def padded_size(h, w, divisor=32):
     return -(-h // divisor) * divisor, -(-w // divisor) * divisor
 
 
+def _dense_out(out, shape, dtype, device, channels_last, any_gpu=False):
+    """`out` if given, after the check that it is a dense `shape` tensor in the asked memory format on `device` (any_gpu:
+    on any GPU); else a new one of `dtype`."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device,
+                           memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    if tuple(out.shape) != shape or not (out.is_cuda if any_gpu else out.device == device) or not (
+            out.is_contiguous(memory_format=torch.channels_last) if channels_last else out.is_contiguous()):
+        raise ValueError(f"out must be a dense [N, 3, {shape[2]}, {shape[3]}] tensor on the GPU in the requested layout")
+    return out
+
+
+def _double3(values):
+    return (ctypes.c_double * 3)(*[float(v) for v in values])
+
+
 def image_normalize_pad(images, mean=None, std=None, to_rgb=False, size_divisor=32, dtype=torch.float16,
                         channels_last=False, out=None):
     """images [N, H0, W0, 3] uint8 or float32 on the GPU (BGR, as cv2 loads them) ->
@@ -28,14 +44,8 @@ def image_normalize_pad(images, mean=None, std=None, to_rgb=False, size_divisor=
     N, H0, W0, _ = images.shape
     Hp, Wp = padded_size(H0, W0, size_divisor)
     images = images.contiguous()
-    if out is not None and (tuple(out.shape) != (N, 3, Hp, Wp) or not out.is_cuda or not (
-            out.is_contiguous(memory_format=torch.channels_last) if channels_last else out.is_contiguous())):
-        raise ValueError(f"out must be a dense [N, 3, {Hp}, {Wp}] tensor on the GPU in the requested layout")
-    if out is None:
-        out = torch.empty((N, 3, Hp, Wp), dtype=dtype, device=images.device,
-                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    m = (ctypes.c_double * 3)(*[float(v) for v in mean])
-    s = (ctypes.c_double * 3)(*[float(v) for v in std])
+    out = _dense_out(out, (N, 3, Hp, Wp), dtype, images.device, channels_last, any_gpu=True)
+    m, s = _double3(mean), _double3(std)
     handle = _lib.load_library()
     with torch.cuda.device(images.device):
         st = handle.bevops_image_normalize_pad(
@@ -96,14 +106,8 @@ def image_normalize_resize_pad(images, scale=None, size=None, mean=None, std=Non
         raise ValueError(f"the resized image would be {Hs} x {Ws}")
     Hp, Wp = padded_size(Hs, Ws, size_divisor)
     images = images.contiguous()
-    if out is not None and (tuple(out.shape) != (N, 3, Hp, Wp) or not out.is_cuda or not (
-            out.is_contiguous(memory_format=torch.channels_last) if channels_last else out.is_contiguous())):
-        raise ValueError(f"out must be a dense [N, 3, {Hp}, {Wp}] tensor on the GPU in the requested layout")
-    if out is None:
-        out = torch.empty((N, 3, Hp, Wp), dtype=dtype, device=images.device,
-                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    m = (ctypes.c_double * 3)(*[float(v) for v in mean])
-    s = (ctypes.c_double * 3)(*[float(v) for v in std])
+    out = _dense_out(out, (N, 3, Hp, Wp), dtype, images.device, channels_last, any_gpu=True)
+    m, s = _double3(mean), _double3(std)
     handle = _lib.load_library()
     with torch.cuda.device(images.device):
         st = handle.bevops_image_normalize_resize_pad(
@@ -213,12 +217,7 @@ def image_resize_crop_normalize(images, plan, flip=False, mean=None, std=None, t
         raise ValueError(f"the plan is for {plan.H0} x {plan.W0} images on {plan.tensor.device}")
     fH, fW = plan.out_size
     images = images.contiguous()
-    if out is not None and (tuple(out.shape) != (N, 3, fH, fW) or out.device != images.device or not (
-            out.is_contiguous(memory_format=torch.channels_last) if channels_last else out.is_contiguous())):
-        raise ValueError(f"out must be a dense [N, 3, {fH}, {fW}] tensor on the GPU in the requested layout")
-    if out is None:
-        out = torch.empty((N, 3, fH, fW), dtype=dtype, device=images.device,
-                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    out = _dense_out(out, (N, 3, fH, fW), dtype, images.device, channels_last)
     if canvas is True:
         canvas = torch.empty((N, fH, fW, 3), dtype=torch.uint8, device=images.device)
     elif canvas is not None and canvas is not False:
@@ -227,8 +226,7 @@ def image_resize_crop_normalize(images, plan, flip=False, mean=None, std=None, t
             raise ValueError(f"canvas must be a dense [N, {fH}, {fW}, 3] uint8 tensor on the GPU")
     else:
         canvas = None
-    m = (ctypes.c_double * 3)(*[float(v) for v in mean])
-    s = (ctypes.c_double * 3)(*[float(v) for v in std])
+    m, s = _double3(mean), _double3(std)
     handle = _lib.load_library()
     with torch.cuda.device(images.device):
         st = handle.bevops_image_resize_crop_normalize(
@@ -306,14 +304,8 @@ def image_letterbox(images, geometry, pipeline, dtype=torch.float16, channels_la
         raise ValueError(f"the geometry is for {tuple(geometry['ori_shape'][:2])} images, got {(H0, W0)}")
     (Hs, Ws), (Hp, Wp), (oy, ox) = geometry["size"], geometry["pad_shape"][:2], geometry["offset"]
     images = images.contiguous()
-    if out is not None and (tuple(out.shape) != (N, 3, Hp, Wp) or out.device != images.device or not (
-            out.is_contiguous(memory_format=torch.channels_last) if channels_last else out.is_contiguous())):
-        raise ValueError(f"out must be a dense [N, 3, {Hp}, {Wp}] tensor on the GPU in the requested layout")
-    if out is None:
-        out = torch.empty((N, 3, Hp, Wp), dtype=dtype, device=images.device,
-                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    D3 = ctypes.c_double * 3
-    pad, m, s = (D3(*[float(v) for v in p[k]]) for k in ("pad", "mean", "std"))
+    out = _dense_out(out, (N, 3, Hp, Wp), dtype, images.device, channels_last)
+    pad, m, s = _double3(p["pad"]), _double3(p["mean"]), _double3(p["std"])
     handle = _lib.load_library()
     with torch.cuda.device(images.device):
         st = handle.bevops_image_letterbox(

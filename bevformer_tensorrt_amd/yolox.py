@@ -37,6 +37,8 @@ import torch.nn.functional as F
 from . import functions as _hip_ops
 from .functions import yolox_ops as _Y
 from .functions.multi_scale_deformable_attn import _TensorCache
+from .functions.image import yolox_test_geometry
+from .graph_runner import Detect2DRunner
 
 # configs/yolox/yolox_x_8x8_300e_coco.py (deepen 1.33, widen 1.25); YOLOX_S: yolox_s_8x8_300e_coco.py (0.33 / 0.5), a
 # narrow architecture without padded layers (Cin 32 / 64, the 64-column tiles)
@@ -461,7 +463,7 @@ def num_priors(height, width, strides=(8, 16, 32)):
     return sum((height // s) * (width // s) for s in strides)
 
 
-class YOLOXRunner:
+class YOLOXRunner(Detect2DRunner):
     """`forward` + `yolox_decode` + `box_nms(padded=True)` captured once for images of one shape: `step(image)` copies
     the image into the static input buffer (unless it IS that buffer), replays the graph and returns the fixed-size
     (boxes [B, P, 4], scores [B, P], labels [B, P] int32, count [B] int32) with no host synchronisation; the boxes are
@@ -474,26 +476,13 @@ class YOLOXRunner:
     `raw_buffer` and writing `image_buffer`; `height` and `width` must be that pipeline's padded size.  Its boxes are in
     the RAW image's pixels: the geometry's scale_factor goes to yolox_decode, before the NMS as in mmdet."""
 
-    def __init__(self, model, batch, height, width, graph=True, clone_outputs=True, raw_size=None, img_scale=None):
-        if height % 32 or width % 32:
-            raise ValueError("YOLOXRunner: height and width are multiples of 32")
+    _detector, _heads, _pipeline = "YOLOX", -4, "yolox"        # (the nine head outputs, then the four of the NMS)
+    _geometry = staticmethod(yolox_test_geometry)
+
+    def _check_size(self, model, height, width):
         if num_priors(height, width, model.cfg["strides"]) > NMS_MAX_ROWS:
             raise ValueError(f"YOLOXRunner: {num_priors(height, width, model.cfg['strides'])} priors at {height} x {width}; "
                              f"box_nms takes at most {NMS_MAX_ROWS} rows")
-        p = next(model.parameters())
-        self.model, self.use_graph, self.clone_outputs = model, graph, clone_outputs
-        self.image_buffer = torch.zeros((batch, 3, height, width), device=p.device, dtype=p.dtype)
-        self._graph, self._outs, self._last = None, None, None
-        self.raw_size, self.geometry, self.raw_buffer, self._graph_raw, self._outs_raw = None, None, None, None, None
-        if raw_size is not None:
-            from .functions.image import DETECT2D_IMAGE_PIPELINES, yolox_test_geometry
-            self.pipeline = DETECT2D_IMAGE_PIPELINES["yolox"]
-            self.raw_size = (int(raw_size[0]), int(raw_size[1]))
-            self.geometry = yolox_test_geometry(*self.raw_size, img_scale or self.pipeline["img_scale"])
-            if tuple(self.geometry["pad_shape"][:2]) != (height, width):
-                raise ValueError(f"raw_size {self.raw_size}: YOLOX's test pipeline gives a network input of "
-                                 f"{tuple(self.geometry['pad_shape'][:2])}, the runner was asked for {(height, width)}")
-            self.raw_buffer = torch.zeros((batch,) + self.raw_size + (3,), device=p.device, dtype=torch.uint8)
 
     def _forward(self, raw=False):
         from .functions.decode2d import box_nms, yolox_decode
@@ -507,59 +496,3 @@ class YOLOXRunner:
         kept = box_nms(boxes, scores, labels, score_threshold=cfg["test_cfg"]["score_thr"],
                        iou_threshold=cfg["test_cfg"]["nms"]["iou_threshold"], class_aware=True, padded=True)
         return tuple(outs) + tuple(kept[:4])
-
-    def _capture(self, raw=False):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):       # warm-up on the capture stream (allocations, packed and merged operands)
-            for _ in range(2):
-                self._forward(raw)
-        torch.cuda.current_stream().wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            outs = self._forward(raw)
-        if raw:
-            self._graph_raw, self._outs_raw = graph, outs
-        else:
-            self._graph, self._outs = graph, outs
-
-    def step(self, image):
-        if tuple(image.shape) != tuple(self.image_buffer.shape):
-            raise ValueError(f"the runner was built for images {tuple(self.image_buffer.shape)}")
-        if image.data_ptr() != self.image_buffer.data_ptr():
-            self.image_buffer.copy_(image, non_blocking=True)
-        if not self.use_graph:
-            self._outs = self._forward()
-        else:
-            if self._graph is None:
-                self._capture()
-            self._graph.replay()
-        self._last = self._outs
-        outs = self._outs[-4:]
-        return tuple(t.clone() for t in outs) if self.clone_outputs and self.use_graph else outs
-
-    def step_raw(self, raw):
-        """`step` from the RAW camera images [B, H0, W0, 3] uint8 BGR on the device (raw_size=(H0, W0) at construction;
-        passing `raw_buffer` itself saves the copy): the letterbox launch, the network, the decode with the geometry's
-        scale_factor and the NMS as one graph of its own.  The boxes are in the raw image's pixels."""
-        if self.raw_size is None:
-            raise RuntimeError("step_raw needs YOLOXRunner(..., raw_size=(H0, W0))")
-        if raw.dtype != torch.uint8 or tuple(raw.shape) != tuple(self.raw_buffer.shape):
-            raise ValueError(f"raw must be uint8 {tuple(self.raw_buffer.shape)}")
-        if raw.data_ptr() != self.raw_buffer.data_ptr():
-            self.raw_buffer.copy_(raw, non_blocking=True)
-        if not self.use_graph:
-            self._outs_raw = self._forward(True)
-        else:
-            if self._graph_raw is None:
-                self._capture(True)
-            self._graph_raw.replay()
-        self._last = self._outs_raw
-        outs = self._outs_raw[-4:]
-        return tuple(t.clone() for t in outs) if self.clone_outputs and self.use_graph else outs
-
-    @property
-    def head_outputs(self):
-        """The nine head outputs of the last `step` / `step_raw`: the graph's static tensors, overwritten by the next
-        one."""
-        return None if self._last is None else self._last[:-4]

@@ -119,6 +119,27 @@ def test_scale_one_equals_image_normalize_pad(arith):
                     assert np.array_equal(bits(a.contiguous()), bits(b.contiguous()))
 
 
+@pytest.mark.parametrize("channels_last", [False, True])
+def test_arith_1_shares_its_taps_with_image_normalize_resize_pad(channels_last):
+    """The two entries share their taps and arithmetic leaves (csrc/image_resample.h).  With mean 0 and std 1 both
+    normalisation orders are exact, so arith 1 pasted at (0, 0) into a zero canvas IS image_normalize_resize_pad:
+    45 x 70 -> 36 x 56 in 64 x 64, bit for bit (and the two numpy restatements agree on it)."""
+    import bevformer_tensorrt_amd as bev
+    import util_image_scale as S
+    zero, one = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
+    img = U.noise(11, 2, 45, 70)
+    want = U.letterbox(img, (36, 56), (64, 64), (0, 0), 1, zero, one, False, zero)
+    assert np.array_equal(bits(want), bits(S.normalize_resize_pad(img, (36, 56), zero, one, False, size_divisor=32)))
+    dev = torch.from_numpy(img).cuda()
+    a = bev.image_letterbox(dev, geometry((45, 70), (36, 56), (64, 64), (0, 0)),
+                            dict(arith=1, mean=zero, std=one, to_rgb=False, pad=zero), dtype=torch.float32,
+                            channels_last=channels_last)
+    b = bev.image_normalize_resize_pad(dev, size=(36, 56), mean=zero, std=one, to_rgb=False, size_divisor=32,
+                                       dtype=torch.float32, channels_last=channels_last)
+    assert tuple(a.shape) == tuple(b.shape) == (2, 3, 64, 64)
+    assert np.array_equal(bits(a), bits(b)) and np.array_equal(bits(a), bits(want))
+
+
 @pytest.mark.parametrize("name", ["yolox", "centernet"])
 def test_camera_frame_through_the_test_geometry(name):
     """2 x 900 x 1600 uint8 through each detector's own geometry and constants (ratio 2.5: 360 x 640 in 640^2 / at

@@ -27,17 +27,9 @@ STEPS = (("depthnet", 300), ("dilated", 240), ("frame", 420))      # (name, seco
 
 
 def _capture(fn):
-    import torch
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        for _ in range(2):
-            fn()
-    torch.cuda.current_stream().wait_stream(s)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        outs = fn()
-    return graph, outs
+    """fn warmed on a side stream, then captured -> (graph, its outputs): the package's own routine."""
+    from bevformer_tensorrt_amd.graph_runner import capture
+    return capture(fn)
 
 
 def _replay_ms(graph, replays):

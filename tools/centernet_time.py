@@ -32,18 +32,9 @@ SHAPES = ((1, 3, 512, 512), (32, 3, 672, 672))
 
 
 def _capture(fn):
-    """fn warmed on a side stream, then captured -> graph."""
-    import torch
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        for _ in range(2):
-            fn()
-    torch.cuda.current_stream().wait_stream(s)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        keep = fn()
-    return graph, keep
+    """fn warmed on a side stream, then captured -> (graph, its outputs): the package's own routine."""
+    from bevformer_tensorrt_amd.graph_runner import capture
+    return capture(fn)
 
 
 def _replay_ms(graph, replays):

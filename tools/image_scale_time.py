@@ -4,6 +4,8 @@ uint8 frames -> normalised, rescaled (0.5: 450 x 800, area form; 0.8: 720 x 1280
 [6, 3, 736, 1280].
 
     python tools/image_scale_time.py [--rounds 9]              (a) the call alone, one JSON line per geometry
+    python tools/image_scale_time.py --other-forms             (a') the forms (a) leaves out: channels-last output,
+                                                                   fp32 input, fp32 output; `us` alone, no yardstick
     python tools/image_scale_time.py --once                    (b) three eager calls per geometry, no timing: for
                                                                    `rocprofv3 --kernel-trace --stats`
     python tools/image_scale_time.py --frame-ab [--pairs 3]    (c) the tiny frame through `step` and through `step_raw`
@@ -68,6 +70,33 @@ def replay_us(g, iters):
 def pipeline_kwargs(name):
     p = bev.BEVFORMER_IMAGE_PIPELINES[name]
     return dict(scale=p["scale"], mean=p["mean"], std=p["std"], to_rgb=p["to_rgb"], size_divisor=p["size_divisor"])
+
+
+OTHER_FORMS = (("u8", torch.float16, True), ("f32", torch.float16, False), ("f32", torch.float16, True),
+               ("u8", torch.float32, False))       # (input, output type, channels-last); (a) is u8, fp16, planes
+
+
+def form_name(src, dtype, channels_last):
+    return f"{src}->{'f16' if dtype == torch.float16 else 'f32'}:{'nhwc' if channels_last else 'planes'}"
+
+
+def other_forms(args):
+    dev = torch.device("cuda")
+    raw = {"u8": raw_frames(dev)}
+    raw["f32"] = raw["u8"].float()
+    cases = []
+    for name in ("tiny", "small"):
+        kw = pipeline_kwargs(name)
+        for src, dt, cl in OTHER_FORMS:
+            out = bev.image_normalize_resize_pad(raw[src], dtype=dt, channels_last=cl, **kw)
+            fn = lambda x=raw[src], out=out, cl=cl, kw=kw: bev.image_normalize_resize_pad(x, channels_last=cl, out=out, **kw)
+            cases.append((name, form_name(src, dt, cl), captured(fn, 100), fn))   # (fn keeps `out` alive)
+    times = [[] for _ in cases]
+    for _ in range(args.rounds):                          # round by round over all forms
+        for t, (_, _, g, _) in zip(times, cases):
+            t.append(replay_us(g, 100))
+    for t, (name, form, _, _) in zip(times, cases):
+        print(json.dumps({"op": "image_normalize_resize_pad", "pipeline": name, "form": form, "us": stats(t)}), flush=True)
 
 
 def prepare(args):
@@ -163,6 +192,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--other-forms", action="store_true")
     ap.add_argument("--frame-ab", action="store_true")
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--frame", choices=["prepared", "raw"])
@@ -172,7 +202,7 @@ def main():
     assert torch.cuda.is_available(), "image_scale_time.py needs the GPU"
     if args.frame:
         return frame(args.frame)
-    prepare(args)
+    other_forms(args) if args.other_forms else prepare(args)
 
 
 if __name__ == "__main__":

@@ -4,6 +4,8 @@
 CenterNet's fp16 [32, 3, 672, 672] (float32 resize, centred paste at (16, 16), normalisation last).
 
     python tools/letterbox_time.py [--rounds 9]              (a) the call alone, one JSON line per pipeline
+    python tools/letterbox_time.py --other-forms             (a') the forms (a) leaves out: fp16 channels-last and fp32
+                                                                 planes; `us` alone, no yardstick
     python tools/letterbox_time.py --once                    (b) three eager calls per pipeline, no timing: for
                                                                  `rocprofv3 --kernel-trace --stats`
     python tools/letterbox_time.py --frame-ab [--pairs 3]    (c) YOLOX-s at batch 1 through `step` and through `step_raw`
@@ -30,7 +32,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bevformer_tensorrt_amd as bev  # noqa: E402
-from image_scale_time import captured, replay_us  # noqa: E402
+from image_scale_time import captured, form_name, replay_us  # noqa: E402
 from qkv_time import stats  # noqa: E402
 
 BATCH, H0, W0 = 32, 480, 640
@@ -81,6 +83,24 @@ def call(args):
         rec["gb_s"] = round(moved / rec["us"]["median"] / 1e3, 1)
         rec["speedup_vs_torch"] = round(rec["torch_us"]["median"] / rec["us"]["median"], 2)
         print(json.dumps(rec), flush=True)
+
+
+def other_forms(args):
+    dev = torch.device("cuda")
+    raw = raw_frames(dev)
+    cases = []
+    for name in ("yolox", "centernet"):
+        geo = GEOMETRIES[name](H0, W0)
+        for dt, cl in ((torch.float16, True), (torch.float32, False)):
+            out = bev.image_letterbox(raw, geo, name, dtype=dt, channels_last=cl)
+            fn = lambda geo=geo, name=name, out=out, cl=cl: bev.image_letterbox(raw, geo, name, channels_last=cl, out=out)
+            cases.append((name, form_name("u8", dt, cl), captured(fn, 100), fn))   # (fn keeps `out` alive)
+    times = [[] for _ in cases]
+    for _ in range(args.rounds):
+        for t, (_, _, g, _) in zip(times, cases):
+            t.append(replay_us(g, 100))
+    for t, (name, form, _, _) in zip(times, cases):
+        print(json.dumps({"op": "image_letterbox", "pipeline": name, "form": form, "us": stats(t)}), flush=True)
 
 
 def frame(mode, frames=300):
@@ -136,6 +156,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--other-forms", action="store_true")
     ap.add_argument("--frame-ab", action="store_true")
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--frame", choices=["prepared", "raw"])
@@ -145,7 +166,7 @@ def main():
     assert torch.cuda.is_available(), "letterbox_time.py needs the GPU"
     if args.frame:
         return frame(args.frame)
-    call(args)
+    other_forms(args) if args.other_forms else call(args)
 
 
 if __name__ == "__main__":
