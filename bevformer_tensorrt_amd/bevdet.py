@@ -122,6 +122,11 @@ BEVDEPTH_R50_DCN = dict(BEVDET_R50, view_transformer="bevdepth", depthnet_cfg=di
 # features (bevdepth.LSSViewTransformerBEVStereo).  The reference tree has no BEVStereo config: bias = 5.0 and the finer
 # depth grid of the original BEVStereo configs are recalled, not read from it; this keeps BEVDET_R50's grid (D = 59).
 BEVSTEREO_R50 = dict(BEVDET_R50, view_transformer="bevstereo", depthnet_cfg=dict(use_dcn=False, stereo=True, bias=5.0))
+# BEVDet4D / BEVDepth4D: the previous num_adj BEV maps, warped into the current ego frame, stacked behind the current one
+# in front of the BEV encoder (functions.bev_align_stack); pre_process: two stride-1 basic blocks on the pooled map first.
+# The reference tree has no BEVDet4D code or config: num_adj = 1 with pre_process is recalled (design/bevdet4d.md).
+BEVDET4D_R50 = dict(BEVDET_R50, temporal=dict(num_adj=1, pre_process=True))
+BEVDEPTH4D_R50 = dict(BEVDEPTH_R50, temporal=dict(num_adj=1, pre_process=True))
 
 
 class LSSViewTransformer(nn.Module):
@@ -491,7 +496,17 @@ class BEVDet(nn.Module):
         else:
             self.view = LSSViewTransformer(**view_kw)
         c = cfg["out_channels"]
-        chans, cin, stages = [2 * c, 4 * c, 8 * c], c, []
+        self.num_adj, self.pre_process_net = 0, None
+        if cfg.get("temporal"):
+            if self.stereo:
+                raise NotImplementedError("temporal with view_transformer='bevstereo' (BEVStereo4D): no runner state keeps "
+                                          "the previous frame's stride-4 features and k2s_sensor (design/bevdet4d.md)")
+            self.num_adj = int(cfg["temporal"]["num_adj"])
+            if not 1 <= self.num_adj <= 15:
+                raise ValueError("temporal: 1 <= num_adj <= 15")
+            if cfg["temporal"].get("pre_process", False):
+                self.pre_process_net = nn.ModuleList([BasicBlock(c, c, 1, False), BasicBlock(c, c, 1, False)])
+        chans, cin, stages = [2 * c, 4 * c, 8 * c], (self.num_adj + 1) * c, []
         for ch in chans:
             stages.append(nn.ModuleList([BasicBlock(cin, ch, 2, True), BasicBlock(ch, ch, 1, False)]))
             cin = ch
@@ -688,6 +703,52 @@ class BEVDet(nn.Module):
                 return self._heads_hip(self.bev_encoder(self.view.view_transform_calibrated(x, calib, **skw)))
         return self._heads(self.view.view_transform_calibrated(x, calib, **skw))
 
+    # ---- BEVDet4D (cfg["temporal"]): functions.bev_align_stack between the pooling and the BEV encoder
+    def _temporal_only(self, what):
+        if not self.num_adj:
+            raise ValueError(f"{what}: a temporal model (cfg temporal=dict(num_adj=...), e.g. BEVDET4D_R50)")
+
+    @torch.no_grad()
+    def bev_feature_calibrated(self, image, calib):
+        """Everything of a temporal model's frame up to and including pre_process: image [B, N, 3, H, W] and the packed
+        calibration as in `forward_calibrated` -> this frame's BEV map [B, C, h, w] (channels-last on the fp16 path),
+        what `forward_temporal` aligns the past maps to and keeps in the ring."""
+        self._temporal_only("bev_feature_calibrated")
+        if calib.dim() == 2 and image.shape[0] != calib.shape[0]:
+            raise ValueError(f"image holds {image.shape[0]} samples, calib {calib.shape[0]}")
+        hip = self._bev_half_ready(image)
+        with _rule_dispatch() if hip else contextlib.nullcontext():
+            x, _ = self._frame_features(image.flatten(0, 1), None)
+            bev = self.view.view_transform_calibrated(x, calib)
+            if bev.is_cuda and bev.dtype == torch.float16:
+                bev = bev.contiguous(memory_format=torch.channels_last)
+            for blk in self.pre_process_net or ():
+                bev = blk(bev, self.ops)
+        return bev
+
+    @torch.no_grad()
+    def forward_temporal(self, image, calib, hist, meta):
+        """`forward_calibrated` of a temporal model: hist [num_adj + 1, B, C, h, w] the ring of past BEV maps (this
+        frame's map is written into its free slot), meta the int32 buffer of functions.pack_bev_align_meta on the
+        image's device (which slot is which past frame, the transforms of functions.bev_align_transform, validity).
+        -> the six maps."""
+        self._temporal_only("forward_temporal")
+        hip = self._bev_half_ready(image)
+        curr = self.bev_feature_calibrated(image, calib)
+        fn = getattr(self.ops, "bev_align_stack", _hip_ops.bev_align_stack)
+        stacked = fn(curr, hist, meta, self.num_adj)
+        if hip:
+            with _rule_dispatch():
+                return self._heads_hip(self.bev_encoder(stacked))
+        return self._heads(stacked)
+
+    def new_history(self, batch, device, dtype):
+        """A zeroed ring for `forward_temporal`: [num_adj + 1, batch, C, h, w], channels-last slots for fp16 on a GPU."""
+        self._temporal_only("new_history")
+        h, w, c = int(self.view.grid_size[1]), int(self.view.grid_size[0]), self.cfg["out_channels"]
+        ring = torch.zeros((self.num_adj + 1, batch, h, w, c), device=device, dtype=dtype)
+        return ring.permute(0, 1, 4, 2, 3)
+
     # ---- CenterHead.get_bboxes up to the NMS (centerpoint_head.py:716-746), configs/bevdet/bevdet-r50-cbgs.py:138-147
     @property
     def bbox_coder(self):
@@ -802,12 +863,16 @@ class BEVDetRunner:
         if raw:
             fn = getattr(self.model.ops, "image_resize_crop_normalize", _hip_ops.image_resize_crop_normalize)
             fn(self._in["raw"], self._plan, flip=self.flip, out=self._in["image"].flatten(0, 1))
-        out = self.model.forward_calibrated(self._in["image"], self._in["calib"])
+        out = self._model_forward()
         if self.post == "candidates":
             return out + tuple(self.model.get_candidates(out, padded=True))
         if self.post == "bboxes":
             return out + tuple(self.model.get_bboxes(out, padded=True))
         return out
+
+    def _model_forward(self):
+        """The model's frame from the static buffers (BEVDet4DRunner overrides it)."""
+        return self.model.forward_calibrated(self._in["image"], self._in["calib"])
 
     def _capture(self, raw=False):
         graph, outs = capture(lambda: self._forward(raw))
@@ -884,6 +949,66 @@ class BEVDetRunner:
         graph, outs = (self._graph_raw, self._outs_raw) if raw else (self._graph, self._outs)
         graph.replay()
         return tuple(t.clone() for t in outs) if self.clone_outputs else outs
+
+
+class BEVDet4DRunner(BEVDetRunner):
+    """`BEVDetRunner` for a temporal model (BEVDET4D_R50, BEVDEPTH4D_R50): the runner keeps the ring of the last num_adj
+    BEV maps on the device (`hist`, T + 1 slots: frame f writes slot f % (T + 1)), each slot's sensor2ego / ego2global on
+    the host, and the number of frames since the sequence began.  Per frame the host builds the T transforms
+    (functions.bev_align_transform: slice t is the t-th most recent frame), marks the slices whose frame does not exist
+    yet as invalid (the launch then feeds the current map, as BEVDet4D does at a sequence's start), and APPENDS the
+    packed meta in front of the calibration in the parent's pinned ring: still ONE upload per frame.  The captured graph
+    holds the index build, the image half, the pooling, pre_process, the alignment launch, the encoder, the heads and
+    the chosen post; it is captured once and serves every frame.
+
+    `step` / `step_raw` take the parent's arguments and start_of_sequence=False; the first frame of a runner always
+    starts a sequence."""
+
+    def __init__(self, model, device, **kw):
+        if not getattr(model, "num_adj", 0):
+            raise ValueError("BEVDet4DRunner: a temporal model (cfg temporal=dict(num_adj=...))")
+        super().__init__(model, device, **kw)
+        self.T = model.num_adj
+        self.hist = model.new_history(self.batch, device, self._dtype)
+        self._poses = [None] * (self.T + 1)          # per slot: (sensor2ego, ego2global) of the frame it holds
+        self._count, self._since_start, self._start = 0, 0, True
+
+    def step(self, *args, start_of_sequence=False):
+        self._start = start_of_sequence
+        return super().step(*args)
+
+    def step_raw(self, *args, start_of_sequence=False):
+        self._start = start_of_sequence
+        return super().step_raw(*args)
+
+    def _host_calib(self, sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda):
+        """[meta (int32 bits) | the parent's packed calibration] as one fp32 host buffer; advances the ring's state."""
+        calib = super()._host_calib(sensor2ego, ego2global, cam2imgs, post_rots, post_trans, bda)
+        T, B, view = self.T, self.batch, self.model.view
+        if self._start or self._count == 0:
+            self._since_start = 0
+        write_slot = self._count % (T + 1)
+        s2e, e2g = sensor2ego.detach().cpu().float(), ego2global.detach().cpu().float()
+        tf, slots, valid = torch.zeros(B, T, 2, 3), [], []
+        for t in range(1, T + 1):
+            slot = (write_slot - t) % (T + 1)
+            slots.append(slot)
+            valid.append(t <= self._since_start)
+            if valid[-1]:
+                tf[:, t - 1] = _hip_ops.bev_align_transform(s2e, e2g, *self._poses[slot], bda, view.grid_lower_bound,
+                                                            view.grid_interval)
+        meta = _hip_ops.pack_bev_align_meta(tf, slots, valid, write_slot)
+        self._poses[write_slot] = (s2e, e2g)
+        self._count += 1
+        self._since_start += 1
+        self._start = False
+        self._meta_words = meta.numel()
+        return torch.cat((meta.view(torch.float32), calib.reshape(-1)))
+
+    def _model_forward(self):
+        buf, n = self._in["calib"], self._meta_words
+        calib = buf[n:] if self.batch == 1 else buf[n:].view(self.batch, -1)
+        return self.model.forward_temporal(self._in["image"], calib, self.hist, buf[:n].view(torch.int32))
 
 
 def synthetic_rig(view, n_cams=6, seed=0):

@@ -363,3 +363,15 @@ def load_depthnet_state_dict(depth_net, state_dict, strict=True, prefix="img_vie
     if strict and (missing or unexpected):
         raise KeyError(f"missing {missing[:8]}; unexpected {unexpected[:8]}")
     return missing, unexpected
+
+
+def pre_process_key_map(model, prefix="pre_process_net.layers.0."):
+    """`reference_key_map` entries for the pre_process net of a temporal bevdet.BEVDet (BEVDet4D's CustomResNet with one
+    stage of two stride-1 BasicBlocks, named as that class registers them: `pre_process_net.layers.0.{0,1}.*`): every
+    BatchNorm2d folded into the convolution in front of it.  {} for a model without one."""
+    m = {}
+    for i, _ in enumerate(getattr(model, "pre_process_net", None) or ()):
+        for k in (1, 2):
+            m[f"pre_process_net.{i}.conv{k}.weight"] = m[f"pre_process_net.{i}.conv{k}.bias"] = \
+                _conv_bn(f"{prefix}{i}.conv{k}", f"{prefix}{i}.bn{k}")
+    return m

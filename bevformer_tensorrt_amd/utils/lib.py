@@ -219,6 +219,8 @@ SIGNATURES = {
     "bevops_stereo_grid": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "bevops_stereo_cost_volume_f16": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 7 +
                                       [c_float, c_void_p]),
+    "bevops_bev_align_stack_f16": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 5 +
+                                   [c_void_p]),
 }
 
 F32, F16, I8, U8 = 0, 1, 2, 3

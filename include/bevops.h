@@ -1636,6 +1636,33 @@ int bevops_stereo_grid(const float *consts, const float *xs, const float *ys, co
 int bevops_stereo_cost_volume_f16(const void *prev, int prev_pitch, const void *curr, int curr_pitch, const float *grid,
                                   const float *consts, const float *xs, const float *ys, const float *ds, void *out,
                                   int out_pitch, int n, int Hc, int Wc, int C, int D, int Dpad, float bias, void *stream);
+/* BEVDet4D's temporal BEV alignment and stacking (csrc/bev_align.hip, bevformer_tensorrt_amd/functions/bev_align.py;
+ * gen_grid / shift_feature of BEVDet4D as recalled -- the reference tree has no BEVDet4D code, design/bevdet4d.md) in
+ * ONE launch, no workspace, no atomics; the entry only launches, so it can be captured:
+ *   out[b, y, x, 0 : C]           = curr[b, y, x, :]                               bit copy
+ *   hist[write_slot][b, y, x, :]  = curr[b, y, x, :]                               bit copy: the frame kept for later
+ *   out[b, y, x, t C : (t + 1) C] = valid(b, t) ? bilinear(hist[slot(b, t)][b], sx, sy) : curr[b, y, x, :]     t = 1 .. T
+ * curr: channels-last fp16 [B, H, W, C] channel slice (pitches in elements, as in bevops_conv_slice_f16); hist: the ring
+ * [T + 1, B, H, W, C], a channel slice of pitch hist_pitch whose slots lie B H W hist_pitch elements apart; out:
+ * [B, H, W, (T + 1) C] channel slice.  hist[write_slot] is written and never read by the call.
+ * meta (device memory, 16-byte aligned, 4-byte fields; the host refreshes it every frame):
+ *   words 0 .. 3                       int32 write_slot, 0, 0, 0
+ *   words 4 + 8 (b T + t - 1) .. + 8   int32 slot, int32 valid, fp32 a00, a01, a02, a10, a11, a12      b < B, t = 1 .. T
+ * (32 bytes per entry).  A write_slot outside 0 .. T keeps no frame; a slot outside 0 .. T gives a slice of zeros.
+ * fp32 position and blend, every operation rounded on its own, never contracted (x, y the pixel of out as floats):
+ *   sx = add(add(mul(a00, x), mul(a01, y)), a02),  sy = add(add(mul(a10, x), mul(a11, y)), a12)
+ *   x0 = floor(sx), x1 = x0 + 1, fx = sx - x0, gx = 1 - fx (y likewise);  w00 = gx gy, w01 = fx gy, w10 = gx fy, w11 = fx fy
+ *   v = ((w00 p(y0, x0) + w01 p(y0, x1)) + w10 p(y1, x0)) + w11 p(y1, x1), rounded once to fp16 (nearest even)
+ * zeros padding, align_corners=True on PIXEL coordinates (no normalisation to [-1, 1] and back: a deviation from
+ * F.grid_sample of a few ulps of the position).  A corner is inside when 0 <= its coordinate <= W - 1 (H - 1), decided
+ * on the floats: a NaN, infinite or huge position is outside; a corner outside counts as zero and is not read.
+ * Statuses, before any device call, in this order: NULL curr / hist / out / meta, B < 0, non-positive H / W / C, T < 1;
+ * a pitch below its channel count (out: (T + 1) C); a pitch that is no multiple of 8; curr / hist / out / meta not
+ * 16-byte aligned: BEVOPS_BAD_PARAM.  dtype other than BEVOPS_F16, C % 8 != 0, T > 15, H or W above 0xffff, an operand
+ * whose byte extent reaches 0x7fffffff (32-bit offsets): BEVOPS_NOT_SUPPORTED.  B == 0: BEVOPS_SUCCESS without a launch.
+ * The device-side write_slot and slots cannot be checked here; pack_bev_align_meta checks them on the host. */
+int bevops_bev_align_stack_f16(int dtype, const void *curr, int curr_pitch, void *hist, int hist_pitch, void *out,
+                               int out_pitch, const void *meta, int B, int H, int W, int C, int T, void *stream);
 
 #ifdef __cplusplus
 }
