@@ -273,7 +273,7 @@ class Int8BEVDepth(_bi.Int8BEVDet):
                                         mlp_input=mlp_input.reshape(-1, MLP_INPUTS)), table)
 
     @torch.no_grad()
-    def bev_half_calibrated(self, x, calib):
+    def bev_half_calibrated(self, x, calib, tensors=None, layers=None):
         """bevdet_int8's, on the [N * 51 + 9] row(s) of LSSViewTransformerBEVDepth.calibration_matrices: the first part
         feeds the index build, the [B N, 27] rest the camera gates."""
         table = self._ready(x)
@@ -286,7 +286,7 @@ class Int8BEVDepth(_bi.Int8BEVDet):
         kw = dict(batch=calib.shape[0]) if calib.dim() == 2 else {}
         pool = lambda d, f, s: ops.bev_pool_v2_indirect(d, f, rd, rf, rb, ist, il, counts, h, w, scales=s, **kw)
         with _dispatch.using(rule=True):
-            return self._heads(self.run(x, pool, table, ops, mlp_input=mlp), table)
+            return self._heads(self.run(x, pool, table, ops, tensors, layers, mlp_input=mlp), table)
 
     @torch.no_grad()
     def fake_quant_reference(self, x, ranks, mlp_input=None, quantize=True, tensors=None):

@@ -661,11 +661,11 @@ class BEVDet(nn.Module):
                 x, skw = self._frame_features(image.flatten(0, 1), stereo_metas)
                 bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths,
                                                **kw, **skw)
-                return self._heads_hip(self.bev_encoder(bev))
+                return self._heads_hip(self.bev_encoder(self._single_frame_stack(bev)))
         x, skw = self._frame_features(image.flatten(0, 1), stereo_metas)
         kw.update(skw)
         bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, **kw)
-        feat = self.bev_encoder(bev)
+        feat = self.bev_encoder(self._single_frame_stack(bev))
         ops = self.ops
         s = _conv(ops, feat, self.shared_conv, True)
         return tuple(_conv(ops, _conv(ops, s, h[0], True), h[1]) for h in (self.heads[k] for k, _ in HEADS_R50))
@@ -719,12 +719,23 @@ class BEVDet(nn.Module):
         hip = self._bev_half_ready(image)
         with _rule_dispatch() if hip else contextlib.nullcontext():
             x, _ = self._frame_features(image.flatten(0, 1), None)
-            bev = self.view.view_transform_calibrated(x, calib)
-            if bev.is_cuda and bev.dtype == torch.float16:
-                bev = bev.contiguous(memory_format=torch.channels_last)
-            for blk in self.pre_process_net or ():
-                bev = blk(bev, self.ops)
+            return self._pre_process(self.view.view_transform_calibrated(x, calib))
+
+    def _pre_process(self, bev):
+        """The pooled map -> this frame's map: channels-last on the fp16 GPU path, then pre_process' blocks."""
+        if bev.is_cuda and bev.dtype == torch.float16:
+            bev = bev.contiguous(memory_format=torch.channels_last)
+        for blk in self.pre_process_net or ():
+            bev = blk(bev, self.ops)
         return bev
+
+    def _single_frame_stack(self, bev):
+        """`forward` (ready-made ranks, no ring) of a temporal model: the frame as a sequence's first, the current map in
+        every slice -- what bev_align_stack feeds while no past frame exists, and what the PTQ calibration frames run.
+        Any other model: bev."""
+        if not self.num_adj:
+            return bev
+        return torch.cat([self._pre_process(bev)] * (self.num_adj + 1), dim=1)
 
     @torch.no_grad()
     def forward_temporal(self, image, calib, hist, meta):

@@ -33,9 +33,11 @@ from .int8_plan import (Int8Model, Layer, Plan, basic_block_conv, basic_block_la
 
 SITE_PREFIX = "bevdet."
 CAT = "cat"
+STACK = "stack"      # a temporal model's [B, (T + 1) C, h, w] buffer in front of the BEV encoder, and this frame's map
 
 
-# Layer ops: "quantize", "conv", "split", "pool", "upsample" (bevdepth_int8.py adds "gate" and "avgpool").
+# Layer ops: "quantize", "conv", "split", "pool", "upsample", a temporal model's "align" (bevdepth_int8.py adds "gate" and
+# "avgpool").
 INT8_OPS = ("conv", "pool")
 
 
@@ -45,7 +47,10 @@ def build_plan(model):
     x = P.add(Layer("quantize", None, "x.f16", "x"))
     dn = P.add(Layer("conv", "depth_net", x, "depth_net"), "f16")
     P.add(Layer("split", None, dn, "feat", extra=("depth",)))
-    x = P.add(Layer("pool", None, "depth", "bev", res="feat"))
+    pre = (model.pre_process_net or ()) if model.num_adj else ()
+    x = P.add(Layer("pool", None, "depth", "bev", res="feat", group=STACK if model.num_adj and not pre else None))
+    if model.num_adj:
+        x = temporal_layers(P, pre, x)
     widths = [stage[0].conv1.out_channels for stage in model.bev_stages]
     c_cat = widths[0] + widths[-1]
     P.buffers[CAT] = c_cat
@@ -67,7 +72,19 @@ def build_plan(model):
     return P
 
 
+def temporal_layers(P, pre, x):
+    """BEVDet4D between the pooling and the BEV encoder (design/bevdet4d_int8.md): `pre`, the BasicBlocks of pre_process
+    (none when the model has none), then the alignment launch.  This frame's map -- the last block's output, or the
+    pooling's -- and the stacked buffer are ONE scale group: the ring holds earlier maps of the same static scale and a
+    bilinear blend is a convex combination, so bevops_bev_align_stack_s8 copies and blends bytes.  -> the stacked tensor."""
+    for j, blk in enumerate(pre):
+        x = basic_block_layers(P, blk, f"pre.b{j}", x, group=STACK if j == len(pre) - 1 else None)
+    return P.add(Layer("align", None, x, STACK))
+
+
 def _conv_of(model, key):
+    if key.startswith("pre."):
+        return basic_block_conv(model.pre_process_net[int(key[5])], key[7:])
     if key[0] == "s" and key[1].isdigit():
         return basic_block_conv(model.bev_stages[int(key[1])][int(key[4])], key[6:])
     if key == "shared_conv":
@@ -169,10 +186,23 @@ def emulate(model, plan, x, ranks, table, scales, tensors=None, layers=None, oth
             v = v.view(1, bev_h, bev_w, C).permute(0, 3, 1, 2)
         elif l.op == "upsample":
             v = fq(F.interpolate(src, scale_factor=l.factor, mode="bilinear", align_corners=True), l.dst)
+        elif l.op == "align":
+            v = align_statement(src, live["hist"], live["meta"], model.num_adj, None if scales is None else sc(l.dst))
         else:
             v = other(l, src, live)
         live[l.dst] = place(plan, l, live, v)
     return live.get("head.packed")                  # (None when `layers` ends in front of the heads)
+
+
+def align_statement(curr, hist, meta, T, scale):
+    """The alignment step of the statement on curr [B, C, h, w] fp32 holding q * scale: dequantised in, the bilinear blend
+    on the launch's positions, requantised with the group's scale -- functions.bev_align_stack_q_plain on the integers;
+    hist: the int8 ring [T + 1, B, C, h, w] (this frame's integers are kept in it).  scale None (the fp32 plain path):
+    functions.bev_align_stack_plain on an fp32 ring."""
+    if scale is None:
+        return _hip_ops.bev_align_stack_plain(curr, hist, meta, T)
+    q = torch.clamp(torch.round(curr / scale), -127, 127).to(torch.int8)
+    return _hip_ops.bev_align_stack_q_plain(q, hist, meta, T).float() * scale
 
 
 class Int8BEVDet(Int8Model):
@@ -180,7 +210,8 @@ class Int8BEVDet(Int8Model):
     half the int8 plan above.  fp: the bevdet.BEVDet whose weights it quantises (kept: its parameters are this module's,
     and a weight reload rebuilds the int8 operands); scales: {site: scale} for every site of the plan.  `forward`,
     `forward_calibrated`, `bev_half_calibrated`, `get_candidates`, `get_bboxes`, `prepare_bev_half` as BEVDet:
-    BEVDetRunner captures and replays it unchanged."""
+    BEVDetRunner captures and replays it unchanged.  A temporal model (BEVDET4D_R50, BEVDEPTH4D_R50) has `num_adj`,
+    `bev_feature_calibrated`, `forward_temporal` and `new_history` on an INT8 ring: BEVDet4DRunner takes it."""
 
     def __init__(self, fp, scales, ops=None):
         super().__init__(fp)
@@ -220,6 +251,8 @@ class Int8BEVDet(Int8Model):
     def _stamped(self):
         fp = self.fp
         mods = [fp.view.depth_net, fp.bev_stages, fp.neck_conv, fp.up2_conv, fp.shared_conv, fp.heads]
+        if fp.pre_process_net is not None:
+            mods.append(fp.pre_process_net)
         return [p for m in mods for p in m.parameters()]
 
     def _quantize(self):
@@ -264,12 +297,16 @@ class Int8BEVDet(Int8Model):
                 y = pool(src, live[l.res], (self.scale(l.src), self.scale(l.res), s_out)).permute(0, 3, 1, 2)
             elif l.op == "upsample":
                 y = ops.upsample_bilinear_nhwc_q(src, self.scale(l.src), s_out, scale_factor=l.factor, out=out)
+            elif l.op == "align":               # (bytes in, bytes out: src, the ring and the stack share s_out)
+                y = ops.bev_align_stack(src, live["hist"], live["meta"], self.num_adj)
             else:
                 y = other(l, src, live, s_out)
             live[l.dst] = y
         return live.get("head.packed")              # (None when `layers` ends in front of the heads)
 
     def _heads(self, packed, table):
+        if packed is None:                          # (the layers ended in front of the heads)
+            return None
         return tuple(packed[:, a:b] for a, b in table["slices"])
 
     def _features(self, image):
@@ -294,11 +331,12 @@ class Int8BEVDet(Int8Model):
         return self.bev_half_calibrated(x, calib)
 
     @torch.no_grad()
-    def bev_half_calibrated(self, x, calib):
+    def bev_half_calibrated(self, x, calib, tensors=None, layers=None):
         """Everything behind `image_features`: x = its fp16 [cams, 256, H / 16, W / 16] channels-last result; the index
         build and the pooling run on the device from the packed calibration buffer.  calib [B, cams * 24 + 9] with x
         [B * cams, ...]: the plan runs for B samples -- the pooled view [B, h, w, C], every later tensor with B items (the
-        concatenation buffer [B, 64, 64, 640]); same operands, same scales."""
+        concatenation buffer [B, 64, 64, 640]); same operands, same scales.  tensors, layers: `run`'s (a temporal model's
+        ring and meta; the part of the plan to run)."""
         table = self._ready(x)
         ops = self.bev_ops
         rb, rd, rf, ist, il, counts = self.view.prepare_calibrated(calib)
@@ -310,7 +348,43 @@ class Int8BEVDet(Int8Model):
             kw["batch"] = calib.shape[0]
         pool = lambda d, f, s: ops.bev_pool_v2_indirect(d, f, rd, rf, rb, ist, il, counts, h, w, scales=s, **kw)
         with _dispatch.using(rule=True):
-            return self._heads(self.run(x, pool, table, ops), table)
+            return self._heads(self.run(x, pool, table, ops, tensors, layers), table)
+
+    # ---- BEVDet4D: the int8 alignment launch between the pooling (pre_process) and the BEV encoder
+    @property
+    def num_adj(self):
+        return self.fp.num_adj
+
+    def _align_index(self, what):
+        self.fp._temporal_only(f"{type(self).__name__}.{what}")
+        return next(i for i, l in enumerate(self.plan.layers) if l.op == "align")
+
+    @torch.no_grad()
+    def bev_feature_calibrated(self, image, calib):
+        """A temporal model's frame up to and including pre_process -> this frame's INT8 BEV map [B, C, h, w]
+        channels-last, in the stack's scale: what `forward_temporal` aligns the past maps to and keeps in the ring."""
+        k, live = self._align_index("bev_feature_calibrated"), {}
+        self._ready(image)
+        with _dispatch.using(rule=True):
+            x = self._features(image)
+        self.bev_half_calibrated(x, calib, live, self.plan.layers[getattr(self.plan, "tail", 0):k])
+        return live[self.plan.layers[k].src]
+
+    @torch.no_grad()
+    def forward_temporal(self, image, calib, hist, meta):
+        """`forward_calibrated` of a temporal model: hist the INT8 ring of `new_history` (this frame's map is written into
+        its free slot), meta the int32 buffer of functions.pack_bev_align_meta on the image's device.  -> the six maps."""
+        self._align_index("forward_temporal")
+        self._ready(image)
+        with _dispatch.using(rule=True):
+            x = self._features(image)
+        return self.bev_half_calibrated(x, calib, {"hist": hist, "meta": meta})
+
+    def new_history(self, batch, device, dtype=None):
+        """A zeroed INT8 ring for `forward_temporal`: [num_adj + 1, batch, C, h, w], channels-last slots (dtype: what
+        BEVDet4DRunner asks its fp16 models for; the ring of this model is int8 whatever it names)."""
+        self._align_index("new_history")
+        return self.fp.new_history(batch, device, torch.int8)
 
     @torch.no_grad()
     def fake_quant_reference(self, x, ranks, quantize=True, tensors=None):
@@ -358,7 +432,17 @@ def calibrate_behind_split(fp, depth, feat, ranks, cal, ops):
         site("feat", feat)
         x = ops.bev_pool_v2_2(depth, feat, rd, rf, rb, ist, il, int(view.grid_size[1]), int(view.grid_size[0]))
         x = x.permute(0, 3, 1, 2)
-        site("bev", x)
+        pre = fp.pre_process_net or ()
+        site(STACK if fp.num_adj and not pre else "bev", x)
+        # a temporal model: pre_process, then the stack as this frame's map repeated -- a warped past map is a convex
+        # combination of an earlier such map under the same static scale, so the group's site sees curr alone
+        for j, blk in enumerate(pre):
+            t = conv(x, blk.conv1, True)
+            site(f"pre.b{j}.t1", t)
+            x = conv(t, blk.conv2, True, x)
+            site(f"pre.b{j}.out" if j < len(pre) - 1 else STACK, x)
+        if fp.num_adj:
+            x = torch.cat([x] * (fp.num_adj + 1), 1).contiguous(memory_format=torch.channels_last)
         feats = []
         for i, stage in enumerate(fp.bev_stages):
             for j, blk in enumerate(stage):

@@ -29,19 +29,16 @@
 // every invalid slice; wider maps (NP = 0) re-read them (L1) where a slice needs them.  Corner vectors are 16-byte
 // loads straight from global memory: the up-to-fourfold reuse between neighbouring pixels is left to L1 / L2 (a
 // rotated footprint is no rectangle; no LDS window).
-#include <math.h>
-
-#include "common.h"
+#include "bev_align.h"
 
 namespace bevops {
 namespace {
 
-constexpr int kBaBlock = 256;
-constexpr int kBaTile = 8;                       // the pixel tile is kBaTile x kBaTile
-constexpr int kBaWavePix = 16;                   // pixels per wave: two tile rows
-constexpr int kBaMaxT = 15;
-constexpr int kBaRegPasses = 4;                  // curr stays in registers up to this many passes (C <= 128)
-constexpr int kBaHead = 4, kBaEntry = 8;         // meta: words of the header and of one (sample, slice) entry
+// bev_align.h: the tile constants, the meta layout, Item / item_of, Footprint / footprint (shared with bev_align_s8.hip)
+constexpr int kBaBlock = balign::kBlock, kBaTile = balign::kTile, kBaWavePix = balign::kWavePix, kBaMaxT = balign::kMaxT;
+constexpr int kBaRegPasses = balign::kRegPasses;      // curr stays in registers up to this many passes (C <= 128)
+constexpr int kBaHead = balign::kHead, kBaEntry = balign::kEntry;
+using balign::Item;
 
 struct AlignArgs {
   const __half *curr;
@@ -61,23 +58,8 @@ __device__ __forceinline__ unsigned blend2(unsigned a, unsigned b, unsigned c, u
   return pack_h2(lo, hi);
 }
 
-// The work item of `lane` in pass k of its wave: pixel (x, y) of the tile rows the wave owns and channel offset ch.
-struct Item {
-  unsigned pix;        // b * H * W + y * W + x
-  int src, ch;         // the lane that holds the pixel's position and weights; first channel of the vector
-  bool act;            // inside the wave's items and inside the map
-};
-
 __device__ __forceinline__ Item item_of(const AlignArgs &p, int k, int lane, int x_base, int y_base, unsigned img) {
-  const int it = k * kWave + lane;
-  const int j = it / p.vecs;
-  const int x = x_base + (j & (kBaTile - 1)), y = y_base + ((j / kBaTile) & 1);
-  Item r;
-  r.src = j & (kBaWavePix - 1);
-  r.ch = (it - j * p.vecs) * 8;
-  r.act = j < kBaWavePix && x < p.w && y < p.h;
-  r.pix = img + (unsigned)y * p.w + x;
-  return r;
+  return balign::item_of<8>(p.vecs, p.w, p.h, k, lane, x_base, y_base, img);
 }
 
 template <int NP>
@@ -135,25 +117,11 @@ __global__ __launch_bounds__(kBaBlock) void bev_align_kernel(AlignArgs p) {
       }
       continue;
     }
-    const float a00 = __int_as_float(m[2]), a01 = __int_as_float(m[3]), a02 = __int_as_float(m[4]);
-    const float a10 = __int_as_float(m[5]), a11 = __int_as_float(m[6]), a12 = __int_as_float(m[7]);
     const bool slot_ok = (unsigned)slot <= (unsigned)p.t;               // (a slot outside the ring: a slice of zeros)
     const __half *src = p.hist + (size_t)(slot_ok ? slot : 0) * p.slot_stride + (size_t)img * p.hist_pitch;
-
-    const float sx = add_rn(add_rn(mul_rn(a00, px), mul_rn(a01, py)), a02);
-    const float sy = add_rn(add_rn(mul_rn(a10, px), mul_rn(a11, py)), a12);
-    const float x0 = floorf(sx), y0 = floorf(sy);
-    const float x1 = add_rn(x0, 1.f), y1 = add_rn(y0, 1.f);
-    const float fx = sub_rn(sx, x0), fy = sub_rn(sy, y0);
-    const float gx = sub_rn(1.f, fx), gy = sub_rn(1.f, fy);
-    const float w00 = mul_rn(gx, gy), w01 = mul_rn(fx, gy), w10 = mul_rn(gx, fy), w11 = mul_rn(fx, fy);
-    // validity on the floats; only a valid coordinate is converted
-    const bool vx0 = x0 >= 0.f && x0 <= wmax, vx1 = x1 >= 0.f && x1 <= wmax;
-    const bool vy0 = y0 >= 0.f && y0 <= hmax, vy1 = y1 >= 0.f && y1 <= hmax;
-    const unsigned pos = (unsigned)(vx0 ? (int)x0 + 1 : 0) | (unsigned)(vy0 ? (int)y0 + 1 : 0) << 16;     // (x0 + 1, y0 + 1)
-    const unsigned mask = slot_ok ? ((unsigned)(vx0 && vy0) | (unsigned)(vx1 && vy0) << 1 | (unsigned)(vx0 && vy1) << 2 |
-                                     (unsigned)(vx1 && vy1) << 3)
-                                  : 0u;
+    const balign::Footprint f = balign::footprint(m, px, py, wmax, hmax, slot_ok);
+    const float w00 = f.w00, w01 = f.w01, w10 = f.w10, w11 = f.w11;
+    const unsigned pos = f.pos, mask = f.mask;
 
 #pragma unroll R
     for (int k = 0; k < passes; ++k) {

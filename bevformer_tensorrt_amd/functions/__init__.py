@@ -46,8 +46,8 @@ from .lss_depthnet import (lss_camera_gate, se_gate2_nhwc, global_avgpool_nhwc, 
 from .deform_conv import deform_conv2d, deform_conv2d_nhwc, deform_conv2d_q_nhwc, deform_conv_packed_weight
 from .stereo import (stereo_calibration, stereo_frustum_tables, stereo_grid, stereo_grid_plain, stereo_cost_volume,
                      stereo_cost_volume_plain)
-from .bev_align import (bev_align_transform, bev_align_stack, bev_align_stack_plain, pack_bev_align_meta,
-                        unpack_bev_align_meta, bev_align_meta_words)
+from .bev_align import (bev_align_transform, bev_align_stack, bev_align_stack_plain, bev_align_stack_q_plain,
+                        pack_bev_align_meta, unpack_bev_align_meta, bev_align_meta_words)
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -89,6 +89,6 @@ __all__ = [
     "deform_conv2d", "deform_conv2d_nhwc", "deform_conv2d_q_nhwc", "deform_conv_packed_weight",
     "stereo_calibration", "stereo_frustum_tables", "stereo_grid", "stereo_grid_plain", "stereo_cost_volume",
     "stereo_cost_volume_plain",
-    "bev_align_transform", "bev_align_stack", "bev_align_stack_plain", "pack_bev_align_meta", "unpack_bev_align_meta",
-    "bev_align_meta_words",
+    "bev_align_transform", "bev_align_stack", "bev_align_stack_plain", "bev_align_stack_q_plain", "pack_bev_align_meta",
+    "unpack_bev_align_meta", "bev_align_meta_words",
 ]

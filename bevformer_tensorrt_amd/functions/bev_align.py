@@ -8,8 +8,11 @@ TRT_FUNCTIONS.
   * `pack_bev_align_meta`   the per-frame buffer of the launch (include/bevops.h fixes its layout), built on the host;
   * `bev_align_stack`       fp16 channels-last CUDA tensors take the one launch (bevops_bev_align_stack_f16): the current
                             map, the T aligned past maps behind it on the channel axis, and the current map kept in the
-                            ring's free slot.  Anything else: `bev_align_stack_plain`, the same positions, then
-                            F.grid_sample, the copies and the cat.
+                            ring's free slot.  int8 channels-last CUDA tensors take the int8 launch
+                            (bevops_bev_align_stack_s8: 16 channels per lane, bytes in, bytes out, no scale: static PTQ
+                            scales and a convex blend keep the ring, the stack and curr in ONE scale).  int8 anywhere
+                            else: `bev_align_stack_q_plain`, the exact statement of that launch.  Anything else:
+                            `bev_align_stack_plain`, the same positions, then F.grid_sample, the copies and the cat.
 
 The launch allocates a fixed-size output and never synchronises: it can be captured; `meta` is a static device buffer
 the host rewrites between replays."""
@@ -125,14 +128,55 @@ def bev_align_stack_plain(curr, hist, meta, T):
     return out
 
 
+def bev_align_stack_q_plain(curr, hist, meta, T):
+    """The statement of the int8 launch for int8 tensors on any device: curr [B, C, H, W], hist [T + 1, B, C, H, W] (slot
+    `write_slot` is overwritten with curr), meta as packed -> int8 [B, (T + 1) C, H, W].  The positions are the launch's
+    (fp32, each product and sum rounded on its own); corner validity on those floats; weights and blend in float64 on
+    the integer values; round half to even, clamp to +-127.  A slot outside the ring gives zeros, a write_slot outside
+    it keeps nothing.  (No F.grid_sample: int8 has none, and the tests need the exact statement.)"""
+    if curr.dtype != torch.int8 or hist.dtype != torch.int8:
+        raise ValueError("bev_align_stack_q_plain: int8 curr and hist")
+    B, C, H, W = curr.shape
+    write_slot, slots, valid, tf = unpack_bev_align_meta(meta, B, T)
+    c, h = curr.detach().cpu(), hist.detach().cpu()
+    xs = torch.arange(W, dtype=torch.float32).view(1, W)
+    ys = torch.arange(H, dtype=torch.float32).view(H, 1)
+    out = torch.zeros(B, (T + 1) * C, H, W, dtype=torch.int8)
+    out[:, :C] = c
+    for b in range(B):
+        for t in range(T):
+            sl, slot = slice((t + 1) * C, (t + 2) * C), int(slots[b, t])
+            if not bool(valid[b, t]):
+                out[b, sl] = c[b]
+                continue
+            if not 0 <= slot <= T:
+                continue
+            a = tf[b, t]
+            sx = ((a[0, 0] * xs + a[0, 1] * ys) + a[0, 2]).double()
+            sy = ((a[1, 0] * xs + a[1, 1] * ys) + a[1, 2]).double()
+            x0, y0 = sx.floor(), sy.floor()
+            fx, fy = sx - x0, sy - y0
+            src, val = h[slot, b].double(), torch.zeros(C, H, W, dtype=torch.float64)
+            for dy, dx, w in ((0, 0, (1 - fx) * (1 - fy)), (0, 1, fx * (1 - fy)), (1, 0, (1 - fx) * fy), (1, 1, fx * fy)):
+                xc, yc = x0 + dx, y0 + dy
+                ok = (xc >= 0) & (xc <= W - 1) & (yc >= 0) & (yc <= H - 1)          # false for NaN and infinities
+                xi, yi = torch.where(ok, xc, 0.0).long(), torch.where(ok, yc, 0.0).long()
+                val += torch.where(ok, w, 0.0) * torch.where(ok, src[:, yi, xi], 0.0)
+            out[b, sl] = val.round().clamp(-127, 127).to(torch.int8)
+    if 0 <= write_slot <= T:
+        hist[write_slot].copy_(curr)
+    return out.to(curr.device)
+
+
 def bev_align_stack(curr, hist, meta, T, out=None):
     """curr [B, C, H, W], hist [T + 1, B, C, H, W] (the ring: T past frames and one free slot), meta = the int32 buffer of
     `pack_bev_align_meta` on curr's device -> [B, (T + 1) C, H, W]: curr, then slice t = hist[slot(b, t)] sampled
     bilinearly at the transformed pixel (or curr where the slice is invalid); curr is also written into
     hist[write_slot].
 
-    fp16 CUDA channel slices of channels-last tensors take ONE launch and return a channels-last tensor (`out`: a channel
-    slice to write).  Anything else: `bev_align_stack_plain`."""
+    fp16 and int8 CUDA channel slices of channels-last tensors take ONE launch and return a channels-last tensor (`out`:
+    a channel slice to write); int8 blends bytes into bytes of the same scale (C % 16 == 0).  int8 elsewhere:
+    `bev_align_stack_q_plain`.  Anything else: `bev_align_stack_plain`."""
     T = int(T)
     if not torch.is_tensor(curr) or curr.dim() != 4:
         raise ValueError("bev_align_stack: curr a [B, C, H, W] tensor")
@@ -143,11 +187,13 @@ def bev_align_stack(curr, hist, meta, T, out=None):
     if not (torch.is_tensor(meta) and meta.dtype == torch.int32 and meta.dim() == 1 and
             meta.numel() == bev_align_meta_words(B, T) and meta.device == curr.device and meta.is_contiguous()):
         raise ValueError(f"bev_align_stack: meta a contiguous int32 tensor of {bev_align_meta_words(B, T)} words on curr's device")
-    if not (curr.is_cuda and curr.dtype == torch.float16):
-        res = bev_align_stack_plain(curr, hist, meta, T)
+    q8 = curr.dtype == torch.int8
+    if not (curr.is_cuda and (q8 or curr.dtype == torch.float16)):
+        res = (bev_align_stack_q_plain if q8 else bev_align_stack_plain)(curr, hist, meta, T)
         return res if out is None else out.copy_(res)
-    if C % 8 or not 1 <= T <= BEV_ALIGN_MAX_T:
-        raise _lib.BevopsError(f"bevops_bev_align_stack_f16: C % 8 == 0 and 1 <= T <= {BEV_ALIGN_MAX_T}", _lib.NOT_SUPPORTED)
+    vec, entry = (16, "bevops_bev_align_stack_s8") if q8 else (8, "bevops_bev_align_stack_f16")
+    if C % vec or not 1 <= T <= BEV_ALIGN_MAX_T:
+        raise _lib.BevopsError(f"{entry}: C % {vec} == 0 and 1 <= T <= {BEV_ALIGN_MAX_T}", _lib.NOT_SUPPORTED)
     cp, hp = slice_pitch(curr, "curr"), slice_pitch(hist[0], "hist[0]")
     if hist.stride(0) != B * H * W * hp:
         raise ValueError("bev_align_stack: the ring's slots lie B H W pitch elements apart")
@@ -156,6 +202,6 @@ def bev_align_stack(curr, hist, meta, T, out=None):
     out = _dest(out, (B, (T + 1) * C, H, W), curr, "bev_align_stack")
     op = slice_pitch(out, "out")
     if B and H * W:
-        _call("bevops_bev_align_stack_f16", curr.device, _lib.F16, curr.data_ptr(), cp, hist.data_ptr(), hp, out.data_ptr(),
-              op, meta.data_ptr(), B, H, W, C, T)
+        _call(entry, curr.device, *(() if q8 else (_lib.F16,)), curr.data_ptr(), cp, hist.data_ptr(), hp, out.data_ptr(), op,
+              meta.data_ptr(), B, H, W, C, T)
     return out

@@ -30,12 +30,14 @@ def fake_quant(t, scale):
 class Layer:
     """op: the model's operator name ("conv" is the shared one); src / dst / res: tensor names; into = (buffer, first
     channel): dst is that channel slice of `buffer`; extra: further int8 tensors the layer writes; factor: an up-sampler's;
-    dilation, image_bias (the name of an fp16 [n, Cout] tensor added in place of the bias): a convolution's."""
+    dilation, image_bias (the name of an fp16 [n, Cout] tensor added in place of the bias): a convolution's; group: the
+    scale group dst joins without being a slice of its buffer (a temporal model's map and the stack it is copied into)."""
 
     def __init__(self, op, key, src, dst, res=None, act="none", stride=1, into=None, extra=(), factor=1, dilation=1,
-                 image_bias=None):
+                 image_bias=None, group=None):
         self.op, self.key, self.src, self.dst, self.res, self.act, self.stride = op, key, src, dst, res, act, stride
         self.into, self.extra, self.factor, self.dilation, self.image_bias = into, extra, factor, dilation, image_bias
+        self.group = group
 
 
 class Plan:
@@ -49,7 +51,8 @@ class Plan:
         self.layers.append(layer)
         for name in layer.extra + (layer.dst,):
             self.tensors[name] = kind if name == layer.dst else "q"
-            self.group[name] = layer.into[0] if (layer.into is not None and name == layer.dst) else name
+            own = layer.into[0] if layer.into is not None else layer.group
+            self.group[name] = own if (own is not None and name == layer.dst) else name
         return layer.dst
 
     def readable(self, buffer):
@@ -73,16 +76,16 @@ class Plan:
         return out
 
 
-def basic_block_layers(P, blk, name, x, kind="q", into=None):
+def basic_block_layers(P, blk, name, x, kind="q", into=None, group=None):
     """A BasicBlock on the plan P from the tensor x: the downsample (a stage's first block) -> name.idt, conv1 + ReLU ->
-    name.t1, conv2 + identity + ReLU with the identity IN FRONT of the ReLU -> name.out (`kind`, `into`: of that last
-    tensor).  -> name.out."""
+    name.t1, conv2 + identity + ReLU with the identity IN FRONT of the ReLU -> name.out (`kind`, `into`, `group`: of that
+    last tensor).  -> name.out."""
     s = blk.conv1.stride[0]
     idt = x
     if blk.downsample is not None:
         idt = P.add(Layer("conv", name + ".down", x, name + ".idt", stride=s))
     t = P.add(Layer("conv", name + ".conv1", x, name + ".t1", act="relu", stride=s))
-    return P.add(Layer("conv", name + ".conv2", t, name + ".out", res=idt, act="relu", into=into), kind)
+    return P.add(Layer("conv", name + ".conv2", t, name + ".out", res=idt, act="relu", into=into, group=group), kind)
 
 
 def basic_block_conv(blk, which):

@@ -1107,7 +1107,12 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
     the layer joins the plan as two int8 layers -- the pack's offset convolution with fp16 out (the offsets are never
     quantised) and the int8 grouped deformable convolution deform_conv2d_q_nhwc with its own site "dn.dcn"
     (design/bevdepth_dcn_int8.md); note["depthnet_dcn"] = "int8".  "int8" on a model without the layer, or any other
-    value: ValueError."""
+    value: ValueError.
+    A temporal model (cfg["temporal"]: BEVDET4D_R50, BEVDEPTH4D_R50) is built with bev_half="int8" only
+    (design/bevdet4d_int8.md): the plan gains pre_process' convolutions and the int8 alignment launch, this frame's map and
+    the stacked buffer are one scale site, calibrated on ordinary single frames with the map repeated; the model has
+    forward_temporal / new_history (an int8 ring) and BEVDet4DRunner captures it.  The default bev_half="fp16":
+    NotImplementedError."""
     if bev_half not in BEVDET_BEV_HALF_BUILDS:
         raise ValueError(f"bev_half = {bev_half!r}: one of {BEVDET_BEV_HALF_BUILDS}")
     if depthnet_dcn not in BEVDET_DEPTHNET_DCN_BUILDS:
@@ -1116,9 +1121,11 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
         raise ValueError("build_int8_bevdet: calibration_cache goes with bev_half='int8'")
     src = D if isinstance(D, torch.nn.Module) else None
     model_cfg = (getattr(src, "cfg", None) if src is not None else cfg) or {}
-    if model_cfg.get("temporal"):
+    temporal = bool(model_cfg.get("temporal"))
+    if temporal and bev_half != "int8":
         raise NotImplementedError("build_int8_bevdet: a temporal model (BEVDet4D / BEVDepth4D: bev_align_stack and the "
-                                  "widened BEV encoder) has no INT8 build (design/bevdet4d.md)")
+                                  "widened BEV encoder) is built with bev_half=\"int8\" only: the ring and the stacked "
+                                  "buffer are int8 there (design/bevdet4d_int8.md)")
     if model_cfg.get("view_transformer") == "bevstereo" or (model_cfg.get("depthnet_cfg") or {}).get("stereo", False):
         raise NotImplementedError("build_int8_bevdet: the BEVStereo model (DepthNet(stereo=True): the temporal-stereo cost "
                                   "volume) has no INT8 build (design/bevstereo.md)")
@@ -1139,7 +1146,7 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
     if src is not None:
         from . import bevdet as D
     kw = {}
-    if src is not None and depthnet:
+    if src is not None and (depthnet or temporal):
         kw["cfg"] = src.cfg
     elif src is None and cfg is not None:
         kw["cfg"] = cfg
@@ -1186,7 +1193,7 @@ def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache,
         try:
             for f in frames:
                 qops.begin_frame()
-                model(*f)
+                model(*f)       # (a temporal model: `forward` is the single frame, this frame's map in every slice)
                 _plan.calibrate_frame(model, seen.pop("x"), f[1:], cal)
                 n += 1
         finally:

@@ -221,6 +221,8 @@ SIGNATURES = {
                                       [c_float, c_void_p]),
     "bevops_bev_align_stack_f16": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 5 +
                                    [c_void_p]),
+    "bevops_bev_align_stack_s8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 5 +
+                                  [c_void_p]),
 }
 
 F32, F16, I8, U8 = 0, 1, 2, 3

@@ -1663,6 +1663,19 @@ int bevops_stereo_cost_volume_f16(const void *prev, int prev_pitch, const void *
  * The device-side write_slot and slots cannot be checked here; pack_bev_align_meta checks them on the host. */
 int bevops_bev_align_stack_f16(int dtype, const void *curr, int curr_pitch, void *hist, int hist_pitch, void *out,
                                int out_pitch, const void *meta, int B, int H, int W, int C, int T, void *stream);
+/* The same step on INT8 maps (csrc/bev_align_s8.hip, design/bevdet4d_int8.md): curr, hist and out are int8 channel
+ * slices of channels-last tensors, pitches in bytes; meta, the positions, the corner validity and the weights are those
+ * of bevops_bev_align_stack_f16, operation for operation.  Slice 0, hist[write_slot] and every invalid slice are byte
+ * copies of curr.  A valid slice is the fp32 blend of the int8 corner values p (converted exactly)
+ *   v = ((w00 p(y0, x0) + w01 p(y0, x1)) + w10 p(y1, x0)) + w11 p(y1, x1),   byte = min(max(rne(v), -127), 127)
+ * There is no scale argument: PTQ scales are static, so every slot of the ring carries curr's scale, and a bilinear
+ * blend with zeros padding is a convex or sub-convex combination, so the blended bytes stay in that scale.
+ * Statuses, before any device call, in this order: NULL curr / hist / out / meta, B < 0, non-positive H / W / C, T < 1;
+ * a pitch below its channel count (out: (T + 1) C); a pitch that is no multiple of 16; curr / hist / out / meta not
+ * 16-byte aligned: BEVOPS_BAD_PARAM.  C % 16 != 0, T > 15, H or W above 0xffff, an operand whose byte extent reaches
+ * 0x7fffffff (32-bit offsets): BEVOPS_NOT_SUPPORTED.  B == 0: BEVOPS_SUCCESS without a launch. */
+int bevops_bev_align_stack_s8(const void *curr, int curr_pitch, void *hist, int hist_pitch, void *out, int out_pitch,
+                              const void *meta, int B, int H, int W, int C, int T, void *stream);
 
 #ifdef __cplusplus
 }
