@@ -166,10 +166,21 @@ def yolox_key_map(model):
       bbox_head.multi_level_conv_{cls,reg,obj}.{l}                    the predictors (plain convolutions, copied)
 
     ("conv_bn_yolox", conv, bn): folded with `fold_conv_bn` at eps 1e-3.  Neither mmdet nor a checkpoint is available
-    to this repository's tests: parity with the library's names is unpinned."""
+    to this repository's tests: parity with the library's names is unpinned.
+
+    A use_depthwise model: each yolox.DWSepConvAct is mmcv's DepthwiseSeparableConvModule, whose two ConvModules are
+    registered as `depthwise_conv` and `pointwise_conv` -- {ours}.depthwise_conv <- {ref}.depthwise_conv.{conv,bn} and
+    {ours}.pointwise_conv <- {ref}.pointwise_conv.{conv,bn}.  These names are written from mmcv's module as recalled,
+    not read from the library: unpinned like the rest."""
+    from .yolox import DWSepConvAct
     m = {}
+    named = dict(model.named_modules())
 
     def fold(ours, ref):
+        if isinstance(named.get(ours), DWSepConvAct):
+            fold(ours + ".depthwise_conv", ref + ".depthwise_conv")
+            fold(ours + ".pointwise_conv", ref + ".pointwise_conv")
+            return
         m[ours + ".weight"] = ("conv_bn_yolox", ref + ".conv", ref + ".bn")
         m[ours + ".bias"] = ("conv_bn_yolox", ref + ".conv", ref + ".bn")
 

@@ -238,6 +238,120 @@ def conv_slice_nhwc(x, weight, bias=None, act="silu", residual=None, stride=1, o
     return conv_slice_taps(x, wp, bias, act, residual, stride, out, dilation, image_bias)
 
 
+# ---- the depthwise-separable layer (mmcv's DepthwiseSeparableConvModule; bevops_dwsep_conv_f16, csrc/dwsep_conv.hip)
+_PACKED_DWSEP = _TensorCache()   # depthwise / pointwise weight tensor -> {padded width(s): packed operand}
+
+
+def dwsep_conv_packed_weight(dw_weight, pw_weight, cin=None, cout=None, build=True):
+    """The two weight operands of bevops_dwsep_conv_f16 for a depthwise weight [C, 1, 3, 3] and a pointwise weight
+    [Cout, C, 1, 1]: (w_dw_taps [3, 3, cin] taps-major, w_pw [cout, cin]), zero-padded behind the real channels to
+    cin / cout (default: `pad_channels`' rule, the next multiple of 32) -- a pad channel has zero taps and a zero column,
+    a pad output a zero row.  Each is cached per weight tensor, stamped like `conv_slice_packed_weight`'s, and rebuilt when
+    its weight changes.  build=False: None when either is missing or stale.  Never built inside a stream capture
+    (RuntimeError)."""
+    if dw_weight.dim() != 4 or tuple(dw_weight.shape[1:]) != (1, 3, 3):
+        raise ValueError("dwsep_conv: dw_weight [C, 1, 3, 3]")
+    C = dw_weight.shape[0]
+    if pw_weight.dim() != 4 or tuple(pw_weight.shape[1:]) != (C, 1, 1):
+        raise ValueError("dwsep_conv: pw_weight [Cout, C, 1, 1] with the depthwise weight's C")
+    cin = padded_width(C) if cin is None else int(cin)
+    cout = padded_width(pw_weight.shape[0]) if cout is None else int(cout)
+    if cin < C or cout < pw_weight.shape[0]:
+        raise ValueError("dwsep_conv: fewer channels than the weights have")
+    hd, hp = _PACKED_DWSEP.get(dw_weight), _PACKED_DWSEP.get(pw_weight)
+    if hd is not None and cin in hd and hp is not None and (cin, cout) in hp:
+        return hd[cin], hp[(cin, cout)]
+    if not build:
+        return None
+    if dw_weight.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("dwsep_conv_nhwc: a packed weight is missing or stale and the stream is capturing; call "
+                           "dwsep_conv_packed_weight(dw_weight, pw_weight, cin, cout) (or the layer once, eagerly) "
+                           "before the capture")
+    d, p = dw_weight.detach(), pw_weight.detach()
+    wd = d.new_zeros((3, 3, cin))
+    wd[:, :, :C] = d[:, 0].permute(1, 2, 0)
+    wp = p.new_zeros((cout, cin))
+    wp[:p.shape[0], :C] = p[:, :, 0, 0]
+    hd = _PACKED_DWSEP.put(dw_weight, {}) if hd is None else hd
+    hp = _PACKED_DWSEP.put(pw_weight, {}) if hp is None else hp
+    hd[cin], hp[(cin, cout)] = wd, wp
+    return wd, wp
+
+
+def _bias_f16(bias, n, name):
+    if bias is None:
+        return None
+    if bias.numel() != n:
+        raise ValueError(f"dwsep_conv: one {name} per channel ({n}), got {bias.numel()}")
+    if bias.dtype != torch.float16 or not bias.is_contiguous():
+        bias = bias.to(torch.float16).contiguous()
+    return bias
+
+
+def dwsep_conv_taps(x, w_dw_taps, bias_dw, w_pw, bias_pw, act_dw="silu", act_pw="silu", residual=None, stride=1, out=None):
+    """One launch of bevops_dwsep_conv_f16 on ready operands:
+        t   = fp16(act_dw(depthwise 3 x 3 (x), stride, pad 1, + bias_dw))      (never written to memory)
+        out = fp16(act_pw(t @ w_pw^T + bias_pw) + residual)                    (the identity BEHIND the activation)
+    x [B, Cin, H, W], residual and out [B, Cout, Hout, Wout]: fp16 CUDA channel slices of channels-last tensors;
+    w_dw_taps [3, 3, Cin] and w_pw [Cout, Cin] contiguous fp16 (`dwsep_conv_packed_weight`); biases [Cin] / [Cout] or
+    None; acts in "none", "relu", "silu"; stride in {1, 2}; Cin % 32 == 0, Cout % 8 == 0 (else BevopsError
+    NOT_SUPPORTED).  The errors are `conv_slice_taps`' for the same faults."""
+    _check_f16(x, "x")
+    B, Cin, H, W = x.shape
+    for w, name, shape in ((w_dw_taps, "w_dw_taps [3, 3, Cin]", (3, 3, Cin)), (w_pw, "w_pw [Cout, Cin]", None)):
+        if w.dtype != torch.float16 or w.device != x.device or not w.is_contiguous() or \
+                (shape is not None and tuple(w.shape) != shape) or (shape is None and w.dim() != 2):
+            raise ValueError(f"dwsep_conv: {name} contiguous fp16 on the input's device, got {tuple(w.shape)}")
+    Cout = w_pw.shape[0]
+    if w_pw.shape[1] != Cin:
+        raise ValueError(f"dwsep_conv: the pointwise weight has {w_pw.shape[1]} input channels, x has {Cin}")
+    if act_dw not in ACTS or act_pw not in ACTS:
+        raise ValueError(f"dwsep_conv: acts in {sorted(k for k in ACTS if k)}")
+    if stride not in (1, 2) or Cin % 32 or Cout % 8:
+        raise _lib.BevopsError("bevops_dwsep_conv_f16: stride in {1, 2}, Cin % 32 == 0, Cout % 8 == 0", _lib.NOT_SUPPORTED)
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    xp = slice_pitch(x, "x")
+    out = _dest(out, (B, Cout, Ho, Wo), x, "dwsep_conv")
+    op = slice_pitch(out, "out")
+    rp = 0
+    if residual is not None:
+        _check_f16(residual, "residual")
+        if tuple(residual.shape) != tuple(out.shape):
+            raise ValueError("dwsep_conv: the identity has the output's shape")
+        rp = slice_pitch(residual, "residual")
+    bias_dw, bias_pw = _bias_f16(bias_dw, Cin, "bias_dw"), _bias_f16(bias_pw, Cout, "bias_pw")
+    if B == 0:
+        return out
+    _call("bevops_dwsep_conv_f16", x.device, x.data_ptr(), xp, w_dw_taps.data_ptr(), _ptr(bias_dw), w_pw.data_ptr(),
+          _ptr(bias_pw), _ptr(residual), rp, out.data_ptr(), op, B, H, W, Cin, Cout, int(stride), ACTS[act_dw], ACTS[act_pw])
+    return out
+
+
+def dwsep_conv_nhwc(x, dw_weight, dw_bias, pw_weight, pw_bias, act_dw="silu", act_pw="silu", residual=None, stride=1,
+                    out=None):
+    """`dwsep_conv_taps` from the layer's own weights: dw_weight [C, 1, 3, 3], pw_weight [Cout, C, 1, 1] fp16, biases
+    [C] / [Cout] or None.  The layer runs at the tensors' widths (x.shape[1] >= C, with `out=` its channels >= Cout)
+    with zero taps, columns, rows and biases behind the weights' own; without `out=` a new channels-last tensor of
+    padded_width(Cout, 8) channels is returned."""
+    for w in (dw_weight, pw_weight):
+        if w.dtype != torch.float16 or w.device != x.device:
+            raise ValueError("dwsep_conv_nhwc: fp16 weights on the input's device")
+    cin = x.shape[1]
+    cout = out.shape[1] if out is not None else padded_width(pw_weight.shape[0], 8)
+    if cin % 32 or cout % 8:
+        raise _lib.BevopsError("bevops_dwsep_conv_f16: Cin % 32 == 0 and Cout % 8 == 0", _lib.NOT_SUPPORTED)
+    wd, wp = dwsep_conv_packed_weight(dw_weight, pw_weight, cin, cout)
+
+    def widen(b, n):
+        if b is None or b.numel() == n:
+            return b
+        full = b.detach().new_zeros((n,))
+        full[:b.numel()] = b.detach()
+        return full
+
+    return dwsep_conv_taps(x, wd, widen(dw_bias, cin), wp, widen(pw_bias, cout), act_dw, act_pw, residual, stride, out)
+
+
 FOCUS_CHANNELS = 32
 
 

@@ -1231,6 +1231,9 @@ def build_int8_yolox(Y, dev, images, calibrator="entropy", calibration_cache=Non
     like YOLOX, and YOLOXRunner captures it unchanged."""
     from . import yolox_int8 as _yi
     fp = Y if isinstance(Y, torch.nn.Module) else Y.YOLOX(cfg)
+    if fp.cfg.get("use_depthwise", False):
+        raise NotImplementedError("build_int8_yolox: a use_depthwise model has no INT8 build (no int8 depthwise-separable "
+                                  "kernel, design/yolox_depthwise.md)")
     fp = fp.to(dev, torch.float16)
     plan = _yi.build_plan(fp)
     _, num_groups = plan.groups()

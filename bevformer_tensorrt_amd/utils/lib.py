@@ -135,6 +135,7 @@ SIGNATURES = {
                               [c_void_p]),
     "bevops_conv_slice_f16_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 11 +
                                  [c_void_p]),
+    "bevops_dwsep_conv_f16": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p] + [c_int] * 9 + [c_void_p]),
     "bevops_lss_camera_gate_packed_size": (c_size_t, [c_int]),
     "bevops_lss_camera_gate": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "bevops_se_gate2_nhwc": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),

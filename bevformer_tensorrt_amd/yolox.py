@@ -29,7 +29,15 @@ Two data paths through the same weights, chosen like CenterNet's (centernet.py):
 CSPLayer, DarknetBottleneck, the CSPDarknet stage list and the head's predictors are written from the reference's
 files; Focus, SPPBottleneck, YOLOXPAFPN and YOLOXHead.forward_single from mmdet 2.x's published modules.  Neither mmdet
 nor a YOLOX checkpoint is available to this repository's tests, so parity with the library's own forward is unpinned
-(as for centernet.py and functions/decode2d.py)."""
+(as for centernet.py and functions/decode2d.py).
+
+use_depthwise (the configuration key; csp_darknet.py:84-162, scp_layer.py:39-47 / 110-150, yolox_head.py:20): every 3x3
+ConvModule outside Focus and SPP -- the stage heads, DarknetBottleneck.conv2, the PAFPN's down-samples, the head's
+towers -- is mmcv's DepthwiseSeparableConvModule: depthwise 3x3 + BN + Swish, pointwise 1x1 + BN + Swish
+(`DWSepConvAct`).  On the fast path such a layer is ONE launch of functions/yolox_ops.dwsep_conv_taps
+(csrc/dwsep_conv.hip, design/yolox_depthwise.md) where the dense model has one conv_slice_taps launch, so the buffer
+plan above is unchanged; only the head's two first tower convolutions, which the dense model stacks, are two launches
+(their depthwise weights differ) into the halves of the same buffer."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -46,6 +54,12 @@ YOLOX_X = dict(deepen=1.33, widen=1.25, in_channels=(320, 640, 1280), out_channe
                feat_channels=320, strides=(8, 16, 32), test_cfg=dict(score_thr=0.01, nms=dict(iou_threshold=0.65)))
 YOLOX_S = dict(deepen=0.33, widen=0.5, in_channels=(128, 256, 512), out_channels=128, num_csp_blocks=1, num_classes=80,
                feat_channels=128, strides=(8, 16, 32), test_cfg=dict(score_thr=0.01, nms=dict(iou_threshold=0.65)))
+# YOLOX-Nano.  The reference tree has only the yolox_x config: these numbers are written from mmdet 2.x's
+# configs/yolox/yolox_nano_8x8_300e_coco.py as recalled (deepen 0.33, widen 0.25, use_depthwise in backbone, neck and
+# head), not read from a file available here.  Its 16-channel layers run at 32 with zero pad channels.
+YOLOX_NANO = dict(deepen=0.33, widen=0.25, in_channels=(64, 128, 256), out_channels=64, num_csp_blocks=1, num_classes=80,
+                  feat_channels=64, strides=(8, 16, 32), use_depthwise=True,
+                  test_cfg=dict(score_thr=0.01, nms=dict(iou_threshold=0.65)))
 # in_channels, out_channels, num_blocks, add_identity, use_spp (csp_darknet.py:61-67, "P5")
 ARCH_P5 = ((64, 128, 3, True, False), (128, 256, 9, True, False), (256, 512, 9, True, False), (512, 1024, 3, False, True))
 SPP_KERNELS = (5, 9, 13)
@@ -79,12 +93,45 @@ class ConvAct(nn.Conv2d):
         return silu(y) if self.act == "silu" else y
 
 
+class DWConvAct(nn.Conv2d):
+    """The depthwise half of mmcv's DepthwiseSeparableConvModule with the BN folded: k x k, groups = channels."""
+
+    def __init__(self, c, k, stride=1, act="silu"):
+        super().__init__(c, c, k, stride, k // 2, groups=c)
+        self.act = act
+
+    def forward(self, x):
+        y = F.conv2d(x, self.weight, self.bias, self.stride, self.padding, 1, self.groups)
+        return silu(y) if self.act == "silu" else y
+
+
+class DWSepConvAct(nn.Module):
+    """mmcv's DepthwiseSeparableConvModule (both BNs folded): depthwise k x k (stride, pad k // 2) + bias + activation,
+    then pointwise 1x1 + bias + activation.  `forward` is the torch statement; the fast path runs the module as one
+    launch (YOLOX._forward_fast)."""
+
+    def __init__(self, cin, cout, k=3, stride=1, act="silu"):
+        super().__init__()
+        if k != 3:
+            raise ValueError("DWSepConvAct: a 3x3 depthwise convolution (5x5 is not built)")
+        self.depthwise_conv = DWConvAct(cin, k, stride, act)
+        self.pointwise_conv = ConvAct(cin, cout, 1, act=act)
+        self.act, self.stride = act, (stride, stride)
+
+    def forward(self, x):
+        return self.pointwise_conv(self.depthwise_conv(x))
+
+
+def conv3x3(cin, cout, stride=1, use_depthwise=False):
+    return DWSepConvAct(cin, cout, 3, stride) if use_depthwise else ConvAct(cin, cout, 3, stride)
+
+
 class DarknetBottleneck(nn.Module):
     """scp_layer.py:9-79 with expansion 1 (as CSPLayer builds it): 1x1, 3x3, + input behind the activation."""
 
-    def __init__(self, c, add_identity):
+    def __init__(self, c, add_identity, use_depthwise=False):
         super().__init__()
-        self.conv1, self.conv2 = ConvAct(c, c, 1), ConvAct(c, c, 3)
+        self.conv1, self.conv2 = ConvAct(c, c, 1), conv3x3(c, c, 1, use_depthwise)
         self.add_identity = add_identity
 
     def forward(self, x):
@@ -95,13 +142,13 @@ class DarknetBottleneck(nn.Module):
 class CSPLayer(nn.Module):
     """scp_layer.py:82-166: final_conv(cat(blocks(main_conv(x)), short_conv(x)))."""
 
-    def __init__(self, cin, cout, num_blocks, add_identity, groups_in=None):
+    def __init__(self, cin, cout, num_blocks, add_identity, groups_in=None, use_depthwise=False):
         super().__init__()
         mid = int(cout * 0.5)
         self.mid = mid
         self.main_conv, self.short_conv = ConvAct(cin, mid, 1, groups_in=groups_in), ConvAct(cin, mid, 1, groups_in=groups_in)
         self.final_conv = ConvAct(2 * mid, cout, 1, groups_in=(mid, mid))
-        self.blocks = nn.ModuleList([DarknetBottleneck(mid, add_identity) for _ in range(num_blocks)])
+        self.blocks = nn.ModuleList([DarknetBottleneck(mid, add_identity, use_depthwise) for _ in range(num_blocks)])
 
     def forward(self, x):
         short = self.short_conv(x)
@@ -168,16 +215,16 @@ class SPPBottleneck(nn.Module):
 class CSPDarknet(nn.Module):
     """csp_darknet.py's CSPDarknetQ, arch P5, out_indices (2, 3, 4): -> the outputs of stages 2, 3, 4."""
 
-    def __init__(self, deepen, widen):
+    def __init__(self, deepen, widen, use_depthwise=False):
         super().__init__()
         self.stem = Focus(int(ARCH_P5[0][0] * widen))
         self.stages = nn.ModuleList()
         for cin, cout, n, add_identity, use_spp in ARCH_P5:
             cin, cout = int(cin * widen), int(cout * widen)
-            stage = [ConvAct(cin, cout, 3, 2)]
+            stage = [conv3x3(cin, cout, 2, use_depthwise)]
             if use_spp:
                 stage.append(SPPBottleneck(cout, cout))
-            stage.append(CSPLayer(cout, cout, csp_blocks(n, deepen), add_identity))
+            stage.append(CSPLayer(cout, cout, csp_blocks(n, deepen), add_identity, use_depthwise=use_depthwise))
             self.stages.append(nn.Sequential(*stage))
 
     def forward(self, x):
@@ -204,16 +251,17 @@ class CSPDarknet(nn.Module):
 class YOLOXPAFPN(nn.Module):
     """mmdet's YOLOXPAFPN (add_identity False in its CSP layers)."""
 
-    def __init__(self, in_channels, out_channels, num_csp_blocks):
+    def __init__(self, in_channels, out_channels, num_csp_blocks, use_depthwise=False):
         super().__init__()
         c = tuple(in_channels)
         self.in_channels = c
         n = len(c)
         self.reduce_layers = nn.ModuleList([ConvAct(c[i], c[i - 1], 1) for i in range(n - 1, 0, -1)])
-        self.top_down_blocks = nn.ModuleList([CSPLayer(2 * c[i - 1], c[i - 1], num_csp_blocks, False, (c[i - 1], c[i - 1]))
+        self.top_down_blocks = nn.ModuleList([CSPLayer(2 * c[i - 1], c[i - 1], num_csp_blocks, False, (c[i - 1], c[i - 1]),
+                                                       use_depthwise)
                                               for i in range(n - 1, 0, -1)])
-        self.downsamples = nn.ModuleList([ConvAct(c[i], c[i], 3, 2) for i in range(n - 1)])
-        self.bottom_up_blocks = nn.ModuleList([CSPLayer(2 * c[i], c[i + 1], num_csp_blocks, False, (c[i], c[i]))
+        self.downsamples = nn.ModuleList([conv3x3(c[i], c[i], 2, use_depthwise) for i in range(n - 1)])
+        self.bottom_up_blocks = nn.ModuleList([CSPLayer(2 * c[i], c[i + 1], num_csp_blocks, False, (c[i], c[i]), use_depthwise)
                                                for i in range(n - 1)])
         self.out_convs = nn.ModuleList([ConvAct(ci, out_channels, 1) for ci in c])
 
@@ -262,10 +310,11 @@ class YOLOXHead(nn.Module):
     """mmdet's YOLOXHead.forward_single per level: cls_convs / reg_convs (two 3x3 ConvModules each), conv_cls on the
     first tower, conv_reg and conv_obj on the second."""
 
-    def __init__(self, num_classes, cin, feat, levels):
+    def __init__(self, num_classes, cin, feat, levels, use_depthwise=False):
         super().__init__()
         self.num_classes, self.feat = num_classes, feat
-        tower = lambda: nn.Sequential(ConvAct(cin, feat, 3), ConvAct(feat, feat, 3))   # noqa: E731
+        tower = lambda: nn.Sequential(conv3x3(cin, feat, 1, use_depthwise),           # noqa: E731
+                                      conv3x3(feat, feat, 1, use_depthwise))
         self.cls_convs = nn.ModuleList([tower() for _ in range(levels)])
         self.reg_convs = nn.ModuleList([tower() for _ in range(levels)])
         self.conv_cls = nn.ModuleList([nn.Conv2d(feat, num_classes, 1) for _ in range(levels)])
@@ -323,9 +372,11 @@ class YOLOX(nn.Module):
         self.ops = ops if ops is not None else _hip_ops
         if any(c % 32 for c in cfg["in_channels"]) or cfg["out_channels"] % 32 or cfg["feat_channels"] % 32:
             raise ValueError("YOLOX: the PAFPN and head widths are multiples of 32")
-        self.backbone = CSPDarknet(cfg["deepen"], cfg["widen"])
-        self.neck = YOLOXPAFPN(cfg["in_channels"], cfg["out_channels"], cfg["num_csp_blocks"])
-        self.bbox_head = YOLOXHead(cfg["num_classes"], cfg["out_channels"], cfg["feat_channels"], len(cfg["strides"]))
+        dw = bool(cfg.get("use_depthwise", False))
+        self.use_depthwise = dw
+        self.backbone = CSPDarknet(cfg["deepen"], cfg["widen"], dw)
+        self.neck = YOLOXPAFPN(cfg["in_channels"], cfg["out_channels"], cfg["num_csp_blocks"], dw)
+        self.bbox_head = YOLOXHead(cfg["num_classes"], cfg["out_channels"], cfg["feat_channels"], len(cfg["strides"]), dw)
         self._init_weights(seed)
         self.eval()
 
@@ -347,13 +398,16 @@ class YOLOX(nn.Module):
         logit map keeps a standard deviation above 0.2 and a maximum below 6.  Zero shifts."""
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
-                nn.init.normal_(m.weight, std=(2.0 / (m.in_channels * m.kernel_size[0] * m.kernel_size[1])) ** 0.5)
+                fan_in = m.in_channels // m.groups * m.kernel_size[0] * m.kernel_size[1]
+                nn.init.normal_(m.weight, std=(2.0 / fan_in) ** 0.5)
                 nn.init.zeros_(m.bias)
         half = {id(m.conv2): 0.5 for m in self.modules() if isinstance(m, DarknetBottleneck) and m.add_identity}
+        half.update({id(m.conv2.pointwise_conv): 0.5 for m in self.modules()
+                     if isinstance(m, DarknetBottleneck) and m.add_identity and isinstance(m.conv2, DWSepConvAct)})
 
         def scale(m, inputs):
-            y = F.conv2d(inputs[0], m.weight, None, m.stride, m.padding)
-            target = half.get(id(m), 1.0) * (INIT_PREACT_STD if isinstance(m, ConvAct) else 1.0)
+            y = F.conv2d(inputs[0], m.weight, None, m.stride, m.padding, 1, m.groups)
+            target = half.get(id(m), 1.0) * (INIT_PREACT_STD if isinstance(m, (ConvAct, DWConvAct)) else 1.0)
             m.weight.data.mul_(target / float(y.std().clamp_min(1e-12)))
 
         hooks = [m.register_forward_pre_hook(scale) for m in self.modules() if isinstance(m, nn.Conv2d)]
@@ -365,23 +419,38 @@ class YOLOX(nn.Module):
 
     # ---- the fast path's cached operands
     def _fast_on(self, x):
-        return x.is_cuda and x.dtype == torch.float16 and all(hasattr(self.ops, f) for f in _FAST_OPS) \
+        need = _FAST_OPS + (("dwsep_conv_taps",) if self.use_depthwise else ())
+        return x.is_cuda and x.dtype == torch.float16 and all(hasattr(self.ops, f) for f in need) \
             and next(self.parameters()).dtype == torch.float16
 
     def _build_operands(self):
         """{module or ("first" | "pred", level): (taps-major weight, bias)}: every ConvAct padded per channel group to a
         multiple of 32 (the stem's 12 input channels to Focus' 32), the head's stacked first tower convolutions and
-        block-diagonal predictors."""
+        block-diagonal predictors.  A DWSepConvAct (use_depthwise): (taps-major depthwise weight [3, 3, Cin], depthwise
+        bias, pointwise weight [Cout, Cin], pointwise bias), both widths padded to a multiple of 32 with zeros; its two
+        halves get no entry of their own, and the first tower convolutions are not stacked (their depthwise weights
+        differ)."""
         ops = {}
         head = self.bbox_head
+        inner = set()
         for m in self.modules():
-            if isinstance(m, ConvAct):
+            if isinstance(m, DWSepConvAct):
+                d, p = m.depthwise_conv, m.pointwise_conv
+                inner.add(p)
+                cin, cout = _Y.padded_width(d.in_channels), _Y.padded_width(p.out_channels)
+                wd, wp = _Y.dwsep_conv_packed_weight(d.weight, p.weight, cin, cout)
+                bd, bp = d.bias.detach().new_zeros((cin,)), p.bias.detach().new_zeros((cout,))
+                bd[:d.in_channels], bp[:p.out_channels] = d.bias.detach(), p.bias.detach()
+                ops[m] = (wd, bd, wp, bp)
+        for m in self.modules():
+            if isinstance(m, ConvAct) and m not in inner:
                 w, b = _Y.pad_channels(m.weight, m.bias, groups_in=m.groups_in)
                 ops[m] = (_taps(w), b.contiguous())
         for l in range(len(head.cls_convs)):
             a, r = head.cls_convs[l][0], head.reg_convs[l][0]
-            ops[("first", l)] = (_taps(torch.cat([a.weight.detach(), r.weight.detach()], 0)),
-                                 torch.cat([a.bias.detach(), r.bias.detach()], 0).contiguous())
+            if not self.use_depthwise:
+                ops[("first", l)] = (_taps(torch.cat([a.weight.detach(), r.weight.detach()], 0)),
+                                     torch.cat([a.bias.detach(), r.bias.detach()], 0).contiguous())
             w, b, slices = merge_yolox_predictors(*((c[l].weight, c[l].bias) for c in (head.conv_cls, head.conv_reg,
                                                                                       head.conv_obj)))
             ops[("pred", l)] = (_taps(w), b)
@@ -415,6 +484,8 @@ class YOLOX(nn.Module):
         ops, table = self.ops, self.operands(build=False)
 
         def run(conv, x, residual=None, out=None):
+            if isinstance(conv, DWSepConvAct):     # one launch for the depthwise and the pointwise half
+                return ops.dwsep_conv_taps(x, *table[conv], conv.act, conv.act, residual, conv.stride[0], out)
             w, b = table[conv]
             return ops.conv_slice_taps(x, w, b, conv.act, residual, conv.stride[0], out)
 
@@ -427,7 +498,12 @@ class YOLOX(nn.Module):
         head, feat = self.bbox_head, self.bbox_head.feat
         cls, reg, obj = [], [], []
         for l, x in enumerate(feats):
-            first = ops.conv_slice_taps(x, *table[("first", l)], "silu")
+            if self.use_depthwise:
+                first = _Y.nhwc_empty(B, 2 * feat, x.shape[2], x.shape[3], x.device)
+                run(head.cls_convs[l][0], x, out=first[:, :feat])
+                run(head.reg_convs[l][0], x, out=first[:, feat:])
+            else:
+                first = ops.conv_slice_taps(x, *table[("first", l)], "silu")
             second = _Y.nhwc_empty(B, 2 * feat, x.shape[2], x.shape[3], x.device)
             run(head.cls_convs[l][1], first[:, :feat], out=second[:, :feat])
             run(head.reg_convs[l][1], first[:, feat:], out=second[:, feat:])

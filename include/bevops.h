@@ -646,6 +646,29 @@ int bevops_conv_slice_f16(const void *x, int x_pitch, const void *weight_taps, c
 int bevops_conv_slice_f16_ex(const void *x, int x_pitch, const void *weight_taps, const void *bias, const void *residual,
                              int res_pitch, void *out, int out_pitch, int B, int H, int W, int Cin, int Cout, int ksize,
                              int stride, int act, int dilation, int bias_pitch, void *stream);
+/* A depthwise-separable layer in ONE launch on channel slices of channels-last fp16 tensors (csrc/dwsep_conv.hip; mmcv's
+ * DepthwiseSeparableConvModule with folded BatchNorms, the 3 x 3 layers of a YOLOX built with use_depthwise;
+ * design/yolox_depthwise.md).  Addressing as bevops_conv_slice_f16: base pointer of the slice, pitch in elements, every
+ * access a 16-byte vector inside its own slice.
+ *   t   = fp16( act_dw( dw3x3(x)[stride, pad 1] + bias_dw[c] ) )                  per input channel c, ONE rounding
+ *   out = fp16( act_pw( sum_c t[c] w_pw[co][c] + bias_pw[co] ) + residual )       ONE rounding, identity BEHIND the activation
+ * x [B, H, W] pixels of Cin channels; w_dw_taps fp16 [3][3][Cin] (taps-major); bias_dw fp16 [Cin], optional; w_pw fp16
+ * [Cout][Cin]; bias_pw fp16 [Cout], optional; residual optional, with its own pitch; out [B, Hout, Wout] pixels of Cout
+ * channels, Hout = (H - 1) / stride + 1.  stride in {1, 2}; act_dw, act_pw: 0 none, 1 ReLU, 2 SiLU (bevops_conv_slice_f16's).
+ * t is never written to memory: no workspace, no atomics.  The depthwise stage in fp32, per channel:
+ *   a = bias_dw[c] (0 without one); for ky = 0, 1, 2: for kx = 0, 1, 2: a = fma(x[s yo + ky - 1, s xo + kx - 1, c], w_dw[ky][kx][c], a)
+ * one FUSED multiply-add per tap inside the image; a tap outside it is skipped and never becomes an address.  Then the
+ * activation in fp32 and one rounding (RNE); these fp16 values are the matrix cores' operand (fp32 accumulation), so the
+ * launch equals two launches with an fp16 tensor between them.  x must not overlap out; out and residual may be the
+ * same slice; x and out may be disjoint slices of one buffer.  Zero weights and biases give exact zeros (pad channels).
+ * Statuses, in this order, before any device call.  BEVOPS_BAD_PARAM: NULL x / w_dw_taps / w_pw / out; B < 0 or a
+ * non-positive H / W / Cin / Cout / stride; a pitch below the channel count, or no multiple of 8; x / w_dw_taps / w_pw /
+ * out / residual / bias_dw not 16-byte aligned (bias_pw: 2 bytes).  BEVOPS_NOT_SUPPORTED: Cin % 32 != 0 or Cout % 8 != 0;
+ * stride > 2 or an activation outside the list; B H W x_pitch or Cout Cin at or above 0xFFFFFF00 bytes (32-bit buffer
+ * offsets).  B == 0: BEVOPS_SUCCESS without a launch. */
+int bevops_dwsep_conv_f16(const void *x, int x_pitch, const void *w_dw_taps, const void *bias_dw, const void *w_pw,
+                          const void *bias_pw, const void *residual, int res_pitch, void *out, int out_pitch, int B, int H,
+                          int W, int Cin, int Cout, int stride, int act_dw, int act_pw, void *stream);
 /* The layers of BEVDepth's DepthNet that are no convolution (csrc/lss_depthnet.hip; LSSViewTransformerBEVDepth,
  * bevformer_tensorrt_amd/bevdepth.py).  None allocates, synchronises or uses atomics; n == 0: BEVOPS_SUCCESS without a
  * launch.
