@@ -40,7 +40,8 @@ from .bev_half import lss_depth_split, upsample_bilinear_concat_nhwc, lss_depth_
 from .deconv import conv_transpose2d_nhwc, pack_deconv4x4s2, deconv_packed_weight, conv_transpose2d_q_nhwc, quantize_deconv_weight
 from .yolox_ops import (conv_slice_nhwc, conv_slice_taps, conv_slice_packed_weight, focus_nhwc, spp_maxpool_nhwc,
                         upsample_nearest2x_nhwc, pad_channels, unpad_channels, conv_slice_q_taps, focus_nhwc_q,
-                        quantize_weight_taps, dwsep_conv_nhwc, dwsep_conv_taps, dwsep_conv_packed_weight)
+                        quantize_weight_taps, dwsep_conv_nhwc, dwsep_conv_taps, dwsep_conv_packed_weight,
+                        dwsep_conv_q_taps, quantize_dwsep_weights)
 from .lss_depthnet import (lss_camera_gate, se_gate2_nhwc, global_avgpool_nhwc, pack_camera_gate, camera_gate_packed,
                            se_gate2_nhwc_q, global_avgpool_nhwc_q)
 from .deform_conv import deform_conv2d, deform_conv2d_nhwc, deform_conv2d_q_nhwc, deform_conv_packed_weight
@@ -84,7 +85,7 @@ __all__ = [
     "conv_slice_nhwc", "conv_slice_taps", "conv_slice_packed_weight", "focus_nhwc", "spp_maxpool_nhwc",
     "upsample_nearest2x_nhwc", "pad_channels", "unpad_channels",
     "conv_slice_q_taps", "focus_nhwc_q", "quantize_weight_taps",
-    "dwsep_conv_nhwc", "dwsep_conv_taps", "dwsep_conv_packed_weight",
+    "dwsep_conv_nhwc", "dwsep_conv_taps", "dwsep_conv_packed_weight", "dwsep_conv_q_taps", "quantize_dwsep_weights",
     "lss_camera_gate", "se_gate2_nhwc", "global_avgpool_nhwc", "pack_camera_gate", "camera_gate_packed",
     "se_gate2_nhwc_q", "global_avgpool_nhwc_q",
     "deform_conv2d", "deform_conv2d_nhwc", "deform_conv2d_q_nhwc", "deform_conv_packed_weight",

@@ -15,7 +15,8 @@ act(0 + 0) + 0 = 0 exactly, for every activation here, so it stays zero through 
 The INT8 flavours (the INT8 build of YOLOX, yolox_int8.py) live beside them: `conv_slice_q_taps`
 (bevops_conv_slice_s8, csrc/conv_slice_s8.hip), `focus_nhwc_q`, and `spp_maxpool_nhwc` / `upsample_nearest2x_nhwc`
 routed by dtype; an int8 slice's pitch is a multiple of 16 and c0 % 16 == 0.  `quantize_weight_taps` is their weight
-quantiser."""
+quantiser.  `dwsep_conv_q_taps` (bevops_dwsep_conv_s8, csrc/dwsep_conv_s8.hip) is the int8 depthwise-separable layer and
+`quantize_dwsep_weights` its weight quantiser."""
 import torch
 
 from ..utils import lib as _lib
@@ -523,6 +524,102 @@ def conv_slice_q_taps(x_q, scale_x, w_q_taps, w_scales, bias, act, residual_q=No
     _call("bevops_conv_slice_s8_ex", x_q.device, x_q.data_ptr(), xp, sx, w_q_taps.data_ptr(), _ptr(w_scales), 1.0,
           _ptr(bias), _ptr(residual_q), rp, sr, _lib.I8 if out8 else _lib.F16, out.data_ptr(), op, so, B, H, W, Cin, Cout, k,
           int(stride), ACTS[act], int(bool(res_first)))
+    return out
+
+
+def quantize_dwsep_weights(dw_weight, dw_bias, pw_weight, pw_bias, cin=None, cout=None):
+    """The int8 operands of dwsep_conv_q_taps for a depthwise weight [C, 1, 3, 3] and a pointwise weight [Cout, C, 1, 1]
+    (biases [C] / [Cout] or None), zero-padded behind the real channels to cin / cout (default: the next multiple of 32):
+    -> (w_dw_q int8 [3, 3, cin] taps-major, w_dw_scales fp32 [cin], bias_dw fp32 [cin], w_pw_q int8 [cout, cin],
+    w_pw_scales fp32 [cout], bias_pw fp32 [cout]).  Each channel -- a depthwise channel's nine taps, a pointwise row -- is
+    quantised by min-max after the padding, by `quantize_weight_taps`' rule: scale = amax / 127 in fp32 (1 for a channel
+    of zeros: the pad channels), q = clamp(rne(w / scale), -127, 127); pad weights and biases are exact zeros."""
+    if dw_weight.dim() != 4 or tuple(dw_weight.shape[1:]) != (1, 3, 3):
+        raise ValueError("dwsep_conv: dw_weight [C, 1, 3, 3]")
+    C = dw_weight.shape[0]
+    if pw_weight.dim() != 4 or tuple(pw_weight.shape[1:]) != (C, 1, 1):
+        raise ValueError("dwsep_conv: pw_weight [Cout, C, 1, 1] with the depthwise weight's C")
+    cin = padded_width(C) if cin is None else int(cin)
+    cout = padded_width(pw_weight.shape[0]) if cout is None else int(cout)
+    if cin < C or cout < pw_weight.shape[0]:
+        raise ValueError("dwsep_conv: fewer channels than the weights have")
+
+    def quant(w, b, rows):                     # w [n, k] fp32 -> rows x k int8, per-row scales, the padded bias
+        wp = w.new_zeros((rows, w.shape[1]))
+        wp[:w.shape[0]] = w
+        amax = wp.abs().amax(dim=1)
+        scales = torch.where(amax > 0, amax / 127.0, torch.ones_like(amax))
+        q = torch.clamp(torch.round(wp / scales[:, None]), -127, 127).to(torch.int8)
+        bp = wp.new_zeros((rows,))
+        if b is not None:
+            bp[:b.numel()] = b.detach().float()
+        return q, scales.contiguous(), bp
+
+    qd, sd, bd = quant(dw_weight.detach().float().reshape(C, 9), dw_bias, cin)
+    pw = pw_weight.detach().float()[:, :, 0, 0]
+    pwp = pw.new_zeros((pw.shape[0], cin))
+    pwp[:, :C] = pw
+    qp, sp, bp = quant(pwp, pw_bias, cout)
+    return qd.t().reshape(3, 3, cin).contiguous(), sd, bd, qp.contiguous(), sp, bp
+
+
+def dwsep_conv_q_taps(x_q, scale_x, w_dw_q, w_dw_scales, bias_dw, scale_t, w_pw_q, w_pw_scales, bias_pw, act_dw="silu",
+                      act_pw="silu", residual_q=None, scale_res=1.0, stride=1, out=None, scale_out=None,
+                      out_dtype=torch.int8):
+    """One launch of bevops_dwsep_conv_s8 (csrc/dwsep_conv_s8.hip) on ready operands, the int8 sibling of
+    `dwsep_conv_taps`:
+        t   = int8(act_dw(depthwise 3 x 3 (x_q) scale_x w_dw_scales[c] + bias_dw[c]) / scale_t)     (never in memory)
+        out = act_pw(t @ w_pw_q^T scale_t w_pw_scales[co] + bias_pw[co]) + residual_q scale_res      (identity BEHIND)
+    leaving as int8 requantised with scale_out, or as fp16 (out_dtype).  x_q [B, Cin, H, W], residual_q and out
+    [B, Cout, Hout, Wout]: int8 (out: out_dtype) CUDA channel slices; w_dw_q int8 [3, 3, Cin], w_pw_q int8 [Cout, Cin],
+    scales and biases fp32 [Cin] / [Cout] (`quantize_dwsep_weights`; the biases may be None); acts in "none", "relu",
+    "silu"; stride in {1, 2}; Cin % 32 == 0, Cout % 16 == 0 (int8 out) or % 8 (fp16 out), else BevopsError
+    NOT_SUPPORTED.  include/bevops.h states the operation order.  The errors are `conv_slice_q_taps`' for the same
+    faults.  Nothing is packed at call time: the call may be captured as it is."""
+    _check_s8(x_q, "x_q")
+    B, Cin, H, W = x_q.shape
+    for w, name, shape in ((w_dw_q, "w_dw_q [3, 3, Cin]", (3, 3, Cin)), (w_pw_q, "w_pw_q [Cout, Cin]", None)):
+        if w.dtype != torch.int8 or w.device != x_q.device or not w.is_contiguous() or \
+                (shape is not None and tuple(w.shape) != shape) or (shape is None and w.dim() != 2):
+            raise ValueError(f"dwsep_conv_q: {name} contiguous int8 on the input's device, got {tuple(w.shape)}")
+    Cout = w_pw_q.shape[0]
+    if w_pw_q.shape[1] != Cin:
+        raise ValueError(f"dwsep_conv_q: the pointwise weight has {w_pw_q.shape[1]} input channels, x_q has {Cin}")
+    if act_dw not in ACTS or act_pw not in ACTS:
+        raise ValueError(f"dwsep_conv_q: acts in {sorted(k for k in ACTS if k)}")
+    if out_dtype not in (torch.int8, torch.float16):
+        raise ValueError("dwsep_conv_q: out_dtype torch.int8 or torch.float16")
+    if out is not None and out.dtype != out_dtype:
+        raise ValueError(f"dwsep_conv_q: out is {out.dtype}, out_dtype {out_dtype}")
+    out8 = out_dtype == torch.int8
+    if stride not in (1, 2) or Cin % 32 or Cout % (16 if out8 else 8):
+        raise _lib.BevopsError("bevops_dwsep_conv_s8: stride in {1, 2}, Cin % 32 == 0, Cout % 16 == 0 (int8 out) or % 8 "
+                               "(fp16 out)", _lib.NOT_SUPPORTED)
+    sx, st = _scale(scale_x, "scale_x"), _scale(scale_t, "scale_t")
+    so = _scale(scale_out, "scale_out") if out8 else 1.0
+    for t, name, n, need in ((w_dw_scales, "w_dw_scales", Cin, True), (bias_dw, "bias_dw", Cin, False),
+                             (w_pw_scales, "w_pw_scales", Cout, True), (bias_pw, "bias_pw", Cout, False)):
+        if (t is None and need) or (t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or
+                                                        t.numel() != n or t.device != x_q.device)):
+            raise ValueError(f"dwsep_conv_q: {name} contiguous fp32 [{n}] on the input's device")
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    xp = slice_pitch(x_q, "x_q")
+    if out is None:
+        out = nhwc_empty(B, Cout, Ho, Wo, x_q.device, out_dtype)
+    elif tuple(out.shape) != (B, Cout, Ho, Wo) or out.device != x_q.device:
+        raise ValueError(f"dwsep_conv_q: out must be {(B, Cout, Ho, Wo)} on {x_q.device}, got {tuple(out.shape)}")
+    op = slice_pitch(out, "out")
+    rp, sr = 0, 1.0
+    if residual_q is not None:
+        _check_s8(residual_q, "residual_q")
+        if tuple(residual_q.shape) != tuple(out.shape):
+            raise ValueError("dwsep_conv_q: the identity has the output's shape")
+        rp, sr = slice_pitch(residual_q, "residual_q"), _scale(scale_res, "scale_res")
+    if B == 0:
+        return out
+    _call("bevops_dwsep_conv_s8", x_q.device, x_q.data_ptr(), xp, sx, w_dw_q.data_ptr(), w_dw_scales.data_ptr(),
+          _ptr(bias_dw), st, w_pw_q.data_ptr(), w_pw_scales.data_ptr(), 1.0, _ptr(bias_pw), _ptr(residual_q), rp, sr,
+          _lib.I8 if out8 else _lib.F16, out.data_ptr(), op, so, B, H, W, Cin, Cout, int(stride), ACTS[act_dw], ACTS[act_pw])
     return out
 
 

@@ -1220,7 +1220,10 @@ def _build_int8_bevdet_bev_half(model, qops, ch, dev, frames, calibration_cache,
     return q, qops, note
 
 
-def build_int8_yolox(Y, dev, images, calibrator="entropy", calibration_cache=None, cfg=None, ops=None):
+YOLOX_DEPTHWISE_BUILDS = (None, "int8")
+
+
+def build_int8_yolox(Y, dev, images, calibrator="entropy", calibration_cache=None, cfg=None, ops=None, depthwise=None):
     """The PTQ build of the re-hosted YOLOX (`Y` = the yolox module, or a yolox.YOLOX instance whose weights to
     quantise; `images` = an iterable of fp16 [B, 3, H, W] calibration images): every convolution of the backbone, the
     PAFPN and the head on bevops_conv_slice_s8, every tensor between two layers int8 with one scale per buffer
@@ -1228,10 +1231,17 @@ def build_int8_yolox(Y, dev, images, calibrator="entropy", calibration_cache=Non
     writes under one site; `calibrator` names any of CALIBRATORS.  calibration_cache: a path -- an existing cache is
     loaded INSTEAD of running frames, otherwise the collected statistics are saved there (the calibration-cache
     format of save_calibration / load_calibration).  Returns (model, note): model has forward / get_bboxes / prepare
-    like YOLOX, and YOLOXRunner captures it unchanged."""
+    like YOLOX, and YOLOXRunner captures it unchanged.
+    depthwise: what to do with a use_depthwise model (YOLOX-Nano).  None (the default): refuse it.  "int8": every
+    DepthwiseSeparableConvModule as ONE launch of bevops_dwsep_conv_s8 (functions.yolox_ops.dwsep_conv_q_taps,
+    design/yolox_depthwise_int8.md) -- both convolutions quantised, the int8 tensor between them never in memory, its scale
+    a per-layer calibration site of its own; the note gains "depthwise_layers".  A dense model builds the same with either
+    value.  Anything else: ValueError."""
     from . import yolox_int8 as _yi
+    if depthwise not in YOLOX_DEPTHWISE_BUILDS:
+        raise ValueError(f"build_int8_yolox: depthwise in {YOLOX_DEPTHWISE_BUILDS}, got {depthwise!r}")
     fp = Y if isinstance(Y, torch.nn.Module) else Y.YOLOX(cfg)
-    if fp.cfg.get("use_depthwise", False):
+    if fp.cfg.get("use_depthwise", False) and depthwise is None:
         raise NotImplementedError("build_int8_yolox: a use_depthwise model has no INT8 build (no int8 depthwise-separable "
                                   "kernel, design/yolox_depthwise.md)")
     fp = fp.to(dev, torch.float16)
@@ -1239,9 +1249,12 @@ def build_int8_yolox(Y, dev, images, calibrator="entropy", calibration_cache=Non
     _, num_groups = plan.groups()
     cal = get_calibrator(calibrator)()
     n = _calibrated(cal, calibration_cache, dev, lambda: _yi.calibrate(fp, images, cal, ops),
-                    lambda n: {"model": "yolox", "scale_groups": num_groups, "frames": n})
-    model = _yi.Int8YOLOX(fp, _yi.group_scales_from(cal, num_groups), ops)
+                    lambda n: dict({"model": "yolox", "scale_groups": num_groups, "frames": n},
+                                   **({"depthwise_layers": plan.num_dwsep} if plan.num_dwsep else {})))
+    model = _yi.Int8YOLOX(fp, _yi.group_scales_from(cal, num_groups), ops, _yi.dwsep_scales_from(cal, plan))
     note = {"int8_layers": model.num_int8_layers, "scale_groups": num_groups, "calibration_frames": n}
+    if plan.num_dwsep:
+        note["depthwise_layers"] = plan.num_dwsep
     return model, note
 
 

@@ -14,7 +14,14 @@ scale.  The two data movers that keep their input's scale merge groups: nearest 
 of its source joins the group of its destination (-> [up(high5) | c4] and [down1 | high5] share one scale, and so do
 [up(high4) | c3] and [down0 | high4]); the SPP pools write three quarters of the buffer their source is the first
 quarter of.  A group's calibration statistic is collected under ONE site name from every slice written into it, so it
-is the joint statistic of the union.  The three packed predictor outputs are fp16 and belong to no group."""
+is the joint statistic of the union.  The three packed predictor outputs are fp16 and belong to no group.
+
+use_depthwise (YOLOX-Nano; build_int8_yolox(depthwise="int8"), design/yolox_depthwise_int8.md).  A DWSepConvAct is ONE
+step of kind "dwsep" where the dense model has a "conv" step -- same source, destination, identity and stride -- on
+functions.yolox_ops.dwsep_conv_q_taps (csrc/dwsep_conv_s8.hip).  Its intermediate tensor never reaches memory, so it is
+no buffer and joins no group: it has a calibration SITE of its own (`dwsep_site`), a per-layer scale.  The head's first
+tower convolutions are two such steps writing the halves of one buffer (their depthwise weights differ), as in
+YOLOX._forward_fast.  A dense model's plan, groups, sites and operand table are what they were."""
 import torch
 import torch.nn.functional as F
 
@@ -37,15 +44,21 @@ class Ref:
 
 
 class Step:
-    """op in "focus", "conv", "pool", "up"; key: the operand-table key of a convolution."""
+    """op in "focus", "conv", "dwsep", "pool", "up"; key: the operand-table key of a convolution; dw: the index of a
+    "dwsep" step among the plan's (the index of its intermediate tensor's site and scale)."""
 
-    def __init__(self, op, src, dst, key=None, res=None, act=None, stride=1, ks=None):
+    def __init__(self, op, src, dst, key=None, res=None, act=None, stride=1, ks=None, dw=None):
         self.op, self.src, self.dst, self.key, self.res, self.act, self.stride, self.ks = op, src, dst, key, res, act, stride, ks
+        self.dw = dw
 
 
 class Plan:
     def __init__(self):
         self.bufs, self.steps, self.outputs = [], [], []    # bufs: (channels, div, "q" | "f16")
+
+    @property
+    def num_dwsep(self):
+        return sum(1 for s in self.steps if s.op == "dwsep")
 
     def new(self, C, div, kind="q"):
         self.bufs.append((C, div, kind))
@@ -81,12 +94,19 @@ def build_plan(model):
     P, pw = Plan(), _Y.padded_width
 
     def run(conv, x, residual=None, out=None, key=None, cout=None, act=None, kind="q"):
-        cout = pw(conv.out_channels) if cout is None else cout
+        dw = key is None and isinstance(conv, _yx.DWSepConvAct)   # one fused step: the dense step plus its own site
+        if cout is None:
+            cout = pw(conv.pointwise_conv.out_channels if dw else conv.out_channels)
         stride = conv.stride[0]
         if out is None:
             out = P.new(cout, x.div * stride, kind)
         assert out.C == cout and out.div == x.div * stride and (residual is None or residual.C == cout)
-        P.steps.append(Step("conv", x, out, conv if key is None else key, residual, conv.act if act is None else act, stride))
+        if dw:
+            assert act is None and x.C == pw(conv.depthwise_conv.in_channels)
+            P.steps.append(Step("dwsep", x, out, conv, residual, conv.act, stride, dw=P.num_dwsep))
+        else:
+            P.steps.append(Step("conv", x, out, conv if key is None else key, residual, conv.act if act is None else act,
+                                stride))
         return out
 
     def csp(layer, x, out=None):
@@ -135,7 +155,12 @@ def build_plan(model):
     feat = head.feat
     n_pred = (head.num_classes + 5 + _yx.HEAD_PACK_MULTIPLE - 1) // _yx.HEAD_PACK_MULTIPLE * _yx.HEAD_PACK_MULTIPLE
     for l, x in enumerate(feats):
-        first = run(head.cls_convs[l][0], x, key=("first", l), cout=2 * feat)
+        if model.use_depthwise:                    # two launches into the halves of one buffer
+            first = P.new(2 * feat, x.div)
+            run(head.cls_convs[l][0], x, out=first.part(0, feat))
+            run(head.reg_convs[l][0], x, out=first.part(feat))
+        else:
+            first = run(head.cls_convs[l][0], x, key=("first", l), cout=2 * feat)
         second = P.new(2 * feat, x.div)
         run(head.cls_convs[l][1], first.part(0, feat), out=second.part(0, feat))
         run(head.reg_convs[l][1], first.part(feat), out=second.part(feat))
@@ -147,18 +172,39 @@ def group_site(g):
     return f"yolox.group{g}"
 
 
+def dwsep_site(n):
+    return f"yolox.dwsep{n}.t"
+
+
+def site_name(g):
+    """The calibration site of what `run_plan` collects: a scale group (an int) or a depthwise layer's site (a str)."""
+    return g if isinstance(g, str) else group_site(g)
+
+
+def plan_sites(plan):
+    """Every calibration site of the plan: the scale groups, then the depthwise-separable layers' intermediates."""
+    return [group_site(g) for g in range(plan.groups()[1])] + [dwsep_site(n) for n in range(plan.num_dwsep)]
+
+
 def quantize_operands(model):
     """{key: (w_q_taps int8, w_scales fp32, bias fp32)} for every convolution of the plan, from the fp weights of
     `model`: per output channel min-max after the padding and merging of YOLOX._build_operands
-    (functions.yolox_ops.quantize_weight_taps)."""
-    table, head = {}, model.bbox_head
+    (functions.yolox_ops.quantize_weight_taps).  A DWSepConvAct: the six operands of
+    functions.yolox_ops.quantize_dwsep_weights, and no entry for its two halves."""
+    table, head, inner = {}, model.bbox_head, set()
     for m in model.modules():
-        if isinstance(m, _yx.ConvAct):
+        if isinstance(m, _yx.DWSepConvAct):
+            d, p = m.depthwise_conv, m.pointwise_conv
+            inner.add(p)
+            table[m] = _Y.quantize_dwsep_weights(d.weight, d.bias, p.weight, p.bias)
+    for m in model.modules():
+        if isinstance(m, _yx.ConvAct) and m not in inner:
             table[m] = _Y.quantize_weight_taps(m.weight, m.bias, groups_in=m.groups_in)
     for l in range(len(head.cls_convs)):
         a, r = head.cls_convs[l][0], head.reg_convs[l][0]
-        table[("first", l)] = _Y.quantize_weight_taps(torch.cat([a.weight.detach(), r.weight.detach()], 0),
-                                                      torch.cat([a.bias.detach(), r.bias.detach()], 0))
+        if not model.use_depthwise:
+            table[("first", l)] = _Y.quantize_weight_taps(torch.cat([a.weight.detach(), r.weight.detach()], 0),
+                                                          torch.cat([a.bias.detach(), r.bias.detach()], 0))
         w, b, slices = _yx.merge_yolox_predictors(*((c[l].weight, c[l].bias) for c in (head.conv_cls, head.conv_reg,
                                                                                       head.conv_obj)))
         table[("pred", l)] = _Y.quantize_weight_taps(w, b, multiple=_yx.HEAD_PACK_MULTIPLE)
@@ -166,12 +212,42 @@ def quantize_operands(model):
     return table
 
 
-def run_plan(plan, image, mode, ops, table, scales=None, collect=None):
+def float_operands(model):
+    """`quantize_operands`' table with the fp32 weights themselves and unit scales -- padded and merged alike, nothing
+    rounded: with it `run_plan(mode="emulate", scales=None)` is the plain model up to the fp32 summation order."""
+    table, head, fl = quantize_operands(model), model.bbox_head, {}
+    taps = lambda w: w.detach().float().permute(0, 2, 3, 1)    # noqa: E731
+    for k, v in table.items():
+        if isinstance(k, _yx.DWSepConvAct):
+            d, p = k.depthwise_conv, k.pointwise_conv
+            wd, wp = torch.zeros_like(v[0], dtype=torch.float32), torch.zeros_like(v[3], dtype=torch.float32)
+            wd[:, :, :d.in_channels] = d.weight.detach().float()[:, 0].permute(1, 2, 0)
+            wp[:p.out_channels, :d.in_channels] = p.weight.detach().float()[:, :, 0, 0]
+            fl[k] = (wd, torch.ones_like(v[1]), v[2], wp, torch.ones_like(v[4]), v[5])
+        elif isinstance(k, _yx.ConvAct):
+            fl[k] = (taps(_Y.pad_channels(k.weight, None, groups_in=k.groups_in)[0]), torch.ones_like(v[1]), v[2])
+        elif k == "slices":
+            fl[k] = v
+        elif k[0] == "first":
+            a, r = head.cls_convs[k[1]][0], head.reg_convs[k[1]][0]
+            fl[k] = (taps(torch.cat([a.weight, r.weight], 0)), torch.ones_like(v[1]), v[2])
+        else:
+            w = _yx.merge_yolox_predictors(*((c[k[1]].weight, c[k[1]].bias) for c in (head.conv_cls, head.conv_reg,
+                                                                                      head.conv_obj)))[0]
+            fl[k] = (taps(w), torch.ones_like(v[1]), v[2])
+    return fl
+
+
+def run_plan(plan, image, mode, ops, table, scales=None, collect=None, dw_scales=None):
     """One forward of `plan`.  mode "fp16": the fp16 fast path's calls (`table` = YOLOX.operands()); "int8": the int8
     operators (`table` = quantize_operands(), scales[g] per group); "emulate": the fp32 fake-quant statement of the int8
     run in torch ops alone (NCHW fp32 tensors holding q * scale; scales None: no activation is quantised).
     collect(group, written slice): called in "fp16" and "emulate" mode behind every write of a convolution or of Focus
-    into an int8 group's buffer.  -> the three packed predictor outputs [B, P, H, W]."""
+    into an int8 group's buffer.  A "dwsep" step: dw_scales[step.dw] is its intermediate tensor's scale ("int8", and
+    "emulate" with scales); the fused fp16 launch never exposes that tensor, so with `collect`, and only then, the "fp16"
+    mode also evaluates the layer's own depthwise_conv module on the real channels of the source view and calls
+    collect(dwsep_site(step.dw), that) -- calibration-time work in torch.  -> the three packed predictor outputs
+    [B, P, H, W]."""
     B, _, H, W = image.shape
     gid, _ = plan.groups()
     last = {}
@@ -207,11 +283,17 @@ def run_plan(plan, image, mode, ops, table, scales=None, collect=None):
             elif s.op == "conv":
                 w, b = table[s.key]
                 ops.conv_slice_taps(view(s.src), w, b, s.act, None if s.res is None else view(s.res), s.stride, dst)
+            elif s.op == "dwsep":
+                ops.dwsep_conv_taps(view(s.src), *table[s.key], s.act, s.act, None if s.res is None else view(s.res),
+                                    s.stride, dst)
+                if collect is not None:
+                    d = s.key.depthwise_conv
+                    collect(dwsep_site(s.dw), d(view(s.src)[:, :d.in_channels]))
             elif s.op == "pool":
                 ops.spp_maxpool_nhwc(view(s.src), out=dst, kernel_sizes=s.ks)
             else:
                 ops.upsample_nearest2x_nhwc(view(s.src), out=dst)
-            if collect is not None and s.op in ("focus", "conv") and gid[s.dst.buf] is not None:
+            if collect is not None and s.op in ("focus", "conv", "dwsep") and gid[s.dst.buf] is not None:
                 collect(gid[s.dst.buf], dst)
         elif mode == "int8":
             if s.op == "focus":
@@ -220,6 +302,13 @@ def run_plan(plan, image, mode, ops, table, scales=None, collect=None):
                 w, ws, b = table[s.key]
                 f16 = gid[s.dst.buf] is None
                 ops.conv_slice_q_taps(view(s.src), scale_of(s.src), w, ws, b, s.act,
+                                      None if s.res is None else view(s.res), 1.0 if s.res is None else scale_of(s.res),
+                                      s.stride, dst, None if f16 else scale_of(s.dst),
+                                      torch.float16 if f16 else torch.int8)
+            elif s.op == "dwsep":
+                wd, sd, bd, wp, sp, bp = table[s.key]
+                f16 = gid[s.dst.buf] is None
+                ops.dwsep_conv_q_taps(view(s.src), scale_of(s.src), wd, sd, bd, dw_scales[s.dw], wp, sp, bp, s.act, s.act,
                                       None if s.res is None else view(s.res), 1.0 if s.res is None else scale_of(s.res),
                                       s.stride, dst, None if f16 else scale_of(s.dst),
                                       torch.float16 if f16 else torch.int8)
@@ -241,11 +330,22 @@ def run_plan(plan, image, mode, ops, table, scales=None, collect=None):
                 if s.res is not None:
                     v = v + view(s.res)
                 dst.copy_(v if gid[s.dst.buf] is None else fq(v, s.dst))
+            elif s.op == "dwsep":
+                wd, sd, bd, wp, sp, bp = table[s.key]
+                act = (lambda v: _yx.silu(v)) if s.act == "silu" else (F.relu if s.act == "relu" else (lambda v: v))
+                wdf = (wd.float() * sd).permute(2, 0, 1)[:, None]
+                v = act(F.conv2d(view(s.src), wdf, bd, s.stride, 1, 1, wdf.shape[0]))
+                if scales is not None:
+                    v = fake_quant(v, dw_scales[s.dw])
+                v = act(F.conv2d(v, (wp.float() * sp[:, None])[:, :, None, None], bp))
+                if s.res is not None:
+                    v = v + view(s.res)
+                dst.copy_(v if gid[s.dst.buf] is None else fq(v, s.dst))
             elif s.op == "pool":
                 dst.copy_(torch.cat([F.max_pool2d(view(s.src), k, 1, k // 2) for k in s.ks], dim=1))
             else:
                 dst.copy_(F.interpolate(view(s.src), scale_factor=2, mode="nearest"))
-            if collect is not None and s.op in ("focus", "conv") and gid[s.dst.buf] is not None:
+            if collect is not None and s.op in ("focus", "conv", "dwsep") and gid[s.dst.buf] is not None:
                 collect(gid[s.dst.buf], dst)
         for r in (s.src, s.dst, s.res):
             if r is not None and last[r.buf] == i and r.buf not in keep:
@@ -265,23 +365,27 @@ def split_outputs(packed, slices):
 class Int8YOLOX(Int8Model):
     """`forward(image fp16 [B, 3, H, W])` -> YOLOX.forward's nine outputs (fp16 logits) through the int8 plan.
     fp: the fp16 yolox.YOLOX whose weights it quantises (kept: its parameters are this module's, and a weight reload
-    rebuilds the int8 operands); group_scales: one scale per scale group.  `forward`, `get_bboxes` and `prepare` as
-    YOLOX: YOLOXRunner captures and replays it unchanged."""
+    rebuilds the int8 operands); group_scales: one scale per scale group; dw_scales: one scale per depthwise-separable
+    step, in the plan's order (a use_depthwise model).  `forward`, `get_bboxes` and `prepare` as YOLOX: YOLOXRunner
+    captures and replays it unchanged."""
 
-    def __init__(self, fp, group_scales, ops=None):
+    def __init__(self, fp, group_scales, ops=None, dw_scales=()):
         super().__init__(fp)
         self.ops = ops if ops is not None else _hip_ops
         self.plan = build_plan(fp)
         self.group_of, self.num_groups = self.plan.groups()
         if len(group_scales) != self.num_groups:
             raise ValueError(f"Int8YOLOX: {self.num_groups} scale groups, {len(group_scales)} scales")
-        sites = [group_site(g) for g in range(self.num_groups)]
-        self._set_scales(dict(zip(sites, group_scales)), sites, what="group scale")
-        self.group_scales = [self.scales[s] for s in sites]
+        if len(dw_scales) != self.plan.num_dwsep:
+            raise ValueError(f"Int8YOLOX: {self.plan.num_dwsep} depthwise-separable layers, {len(dw_scales)} scales")
+        sites = plan_sites(self.plan)
+        self._set_scales(dict(zip(sites, list(group_scales) + list(dw_scales))), sites, what="group scale")
+        self.group_scales = [self.scales[s] for s in sites[:self.num_groups]]
+        self.dw_scales = [self.scales[s] for s in sites[self.num_groups:]]
 
     @property
     def num_int8_layers(self):
-        return sum(1 for s in self.plan.steps if s.op == "conv")
+        return sum(1 for s in self.plan.steps if s.op in ("conv", "dwsep"))
 
     def _quantize(self):
         return quantize_operands(self.fp)
@@ -297,7 +401,8 @@ class Int8YOLOX(Int8Model):
         if image.dim() != 4 or image.shape[1] != 3 or image.shape[2] % 32 or image.shape[3] % 32:
             raise ValueError(f"YOLOX: image [B, 3, H, W] with H and W multiples of 32, got {tuple(image.shape)}")
         table = self._ready(image, "an fp16 CUDA image")
-        packed = run_plan(self.plan, image.contiguous(), "int8", self.ops, table, self.group_scales)
+        packed = run_plan(self.plan, image.contiguous(), "int8", self.ops, table, self.group_scales,
+                          dw_scales=self.dw_scales)
         return split_outputs(packed, table["slices"])
 
     @torch.no_grad()
@@ -305,7 +410,7 @@ class Int8YOLOX(Int8Model):
         """The fp32 torch statement of `forward` (quantise and dequantise at every group with the same scales, the same
         per-channel weight quantisation): independent of the kernels.  -> nine fp32 outputs."""
         table = self.operands()
-        packed = run_plan(self.plan, image, "emulate", None, table, self.group_scales)
+        packed = run_plan(self.plan, image, "emulate", None, table, self.group_scales, dw_scales=self.dw_scales)
         return split_outputs(packed, table["slices"])
 
     def get_bboxes(self, outputs, img_metas, rescale=True):
@@ -316,7 +421,8 @@ class Int8YOLOX(Int8Model):
 
 def calibrate(fp, images, cal, ops=None):
     """Run the fp16 fast path of `fp` on `images` (an iterable of fp16 CUDA images), collecting every write into an
-    int8 group's buffer under the group's site.  -> the number of frames."""
+    int8 group's buffer under the group's site, and every depthwise-separable layer's intermediate tensor under the
+    layer's.  -> the number of frames."""
     ops = ops if ops is not None else _hip_ops
     plan = build_plan(fp)
     fp.prepare()
@@ -324,7 +430,7 @@ def calibrate(fp, images, cal, ops=None):
     with torch.no_grad():
         for image in images:
             run_plan(plan, image.contiguous(), "fp16", ops, fp.operands(),
-                     collect=lambda g, t: cal.collect(group_site(g), t))
+                     collect=lambda g, t: cal.collect(site_name(g), t))
             n += 1
     return n
 
@@ -332,4 +438,10 @@ def calibrate(fp, images, cal, ops=None):
 def group_scales_from(cal, num_groups):
     """One scale per scale group, in the order of the groups."""
     sites = [group_site(g) for g in range(num_groups)]
+    return list(scales_from(cal, sites, "build_int8_yolox").values())
+
+
+def dwsep_scales_from(cal, plan):
+    """One scale per depthwise-separable step of `plan`, in its order (none for a dense model)."""
+    sites = [dwsep_site(n) for n in range(plan.num_dwsep)]
     return list(scales_from(cal, sites, "build_int8_yolox").values())

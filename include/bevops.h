@@ -754,6 +754,40 @@ int bevops_conv_slice_s8(const void *x_q, int x_pitch, float scale_a, const void
                          float scale_w, const float *bias, const void *residual_q, int res_pitch, float scale_res,
                          int out_dtype, void *out, int out_pitch, float scale_out, int B, int H, int W, int Cin, int Cout,
                          int ksize, int stride, int act, void *stream);
+/* bevops_dwsep_conv_f16's INT8 sibling (csrc/dwsep_conv_s8.hip; the 3 x 3 layers of the INT8 build of a YOLOX with
+ * use_depthwise, design/yolox_depthwise_int8.md): depthwise 3 x 3 + pointwise 1 x 1, both quantised, in ONE launch on int8
+ * channel slices; the int8 tensor t between them lives only in LDS (no workspace, no atomics).  Both sums are exact int32:
+ *   sum_dw = sum_{ky,kx} x_q[b, s yo + ky - 1, s xo + kx - 1, c] w_dw_q[ky][kx][c]     (a tap outside the image adds 0)
+ *   sum    = sum_c t[b, yo, xo, c] w_pw_q[co][c]                                        (int8 matrix cores)
+ * and every step behind them is ONE fp32 operation in exactly this order (inv_t = 1.f / scale_t, inv_out = 1.f /
+ * scale_out and s_tw = scale_t * scale_w_pw are computed once on the host in fp32, one rounding each):
+ *   stage 1, per channel c:
+ *     sc = scale_x * w_dw_scales[c]
+ *     v  = fma((float)sum_dw, sc, bias_dw[c])          (|sum_dw| <= 9 * 127 * 127: (float) is exact; bias 0 when NULL)
+ *     v  = act_dw(v)                                   (0 none, 1 ReLU, 2 SiLU as bevops_conv_slice_s8)
+ *     t  = min(max(rne(v * inv_t), -127), 127)
+ *   stage 2, per output channel co: bevops_conv_slice_s8's epilogue with scale_a := scale_t
+ *     sc = s_tw * w_pw_scales[co] (s_tw when NULL);  v = fma((float)sum, sc, bias_pw[co]);  v = act_pw(v)
+ *     v  = fma((float)res_q, scale_res, v)             (with residual_q only: the identity BEHIND the activation)
+ *     BEVOPS_I8: q = min(max(rne(v * inv_out), -127), 127)      BEVOPS_F16: one rounding of v to binary16
+ * So the launch equals bevops_conv_slice_s8 (1 x 1) applied to the bytes t.  Non-finite values as there; a NaN in stage 1
+ * is t = -127 of its own channel and reaches the sums through column c of w_pw_q alone.
+ * x_q, residual_q, out: channel slices as in bevops_conv_slice_s8 (16-byte boundary, int8 pitch a multiple of 16, fp16
+ * out pitch a multiple of 8); x must not overlap out, out and residual_q may be the same slice.  w_dw_q_taps int8
+ * [3][3][Cin]; w_dw_scales fp32 [Cin] and bias_dw fp32 [Cin] (optional), read as 16-byte vectors; w_pw_q int8 [Cout][Cin];
+ * w_pw_scales, bias_pw fp32 [Cout], optional.  stride in {1, 2}, pad 1, Hout = (H - 1) / stride + 1.
+ * Statuses, in bevops_conv_slice_s8's order.  BEVOPS_BAD_PARAM: NULL x_q / w_dw_q_taps / w_dw_scales / w_pw_q / out, B < 0,
+ * non-positive H / W / Cin / Cout / stride.  BEVOPS_NOT_SUPPORTED: out_dtype outside the list.  BEVOPS_BAD_PARAM: a pitch
+ * below the channel count or no multiple of 16 (8); x_q / w_dw_q_taps / w_pw_q / out / residual_q / w_dw_scales / bias_dw
+ * not 16-byte aligned, w_pw_scales / bias_pw not 4-byte aligned; a scale in use (scale_x, scale_t, scale_w_pw; scale_res
+ * with residual_q; scale_out with int8 out) that is not positive and finite.  BEVOPS_NOT_SUPPORTED: stride > 2, an
+ * activation outside the list; Cin % 32 != 0, Cout % 16 != 0 (int8 out) or % 8 (fp16 out); B H W x_pitch or Cout Cin of
+ * 0xFFFFFF00 bytes or more.  B == 0: BEVOPS_SUCCESS without a launch. */
+int bevops_dwsep_conv_s8(const void *x_q, int x_pitch, float scale_x, const void *w_dw_q_taps, const float *w_dw_scales,
+                         const float *bias_dw, float scale_t, const void *w_pw_q, const float *w_pw_scales,
+                         float scale_w_pw, const float *bias_pw, const void *residual_q, int res_pitch, float scale_res,
+                         int out_dtype, void *out, int out_pitch, float scale_out, int B, int H, int W, int Cin, int Cout,
+                         int stride, int act_dw, int act_pw, void *stream);
 /* bevops_conv_slice_s8 with the identity IN FRONT of the activation when res_first != 0 (mmdet's BasicBlock,
  * relu(conv2(t) + identity); the INT8 build of CenterNet): the epilogue order becomes
  *   v = fma((float)sum, sc, bias[co]);  v = fma((float)res_q, scale_res, v);  v = act(v);  requantise / round
