@@ -127,6 +127,15 @@ BEVSTEREO_R50 = dict(BEVDET_R50, view_transformer="bevstereo", depthnet_cfg=dict
 # The reference tree has no BEVDet4D code or config: num_adj = 1 with pre_process is recalled (design/bevdet4d.md).
 BEVDET4D_R50 = dict(BEVDET_R50, temporal=dict(num_adj=1, pre_process=True))
 BEVDEPTH4D_R50 = dict(BEVDEPTH_R50, temporal=dict(num_adj=1, pre_process=True))
+# FlashOcc-R50 (BEVDetOCC with a 2-D BEV encoder and the channel-to-height head BEVOCCHead2D): BEVDet-R50 on a 200 x 200
+# grid of 0.4 m cells with ONE 6.4 m pillar, and the occupancy head instead of CenterPoint's: final_conv (3 x 3, ReLU),
+# predicter = Linear(256, 512) + Softplus + Linear(512, 16 * 18), arg-max over the 18 classes of each of the 16 height
+# bins.  The reference tree has no FlashOcc code or config: the values are recalled (design/flashocc.md).  Deviation: the
+# recalled depth grid [1, 45, 0.5] gives D = 88, and the merged depth_net operand of bev_half="hip" holds
+# D + 64 <= 128 columns (merge_depth_net); this keeps BEVDET_R50's depth grid (D = 59), as BEVSTEREO_R50 does.
+FLASHOCC_R50 = dict(BEVDET_R50, grid_config=dict(x=[-40.0, 40.0, 0.4], y=[-40.0, 40.0, 0.4], z=[-1.0, 5.4, 6.4],
+                                                 depth=[1.0, 60.0, 1.0]),
+                    occ_head=dict(Dz=16, num_classes=18, hidden=512))
 
 
 class LSSViewTransformer(nn.Module):
@@ -513,9 +522,18 @@ class BEVDet(nn.Module):
         self.bev_stages = nn.ModuleList(stages)
         self.neck_conv = nn.ModuleList([nn.Conv2d(chans[2] + chans[0], 512, 3, 1, 1), nn.Conv2d(512, 512, 3, 1, 1)])
         self.up2_conv = nn.ModuleList([nn.Conv2d(512, 256, 3, 1, 1), nn.Conv2d(256, 256, 1)])
-        self.shared_conv = nn.Conv2d(256, 64, 3, 1, 1)
-        self.heads = nn.ModuleDict({k: nn.ModuleList([nn.Conv2d(64, 64, 3, 1, 1), nn.Conv2d(64, n, 3, 1, 1)])
-                                    for k, n in HEADS_R50})
+        self.occ_cfg = cfg.get("occ_head")
+        if self.occ_cfg:      # FLASHOCC_R50: the occupancy head INSTEAD of CenterPoint's (BEVOCCHead2D's module names)
+            if self.num_adj:
+                raise NotImplementedError("temporal with occ_head (FlashOcc4D): not built; design/flashocc.md")
+            dz, ncls, hid = (int(self.occ_cfg[k]) for k in ("Dz", "num_classes", "hidden"))
+            self.final_conv = nn.Conv2d(256, 256, 3, 1, 1)
+            self.predicter = nn.Sequential(nn.Linear(256, hid), nn.Softplus(), nn.Linear(hid, dz * ncls))
+            self.heads = nn.ModuleDict()
+        else:
+            self.shared_conv = nn.Conv2d(256, 64, 3, 1, 1)
+            self.heads = nn.ModuleDict({k: nn.ModuleList([nn.Conv2d(64, 64, 3, 1, 1), nn.Conv2d(64, n, 3, 1, 1)])
+                                        for k, n in HEADS_R50})
         self.eval()
 
     def _nhwc_weights(self):
@@ -589,6 +607,13 @@ class BEVDet(nn.Module):
         self.__dict__["_heads_merged"] = (stamp, merged)
         return merged
 
+    def _head_operands(self, build=True):
+        """What the head's launches read beside the weights: `heads_merged`, or for an occupancy model the packed
+        predicter (functions.pack_occ_head).  build=False: None when missing or stale."""
+        if self.occ_cfg:
+            return getattr(self.ops, "pack_occ_head", _hip_ops.pack_occ_head)(*self._occ_weights(), build=build)
+        return self.heads_merged(build)
+
     def prepare_bev_half(self):
         """Build (or refresh) the merged operands of the "hip" BEV half on the device the weights live on: depth_net as
         a 128-column GEMM ([features | depth logits | zeros]), the six heads' first convolutions as one 64 -> 384
@@ -601,19 +626,54 @@ class BEVDet(nn.Module):
         if p.is_cuda and p.dtype == torch.float16 and hasattr(self.ops, "conv3x3_auto"):
             self._nhwc_weights()      # (what the first fp16 frame does to the filters; the merged operands follow them)
         self.view.depth_net_merged()
-        self.heads_merged()
+        self._head_operands()
         return self
 
     def _bev_half_ready(self, x):
         """True when the "hip" BEV half runs for activations like `x`, with its merged operands in place."""
+        if self._occ_fast(x) and self._head_operands(build=False) is None:
+            # (the occupancy launch runs for fp16 on the GPU whatever bev_half is: its pack is checked here, in front of
+            # the frame's first launch, on both routes)
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("BEVDet(occ_head): the packed predicter is missing or stale and the stream is capturing; "
+                                   "call prepare_bev_half() (or the model once, eagerly) before the capture")
+            self._head_operands()
         if not self._hip_on(x):
             return False
-        if self.view.depth_net_merged(build=False) is None or self.heads_merged(build=False) is None:
+        if self.view.depth_net_merged(build=False) is None or self._head_operands(build=False) is None:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("BEVDet(bev_half='hip'): the merged operands are missing or stale and the stream is "
                                    "capturing; call prepare_bev_half() (or the model once, eagerly) before the capture")
             self.prepare_bev_half()
         return True
+
+    # ---- the occupancy head (cfg["occ_head"], FLASHOCC_R50; design/flashocc.md)
+    def _occ_weights(self):
+        p = self.predicter
+        return p[0].weight, p[0].bias, p[2].weight, p[2].bias, int(self.occ_cfg["Dz"]), int(self.occ_cfg["num_classes"])
+
+    def _occ_fast(self, x):
+        """The occupancy head takes its launch for fp16 tensors on the GPU, whatever `bev_half` is."""
+        return bool(self.occ_cfg) and x.is_cuda and x.dtype == torch.float16 \
+            and hasattr(self.ops, "occ_head_nhwc") and hasattr(self.ops, "conv_nhwc")
+
+    def _occ(self, feat):
+        """BEVOCCHead2D on the BEV neck's map [B, 256, H, W]: final_conv + ReLU, the library's permute (B, C, H, W) ->
+        (B, W, H, C), the predicter, the view [.., Dz, classes] and the arg-max (softmax is monotonic: not computed)
+        -> occ [B, W, H, Dz] uint8: the SECOND axis is the map's W.  fp16 on the GPU: final_conv on the tiled 3 x 3
+        kernel by rule, then ONE launch of functions.occ_head_nhwc that writes the permuted bytes itself; everything else:
+        the torch statement (functions.occ_head_plain)."""
+        w, ops = self._occ_weights(), self.ops
+        if self._occ_fast(feat):
+            packed = self._head_operands()         # (cached; `_bev_half_ready` looked at it before the frame's first launch)
+            feat = feat.contiguous(memory_format=torch.channels_last)
+            y = ops.conv_nhwc(feat, self.final_conv.weight, self.final_conv.bias, True)
+            B, _, H, W = y.shape
+            occ = torch.empty((B, W, H, w[4]), dtype=torch.uint8, device=y.device)
+            ops.occ_head_nhwc(y, packed, out=occ.permute(0, 2, 1, 3))
+            return occ
+        y = F.relu(F.conv2d(feat, self.final_conv.weight, self.final_conv.bias, 1, 1))
+        return _hip_ops.occ_head_plain(y, *w).permute(0, 2, 1, 3).contiguous()
 
     def _heads_hip(self, feat):
         """shared_conv, then the six heads as two launches of the tiled implicit GEMM BY RULE (functions.conv_nhwc, not
@@ -624,6 +684,10 @@ class BEVDet(nn.Module):
         s = _conv(ops, feat, self.shared_conv, True)
         packed = ops.conv_nhwc(ops.conv_nhwc(s, w1, b1, True), w2, b2, False)
         return tuple(packed[:, a:b] for a, b in slices)
+
+    def _tail_hip(self, feat):
+        """Behind the BEV neck on the "hip" route: the occupancy head, or the CenterPoint heads."""
+        return self._occ(feat) if self.occ_cfg else self._heads_hip(feat)
 
     def bev_encoder(self, x):
         ops = self.ops
@@ -661,17 +725,21 @@ class BEVDet(nn.Module):
                 x, skw = self._frame_features(image.flatten(0, 1), stereo_metas)
                 bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths,
                                                **kw, **skw)
-                return self._heads_hip(self.bev_encoder(self._single_frame_stack(bev)))
+                return self._tail_hip(self.bev_encoder(self._single_frame_stack(bev)))
         x, skw = self._frame_features(image.flatten(0, 1), stereo_metas)
         kw.update(skw)
         bev = self.view.view_transform(x, ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, **kw)
         feat = self.bev_encoder(self._single_frame_stack(bev))
+        if self.occ_cfg:
+            return self._occ(feat)
         ops = self.ops
         s = _conv(ops, feat, self.shared_conv, True)
         return tuple(_conv(ops, _conv(ops, s, h[0], True), h[1]) for h in (self.heads[k] for k, _ in HEADS_R50))
 
     def _heads(self, bev):
         feat = self.bev_encoder(bev)
+        if self.occ_cfg:
+            return self._occ(feat)
         ops = self.ops
         s = _conv(ops, feat, self.shared_conv, True)
         return tuple(_conv(ops, _conv(ops, s, h[0], True), h[1]) for h in (self.heads[k] for k, _ in HEADS_R50))
@@ -700,7 +768,7 @@ class BEVDet(nn.Module):
         skw = {} if stereo_metas is None else dict(stereo_metas=stereo_metas)
         if self._bev_half_ready(x) if hip is None else hip:
             with _rule_dispatch():
-                return self._heads_hip(self.bev_encoder(self.view.view_transform_calibrated(x, calib, **skw)))
+                return self._tail_hip(self.bev_encoder(self.view.view_transform_calibrated(x, calib, **skw)))
         return self._heads(self.view.view_transform_calibrated(x, calib, **skw))
 
     # ---- BEVDet4D (cfg["temporal"]): functions.bev_align_stack between the pooling and the BEV encoder
@@ -750,7 +818,7 @@ class BEVDet(nn.Module):
         stacked = fn(curr, hist, meta, self.num_adj)
         if hip:
             with _rule_dispatch():
-                return self._heads_hip(self.bev_encoder(stacked))
+                return self._tail_hip(self.bev_encoder(stacked))
         return self._heads(stacked)
 
     def new_history(self, batch, device, dtype):
@@ -774,6 +842,8 @@ class BEVDet(nn.Module):
         the rotated scale-NMS of CenterHead.get_task_detections (`get_bboxes`).  padded=True: (boxes
         [B, 500, 9], scores [B, 500], labels [B, 500] int32, count [B] int32) without a host synchronisation; else one
         {"bboxes", "scores", "labels"} per batch item, trimmed (labels float32, as the reference's)."""
+        if getattr(self, "occ_cfg", None):      # (getattr: the INT8 models borrow this method)
+            raise RuntimeError("get_candidates: an occupancy model (cfg occ_head) has no CenterPoint heads; forward returns occ")
         reg, height, dim, rot, vel, heatmap = outputs
         out = self.bbox_coder.decode_heads(reg, height, dim, rot, vel, heatmap, norm_bbox=True)
         if padded:
@@ -792,6 +862,8 @@ class BEVDet(nn.Module):
         [bboxes [n, 9], scores [n], labels [n] int32] per batch item, as the reference returns them -- the boxes as a
         plain tensor: the `box_type_3d` wrapper class of the reference is not re-hosted.  A multi-task head would add
         its class offset to the labels (centerpoint_head.py:800-804); that bookkeeping is the caller's."""
+        if getattr(self, "occ_cfg", None):      # (getattr: the INT8 models borrow this method)
+            raise RuntimeError("get_bboxes: an occupancy model (cfg occ_head) has no CenterPoint heads; forward returns occ")
         from .functions.nms import bev_nms
         cfg = self.test_cfg
         boxes, scores, labels, count = self.get_candidates(outputs, padded=True)
@@ -834,6 +906,8 @@ class BEVDetRunner:
                  data_config=None, batch=1):
         if post not in (None, "candidates", "bboxes"):
             raise ValueError(f"post = {post!r}: None, 'candidates' or 'bboxes'")
+        if post is not None and getattr(model, "occ_cfg", None):
+            raise ValueError(f"post = {post!r}: an occupancy model has no boxes to decode (post=None)")
         if int(batch) != batch or batch < 1:
             raise ValueError(f"batch = {batch!r}: a positive integer")
         self.batch = int(batch)
@@ -959,6 +1033,8 @@ class BEVDetRunner:
             self._capture(raw)
         graph, outs = (self._graph_raw, self._outs_raw) if raw else (self._graph, self._outs)
         graph.replay()
+        if torch.is_tensor(outs):                           # (an occupancy model: occ)
+            return outs.clone() if self.clone_outputs else outs
         return tuple(t.clone() for t in outs) if self.clone_outputs else outs
 
 

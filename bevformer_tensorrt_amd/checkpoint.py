@@ -386,3 +386,15 @@ def pre_process_key_map(model, prefix="pre_process_net.layers.0."):
             m[f"pre_process_net.{i}.conv{k}.weight"] = m[f"pre_process_net.{i}.conv{k}.bias"] = \
                 _conv_bn(f"{prefix}{i}.conv{k}", f"{prefix}{i}.bn{k}")
     return m
+
+
+def occ_head_key_map(model, prefix="occ_head."):
+    """`reference_key_map` entries for the occupancy head of a bevdet.BEVDet built with cfg occ_head (FLASHOCC_R50), under
+    the names FlashOcc's BEVOCCHead2D registers (recalled, the reference tree has no FlashOcc code: design/flashocc.md):
+    `occ_head.final_conv.conv.*` (a ConvModule without a norm layer) and `occ_head.predicter.{0,2}.*`.  {} for a model
+    without the head."""
+    if not getattr(model, "occ_cfg", None):
+        return {}
+    m = {f"final_conv.{n}": f"{prefix}final_conv.conv.{n}" for n in ("weight", "bias")}
+    m.update({f"predicter.{i}.{n}": f"{prefix}predicter.{i}.{n}" for i in (0, 2) for n in ("weight", "bias")})
+    return m

@@ -49,6 +49,7 @@ from .stereo import (stereo_calibration, stereo_frustum_tables, stereo_grid, ste
                      stereo_cost_volume_plain)
 from .bev_align import (bev_align_transform, bev_align_stack, bev_align_stack_plain, bev_align_stack_q_plain,
                         pack_bev_align_meta, unpack_bev_align_meta, bev_align_meta_words)
+from .occ_head import pack_occ_head, occ_head_nhwc, occ_head_plain
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -93,4 +94,5 @@ __all__ = [
     "stereo_cost_volume_plain",
     "bev_align_transform", "bev_align_stack", "bev_align_stack_plain", "bev_align_stack_q_plain", "pack_bev_align_meta",
     "unpack_bev_align_meta", "bev_align_meta_words",
+    "pack_occ_head", "occ_head_nhwc", "occ_head_plain",
 ]

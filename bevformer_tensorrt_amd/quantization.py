@@ -1121,6 +1121,9 @@ def build_int8_bevdet(D, dev, frames, calibrator="entropy", bev_half="fp16", cal
         raise ValueError("build_int8_bevdet: calibration_cache goes with bev_half='int8'")
     src = D if isinstance(D, torch.nn.Module) else None
     model_cfg = (getattr(src, "cfg", None) if src is not None else cfg) or {}
+    if model_cfg.get("occ_head"):
+        raise NotImplementedError("build_int8_bevdet: an occupancy model (cfg occ_head, FLASHOCC_R50: the predictor and its "
+                                  "arg-max launch) has no INT8 build (design/flashocc.md)")
     temporal = bool(model_cfg.get("temporal"))
     if temporal and bev_half != "int8":
         raise NotImplementedError("build_int8_bevdet: a temporal model (BEVDet4D / BEVDepth4D: bev_align_stack and the "

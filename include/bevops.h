@@ -669,6 +669,32 @@ int bevops_conv_slice_f16_ex(const void *x, int x_pitch, const void *weight_taps
 int bevops_dwsep_conv_f16(const void *x, int x_pitch, const void *w_dw_taps, const void *bias_dw, const void *w_pw,
                           const void *bias_pw, const void *residual, int res_pitch, void *out, int out_pitch, int B, int H,
                           int W, int Cin, int Cout, int stride, int act_dw, int act_pw, void *stream);
+/* FlashOcc's occupancy predictor in ONE launch (csrc/occ_head.hip; BEVOCCHead2D behind final_conv, the occ_head of
+ * bevformer_tensorrt_amd/bevdet.py; design/flashocc.md).  Per row m = (b H + yy) W + xx of y (channels-last fp16, C
+ * channels at base + m y_pitch, pitch in elements):
+ *   h[j]     = fp16( softplus( b1[j] + sum_c y[m][c] W1[j][c] ) )       fp32 sum, fp32 Softplus, ONE rounding (RNE)
+ *   logit[n] = b2[n] + sum_j h[j] W2[n][j]                              fp32; n = z Ncls + cls, class fastest
+ *   occ[z]   = the LOWEST cls whose logit[z Ncls + cls] is the largest of voxel z, compared in fp32
+ * softplus(v) is v itself for v > 20 (bit for bit) and ln2 log2(1 + exp2(v log2e)) on the hardware exp2 / log2 otherwise.
+ * The row's Dz bytes go to occ + b occ_stride_image + yy occ_stride_line + xx occ_stride_pixel (bytes; one 16-byte store
+ * when Dz == 16 and occ and the three strides are multiples of 16); logits, when not NULL, receives fp16(logit) as a dense
+ * [B H W][Dz Ncls] matrix, and with NULL nothing but occ is written.  No workspace, no atomics; h and (without `logits`)
+ * the logits never reach memory; a row's result depends on its own operands only.
+ * w1 fp16 [Hd][C]; b1 fp16 [Hd]; w2_packed fp16 [Hd / 64][32 nb][64] and b2_packed fp16 [32 nb] with
+ * nb = bevops_occ_head_blocks(Dz, Ncls) = ceil(ceil(Dz / 2) Ncls / 16) (0 outside the domain): physical row
+ * P = 32 i + 8 g + 4 hb + c is slot t = 16 i + 4 g + c of half hb, that is voxel z = 2 (t / Ncls) + hb, class t % Ncls
+ * (a zero row where z >= Dz), and position j = 32 i + 16 p + 8 hb + 4 q + c of slab s is W2[.][64 s + 32 i + 16 p + 8 q +
+ * 4 hb + c] (functions.occ_head.pack_occ_head).
+ * Statuses, in this order, before any device call.  BEVOPS_BAD_PARAM: NULL y / w1 / b1 / w2_packed / b2_packed / occ; B < 0
+ * or a non-positive H / W / C / Hd / Dz / Ncls; y_pitch below C or no multiple of 8; occ_stride_pixel below Dz or a
+ * negative line / image stride; y / w1 / b1 / w2_packed / b2_packed not 16-byte aligned (logits: 2 bytes).
+ * BEVOPS_NOT_SUPPORTED: C % 32 != 0 or C > 256; Hd % 64 != 0 or Hd > 1024; Dz > 16, Ncls > 32 or Dz Ncls > 320; H W at or
+ * above 2^31.  B == 0: BEVOPS_SUCCESS without a launch. */
+int bevops_occ_head_blocks(int Dz, int Ncls);
+int bevops_occ_head_f16(const void *y, int y_pitch, const void *w1, const void *b1, const void *w2_packed,
+                        const void *b2_packed, void *occ, long long occ_stride_image, long long occ_stride_line,
+                        long long occ_stride_pixel, void *logits, int B, int H, int W, int C, int Hd, int Dz, int Ncls,
+                        void *stream);
 /* The layers of BEVDepth's DepthNet that are no convolution (csrc/lss_depthnet.hip; LSSViewTransformerBEVDepth,
  * bevformer_tensorrt_amd/bevdepth.py).  None allocates, synchronises or uses atomics; n == 0: BEVOPS_SUCCESS without a
  * launch.
