@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from . import functions as _hip_ops
 from .functions import dispatch as _dispatch
+from .functions.depth_head import depth_head_supported as _depth_head_supported
 from .functions.multi_scale_deformable_attn import _TensorCache
 from .graph_runner import capture
 
@@ -130,12 +131,14 @@ BEVDEPTH4D_R50 = dict(BEVDEPTH_R50, temporal=dict(num_adj=1, pre_process=True))
 # FlashOcc-R50 (BEVDetOCC with a 2-D BEV encoder and the channel-to-height head BEVOCCHead2D): BEVDet-R50 on a 200 x 200
 # grid of 0.4 m cells with ONE 6.4 m pillar, and the occupancy head instead of CenterPoint's: final_conv (3 x 3, ReLU),
 # predicter = Linear(256, 512) + Softplus + Linear(512, 16 * 18), arg-max over the 18 classes of each of the 16 height
-# bins.  The reference tree has no FlashOcc code or config: the values are recalled (design/flashocc.md).  Deviation: the
-# recalled depth grid [1, 45, 0.5] gives D = 88, and the merged depth_net operand of bev_half="hip" holds
-# D + 64 <= 128 columns (merge_depth_net); this keeps BEVDET_R50's depth grid (D = 59), as BEVSTEREO_R50 does.
+# bins.  The reference tree has no FlashOcc code or config: the values are recalled (design/flashocc.md).  FLASHOCC_R50 keeps
+# BEVDET_R50's depth grid (D = 59), as BEVSTEREO_R50 does; FLASHOCC_R50_D88 has the recalled depth grid [1, 45, 0.5],
+# D = 88: D + 64 columns are more than the merged depth_net operand of bev_half="hip" holds (merge_depth_net: 128), so
+# its view transformer's front is the one launch of functions.lss_depth_head (design/depth_head.md).
 FLASHOCC_R50 = dict(BEVDET_R50, grid_config=dict(x=[-40.0, 40.0, 0.4], y=[-40.0, 40.0, 0.4], z=[-1.0, 5.4, 6.4],
                                                  depth=[1.0, 60.0, 1.0]),
                     occ_head=dict(Dz=16, num_classes=18, hidden=512))
+FLASHOCC_R50_D88 = dict(FLASHOCC_R50, grid_config=dict(FLASHOCC_R50["grid_config"], depth=[1.0, 45.0, 0.5]))
 
 
 class LSSViewTransformer(nn.Module):
@@ -314,13 +317,23 @@ class LSSViewTransformer(nn.Module):
         return prepare(self._frustum_on(calib.device), calib, self.grid_lower_bound, self.grid_interval, self.grid_size,
                        padded=padded)
 
-    # ---- bev_half = "hip": depth_net as one 128-column GEMM, softmax + split as one launch, no layout copies
+    # ---- bev_half = "hip": depth_net as one 128-column GEMM, softmax + split as one launch, no layout copies; a depth
+    # grid too fine for the 128 columns: GEMM, softmax and split as ONE launch (functions.lss_depth_head)
+    def _depth_head_fused(self):
+        """True where `merge_depth_net` refuses the shape (C rounded up to 8, + D > 128 columns): the fused launch's."""
+        return (self.out_channels + 7) // 8 * 8 + self.D > DEPTH_NET_COLUMNS
+
     def _hip_on(self, x):
         """"hip" takes effect for channels-last fp16 CUDA activations on an operator set that has the new functions and
-        a plain depth_net (an INT8 build's operator set / quantised layer keep the torch statements)."""
-        return self.bev_half == "hip" and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 \
-            and x.is_contiguous(memory_format=torch.channels_last) and type(self.depth_net) is nn.Conv2d \
-            and all(hasattr(self.ops, f) for f in ("lss_depth_split", "dense_auto"))
+        a plain depth_net (an INT8 build's operator set / quantised layer keep the torch statements).  A wide depth_net
+        (`_depth_head_fused`): an operator set with lss_depth_head and a shape inside that kernel's domain."""
+        if not (self.bev_half == "hip" and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4
+                and x.is_contiguous(memory_format=torch.channels_last) and type(self.depth_net) is nn.Conv2d):
+            return False
+        if self._depth_head_fused():
+            return hasattr(self.ops, "lss_depth_head") \
+                and _depth_head_supported(self.in_channels, self.out_channels, self.D)
+        return all(hasattr(self.ops, f) for f in ("lss_depth_split", "dense_auto"))
 
     def _depth_net_sources(self):
         return [self.depth_net.weight] + ([] if self.depth_net.bias is None else [self.depth_net.bias])
@@ -328,7 +341,11 @@ class LSSViewTransformer(nn.Module):
     def depth_net_merged(self, build=True):
         """(weight [128, Cin], bias [128], layout) of `merge_depth_net` on the device of depth_net's weight, cached and
         rebuilt when the weight or bias changes (stamped like functions.conv.pack_taps' cache).  build=False: None when
-        the cached operand is missing or stale."""
+        the cached operand is missing or stale.  A wide depth_net (`_depth_head_fused`): the fused launch's pack
+        (functions.pack_depth_head, its own cache) instead."""
+        if self._depth_head_fused():
+            pack = getattr(self.ops, "pack_depth_head", _hip_ops.pack_depth_head)
+            return pack(self.depth_net.weight, self.depth_net.bias, self.D, self.out_channels, build=build)
         stamp = tuple(_TensorCache._stamp(t) for t in self._depth_net_sources())
         hit = self.__dict__.get("_depth_net_merged")
         if hit is not None and hit[0] == stamp:
@@ -340,16 +357,19 @@ class LSSViewTransformer(nn.Module):
         return merged
 
     def _depth_feat_hip(self, x):
-        """x [N, Cin, H, W] channels-last fp16 -> (depth [N, D, H, W], feat [N, H, W, C]): two launches."""
+        """x [N, Cin, H, W] channels-last fp16 -> (depth [N, D, H, W], feat [N, H, W, C]): two launches, ONE for a wide
+        depth_net (`_depth_head_fused`)."""
         merged = self.depth_net_merged(build=False)
         if merged is None:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("LSSViewTransformer: the merged depth_net operand is missing or stale and the stream "
                                    "is capturing; call BEVDet.prepare_bev_half() (or the model once, eagerly) first")
             merged = self.depth_net_merged()
-        w, b, lay = merged
         n, cin, h, wd = x.shape
         rows = x.permute(0, 2, 3, 1).reshape(n * h * wd, cin)        # (a view: channels-last)
+        if self._depth_head_fused():
+            return self.ops.lss_depth_head(rows, merged, n, spatial=(h, wd))
+        w, b, lay = merged
         with _rule_dispatch():
             y = self.ops.dense_auto(rows, w, b, None, False)
         return self.ops.lss_depth_split(y, n, self.D, self.out_channels, lay["depth_offset"], lay["feat_offset"],
@@ -616,8 +636,8 @@ class BEVDet(nn.Module):
 
     def prepare_bev_half(self):
         """Build (or refresh) the merged operands of the "hip" BEV half on the device the weights live on: depth_net as
-        a 128-column GEMM ([features | depth logits | zeros]), the six heads' first convolutions as one 64 -> 384
-        convolution, their final convolutions as one block-diagonal 384 -> 32 convolution.  Allocates and copies, so it
+        a 128-column GEMM ([features | depth logits | zeros]; a wider one: functions.pack_depth_head), the six heads'
+        first convolutions as one 64 -> 384 convolution, their final convolutions as one block-diagonal 384 -> 32 convolution.  Allocates and copies, so it
         must run OUTSIDE stream capture; `forward` / `forward_calibrated` call it themselves when the operands are
         missing or a source weight changed, and raise RuntimeError when that happens on a capturing stream."""
         p = next(self.parameters())

@@ -50,6 +50,7 @@ from .stereo import (stereo_calibration, stereo_frustum_tables, stereo_grid, ste
 from .bev_align import (bev_align_transform, bev_align_stack, bev_align_stack_plain, bev_align_stack_q_plain,
                         pack_bev_align_meta, unpack_bev_align_meta, bev_align_meta_words)
 from .occ_head import pack_occ_head, occ_head_nhwc, occ_head_plain
+from .depth_head import pack_depth_head, lss_depth_head, lss_depth_head_plain
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -95,4 +96,5 @@ __all__ = [
     "bev_align_transform", "bev_align_stack", "bev_align_stack_plain", "bev_align_stack_q_plain", "pack_bev_align_meta",
     "unpack_bev_align_meta", "bev_align_meta_words",
     "pack_occ_head", "occ_head_nhwc", "occ_head_plain",
+    "pack_depth_head", "lss_depth_head", "lss_depth_head_plain",
 ]

@@ -139,6 +139,7 @@ SIGNATURES = {
     "bevops_occ_head_blocks": (c_int, [c_int, c_int]),
     "bevops_occ_head_f16": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [ctypes.c_longlong] * 3 + [c_void_p] + [c_int] * 7 +
                             [c_void_p]),
+    "bevops_lss_depth_head_f16": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
     "bevops_lss_camera_gate_packed_size": (c_size_t, [c_int]),
     "bevops_lss_camera_gate": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "bevops_se_gate2_nhwc": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),

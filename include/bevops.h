@@ -695,6 +695,26 @@ int bevops_occ_head_f16(const void *y, int y_pitch, const void *w1, const void *
                         const void *b2_packed, void *occ, long long occ_stride_image, long long occ_stride_line,
                         long long occ_stride_pixel, void *logits, int B, int H, int W, int C, int Hd, int Dz, int Ncls,
                         void *stream);
+/* The front of a plain LSS view transformer in ONE launch (csrc/depth_head.hip; LSSViewTransformer's depth_net, softmax
+ * and split, bevformer_tensorrt_amd/bevdet.py; design/depth_head.md).  Per pixel row m = i hw + p of x (channels-last
+ * fp16, Cin channels at x + m x_pitch, pitch in elements), with column j < C a context feature and column C + d depth
+ * bin d:
+ *   v[j]           = b[j] + sum_k x[m][k] W[j][k]                    fp32 sum on the matrix cores, bias added in fp32
+ *   feat[i][p][c]  = fp16(v[c])                                      c < C; ONE rounding (RNE); dense [n][hw][C]
+ *   depth[i][d][p] = fp16(exp(v[C + d] - mx) / sum_d exp(v[C + d] - mx))    mx = max_d v[C + d]; dense [n][D][hw]
+ * maximum, exponentials (expf), sum and division (one IEEE reciprocal of the sum, one product) in fp32 on the unrounded
+ * logits, ONE rounding.  Neither v nor the logits reach memory.  No workspace, no atomics; a row's result depends on its
+ * own operands only (a NaN in x[m] makes feat[i][p][:] and depth[i][:][p] NaN and nothing else).
+ * w_packed fp16 [nt][Cin / 16][64][8] with nt = ceil((C + D) / 32): the 8 values of lane l of k-step s of tile t are
+ * W[32 t + (l & 31)][16 s + 8 (l >> 5) .. + 7], zeros for a column at or past C + D; bias_packed fp32 [32 nt], zeros
+ * likewise (functions.depth_head.pack_depth_head; columns [features | depth bins | pad]).  The padded columns take part
+ * in neither the maximum nor the sum.
+ * Statuses, in this order, before any device call.  BEVOPS_BAD_PARAM: NULL x / w_packed / bias_packed / depth / feat;
+ * n < 0, hw < 0 or a non-positive Cin / C / D; x_pitch below Cin or no multiple of 8; x / w_packed / bias_packed / feat not
+ * 16-byte aligned (depth: 2 bytes).  BEVOPS_NOT_SUPPORTED: Cin % 32 != 0 or Cin > 512; C % 8 != 0 or C > 128;
+ * C + D > 256; n hw at or above 2^31.  n hw == 0: BEVOPS_SUCCESS without a launch. */
+int bevops_lss_depth_head_f16(const void *x, int x_pitch, const void *w_packed, const void *bias_packed, void *depth,
+                              void *feat, int n, int hw, int Cin, int C, int D, void *stream);
 /* The layers of BEVDepth's DepthNet that are no convolution (csrc/lss_depthnet.hip; LSSViewTransformerBEVDepth,
  * bevformer_tensorrt_amd/bevdepth.py).  None allocates, synchronises or uses atomics; n == 0: BEVOPS_SUCCESS without a
  * launch.
