@@ -139,6 +139,14 @@ FLASHOCC_R50 = dict(BEVDET_R50, grid_config=dict(x=[-40.0, 40.0, 0.4], y=[-40.0,
                                                  depth=[1.0, 60.0, 1.0]),
                     occ_head=dict(Dz=16, num_classes=18, hidden=512))
 FLASHOCC_R50_D88 = dict(FLASHOCC_R50, grid_config=dict(FLASHOCC_R50["grid_config"], depth=[1.0, 45.0, 0.5]))
+# BEVDet-Occ-R50 (BEVDetOCC with LSSViewTransformer(collapse_z=False), CustomResNet3D, LSSFPN3D and a 3-D final_conv: the
+# model FlashOcc is the channel-to-height shortcut of): 16 z cells of 0.4 m, the pooled tensor is the [B, 16, 200, 200, 32]
+# volume, a 3-D BEV encoder on functions.conv3d_taps (bevdet_occ3d.py, design/conv3d.md) and the predicter
+# Linear(32, 64) + Softplus + Linear(64, 18) per voxel.  The reference tree has no BEVDet-Occ code or config: the values
+# are recalled from the BEVDet library's bevdet-occ-r50 config, parity with it is unpinned.
+BEVDET_OCC_R50 = dict(BEVDET_R50, out_channels=32,
+                      grid_config=dict(x=[-40, 40, 0.4], y=[-40, 40, 0.4], z=[-1.0, 5.4, 0.4], depth=[1.0, 45.0, 0.5]),
+                      bev_encoder="3d", occ_head=dict(Dz=16, num_classes=18, hidden=64))
 
 
 class LSSViewTransformer(nn.Module):
@@ -375,13 +383,17 @@ class LSSViewTransformer(nn.Module):
         return self.ops.lss_depth_split(y, n, self.D, self.out_channels, lay["depth_offset"], lay["feat_offset"],
                                         spatial=(h, wd))
 
+    def _pooled_hw(self):
+        """(rows, columns) of the pooled map: the grid's z cells stay rows, z-major (Dz * Dy; Dz = 1: a collapsed grid)."""
+        return int(self.grid_size[2]) * int(self.grid_size[1]), int(self.grid_size[0])
+
     @torch.no_grad()
     def view_transform_calibrated(self, x, calib):
         """`view_transform` with the index build on the device: x as there, calib = the packed fp32 buffer of
         `calibration_matrices` on x's device.  No host synchronisation: capturable with the frame.
         calib [B, N * 24 + 9] (`calibration_matrices_batched`) with x [B * N_cams, ...]: B samples -> [B, C, h, w]."""
         rb, rd, rf, ist, il, counts = self.prepare_calibrated(calib)
-        bev_h, bev_w = int(self.grid_size[1]), int(self.grid_size[0])
+        bev_h, bev_w = self._pooled_hw()
         # (batch is passed only when there is one, so an operator set written for one sample serves a 1-D calib as before)
         kw = dict(batch=calib.shape[0]) if calib.dim() == 2 else {}
         if calib.dim() == 2 and x.shape[0] * 24 != calib.shape[0] * (calib.shape[1] - 9):
@@ -394,7 +406,7 @@ class LSSViewTransformer(nn.Module):
         depth = x[:, : self.D].softmax(dim=1)
         tran_feat = x[:, self.D: self.D + self.out_channels].permute(0, 2, 3, 1)
         depth, tran_feat = depth.contiguous(), tran_feat.contiguous()
-        bev_h, bev_w = int(self.grid_size[1]), int(self.grid_size[0])
+        bev_h, bev_w = self._pooled_hw()
         out = self.ops.bev_pool_v2_indirect(depth, tran_feat, rd, rf, rb, ist, il, counts, bev_h, bev_w, **kw)
         return out.permute(0, 3, 1, 2).contiguous()
 
@@ -405,13 +417,13 @@ class LSSViewTransformer(nn.Module):
         if self._hip_on(x):
             depth, tran_feat = self._depth_feat_hip(x)
             out = self.ops.bev_pool_v2_2(depth, tran_feat, ranks_depth, ranks_feat, ranks_bev, interval_starts,
-                                         interval_lengths, int(self.grid_size[1]), int(self.grid_size[0]))
+                                         interval_lengths, *self._pooled_hw())
             return out.permute(0, 3, 1, 2)
         x = self.depth_net(x)
         depth = x[:, : self.D].softmax(dim=1)
         tran_feat = x[:, self.D: self.D + self.out_channels].permute(0, 2, 3, 1)
         depth, tran_feat = depth.contiguous(), tran_feat.contiguous()
-        bev_h, bev_w = int(self.grid_size[1]), int(self.grid_size[0])
+        bev_h, bev_w = self._pooled_hw()
         out = self.ops.bev_pool_v2_2(depth, tran_feat, ranks_depth, ranks_feat, ranks_bev, interval_starts,
                                      interval_lengths, bev_h, bev_w)
         return out.permute(0, 3, 1, 2).contiguous()
@@ -535,6 +547,20 @@ class BEVDet(nn.Module):
                 raise ValueError("temporal: 1 <= num_adj <= 15")
             if cfg["temporal"].get("pre_process", False):
                 self.pre_process_net = nn.ModuleList([BasicBlock(c, c, 1, False), BasicBlock(c, c, 1, False)])
+        self.occ_cfg = cfg.get("occ_head")
+        self.bev3d = None
+        if cfg.get("bev_encoder", "2d") not in ("2d", "3d"):
+            raise ValueError(f"bev_encoder = {cfg.get('bev_encoder')!r}: '2d' or '3d'")
+        if cfg.get("bev_encoder") == "3d":      # BEVDET_OCC_R50: the 3-D BEV half (bevdet_occ3d.py) instead of all below
+            if self.num_adj:
+                raise NotImplementedError("temporal with bev_encoder='3d' (BEVDet-Occ 4D): not built; design/conv3d.md")
+            if not self.occ_cfg or cfg.get("view_transformer") not in (None, "lss"):
+                raise ValueError("bev_encoder='3d' (BEVDet-Occ): cfg occ_head and the plain 'lss' view transformer")
+            from .bevdet_occ3d import BEVEncoderOcc3D
+            self.bev3d = BEVEncoderOcc3D(c, *(int(self.occ_cfg[k]) for k in ("Dz", "num_classes", "hidden")))
+            self.heads = nn.ModuleDict()
+            self.eval()
+            return
         chans, cin, stages = [2 * c, 4 * c, 8 * c], (self.num_adj + 1) * c, []
         for ch in chans:
             stages.append(nn.ModuleList([BasicBlock(cin, ch, 2, True), BasicBlock(ch, ch, 1, False)]))
@@ -542,7 +568,6 @@ class BEVDet(nn.Module):
         self.bev_stages = nn.ModuleList(stages)
         self.neck_conv = nn.ModuleList([nn.Conv2d(chans[2] + chans[0], 512, 3, 1, 1), nn.Conv2d(512, 512, 3, 1, 1)])
         self.up2_conv = nn.ModuleList([nn.Conv2d(512, 256, 3, 1, 1), nn.Conv2d(256, 256, 1)])
-        self.occ_cfg = cfg.get("occ_head")
         if self.occ_cfg:      # FLASHOCC_R50: the occupancy head INSTEAD of CenterPoint's (BEVOCCHead2D's module names)
             if self.num_adj:
                 raise NotImplementedError("temporal with occ_head (FlashOcc4D): not built; design/flashocc.md")
@@ -605,7 +630,8 @@ class BEVDet(nn.Module):
         return self.bev_half == "hip" and x.is_cuda and x.dtype == torch.float16 \
             and all(hasattr(self.ops, f) for f in ("upsample_bilinear_concat_nhwc", "lss_depth_split", "conv_nhwc",
                                                    "conv3x3_auto", "dense_auto")) \
-            and all(type(c) is nn.Conv2d for h in self.heads.values() for c in h)
+            and all(type(c) is nn.Conv2d for h in self.heads.values() for c in h) \
+            and (self.bev3d is None or hasattr(self.ops, "conv3d_taps"))
 
     def _head_sources(self):
         return [t for k, _ in HEADS_R50 for c in self.heads[k] for t in (c.weight, c.bias) if t is not None]
@@ -647,6 +673,8 @@ class BEVDet(nn.Module):
             self._nhwc_weights()      # (what the first fp16 frame does to the filters; the merged operands follow them)
         self.view.depth_net_merged()
         self._head_operands()
+        if self.bev3d is not None:
+            self.bev3d.prepare()      # (the taps-major weights of the 3-D layers)
         return self
 
     def _bev_half_ready(self, x):
@@ -660,7 +688,8 @@ class BEVDet(nn.Module):
             self._head_operands()
         if not self._hip_on(x):
             return False
-        if self.view.depth_net_merged(build=False) is None or self._head_operands(build=False) is None:
+        if self.view.depth_net_merged(build=False) is None or self._head_operands(build=False) is None \
+                or (self.bev3d is not None and not self.bev3d.prepare(build=False)):
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("BEVDet(bev_half='hip'): the merged operands are missing or stale and the stream is "
                                    "capturing; call prepare_bev_half() (or the model once, eagerly) before the capture")
@@ -669,6 +698,8 @@ class BEVDet(nn.Module):
 
     # ---- the occupancy head (cfg["occ_head"], FLASHOCC_R50; design/flashocc.md)
     def _occ_weights(self):
+        if self.bev3d is not None:      # (one row per voxel: Dz = 1)
+            return self.bev3d.head_weights()
         p = self.predicter
         return p[0].weight, p[0].bias, p[2].weight, p[2].bias, int(self.occ_cfg["Dz"]), int(self.occ_cfg["num_classes"])
 
@@ -684,6 +715,8 @@ class BEVDet(nn.Module):
         kernel by rule, then ONE launch of functions.occ_head_nhwc that writes the permuted bytes itself; everything else:
         the torch statement (functions.occ_head_plain)."""
         w, ops = self._occ_weights(), self.ops
+        if self.bev3d is not None:      # feat: final_conv's volume; the predicter per voxel
+            return self.bev3d.head(feat, ops, self._head_operands() if self._occ_fast(feat) else None)
         if self._occ_fast(feat):
             packed = self._head_operands()         # (cached; `_bev_half_ready` looked at it before the frame's first launch)
             feat = feat.contiguous(memory_format=torch.channels_last)
@@ -712,6 +745,8 @@ class BEVDet(nn.Module):
     def bev_encoder(self, x):
         ops = self.ops
         hip = self._hip_on(x) and x.is_contiguous(memory_format=torch.channels_last)
+        if self.bev3d is not None:
+            return self.bev3d.encode(x, ops, hip)
         if x.is_cuda and x.dtype == torch.float16:
             x = x.contiguous(memory_format=torch.channels_last)
         feats = []

@@ -398,3 +398,26 @@ def occ_head_key_map(model, prefix="occ_head."):
     m = {f"final_conv.{n}": f"{prefix}final_conv.conv.{n}" for n in ("weight", "bias")}
     m.update({f"predicter.{i}.{n}": f"{prefix}predicter.{i}.{n}" for i in (0, 2) for n in ("weight", "bias")})
     return m
+
+
+def occ3d_key_map(model):
+    """`reference_key_map` entries for the 3-D BEV half of a bevdet.BEVDet built with cfg bev_encoder="3d" (BEVDET_OCC_R50),
+    under the names the BEVDet library's BEVDetOCC registers (recalled, the reference tree has no such code:
+    design/conv3d.md): CustomResNet3D `img_bev_encoder_backbone.layers.{s}.{j}.{conv1,conv2,downsample}.{conv,bn}`,
+    LSSFPN3D `img_bev_encoder_neck.conv.{conv,bn}`, `final_conv.conv.*` (no norm layer) and `predicter.{0,2}.*`; every
+    BatchNorm3d folded into the convolution in front of it.  {} for a model without the 3-D half."""
+    bev3d = getattr(model, "bev3d", None)
+    if bev3d is None:
+        return {}
+    m = {}
+    for s, stage in enumerate(bev3d.stages):
+        for j, blk in enumerate(stage):
+            for name in ("conv1", "conv2") + (() if blk.downsample is None else ("downsample",)):
+                ref = f"img_bev_encoder_backbone.layers.{s}.{j}.{name}"
+                m[f"bev3d.stages.{s}.{j}.{name}.weight"] = m[f"bev3d.stages.{s}.{j}.{name}.bias"] = \
+                    _conv_bn(ref + ".conv", ref + ".bn")
+    m["bev3d.fpn_conv.weight"] = m["bev3d.fpn_conv.bias"] = _conv_bn("img_bev_encoder_neck.conv.conv",
+                                                                     "img_bev_encoder_neck.conv.bn")
+    m.update({f"bev3d.final_conv.{n}": f"final_conv.conv.{n}" for n in ("weight", "bias")})
+    m.update({f"bev3d.predicter.{i}.{n}": f"predicter.{i}.{n}" for i in (0, 2) for n in ("weight", "bias")})
+    return m

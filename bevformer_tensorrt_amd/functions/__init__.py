@@ -51,6 +51,7 @@ from .bev_align import (bev_align_transform, bev_align_stack, bev_align_stack_pl
                         pack_bev_align_meta, unpack_bev_align_meta, bev_align_meta_words)
 from .occ_head import pack_occ_head, occ_head_nhwc, occ_head_plain
 from .depth_head import pack_depth_head, lss_depth_head, lss_depth_head_plain
+from .conv3d import conv3d_ndhwc, conv3d_taps, conv3d_taps_weight, conv3d_plain
 from ..utils.register import TRT_FUNCTIONS
 
 TRT_FUNCTIONS.register_module(module=multi_scale_deformable_attn)
@@ -97,4 +98,5 @@ __all__ = [
     "unpack_bev_align_meta", "bev_align_meta_words",
     "pack_occ_head", "occ_head_nhwc", "occ_head_plain",
     "pack_depth_head", "lss_depth_head", "lss_depth_head_plain",
+    "conv3d_ndhwc", "conv3d_taps", "conv3d_taps_weight", "conv3d_plain",
 ]

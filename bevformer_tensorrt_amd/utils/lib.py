@@ -135,6 +135,8 @@ SIGNATURES = {
                               [c_void_p]),
     "bevops_conv_slice_f16_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 11 +
                                  [c_void_p]),
+    "bevops_conv3d_slice_f16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 10 +
+                                [c_void_p]),
     "bevops_dwsep_conv_f16": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_void_p] + [c_int] * 9 + [c_void_p]),
     "bevops_occ_head_blocks": (c_int, [c_int, c_int]),
     "bevops_occ_head_f16": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [ctypes.c_longlong] * 3 + [c_void_p] + [c_int] * 7 +

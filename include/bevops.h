@@ -646,6 +646,28 @@ int bevops_conv_slice_f16(const void *x, int x_pitch, const void *weight_taps, c
 int bevops_conv_slice_f16_ex(const void *x, int x_pitch, const void *weight_taps, const void *bias, const void *residual,
                              int res_pitch, void *out, int out_pitch, int B, int H, int W, int Cin, int Cout, int ksize,
                              int stride, int act, int dilation, int bias_pitch, void *stream);
+/* 3-D convolution on CHANNEL SLICES of channels-last fp16 VOLUMES (csrc/conv3d_slice.hip; the layers of BEVDet-Occ's
+ * CustomResNet3D, LSSFPN3D and final_conv; design/conv3d.md): a tiled implicit GEMM over M = B Zo Yo Xo output voxels,
+ * N = Cout, K = ksize^3 Cin, without a column buffer or a workspace.
+ *   out = act(conv3d(x) + bias[co] + residual)   kernel ksize in {1, 3}, pad ksize / 2, stride in {1, 2}, on all three axes
+ * The identity is added IN FRONT OF the activation (BasicBlock3D: relu(conv2 + identity)).  act: 0 none, 1 ReLU (a NaN
+ * stays a NaN).  fp32 accumulation, taps in the fixed order (kz, ky, kx, 32-channel chunks) for every output; bias,
+ * identity and ReLU in fp32, ONE rounding to fp16.
+ * x, residual and out each point at the first channel of a slice of a wider channels-last volume, addressed as
+ * bevops_conv_slice_f16 addresses its images: element (b, z, y, x, c) lives at base + (((b Z + z) Y + y) X + x) pitch + c,
+ * every pitch in elements, at least the slice's channel count and a multiple of 8.  x and out MAY be disjoint channel
+ * slices of one buffer (every access is a 16-byte vector inside its own slice); out and residual may be the same slice;
+ * x must not overlap out.  weight_taps fp16 [Cout][kz][ky][kx][Cin]; bias fp16 [Cout], optional; residual optional;
+ * out [B, Zo, Yo, Xo] voxels of Cout channels, size per axis (n + 2 pad - ksize) / stride + 1.
+ * Statuses, checked in this order before any device call.  BEVOPS_BAD_PARAM: NULL x / weight_taps / out; non-positive Z,
+ * Y, X, Cin or Cout; B < 0; a pitch below its channel count or no multiple of 8; x, weight_taps, residual, bias or out not
+ * 16-byte aligned.  BEVOPS_NOT_SUPPORTED: Cin % 32 != 0; Cout % 8 != 0; ksize, stride or act outside the lists; x and the
+ * weight are addressed through 32-bit byte offsets: B Z Y X x_pitch 2 or Cout ksize^3 Cin 2 at or above 0xFFFFFF00
+ * bytes; (Y X + X + 1) x_pitch 2 > 0x7FFFFFFF (the displacement of a tap is a signed 32-bit byte count, computed for
+ * taps outside the volume too; such a tap is never addressed, it reads zero).  B == 0: BEVOPS_SUCCESS without a launch. */
+int bevops_conv3d_slice_f16(const void *x, int x_pitch, const void *weight_taps, const void *bias, const void *residual,
+                            int res_pitch, void *out, int out_pitch, int B, int Z, int Y, int X, int Cin, int Cout,
+                            int ksize, int stride, int act, void *stream);
 /* A depthwise-separable layer in ONE launch on channel slices of channels-last fp16 tensors (csrc/dwsep_conv.hip; mmcv's
  * DepthwiseSeparableConvModule with folded BatchNorms, the 3 x 3 layers of a YOLOX built with use_depthwise;
  * design/yolox_depthwise.md).  Addressing as bevops_conv_slice_f16: base pointer of the slice, pitch in elements, every
